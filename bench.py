@@ -18,6 +18,12 @@ reference's own translation units timed beside it).
 `--mode live` measures BASELINE configs[1] instead: VLP-16 sweeps, 200 k-pt LIVE map, one sweep in flight through the
 single-stream entry points (loamx_scanreg_process / loamx_odom_process / loamx_map_process: host clouds in and out, map
 updated and re-voxelised every sweep, sub-map index rebuilt every sweep) — the sequential-SLAM mode.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what its headline figure needs: set-up, W warm-up steps, the
+N timed steps, the result line.  `--full` adds everything else the line used to carry by default: the repeated windows, the
+PCIe-inclusive window, the other single-GPU configurations, the CPU baseline, the pose parity against the oracle and the long
+window.  `--dump-outputs DIR` writes what the timed path returned in its last step (poses, statistics, registered clouds) as
+DIR/<name>.npy.  A stream's sweeps come from a bounded pool (POOL_HALF, sweep_index): a run of any length stages in seconds.
 """
 from __future__ import annotations
 
@@ -40,6 +46,33 @@ MAP_POINTS = 1_000_000
 HBM_PEAK_GBS = 8000.0
 HBM_COPY_GBS = 6290.0      # measured float4 copy on MI355X (MI355X_MICROARCH.md): the ceiling a streaming kernel can reach, quoted beside the 8 TB/s peak
 PROFILE_ROUNDS = ("r06", "r05", "r04")   # committed rocprofv3 summaries of this command, newest first (profiles/<round>_bench_kernel_stats.csv, <round>_pmc_summary.json)
+POOL_HALF = 24             # forward sweeps per stream in the pool (sweep_index): runs of up to 1 + POOL_HALF steps see the trajectory's own sweeps
+DUMP_FULL_RES_BYTES = 40 << 20   # --dump-outputs: registered full-resolution points written in all (a fixed, seeded sample per stream beyond that)
+
+
+def sweep_index(t, half=POOL_HALF):
+    """Step t of a stream -> (k, forward): which sweep of the stream's pool the step registers.  The pool holds the first 1 + half
+    sweeps of the trajectory (k = 0 .. half: pose k -> pose k + 1, the first one at rest) and the same stretch driven in reverse
+    (k = half .. 1: pose k + 1 -> pose k).  A run of more steps shuttles back and forth over it, so the sweeps staged for a run are
+    a bounded set whatever --steps is (ray casting one HDL-64E sweep takes ~0.35 s of a host core), and the motion between any
+    two consecutive steps is one the trajectory itself has."""
+    if t == 0:
+        return 0, True
+    m = (t - 1) % (2 * half)
+    return (1 + m, True) if m < half else (2 * half - m, False)
+
+
+def pool_jobs(T, start, sensor, seed0, half=POOL_HALF, extent=125.0):
+    """{(k, forward): make_sweep_job argument} of every pool sweep steps 0 .. T-1 use (forward sweep k: the trajectory's own seed)"""
+    from loam_velodyne_amd import synth
+    poses = synth.trajectory(half + 1, start=start)
+    jobs = {}
+    for t in range(T):
+        k, fwd = sweep_index(t, half)
+        if (k, fwd) not in jobs:
+            jobs[(k, fwd)] = ((extent, sensor, poses[k], poses[k + 1], seed0 + k) if fwd else
+                              (extent, sensor, poses[k + 1], poses[k], seed0 + 500 + k))
+    return jobs
 
 
 def unbind_worker():
@@ -57,6 +90,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: repeated windows, PCIe-inclusive window, the other single-GPU configurations, "
+                         "CPU baseline, pose parity against the oracle, long window (a plain run does set-up, warm-up, the timed steps and the line only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--map-points", type=int, default=MAP_POINTS)
     ap.add_argument("--map-epoch-steps", type=int, default=0,
@@ -75,11 +113,11 @@ def main():
     ap.add_argument("--handles", type=int, default=HANDLES_PER_GPU,
                     help="pipeline handles per GPU, each on its own HIP stream and host thread, sharing the streams evenly")
     ap.add_argument("--no-pcie", action="store_true", help="skip the second, PCIe-inclusive timed window")
-    ap.add_argument("--repeat", type=int, default=5, help="repeat the timed window this many times (fresh handles, same sweeps): value_median / value_min / value_max; `value` is the first window")
+    ap.add_argument("--repeat", type=int, default=None, help="repeat the timed window this many times (fresh handles, same sweeps): value_median / value_min / value_max; `value` is the first window (default: 5 with --full, else 1)")
     ap.add_argument("--ab-pcie", default=None, help="diagnostic: like --ab, but each variant runs the PCIe-inclusive window")
     ap.add_argument("--ab", default=None, help="diagnostic: ';'-separated environment variants ('A=1 B=2;C=3;' — empty = defaults) timed inside this process before the contract's window, one line each on stderr")
-    ap.add_argument("--long-steps", type=int, default=400,
-                    help="N > 0 (default 400; single rank, with the CPU baseline only): an additional window of N steps over a trajectory of its own, "
+    ap.add_argument("--long-steps", type=int, default=None,
+                    help="N > 0 (default 400 with --full, else 0; single rank, with the CPU baseline only): an additional window of N steps over a trajectory of its own, "
                          "reported as value_long — ~0.2 s of device time, twice (timed, then once more for the iteration counts), so that an external "
                          "sampler (rocm-smi) can see the GPU busy; costs ~60 s of host time for the sweeps; 0 = skip")
     ap.add_argument("--no-live-nodes", action="store_true", help="live mode: skip the additional run with the three entry points as concurrent nodes")
@@ -90,7 +128,15 @@ def main():
     ap.add_argument("--mode", default="batched", choices=["batched", "live"],
                     help="live: sequential SLAM (BASELINE configs[1]: VLP-16, 200 k-pt live map, one sweep in flight, host clouds in / out)")
     args = ap.parse_args()
+    if args.repeat is None:
+        args.repeat = 5 if args.full else 1
+    if args.long_steps is None:
+        args.long_steps = 400 if args.full else 0
+    if not args.full:   # a plain run: the headline figure only (what these blocks measure is --full's)
+        args.no_cpu_baseline = args.no_pcie = args.no_side_configs = args.no_live_nodes = args.no_envelope = True
     if args.mode == "live":
+        if args.dump_outputs:
+            ap.error("--dump-outputs writes the batched path's outputs: not with --mode live")
         return run_live(args)
 
     # the pipeline keeps three HIP streams busy; with torch's and RCCL's streams in the same process the runtime's default of
@@ -175,15 +221,15 @@ def main():
         ldist_merge = loamx.Dist(bytes(uid2.cpu().numpy().tobytes()), rank, world, local_rank)
 
     # ---- this rank's streams and staged sweeps (distinct trajectories per rank and stream)
+    # (every step's sweeps come from the stream's pool, sweep_index: a run of up to 1 + POOL_HALF steps is the trajectory itself)
     sweeps = [[None] * ns for _ in range(T_all)]
     starts = []
     jobs = []
     for s, gs in enumerate(lxdist.stream_ids(rank, world, ns)):
         start = lxdist.stream_start(gs)
-        poses = synth.trajectory(T_all, start=start)
         starts.append(np.array([0, 0, 0, start[0], start[1], start[2]], np.float32))
-        for t in range(T_all):
-            jobs.append((t, s, (125.0, args.sensor, poses[t], poses[t + 1], 1000 * gs + t)))
+        for key, job in pool_jobs(T_all, start, args.sensor, 1000 * gs).items():
+            jobs.append((key, s, job))
     # ray casting is ~0.5 s per HDL-64E sweep on one core and the GPU box is leased by the minute: the (seeded, order-independent)
     # sweeps are generated by worker processes — spawned, not forked: the HIP runtime is already up in this one
     # (32: measured on the pool's 256-thread hosts — 96 workers took four times as long for the long window's 3,296 sweeps as 32 did)
@@ -195,8 +241,13 @@ def main():
             made = list(ex.map(synth.make_sweep_job, [j[2] for j in jobs], chunksize=max(1, len(jobs) // (4 * n_workers))))
     else:
         made = [synth.make_sweep_job(j[2]) for j in jobs]
-    for (t, s, _), (pts, rs) in zip(jobs, made):
-        sweeps[t][s] = (pts, rs)
+    pooled = [{} for _ in range(ns)]
+    for (key, s, _), (pts, rs) in zip(jobs, made):
+        pooled[s][key] = (pts, rs)
+    for t in range(T_all):
+        for s in range(ns):
+            sweeps[t][s] = pooled[s][sweep_index(t)]
+    del pooled
     n_points = len(sweeps[0][0][0])
 
     from concurrent.futures import ThreadPoolExecutor
@@ -589,6 +640,8 @@ def main():
         n_results = len(allp)
     sweeps_total = world * ns * K
     value = sweeps_total / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pipes, per, n_points)
     for p in pipes:   # free the window's HIP streams: beyond 8 streams per process the runtime aliases busy streams onto shared
         p.close()     # hardware queues and they serialise (GPU_MAX_HW_QUEUES above)
     # run-to-run spread: the same window (same sweeps, fresh handles) repeated; `value` stays the first window's
@@ -766,11 +819,43 @@ def main():
         dist.destroy_process_group()
 
 
+def dump_outputs(out_dir, pipes, per, capacity):
+    """What a caller of the timed path receives for the last timed step, every stream of this rank in stream order: the three poses and
+    the statistics of loamx_pipeline_get, the registered full-resolution cloud (loamx_pipeline_download_full_res; a fixed, seeded sample
+    per stream where all of them would exceed DUMP_FULL_RES_BYTES) and the re-projected corner / surf clouds handed to the mapping
+    (loamx_pipeline_download_last_clouds).  Clouds of all streams are concatenated; <name>_counts holds each stream's rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = max(4096, DUMP_FULL_RES_BYTES // (16 * per * len(pipes)))   # 8 HDL-64E streams: every point
+    got = [p.get(k) for p in pipes for k in range(per)]
+    arrays = {
+        "transform": np.stack([g[0] for g in got]),
+        "transform_sum": np.stack([g[1] for g in got]),
+        "transform_aft_mapped": np.stack([g[2] for g in got]),
+        "stats": np.array([list(g[3].values()) for g in got], np.float64),
+    }
+    rng = np.random.default_rng(0)
+    full, last_c, last_s = [], [], []
+    for p in pipes:
+        for k in range(per):
+            f = p.download_full_res(k, capacity)
+            if len(f) > cap:
+                f = f[np.sort(rng.choice(len(f), cap, replace=False))]
+            full.append(f)
+            c, s = p.last_clouds(k, capacity)
+            last_c.append(c)
+            last_s.append(s)
+    for name, parts in (("full_res", full), ("last_corner", last_c), ("last_surf", last_s)):
+        arrays[name] = np.concatenate(parts).astype(np.float32).reshape(-1, 4)
+        arrays[name + "_counts"] = np.array([len(a) for a in parts], np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def run_live(args):
     """`--mode live`: one sequential-SLAM configuration as a line of its own (the default run carries both as blocks)."""
     sensor = "VLP-16" if args.sensor == SENSOR else args.sensor
     M = 200_000 if args.map_points == MAP_POINTS else args.map_points
-    out = live_block(sensor, M, args.steps, args.warmup, cpu=not args.no_cpu_baseline, nodes=not args.no_live_nodes)
+    out = live_block(sensor, M, args.steps, args.warmup, cpu=not args.no_cpu_baseline, nodes=not args.no_live_nodes, host_chain=args.full)
     out["config"]["env_overrides"] = env_overrides()
     from loam_velodyne_amd import loamx
     out["config"]["library_build"] = loamx.build_info()
@@ -789,7 +874,7 @@ def side_live(sensor, M, K, W, cpu=True, nodes=True):
     if os.environ.get("LOAMX_BENCH_LIVE_INPROCESS"):
         return live_block(sensor, M, K, W, cpu=cpu, nodes=nodes)
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--mode", "live", "--sensor", sensor, "--map-points", str(M), "--steps", str(K), "--warmup", str(W)]
+    cmd = [sys.executable, os.path.abspath(__file__), "--mode", "live", "--full", "--sensor", sensor, "--map-points", str(M), "--steps", str(K), "--warmup", str(W)]
     if not cpu:
         cmd.append("--no-cpu-baseline")
     if not nodes:
@@ -805,12 +890,13 @@ def side_live(sensor, M, K, W, cpu=True, nodes=True):
     return blk
 
 
-def live_block(sensor, M, K, W, cpu=True, nodes=True):
+def live_block(sensor, M, K, W, cpu=True, nodes=True, host_chain=True):
     """BASELINE configs[1] / [2]: VLP-16 / 200 k-pt or HDL-32 / 500 k-pt LIVE map, ONE sweep in flight, sequential SLAM
     semantics — every sweep goes through the scan registration, the odometry and the mapping's process() (BasicLaserMapping.cpp:266-599:
     the map is updated and re-voxelised after every sweep, its grid index rebuilt for every sweep), the sweep from (pinned) host memory
     in and the registered cloud out to it, so the PCIe is inside the timed region.  CPU leg: the oracle's live-map process() on the same
-    sweeps and the same initial map.  Returns the block (a bench line of its own under --mode live)."""
+    sweeps and the same initial map.  host_chain: the same sweeps once more with the clouds through host arrays, asserted identical
+    (--full).  Returns the block (a bench line of its own under --mode live)."""
     import torch
     from loam_velodyne_amd import loamx, synth
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -890,9 +976,10 @@ def live_block(sensor, M, K, W, cpu=True, nodes=True):
             h_.close()
         return r
 
-    host = run_chain(False)
+    host = run_chain(False) if host_chain else None
     run = run_chain(True)
-    assert np.array_equal(run["aft"], host["aft"]) and all(np.array_equal(p[2], q[2]) and np.array_equal(p[3], q[3]) and p[4:] == q[4:] for p, q in zip(run["poses"], host["poses"])), \
+    assert host is None or (np.array_equal(run["aft"], host["aft"]) and all(np.array_equal(p[2], q[2]) and np.array_equal(p[3], q[3]) and p[4:] == q[4:]
+                                                                           for p, q in zip(run["poses"], host["poses"]))), \
         "the linked chain and the host-message chain disagree"
     args = types.SimpleNamespace(no_live_nodes=not nodes, no_cpu_baseline=not cpu)
     stage, stats, gn_ms, gn_launches, gn_qi, reg_ms, n_timed = (run[k] for k in ("stage", "stats", "gn_ms", "gn_launches", "gn_qi", "reg_ms", "n_timed"))
@@ -911,12 +998,12 @@ def live_block(sensor, M, K, W, cpu=True, nodes=True):
                    "partition_prepared_ahead": {"adopted": run["speculation"][0], "redone": run["speculation"][1],
                                                 "what": "sweeps (warm-up included) whose map partition + sub-map index had been built behind the previous sweep's "
                                                         "update for the predicted pose and were adopted because the true pose's plan was identical / sweeps that partitioned afresh"},
-                   "host_message_chain": {"sweeps_per_s": round(K / host["elapsed"], 2), "ms_per_step": round(host["elapsed"] / K * 1e3, 4),
-                                          "stage_ms_per_sweep": {"features": round(host["stage"][0] / K * 1e3, 4), "odometry": round(host["stage"][1] / K * 1e3, 4),
-                                                                 "mapping": round(host["stage"][2] / K * 1e3, 4), "harness_between_calls": round(host["other"] / K * 1e3, 4)},
-                                          "what": "the same sweeps with every cloud between the handles through host arrays, as the reference's nodes exchange ROS messages "
-                                                  "(loamx_scanreg_process / loamx_odom_process / get_last_clouds / transform_to_end / loamx_map_process); poses, iteration "
-                                                  "counts and the final map pose are asserted bit-identical to the linked chain's"},
+                   "host_message_chain": ({"sweeps_per_s": round(K / host["elapsed"], 2), "ms_per_step": round(host["elapsed"] / K * 1e3, 4),
+                                           "stage_ms_per_sweep": {"features": round(host["stage"][0] / K * 1e3, 4), "odometry": round(host["stage"][1] / K * 1e3, 4),
+                                                                  "mapping": round(host["stage"][2] / K * 1e3, 4), "harness_between_calls": round(host["other"] / K * 1e3, 4)},
+                                           "what": "the same sweeps with every cloud between the handles through host arrays, as the reference's nodes exchange ROS messages "
+                                                   "(loamx_scanreg_process / loamx_odom_process / get_last_clouds / transform_to_end / loamx_map_process); poses, iteration "
+                                                   "counts and the final map pose are asserted bit-identical to the linked chain's"} if host is not None else None),
                    "mean_map_iterations": round(float(np.mean([s["iterations"] for s in stats])), 2),
                    "mean_submap_points": round(float(np.mean([s["corner_from_map"] + s["surf_from_map"] for s in stats])), 1),
                    "registration_device_ms_per_sweep": round(reg_ms / max(n_timed, 1), 4),

@@ -8,7 +8,7 @@ root=$(pwd); out=$root/gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
 ( timeout 900 python -m pytest tests -m gpu -q --timeout 300 2>&1 | tail -30 ) > $out/gpu_tests.log; tail -2 $out/gpu_tests.log
 ( timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3 ) > $out/smoke.log; tail -1 $out/smoke.log
-timeout 900 python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err; tail -c 400 $out/bench.json; echo
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err; tail -c 400 $out/bench.json; echo
 SKIP_PLAIN_BENCH=1 scripts/gpu_profile.sh ${tag}_prof > /dev/null 2>&1; cp gpurun_out/${tag}_prof/kernel_stats.csv gpurun_out/${tag}_prof/kernels.txt gpurun_out/${tag}_prof/chain.txt gpurun_out/${tag}_prof/chain_by_registration.txt $out/ 2>/dev/null
 scripts/gpu_pmc.sh ${tag}_pmc > $out/pmc.log 2>&1; cp gpurun_out/${tag}_pmc/pmc_summary.json $out/ 2>/dev/null; tail -3 $out/pmc.log
 LOAMX_NO_LOOKAHEAD=1 scripts/gpu_trace_raw.sh ${tag}_seq > /dev/null 2>&1; cp gpurun_out/${tag}_seq/summary.txt $out/sequential_summary.txt 2>/dev/null
@@ -22,7 +22,7 @@ for S in 1 4 16 32; do
   python -c "import json,sys; d=json.loads(open('$out/streams_$S.json').read().strip().splitlines()[-1]); print('streams', $S, d['value'], d['value_median'], d['ms_per_step'])"
 done
 cd /tmp; rm -rf /tmp/prof_copy
-LOAMX_PIPE_TRACE=1 timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d /tmp/prof_copy -- python $root/bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-side-configs --repeat 1 > $out/pcie_traced.json 2> $out/pcie_traced.err
+LOAMX_PIPE_TRACE=1 timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d /tmp/prof_copy -- python $root/bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-side-configs --repeat 1 > $out/pcie_traced.json 2> $out/pcie_traced.err
 mc=$(find /tmp/prof_copy -name '*memory_copy_trace.csv' | head -1)
 python - "$mc" > $out/pcie_copies.txt 2>&1 <<'PY'
 import csv, sys, collections

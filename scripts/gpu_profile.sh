@@ -19,6 +19,6 @@ python $root/scripts/prof_chain.py "$kt" v > $out/chain.txt 2>&1
 python $root/scripts/prof_chain.py "$kt" v k_pose_init > $out/chain_by_registration.txt 2>&1   # (the window between two registrations' first kernels)
 cd $root
 if [ -z "${SKIP_PLAIN_BENCH:-}" ]; then
-  timeout 300 python bench.py --steps 20 --warmup 5 "$@" > $out/bench.json 2> $out/bench.err
+  timeout 300 python bench.py --full --steps 20 --warmup 5 "$@" > $out/bench.json 2> $out/bench.err
   tail -c 3000 $out/bench.json
 fi

@@ -9,7 +9,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 ( timeout 900 python -m pytest tests -m gpu -q -x --timeout 300 2>&1 | tail -40 ) > $out/tests.log
 tail -5 $out/tests.log
-timeout 300 python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
 python - "$out/bench.json" <<'PY'
 import json, sys
 try:
@@ -20,7 +20,7 @@ except Exception as e:
 PY
 for v in "$@"; do
   name=$(echo "$v" | tr '= ' '__')
-  env $v timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-side-configs --no-pcie > $out/bench_$name.json 2> $out/bench_$name.err
+  env $v timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-side-configs --no-pcie > $out/bench_$name.json 2> $out/bench_$name.err
   python - "$out/bench_$name.json" "$v" <<'PY'
 import json, sys
 try:

@@ -207,6 +207,11 @@ class FakePipeline:
         z = np.zeros(6, np.float32)
         return z, z, z, dict(map_iterations=3, mapped=1, odom_iterations=7, odom_sel=100, map_sel=500, corner_ds=100, surf_ds=900, degenerate=0)
 
+    def download_full_res(self, slot, n):
+        assert self.last >= 1 and 0 <= slot < self.ns and not self.closed
+        rng = np.random.default_rng(7 * self.last + slot)
+        return rng.normal(size=(min(n, 300), 4)).astype(np.float32)
+
     def wait_downloads(self):
         pass
 
@@ -256,9 +261,9 @@ class FakeLib:
         return b"abi=6;diag=0;rccl=1;roctx=1"
 
 
-@pytest.mark.parametrize("argv", [["--steps", "3", "--warmup", "1", "--streams", "2", "--sensor", "VLP-16", "--map-points", "2000", "--no-cpu-baseline",
+@pytest.mark.parametrize("argv", [["--full", "--steps", "3", "--warmup", "1", "--streams", "2", "--sensor", "VLP-16", "--map-points", "2000", "--no-cpu-baseline",
                                    "--repeat", "2", "--no-side-configs"],
-                                  ["--steps", "3", "--warmup", "1", "--streams", "2", "--sensor", "VLP-16", "--map-points", "2000", "--no-cpu-baseline",
+                                  ["--full", "--steps", "3", "--warmup", "1", "--streams", "2", "--sensor", "VLP-16", "--map-points", "2000", "--no-cpu-baseline",
                                    "--repeat", "2", "--handles", "2", "--no-side-configs"]])
 def test_bench_main_runs_over_stand_ins(monkeypatch, capsys, argv):
     H = int(argv[argv.index("--handles") + 1]) if "--handles" in argv else 1
@@ -299,6 +304,69 @@ def test_bench_main_runs_over_stand_ins(monkeypatch, capsys, argv):
         assert p.uploaded == 1 + W + K + 6 and p.last == W + K and p.drains == [W, W + K] and p.closed
     for p in streaming:
         assert p.staged == 1 + W + K + 6 and p.last == W + K and p.drains == [W, W + K] and p.downloads == W + K and p.closed
+
+
+def test_plain_run_times_the_steps_only_and_dumps_outputs(monkeypatch, capsys, tmp_path):
+    """a plain run (no --full): ONE resident window of exactly K timed steps and the line — no repeats, no PCIe-inclusive window, no side
+    configurations, no CPU legs — and --dump-outputs writes the last timed step's results, identical for two runs with the same arguments"""
+    from loam_velodyne_amd import loamx
+    monkeypatch.setitem(sys.modules, "torch", fake_torch())
+    monkeypatch.setattr(loamx, "Pipeline", FakePipeline)
+    monkeypatch.setattr(loamx, "lib", lambda: FakeLib(loamx))
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "side_live", lambda *a, **kw: pytest.fail("a plain run measured a side configuration"))
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **kw: pytest.fail("a plain run ran the CPU baseline"))
+    K, W, ns = 3, 1, 2
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--streams", str(ns), "--sensor", "VLP-16",
+                                          "--map-points", "2000", "--dump-outputs", str(d)])
+        FakePipeline.instances.clear()
+        bench.main()
+        out = json.loads([l for l in capsys.readouterr().out.strip().splitlines() if l.startswith("{")][-1])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in out, key
+        assert out["steps"] == K and out["value_repeats"] == 1 and out["pcie_inclusive"] is None
+        assert not {"cpu_baseline", "value_long", "map_2m", "live_vlp16", "live_hdl32", "pose_err_vs_oracle"} & set(out)
+        assert abs(out["value"] * out["ms_per_step"] * 1e-3 - ns) < 0.05 * ns
+        assert len(FakePipeline.instances) == 1 and not FakePipeline.instances[0].staged
+        p = FakePipeline.instances[0]
+        assert p.uploaded == 1 + W + K + 6 and p.last == W + K and p.drains == [W, W + K] and p.closed
+        names = sorted(f.name for f in d.iterdir())
+        assert names == sorted(n + ".npy" for n in ("transform", "transform_sum", "transform_aft_mapped", "stats", "full_res", "full_res_counts",
+                                                    "last_corner", "last_corner_counts", "last_surf", "last_surf_counts"))
+        arrays = {n: np.load(d / n) for n in names}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["transform_aft_mapped.npy"].shape == (ns, 6) and arrays["stats.npy"].shape == (ns, 8)
+        assert arrays["full_res.npy"].shape == (int(arrays["full_res_counts.npy"].sum()), 4)
+        dumps.append(arrays)
+    assert all(np.array_equal(dumps[0][n], dumps[1][n]) for n in dumps[0])
+
+
+def test_sweep_pool_is_the_trajectory_then_shuttles_over_it():
+    """every step's sweep comes from a bounded pool: the first 1 + POOL_HALF steps are the trajectory's own sweeps (pose t -> t + 1, seed
+    t), a longer run drives the same stretch backwards and forwards — consecutive steps always join end pose to start pose"""
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    from loam_velodyne_amd import synth
+    H = 4
+    start = (1.0, 0.0, -3.0)
+    jobs = bench.pool_jobs(200, start, "VLP-16", 5000, half=H)
+    assert len(jobs) == 2 * H + 1
+    poses = synth.trajectory(1 + H + 6, start=start)
+    for t in range(1 + H):
+        assert bench.sweep_index(t, H) == (t, True)
+        _, sensor, p0, p1, seed = jobs[(t, True)]
+        assert np.array_equal(p0, poses[t]) and np.array_equal(p1, poses[t + 1]) and seed == 5000 + t
+    ends = [jobs[bench.sweep_index(t, H)] for t in range(200)]
+    for t in range(1, 199):
+        assert np.array_equal(ends[t][3], ends[t + 1][2]), t
+    assert len({j[4] for j in jobs.values()}) == len(jobs)
 
 
 def test_bench_main_as_rank_0_of_two(monkeypatch, capsys):
@@ -473,8 +541,8 @@ def test_default_line_carries_every_single_gpu_configuration(monkeypatch, capsys
     monkeypatch.setitem(sys.modules, "torch", fake_torch())
     monkeypatch.setattr(loamx, "Pipeline", FakePipeline)
     monkeypatch.setattr(loamx, "lib", lambda: FakeLib(loamx))
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1", "--streams", "2", "--sensor", "VLP-16", "--map-points", "2000", "--map2-points", "4000",
-                                      "--no-cpu-baseline", "--repeat", "1", "--no-pcie"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "3", "--warmup", "1", "--streams", "2", "--sensor", "VLP-16", "--map-points", "2000",
+                                      "--map2-points", "4000", "--no-cpu-baseline", "--repeat", "1", "--no-pcie"])
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         monkeypatch.delenv(k, raising=False)
     FakePipeline.instances.clear()
