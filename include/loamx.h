@@ -133,6 +133,49 @@ int loamx_scanreg_process_raw(loamx_scanreg* h, const loamx_multiscan_mapper* ma
                               uint32_t stride, loamx_cloud* full, uint32_t* ring_size, loamx_cloud* sharp, loamx_cloud* less_sharp,
                               loamx_cloud* flat, loamx_cloud* less_flat);
 
+/* Sensor model: raw-sweep ingestion for any lidar.  It generalises loamx_multiscan_mapper: it says where the ring of a record
+ * comes from (linear bounds as the mapper, a table of laser elevations, or a ring field of the record) and where its time within
+ * the sweep comes from (the azimuth, as the reference computes it, or a time field of the record).  Records keep x, y, z float32 at
+ * byte offsets 0 / 4 / 8; field offsets are byte offsets inside a record of `stride` bytes (a PointCloud2 field list).
+ * A record is kept when its x, y, z are finite and not near zero (MultiScanRegistration.cpp:187-196), its ring is valid, and — in
+ * time-field mode — its time is finite.  Then:
+ *   RING_FROM_BOUNDS   ring = getRingForAngle of the vertical angle, as loamx_scanreg_process_raw computes it, bit for bit.
+ *   RING_FROM_TABLE    with angle and deg = (double)(angle * 180) / PI taken as for BOUNDS: ring = the k that minimises
+ *                      |deg - ring_angles_deg[k]| in double (a tie goes to the smaller k); dropped when that minimum is above
+ *                      max_angle_error_deg.  The table has n_scan_rings finite entries, strictly increasing (ring 0 = lowest).
+ *   RING_FROM_FIELD    ring = the unsigned integer at ring_offset (U8 / U16 / U32); dropped when >= n_scan_rings.
+ *   TIME_FROM_AZIMUTH  relTime as loamx_scanreg_process_raw computes it, halfPassed included, over the records kept by THIS model
+ *                      in record order; startOri / endOri from records 0 and count - 1 (MultiScanRegistration.cpp:165-173).  It
+ *                      assumes firing order.
+ *   TIME_FROM_FIELD    t_i = the field at time_offset (U32 / F32 / F64) as a double; t_ref = the smallest t_i of the kept records;
+ *                      relTime = (float)((t_i - t_ref) * time_scale), clamped to scan_period when above it.  No azimuth is used,
+ *                      so any record order works: RING-MAJOR CLOUDS (Ouster) REQUIRE THIS MODE.
+ * The kept records are split by ring in record order (stable), intensity = (float)ring + relTime, and IMU de-skew uses that relTime
+ * (the IMU index is the running maximum over the kept records in record order), as for loamx_scanreg_process_raw. */
+enum { LOAMX_RING_FROM_BOUNDS = 0, LOAMX_RING_FROM_TABLE = 1, LOAMX_RING_FROM_FIELD = 2 };
+enum { LOAMX_TIME_FROM_AZIMUTH = 0, LOAMX_TIME_FROM_FIELD = 1 };
+enum { LOAMX_FIELD_U8 = 1, LOAMX_FIELD_U16 = 2, LOAMX_FIELD_U32 = 3, LOAMX_FIELD_F32 = 4, LOAMX_FIELD_F64 = 5 };
+typedef struct loamx_sensor_model {
+  uint32_t n_scan_rings;                  /* 1..256 (BOUNDS: >= 2, as loamx_scanreg_process_raw) */
+  uint32_t ring_source, time_source;      /* LOAMX_RING_FROM_*, LOAMX_TIME_FROM_* */
+  float lower_bound_deg, upper_bound_deg; /* BOUNDS: exactly loamx_multiscan_mapper (upper > lower) */
+  const float* ring_angles_deg;           /* TABLE: n_scan_rings entries, strictly increasing; read during the call only */
+  float max_angle_error_deg;              /* TABLE: > 0; a record farther than this from every entry is dropped */
+  uint32_t ring_offset, ring_type;        /* FIELD ring: byte offset in the record, LOAMX_FIELD_U8 / U16 / U32 */
+  uint32_t time_offset, time_type;        /* FIELD time: byte offset in the record, LOAMX_FIELD_U32 / F32 / F64 */
+  double time_scale;                      /* FIELD time: seconds per unit of the field (1 for seconds, 1e-9 for nanoseconds) */
+} loamx_sensor_model;
+/* BOUNDS + AZIMUTH model of a mapper (zeroes the other fields); host only */
+int loamx_sensor_model_from_mapper(const loamx_multiscan_mapper* m, loamx_sensor_model* out);
+/* LOAMX_OK, or LOAMX_E_INVALID with a message: unknown source or type; table NULL, not strictly increasing or not finite;
+ * max_angle_error_deg <= 0; a field that does not fit inside `stride` or is not naturally aligned; time_scale <= 0 or not finite;
+ * a ring count out of range; a stride below 12 or not a multiple of 4.  Host only: needs no device. */
+int loamx_sensor_model_check(const loamx_sensor_model* m, uint32_t stride);
+/* loamx_scanreg_process_raw with a sensor model: same outputs (ring_size has m->n_scan_rings entries), IMU handling and errors */
+int loamx_scanreg_process_sensor(loamx_scanreg* h, const loamx_sensor_model* m, const void* records, uint32_t count, uint32_t stride,
+                                 loamx_cloud* full, uint32_t* ring_size, loamx_cloud* sharp, loamx_cloud* less_sharp,
+                                 loamx_cloud* flat, loamx_cloud* less_flat);
+
 /* IMU data for the scan registration: updateIMUData (BasicScanRegistration.cpp:82-98) feeds the
  * handle's IMU history (capacity max(200, imu_history_size): the reference's buffer is created with 200 entries and
  * ensureCapacity only grows it, include/loam_velodyne/CircularBuffer.h); loamx_scanreg_set_time gives the scanTime of the
@@ -401,6 +444,9 @@ int loamx_pipeline_stage_step(loamx_pipeline* h, uint32_t step, const loamx_clou
  * that had arrived when it was staged, before its full-resolution cloud is registered. */
 int loamx_pipeline_stage_step_raw(loamx_pipeline* h, uint32_t step, const void* const* raw_xyz, const uint32_t* counts, uint32_t stride,
                                   const loamx_multiscan_mapper* mapper, const double* scan_time_sec);
+/* loamx_pipeline_stage_step_raw with a sensor model (loamx_sensor_model above): records[s] = counts[s] records of `stride` bytes */
+int loamx_pipeline_stage_step_sensor(loamx_pipeline* h, uint32_t step, const void* const* records, const uint32_t* counts,
+                                     uint32_t stride, const loamx_sensor_model* m, const double* scan_time_sec);
 int loamx_pipeline_update_imu(loamx_pipeline* h, uint32_t stream, double stamp_sec, float roll, float pitch, float yaw, const float acc_xyz[3]);
 /* Asynchronous output: after enable (before the first step), download_step_async — called after loamx_pipeline_step(t) —
  * starts copying the registered full-resolution clouds of step t (out[k] = k-th stream that was registered; packed float4

@@ -126,6 +126,41 @@ int loamx_scanreg_process_raw(loamx_scanreg* h, const loamx_multiscan_mapper* ma
   });
 }
 
+int loamx_sensor_model_from_mapper(const loamx_multiscan_mapper* m, loamx_sensor_model* out) {
+  return guard([&]() {
+    LX_REQUIRE(m && out, "NULL argument");
+    memset(out, 0, sizeof(*out));
+    out->n_scan_rings = m->n_scan_rings;
+    out->ring_source = LOAMX_RING_FROM_BOUNDS;
+    out->time_source = LOAMX_TIME_FROM_AZIMUTH;
+    out->lower_bound_deg = m->lower_bound_deg;
+    out->upper_bound_deg = m->upper_bound_deg;
+    out->time_scale = 1.0;
+    return LOAMX_OK;
+  });
+}
+
+int loamx_sensor_model_check(const loamx_sensor_model* m, uint32_t stride) {
+  return guard([&]() {
+    LX_REQUIRE(m, "NULL argument");
+    sensor_model_check(*m, stride);
+    return LOAMX_OK;
+  });
+}
+
+int loamx_scanreg_process_sensor(loamx_scanreg* h, const loamx_sensor_model* m, const void* records, uint32_t count, uint32_t stride,
+                                 loamx_cloud* full, uint32_t* ring_size, loamx_cloud* sharp, loamx_cloud* less_sharp, loamx_cloud* flat,
+                                 loamx_cloud* less_flat) {
+  return guard([&]() {
+    LX_REQUIRE(h && m, "NULL argument");
+    h->fx.upload_sensor(records, count, stride, *m);   // (checks the model first)
+    h->fx.run_async();
+    int rc = h->fx.download_cloud(0, full, ring_size);
+    const int rc2 = h->fx.download(0, sharp, less_sharp, flat, less_flat);
+    return rc != LOAMX_OK ? rc : rc2;
+  });
+}
+
 // updateIMUData(acc, newState) — BasicScanRegistration.cpp:82-98; acc = local acceleration with gravity removed and axes
 // remapped as ScanRegistration::handleIMUMessage does (src/lib/ScanRegistration.cpp:164-184)
 int loamx_scanreg_update_imu(loamx_scanreg* h, double stamp_sec, float roll, float pitch, float yaw, const float acc_xyz[3]) {

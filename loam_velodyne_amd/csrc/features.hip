@@ -925,9 +925,45 @@ void FeatureExtractor::upload_raw(const void* raw_xyz, uint32_t count, uint32_t 
   M.lower = lower_deg; M.upper = upper_deg; M.n_rings = n_scan_rings;
   M.factor = (float)((int)n_scan_rings - 1) / (upper_deg - lower_deg);   // (nScanRings - 1) / (upperBound - lowerBound), :41-50
   binner_.init(st_);
-  // IMU de-skew (projectPointToStartOfSweep, :231): the state the PREVIOUS reset() left behind — the reference projects the
-  // points of a sweep before processScanlines resets the state with this sweep's scan time
   ImuTable I;
+  const uint32_t H = stage_imu_table_(I);
+  binner_.run(raw_.p, count, M, params.scan_period, cloud_.p, raw_ring_cnt_.p, H ? &I : nullptr, H ? imu_last_.p : nullptr);
+  finish_raw_(n_scan_rings, H);
+}
+
+// The same with a sensor model (include/loamx.h, loamx_sensor_model): the record bytes go up as they are and are unpacked on the
+// device (sensor_unpack), as the pipeline's stage_step_raw does with its payloads.
+void FeatureExtractor::upload_sensor(const void* records, uint32_t count, uint32_t stride, const loamx_sensor_model& model) {
+  LX_REQUIRE(records || count == 0, "NULL raw cloud");
+  sensor_model_check(model, stride);
+  check_params_();
+  LX_HIP(hipSetDevice(device_));
+  const size_t bytes = (size_t)count * stride;
+  const bool direct = host_pinned(records, bytes);   // (a pinned payload goes up by DMA straight from the caller's memory)
+  if (!direct && count) {
+    h_bytes_.reserve(bytes);
+    memcpy(h_bytes_.p, records, bytes);
+  }
+  bytes_.reserve(bytes + 16);
+  raw_.reserve(count + 1);
+  cloud_.reserve(count + 1);
+  raw_ring_cnt_.reserve(RawBinner::MAX_RINGS);
+  h_raw_ring_cnt_.reserve(RawBinner::MAX_RINGS);
+  SensorParams sp = sensor_params(model);
+  if (sp.ring_src == RING_FIELD) { ring_fld_.reserve(count + 1); sp.ring_fld = ring_fld_.p; }
+  if (sp.time_src == TIME_FIELD) { time_fld_.reserve(count + 1); sp.time_fld = time_fld_.p; }
+  if (count) LX_HIP(hipMemcpyAsync(bytes_.p, direct ? records : (const void*)h_bytes_.p, bytes, hipMemcpyHostToDevice, st_));
+  sensor_unpack(bytes_.p, stride, count, sp, raw_.p, ring_fld_.p, time_fld_.p, st_);
+  binner_.init(st_);
+  ImuTable I;
+  const uint32_t H = stage_imu_table_(I);
+  binner_.run(raw_.p, count, sp, params.scan_period, cloud_.p, raw_ring_cnt_.p, H ? &I : nullptr, H ? imu_last_.p : nullptr);
+  finish_raw_(model.n_scan_rings, H);
+}
+
+// IMU de-skew (projectPointToStartOfSweep, :231): the state the PREVIOUS reset() left behind — the reference projects the
+// points of a sweep before processScanlines resets the state with this sweep's scan time.  Returns the history length (0: none).
+uint32_t FeatureExtractor::stage_imu_table_(ImuTable& I) {
   const uint32_t H = imu_.size();
   if (H) {
     h_imu_d_.reserve(2 * (size_t)H);
@@ -944,7 +980,11 @@ void FeatureExtractor::upload_raw(const void* raw_xyz, uint32_t count, uint32_t 
     I.dstamp = imu_dt_.p + H;
     I.state = imu_state_.p;
   }
-  binner_.run(raw_.p, count, M, params.scan_period, cloud_.p, raw_ring_cnt_.p, H ? &I : nullptr, H ? imu_last_.p : nullptr);
+  return H;
+}
+
+// the ring sizes (and the IMU state the projection loop left behind) come back; processScanlines' reset and the per-ring layout
+void FeatureExtractor::finish_raw_(uint32_t n_scan_rings, uint32_t H) {
   LX_HIP(hipMemcpyAsync(h_raw_ring_cnt_.p, raw_ring_cnt_.p, sizeof(uint32_t) * n_scan_rings, hipMemcpyDeviceToHost, st_));
   if (H) LX_HIP(hipMemcpyAsync(h_imu_last_.p, imu_last_.p, sizeof(ImuLast), hipMemcpyDeviceToHost, st_));
   LX_HIP(hipStreamSynchronize(st_));

@@ -75,6 +75,8 @@ class FeatureExtractor {
   // one raw revolution in sensor axes / firing order (MultiScanRegistration::process): binned into rings on the device and,
   // with IMU data, de-skewed point by point (projectPointToStartOfSweep)
   void upload_raw(const void* raw_xyz, uint32_t count, uint32_t stride, float lower_deg, float upper_deg, uint32_t n_scan_rings);
+  // the same with a sensor model (loamx_sensor_model: ring and relTime from the model's sources); the records are unpacked on the device
+  void upload_sensor(const void* records, uint32_t count, uint32_t stride, const loamx_sensor_model& model);
   // ---- IMU state machine of BasicScanRegistration (src/lib/BasicScanRegistration.cpp:55-152, :258-281); times in seconds
   void update_imu_data(double stamp, float roll, float pitch, float yaw, const float acc[3]) { imu_.history_size = imu_history_size; imu_.update(stamp, roll, pitch, yaw, acc); }
   void set_scan_time(double t) { imu_.set_scan_time(t); }   // the scanTime argument of the next process call
@@ -129,8 +131,14 @@ class FeatureExtractor {
   void layout_(uint32_t nsw, const uint32_t* const* ring_size, const uint32_t* n_rings);
   void allocate_(hipStream_t table_stream = nullptr);
   PinBuf<uint32_t> h_tab_;
+  uint32_t stage_imu_table_(ImuTable& I);
+  void finish_raw_(uint32_t n_scan_rings, uint32_t H);
   RawBinner binner_;
   DevBuf<float4> raw_;
+  DevBuf<char> bytes_;                 // upload_sensor: the records as they came, their ring / time fields
+  PinBuf<char> h_bytes_;
+  DevBuf<uint32_t> ring_fld_;
+  DevBuf<double> time_fld_;
   DevBuf<uint32_t> raw_ring_cnt_;
   PinBuf<uint32_t> h_raw_ring_cnt_;
   int device_;

@@ -289,6 +289,168 @@ __global__ __launch_bounds__(256) void k_raw_scatter(const float4* __restrict__ 
   out[pos] = make_float4(x, y, z, (float)id + relTime);                                  // :229
 }
 
+
+// ---- sensor models (include/loamx.h, loamx_sensor_model).  The mapper path above stays as it is; these kernels serve every other
+// combination of ring and time source.  With TIME_FROM_AZIMUTH only the classification differs (k_sns_classify), and the rest of
+// the mapper path's kernels run as they are: they read nothing but the ring ids and the sweep's first-pass / last-kept indices.
+
+// :184-196 (the first half of classify): remapped point; false = rejected (NaN / zero return)
+__device__ inline bool remap_keep(const float4 r, float& x, float& y, float& z) {
+  x = r.y; y = r.z; z = r.x;
+  if (!isfinite(x) || !isfinite(y) || !isfinite(z)) return false;
+  return (double)(x * x + y * y + z * z) >= 0.0001;
+}
+
+// RING_FROM_TABLE: the entry of the sorted table `tab` (LDS) nearest to the vertical angle, in double, ties to the smaller index; -1 when
+// it is farther than max_err.  deg is taken exactly as classify() takes it.
+__device__ inline int ring_from_table(float x, float y, float z, const float* tab, uint32_t nr, float max_err) {
+  const float angle = atan_f(y / sqrtf(x * x + z * z));
+  const double deg = (double)(angle * 180) / PI_D;
+  uint32_t lo = 0, hi = nr;   // first k with tab[k] >= deg: the nearest entry is k or k - 1
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if ((double)tab[mid] < deg) lo = mid + 1; else hi = mid;
+  }
+  uint32_t k = lo < nr ? lo : nr - 1;
+  double best = fabs(deg - (double)tab[k]);
+  // (rounded distances grow weakly away from deg on either side: a tie with a smaller index can only lie further left)
+  while (k > 0 && fabs(deg - (double)tab[k - 1]) <= best) { k--; best = fabs(deg - (double)tab[k]); }
+  return best > (double)max_err ? -1 : (int)k;
+}
+
+// TIME_FROM_FIELD: t_i of every record (sensor_unpack), the sweep's t_ref (k_sns_colscan), seconds per unit
+struct TimeField {
+  const double* t;
+  const double* tref;
+  double scale;
+};
+__device__ inline float rel_time_field(const TimeField& tf, uint32_t i, float scan_period) {
+  const float rt = (float)((tf.t[i] - *tf.tref) * tf.scale);
+  return rt > scan_period ? scan_period : rt;
+}
+// smallest double of a workgroup of 256 (every thread passes one value; w: 4 doubles of LDS), valid in thread 0
+__device__ inline double block_min_256(double t, double* w) {
+  for (int d = 32; d >= 1; d >>= 1) t = fmin(t, __shfl_xor(t, d, 64));
+  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = t;
+  __syncthreads();
+  return fmin(fmin(w[0], w[1]), fmin(w[2], w[3]));
+}
+
+// k_raw_classify for a sensor model: the ring from the model's source; with TIME_FROM_AZIMUTH the first-pass index over the points
+// this model keeps, with TIME_FROM_FIELD the smallest time of the workgroup's kept points instead (k_sns_colscan reduces it to t_ref)
+template <int RS, int TS>
+__global__ __launch_bounds__(256) void k_sns_classify(const float4* __restrict__ raw, uint32_t n, SensorParams sp, int* __restrict__ ring_of,
+                                                      uint32_t* __restrict__ blk_cnt, const uint32_t* __restrict__ jstar,
+                                                      uint32_t* __restrict__ blk_first_pass, uint32_t* __restrict__ blk_last_kept,
+                                                      double* __restrict__ blk_tmin) {
+  __shared__ uint32_t hist[RawBinner::MAX_RINGS];
+  __shared__ float tab[RawBinner::MAX_RINGS];
+  __shared__ uint32_t s_first, s_last;
+  __shared__ double w_tmin[4];
+  const uint32_t nr = sp.M.n_rings;
+  if (threadIdx.x == 0) { s_first = 0xffffffffu; s_last = 0u; }
+  for (uint32_t r = threadIdx.x; r < nr; r += blockDim.x) {
+    hist[r] = 0;
+    if (RS == RING_TABLE) tab[r] = sp.table[r];
+  }
+  __syncthreads();
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool kept = false, passes = false;
+  double t = HUGE_VAL;
+  if (i < n) {
+    float x, y, z;
+    int id;
+    if (RS == RING_BOUNDS) id = classify(raw[i], sp.M, x, y, z);
+    else if (!remap_keep(raw[i], x, y, z)) id = -1;
+    else if (RS == RING_TABLE) id = ring_from_table(x, y, z, tab, nr, sp.max_err);
+    else id = sp.ring_fld[i] < nr ? (int)sp.ring_fld[i] : -1;
+    if (TS == TIME_FIELD && id >= 0) {
+      t = sp.time_fld[i];
+      if (!isfinite(t)) { id = -1; t = HUGE_VAL; }
+    }
+    ring_of[i] = id;
+    if (id >= 0) {
+      kept = true;
+      atomicAdd(&hist[id], 1u);
+      if (TS == TIME_AZIMUTH) (void)ori_first_half(x, z, __uint_as_float(jstar[2]), passes);
+    }
+  }
+  const unsigned long long mp = __ballot(passes), mk = __ballot(kept);
+  const int lane = threadIdx.x & 63;
+  if (mp && lane == __builtin_ctzll(mp)) atomicMin(&s_first, i);
+  if (mk && lane == 63 - __builtin_clzll(mk)) atomicMax(&s_last, i + 1u);
+  const double tmin = TS == TIME_FIELD ? block_min_256(t, w_tmin) : 0.0;   // (its barrier also orders the LDS atomics above)
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    blk_first_pass[blockIdx.x] = s_first;
+    blk_last_kept[blockIdx.x] = s_last;
+    if (TS == TIME_FIELD) blk_tmin[blockIdx.x] = tmin;
+  }
+  for (uint32_t r = threadIdx.x; r < nr; r += blockDim.x) blk_cnt[(size_t)blockIdx.x * nr + r] = hist[r];
+}
+
+// TIME_FROM_FIELD: t_ref = the smallest time of the kept points, over the per-workgroup minima (one workgroup; k_raw_colscan reduces
+// the indices the same way)
+__global__ __launch_bounds__(256) void k_sns_tref(const double* __restrict__ blk_tmin, uint32_t nblk, double* __restrict__ tref) {
+  __shared__ double w[4];
+  double t = HUGE_VAL;
+  for (uint32_t b = threadIdx.x; b < nblk; b += 256) t = fmin(t, blk_tmin[b]);
+  t = block_min_256(t, w);
+  if (threadIdx.x == 0) *tref = t;
+}
+
+// k_raw_imu_need with the relTime of the time field
+__global__ __launch_bounds__(256) void k_sns_imu_need(uint32_t n, float scan_period, const int* __restrict__ ring_of, ImuTable I,
+                                                      uint32_t* __restrict__ first, TimeField tf) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = i < n && ring_of[i] >= 0;
+  const uint32_t v = active ? imu_need(I, rel_time_field(tf, i, scan_period)) : 0u;
+  const int lane = threadIdx.x & 63;
+  const uint32_t pv = __shfl_up(v, 1, 64);
+  const unsigned long long act = __ballot(active);
+  const bool head = active && (lane == 0 || pv != v || !((act >> (lane > 0 ? lane - 1 : 0)) & 1ull));
+  if (head && v > I.idx0) atomicMin(&first[v], i);
+}
+
+// k_raw_scatter with the relTime of the time field
+__global__ __launch_bounds__(256) void k_sns_scatter(const float4* __restrict__ raw, uint32_t n, uint32_t nr, float scan_period,
+                                                     const int* __restrict__ ring_of, const uint32_t* __restrict__ blk_pre,
+                                                     const uint32_t* __restrict__ ring_cnt, const uint32_t* __restrict__ jstar,
+                                                     float4* __restrict__ out, ImuTable I, const uint32_t* __restrict__ imu_first,
+                                                     ImuLast* __restrict__ d_last, TimeField tf) {
+  __shared__ uint32_t ring_off[RawBinner::MAX_RINGS];
+  __shared__ uint32_t wcnt[4][RawBinner::MAX_RINGS];
+  if (threadIdx.x == 0) {
+    uint32_t acc = 0;
+    for (uint32_t r = 0; r < nr; r++) { ring_off[r] = acc; acc += ring_cnt[r]; }
+  }
+  for (uint32_t e = threadIdx.x; e < 4 * RawBinner::MAX_RINGS; e += blockDim.x) (&wcnt[0][0])[e] = 0;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int id = i < n ? ring_of[i] : -1;
+  uint32_t rank = 0;   // stable rank among the same-ring points of this wave
+  unsigned long long todo = __ballot(id >= 0);
+  while (todo) {
+    const int src = __builtin_ctzll(todo);
+    const int r0 = __shfl(id, src, 64);
+    const unsigned long long m = __ballot(id == r0);
+    if (id == r0) {
+      rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      if (lane == src) wcnt[wid][r0] = (uint32_t)__popcll(m);
+    }
+    todo &= ~m;
+  }
+  __syncthreads();
+  if (id < 0) return;
+  for (int w = 0; w < wid; w++) rank += wcnt[w][id];
+  const uint32_t pos = ring_off[id] + blk_pre[(size_t)blockIdx.x * nr + id] + rank;
+  const float4 r = raw[i];
+  float x = r.y, y = r.z, z = r.x;
+  const float relTime = rel_time_field(tf, i, scan_period);
+  if (I.H) imu_project(I, imu_first, i, relTime, x, y, z, i == jstar[1] ? d_last : nullptr);
+  out[pos] = make_float4(x, y, z, (float)id + relTime);
+}
 }  // namespace
 
 // raw records (x, y, z float32 at byte offsets 0 / 4 / 8, `stride` bytes apart) -> float4 (x, y, z, 0): the payload crosses PCIe as
@@ -301,6 +463,96 @@ __global__ __launch_bounds__(256) void k_raw_unpack(const char* __restrict__ byt
 }
 void raw_unpack(const void* d_bytes, uint32_t stride, uint32_t n, float4* d_out, hipStream_t st) {
   if (n) hipLaunchKernelGGL(k_raw_unpack, dim3((n + 255) / 256), dim3(256), 0, st, (const char*)d_bytes, stride, n, d_out);
+}
+
+// sensor records: as k_raw_unpack, plus the ring field (-> uint32) and the time field (-> double) where the model reads them.  Fields are
+// read as aligned dwords (stride % 4 == 0, natural alignment inside the record): u8 / u16 are shifted out, an f64 is two dwords.
+__device__ inline uint32_t rec_dword(const char* rec, uint32_t off) { return *(const uint32_t*)(rec + (off & ~3u)); }
+__global__ __launch_bounds__(256) void k_sensor_unpack(const char* __restrict__ bytes, uint32_t stride, uint32_t n, uint32_t ring_off,
+                                                       uint32_t ring_type, uint32_t time_off, uint32_t time_type, float4* __restrict__ out,
+                                                       uint32_t* __restrict__ ring, double* __restrict__ time) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const char* rec = bytes + (size_t)i * stride;
+  const float* r = (const float*)rec;
+  out[i] = make_float4(r[0], r[1], r[2], 0.f);
+  if (ring) {
+    const uint32_t w = rec_dword(rec, ring_off);
+    ring[i] = ring_type == LOAMX_FIELD_U8 ? (w >> (8 * (ring_off & 3u))) & 0xffu
+            : ring_type == LOAMX_FIELD_U16 ? (w >> (8 * (ring_off & 2u))) & 0xffffu : w;
+  }
+  if (time) {
+    const uint32_t w = rec_dword(rec, time_off);
+    time[i] = time_type == LOAMX_FIELD_U32 ? (double)w
+            : time_type == LOAMX_FIELD_F32 ? (double)__uint_as_float(w)
+            : __hiloint2double((int)rec_dword(rec, time_off + 4), (int)w);   // (little endian: the low word first)
+  }
+}
+void sensor_unpack(const void* d_bytes, uint32_t stride, uint32_t n, const SensorParams& sp, float4* d_out, uint32_t* d_ring, double* d_time,
+                   hipStream_t st) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_sensor_unpack, dim3((n + 255) / 256), dim3(256), 0, st, (const char*)d_bytes, stride, n, sp.ring_off, sp.ring_type,
+                     sp.time_off, sp.time_type, d_out, sp.ring_src == RING_FIELD ? d_ring : nullptr, sp.time_src == TIME_FIELD ? d_time : nullptr);
+}
+
+static uint32_t field_size(uint32_t type) {
+  switch (type) {
+    case LOAMX_FIELD_U8: return 1;
+    case LOAMX_FIELD_U16: return 2;
+    case LOAMX_FIELD_U32: case LOAMX_FIELD_F32: return 4;
+    case LOAMX_FIELD_F64: return 8;
+    default: return 0;
+  }
+}
+static void check_field(uint32_t off, uint32_t type, uint32_t stride, const char* what) {
+  const uint32_t sz = field_size(type);
+  if (off % sz) throw Error(LOAMX_E_INVALID, std::string(what) + " field is not naturally aligned in the record");
+  if ((uint64_t)off + sz > stride) throw Error(LOAMX_E_INVALID, std::string(what) + " field does not fit inside the record stride");
+}
+
+void sensor_model_check(const loamx_sensor_model& m, uint32_t stride) {
+  LX_REQUIRE(stride >= 12 && stride % 4 == 0, "raw stride must be a multiple of 4 and at least 12");
+  LX_REQUIRE(m.ring_source <= LOAMX_RING_FROM_FIELD, "unknown ring source");
+  LX_REQUIRE(m.time_source <= LOAMX_TIME_FROM_FIELD, "unknown time source");
+  LX_REQUIRE(m.n_scan_rings >= 1 && m.n_scan_rings <= RawBinner::MAX_RINGS, "n_scan_rings must be in [1, 256]");
+  if (m.ring_source == LOAMX_RING_FROM_BOUNDS) {   // as loamx_scanreg_process_raw (MultiScanRegistration.cpp:107-127)
+    LX_REQUIRE(m.upper_bound_deg > m.lower_bound_deg, "invalid vertical range (upper <= lower)");
+    LX_REQUIRE(m.n_scan_rings >= 2, "invalid number of scan rings (n < 2)");
+  } else if (m.ring_source == LOAMX_RING_FROM_TABLE) {
+    LX_REQUIRE(m.ring_angles_deg, "ring angle table is NULL");
+    for (uint32_t k = 0; k < m.n_scan_rings; k++) {
+      LX_REQUIRE(std::isfinite(m.ring_angles_deg[k]), "ring angle table holds a value that is not finite");
+      LX_REQUIRE(k == 0 || m.ring_angles_deg[k] > m.ring_angles_deg[k - 1], "ring angle table is not strictly increasing");
+    }
+    LX_REQUIRE(m.max_angle_error_deg > 0, "max_angle_error_deg must be > 0");
+  } else {
+    LX_REQUIRE(m.ring_type == LOAMX_FIELD_U8 || m.ring_type == LOAMX_FIELD_U16 || m.ring_type == LOAMX_FIELD_U32,
+               "unknown ring field type (U8, U16 or U32)");
+    check_field(m.ring_offset, m.ring_type, stride, "ring");
+  }
+  if (m.time_source == LOAMX_TIME_FROM_FIELD) {
+    LX_REQUIRE(m.time_type == LOAMX_FIELD_U32 || m.time_type == LOAMX_FIELD_F32 || m.time_type == LOAMX_FIELD_F64,
+               "unknown time field type (U32, F32 or F64)");
+    check_field(m.time_offset, m.time_type, stride, "time");
+    LX_REQUIRE(std::isfinite(m.time_scale) && m.time_scale > 0, "time_scale must be finite and > 0");
+  }
+}
+
+SensorParams sensor_params(const loamx_sensor_model& m) {
+  SensorParams sp;
+  sp.M.n_rings = m.n_scan_rings;
+  sp.M.lower = m.lower_bound_deg;
+  sp.M.upper = m.upper_bound_deg;
+  sp.M.factor = m.ring_source == LOAMX_RING_FROM_BOUNDS ? (float)((int)m.n_scan_rings - 1) / (m.upper_bound_deg - m.lower_bound_deg) : 0.f;
+  sp.ring_src = (int)m.ring_source;
+  sp.time_src = (int)m.time_source;
+  for (uint32_t k = 0; k < RawBinner::MAX_RINGS; k++)
+    sp.table[k] = m.ring_source == LOAMX_RING_FROM_TABLE && k < m.n_scan_rings ? m.ring_angles_deg[k] : 0.f;
+  sp.max_err = m.max_angle_error_deg;
+  sp.ring_off = m.ring_offset; sp.ring_type = m.ring_type;
+  sp.time_off = m.time_offset; sp.time_type = m.time_type;
+  sp.time_scale = m.time_scale;
+  return sp;
 }
 
 void RawBinner::run(const float4* d_raw, uint32_t n, const MapperParams& m, float scan_period, float4* d_out, uint32_t* d_ring_cnt,
@@ -330,6 +582,56 @@ void RawBinner::run(const float4* d_raw, uint32_t n, const MapperParams& m, floa
   }
   hipLaunchKernelGGL(k_raw_scatter, dim3(nb), dim3(256), 0, st_, d_raw, n, m, scan_period, ring_of_.p, blk_pre_.p, d_ring_cnt, scratch_.p,
                      d_out, I, imu_first_.p, d_last);
+  LX_HIP(hipGetLastError());
+}
+
+void RawBinner::run(const float4* d_raw, uint32_t n, const SensorParams& sp, float scan_period, float4* d_out, uint32_t* d_ring_cnt,
+                    const ImuTable* imu, ImuLast* d_last) {
+  if (sp.ring_src == RING_BOUNDS && sp.time_src == TIME_AZIMUTH) return run(d_raw, n, sp.M, scan_period, d_out, d_ring_cnt, imu, d_last);
+  const MapperParams& m = sp.M;
+  LX_REQUIRE(m.n_rings >= 1 && m.n_rings <= MAX_RINGS, "n_scan_rings must be in [1, 256]");
+  if (n == 0) {
+    LX_HIP(hipMemsetAsync(d_ring_cnt, 0, sizeof(uint32_t) * m.n_rings, st_));
+    return;
+  }
+  const bool tfield = sp.time_src == TIME_FIELD;
+  const uint32_t nb = (n + 255) / 256;
+  ring_of_.reserve(n + 1);
+  blk_cnt_.reserve((size_t)nb * m.n_rings + 1);
+  blk_pre_.reserve((size_t)nb * m.n_rings + 1);
+  scratch_.reserve(8);
+  blk_tmin_.reserve((size_t)nb + 1);
+  tref_.reserve(1);
+  ImuTable I;
+  if (imu) I = *imu;
+  LX_REQUIRE(I.H <= 4096, "IMU history longer than 4096 states");
+  imu_first_.reserve(I.H + 1);
+  const TimeField tf{sp.time_fld, tref_.p, sp.time_scale};
+  hipLaunchKernelGGL(k_raw_init, dim3((I.H + 256) / 256), dim3(256), 0, st_, d_raw, n, scratch_.p, imu_first_.p, I.H);
+  blk_idx_.reserve(2 * (size_t)nb + 2);
+#define LX_SNS_CLASSIFY(RS, TS) \
+  hipLaunchKernelGGL((k_sns_classify<RS, TS>), dim3(nb), dim3(256), 0, st_, d_raw, n, sp, ring_of_.p, blk_cnt_.p, scratch_.p, blk_idx_.p, blk_idx_.p + nb, blk_tmin_.p)
+  if (sp.ring_src == RING_BOUNDS) LX_SNS_CLASSIFY(RING_BOUNDS, TIME_FIELD);   // (BOUNDS + AZIMUTH took the mapper path above)
+  else if (sp.ring_src == RING_TABLE && tfield) LX_SNS_CLASSIFY(RING_TABLE, TIME_FIELD);
+  else if (sp.ring_src == RING_TABLE) LX_SNS_CLASSIFY(RING_TABLE, TIME_AZIMUTH);
+  else if (tfield) LX_SNS_CLASSIFY(RING_FIELD, TIME_FIELD);
+  else LX_SNS_CLASSIFY(RING_FIELD, TIME_AZIMUTH);
+#undef LX_SNS_CLASSIFY
+  // (with TIME_AZIMUTH the rest is the mapper path's kernels: they only read the ring ids classify left behind)
+  if (tfield) hipLaunchKernelGGL(k_sns_tref, dim3(1), dim3(256), 0, st_, blk_tmin_.p, nb, tref_.p);
+  hipLaunchKernelGGL(k_raw_colscan, dim3(m.n_rings), dim3(256), 0, st_, blk_cnt_.p, nb, m.n_rings, blk_pre_.p, d_ring_cnt, blk_idx_.p,
+                     blk_idx_.p + nb, scratch_.p);
+  if (I.H) {
+    if (tfield) hipLaunchKernelGGL(k_sns_imu_need, dim3(nb), dim3(256), 0, st_, n, scan_period, ring_of_.p, I, imu_first_.p, tf);
+    else hipLaunchKernelGGL(k_raw_imu_need, dim3(nb), dim3(256), 0, st_, d_raw, n, scan_period, ring_of_.p, scratch_.p, I, imu_first_.p);
+    hipLaunchKernelGGL(k_raw_imu_suffix, dim3(1), dim3(1024), 0, st_, imu_first_.p, I.H);
+  }
+  if (tfield)
+    hipLaunchKernelGGL(k_sns_scatter, dim3(nb), dim3(256), 0, st_, d_raw, n, m.n_rings, scan_period, ring_of_.p, blk_pre_.p, d_ring_cnt, scratch_.p,
+                       d_out, I, imu_first_.p, d_last, tf);
+  else
+    hipLaunchKernelGGL(k_raw_scatter, dim3(nb), dim3(256), 0, st_, d_raw, n, m, scan_period, ring_of_.p, blk_pre_.p, d_ring_cnt, scratch_.p,
+                       d_out, I, imu_first_.p, d_last);
   LX_HIP(hipGetLastError());
 }
 

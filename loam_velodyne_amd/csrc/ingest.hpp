@@ -32,6 +32,26 @@ struct ImuLast {
 // device-side re-striding of a raw payload (x, y, z at 0 / 4 / 8 of every `stride` bytes) into float4 records
 void raw_unpack(const void* d_bytes, uint32_t stride, uint32_t n, float4* d_out, hipStream_t st);
 
+// Sensor model (loamx_sensor_model, include/loamx.h) as the kernels see it: where a record's ring and relTime come from
+enum RingSrc : int { RING_BOUNDS = 0, RING_TABLE = 1, RING_FIELD = 2 };
+enum TimeSrc : int { TIME_AZIMUTH = 0, TIME_FIELD = 1 };
+struct SensorParams {
+  MapperParams M;                        // n_rings always; lower / upper / factor for RING_BOUNDS
+  int ring_src = RING_BOUNDS, time_src = TIME_AZIMUTH;
+  float table[256];                      // RING_TABLE: n_rings elevations (degrees, strictly increasing)
+  float max_err = 0;                     // RING_TABLE: max_angle_error_deg
+  uint32_t ring_off = 0, ring_type = 0, time_off = 0, time_type = 0;   // field offsets in the record, LOAMX_FIELD_*
+  double time_scale = 1;                 // TIME_FIELD: seconds per unit
+  const uint32_t* ring_fld = nullptr;    // [n] device: the ring field of every record (RING_FIELD; filled by sensor_unpack)
+  const double* time_fld = nullptr;      // [n] device: the time field of every record (TIME_FIELD; filled by sensor_unpack)
+};
+// validated model (loamx_sensor_model_check) -> SensorParams without the device arrays; throws LOAMX_E_INVALID
+void sensor_model_check(const loamx_sensor_model& m, uint32_t stride);
+SensorParams sensor_params(const loamx_sensor_model& m);
+// records -> float4 (x, y, z, 0) and, where the model reads them, the ring field (d_ring) and the time field as a double (d_time)
+void sensor_unpack(const void* d_bytes, uint32_t stride, uint32_t n, const SensorParams& sp, float4* d_out, uint32_t* d_ring, double* d_time,
+                   hipStream_t st);
+
 class RawBinner {
  public:
   static constexpr uint32_t MAX_RINGS = 256;
@@ -40,11 +60,15 @@ class RawBinner {
   // frame, rings concatenated, intensity = ring + relTime.  d_ring_cnt[n_rings]: points per ring.  Asynchronous.
   void run(const float4* d_raw, uint32_t n, const MapperParams& m, float scan_period, float4* d_out, uint32_t* d_ring_cnt,
            const ImuTable* imu = nullptr, ImuLast* d_last = nullptr);
+  // the same with a sensor model (sp.ring_fld / sp.time_fld: this sweep's unpacked fields); BOUNDS + AZIMUTH runs the path above
+  void run(const float4* d_raw, uint32_t n, const SensorParams& sp, float scan_period, float4* d_out, uint32_t* d_ring_cnt,
+           const ImuTable* imu = nullptr, ImuLast* d_last = nullptr);
 
  private:
   hipStream_t st_ = nullptr;
   DevBuf<int> ring_of_;
   DevBuf<uint32_t> blk_cnt_, blk_pre_, scratch_, imu_first_, blk_idx_;
+  DevBuf<double> blk_tmin_, tref_;
 };
 
 }  // namespace loamx

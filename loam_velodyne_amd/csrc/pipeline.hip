@@ -136,6 +136,8 @@ class Pipeline {
     std::vector<uint32_t> count, off;            // raw points per stream, their offsets in the slot's arrays
     DevBuf<char> d_bytes;
     DevBuf<float4> d_raw4, d_binned;
+    DevBuf<uint32_t> d_ring_fld;                 // stage_step_sensor: the records' ring / time fields (as the model reads them)
+    DevBuf<double> d_time_fld;
     DevBuf<uint32_t> d_ring_cnt;                 // [stream][n_rings]
     PinBuf<uint32_t> h_ring_cnt;
     DevBuf<ImuLast> d_last;
@@ -496,13 +498,28 @@ class Pipeline {
     LX_REQUIRE(stride >= 12 && stride % 4 == 0, "raw stride must be a multiple of 4 and at least 12");
     LX_REQUIRE(mapper.n_scan_rings >= 1 && mapper.n_scan_rings <= RawBinner::MAX_RINGS, "n_scan_rings must be in [1, 256]");
     LX_REQUIRE(mapper.upper_bound_deg != mapper.lower_bound_deg, "vertical bounds must differ");
+    SensorParams sp;
+    sp.M.lower = mapper.lower_bound_deg; sp.M.upper = mapper.upper_bound_deg; sp.M.n_rings = mapper.n_scan_rings;
+    sp.M.factor = (float)((int)mapper.n_scan_rings - 1) / (mapper.upper_bound_deg - mapper.lower_bound_deg);   // MultiScanRegistration.cpp:41-50
+    stage_records_(t, raw_xyz, counts, stride, sp, scan_time);
+  }
+  // the same with a sensor model (loamx_sensor_model): ring and relTime from the model's sources, the records unpacked on the device
+  void stage_step_sensor(uint32_t t, const void* const* records, const uint32_t* counts, uint32_t stride, const loamx_sensor_model& model,
+                         const double* scan_time) {
+    LX_REQUIRE(records && counts, "invalid argument");
+    sensor_model_check(model, stride);
+    stage_records_(t, records, counts, stride, sensor_params(model), scan_time);
+  }
+  void stage_records_(uint32_t t, const void* const* raw_xyz, const uint32_t* counts, uint32_t stride, const SensorParams& model,
+                      const double* scan_time) {
     LX_HIP(hipSetDevice(device));
     ensure_streaming_(t);
     LX_REQUIRE(t == staged_hi.load(), "steps must be staged in order");
     LX_REQUIRE(t < RING || last_step.load() + (long)RING >= (long)t, "stage_step_raw(t) needs step(t - 8) to have run: only eight steps can be in flight");
     TraceRange trace_range("loamx:pipeline:stage_step_raw");
     if (t > 0) finalize_raw(t - 1);   // the IMU state machine advances sweep by sweep: this step's table needs the previous reset
-    const uint32_t ns = n_streams_, nr = mapper.n_scan_rings;
+    const uint32_t ns = n_streams_, nr = model.M.n_rings;
+    const bool mapper_path = model.ring_src == RING_BOUNDS && model.time_src == TIME_AZIMUTH;
     RawSlot& R = rawslot[t % RING];
     R.raw = true;
     R.finalized = false;
@@ -517,6 +534,8 @@ class Pipeline {
     R.d_bytes.reserve((size_t)ntot * stride + 16);
     R.d_raw4.reserve((size_t)ntot + 1);
     R.d_binned.reserve((size_t)ntot + 1);
+    if (model.ring_src == RING_FIELD) R.d_ring_fld.reserve((size_t)ntot + 1);
+    if (model.time_src == TIME_FIELD) R.d_time_fld.reserve((size_t)ntot + 1);
     R.d_ring_cnt.reserve((size_t)ns * nr + 1);
     R.h_ring_cnt.reserve((size_t)ns * nr + 1);
     R.d_last.reserve(ns);
@@ -535,9 +554,6 @@ class Pipeline {
     if (Htot) {
       R.h_imu_d.reserve(2 * Htot); R.h_imu_f.reserve(9 * Htot); R.d_imu_d.reserve(2 * Htot); R.d_imu_f.reserve(9 * Htot);
     }
-    MapperParams M;
-    M.lower = mapper.lower_bound_deg; M.upper = mapper.upper_bound_deg; M.n_rings = nr;
-    M.factor = (float)((int)nr - 1) / (mapper.upper_bound_deg - mapper.lower_bound_deg);   // MultiScanRegistration.cpp:41-50
     binner.init(cstream);
     LX_HIP(hipMemsetAsync(R.d_last.p, 0, sizeof(ImuLast) * ns, cstream));
     size_t hbase = 0;
@@ -560,9 +576,20 @@ class Pipeline {
     for (uint32_t s = 0; s < ns; s++) {
       const uint32_t n = counts[s];
       if (n) LX_HIP(hipMemcpyAsync(R.d_bytes.p + (size_t)R.off[s] * stride, raw_xyz[s], (size_t)n * stride, hipMemcpyHostToDevice, cstream));
-      raw_unpack(R.d_bytes.p + (size_t)R.off[s] * stride, stride, n, R.d_raw4.p + R.off[s], cstream);
-      binner.run(R.d_raw4.p + R.off[s], n, M, fcfg.scan_period, R.d_binned.p + R.off[s], R.d_ring_cnt.p + (size_t)s * nr,
-                 R.imu_H[s] ? &tables[s] : nullptr, R.imu_H[s] ? R.d_last.p + s : nullptr);
+      if (mapper_path) {
+        raw_unpack(R.d_bytes.p + (size_t)R.off[s] * stride, stride, n, R.d_raw4.p + R.off[s], cstream);
+        binner.run(R.d_raw4.p + R.off[s], n, model.M, fcfg.scan_period, R.d_binned.p + R.off[s], R.d_ring_cnt.p + (size_t)s * nr,
+                   R.imu_H[s] ? &tables[s] : nullptr, R.imu_H[s] ? R.d_last.p + s : nullptr);
+      } else {
+        uint32_t* d_ring = model.ring_src == RING_FIELD ? R.d_ring_fld.p + R.off[s] : nullptr;
+        double* d_time = model.time_src == TIME_FIELD ? R.d_time_fld.p + R.off[s] : nullptr;
+        SensorParams sp = model;
+        sp.ring_fld = d_ring;
+        sp.time_fld = d_time;
+        sensor_unpack(R.d_bytes.p + (size_t)R.off[s] * stride, stride, n, sp, R.d_raw4.p + R.off[s], d_ring, d_time, cstream);
+        binner.run(R.d_raw4.p + R.off[s], n, sp, fcfg.scan_period, R.d_binned.p + R.off[s], R.d_ring_cnt.p + (size_t)s * nr,
+                   R.imu_H[s] ? &tables[s] : nullptr, R.imu_H[s] ? R.d_last.p + s : nullptr);
+      }
     }
     LX_HIP(hipMemcpyAsync(R.h_ring_cnt.p, R.d_ring_cnt.p, sizeof(uint32_t) * ns * nr, hipMemcpyDeviceToHost, cstream));
     LX_HIP(hipMemcpyAsync(R.h_last.p, R.d_last.p, sizeof(ImuLast) * ns, hipMemcpyDeviceToHost, cstream));
@@ -1043,6 +1070,14 @@ int loamx_pipeline_stage_step_raw(loamx_pipeline* h, uint32_t step, const void* 
   return guard([&]() {
     LX_REQUIRE(h && mapper, "NULL argument");
     h->p.stage_step_raw(step, raw_xyz, counts, stride, *mapper, scan_time_sec);
+    return LOAMX_OK;
+  });
+}
+int loamx_pipeline_stage_step_sensor(loamx_pipeline* h, uint32_t step, const void* const* records, const uint32_t* counts, uint32_t stride,
+                                     const loamx_sensor_model* m, const double* scan_time_sec) {
+  return guard([&]() {
+    LX_REQUIRE(h && m, "NULL argument");
+    h->p.stage_step_sensor(step, records, counts, stride, *m, scan_time_sec);
     return LOAMX_OK;
   });
 }

@@ -311,6 +311,89 @@ class MultiScanMapper(C.Structure):
     _fields_ = [("lower_bound_deg", C.c_float), ("upper_bound_deg", C.c_float), ("n_scan_rings", C.c_uint32)]
 
 
+RING_FROM_BOUNDS, RING_FROM_TABLE, RING_FROM_FIELD = 0, 1, 2
+TIME_FROM_AZIMUTH, TIME_FROM_FIELD = 0, 1
+FIELD_U8, FIELD_U16, FIELD_U32, FIELD_F32, FIELD_F64 = 1, 2, 3, 4, 5
+_FIELD_TYPES = {"u1": FIELD_U8, "u2": FIELD_U16, "u4": FIELD_U32, "f4": FIELD_F32, "f8": FIELD_F64}
+
+
+class SensorModel(C.Structure):
+    """loamx_sensor_model (include/loamx.h): where a raw record's ring and its time within the sweep come from."""
+    _fields_ = [("n_scan_rings", C.c_uint32), ("ring_source", C.c_uint32), ("time_source", C.c_uint32),
+                ("lower_bound_deg", C.c_float), ("upper_bound_deg", C.c_float), ("ring_angles_deg", C.c_void_p),
+                ("max_angle_error_deg", C.c_float), ("ring_offset", C.c_uint32), ("ring_type", C.c_uint32),
+                ("time_offset", C.c_uint32), ("time_type", C.c_uint32), ("time_scale", C.c_double)]
+
+    @classmethod
+    def from_mapper(cls, sensor="VLP-16", mapper=None):
+        """BOUNDS + AZIMUTH: a preset by name, or mapper = (lower_deg, upper_deg, n_rings)"""
+        out = cls()
+        _check(lib().loamx_sensor_model_from_mapper(C.byref(_mapper(sensor, mapper)), C.byref(out)))
+        return out
+
+    def set_table(self, angles_deg, max_error_deg):
+        """RING_FROM_TABLE: laser elevations in degrees, strictly increasing (ring 0 = lowest); kept referenced by the model"""
+        self._table = np.ascontiguousarray(angles_deg, np.float32)
+        self.ring_source = RING_FROM_TABLE
+        self.n_scan_rings = len(self._table)
+        self.ring_angles_deg = self._table.ctypes.data if len(self._table) else None
+        self.max_angle_error_deg = float(max_error_deg)
+        return self
+
+    @classmethod
+    def from_dtype(cls, dtype, ring="ring", time=None, time_scale=1.0, n_rings=None, table=None, max_error_deg=None, mapper=None):
+        """Fill the model from a numpy structured dtype (a PointCloud2 field list: name -> offset, type).  ring: the name of the
+        ring field (FIELD), or None for table= (TABLE, with max_error_deg) or mapper= (BOUNDS: a preset name or (lower, upper,
+        n)).  time: the name of the time field (FIELD, time_scale = seconds per unit), or None (AZIMUTH: firing order only)."""
+        dtype = np.dtype(dtype)
+        if ring is not None:
+            m = cls()
+            off, kind = _field(dtype, ring, (FIELD_U8, FIELD_U16, FIELD_U32))
+            assert n_rings is not None, "a ring field needs n_rings"
+            m.ring_source, m.ring_offset, m.ring_type, m.n_scan_rings = RING_FROM_FIELD, off, kind, int(n_rings)
+        elif table is not None:
+            m = cls().set_table(table, max_error_deg)
+        else:
+            m = cls.from_mapper(mapper) if isinstance(mapper, str) else cls.from_mapper(mapper=mapper)
+        m.time_scale = float(time_scale)
+        if time is not None:
+            m.time_offset, m.time_type = _field(dtype, time, (FIELD_U32, FIELD_F32, FIELD_F64))
+            m.time_source = TIME_FROM_FIELD
+        return m
+
+    def check(self, stride):
+        """loamx_sensor_model_check: raises LoamxError for an invalid model (no device needed)"""
+        _check(lib().loamx_sensor_model_check(C.byref(self), int(stride)))
+
+
+def _field(dtype, name, kinds):
+    ft, off = dtype.fields[name][:2]
+    kind = _FIELD_TYPES.get(f"{ft.kind}{ft.itemsize}") if ft.byteorder != ">" else None
+    assert kind in kinds, f"field {name!r} has type {ft}, the model reads {kinds}"
+    return off, kind
+
+
+def _mapper(sensor, mapper):
+    m = MultiScanMapper()
+    if mapper is None:
+        _check(lib().loamx_multiscan_mapper_preset(sensor.encode(), C.byref(m)))
+    else:
+        m.lower_bound_deg, m.upper_bound_deg, m.n_scan_rings = float(mapper[0]), float(mapper[1]), int(mapper[2])
+    return m
+
+
+def as_records(records):
+    """(bytes as uint8 array, count, stride) of a structured record array (itemsize = stride) or an (n, 3) float32 array"""
+    a = np.asarray(records)
+    if a.dtype.fields is None:
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+    else:
+        a = np.ascontiguousarray(a).reshape(-1)
+        names = list(a.dtype.fields)
+        assert a.dtype.fields[names[0]][1] == 0 and all(a.dtype.fields[k][0] == np.float32 for k in names[:3]), "x, y, z float32 at 0 / 4 / 8"
+    return a, len(a), a.dtype.itemsize * (3 if a.dtype.fields is None else 1)
+
+
 class ScanRegistration:
     """loamx_scanreg_*: BasicScanRegistration::processScanlines / extractFeatures on the GPU."""
     NAMES = ("sharp", "less_sharp", "flat", "less_flat")
@@ -396,6 +479,21 @@ class ScanRegistration:
         res = {name: outs[k][:cl[k].count].copy() for k, name in enumerate(self.NAMES)}
         res["full"] = outs[4][:cl[4].count].copy()
         res["ring_sizes"] = rs.astype(np.int32)
+        return res
+
+    def process_sensor(self, records, model: SensorModel):
+        """loamx_scanreg_process_sensor: process_raw with a sensor model.  records: a structured array (itemsize = stride, x, y, z
+        float32 first) or an (n, 3) float32 array.  Same results as process_raw."""
+        a, n, stride = as_records(records)
+        outs = [np.zeros((max(n, 1), 4), np.float32) for _ in range(5)]
+        cl = [cloud_of(o) for o in outs]
+        rs = np.zeros(max(int(model.n_scan_rings), 1), np.uint32)
+        _check(lib().loamx_scanreg_process_sensor(self.h, C.byref(model), a.ctypes.data_as(C.c_void_p) if n else None, n, stride,
+                                                  C.byref(cl[4]), rs.ctypes.data_as(C.c_void_p), C.byref(cl[0]), C.byref(cl[1]),
+                                                  C.byref(cl[2]), C.byref(cl[3])))
+        res = {name: outs[k][:cl[k].count].copy() for k, name in enumerate(self.NAMES)}
+        res["full"] = outs[4][:cl[4].count].copy()
+        res["ring_sizes"] = rs[:model.n_scan_rings].astype(np.int32)
         return res
 
 
@@ -698,6 +796,22 @@ class Pipeline:
         if not hasattr(self, "_staged"):
             self._staged = {}
         self._staged[t % 8] = (arrs, PP, CN, st)
+
+    def stage_step_sensor(self, t: int, records_list, model: SensorModel, scan_times=None):
+        """stage_step_raw with a sensor model: records_list[s] = structured records (one dtype for every stream) or (n, 3) float32"""
+        ns = self.n_streams
+        assert len(records_list) == ns
+        recs = [as_records(r) for r in records_list]
+        strides = {r[2] for r in recs if r[1]}
+        assert len(strides) <= 1, "every stream's records must have the same stride"
+        stride = strides.pop() if strides else recs[0][2]
+        PP = (C.c_void_p * ns)(*[r[0].ctypes.data if r[1] else None for r in recs])
+        CN = (C.c_uint32 * ns)(*[r[1] for r in recs])
+        st = (C.c_double * ns)(*[float(x) for x in scan_times]) if scan_times is not None else None
+        _check(lib().loamx_pipeline_stage_step_sensor(self.h, t, PP, CN, stride, C.byref(model), st))
+        if not hasattr(self, "_staged"):
+            self._staged = {}
+        self._staged[t % 8] = (recs, PP, CN, st, model)
 
     def update_imu(self, stream: int, stamp, roll, pitch, yaw, acc):
         a = np.ascontiguousarray(acc, np.float32)

@@ -168,17 +168,20 @@ class Sweep:
 
 
 def make_sweep(world: World, sensor: str, pose_start, pose_end, noise: float = 0.01, seed: int = 0,
-               scan_period: float = 0.1, az_steps: int | None = None) -> Sweep:
+               scan_period: float = 0.1, az_steps: int | None = None, elevations_deg=None) -> Sweep:
     """One sweep captured while the sensor moves linearly (in the 6 pose parameters) from pose_start to pose_end.
     Every point is expressed in the sensor frame at ITS OWN firing time (raw, motion-distorted), as a real driver
-    delivers it; intensity = ring + scan_period * sweep fraction."""
+    delivers it; intensity = ring + scan_period * sweep fraction.  elevations_deg: the lasers' elevations (ring 0 first) of a
+    sensor whose lasers are not evenly spaced, instead of the preset's even spacing (the preset still gives the azimuth steps)."""
     R, A, lo, hi = SENSORS[sensor]
+    if elevations_deg is not None:
+        R = len(elevations_deg)
     if az_steps:
         A = az_steps
     rng = np.random.default_rng(20240601 + seed)
     pose_start = np.asarray(pose_start, np.float64)
     pose_end = np.asarray(pose_end, np.float64)
-    elev = np.deg2rad(np.linspace(lo, hi, R))
+    elev = np.deg2rad(np.linspace(lo, hi, R) if elevations_deg is None else np.asarray(elevations_deg, np.float64))
     frac = np.arange(A) / A
     ori = -np.pi + 2 * np.pi * frac                     # ori = -atan2(x, z), increasing with time
     # sensor-frame unit directions (R, A, 3)
@@ -227,6 +230,49 @@ def to_raw(sweep: Sweep, bad_every: int = 0) -> np.ndarray:
             raw[a, 1 % R] = 0.0
             raw[a, 2 % R] = (0.1, 0.1, 50.0)
     return raw.reshape(-1, 3).astype(np.float32)
+
+
+# driver record layouts of to_records (numpy structured dtypes = PointCloud2 field lists)
+RECORD_LAYOUTS = {
+    # velodyne_pointcloud PointXYZIRT: ring u16, time f32 seconds since the sweep's stamp; firing order
+    "velodyne": np.dtype({"names": ["x", "y", "z", "intensity", "ring", "time"], "formats": ["f4", "f4", "f4", "f4", "u2", "f4"],
+                          "offsets": [0, 4, 8, 16, 20, 24], "itemsize": 32}),
+    # ouster_ros point: t u32 nanoseconds, ring u16; delivered ring by ring (ring-major)
+    "ouster": np.dtype({"names": ["x", "y", "z", "intensity", "t", "reflectivity", "ring", "ambient", "range"],
+                        "formats": ["f4", "f4", "f4", "f4", "u4", "u2", "u2", "u2", "u4"],
+                        "offsets": [0, 4, 8, 16, 20, 24, 26, 28, 32], "itemsize": 48}),
+    # Hesai-style: absolute timestamp f64 seconds, ring u16; firing order
+    "hesai": np.dtype({"names": ["x", "y", "z", "intensity", "timestamp", "ring"], "formats": ["f4", "f4", "f4", "f4", "f8", "u2"],
+                       "offsets": [0, 4, 8, 12, 16, 24], "itemsize": 32}),
+}
+
+
+def to_records(sweep: Sweep, layout: str = "velodyne", bad_every: int = 0, scan_period: float = 0.1, t0: float = 1.7e9,
+               ring_major: bool | None = None) -> np.ndarray:
+    """The sweep as a driver with per-point ring and time fields delivers it (RECORD_LAYOUTS): x, y, z as to_raw, ring = the laser
+    index, time = the true firing time (scan_period * azimuth step / steps; "hesai": t0 + that, absolute).  "ouster" is ring-major
+    unless ring_major=False, the others are in firing order unless ring_major=True.  bad_every plants to_raw's bad returns; the
+    out-of-field one carries an out-of-range ring."""
+    R = len(sweep.ring_sizes)
+    A = int(sweep.ring_sizes[0])
+    raw = to_raw(sweep, bad_every=bad_every).reshape(A, R, 3)
+    ring = np.broadcast_to(np.arange(R, dtype=np.int64)[None, :], (A, R)).copy()
+    if bad_every:
+        ring[bad_every // 2:A - 1:bad_every, 2 % R] = R
+    rel = np.broadcast_to((scan_period * np.arange(A) / A)[:, None], (A, R))
+    rec = np.zeros((A, R), RECORD_LAYOUTS[layout])
+    rec["x"], rec["y"], rec["z"] = raw[..., 0], raw[..., 1], raw[..., 2]
+    rec["intensity"] = 100.0
+    rec["ring"] = ring
+    if layout == "velodyne":
+        rec["time"] = rel
+    elif layout == "ouster":
+        rec["t"] = np.round(rel * 1e9)
+    else:
+        rec["timestamp"] = t0 + rel
+    if ring_major if ring_major is not None else layout == "ouster":
+        rec = rec.T
+    return np.ascontiguousarray(rec).reshape(-1)
 
 
 def trajectory(n_sweeps: int, step: float = 1.0, yaw_step_deg: float = 0.5, start=(0.0, 0.0, 0.0), n_static: int = 1):

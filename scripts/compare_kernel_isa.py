@@ -1,0 +1,52 @@
+"""Compare the gfx950 instruction streams of the kernels two builds of one object file hold (e.g. ingest.o of two commits):
+python scripts/compare_kernel_isa.py OLD.o NEW.o [name-substring ...]
+
+Each object's device code is unbundled (clang-offload-bundler) and disassembled (llvm-objdump); per kernel present in OLD the
+instructions are compared with branch-target labels and the trailing alignment padding stripped.  Exit status 1 when a kernel differs."""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+LLVM = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
+TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
+
+
+def kernels(obj, tmp):
+    fat, co = os.path.join(tmp, os.path.basename(obj) + ".fat"), os.path.join(tmp, os.path.basename(obj) + ".gfx950")
+    subprocess.run(["objcopy", "--dump-section", ".hip_fatbin=" + fat, obj], check=True)
+    subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat, "--targets=" + TARGET,
+                    "--output=" + co], check=True)
+    dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], check=True, capture_output=True, text=True).stdout
+    out, cur = {}, None
+    for line in dis.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+        elif cur is not None and line.strip():
+            cur.append(re.sub(r"<[^>]*>", "", line.split("//")[0]).strip())
+    for ins in out.values():   # (the padding up to the next kernel depends on what follows)
+        while ins and ins[-1] in ("s_nop 0", "s_code_end", "..."):
+            ins.pop()
+    return out
+
+
+def main():
+    old_obj, new_obj, pats = sys.argv[1], sys.argv[2], sys.argv[3:]
+    with tempfile.TemporaryDirectory() as tmp:
+        os.makedirs(os.path.join(tmp, "old"))
+        os.makedirs(os.path.join(tmp, "new"))
+        a, b = kernels(old_obj, os.path.join(tmp, "old")), kernels(new_obj, os.path.join(tmp, "new"))
+    bad = 0
+    for name in sorted(a):
+        if pats and not any(p in name for p in pats):
+            continue
+        same = a[name] == b.get(name)
+        bad += not same
+        print(("identical " if same else "DIFFERENT ") + name, len(a[name]), len(b.get(name, [])))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
