@@ -568,6 +568,54 @@ int loamx_dist_gatherv(loamx_dist* h, const uint32_t* send_words, uint32_t n_wor
 int loamx_dist_barrier(loamx_dist* h);
 void* loamx_dist_stream(loamx_dist* h);   /* hipStream_t of the collectives */
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Dense global map (not in the reference): a sparse voxel map of the whole run in device memory, fed with registered sweeps where
+ * they lie (the mapper's and the pipeline's registered full-resolution clouds) or with map-frame points from the host.
+ *
+ * Per point, in f32 (inv = 1.0f / leaf): d = p - origin, d2 = (dx*dx + dy*dy) + dz*dz; the point is kept when d2 >= min_range^2 and,
+ * with max_range > 0, d2 <= max_range^2.  Per axis t = p*inv, i = floor(t), f = t - (float)i, q = min((uint32)(f * 2^20), 2^20 - 1);
+ * a point with any |i| >= 2^20 is dropped.  The voxel key packs (iz + 2^20, iy + 2^20, ix + 2^20) in 21 bits each (ascending key =
+ * ascending (iz, iy, ix), the order of csrc/voxel.hpp).  Each voxel keeps n and the 64-bit integer sums Sx, Sy, Sz of q: the map, and
+ * every byte exported from it, does not depend on the thread schedule or on the order of the points.
+ * Export: one record per voxel in ascending key order, x = (float)(((double)ix + (double)Sx / ((double)n * 2^20)) * (double)leaf)
+ * (y, z alike), intensity = (float)n; axes 1 writes the sensor axes ingestion started from (x_s = z, y_s = x, z_s = y), axes 0 the LOAM
+ * frame.
+ * Capacity: with max_voxels > 0 an add is refused (LOAMX_E_CAPACITY, map unchanged) when voxels_now + points_in_call > max_voxels
+ * (the cloud's point count before filtering).  Without a cap the table doubles on its own, on the device, before its load would pass
+ * one half; the adds from a mapper / a pipeline do not block the calling thread.
+ * Ordering: an add from a mapper or a pipeline is enqueued on that handle's own stream, behind the kernel that wrote the registered
+ * cloud; download, get_stats and save_pcd wait for every add first.  A source on another device than the map: LOAMX_E_INVALID.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct loamx_densemap loamx_densemap;
+typedef struct loamx_densemap_config {
+  float leaf;             /* voxel edge in metres, > 0 (default 0.1) */
+  float min_range;        /* points closer than this to the sweep's origin are dropped (default 0: none) */
+  float max_range;        /* points farther than this are dropped (default 0: no limit) */
+  uint64_t max_voxels;    /* cap on stored voxels; 0 = bounded by device memory only */
+  uint32_t initial_slots; /* hash-table slots at creation, power of two >= 1024 (default 1 << 20) */
+  int device;
+} loamx_densemap_config;
+
+void loamx_densemap_default_config(loamx_densemap_config* cfg);      /* host only, no device needed */
+loamx_densemap* loamx_densemap_create(const loamx_densemap_config* cfg);
+void loamx_densemap_destroy(loamx_densemap* h);
+int loamx_densemap_reset(loamx_densemap* h);
+/* map-frame points from the host; origin[3] = the sensor position used by the range filter */
+int loamx_densemap_add(loamx_densemap* h, const loamx_cloud* points, const float origin[3]);
+/* the registered full-resolution cloud of m's last process() / process_linked(), origin = that sweep's transformAftMapped translation;
+ * LOAMX_SKIPPED when that call produced no registered cloud */
+int loamx_densemap_add_from_map(loamx_densemap* h, loamx_map* m);
+/* the registered cloud of the slot-th stream registered in p's last step (the slot of loamx_pipeline_download_full_res), origin = that
+ * stream's transformAftMapped translation; LOAMX_SKIPPED when the last step registered nothing */
+int loamx_densemap_add_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot);
+/* stats: voxels, slots, points offered, points added, dropped by range, dropped outside the key range */
+int loamx_densemap_get_stats(loamx_densemap* h, uint64_t stats[6]);
+/* count in = capacity, out = voxels (LOAMX_E_CAPACITY, nothing written, when they do not fit); records as described above */
+int loamx_densemap_download(loamx_densemap* h, loamx_cloud* out, int axes /* 0 LOAM frame, 1 sensor axes */);
+int loamx_densemap_save_pcd(loamx_densemap* h, const char* path, int axes);
+/* host only: any cloud as a binary PCD v0.7 file, fields x y z intensity (F 4); axes as above */
+int loamx_write_pcd(const char* path, const loamx_cloud* c, int axes);
+
 #ifdef __cplusplus
 }
 #endif

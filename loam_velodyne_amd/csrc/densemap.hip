@@ -1,0 +1,548 @@
+// Dense global map (densemap.hpp, include/loamx.h loamx_densemap_*): registered sweeps accumulated into a voxel hash table in HBM.
+//
+// One insert kernel per add: range filter, voxel key, a combine of equal keys inside the wave, the open-addressing insert and the
+// accumulation, in one pass over the cloud.  The host keeps an upper bound of the occupancy (last known count + points enqueued since)
+// and enqueues a rehash into a table twice the size before that bound could pass half the slots — no wait for the device.  The known
+// count is refreshed by a kernel store into pinned memory (pinned_copy.hpp), read once an event shows it has landed.
+#include "densemap.hpp"
+#include "pinned_copy.hpp"
+#include "scan.hpp"
+#include <algorithm>
+#include <numeric>
+
+namespace loamx {
+
+struct DmFilter {
+  float inv, min2, max2;
+  int use_max;
+  float ox, oy, oz;
+};
+
+// counters: [0] occupied slots, [1] dropped by range, [2] dropped outside the key range, [3] probe overflow (never set while the host's
+// load rule holds: a guard against hanging the device, reported by the next reading call)
+constexpr int DM_CTR_WORDS = 4;
+
+__device__ inline unsigned long long dm_hash(unsigned long long key, uint32_t shift) {
+  return (key * 0x9E3779B97F4A7C15ull) >> shift;
+}
+
+// the slot of `key` (claimed when absent); won: this call claimed it.  false: the table is full (cannot happen at a load <= 1/2)
+__device__ inline bool dm_find_or_claim(unsigned long long* __restrict__ keys, uint32_t mask, uint32_t shift, unsigned long long key,
+                                        uint32_t& slot, bool& won) {
+  uint32_t h = (uint32_t)dm_hash(key, shift);
+  won = false;
+  for (uint32_t probe = 0; probe <= mask; probe++) {
+    // (a stale EMPTY from another XCD's L2 only costs the CAS below: a slot's key is written once, by the CAS that claims it)
+    unsigned long long cur = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == DM_EMPTY) {
+      cur = atomicCAS(&keys[h], DM_EMPTY, key);
+      if (cur == DM_EMPTY) { won = true; slot = h; return true; }
+    }
+    if (cur == key) { slot = h; return true; }
+    h = (h + 1u) & mask;
+  }
+  return false;
+}
+
+// wave-aggregated add of this lane's `c` to a 64-bit counter
+__device__ inline void dm_wave_count(unsigned long long* ctr, bool c) {
+  const unsigned long long m = __ballot(c);
+  if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(ctr, (unsigned long long)__popcll(m));
+}
+
+// one point per thread.  vals: 4 words per slot (n, Sx, Sy, Sz).  COMBINE: equal keys of a wave are summed in LDS first, and one lane
+// per distinct key touches the table (the sweep is in firing order: neighbouring lanes share voxels)
+template <bool COMBINE>
+__global__ __launch_bounds__(256) void k_dm_insert(const float4* __restrict__ pts, uint32_t n, DmFilter F, unsigned long long* __restrict__ keys,
+                                                   unsigned long long* __restrict__ vals, uint32_t mask, uint32_t shift,
+                                                   unsigned long long* __restrict__ ctr) {
+  __shared__ uint32_t acc[4][64][3];
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
+  unsigned long long key = DM_EMPTY;
+  uint32_t q[3] = {0u, 0u, 0u};
+  bool drop_range = false, drop_key = false;
+  if (i < n) {
+    const float4 p = pts[i];
+    const float dx = p.x - F.ox, dy = p.y - F.oy, dz = p.z - F.oz;
+    const float d2 = (dx * dx + dy * dy) + dz * dz;
+    if (!(d2 >= F.min2 && (!F.use_max || d2 <= F.max2))) {
+      drop_range = true;
+    } else {
+      const float c[3] = {p.x, p.y, p.z};
+      unsigned long long k = 0ull;
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+        const float t = c[a] * F.inv;
+        const float fi = floorf(t);
+        if (!(fabsf(fi) < DM_IMAX)) drop_key = true;   // (NaN too)
+        const float f = t - fi;
+        const uint32_t qa = (uint32_t)(f * DM_QSCALE);
+        q[a] = drop_key ? 0u : (qa < (1u << DM_QBITS) - 1u ? qa : (1u << DM_QBITS) - 1u);
+        const uint32_t ia = drop_key ? 0u : (uint32_t)((int)fi + (1 << DM_QBITS));
+        k |= (unsigned long long)ia << (DM_KBITS * a);
+      }
+      if (!drop_key) key = k;
+    }
+  }
+  dm_wave_count(&ctr[1], drop_range);
+  dm_wave_count(&ctr[2], drop_key);
+  const bool valid = key != DM_EMPTY;
+  uint32_t cnt = valid ? 1u : 0u;
+  bool owner = valid;
+  if (COMBINE) {
+    // group the lanes by key: the lowest lane of each group (its leader) collects the group's count and sums
+    int leader = -1;
+    unsigned long long todo = __ballot(valid);
+    while (todo) {
+      const int src = __builtin_ctzll(todo);
+      const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)key, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(key >> 32), src, 64);
+      const unsigned long long k0 = ((unsigned long long)hi << 32) | lo;
+      const unsigned long long m = __ballot(valid && key == k0);
+      if (valid && key == k0) {
+        leader = src;
+        if (lane == src) cnt = (uint32_t)__popcll(m);
+      }
+      todo &= ~m;
+    }
+    owner = valid && leader == lane;
+    if (owner) { acc[wid][lane][0] = 0u; acc[wid][lane][1] = 0u; acc[wid][lane][2] = 0u; }
+    __syncthreads();
+    if (valid) {   // (integer adds: the order does not matter; <= 64 x 2^20 fits 32 bits)
+      atomicAdd(&acc[wid][leader][0], q[0]);
+      atomicAdd(&acc[wid][leader][1], q[1]);
+      atomicAdd(&acc[wid][leader][2], q[2]);
+    }
+    __syncthreads();
+    if (owner) { q[0] = acc[wid][lane][0]; q[1] = acc[wid][lane][1]; q[2] = acc[wid][lane][2]; }
+  }
+  uint32_t slot = 0;
+  bool won = false, ok = true;
+  if (owner) ok = dm_find_or_claim(keys, mask, shift, key, slot, won);
+  dm_wave_count(&ctr[0], won);
+  if (owner && !ok) ctr[3] = 1ull;
+  if (owner && ok) {
+    unsigned long long* v = vals + 4ull * slot;
+    atomicAdd(&v[0], (unsigned long long)cnt);
+    atomicAdd(&v[1], (unsigned long long)q[0]);
+    atomicAdd(&v[2], (unsigned long long)q[1]);
+    atomicAdd(&v[3], (unsigned long long)q[2]);
+  }
+}
+
+// every occupied slot of the old table into the new one (keys are unique: claim the first empty slot of the probe sequence)
+__global__ __launch_bounds__(256) void k_dm_rehash(const unsigned long long* __restrict__ okeys, const unsigned long long* __restrict__ ovals,
+                                                   uint32_t on, unsigned long long* __restrict__ keys, unsigned long long* __restrict__ vals,
+                                                   uint32_t mask, uint32_t shift, unsigned long long* __restrict__ ctr) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= on) return;
+  const unsigned long long key = okeys[i];
+  if (key == DM_EMPTY) return;
+  uint32_t slot = 0;
+  bool won = false;
+  if (!dm_find_or_claim(keys, mask, shift, key, slot, won)) { ctr[3] = 1ull; return; }
+  const ulonglong2* s = (const ulonglong2*)(ovals + 4ull * i);
+  ulonglong2* d = (ulonglong2*)(vals + 4ull * slot);
+  d[0] = s[0];
+  d[1] = s[1];
+}
+
+// compaction of the occupied slots in slot order: occupied slots per 256-slot block (ballot), then (behind an exclusive scan of those
+// counts) each block writes its keys and values at its offset
+__global__ __launch_bounds__(256) void k_dm_count(const unsigned long long* __restrict__ keys, uint32_t slots, uint32_t* __restrict__ blk) {
+  __shared__ uint32_t wc[4];
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned long long m = __ballot(i < slots && keys[i] != DM_EMPTY);
+  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) blk[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+}
+
+__global__ __launch_bounds__(256) void k_dm_compact(const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ vals,
+                                                    uint32_t slots, const uint32_t* __restrict__ blk_off, unsigned long long* __restrict__ okeys,
+                                                    unsigned long long* __restrict__ ovals) {
+  __shared__ uint32_t wc[4];
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
+  const bool occ = i < slots && keys[i] != DM_EMPTY;
+  const unsigned long long m = __ballot(occ);
+  if (lane == 0) wc[wid] = (uint32_t)__popcll(m);
+  __syncthreads();
+  if (!occ) return;
+  uint32_t pos = blk_off[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+  for (int w = 0; w < wid; w++) pos += wc[w];
+  okeys[pos] = keys[i];
+  const ulonglong2* s = (const ulonglong2*)(vals + 4ull * i);
+  ulonglong2* d = (ulonglong2*)(ovals + 4ull * pos);
+  d[0] = s[0];
+  d[1] = s[1];
+}
+
+static uint32_t log2u(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }
+
+class DenseMap {
+ public:
+  explicit DenseMap(const loamx_densemap_config& c) : cfg(c) {
+    select_device(cfg.device);
+    LX_HIP(hipStreamCreateWithFlags(&own_, hipStreamNonBlocking));
+    LX_HIP(hipEventCreateWithFlags(&ev_last_, hipEventDisableTiming));
+    LX_HIP(hipEventCreateWithFlags(&ev_snap_, hipEventDisableTiming));
+    LX_HIP(hipEventCreateWithFlags(&ev_staged_, hipEventDisableTiming));
+    ctr_.reserve(DM_CTR_WORDS);
+    h_ctr_.reserve(2 * DM_CTR_WORDS);
+    h_snap_.reserve(2);
+    inv_ = 1.0f / cfg.leaf;
+    alloc_table(cfg.initial_slots, keys_, vals_);
+    slots_ = cfg.initial_slots;
+    clear(own_);
+    LX_HIP(hipStreamSynchronize(own_));
+  }
+  ~DenseMap() {
+    (void)hipSetDevice(cfg.device);
+    if (last_st_) (void)hipEventSynchronize(ev_last_);
+    (void)hipStreamSynchronize(own_);
+    free_graveyard();
+    (void)hipFree(keys_);
+    (void)hipFree(vals_);
+    (void)hipEventDestroy(ev_last_);
+    (void)hipEventDestroy(ev_snap_);
+    (void)hipEventDestroy(ev_staged_);
+    (void)hipStreamDestroy(own_);
+  }
+  loamx_densemap_config cfg;
+
+  int add_host(const loamx_cloud* c, const float origin[3]) {
+    check_cloud(c, false);
+    LX_HIP(hipSetDevice(cfg.device));
+    const uint32_t n = c->count;
+    if (!admit(n)) return LOAMX_E_CAPACITY;
+    if (!n) return LOAMX_OK;
+    if (staged_pending_) { LX_HIP(hipEventSynchronize(ev_staged_)); staged_pending_ = false; }   // (the staging block is still being read)
+    h_stage_.reserve(n);
+    pack_cloud(c, h_stage_.p);
+    d_stage_.reserve(n);
+    order_behind(own_);
+    fetch_from_pinned(d_stage_.p, h_stage_.p, n, own_);
+    LX_HIP(hipEventRecord(ev_staged_, own_));
+    staged_pending_ = true;
+    enqueue_add(d_stage_.p, n, origin, own_);
+    return LOAMX_OK;
+  }
+
+  int add_device(const DenseSource& s) {
+    LX_REQUIRE(s.device == cfg.device, "the dense map and its source live on different devices");
+    if (!s.has_cloud) return LOAMX_SKIPPED;
+    LX_HIP(hipSetDevice(cfg.device));
+    if (!admit(s.n)) return LOAMX_E_CAPACITY;
+    order_behind(s.stream);
+    enqueue_add(s.pts, s.n, s.origin, s.stream);
+    return LOAMX_OK;
+  }
+
+  // [voxels, slots, offered, added, dropped by range, dropped by key]
+  void stats(uint64_t out[6]) {
+    read_counters();
+    out[0] = occ_; out[1] = slots_; out[2] = offered_;
+    out[3] = offered_ - drop_range_ - drop_key_; out[4] = drop_range_; out[5] = drop_key_;
+  }
+
+  // the voxels as records (axes 0: LOAM frame, 1: sensor axes), ascending key order
+  void records(std::vector<float4>& out, int axes) {
+    read_counters();
+    const uint32_t slots = slots_, nblk = (slots + 255) / 256;
+    DevBuf<uint32_t> blk, scratch;
+    DevBuf<unsigned long long> tiles, okeys, ovals;
+    blk.reserve((size_t)nblk + 1);
+    scratch.reserve(2);
+    tiles.reserve(SCAN_SCRATCH_WORDS / 2);
+    okeys.reserve(occ_ + 1);
+    ovals.reserve(4 * (occ_ + 1));
+    LX_HIP(hipMemsetAsync(tiles.p, 0, sizeof(unsigned long long) * (SCAN_SCRATCH_WORDS / 2), own_));
+    hipLaunchKernelGGL(k_dm_count, dim3(nblk), dim3(256), 0, own_, keys_, slots, blk.p);
+    exclusive_scan_u32_n(blk.p, blk.p, (uint32_t*)tiles.p, scratch.p, nblk, own_);
+    hipLaunchKernelGGL(k_dm_compact, dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p);
+    LX_HIP(hipGetLastError());
+    std::vector<unsigned long long> hk(occ_), hv(4 * (size_t)occ_);
+    uint32_t total = 0;
+    LX_HIP(hipMemcpyAsync(&total, blk.p + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, own_));
+    if (occ_) {
+      LX_HIP(hipMemcpyAsync(hk.data(), okeys.p, sizeof(unsigned long long) * occ_, hipMemcpyDeviceToHost, own_));
+      LX_HIP(hipMemcpyAsync(hv.data(), ovals.p, sizeof(unsigned long long) * 4 * occ_, hipMemcpyDeviceToHost, own_));
+    }
+    LX_HIP(hipStreamSynchronize(own_));
+    scan_check_errors();
+    LX_REQUIRE(total == occ_, "dense map: the compaction disagrees with the occupancy count");
+    std::vector<uint32_t> idx(occ_);
+    std::iota(idx.begin(), idx.end(), 0u);
+    std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return hk[a] < hk[b]; });
+    out.resize(occ_);
+    const double leaf = (double)cfg.leaf, qs = (double)(1u << DM_QBITS);
+    const unsigned long long km = (1ull << DM_KBITS) - 1ull;
+    for (size_t r = 0; r < idx.size(); r++) {
+      const uint32_t j = idx[r];
+      const unsigned long long k = hk[j];
+      const double cnt = (double)hv[4 * (size_t)j];
+      float v[3];
+      for (int a = 0; a < 3; a++) {
+        const double ia = (double)((long long)((k >> (DM_KBITS * a)) & km) - (1ll << DM_QBITS));
+        v[a] = (float)((ia + (double)hv[4 * (size_t)j + 1 + a] / (cnt * qs)) * leaf);
+      }
+      out[r] = axes == 1 ? make_float4(v[2], v[0], v[1], (float)cnt) : make_float4(v[0], v[1], v[2], (float)cnt);
+    }
+  }
+
+  void reset() {
+    LX_HIP(hipSetDevice(cfg.device));
+    wait_adds();
+    clear(own_);
+    LX_HIP(hipStreamSynchronize(own_));
+    occ_ = pend_ = pend_snap_ = 0;
+    offered_ = drop_range_ = drop_key_ = 0;
+  }
+
+  bool combine = true;   // (bench A/B: the in-wave combining of equal keys)
+  uint64_t rehashes = 0;
+
+ private:
+  hipStream_t own_ = nullptr;      // host-fed adds, rehash of those, exports
+  hipStream_t last_st_ = nullptr;  // the stream of the last enqueued add (ev_last_ recorded behind it)
+  hipEvent_t ev_last_ = nullptr, ev_snap_ = nullptr, ev_staged_ = nullptr;
+  bool snap_pending_ = false, staged_pending_ = false;
+  unsigned long long* keys_ = nullptr;
+  unsigned long long* vals_ = nullptr;
+  uint32_t slots_ = 0;
+  float inv_ = 10.f;
+  DevBuf<unsigned long long> ctr_;
+  PinBuf<uint32_t> h_ctr_, h_snap_;
+  PinBuf<float4> h_stage_;
+  DevBuf<float4> d_stage_;
+  std::vector<void*> graveyard_;   // tables replaced by a rehash: freed at the next point where the host waits anyway
+  // occupancy: occ_ exact as of the last snapshot; pend_ points enqueued since (the bound is occ_ + pend_); pend_snap_ those enqueued
+  // behind the snapshot in flight
+  uint64_t occ_ = 0, pend_ = 0, pend_snap_ = 0;
+  uint64_t offered_ = 0, drop_range_ = 0, drop_key_ = 0;
+
+  void alloc_table(uint64_t slots, unsigned long long*& k, unsigned long long*& v) {
+    LX_HIP(hipMalloc((void**)&k, sizeof(unsigned long long) * slots));
+    LX_HIP(hipMalloc((void**)&v, sizeof(unsigned long long) * 4 * slots));
+  }
+  void clear(hipStream_t st) {
+    LX_HIP(hipMemsetAsync(keys_, 0xff, sizeof(unsigned long long) * slots_, st));
+    LX_HIP(hipMemsetAsync(vals_, 0, sizeof(unsigned long long) * 4 * slots_, st));
+    LX_HIP(hipMemsetAsync(ctr_.p, 0, sizeof(unsigned long long) * DM_CTR_WORDS, st));
+  }
+  void free_graveyard() {
+    for (void* p : graveyard_) (void)hipFree(p);
+    graveyard_.clear();
+  }
+  // st runs behind every add enqueued so far (on whichever stream)
+  void order_behind(hipStream_t st) {
+    if (last_st_ && last_st_ != st) LX_HIP(hipStreamWaitEvent(st, ev_last_, 0));
+  }
+  void wait_adds() {
+    if (last_st_) LX_HIP(hipEventSynchronize(ev_last_));
+    if (staged_pending_) { LX_HIP(hipEventSynchronize(ev_staged_)); staged_pending_ = false; }
+    snap_pending_ = false;
+    free_graveyard();
+  }
+  // exact counters, after every add
+  void read_counters() {
+    LX_HIP(hipSetDevice(cfg.device));
+    wait_adds();
+    store_to_pinned_u32(h_ctr_.p, (const uint32_t*)ctr_.p, 2 * DM_CTR_WORDS, own_);
+    LX_HIP(hipStreamSynchronize(own_));
+    const unsigned long long* c = (const unsigned long long*)h_ctr_.p;
+    LX_REQUIRE(c[3] == 0ull, "dense map: hash table overflow");
+    occ_ = c[0]; drop_range_ = c[1]; drop_key_ = c[2];
+    pend_ = pend_snap_ = 0;
+  }
+  // the occupancy snapshot that has landed, if any
+  void poll_snapshot() {
+    if (!snap_pending_) return;
+    const hipError_t e = hipEventQuery(ev_snap_);
+    if (e == hipErrorNotReady) return;
+    LX_HIP(e);
+    occ_ = h_snap_.p[0] | ((uint64_t)h_snap_.p[1] << 32);
+    pend_ = pend_snap_;
+    snap_pending_ = false;
+  }
+  // capacity rule (include/loamx.h): decided before anything is enqueued; the exact count is waited for only near the cap
+  bool admit(uint32_t n) {
+    poll_snapshot();
+    if (!cfg.max_voxels) return true;
+    if (occ_ + pend_ + n <= cfg.max_voxels) return true;
+    read_counters();
+    return occ_ + n <= cfg.max_voxels;
+  }
+  void enqueue_add(const float4* pts, uint32_t n, const float origin[3], hipStream_t st) {
+    // growth: keep the load at most one half even if every point enqueued since the last count made a voxel of its own
+    uint64_t want = slots_;
+    while (occ_ + pend_ + n > want / 2) want *= 2;
+    LX_REQUIRE(want <= (1ull << 31), "dense map: more voxels than the table can index");
+    if (want != slots_) {
+      unsigned long long *nk = nullptr, *nv = nullptr;
+      alloc_table(want, nk, nv);
+      LX_HIP(hipMemsetAsync(nk, 0xff, sizeof(unsigned long long) * want, st));
+      LX_HIP(hipMemsetAsync(nv, 0, sizeof(unsigned long long) * 4 * want, st));   // (slots claimed later accumulate from zero)
+      const uint32_t sh = 64u - log2u(want);
+      hipLaunchKernelGGL(k_dm_rehash, dim3((slots_ + 255) / 256), dim3(256), 0, st, keys_, vals_, slots_, nk, nv, (uint32_t)(want - 1), sh, ctr_.p);
+      graveyard_.push_back(keys_);
+      graveyard_.push_back(vals_);
+      keys_ = nk;
+      vals_ = nv;
+      slots_ = (uint32_t)want;
+      rehashes++;
+    }
+    if (n) {
+      DmFilter F;
+      F.inv = inv_;
+      F.min2 = cfg.min_range * cfg.min_range;
+      F.max2 = cfg.max_range * cfg.max_range;
+      F.use_max = cfg.max_range > 0.f ? 1 : 0;
+      F.ox = origin[0]; F.oy = origin[1]; F.oz = origin[2];
+      const uint32_t sh = 64u - log2u(slots_);
+      if (combine)
+        hipLaunchKernelGGL(k_dm_insert<true>, dim3((n + 255) / 256), dim3(256), 0, st, pts, n, F, keys_, vals_, slots_ - 1u, sh, ctr_.p);
+      else
+        hipLaunchKernelGGL(k_dm_insert<false>, dim3((n + 255) / 256), dim3(256), 0, st, pts, n, F, keys_, vals_, slots_ - 1u, sh, ctr_.p);
+    }
+    LX_HIP(hipGetLastError());
+    offered_ += n;
+    pend_ += n;
+    if (snap_pending_) {
+      pend_snap_ += n;
+    } else {
+      store_to_pinned_u32(h_snap_.p, (const uint32_t*)ctr_.p, 2, st);
+      LX_HIP(hipEventRecord(ev_snap_, st));
+      snap_pending_ = true;
+      pend_snap_ = 0;
+    }
+    LX_HIP(hipEventRecord(ev_last_, st));
+    last_st_ = st;
+  }
+};
+
+static void write_pcd_records(const char* path, const float4* rec, size_t n) {
+  FILE* f = fopen(path, "wb");
+  LX_REQUIRE(f, std::string("cannot open ") + path + " for writing");
+  const int hl = fprintf(f,
+                         "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity\nSIZE 4 4 4 4\nTYPE F F F F\n"
+                         "COUNT 1 1 1 1\nWIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %zu\nDATA binary\n", n, n);
+  const bool ok = hl > 0 && (n == 0 || fwrite(rec, sizeof(float4), n, f) == n);
+  const bool closed = fclose(f) == 0;
+  LX_REQUIRE(ok && closed, std::string("write to ") + path + " failed");
+}
+
+}  // namespace loamx
+
+using namespace loamx;
+
+struct loamx_densemap {
+  DenseMap d;
+  explicit loamx_densemap(const loamx_densemap_config& c) : d(c) {}
+};
+
+extern "C" {
+
+void loamx_densemap_default_config(loamx_densemap_config* cfg) {
+  if (!cfg) return;
+  memset(cfg, 0, sizeof(*cfg));
+  cfg->leaf = 0.1f;
+  cfg->min_range = 0.f;
+  cfg->max_range = 0.f;
+  cfg->max_voxels = 0;
+  cfg->initial_slots = 1u << 20;
+  cfg->device = 0;
+}
+
+loamx_densemap* loamx_densemap_create(const loamx_densemap_config* cfg) {
+  loamx_densemap* h = nullptr;
+  guard([&]() {
+    loamx_densemap_config c;
+    if (cfg) c = *cfg; else loamx_densemap_default_config(&c);
+    LX_REQUIRE(c.leaf > 0.f && std::isfinite(c.leaf), "leaf must be positive");
+    LX_REQUIRE(c.min_range >= 0.f && c.max_range >= 0.f && std::isfinite(c.min_range) && std::isfinite(c.max_range), "ranges must be >= 0");
+    LX_REQUIRE(c.max_range == 0.f || c.max_range >= c.min_range, "max_range must be 0 or >= min_range");
+    LX_REQUIRE(c.initial_slots >= 1024u && c.initial_slots <= (1u << 30) && (c.initial_slots & (c.initial_slots - 1u)) == 0u,
+               "initial_slots must be a power of two in [1024, 2^30]");
+    h = new loamx_densemap(c);
+    return LOAMX_OK;
+  });
+  return h;
+}
+void loamx_densemap_destroy(loamx_densemap* h) { delete h; }
+
+int loamx_densemap_reset(loamx_densemap* h) {
+  return guard([&]() { LX_REQUIRE(h, "NULL handle"); h->d.reset(); return LOAMX_OK; });
+}
+int loamx_densemap_add(loamx_densemap* h, const loamx_cloud* points, const float origin[3]) {
+  return guard([&]() {
+    LX_REQUIRE(h && points && origin, "NULL argument");
+    return h->d.add_host(points, origin);
+  });
+}
+int loamx_densemap_add_from_map(loamx_densemap* h, loamx_map* m) {
+  return guard([&]() {
+    LX_REQUIRE(h && m, "NULL argument");
+    DenseSource s;
+    loamx_map_dense_source(m, s);
+    return h->d.add_device(s);
+  });
+}
+int loamx_densemap_add_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot) {
+  return guard([&]() {
+    LX_REQUIRE(h && p, "NULL argument");
+    DenseSource s;
+    loamx_pipeline_dense_source(p, slot, s);
+    return h->d.add_device(s);
+  });
+}
+int loamx_densemap_get_stats(loamx_densemap* h, uint64_t stats[6]) {
+  return guard([&]() {
+    LX_REQUIRE(h && stats, "NULL argument");
+    h->d.stats(stats);
+    return LOAMX_OK;
+  });
+}
+int loamx_densemap_download(loamx_densemap* h, loamx_cloud* out, int axes) {
+  return guard([&]() {
+    LX_REQUIRE(h && out, "NULL argument");
+    LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+    check_cloud(out, false);
+    std::vector<float4> rec;
+    h->d.records(rec, axes);
+    if (rec.size() > out->count) { out->count = (uint32_t)rec.size(); return LOAMX_E_CAPACITY; }
+    return unpack_cloud(rec.data(), (uint32_t)rec.size(), out);
+  });
+}
+int loamx_densemap_save_pcd(loamx_densemap* h, const char* path, int axes) {
+  return guard([&]() {
+    LX_REQUIRE(h && path, "NULL argument");
+    LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+    std::vector<float4> rec;
+    h->d.records(rec, axes);
+    write_pcd_records(path, rec.data(), rec.size());
+    return LOAMX_OK;
+  });
+}
+int loamx_write_pcd(const char* path, const loamx_cloud* c, int axes) {
+  return guard([&]() {
+    LX_REQUIRE(path && c, "NULL argument");
+    LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+    check_cloud(c, false);
+    std::vector<float4> rec(c->count);
+    pack_cloud(c, rec.data());
+    if (axes == 1)
+      for (float4& r : rec) r = make_float4(r.z, r.x, r.y, r.w);
+    write_pcd_records(path, rec.data(), rec.size());
+    return LOAMX_OK;
+  });
+}
+
+// bench / test hooks (not in include/loamx.h): the in-wave combining of equal keys on or off, and the number of rehashes so far
+int loamx_densemap_set_combine(loamx_densemap* h, int on) {
+  return guard([&]() { LX_REQUIRE(h, "NULL handle"); h->d.combine = on != 0; return LOAMX_OK; });
+}
+uint64_t loamx_densemap_rehashes(loamx_densemap* h) { return h ? h->d.rehashes : 0; }
+
+}  // extern "C"

@@ -24,6 +24,7 @@
 #include <thread>
 #include "host_math.h"
 #include "scan.hpp"
+#include "densemap.hpp"
 
 namespace loamx {
 
@@ -1322,3 +1323,19 @@ int loamx_map_get_stats(loamx_map* h, int s[8]) {
 }
 
 }  // extern "C"
+
+// the registered cloud of the last process() / process_linked(), for the dense map (densemap.hpp): the registrar's full-resolution buffer,
+// written on the registrar's stream and rewritten only by the next sweep's upload on that same stream
+void loamx_map_dense_source(loamx_map* h, loamx::DenseSource& out) {
+  LX_REQUIRE(h, "NULL mapper");
+  Mapper& M = h->m;
+  out = loamx::DenseSource{};
+  out.stream = M.reg.stream();
+  out.device = M.cfg.device;
+  if (M.reg.n_sweeps() < 1) return;
+  out.n = M.reg.full_offset(1) - M.reg.full_offset(0);
+  if (!out.n) return;
+  out.pts = M.reg.d_full_res() + M.reg.full_offset(0);
+  out.origin[0] = M.aft.pos.x; out.origin[1] = M.aft.pos.y; out.origin[2] = M.aft.pos.z;
+  out.has_cloud = true;
+}

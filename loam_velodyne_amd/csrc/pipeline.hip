@@ -10,6 +10,7 @@
 #include "odometry.hpp"
 #include "registration.hpp"
 #include "hostlink.hpp"
+#include "densemap.hpp"
 #include <atomic>
 #include <deque>
 #include <functional>
@@ -130,6 +131,7 @@ class Pipeline {
   uint32_t up_runs[RING] = {};                            // block copies of the slot's step handed to uplink (0: none, the HIP copy stream carried them)
   std::atomic<long> last_step{-1};                        // the last step that has run (-1: none yet)
   std::vector<uint32_t> last_full_off;                   // offsets of the registered clouds of the last step (k-th mapped stream)
+  std::vector<uint32_t> last_who;                        // ... and the stream of each (loamx_densemap_add_from_pipeline: its pose)
   // Raw input (loamx_pipeline_stage_step_raw): per slot the payloads, their binned clouds and what the binning leaves behind
   struct RawSlot {
     bool raw = false, finalized = true;
@@ -901,6 +903,7 @@ class Pipeline {
           chains[0]->ob->to_end_gather(full_dst, foff.data(), fsrc.data(), tep.data(), nw, s_);
         }
         last_full_off = foff;
+        last_who = who;
         run_count++;
         reg.upload_device(nw, cl.data(), ncl.data(), sl.data(), nsl.data(), nullptr, nullptr, guess.data());
         // transformUpdate's IMU blend (BasicLaserMapping.cpp:171-200) changes transformTobeMapped BEFORE the full-resolution cloud is
@@ -928,6 +931,7 @@ class Pipeline {
         }
       } else {
         last_full_off.clear();
+        last_who.clear();
       }
       launch_f2();
       if (nw) prestage_gather(ti + 1, last_staged, s_);   // (no-op when the first wait's callback did it)
@@ -1197,3 +1201,21 @@ int loamx_pipeline_lookahead_depth(loamx_pipeline* h) { return h ? h->p.depth() 
 void* loamx_pipeline_stream(loamx_pipeline* h) { return h ? (void*)h->p.reg.stream() : nullptr; }
 
 }  // extern "C"
+
+// the registered cloud of the slot-th stream registered in the last step, for the dense map (densemap.hpp): it lies in the registrar's
+// full-resolution buffer until the registrar's stream passes the next step's gather, so an add enqueued on that stream reads it in time
+void loamx_pipeline_dense_source(loamx_pipeline* h, uint32_t slot, loamx::DenseSource& out) {
+  LX_REQUIRE(h, "NULL pipeline");
+  Pipeline& P = h->p;
+  out = loamx::DenseSource{};
+  out.stream = P.reg.stream();
+  out.device = P.device;
+  const uint32_t nw = P.last_full_off.empty() ? 0u : (uint32_t)P.last_full_off.size() - 1;
+  if (!nw) return;
+  LX_REQUIRE(slot < nw, "slot beyond the streams registered in the last step");
+  out.pts = P.reg.d_full_res() + P.last_full_off[slot];
+  out.n = P.last_full_off[slot + 1] - P.last_full_off[slot];
+  const HTwist& aft = P.st[P.last_who[slot]].aft;
+  out.origin[0] = aft.pos.x; out.origin[1] = aft.pos.y; out.origin[2] = aft.pos.z;
+  out.has_cloud = true;
+}

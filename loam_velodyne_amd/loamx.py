@@ -900,6 +900,103 @@ class Pipeline:
         return int(lib().loamx_pipeline_stream(self.h) or 0)
 
 
+class DenseMapConfig(C.Structure):
+    _fields_ = [("leaf", C.c_float), ("min_range", C.c_float), ("max_range", C.c_float), ("max_voxels", C.c_uint64),
+                ("initial_slots", C.c_uint32), ("device", C.c_int)]
+
+
+_AXES = {"loam": 0, "sensor": 1}
+
+
+def _axes(axes) -> int:
+    assert axes in _AXES, f"axes must be one of {tuple(_AXES)}"
+    return _AXES[axes]
+
+
+def write_pcd(path: str, points, axes="loam"):
+    """loamx_write_pcd: an (N, 4) / (N, 8) float32 cloud as a binary PCD v0.7 file (x y z intensity); axes="sensor" writes the sensor
+    axes ingestion started from (x_s = z, y_s = x, z_s = y).  Host only."""
+    a = as_points(points)
+    c = cloud_of(a)
+    _check(lib().loamx_write_pcd(os.fsencode(path), C.byref(c), _axes(axes)))
+
+
+class DenseMap:
+    """loamx_densemap_*: a sparse voxel map of the whole run in device memory, fed with registered sweeps where they lie (add_from: a
+    LaserMapping's last process; add_from_pipeline: a Pipeline's last step) or with map-frame points from the host (add)."""
+
+    def __init__(self, leaf=0.1, min_range=0.0, max_range=0.0, max_voxels=0, initial_slots=1 << 20, device=0):
+        L = lib()
+        L.loamx_densemap_create.restype = C.c_void_p
+        L.loamx_densemap_rehashes.restype = C.c_uint64
+        self._c = _cfg(DenseMapConfig, "loamx_densemap_default_config", leaf=leaf, min_range=min_range, max_range=max_range,
+                       max_voxels=max_voxels, initial_slots=initial_slots, device=device)
+        self.h = C.c_void_p(L.loamx_densemap_create(C.byref(self._c)))
+        if not self.h:
+            raise LoamxError(E_INVALID, L.loamx_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().loamx_densemap_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def add(self, points, origin=(0.0, 0.0, 0.0)):
+        """map-frame points (N, 4) / (N, 8); origin = the sensor position the range filter measures from.  Returns the status (OK);
+        LoamxError E_CAPACITY when max_voxels would be passed (the map is then unchanged)"""
+        a = as_points(points)
+        c = cloud_of(a)
+        o = np.ascontiguousarray(origin, np.float32)
+        assert o.shape == (3,)
+        return _check(lib().loamx_densemap_add(self.h, C.byref(c), o.ctypes.data_as(C.c_void_p)))
+
+    def add_from(self, mapping):
+        """the registered full-resolution cloud of mapping's last process / process_linked (SKIPPED when it produced none)"""
+        return _check(lib().loamx_densemap_add_from_map(self.h, mapping.h))
+
+    def add_from_pipeline(self, pipeline, slot: int):
+        """the registered cloud of the slot-th stream registered in pipeline's last step (SKIPPED when that step registered none)"""
+        return _check(lib().loamx_densemap_add_from_pipeline(self.h, pipeline.h, slot))
+
+    def stats(self):
+        s = (C.c_uint64 * 6)()
+        _check(lib().loamx_densemap_get_stats(self.h, s))
+        keys = ("voxels", "slots", "offered", "added", "dropped_range", "dropped_key")
+        return dict(zip(keys, (int(v) for v in s)))
+
+    def __len__(self):
+        return self.stats()["voxels"]
+
+    def points(self, axes="loam"):
+        """(n, 4) float32: one record per voxel in ascending key order — the mean position, intensity = the voxel's point count"""
+        n = len(self)
+        while True:
+            out = np.zeros((max(n, 1), 4), np.float32)
+            c = cloud_of(out)
+            c.count = n
+            rc = lib().loamx_densemap_download(self.h, C.byref(c), _axes(axes))
+            if rc == E_CAPACITY:
+                n = int(c.count)
+                continue
+            _check(rc)
+            return out[:c.count]
+
+    def save_pcd(self, path: str, axes="loam"):
+        _check(lib().loamx_densemap_save_pcd(self.h, os.fsencode(path), _axes(axes)))
+
+    def reset(self):
+        _check(lib().loamx_densemap_reset(self.h))
+
+    def set_combine(self, on: bool):
+        """bench hook: the in-wave combining of equal keys before the table is touched (default on; results are the same)"""
+        _check(lib().loamx_densemap_set_combine(self.h, 1 if on else 0))
+
+    @property
+    def rehashes(self) -> int:
+        return int(lib().loamx_densemap_rehashes(self.h))
+
+
 def dist_shard_of(rank: int, world: int, batch: int):
     b, e = C.c_uint32(0), C.c_uint32(0)
     _check(lib().loamx_dist_shard_of(rank, world, batch, C.byref(b), C.byref(e)))
