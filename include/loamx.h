@@ -105,6 +105,18 @@ typedef struct loamx_scanreg_config {
                                         behave as 200; at most 4096 here */
 } loamx_scanreg_config;
 
+/* Ring-length limit.  The feature extraction holds a whole scan ring in one workgroup's LDS, so the longest ring of a sweep (of any
+ * sweep of a pipeline step) has a limit that depends on n_feature_regions (R) and the pick limits.  With L the ring length,
+ *   F = 16 * ceil(L / 16),   N = 16 * ceil((floor(L / R) + 8) / 16),   S = the smallest power of two >= max(N, 64),
+ *   W = min(R, 6),           C = 4 * R * (max_corner_sharp + max_corner_less_sharp + max_surface_flat),
+ *   bytes = 16 * ceil((8 * F + C) / 16) + 9 * W * N + (S > 512 ? 8 * W * S : 0) + 16,
+ * a ring is accepted when bytes <= 162816 (160 KB less 1 KB).  The longest ring accepted at the default pick limits (2, 20, 4):
+ *   R        1     2     3     4     5     6     7     8     12    13    16    32     64
+ *   L_max  5704  5681  6122  5667  5084  6101  7118  7616  8939  9168  9776  16159  17568
+ * curvature_region does not enter.  A longer ring is refused with LOAMX_E_INVALID before anything is enqueued; the handle stays
+ * usable.  With raw input (process_raw, process_sensor, the pipeline's raw steps) the ring sizes are known only after binning,
+ * so the refusal comes after the binning and before the extraction. */
+
 void loamx_scanreg_default_config(loamx_scanreg_config* cfg);
 loamx_scanreg* loamx_scanreg_create(const loamx_scanreg_config* cfg);
 void loamx_scanreg_destroy(loamx_scanreg* h);

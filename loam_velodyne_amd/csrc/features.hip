@@ -220,11 +220,13 @@ __device__ unsigned long long g_feat_ts[8];
 #endif
 constexpr int FEAT_WAVES = 6;   // regions sorted concurrently per ring
 
-// one workgroup of FEAT_WAVES waves per ring.  Dynamic LDS: flags[flag_bytes] | gaps[flag_bytes] | per wave { c | sorted | label }[nmax]
+// one workgroup of FEAT_WAVES waves per ring.  Dynamic LDS (feat_ring_lds): flags | gaps | fwd | flags0 [flag_bytes each] | curvatures
+// [flag_bytes floats] | pick lists | per wave { c | sorted | label }[nmax] | per wave LDS sort keys[sortP] (sortP > 512 only).  Only
+// nwaves = min(n_regions, FEAT_WAVES) waves ever hold a region, so only they have per-wave areas.
 // 5 waves per SIMD (<= 96 VGPRs): three 6-wave workgroups share a CU, and 512 rings on 256 CUs are not dealt two apiece
 __global__ __launch_bounds__(64 * FEAT_WAVES) __attribute__((amdgpu_waves_per_eu(5))) void k_feat_ring(
     const float4* __restrict__ cloud, const uint32_t* __restrict__ ring_off, const uint32_t* __restrict__ ring_sweep_base, FeatParams P,
-    uint32_t flag_bytes, uint32_t nmax, uint32_t sortP, float4* __restrict__ slotS,
+    uint32_t flag_bytes, uint32_t nmax, uint32_t sortP, uint32_t nwaves, float4* __restrict__ slotS,
     float4* __restrict__ slotLS, float4* __restrict__ slotF, uint32_t* __restrict__ cntS, uint32_t* __restrict__ cntLS,
     uint32_t* __restrict__ cntF, uint8_t* __restrict__ lf_valid, int force_sequential, uint32_t* __restrict__ bad_word) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -273,7 +275,7 @@ __global__ __launch_bounds__(64 * FEAT_WAVES) __attribute__((amdgpu_waves_per_eu
     // 41 us).  The chunks live in the per-wave sort buffers, which nothing touches before the prologue is over.  Same values, same
     // operations in the same order: bit-identical.
     float4* stg = (float4*)wave_base;
-    const uint32_t stg_cap = (uint32_t)((FEAT_WAVES * wave_bytes) / sizeof(float4));
+    const uint32_t stg_cap = (uint32_t)((nwaves * wave_bytes) / sizeof(float4));
     const uint32_t halo = (uint32_t)(cr > 1 ? cr : 1);
     const bool staged = stg_cap >= 2u * halo + 64u;          // (block-uniform; otherwise — a huge curvature region — straight from memory)
     const uint32_t chunk = staged ? stg_cap - 2u * halo : len;
@@ -380,8 +382,8 @@ __global__ __launch_bounds__(64 * FEAT_WAVES) __attribute__((amdgpu_waves_per_eu
       else if (sortP == 128) wave_sort_curvature<2>(c, n, sorted, lane);
       else if (sortP == 256) wave_sort_curvature<4>(c, n, sorted, lane);
       else if (sortP == 512) wave_sort_curvature<8>(c, n, sorted, lane);
-      else {
-        unsigned long long* keys = (unsigned long long*)(wave_base + FEAT_WAVES * wave_bytes + (size_t)wid * sortP * 8);
+      else if (wid < (int)nwaves) {   // (a wave beyond the regions holds none and has no key buffer)
+        unsigned long long* keys = (unsigned long long*)(wave_base + nwaves * wave_bytes + (size_t)wid * sortP * 8);
         for (uint32_t e = lane; e < sortP; e += 64)
           keys[e] = e < n ? ((unsigned long long)__float_as_uint(c[e]) << 32) | e : ~0ull;
         wave_lds_sync();
@@ -489,6 +491,31 @@ __global__ __launch_bounds__(64 * FEAT_WAVES) __attribute__((amdgpu_waves_per_eu
   for (uint32_t k = tid; k < npick[1]; k += blockDim.x) slotLS[(size_t)r * capLS + k] = cloud[pickLS[k]];
   for (uint32_t k = tid; k < npick[2]; k += blockDim.x) slotF[(size_t)r * capF + k] = cloud[pickF[k]];
   FT_TS(4);
+}
+
+// The dynamic LDS of k_feat_ring for a batch whose longest ring has max_len points.  A region holds at most max_len / n_regions + 1
+// points; nmax leaves room for the 4 padding entries behind it.  The limit this puts on the ring length is stated in include/loamx.h
+// (loamx_scanreg_config) and pinned by tests/test_gpu_ring_shapes.py, which restates this function.
+struct FeatRingLds {
+  uint32_t flag_bytes, nmax, sortP, nwaves;
+  size_t bytes;
+};
+// 160 KB of LDS per workgroup, 1 KB of it kept for k_feat_ring's own __shared__ arrays (reg_n ... s_simple: 864 bytes)
+constexpr size_t FEAT_LDS_STATIC = 1024;
+constexpr size_t FEAT_LDS_MAX = 160 * 1024 - FEAT_LDS_STATIC;
+static_assert(sizeof(uint32_t) * (3 * FEAT_WAVES + 3 + 64 * 3) + sizeof(int) <= FEAT_LDS_STATIC, "k_feat_ring's static LDS");
+
+static FeatRingLds feat_ring_lds(uint32_t max_len, const FeatParams& p) {
+  FeatRingLds r;
+  const size_t caps = (size_t)(p.max_sharp + p.max_less_sharp + p.max_flat) * p.n_regions;
+  r.flag_bytes = (max_len + 15u) & ~15u;
+  r.nmax = (max_len / (uint32_t)p.n_regions + 8u + 15u) & ~15u;
+  r.sortP = 64;   // bitonic sort size of one region
+  while (r.sortP < r.nmax) r.sortP <<= 1;
+  r.nwaves = (uint32_t)std::min(p.n_regions, FEAT_WAVES);
+  r.bytes = ((8 * (size_t)r.flag_bytes + 4 * caps + 15) & ~(size_t)15) + (size_t)r.nwaves * r.nmax * (4 + 4 + 1) +
+            (r.sortP > 512 ? (size_t)r.nwaves * r.sortP * 8 : 0) + 16;   // (regions of up to 512 points are sorted in registers)
+  return r;
 }
 
 // ----------------------------------------------------------------------------------------------------------------
@@ -809,6 +836,11 @@ void FeatureExtractor::upload_device(uint32_t nsw, const float4* d_src, const ui
   LX_HIP(hipEventRecord(done, copy_stream));
 }
 void FeatureExtractor::layout_(uint32_t nsw, const uint32_t* const* ring_size, const uint32_t* n_rings) {
+  // the longest ring must fit k_feat_ring's LDS: refused here, before this object's state changes or anything is enqueued
+  uint32_t longest = 0;
+  for (uint32_t s = 0; s < nsw; s++)
+    for (uint32_t r = 0; r < n_rings[s]; r++) longest = std::max(longest, ring_size[s][r]);
+  LX_REQUIRE(feat_ring_lds(longest, params).bytes <= FEAT_LDS_MAX, "scan ring too long for the LDS staging of k_feat_ring (include/loamx.h)");
   nsw_ = nsw;
   h_ring_off_.assign(1, 0);
   h_ring_base_.assign(nsw + 1, 0);
@@ -1115,18 +1147,14 @@ void FeatureExtractor::run_async(bool mirror_offsets) {
   (void)cr;   // (lf_valid_ is cleared ring by ring in k_feat_ring's prologue: no memset)
   const uint32_t caps[3] = {(uint32_t)(params.max_sharp * params.n_regions), (uint32_t)(params.max_less_sharp * params.n_regions),
                             (uint32_t)(params.max_flat * params.n_regions)};
-  const uint32_t flag_bytes = (max_ring_len_ + 15u) & ~15u;
-  const uint32_t nmax = (max_ring_len_ / (uint32_t)params.n_regions + 8u + 15u) & ~15u;
-  uint32_t sortP = 64;   // bitonic sort size of one region
-  while (sortP < nmax) sortP <<= 1;
-  const size_t lds = ((8 * (size_t)flag_bytes + 4 * (size_t)(caps[0] + caps[1] + caps[2]) + 15) & ~(size_t)15) + (size_t)FEAT_WAVES * nmax * (4 + 4 + 1) +
-                     (sortP > 512 ? (size_t)FEAT_WAVES * sortP * 8 : 0) + 16;   // (regions of up to 512 points are sorted in registers)
-  LX_REQUIRE(lds <= 160 * 1024, "scan ring too long for the LDS staging of k_feat_ring");
+  const FeatRingLds L = feat_ring_lds(max_ring_len_, params);
+  const size_t lds = L.bytes;
+  LX_REQUIRE(lds <= FEAT_LDS_MAX, "internal: scan ring too long for the LDS staging of k_feat_ring");   // (layout_ refuses such a batch)
   static const bool force_seq = diag_env("LOAMX_FEAT_SEQUENTIAL") && atoi(diag_env("LOAMX_FEAT_SEQUENTIAL")) != 0;   // (diagnostic: the regions one after the other)
   if (lds > 64 * 1024)
     LX_HIP(hipFuncSetAttribute((const void*)k_feat_ring, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_feat_ring, dim3(nring_), dim3(64 * FEAT_WAVES), lds, st_, cloud_.p, ring_off_.p, ring_sweep_base_.p, params, flag_bytes, nmax,
-                     sortP, slots_[0].p, slots_[1].p, slots_[2].p, slot_cnt_[0].p, slot_cnt_[1].p, slot_cnt_[2].p, lf_valid_.p, force_seq ? 1 : 0,
+  hipLaunchKernelGGL(k_feat_ring, dim3(nring_), dim3(64 * FEAT_WAVES), lds, st_, cloud_.p, ring_off_.p, ring_sweep_base_.p, params, L.flag_bytes, L.nmax,
+                     L.sortP, L.nwaves, slots_[0].p, slots_[1].p, slots_[2].p, slot_cnt_[0].p, slot_cnt_[1].p, slot_cnt_[2].p, lf_valid_.p, force_seq ? 1 : 0,
                      h_bad_.p);
   hipLaunchKernelGGL(k_feat_compact, dim3(nring_, 3), dim3(64), 0, st_, slots_[0].p, slots_[1].p, slots_[2].p, slot_cnt_[0].p, slot_cnt_[1].p,
                      slot_cnt_[2].p, caps[0], caps[1], caps[2], out_[0].p, out_[1].p, out_[2].p, offs_.p, sweep_ring_base_.p, nsw_, hmir);

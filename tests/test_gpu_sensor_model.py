@@ -5,6 +5,7 @@ import pytest
 
 import oracle_py as op
 from loam_velodyne_amd import loamx, synth
+from sensor_model_np import _np_bin_time_field
 
 pytestmark = pytest.mark.gpu
 
@@ -86,24 +87,6 @@ def test_table_on_uneven_lasers(orc, small_world):
     of = op.ScanRegistration(orc).process(t["full"], t["ring_sizes"])
     for k in FEATS:
         assert t[k].shape == of[k].shape and np.array_equal(t[k][:, :3], of[k][:, :3]), k
-
-
-def _np_bin_time_field(rec, time, scale, n_rings, scan_period=0.1):
-    """include/loamx.h's semantics for RING_FROM_FIELD + TIME_FROM_FIELD restated in numpy"""
-    X, Y, Z = rec["y"].astype(np.float32), rec["z"].astype(np.float32), rec["x"].astype(np.float32)
-    with np.errstate(invalid="ignore", over="ignore"):
-        keep = np.isfinite(X) & np.isfinite(Y) & np.isfinite(Z)
-        keep &= (X * X + Y * Y + Z * Z).astype(np.float64) >= 0.0001
-    ring = rec["ring"].astype(np.int64)
-    t = rec[time].astype(np.float64)
-    keep &= (ring < n_rings) & np.isfinite(t)
-    idx = np.nonzero(keep)[0]
-    tref = t[idx].min()
-    rel = ((t[idx] - tref) * scale).astype(np.float32)
-    rel = np.where(rel > np.float32(scan_period), np.float32(scan_period), rel)
-    order = np.argsort(ring[idx], kind="stable")
-    full = np.stack([X[idx], Y[idx], Z[idx], ring[idx].astype(np.float32) + rel], 1)[order]
-    return full, np.bincount(ring[idx], minlength=n_rings).astype(np.int32)
 
 
 @pytest.mark.parametrize("layout,time,scale", [("velodyne", "time", 1.0), ("ouster", "t", 1e-9), ("hesai", "timestamp", 1.0)])

@@ -87,14 +87,26 @@ needs_sr = pytest.mark.skipif(not op.RefScanRegistration.available(), reason="or
                                            ("VLP-16", 600, dict(nFeatureRegions=4, curvatureRegion=3, maxCornerSharp=3, maxSurfaceFlat=2,
                                                                 surfaceCurvatureThreshold=0.2)),
                                            ("VLP-16", 600, dict(maxCornerSharp=3, maxCornerLessSharp=7)),      # parsed on its own, ScanRegistration.cpp:100-109
-                                           ("HDL-32", 500, dict(maxCornerSharp=1, maxCornerLessSharp=40))])
+                                           ("HDL-32", 500, dict(maxCornerSharp=1, maxCornerLessSharp=40)),
+                                           # 5 Hz ring lengths; (preset, n) = n evenly spaced lasers over [-25, 15] deg
+                                           ("VLP-16", 3600, {}), ("VLP-16", 4097, {}), ("HDL-64E", 6000, {}),
+                                           (("HDL-64E", 128), 1024, {}), (("HDL-64E", 256), 256, {}),
+                                           # region extremes
+                                           ("VLP-16", 200, dict(nFeatureRegions=64, curvatureRegion=16)),
+                                           ("VLP-16", 2048, dict(nFeatureRegions=64, curvatureRegion=1)),
+                                           ("VLP-16", 1800, dict(nFeatureRegions=1)), ("VLP-16", 2048, dict(nFeatureRegions=2)),
+                                           ("VLP-16", 2048, dict(maxCornerSharp=12, maxCornerLessSharp=180, maxSurfaceFlat=40,
+                                                                 surfaceCurvatureThreshold=0.02))])
 def test_feature_extraction_equals_the_reference(orc, small_world, sensor, az, cfg):
     """processScanlines / extractFeatures (BasicScanRegistration.cpp:28-46, :155-386) run by the reference's own code: sharp,
     less-sharp and flat picks identical point for point; the less-flat cloud identical too (its candidate set is the
     reference's, its voxel grid is the oracle's on both sides — see oracle/ref_stubs/pcl/filters/voxel_grid.h)."""
     from loam_velodyne_amd import synth
+    elev = None if isinstance(sensor, str) else np.linspace(-25.0, 15.0, sensor[1])
+    sensor = sensor if isinstance(sensor, str) else sensor[0]
     for seed in (1, 2):
-        sw = synth.make_sweep(small_world, sensor, np.zeros(6), np.array([0.002, 0.02, -0.001, 0.2, 0.01, 0.8]), seed=seed, az_steps=az)
+        sw = synth.make_sweep(small_world, sensor, np.zeros(6), np.array([0.002, 0.02, -0.001, 0.2, 0.01, 0.8]), seed=seed, az_steps=az,
+                              elevations_deg=elev)
         o = op.ScanRegistration(orc, **cfg).process(sw.points, sw.ring_sizes)
         r = op.RefScanRegistration(**cfg).process(sw.points, sw.ring_sizes)
         for name in ("full", "sharp", "less_sharp", "flat", "less_flat"):
@@ -335,12 +347,15 @@ needs_ms = pytest.mark.skipif(not op.RefMultiScanRegistration.available(), reaso
 
 
 @needs_ms
-@pytest.mark.parametrize("sensor,az", [("VLP-16", 600), ("HDL-32", 512), ("HDL-64E", 512)])
+@pytest.mark.parametrize("sensor,az", [("VLP-16", 600), ("HDL-32", 512), ("HDL-64E", 512),
+                                       ("VLP-16", 3600), ((-25.0, 15.0, 128), 512)])   # (a mapper tuple: that many evenly spaced lasers)
 def test_raw_ingestion_equals_the_reference(orc, small_world, sensor, az):
     o, r = op.ScanRegistration(orc), op.RefMultiScanRegistration(sensor)
     poses = synth.trajectory(3, yaw_step_deg=3.0)
+    elev = None if isinstance(sensor, str) else np.linspace(*sensor)
     for k in range(3):
-        sw = synth.make_sweep(small_world, sensor, poses[k], poses[k + 1], seed=60 + k, az_steps=az)
+        sw = synth.make_sweep(small_world, sensor if elev is None else "HDL-64E", poses[k], poses[k + 1], seed=60 + k, az_steps=az,
+                              elevations_deg=elev)
         raw = synth.to_raw(sw, bad_every=53)                                   # NaN, zero and out-of-field returns in the packet
         if k == 2:
             raw = np.roll(raw, 7 * len(sw.ring_sizes) + 3, axis=0)              # the sweep starts mid-firing at another azimuth
