@@ -628,6 +628,88 @@ int loamx_densemap_save_pcd(loamx_densemap* h, const char* path, int axes);
 /* host only: any cloud as a binary PCD v0.7 file, fields x y z intensity (F 4); axes as above */
 int loamx_write_pcd(const char* path, const loamx_cloud* c, int axes);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Place recognition (not in the reference): a database of rotation-invariant sweep descriptors in device memory (Scan Context: a
+ * ring x sector polar grid of maximum heights around the sensor) and an exhaustive search for the earlier entries that look like a
+ * query, with the yaw between the two.  Detection only: what is done with a match (a pose graph, a correction) is the host's.
+ *
+ * Descriptor of a cloud about an origin o (LOAM frame: x left, y up, z forward), everything per point in f32, no fused multiply-add:
+ *   d = p - o per component;  a = d.z, b = d.x;  r2 = a*a + b*b;  h = d.y + height_offset.
+ *   The point is used when x, y, z are finite, r2 >= min_range^2, r2 < max_range^2 (the squares in f32) and h > 0.
+ *   ring   i = min((int)(sqrtf(r2) * ring_scale), R - 1),  ring_scale = (float)R / max_range  (sqrtf and / correctly rounded).
+ *   sector: S boundary directions (c_k, s_k) = ((float)cos(2 pi k / S), (float)sin(2 pi k / S)), cos / sin evaluated in double on the
+ *          host (loamx_place_sector_table returns them);  cross(k) = c_k*b - s_k*a.  The sector is the smallest k with cross(k) >= 0
+ *          and cross((k + 1) mod S) < 0: the angle from +z towards +x lies in [2 pi k / S, 2 pi (k + 1) / S).  A point for which no k
+ *          qualifies (a = b = 0) is dropped.  No atan2 enters the definition.
+ *   cell   D[i][k] = the maximum h over its points, 0 when empty — a maximum does not depend on the order of the points, so an entry, and
+ *          every byte derived from it, does not depend on the thread schedule.
+ *   ring key  rk[i] = (D[i][0] + D[i][1] + ... in ascending k, one f32 addition at a time) / (float)S.
+ * Distance of a query Q and a stored C at shift s (0 <= s < S): nq[j] = sqrtf(sum_i Q[i][j]^2), nc alike (i ascending, each product
+ * rounded, then added);  dot(j, s) = sum_i Q[i][j] * C[i][(j + s) mod S] likewise;  the terms dot(j, s) / (nq[j] * nc[(j + s) mod S])
+ * are summed over the columns j, ascending, where both norms are > 0;  d(s) = 1 - sum / (float)count, and 1 when count is 0.  The
+ * distance of the pair is the smallest d(s), ties to the smaller s, and `shift` is that s:  Q[i][j] ~ C[i][(j + shift) mod S].
+ * Yaw convention: yaw_hint = shift * 2 pi / S is the yaw (rot_y of the pose convention above, mod 2 pi) of the query's frame relative
+ * to the stored entry's frame.  For sensor-frame clouds that is the heading of the revisit relative to the first visit; the clouds of
+ * add_from_map / add_from_pipeline are in the map frame — levelled and headed by the pose estimate — so there it is the yaw DRIFT
+ * between the two visits.
+ * Search for a query with id q (a query that is not stored: q = the number of entries): the candidates are the entries with
+ * id + exclude_recent < q.  With n_candidates K > 0 and more than K candidates they are first cut to the K smallest by
+ * (sum_i (rk_q[i] - rk_c[i])^2 in ascending i, id); with K = 0 every candidate is compared.  Result: the n_results best by
+ * (distance, id) ascending.
+ * Ordering: an add from a mapper or a pipeline is enqueued on that handle's own stream behind the kernel that wrote the registered
+ * cloud and does not block the caller; ids are the running count of entries.  Queries, get_descriptor and save wait for every add.
+ * The table of entries doubles on its own, on the device.  A source on another device than the database: LOAMX_E_INVALID.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct loamx_place loamx_place;
+typedef struct loamx_place_config {
+  int n_rings;              /* R, 1..64 (default 20) */
+  int n_sectors;            /* S, 4..128 (default 60) */
+  float max_range;          /* > 0 (default 80 m) */
+  float min_range;          /* >= 0, < max_range (default 0) */
+  float height_offset;      /* the sensor's height above the ground, so that heights are positive (default 2.0 m) */
+  int n_candidates;         /* K: 0 = exhaustive search (default); 1..256 = ring-key pre-selection */
+  uint32_t exclude_recent;  /* loamx_place_query_entry: entries this close in id to the query are not candidates (default 50) */
+  uint32_t max_entries;     /* cap on stored entries; 0 = bounded by device memory only */
+  uint32_t initial_entries; /* room at creation, a power of two (default 1024) */
+  int device;
+} loamx_place_config;
+typedef struct loamx_place_match {
+  uint32_t id;
+  uint32_t shift;            /* yaw_hint = shift * 2 pi / n_sectors */
+  float distance;
+  float ring_key_distance;
+} loamx_place_match;
+#define LOAMX_PLACE_MAX_RESULTS 64
+
+void loamx_place_default_config(loamx_place_config* cfg);            /* host only, no device needed */
+loamx_place* loamx_place_create(const loamx_place_config* cfg);
+void loamx_place_destroy(loamx_place* h);
+int loamx_place_reset(loamx_place* h);
+uint32_t loamx_place_size(loamx_place* h);                           /* entries, those still in flight included; no wait */
+/* host only: table[2k] = c_k, table[2k + 1] = s_k for k < n_sectors */
+int loamx_place_sector_table(int n_sectors, float* table);
+/* a cloud from the host, described about origin[3]; *id (may be NULL) = the new entry.  LOAMX_E_CAPACITY, database unchanged, when
+ * max_entries would be passed */
+int loamx_place_add(loamx_place* h, const loamx_cloud* points, const float origin[3], uint32_t* id);
+/* the registered full-resolution cloud of m's last process() / process_linked() where it lies, origin = that sweep's transformAftMapped
+ * translation; LOAMX_SKIPPED, and no entry, when that call produced no registered cloud */
+int loamx_place_add_from_map(loamx_place* h, loamx_map* m, uint32_t* id);
+/* the registered cloud of the slot-th stream registered in p's last step (the slot of loamx_pipeline_download_full_res); LOAMX_SKIPPED
+ * when the last step registered nothing */
+int loamx_place_add_from_pipeline(loamx_place* h, loamx_pipeline* p, uint32_t slot, uint32_t* id);
+/* the n_results (<= LOAMX_PLACE_MAX_RESULTS) best earlier entries for the stored entry `id` (the configuration's exclude_recent), and
+ * for a cloud that is not stored (exclude_recent as passed; 0 = every entry); *n_found = records written */
+int loamx_place_query_entry(loamx_place* h, uint32_t id, loamx_place_match* matches, uint32_t n_results, uint32_t* n_found);
+int loamx_place_query(loamx_place* h, const loamx_cloud* points, const float origin[3], uint32_t exclude_recent, loamx_place_match* matches,
+                      uint32_t n_results, uint32_t* n_found);
+/* entry id: desc[R * S] (ring-major) and ring_key[R]; either may be NULL */
+int loamx_place_get_descriptor(loamx_place* h, uint32_t id, float* desc, float* ring_key);
+/* the database as a file ('LXPL', version, R, S, the three f32 parameters, the count; then the descriptors and the ring keys), so that a
+ * map snapshot can travel with its keyframes.  load replaces the entries of a handle whose R, S, ranges and height_offset equal the
+ * file's (LOAMX_E_INVALID otherwise, handle unchanged); the loaded handle answers every query with the same bytes */
+int loamx_place_save(loamx_place* h, const char* path);
+int loamx_place_load(loamx_place* h, const char* path);
+
 #ifdef __cplusplus
 }
 #endif

@@ -997,6 +997,130 @@ class DenseMap:
         return int(lib().loamx_densemap_rehashes(self.h))
 
 
+class PlaceConfig(C.Structure):
+    _fields_ = [("n_rings", C.c_int), ("n_sectors", C.c_int), ("max_range", C.c_float), ("min_range", C.c_float),
+                ("height_offset", C.c_float), ("n_candidates", C.c_int), ("exclude_recent", C.c_uint32), ("max_entries", C.c_uint32),
+                ("initial_entries", C.c_uint32), ("device", C.c_int)]
+
+
+class PlaceMatch(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("shift", C.c_uint32), ("distance", C.c_float), ("ring_key_distance", C.c_float)]
+
+
+PLACE_MAX_RESULTS = 64
+
+
+def place_sector_table(n_sectors: int) -> np.ndarray:
+    """loamx_place_sector_table: (S, 2) float32 boundary directions (cos, sin)(2 pi k / S) of the sectors.  Host only."""
+    out = np.zeros((max(int(n_sectors), 1), 2), np.float32)
+    _check(lib().loamx_place_sector_table(int(n_sectors), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+class PlaceDB:
+    """loamx_place_*: scan-context descriptors of sweeps in device memory and the search for earlier entries that look like a query.
+    add: a cloud from the host; add_from: a LaserMapping's last registered cloud; add_from_pipeline: a Pipeline's.  A match is
+    (id, shift, distance, ring_key_distance); yaw_hint(shift) = shift * 2 pi / n_sectors (include/loamx.h has the convention)."""
+
+    def __init__(self, n_rings=20, n_sectors=60, max_range=80.0, min_range=0.0, height_offset=2.0, n_candidates=0, exclude_recent=50,
+                 max_entries=0, initial_entries=1024, device=0):
+        L = lib()
+        L.loamx_place_create.restype = C.c_void_p
+        L.loamx_place_size.restype = C.c_uint32
+        L.loamx_place_growths.restype = C.c_uint64
+        self._c = _cfg(PlaceConfig, "loamx_place_default_config", n_rings=n_rings, n_sectors=n_sectors, max_range=max_range,
+                       min_range=min_range, height_offset=height_offset, n_candidates=n_candidates, exclude_recent=exclude_recent,
+                       max_entries=max_entries, initial_entries=initial_entries, device=device)
+        self.n_rings, self.n_sectors = n_rings, n_sectors
+        self.h = C.c_void_p(L.loamx_place_create(C.byref(self._c)))
+        if not self.h:
+            raise LoamxError(E_INVALID, L.loamx_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().loamx_place_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def __len__(self):
+        return int(lib().loamx_place_size(self.h))
+
+    @staticmethod
+    def _origin(origin):
+        o = np.ascontiguousarray(origin, np.float32)
+        assert o.shape == (3,)
+        return o
+
+    def add(self, points, origin=(0.0, 0.0, 0.0)) -> int:
+        """describe an (N, 4) / (N, 8) cloud about origin and store it; returns the new entry's id.  LoamxError E_CAPACITY when
+        max_entries would be passed (the database is then unchanged)"""
+        a = as_points(points)
+        c = cloud_of(a)
+        o = self._origin(origin)
+        i = C.c_uint32(0)
+        _check(lib().loamx_place_add(self.h, C.byref(c), o.ctypes.data_as(C.c_void_p), C.byref(i)))
+        return int(i.value)
+
+    def add_from(self, mapping):
+        """the registered full-resolution cloud of mapping's last process / process_linked: the new id, or None when it produced none"""
+        i = C.c_uint32(0)
+        rc = _check(lib().loamx_place_add_from_map(self.h, mapping.h, C.byref(i)))
+        return int(i.value) if rc == OK else None
+
+    def add_from_pipeline(self, pipeline, slot: int):
+        """the registered cloud of the slot-th stream registered in pipeline's last step: the new id, or None when it registered none"""
+        i = C.c_uint32(0)
+        rc = _check(lib().loamx_place_add_from_pipeline(self.h, pipeline.h, slot, C.byref(i)))
+        return int(i.value) if rc == OK else None
+
+    @staticmethod
+    def _matches(m, n):
+        return [(int(m[i].id), int(m[i].shift), np.float32(m[i].distance), np.float32(m[i].ring_key_distance)) for i in range(n)]
+
+    def query_entry(self, entry: int, n_results=5):
+        """the best earlier entries for a stored one (the configuration's exclude_recent): [(id, shift, distance, ring_key_distance)]"""
+        m = (PlaceMatch * PLACE_MAX_RESULTS)()
+        n = C.c_uint32(0)
+        _check(lib().loamx_place_query_entry(self.h, C.c_uint32(entry), m, C.c_uint32(n_results), C.byref(n)))
+        return self._matches(m, n.value)
+
+    def query(self, points, origin=(0.0, 0.0, 0.0), exclude_recent=0, n_results=5):
+        """the best entries for a cloud that is not stored (exclude_recent 0: every entry is a candidate)"""
+        a = as_points(points)
+        c = cloud_of(a)
+        o = self._origin(origin)
+        m = (PlaceMatch * PLACE_MAX_RESULTS)()
+        n = C.c_uint32(0)
+        _check(lib().loamx_place_query(self.h, C.byref(c), o.ctypes.data_as(C.c_void_p), C.c_uint32(exclude_recent), m, C.c_uint32(n_results),
+                                       C.byref(n)))
+        return self._matches(m, n.value)
+
+    def yaw_hint(self, shift: int) -> float:
+        return float(shift) * 2.0 * np.pi / self.n_sectors
+
+    def descriptor(self, entry: int):
+        """(desc (R, S), ring_key (R,)) float32 of a stored entry"""
+        d = np.zeros((self.n_rings, self.n_sectors), np.float32)
+        k = np.zeros(self.n_rings, np.float32)
+        _check(lib().loamx_place_get_descriptor(self.h, C.c_uint32(entry), d.ctypes.data_as(C.c_void_p), k.ctypes.data_as(C.c_void_p)))
+        return d, k
+
+    def save(self, path: str):
+        _check(lib().loamx_place_save(self.h, os.fsencode(path)))
+
+    def load(self, path: str):
+        _check(lib().loamx_place_load(self.h, os.fsencode(path)))
+
+    def reset(self):
+        _check(lib().loamx_place_reset(self.h))
+
+    @property
+    def growths(self) -> int:
+        """test hook: how often the table of entries has doubled"""
+        return int(lib().loamx_place_growths(self.h))
+
+
 def dist_shard_of(rank: int, world: int, batch: int):
     b, e = C.c_uint32(0), C.c_uint32(0)
     _check(lib().loamx_dist_shard_of(rank, world, batch, C.byref(b), C.byref(e)))
