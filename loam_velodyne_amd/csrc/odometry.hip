@@ -14,6 +14,7 @@
 //                  the de-skew chain rule, J^T J / J^T r reduced with wave shuffles (double accumulators), thread 0:
 //                  6x6 pivoted QR solve, degeneracy projector, update, convergence test.
 #include "odometry.hpp"
+#include "odom_schedule.hpp"
 #include "pinned_copy.hpp"
 #include <chrono>
 #include <cstring>
@@ -1045,108 +1046,133 @@ ToEndParams odom_to_end_params(const OdomStream& S, float scan_period, bool enab
   return P;
 }
 
+// what the stages of one process() call share
+struct OdometryBatch::Pass {
+  const OdomInput* in;
+  int* rc;
+  uint32_t ns, K;
+  std::vector<OdomInput> in_late;   // (late: the caller's inputs, the less-flat cloud empty until resolve_late_())
+  bool late_pending = false, patch_pending = false;   // patch: the offsets again, now complete — with the next correspondence launch, or by a copy in front of the tail
+  uint32_t n_corner_all = 0, n_all = 0;               // (late: n_all without the less-flat cloud until resolve_late_())
+  const float4 *src_c = nullptr, *src_s = nullptr;   // contiguous inputs (the feature extractor's layout) are not staged at all: the re-projection at the tail reads them
+  std::vector<uint32_t> active;                       // the streams that optimise this sweep, and the most features any of them brings
+  uint32_t max_feat = 0, max_sharp = 0, max_flat = 0;
+  LtCall* lt = nullptr;                               // launch timing: this call's slot (a call whose slot is still in flight goes untimed)
+};
+
 void OdometryBatch::process(const OdomInput* in, int* rc, bool defer_tail) {
   TraceRange trace_range("loamx:odometry");
   LX_HIP(hipSetDevice(device_));
-  const uint32_t ns = n_streams(), K = 2 * ns;
   if (up_pending_) {   // the previous call's uploads read the pinned staging buffers this call is about to rewrite (they finished long ago:
     LX_HIP(hipEventSynchronize(ev_up_));   // they precede its iterations); the device-side tail of that call needs no waiting for — same stream
     up_pending_ = false;
   }
+  Pass p{in, rc, n_streams(), 2 * n_streams()};
+  stage_clouds_(p);
+  build_problems_(p);
+  upload_(p);
+  launch_pairs_(p);
+  enqueue_tail_(p);    // right behind the iterations; the host only waits for the poses
+  if (!p.active.empty()) collect_(p);
+  integrate_poses_(p);
+  if (!defer_tail) {   // (a deferring caller orders its consumers behind tail_event() instead of blocking the host here)
+    LX_HIP(hipStreamSynchronize(st_));
+    tail_pending_ = false;
+  }
+}
+
+// the current less-sharp / less-flat clouds of all streams and their offsets (the clouds are re-projected in place later)
+void OdometryBatch::stage_clouds_(Pass& p) {
+  const uint32_t ns = p.ns;
   // A single-stream caller may hand the less-flat cloud over LATE (late_less_flat, process_linked): the iterations read the sharp / flat
   // features and the previous sweep's clouds only; the less-flat cloud of THIS sweep is first read by the tail (re-projection, index of
   // the "last" clouds).  Its producer — the per-ring voxel grid of the extraction, ~50 us on a stream of its own — then runs beside the
   // first launch pair instead of in front of it.  The callback is called once, before the tail is enqueued, and blocks until the cloud
   // and its size are known; until then the cloud counts as empty (offsets, staging) and the buffers are sized with late_bound.
-  const bool late = ns == 1 && (bool)late_less_flat;
-  std::vector<OdomInput> in_late;
-  if (late) {
-    in_late.assign(in, in + ns);
-    in_late[0].less_flat = nullptr; in_late[0].n_less_flat = 0;
-    in = in_late.data();
+  p.late_pending = ns == 1 && (bool)late_less_flat;
+  if (p.late_pending) {
+    p.in_late.assign(p.in, p.in + ns);
+    p.in_late[0].less_flat = nullptr; p.in_late[0].n_less_flat = 0;
+    p.in = p.in_late.data();
   }
-  // ---- stage the current less-sharp / less-flat clouds of all streams (they are re-projected in place later)
+  const OdomInput* in = p.in;
   for (uint32_t s = 0; s < ns; s++) {
     h_cur_off_[s + 1] = h_cur_off_[s] + in[s].n_less_sharp;
     if (s > 0) LX_REQUIRE(in[s].less_sharp == in[s - 1].less_sharp + in[s - 1].n_less_sharp || in[s].n_less_sharp == 0 || in[s - 1].n_less_sharp == 0,
                           "less_sharp clouds of the streams must be contiguous");
   }
   for (uint32_t s = 0; s < ns; s++) h_cur_off_[ns + s + 1] = h_cur_off_[ns + s] + in[s].n_less_flat;
-  const uint32_t n_corner_all = h_cur_off_[ns];
-  uint32_t n_all = h_cur_off_[K];   // (late: without the less-flat cloud until resolve_late())
-  cur_.reserve((size_t)n_all + (late ? late_bound : 0u) + 1);
+  const uint32_t n_corner_all = p.n_corner_all = h_cur_off_[ns], n_all = p.n_all = h_cur_off_[p.K];
+  cur_.reserve((size_t)n_all + (p.late_pending ? late_bound : 0u) + 1);
   // per-type bulk copies when the inputs are contiguous, else per stream
   bool contig_c = true, contig_s = true;
   for (uint32_t s = 1; s < ns; s++) {
     contig_c = contig_c && in[s].less_sharp == in[s - 1].less_sharp + in[s - 1].n_less_sharp;
     contig_s = contig_s && in[s].less_flat == in[s - 1].less_flat + in[s - 1].n_less_flat;
   }
-  // contiguous inputs (the feature extractor's layout) are not staged at all: the re-projection at the tail reads them
-  const bool fused_stage = contig_c && contig_s;
-  const float4* src_c = fused_stage ? in[0].less_sharp : nullptr;
-  const float4* src_s = fused_stage ? in[0].less_flat : nullptr;
-  bool late_pending = late, patch_pending = false;
-  auto resolve_late = [&]() {
-    if (!late_pending) return;
-    late_pending = false;
-    const float4* p = nullptr;
-    uint32_t n = 0;
-    late_less_flat(p, n);
-    LX_REQUIRE(n <= late_bound, "internal: the late less-flat cloud is larger than its announced bound");
-    in_late[0].less_flat = p; in_late[0].n_less_flat = n;
-    h_cur_off_[ns + 1] = h_cur_off_[ns] + n;
-    n_all = h_cur_off_[K];
-    src_s = p;   // (ns == 1: contiguous by construction, the re-projection reads the cloud where it lies)
-    patch_pending = true;   // the offsets again, now complete: with the next correspondence launch, or by a copy in front of the tail
-  };
-  auto flush_patch = [&]() {
-    if (!patch_pending) return;
-    patch_pending = false;
-    h_off_late_.reserve(K + 1);
-    memcpy(h_off_late_.p, h_cur_off_.data(), sizeof(uint32_t) * (K + 1));
-    LX_HIP(hipMemcpyAsync(d_cur_off_.p, h_off_late_.p, sizeof(uint32_t) * (K + 1), hipMemcpyHostToDevice, st_));
-    LX_HIP(hipEventRecord(ev_up_, st_));   // (the next call waits for this copy too before it rewrites the pinned blocks)
-  };
-  if (fused_stage) {
-  } else if (contig_c) {
+  if (contig_c && contig_s) { p.src_c = in[0].less_sharp; p.src_s = in[0].less_flat; return; }
+  if (contig_c) {
     if (n_corner_all) LX_HIP(hipMemcpyAsync(cur_.p, in[0].less_sharp, sizeof(float4) * n_corner_all, hipMemcpyDeviceToDevice, st_));
   } else {
     for (uint32_t s = 0; s < ns; s++)
       if (in[s].n_less_sharp) LX_HIP(hipMemcpyAsync(cur_.p + h_cur_off_[s], in[s].less_sharp, sizeof(float4) * in[s].n_less_sharp, hipMemcpyDeviceToDevice, st_));
   }
-  if (fused_stage) {
-  } else if (contig_s) {
+  if (contig_s) {
     if (n_all > n_corner_all) LX_HIP(hipMemcpyAsync(cur_.p + n_corner_all, in[0].less_flat, sizeof(float4) * (n_all - n_corner_all), hipMemcpyDeviceToDevice, st_));
   } else {
     for (uint32_t s = 0; s < ns; s++)
       if (in[s].n_less_flat) LX_HIP(hipMemcpyAsync(cur_.p + h_cur_off_[ns + s], in[s].less_flat, sizeof(float4) * in[s].n_less_flat, hipMemcpyDeviceToDevice, st_));
   }
+}
 
-  // ---- problems of the streams that optimise this sweep
+// the late less-flat cloud, asked for once: by the first caller that can afford the wait or needs the cloud
+void OdometryBatch::resolve_late_(Pass& p) {
+  if (!p.late_pending) return;
+  p.late_pending = false;
+  const float4* pts = nullptr;
+  uint32_t n = 0;
+  late_less_flat(pts, n);
+  LX_REQUIRE(n <= late_bound, "internal: the late less-flat cloud is larger than its announced bound");
+  p.in_late[0].less_flat = pts; p.in_late[0].n_less_flat = n;
+  h_cur_off_[p.ns + 1] = h_cur_off_[p.ns] + n;
+  p.n_all = h_cur_off_[p.K];
+  p.src_s = pts;   // (ns == 1: contiguous by construction, the re-projection reads the cloud where it lies)
+  p.patch_pending = true;
+}
+// the completed offsets by a copy (no correspondence launch took them along)
+void OdometryBatch::flush_patch_(Pass& p) {
+  if (!p.patch_pending) return;
+  p.patch_pending = false;
+  h_off_late_.reserve(p.K + 1);
+  memcpy(h_off_late_.p, h_cur_off_.data(), sizeof(uint32_t) * (p.K + 1));
+  LX_HIP(hipMemcpyAsync(d_cur_off_.p, h_off_late_.p, sizeof(uint32_t) * (p.K + 1), hipMemcpyHostToDevice, st_));
+  LX_HIP(hipEventRecord(ev_up_, st_));   // (the next call waits for this copy too before it rewrites the pinned blocks)
+}
+
+// problems of the streams that optimise this sweep
+void OdometryBatch::build_problems_(Pass& p) {
+  const uint32_t ns = p.ns;
   xchg_epoch_ = xchg_epoch_ % 0xffffffu + 1u;   // (the records of a stream keep its position among the active ones only by accident: the tag, not the place, says whose they are)
-  std::vector<uint32_t> active;
-  uint32_t max_feat = 0, max_sharp = 0, max_flat = 0, ind_total = 0;
   std::vector<uint32_t> ind_off(ns + 1, 0);
-  for (uint32_t s = 0; s < ns; s++) ind_off[s + 1] = ind_off[s] + 5 * (in[s].n_sharp + in[s].n_flat) + 5;
-  ind_total = ind_off[ns];
-  ind_.reserve(ind_total + 8);
+  for (uint32_t s = 0; s < ns; s++) ind_off[s + 1] = ind_off[s] + 5 * (p.in[s].n_sharp + p.in[s].n_flat) + 5;
+  ind_.reserve(ind_off[ns] + 8);
   for (uint32_t s = 0; s < ns; s++) {
     OdomStream& S = *streams_[s];
-    const OdomInput& I = in[s];
+    const OdomInput& I = p.in[s];
     if (!S.inited) {   // :198-211: only stash the clouds and seed transformSum with the IMU start angles
       S.transform_sum.rot_x = HAngle(S.transform_sum.rot_x.r + S.imu_pitch_start.r);
       S.transform_sum.rot_z = HAngle(S.transform_sum.rot_z.r + S.imu_roll_start.r);
-      rc[s] = LOAMX_SKIPPED;
+      p.rc[s] = LOAMX_SKIPPED;
       continue;
     }
-    rc[s] = LOAMX_OK;
+    p.rc[s] = LOAMX_OK;
     S.frame++;
     S.transform.pos.x -= S.imu_velo.x * params.scan_period;
     S.transform.pos.y -= S.imu_velo.y * params.scan_period;
     S.transform.pos.z -= S.imu_velo.z * params.scan_period;
     S.stats = {0, 0, (int)S.frame, 0};
     if (S.n_last_corner > 10 && S.n_last_surf > 100) {
-      OdomProblem& pb = h_prob_.p[active.size()];
+      OdomProblem& pb = h_prob_.p[p.active.size()];
       pb.sharp = I.sharp; pb.n_sharp = I.n_sharp;
       pb.flat = I.flat; pb.n_flat = I.n_flat;
       pb.last_corner = last_.p + h_last_off_[s]; pb.n_last_corner = S.n_last_corner;
@@ -1162,248 +1188,228 @@ void OdometryBatch::process(const OdomInput* in, int* rc, bool defer_tail) {
       pb.ticket = 0;
       pb.xchg_epoch = xchg_epoch_;
       pb.stream_id = (int)s;
-      pb.host_mirror = h_mirror_.p + active.size();
+      pb.host_mirror = h_mirror_.p + p.active.size();
       pb.te_out = te_.p + s;
-      pb.part = part_.p + (size_t)active.size() * OD_PART_STRIDE;
+      pb.part = part_.p + (size_t)p.active.size() * OD_PART_STRIDE;
       pb.err_word = h_err_.p;
       pb.rf_corner = rf_.p + (size_t)s * OD_RF_N;
       pb.rf_surf = rf_.p + (size_t)(ns + s) * OD_RF_N;
       pb.rf_epoch = rf_epoch_;   // the table the previous call's re-projection left behind
-      max_feat = std::max(max_feat, I.n_sharp + I.n_flat);
-      max_sharp = std::max(max_sharp, I.n_sharp);
-      max_flat = std::max(max_flat, I.n_flat);
-      active.push_back(s);
+      p.max_feat = std::max(p.max_feat, I.n_sharp + I.n_flat);
+      p.max_sharp = std::max(p.max_sharp, I.n_sharp);
+      p.max_flat = std::max(p.max_flat, I.n_flat);
+      p.active.push_back(s);
     }
   }
-  const uint32_t na = (uint32_t)active.size();
-  if (max_feat > 32 * OD_THREADS) throw Error(LOAMX_E_CAPACITY, "more than 8192 sharp+flat features in one sweep");
-  // ---- everything the device needs for the whole sweep goes up first: problems, cloud offsets, re-projection
-  // parameters (those of the optimising streams are completed on the device, k_te_patch)
-  for (uint32_t s = 0; s < ns; s++) h_te_.p[s] = to_end_params(s, rc[s] == LOAMX_OK);   // a first sweep is stored as it came (:200-201)
-  memcpy(h_off_pin_.p, h_cur_off_.data(), sizeof(uint32_t) * (K + 1));
+  if (p.max_feat > 32 * OD_THREADS) throw Error(LOAMX_E_CAPACITY, "more than 8192 sharp+flat features in one sweep");
+}
+
+// everything the device needs for the whole sweep goes up first: problems, cloud offsets, re-projection parameters (those of the
+// optimising streams are completed on the device, k_te_patch)
+void OdometryBatch::upload_(Pass& p) {
+  for (uint32_t s = 0; s < p.ns; s++) h_te_.p[s] = to_end_params(s, p.rc[s] == LOAMX_OK);   // a first sweep is stored as it came (:200-201)
+  memcpy(h_off_pin_.p, h_cur_off_.data(), sizeof(uint32_t) * (p.K + 1));
   // (measured, round 6: fetching this block by kernel instead — pinned_copy.hpp — is no faster: 16.80 k against 16.93 k sweeps/s, profiles/r06_ab.md)
   LX_HIP(hipMemcpyAsync(up_dev_.p, up_host_.p, up_bytes_, hipMemcpyHostToDevice, st_));   // problems + re-projection parameters + offsets
-  index_.prepare(K);   // bounding-box accumulators of the NEXT index (a launch only the first time: every build leaves them reset)
-  const bool index_prepared = true;
+  index_.prepare(p.K);   // bounding-box accumulators of the NEXT index (a launch only the first time: every build leaves them reset)
   if (!ev_up_) LX_HIP(hipEventCreateWithFlags(&ev_up_, hipEventDisableTiming));
   LX_HIP(hipEventRecord(ev_up_, st_));
   up_pending_ = true;
-  LtCall* lt = nullptr;
-  if (launch_timing_.load(std::memory_order_relaxed) && na && max_feat) {
+}
+
+// launch geometry of a pair.  k_odom_corr_grid: a wave per feature, four to a workgroup; workgroup x serves XCD x % 8, which takes that
+// eighth of every stream's sharp and flat lists
+static dim3 odom_corr_grid(uint32_t max_sharp, uint32_t max_flat, uint32_t na) {
+  return dim3(8 * (((max_sharp + 7) / 8 + (max_flat + 7) / 8 + 3) / 4), na);
+}
+// k_odom_lm: nb workgroups per stream, one or two features per thread, and at most `chunk` streams per launch
+OdometryBatch::LmGeometry OdometryBatch::lm_geometry_(uint32_t max_feat) {
+#ifdef OD_LM_HALF_WGS   // (measurement: half as many workgroups per stream, two features per thread — profiles/r05_ab.md section 2)
+  const uint32_t nb = std::min<uint32_t>(16u, std::max<uint32_t>(1u, (max_feat + 2 * OD_THREADS - 1) / (2 * OD_THREADS)));
+#else
+  const uint32_t nb = std::min<uint32_t>(16u, (max_feat + OD_THREADS - 1) / OD_THREADS);
+#endif
+  // k_odom_lm's workgroups of one stream spin on each other: everything a launch puts on the device must be resident
+  // at once.  The launch is cut into chunks of streams that fill at most half of what the device can hold (occupancy x
+  // CUs, queried once) — the registration and feature kernels of the other HIP streams share the CUs.
+  const bool two = max_feat > nb * OD_THREADS;
+  if (!lm_slots_[two]) {
+    int per_cu = 0;
+    if (two) LX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_odom_lm<2>, OD_THREADS, 0));
+    else LX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_odom_lm<1>, OD_THREADS, 0));
+    hipDeviceProp_t prop;
+    LX_HIP(hipGetDeviceProperties(&prop, device_));
+    lm_slots_[two] = (uint32_t)std::max(per_cu, 1) * (uint32_t)std::max(prop.multiProcessorCount, 1);
+  }
+  return {nb, two, std::max<uint32_t>(1u, (lm_slots_[two] / 2) / nb)};
+}
+
+// the two halves of launch pair k, enqueued apart (odom_schedule.hpp)
+void OdometryBatch::enqueue_corr_(Pass& p, int k) {
+  LtCall* lt = p.lt;
+  const int lk = lt && k < LT_MAXP ? k : -1;
+  if (lk >= 0) {
+    for (int e = 0; e < 3; e++) if (!lt->ev[3 * lk + e]) LX_HIP(hipEventCreate(&lt->ev[3 * lk + e]));
+    LX_HIP(hipEventRecord(lt->ev[3 * lk], st_));
+  }
+  uint32_t* pd = nullptr;
+  uint4 pv = make_uint4(0u, 0u, 0u, 0u);
+  if (p.patch_pending) { p.patch_pending = false; pd = d_cur_off_.p; pv = make_uint4(h_cur_off_[0], h_cur_off_[1], h_cur_off_[2], 0u); }   // (ns == 1: K + 1 = 3 words)
+  hipLaunchKernelGGL(k_odom_corr_grid, odom_corr_grid(p.max_sharp, p.max_flat, (uint32_t)p.active.size()), dim3(256), 0, st_, prob_.p, params, pd, pv);
+  if (lk >= 0) LX_HIP(hipEventRecord(lt->ev[3 * lk + 1], st_));
+}
+void OdometryBatch::enqueue_lm_(Pass& p, int k) {
+  LtCall* lt = p.lt;
+  const uint32_t na = (uint32_t)p.active.size();
+  const int it0 = 5 * k;
+  const int nit = std::min(5, params.max_iterations - it0);
+  const int lk = lt && k < LT_MAXP ? k : -1;
+  const LmGeometry g = lm_geometry_(p.max_feat);
+  for (uint32_t a0 = 0; a0 < na; a0 += g.chunk) {
+    const uint32_t nc = std::min(g.chunk, na - a0);
+    if (g.two) hipLaunchKernelGGL(k_odom_lm<2>, dim3(g.nb, nc), dim3(OD_THREADS), 0, st_, prob_.p + a0, params, it0, nit);
+    else hipLaunchKernelGGL(k_odom_lm<1>, dim3(g.nb, nc), dim3(OD_THREADS), 0, st_, prob_.p + a0, params, it0, nit);
+  }
+  if (lk >= 0) { LX_HIP(hipEventRecord(lt->ev[3 * lk + 2], st_)); lt->pairs = lk + 1; }
+}
+
+// what odom_schedule_pairs() drives: the launches of this pass, and the pinned mirror's view of how far the streams have come
+struct OdometryBatch::PairOps {
+  OdometryBatch& o; Pass& p;
+  void corr(int k) { o.enqueue_corr_(p, k); }
+  void lm(int k) { o.enqueue_lm_(p, k); }
+  void after_first() { o.resolve_late_(p); }   // (`lag`: the device has a launch pair and a half in its queue: the wait for the less-flat cloud costs the chain nothing)
+  bool behind(int want) const {                // some stream has not converged and is short of `want` iterations
+    const volatile OdomProblem* hm = o.h_mirror_.p;
+    for (size_t a = 0; a < p.active.size(); a++) if (hm[a].done == 0 && hm[a].stats.iterations < want) return true;
+    return false;
+  }
+  bool converged() const { return !behind(o.params.max_iterations); }
+  bool wait_settled(int k) const {             // false: the mirror did not answer in time
+    const int want = std::min(5 * (k + 1), o.params.max_iterations);
+    const auto t_in = std::chrono::steady_clock::now();
+    for (unsigned spins = 0; behind(want);) {
+      if ((++spins & 255u) == 0u && std::chrono::steady_clock::now() - t_in > std::chrono::milliseconds(20)) return false;
+      __builtin_ia32_pause();
+    }
+    return true;
+  }
+};
+
+// launch pairs (correspondences + up to five iterations) as the schedule asks for them, then the pose event
+void OdometryBatch::launch_pairs_(Pass& p) {
+  const uint32_t na = (uint32_t)p.active.size();
+  if (launch_timing_.load(std::memory_order_relaxed) && na && p.max_feat) {
     std::lock_guard<std::mutex> lk(lt_mu_);
     lt_resolve_();
     LtCall& c = lt_[lt_next_ % LT_RING];
-    if (!c.pending) { lt = &c; lt_next_++; c.pairs = 0; }   // (a call whose slot is still in flight goes untimed)
+    if (!c.pending) { p.lt = &c; lt_next_++; c.pairs = 0; }
   }
-  if (na) {
-    if (max_feat) {
-      // Launch pairs (correspondences + up to five iterations).  The reference leaves its loop when the stop test fires
-      // (BasicLaserOdometry.cpp:613-620); launches enqueued behind a sweep that has converged cost ~10 us each, so they are enqueued as
-      // they turn out to be needed: the host reads from the pinned mirror (k_odom_lm writes a stream's state there at the end of every
-      // launch) whether a pair left any stream unconverged.  Round 5 enqueued all five pairs up front (1.6 empty pairs per pass on
-      // average).  Result-neutral by construction: a launch that is not enqueued would have returned at its first instruction (pb.done /
-      // the iteration bound).  LOAMX_ODOM_PAIRS: `lag` (default) speculates on ONE launch (the next pair's correspondences), `lag2` on one
-      // PAIR (round 6's first form), `exact` on nothing (a host round trip in front of every further pair and of the tail), `all` = round 5.
-      const int pair_mode = [] { const char* e = getenv("LOAMX_ODOM_PAIRS"); return !e ? 1 : !strcmp(e, "all") ? 0 : !strcmp(e, "exact") ? 2 : !strcmp(e, "lag2") ? 3 : 1; }();
-      const int maxp = (params.max_iterations + 4) / 5;
-      for (uint32_t a = 0; a < na; a++) { h_mirror_.p[a].done = 0; h_mirror_.p[a].stats.iterations = 0; }   // (the previous sweep's launches finished before its poses were read)
-      // the two halves of a pair, enqueued apart: `lag` speculates on the correspondence launch only
-      auto enqueue_corr = [&](int k) {
-        const int lk = lt && k < LT_MAXP ? k : -1;
-        if (lk >= 0) {
-          for (int e = 0; e < 3; e++) if (!lt->ev[3 * lk + e]) LX_HIP(hipEventCreate(&lt->ev[3 * lk + e]));
-          LX_HIP(hipEventRecord(lt->ev[3 * lk], st_));
-        }
-        uint32_t* pd = nullptr;
-        uint4 pv = make_uint4(0u, 0u, 0u, 0u);
-        if (patch_pending) { patch_pending = false; pd = d_cur_off_.p; pv = make_uint4(h_cur_off_[0], h_cur_off_[1], h_cur_off_[2], 0u); }   // (ns == 1: K + 1 = 3 words)
-        hipLaunchKernelGGL(k_odom_corr_grid, dim3(8 * (((max_sharp + 7) / 8 + (max_flat + 7) / 8 + 3) / 4), na), dim3(256), 0, st_, prob_.p, params, pd, pv);
-        if (lk >= 0) LX_HIP(hipEventRecord(lt->ev[3 * lk + 1], st_));
-      };
-      auto enqueue_lm = [&](int k) {
-        const int it0 = 5 * k;
-        const int nit = std::min(5, params.max_iterations - it0);
-        const int lk = lt && k < LT_MAXP ? k : -1;
-#ifdef OD_LM_HALF_WGS   // (measurement: half as many workgroups per stream, two features per thread — profiles/r05_ab.md section 2)
-        const uint32_t nb = std::min<uint32_t>(16u, std::max<uint32_t>(1u, (max_feat + 2 * OD_THREADS - 1) / (2 * OD_THREADS)));
-#else
-        const uint32_t nb = std::min<uint32_t>(16u, (max_feat + OD_THREADS - 1) / OD_THREADS);
-#endif
-        // k_odom_lm's workgroups of one stream spin on each other: everything a launch puts on the device must be resident
-        // at once.  The launch is cut into chunks of streams that fill at most half of what the device can hold (occupancy x
-        // CUs, queried once) — the registration and feature kernels of the other HIP streams share the CUs.
-        const bool two = max_feat > nb * OD_THREADS;
-        if (!lm_slots_[two]) {
-          int per_cu = 0;
-          if (two) LX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_odom_lm<2>, OD_THREADS, 0));
-          else LX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_odom_lm<1>, OD_THREADS, 0));
-          hipDeviceProp_t prop;
-          LX_HIP(hipGetDeviceProperties(&prop, device_));
-          lm_slots_[two] = (uint32_t)std::max(per_cu, 1) * (uint32_t)std::max(prop.multiProcessorCount, 1);
-        }
-        const uint32_t chunk = std::max<uint32_t>(1u, (lm_slots_[two] / 2) / nb);
-        for (uint32_t a0 = 0; a0 < na; a0 += chunk) {
-          const uint32_t nc = std::min(chunk, na - a0);
-          if (two) hipLaunchKernelGGL(k_odom_lm<2>, dim3(nb, nc), dim3(OD_THREADS), 0, st_, prob_.p + a0, params, it0, nit);
-          else hipLaunchKernelGGL(k_odom_lm<1>, dim3(nb, nc), dim3(OD_THREADS), 0, st_, prob_.p + a0, params, it0, nit);
-        }
-        if (lk >= 0) { LX_HIP(hipEventRecord(lt->ev[3 * lk + 2], st_)); lt->pairs = lk + 1; }
-      };
-      auto enqueue_pair = [&](int it0) { enqueue_corr(it0 / 5); enqueue_lm(it0 / 5); };
-      const volatile OdomProblem* hm = h_mirror_.p;
-      auto settled = [&](int k) {     // every stream is through launch pair k (or had converged before it)
-        const int want = std::min(5 * (k + 1), params.max_iterations);
-        for (uint32_t a = 0; a < na; a++) if (hm[a].done == 0 && hm[a].stats.iterations < want) return false;
-        return true;
-      };
-      auto converged = [&]() {        // no stream has anything left to iterate
-        for (uint32_t a = 0; a < na; a++) if (hm[a].done == 0 && hm[a].stats.iterations < params.max_iterations) return false;
-        return true;
-      };
-      auto wait_settled = [&](int k) {   // false: the mirror did not answer in time (the caller then enqueues the rest unconditionally)
-        const auto t_in = std::chrono::steady_clock::now();
-        for (unsigned spins = 0; !settled(k);) {
-          if ((++spins & 255u) == 0u && std::chrono::steady_clock::now() - t_in > std::chrono::milliseconds(20)) return false;
-          __builtin_ia32_pause();
-        }
-        return true;
-      };
-      int enq = 0;                    // launch pairs whose iterations have been enqueued
-      if (pair_mode == 1) {
-        // `lag` (default): pair 0, then only the NEXT pair's correspondence launch ahead of need.  When pair k's iterations have ended the
-        // host knows whether pair k + 1 is needed: if so it enqueues its iterations (and the correspondence launch of pair k + 2) while
-        // the correspondence launch of k + 1 runs — the queue never runs dry; if not, that one launch is the pass's only empty one.
-        enqueue_corr(0);
-        enqueue_lm(0);
-        enq = 1;
-        if (maxp > 1) enqueue_corr(1);
-        resolve_late();   // (the device has a launch pair and a half in its queue: the wait for the less-flat cloud costs the chain nothing)
-        while (enq < maxp) {
-          if (!wait_settled(enq - 1)) {   // blind: everything that is left, unconditionally (always correct)
-            enqueue_lm(enq);
-            for (enq++; enq < maxp; enq++) enqueue_pair(5 * enq);
-            break;
-          }
-          if (converged()) break;
-          enqueue_lm(enq);
-          enq++;
-          if (enq < maxp) enqueue_corr(enq);
-        }
-      } else {
-      const int first = pair_mode == 0 ? maxp : std::min(maxp, pair_mode == 2 ? std::max(1, pred_pairs_) : 2);
-      for (; enq < first; enq++) enqueue_pair(5 * enq);
-      resolve_late();
-      bool blind = false;             // the mirror did not answer in time: enqueue the rest unconditionally (always correct)
-      while (enq < maxp) {
-        const int watch = pair_mode == 2 ? enq - 1 : enq - 2;
-        if (!blind && watch >= 0) {
-          if (!wait_settled(watch)) blind = true;
-          if (!blind && converged()) break;
-        }
-        enqueue_pair(5 * enq);
-        enq++;
-      }
-      }
-      pairs_enqueued_ += (uint64_t)enq;
-      pair_calls_++;
-    }
-    if (!max_feat) LX_HIP(hipMemcpyAsync(h_mirror_.p, prob_.p, sizeof(OdomProblem) * na, hipMemcpyDeviceToHost, st_));   // (no launch wrote the mirror)
-    if (!ev_pose_) LX_HIP(hipEventCreateWithFlags(&ev_pose_, hipEventDisableTiming));
-    LX_HIP(hipEventRecord(ev_pose_, st_));
-    if (!max_feat) hipLaunchKernelGGL(k_te_patch, dim3((na + 63) / 64), dim3(64), 0, st_, prob_.p, na, te_.p);   // (otherwise k_odom_lm did it)
+  if (!na) return;
+  if (p.max_feat) {
+    const char* e = getenv("LOAMX_ODOM_PAIRS");
+    const OdomPairMode mode = !e ? OdomPairMode::Lag : !strcmp(e, "all") ? OdomPairMode::All : !strcmp(e, "exact") ? OdomPairMode::Exact : !strcmp(e, "lag2") ? OdomPairMode::Lag2 : OdomPairMode::Lag;
+    for (uint32_t a = 0; a < na; a++) { h_mirror_.p[a].done = 0; h_mirror_.p[a].stats.iterations = 0; }   // (the previous sweep's launches finished before its poses were read)
+    odom_schedule_pairs(PairOps{*this, p}, mode, (params.max_iterations + 4) / 5, pred_pairs_);
   }
-  // ---- re-project to the sweep end (:651-652), hand over as "last" clouds and rebuild their index (:654-664): enqueued
-  // right behind the iterations; the host only waits for the poses
+  if (!p.max_feat) LX_HIP(hipMemcpyAsync(h_mirror_.p, prob_.p, sizeof(OdomProblem) * na, hipMemcpyDeviceToHost, st_));   // (no launch wrote the mirror)
+  if (!ev_pose_) LX_HIP(hipEventCreateWithFlags(&ev_pose_, hipEventDisableTiming));
+  LX_HIP(hipEventRecord(ev_pose_, st_));
+  if (!p.max_feat) hipLaunchKernelGGL(k_te_patch, dim3((na + 63) / 64), dim3(64), 0, st_, prob_.p, na, te_.p);   // (otherwise k_odom_lm did it)
+}
+
+// re-project to the sweep end (:651-652), hand over as "last" clouds and rebuild their index (:654-664)
+void OdometryBatch::enqueue_tail_(Pass& p) {
   static const bool fuse_bounds = !(diag_env("LOAMX_BB_FUSED") && atoi(diag_env("LOAMX_BB_FUSED")) == 0);   // diagnostic: 0 = separate k_bb_bbox launch
-  resolve_late();   // (a sweep without iterations: the tail is the first reader)
-  flush_patch();    // (no correspondence launch took the completed offsets along)
-  if (n_all)
-  {
+  resolve_late_(p);   // (a sweep without iterations: the tail is the first reader)
+  flush_patch_(p);
+  if (p.n_all) {
     if (++rf_epoch_ > 255u) rf_epoch_ = 1u;   // entries of this re-projection carry the new epoch; the problems of the NEXT call name it
-    hipLaunchKernelGGL(k_transform_to_end_batch, dim3((n_all + 255) / 256), dim3(256), 0, st_, cur_.p, n_all, d_cur_off_.p, K, ns, te_.p, src_c,
-                       src_s, n_corner_all, fuse_bounds ? index_.d_bounds() : nullptr, rf_.p, rf_epoch_);
+    hipLaunchKernelGGL(k_transform_to_end_batch, dim3((p.n_all + 255) / 256), dim3(256), 0, st_, cur_.p, p.n_all, d_cur_off_.p, p.K, p.ns, te_.p, p.src_c,
+                       p.src_s, p.n_corner_all, fuse_bounds ? index_.d_bounds() : nullptr, rf_.p, rf_epoch_);
   }
   // rotating buffers: the clouds this call hands on stay untouched during the next keep_ calls (a registration reads them while the
   // odometry chain is already that many sweeps ahead — Pipeline)
   {
-    float4* p = cur_.p; size_t c = cur_.cap;
+    float4* q = cur_.p; size_t c = cur_.cap;
     DevBuf<float4>& oldest = older_[keep_ - 2];
     cur_.p = oldest.p; cur_.cap = oldest.cap;
     for (int k = keep_ - 2; k > 0; k--) { older_[k].p = older_[k - 1].p; older_[k].cap = older_[k - 1].cap; }
     older_[0].p = last_.p; older_[0].cap = last_.cap;
-    last_.p = p; last_.cap = c;
+    last_.p = q; last_.cap = c;
   }
   h_last_off_ = h_cur_off_;
-  index_.build(last_.p, h_last_off_.data(), K, d_cur_off_.p, index_prepared, /*bounds_done=*/fuse_bounds && n_all > 0);
+  index_.build(last_.p, h_last_off_.data(), p.K, d_cur_off_.p, /*prepared=*/true, /*bounds_done=*/fuse_bounds && p.n_all > 0);
   if (!ev_tail_) LX_HIP(hipEventCreateWithFlags(&ev_tail_, hipEventDisableTiming));
   LX_HIP(hipEventRecord(ev_tail_, st_));
   tail_pending_ = true;
-  if (na) {
-    wait_event(ev_pose_);
-    if (*(volatile uint32_t*)h_err_.p) {   // k_odom_lm's exchange timed out (its workgroups were not all resident)
-      *h_err_.p = 0u;
-      throw Error(LOAMX_E_HIP, "odometry: the exchange between a stream's k_odom_lm workgroups timed out (not all of them resident)");
-    }
+}
+
+// diagnostic builds (-DLOAMX_PROF_CORR / -DLOAMX_PROF_LM): the timestamps the pass's last launches left behind
+void OdometryBatch::prof_print_() {
 #ifdef LOAMX_PROF_CORR
-    {
-      unsigned long long ts[3][16];
-      LX_HIP(hipMemcpyFromSymbol(ts, HIP_SYMBOL(g_corr_ts), sizeof(ts)));
-      for (int q = 0; q < 3; q++)
-        fprintf(stderr, "[corr ts %s, us since entry] feature+trig %.2f block table %.2f nn1 %.2f decision %.2f block windows %.2f walk %.2f end %.2f | block %llu pts, via block %llu, closest %lld cscan %lld\n",
-                q == 0 ? "corner" : q == 1 ? "flat mid" : "flat last", (ts[q][1] - ts[q][0]) * 0.01, (ts[q][2] - ts[q][0]) * 0.01, (ts[q][3] - ts[q][0]) * 0.01,
-                (ts[q][4] - ts[q][0]) * 0.01, (ts[q][5] - ts[q][0]) * 0.01, (ts[q][6] - ts[q][0]) * 0.01, (ts[q][7] - ts[q][0]) * 0.01, ts[q][8], ts[q][9],
-                (long long)ts[q][10], (long long)ts[q][11]);
-    }
+  unsigned long long ts[3][16];
+  LX_HIP(hipMemcpyFromSymbol(ts, HIP_SYMBOL(g_corr_ts), sizeof(ts)));
+  for (int q = 0; q < 3; q++)
+    fprintf(stderr, "[corr ts %s, us since entry] feature+trig %.2f block table %.2f nn1 %.2f decision %.2f block windows %.2f walk %.2f end %.2f | block %llu pts, via block %llu, closest %lld cscan %lld\n",
+            q == 0 ? "corner" : q == 1 ? "flat mid" : "flat last", (ts[q][1] - ts[q][0]) * 0.01, (ts[q][2] - ts[q][0]) * 0.01, (ts[q][3] - ts[q][0]) * 0.01,
+            (ts[q][4] - ts[q][0]) * 0.01, (ts[q][5] - ts[q][0]) * 0.01, (ts[q][6] - ts[q][0]) * 0.01, (ts[q][7] - ts[q][0]) * 0.01, ts[q][8], ts[q][9],
+            (long long)ts[q][10], (long long)ts[q][11]);
 #endif
 #ifdef LOAMX_PROF_LM
-    {
-      double ts[16];
-      LX_HIP(hipMemcpy(ts, part_.p + OD_PART_TS, sizeof(ts), hipMemcpyDeviceToHost));
-      fprintf(stderr, "[lm ts, 10ns ticks]");
-      for (int k = 1; k < 10; k++) fprintf(stderr, " %d:%+.0f", k, ts[k] - ts[0]);
-      fprintf(stderr, "\n");
-    }
+  double tl[16];
+  LX_HIP(hipMemcpy(tl, part_.p + OD_PART_TS, sizeof(tl), hipMemcpyDeviceToHost));
+  fprintf(stderr, "[lm ts, 10ns ticks]");
+  for (int k = 1; k < 10; k++) fprintf(stderr, " %d:%+.0f", k, tl[k] - tl[0]);
+  fprintf(stderr, "\n");
 #endif
-    {
-      int need = 1;
-      for (uint32_t a = 0; a < na; a++) need = std::max(need, (h_mirror_.p[a].stats.iterations + 4) / 5);
-      pred_pairs_ = need;   // (LOAMX_ODOM_PAIRS=exact: a stream that needs every iteration needs them for several sweeps in a row)
-    }
-    for (uint32_t a = 0; a < na; a++) {
-      OdomStream& S = *streams_[active[a]];
-      // _transform.rot_* = rad + x re-derives the cached sin/cos (:599-601)
-      S.transform.set(h_mirror_.p[a].transform);
-      S.stats.iterations = h_mirror_.p[a].stats.iterations;
-      S.stats.sel = h_mirror_.p[a].stats.sel;
-      S.stats.degenerate = h_mirror_.p[a].stats.degenerate;
-    }
-    if (lt) {   // what every timed launch did, now that the iteration counts are known
-      std::lock_guard<std::mutex> lk(lt_mu_);
-      for (int k = 0; k < lt->pairs; k++) {
-        lt->iters[k] = 0; lt->bytes[k] = 0; lt->feats[k] = 0;
-        for (uint32_t a = 0; a < na; a++) {
-          const int it = h_mirror_.p[a].stats.iterations - 5 * k;
-          if (it <= 0) continue;
-          const uint64_t nf = (uint64_t)in[active[a]].n_sharp + in[active[a]].n_flat;
-          lt->iters[k] = std::max(lt->iters[k], std::min(it, 5));
-          lt->bytes[k] += 48ull * nf;
-          lt->feats[k] += nf;
-        }
+}
+
+// wait for the poses and read them back from the mirror
+void OdometryBatch::collect_(Pass& p) {
+  const uint32_t na = (uint32_t)p.active.size();
+  wait_event(ev_pose_);
+  if (*(volatile uint32_t*)h_err_.p) {   // k_odom_lm's exchange timed out (its workgroups were not all resident)
+    *h_err_.p = 0u;
+    throw Error(LOAMX_E_HIP, "odometry: the exchange between a stream's k_odom_lm workgroups timed out (not all of them resident)");
+  }
+  prof_print_();
+  int need = 1;
+  for (uint32_t a = 0; a < na; a++) need = std::max(need, (h_mirror_.p[a].stats.iterations + 4) / 5);
+  pred_pairs_ = need;   // (LOAMX_ODOM_PAIRS=exact: a stream that needs every iteration needs them for several sweeps in a row)
+  for (uint32_t a = 0; a < na; a++) {
+    OdomStream& S = *streams_[p.active[a]];
+    // _transform.rot_* = rad + x re-derives the cached sin/cos (:599-601)
+    S.transform.set(h_mirror_.p[a].transform);
+    S.stats.iterations = h_mirror_.p[a].stats.iterations;
+    S.stats.sel = h_mirror_.p[a].stats.sel;
+    S.stats.degenerate = h_mirror_.p[a].stats.degenerate;
+  }
+  if (LtCall* lt = p.lt) {   // what every timed launch did, now that the iteration counts are known
+    std::lock_guard<std::mutex> lk(lt_mu_);
+    for (int k = 0; k < lt->pairs; k++) {
+      lt->iters[k] = 0; lt->bytes[k] = 0; lt->feats[k] = 0;
+      for (uint32_t a = 0; a < na; a++) {
+        const int it = h_mirror_.p[a].stats.iterations - 5 * k;
+        if (it <= 0) continue;
+        const uint64_t nf = (uint64_t)p.in[p.active[a]].n_sharp + p.in[p.active[a]].n_flat;
+        lt->iters[k] = std::max(lt->iters[k], std::min(it, 5));
+        lt->bytes[k] += 48ull * nf;
+        lt->feats[k] += nf;
       }
-      lt->pending = true;
     }
+    lt->pending = true;
   }
-  // ---- pose integration (:626-649)
-  for (uint32_t s = 0; s < ns; s++) {
+}
+
+// pose integration (:626-649)
+void OdometryBatch::integrate_poses_(const Pass& p) {
+  for (uint32_t s = 0; s < p.ns; s++) {
     OdomStream& S = *streams_[s];
-    if (rc[s] == LOAMX_OK) odom_integrate_pose(S);
+    if (p.rc[s] == LOAMX_OK) odom_integrate_pose(S);
     S.inited = true;
-    S.n_last_corner = in[s].n_less_sharp;
-    S.n_last_surf = in[s].n_less_flat;
-  }
-  if (!defer_tail) {   // (a deferring caller orders its consumers behind tail_event() instead of blocking the host here)
-    LX_HIP(hipStreamSynchronize(st_));
-    tail_pending_ = false;
+    S.n_last_corner = p.in[s].n_less_sharp;
+    S.n_last_surf = p.in[s].n_less_flat;
   }
 }
 

@@ -79,6 +79,8 @@ struct OdomStream {
   uint32_t n_last_corner = 0, n_last_surf = 0;
 };
 
+// process() is a list of stages (stage_clouds_ .. integrate_poses_ below) that share one Pass; WHICH launch pairs a pass enqueues, and
+// when, is odom_schedule.hpp's — host logic without HIP, pinned launch by launch in tests/test_odom_schedule.py.
 class OdometryBatch {
  public:
   OdometryBatch(int device, uint32_t n_streams, hipStream_t shared_stream = nullptr);
@@ -171,7 +173,6 @@ class OdometryBatch {
   bool link_valid_ = false;
   hipEvent_t ev_link_ = nullptr;
   int pred_pairs_ = 5;               // launch pairs the slowest stream of the previous sweep needed (LOAMX_ODOM_PAIRS=exact)
-  uint64_t pairs_enqueued_ = 0, pair_calls_ = 0;   // launch pairs enqueued / sweeps with iterations, since creation
   uint32_t lm_slots_[2] = {0, 0};   // workgroups of k_odom_lm<1> / <2> the device holds at once (occupancy x CUs)
   hipEvent_t ev_tail_ = nullptr, ev_pose_ = nullptr, ev_up_ = nullptr;
   bool tail_pending_ = false, up_pending_ = false;
@@ -192,7 +193,14 @@ class OdometryBatch {
   std::mutex lt_mu_;   // (the totals are read by the calling thread while a chain's worker thread is inside process())
   LaunchTotals lt_tot_;
   void lt_resolve_();
+  // one process() call: what its stages share, and the stages in the order they run (odometry.hip)
+  struct Pass;
+  struct PairOps;   // the launches and the mirror as odom_schedule_pairs() sees them
+  struct LmGeometry { uint32_t nb; bool two; uint32_t chunk; };
+  void stage_clouds_(Pass& p), build_problems_(Pass& p), upload_(Pass& p), launch_pairs_(Pass& p), enqueue_tail_(Pass& p), collect_(Pass& p);
+  void integrate_poses_(const Pass& p);
+  void resolve_late_(Pass& p), flush_patch_(Pass& p), enqueue_corr_(Pass& p, int k), enqueue_lm_(Pass& p, int k), prof_print_();
+  LmGeometry lm_geometry_(uint32_t max_feat);
 };
-
 
 }  // namespace loamx
