@@ -11,6 +11,7 @@
 #include <vector>
 #include <stdexcept>
 #include "../../include/loamx.h"
+#include "host_wait.hpp"
 #ifndef LOAMX_NO_ROCTX   // (make NO_ROCTX=1: a ROCm install without the rocprofiler SDK; the trace ranges become no-ops)
 #include <rocprofiler-sdk-roctx/roctx.h>
 #endif
@@ -200,28 +201,16 @@ inline const char* diag_env(const char*) { return nullptr; }
 // Wait for a stream by polling (hipStreamQuery) for up to `spin_ms` before falling back to hipStreamSynchronize.  The runtime's blocking
 // wait sleeps on an interrupt after a short spin; on the sequential-SLAM path — a wait every ~0.3 ms — one wake-up in a few hundred
 // arrived ~10 ms late on some hosts (one such call in a window of 100 sweeps is 15 % of the window: profiles/r06_ab.md section 8).
-inline void spin_sync(hipStream_t st, int spin_ms = 4) {
-  const auto t_in = std::chrono::steady_clock::now();
-  for (unsigned spins = 0;; spins++) {
-    const hipError_t e = hipStreamQuery(st);
-    if (e == hipSuccess) return;
-    if (e != hipErrorNotReady) { LX_HIP(e); }
-    if ((spins & 63u) == 63u && std::chrono::steady_clock::now() - t_in > std::chrono::milliseconds(spin_ms)) break;
-    __builtin_ia32_pause();
-  }
-  LX_HIP(hipStreamSynchronize(st));
+// (the clock is looked at on every 64th query: a query is a call into the runtime, not a load)
+inline bool query_done(hipError_t e) {
+  if (e != hipSuccess && e != hipErrorNotReady) LX_HIP(e);
+  return e == hipSuccess;
 }
-
+inline void spin_sync(hipStream_t st, int spin_ms = 4) {
+  if (!spin_until([&]() { return query_done(hipStreamQuery(st)); }, std::chrono::milliseconds(spin_ms), 64)) LX_HIP(hipStreamSynchronize(st));
+}
 inline void spin_event(hipEvent_t ev, int spin_ms = 4) {   // the same for an event
-  const auto t_in = std::chrono::steady_clock::now();
-  for (unsigned spins = 0;; spins++) {
-    const hipError_t e = hipEventQuery(ev);
-    if (e == hipSuccess) return;
-    if (e != hipErrorNotReady) { LX_HIP(e); }
-    if ((spins & 63u) == 63u && std::chrono::steady_clock::now() - t_in > std::chrono::milliseconds(spin_ms)) break;
-    __builtin_ia32_pause();
-  }
-  LX_HIP(hipEventSynchronize(ev));
+  if (!spin_until([&]() { return query_done(hipEventQuery(ev)); }, std::chrono::milliseconds(spin_ms), 64)) LX_HIP(hipEventSynchronize(ev));
 }
 
 // The steady-state waits of the chains (the odometry's pose event, the features' event in front of a pass, the registration's results):

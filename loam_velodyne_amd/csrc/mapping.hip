@@ -13,15 +13,10 @@
 #include "registration.hpp"
 #include "api_handles.h"
 #include "pinned_copy.hpp"
+#include "helper_thread.hpp"
 #include <algorithm>
 #include <chrono>
-#include <condition_variable>
 #include <deque>
-#include <exception>
-#include <functional>
-#include <memory>
-#include <mutex>
-#include <thread>
 #include "host_math.h"
 #include "scan.hpp"
 #include "densemap.hpp"
@@ -287,6 +282,58 @@ struct TypeMap {   // one feature type (corner / surf)
   uint32_t chain_epoch = 0;
 };
 
+// LOAMX_MAP_TRACE (read once): where the host's share of a sweep goes
+inline bool map_trace_on() { static const bool on = getenv("LOAMX_MAP_TRACE") != nullptr; return on; }
+// the caller's side: stamps of process() (us since entry), averaged over 50 calls and printed
+struct MapTrace {
+  const bool on = map_trace_on();
+  int n = 0, calls = 0;
+  double t0 = 0;
+  const char* name[16];
+  double at[16], sum[16] = {}, worst = 0;
+  static double now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  void begin() { if (on) { n = 0; t0 = now(); } }
+  void mark(const char* what) { if (on && n < 16) { name[n] = what; at[n++] = now() - t0; } }
+  void end() {
+    if (!on) return;
+    for (int k = 0; k < n; k++) sum[k] += at[k];
+    if (n) worst = std::max(worst, at[n - 1]);
+    if (n && at[n - 1] > 700.0) {
+      fprintf(stderr, "[map trace, slow call]");
+      for (int k = 0; k < n; k++) fprintf(stderr, " %s %.1f", name[k], at[k]);
+      fprintf(stderr, "\n");
+    }
+    if (++calls < 50) return;
+    fprintf(stderr, "[map trace, mean of %d calls]", calls);
+    for (int k = 0; k < n; k++) { fprintf(stderr, " %s %.1f", name[k], sum[k] / calls); sum[k] = 0; }
+    fprintf(stderr, " (slowest call %.1f)\n", worst);
+    calls = 0; worst = 0;
+  }
+};
+// the helper's side, one per job: stamps (us since the job began) and which call of the update's enqueue took longest — a job that needs
+// milliseconds to ENQUEUE is a call that blocked
+struct HelperTrace {
+  const bool on = map_trace_on();
+  int n = 0;
+  const char* name[8];
+  double at[8], t0 = 0, prev = 0, longest = 0;
+  const char* longest_what = "";
+  HelperTrace() { if (on) t0 = prev = MapTrace::now(); }
+  void call(const char* what) {
+    if (!on) return;
+    const double t = MapTrace::now();
+    if (t - prev > longest) { longest = t - prev; longest_what = what; }
+    prev = t;
+  }
+  void mark(const char* what) { if (on && n < 8) { name[n] = what; at[n++] = MapTrace::now() - t0; } }
+  void report(const char* title, double slower_than_us) const {
+    if (!on || !n || at[n - 1] <= slower_than_us) return;
+    fprintf(stderr, "[map trace, %s]", title);
+    for (int k = 0; k < n; k++) fprintf(stderr, " %s %.0f", name[k], at[k]);
+    fprintf(stderr, " (longest call of the enqueue: %s, %.0f us)\n", longest_what, longest);
+  }
+};
+
 class Mapper {
  public:
   explicit Mapper(const loamx_map_config& cfg);
@@ -371,14 +418,19 @@ class Mapper {
   VoxelPipeline sur_vox;
   uint32_t n_surround = 0;
   PinBuf<uint32_t> h_sur;
-  PinBuf<uint32_t> h_err;                            // raised by a fused kernel whose look-back gave up (checked behind process()'s synchronisation)
+  // Raised by a fused kernel whose look-back gave up.  One word per owner: whoever enqueues the kernels clears the word, and one thread at
+  // a time reads it — the partition of table set 0 / 1: process(), behind the synchronisation of the sweep that registers against that
+  // set; the map update: complete_update()
+  enum { ERR_PARTITION = 0 /* + set */, ERR_UPDATE = 2, ERR_WORDS = 16 };
+  PinBuf<uint32_t> h_err;
+  bool err_raised(int word) const { return *(const volatile uint32_t*)(h_err.p + word) != 0u; }
   hipStream_t st2 = nullptr, st3 = nullptr;         // the corner / surf map's update (the sub-map partition: st2 and the registration's stream)
   // The map update of a sweep (insertion, per-cube re-filtering, the new cube directory) is enqueued behind the registration but NOT waited
   // for: process() returns with the pose and the registered cloud while the update runs on st2 / st3; whoever needs the map next — the
   // next process(), the getters, a snapshot — finishes it first (finish_update: a wait that is normally over long before).
   // Its ~14 launches and copies cost the host ~60 us: a helper thread of this object enqueues them (behind an event of the
   // registration's stream) while the calling thread fetches the results.
-  bool upd_pending = false;
+  bool upd_pending = false;   // (set by the helper's job when it enqueues the update, cleared by whoever completes it: either is behind the other)
   uint32_t upd_n_sub[2] = {0, 0};
   void finish_update();     // the calling thread: the helper has run its job; the update's result is in the host's cube directory
   // the same for the next process() call only: the helper's job is through the update and the prepared partition — on every fifth frame it
@@ -387,21 +439,16 @@ class Mapper {
   void finish_update_front();
   void complete_update();   // the wait + the bookkeeping themselves (either thread, behind the helper's enqueue)
   void compute_surround(const MapWindow& w, const uint8_t* sur_lut);
-  struct Helper {
-    std::thread th;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::function<void()> job;
-    bool busy = false, quit = false;
-    std::atomic<uint32_t> posted{0};   // bumped by post(): the helper spins on it for a while before it sleeps on cv
-    std::atomic<bool> running{false};  // mirror of `busy` for wait()'s spin phase
-    std::atomic<bool> front_done{true};   // the running job has left its front part (update + prepared partition) behind: finish_update_front()
-    std::atomic<bool> front_failed{false};   // ... by an exception (wait() rethrows it)
-    std::exception_ptr err;
-    void post(std::function<void()> f);
-    void wait();          // returns when the posted job has run; rethrows what it threw
-    ~Helper();
-  } helper;
+  HelperThread helper;
+  // whatever happens to a sweep after its update was posted, the helper must not wait for its results for ever
+  struct SpecRelease {
+    Mapper* m;
+    ~SpecRelease() {
+      std::lock_guard<std::mutex> lk(m->helper.mu);
+      m->spec_in.ready = true;
+      m->helper.cv.notify_all();
+    }
+  };
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   ~Mapper() {
     try { helper.wait(); } catch (...) {}
@@ -425,6 +472,36 @@ class Mapper {
   // optimisation (:628-923) does not run, the pose is taken as transformTobeMapped.  The merge step of a map epoch.
   int insert(const loamx_cloud* corner_last, const loamx_cloud* surf_last, const float pose6[6]);
   const float* forced_pose = nullptr;   // (insert(): process() takes this as transformTobeMapped instead of transformAssociateToMap's)
+  // ---- process() is this list of stages, run in this order on the calling thread ...
+  struct UpdateArgs {   // what the helper's job needs of a sweep (copied into the job)
+    uint32_t n_in[2], n_sub[2];
+    int nvalid;
+    MapWindow w;
+    bool surround_due, speculate;
+  };
+  struct Sweep : UpdateArgs {   // what the stages of one process() call share
+    const loamx_cloud *corner_last, *surf_last;
+    loamx_cloud* full_res;
+    const DeviceInput* dev;
+    Plan plan;
+    bool want_full, adopt, imu_blend;
+  };
+  bool begin_sweep(const Sweep& sw);   // argument checks, the previous update's front, the frame counter (false: a skipped frame)
+  void plan_sweep(Sweep& sw);          // the pose guess, the plan, whether the prepared partition is this sweep's
+  void upload_sweep(const Sweep& sw);
+  void partition_sweep(const Sweep& sw);
+  void register_sweep(Sweep& sw);      // ... with the IMU blend
+  void post_update(Sweep& sw);         // whether a surround cloud is due; the job goes to the helper
+  int collect_results(const Sweep& sw);
+  MapTrace tr;
+  // ... and the helper's job is this one, on the helper thread.  Who touches what between post() and the next call's begin_sweep():
+  //   the job's front   tm[] (the update's buffers, then n / cur / cube_cnt), upd_pending, upd_n_sub, the update's error word; when it
+  //                     speculates: spec_plan / spec_valid / spec_room, the table set tab_cur ^ 1 with its error word, the three *_v views
+  //   the job's tail    the surround cloud's buffers, n_surround (it reads the updated map, as the next partition does)
+  //   the caller        reg, the transforms, the statistics, the error word of table set tab_cur; spec_in under helper.mu
+  void run_update_job(const UpdateArgs& a);
+  void enqueue_update(const UpdateArgs& a, HelperTrace& ht);   // both feature types' insertion + re-filtering, on st2 / st3 behind ev_fork
+  void prepare_next_partition(HelperTrace& ht);                // (see spec_plan)
   void load_cubes(const loamx_cloud* corner, const loamx_cloud* surf);
   int get_cubes(int which, loamx_cloud* out);
   int get_surround(loamx_cloud* out);
@@ -444,8 +521,8 @@ Mapper::Mapper(const loamx_map_config& c) : cfg(c), reg(c.device, 1) {
   reg.params.surf_leaf = c.surf_filter_size;
   // the two feature types' map updates are independent: the corner map's runs on a stream of its own next to the surf map's
   // (process(): forked behind the registration, joined before the results are read)
-  h_err.reserve(16);
-  *h_err.p = 0u;
+  h_err.reserve(ERR_WORDS);
+  for (int k = 0; k < ERR_WORDS; k++) h_err.p[k] = 0u;
   st2 = create_stream(0);
   st3 = create_stream(0);
   LX_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
@@ -509,105 +586,99 @@ void Mapper::ensure(TypeMap& t, uint32_t n_map_max, uint32_t n_in) {
   (&t == &tm[0] ? reg.corner_index : reg.surf_index).reserve_points(room);
 }
 
-namespace {
-// LOAMX_MAP_TRACE: host-side stamps of process() (us since entry), averaged over 50 calls and printed — where the host's share of a sweep goes
-struct MapTrace {
-  bool on;
-  int n = 0, calls = 0;
-  double t0 = 0;
-  const char* name[16];
-  double at[16], sum[16] = {}, worst = 0;
-  static double now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-  MapTrace() : on(getenv("LOAMX_MAP_TRACE") != nullptr) {}
-  void begin() { if (on) { n = 0; t0 = now(); } }
-  void mark(const char* what) { if (on && n < 16) { name[n] = what; at[n++] = now() - t0; } }
-  void end() {
-    if (!on) return;
-    for (int k = 0; k < n; k++) sum[k] += at[k];
-    if (n) worst = std::max(worst, at[n - 1]);
-    if (n && at[n - 1] > 700.0) {
-      fprintf(stderr, "[map trace, slow call]");
-      for (int k = 0; k < n; k++) fprintf(stderr, " %s %.1f", name[k], at[k]);
-      fprintf(stderr, "\n");
-    }
-    if (++calls < 50) return;
-    fprintf(stderr, "[map trace, mean of %d calls]", calls);
-    for (int k = 0; k < n; k++) { fprintf(stderr, " %s %.1f", name[k], sum[k] / calls); sum[k] = 0; }
-    fprintf(stderr, " (slowest call %.1f)\n", worst);
-    calls = 0; worst = 0;
-  }
-};
-}  // namespace
-
 int Mapper::process(const loamx_cloud* corner_last, const loamx_cloud* surf_last, loamx_cloud* full_res, const DeviceInput* dev) {
   TraceRange trace_range("loamx:mapping:process");
-  static thread_local MapTrace tr;
   tr.begin();
-  if (!dev) {
-    check_cloud(corner_last, false);
-    check_cloud(surf_last, false);
+  Sweep sw;
+  sw.corner_last = corner_last;
+  sw.surf_last = surf_last;
+  sw.full_res = full_res;
+  sw.dev = dev;
+  if (!begin_sweep(sw)) return LOAMX_SKIPPED;
+  tr.mark("finished_update");
+  plan_sweep(sw);
+  tr.mark("planned");
+  upload_sweep(sw);
+  tr.mark("uploaded");
+  partition_sweep(sw);
+  tr.mark(sw.adopt ? "partition_adopted" : "partition+index");
+  register_sweep(sw);
+  tr.mark("registered");
+  SpecRelease spec_release{this};
+  post_update(sw);
+  tr.mark("update_posted");
+  const int rc = collect_results(sw);
+  tr.mark("results");
+  tr.end();
+  return rc;
+}
+
+bool Mapper::begin_sweep(const Sweep& sw) {
+  if (!sw.dev) {
+    check_cloud(sw.corner_last, false);
+    check_cloud(sw.surf_last, false);
   }
-  if (full_res) check_cloud(full_res, false);
+  if (sw.full_res) check_cloud(sw.full_res, false);
   LX_HIP(hipSetDevice(cfg.device));
   finish_update_front();
-  tr.mark("finished_update");
   frame_count++;
-  if (frame_count < 1) return LOAMX_SKIPPED;   // _stackFrameNum = 1 (:269-274)
+  if (frame_count < 1) return false;   // _stackFrameNum = 1 (:269-274)
   frame_count = 0;
+  return true;
+}
 
+void Mapper::plan_sweep(Sweep& sw) {
   if (forced_pose) tobe.set(forced_pose);
   else transform_associate_to_map(sum, bef, aft, incre, tobe);
-  Plan plan;
-  make_plan(tobe, /*may_shift=*/true, plan);
-  const int nvalid = plan.nvalid;
-  uint32_t n_sub[2] = {plan.n_sub[0], plan.n_sub[1]};
-  last_sub[0] = n_sub[0];
-  last_sub[1] = n_sub[1];
-  tr.mark("planned");
-  MapWindow w;
-  for (int a = 0; a < 3; a++) w.cen[a] = cen[a];
-  const uint32_t n_in[2] = {dev ? dev->n_corner : corner_last->count, dev ? dev->n_surf : surf_last->count};
-  const bool want_full = dev ? dev->n_full != 0 : (full_res && full_res->count);
+  make_plan(tobe, /*may_shift=*/true, sw.plan);
+  sw.nvalid = sw.plan.nvalid;
+  for (int t = 0; t < 2; t++) last_sub[t] = sw.n_sub[t] = sw.plan.n_sub[t];
+  for (int a = 0; a < 3; a++) sw.w.cen[a] = cen[a];
+  sw.n_in[0] = sw.dev ? sw.dev->n_corner : sw.corner_last->count;
+  sw.n_in[1] = sw.dev ? sw.dev->n_surf : sw.surf_last->count;
+  sw.want_full = sw.dev ? sw.dev->n_full != 0 : (sw.full_res && sw.full_res->count);
 
   // a partition prepared for the predicted pose is this sweep's own if the plans agree entry by entry (and the sweep fits the room the
   // buffers were given: ensure() must not move them)
   // ... nor grow a look-back chain: the prepared side sized them for sweeps of at most spec_room points
-  const bool adopt = spec_valid && plan.same_as(spec_plan) && tm[0].n + n_in[0] + 65 <= tm[0].room && tm[1].n + n_in[1] + 65 <= tm[1].room &&
-                     n_in[0] <= spec_room[0] && n_in[1] <= spec_room[1];
-  if (spec_valid) (adopt ? spec_hits : spec_misses)++;
+  sw.adopt = spec_valid && sw.plan.same_as(spec_plan) && tm[0].n + sw.n_in[0] + 65 <= tm[0].room && tm[1].n + sw.n_in[1] + 65 <= tm[1].room &&
+             sw.n_in[0] <= spec_room[0] && sw.n_in[1] <= spec_room[1];
+  if (spec_valid) (sw.adopt ? spec_hits : spec_misses)++;
   spec_valid = false;
-  if (adopt) tab_cur ^= 1;   // (the prepared tables are the current ones now; slot_lut_v / sur_lut_v / slot_tag_v point into them already)
+  if (sw.adopt) tab_cur ^= 1;   // (the prepared tables are the current ones now; slot_lut_v / sur_lut_v / slot_tag_v point into them already)
+}
 
-  // the sweep's clouds and the guess go up first: the copies run while this thread is still enqueuing the partition (the chain
-  // of short launches below is bound by the host's launch rate, not by the device)
-  {
-    float g6[6];
-    tobe.get(g6);
-    if (dev) {
-      if (dev->ready) LX_HIP(hipStreamWaitEvent(reg.stream(), dev->ready, 0));
-      const float4* c[1] = {dev->corner};
-      const float4* sf[1] = {dev->surf};
-      const float4* fl[1] = {dev->full};
-      reg.upload_device(1, c, &dev->n_corner, sf, &dev->n_surf, dev->n_full ? fl : nullptr, &dev->n_full, g6);
-    } else {
-      reg.upload(1, corner_last, surf_last, full_res, g6, false);
-    }
+// the sweep's clouds and the guess go up first: the copies run while this thread is still enqueuing the partition (the chain
+// of short launches behind them is bound by the host's launch rate, not by the device)
+void Mapper::upload_sweep(const Sweep& sw) {
+  float g6[6];
+  tobe.get(g6);
+  if (const DeviceInput* dev = sw.dev) {
+    if (dev->ready) LX_HIP(hipStreamWaitEvent(reg.stream(), dev->ready, 0));
+    const float4* c[1] = {dev->corner};
+    const float4* sf[1] = {dev->surf};
+    const float4* fl[1] = {dev->full};
+    reg.upload_device(1, c, &dev->n_corner, sf, &dev->n_surf, dev->n_full ? fl : nullptr, &dev->n_full, g6);
+  } else {
+    reg.upload(1, sw.corner_last, sw.surf_last, sw.full_res, g6, false);
   }
-  tr.mark("uploaded");
-  if (!adopt) {
-    helper.wait();   // (a surround cloud still being cut reads the look-up tables the partition is about to rewrite; ensure() may move the map)
-    enqueue_partition(plan, tab_cur, n_in);
-  }
-  tr.mark(adopt ? "partition_adopted" : "partition+index");
+}
 
-  // ---- registration against the sub-map (guard + iterations inside Registrar::run_async)
+void Mapper::partition_sweep(const Sweep& sw) {
+  if (sw.adopt) return;
+  helper.wait();   // (a surround cloud still being cut reads the look-up tables the partition is about to rewrite; ensure() may move the map)
+  enqueue_partition(sw.plan, tab_cur, sw.n_in);
+}
+
+// registration against the sub-map (guard + iterations inside Registrar::run_async)
+void Mapper::register_sweep(Sweep& sw) {
   reg.early_exit = true;   // process() is blocking
   // (insert(): the caller's pose goes into the map verbatim — a pipeline pose has had its IMU blend already)
-  const bool imu_blend = !imu_history.empty() && !forced_pose;
-  reg.defer_full = imu_blend;
+  sw.imu_blend = !imu_history.empty() && !forced_pose;
+  reg.defer_full = sw.imu_blend;
   reg.run_async();
   last_optimized = reg.submap_sufficient();
-  if (imu_blend) {
+  if (sw.imu_blend) {
     // transformUpdate with IMU data (:171-200) changes transformTobeMapped before the new features are inserted into the map
     // and before the full-resolution cloud is registered: blend on the host, hand the pose back to the device
     float p6[6];
@@ -615,144 +686,39 @@ int Mapper::process(const loamx_cloud* corner_last, const loamx_cloud* surf_last
     if (last_optimized) imu_blend_pose(p6);
     reg.finish_with_poses(p6);
   }
+}
 
-  tr.mark("registered");
-  // ---- map insertion + per-cube re-filtering: corners on st2, surfs on st3, side by side behind the registration — and NOT in front of
-  // its results (see upd_pending)
+// map insertion + per-cube re-filtering: corners on st2, surfs on st3, side by side behind the registration — and NOT in front of its
+// results (see upd_pending)
+void Mapper::post_update(Sweep& sw) {
   LX_HIP(hipEventRecord(ev_fork, reg.stream()));
-  if (want_full && full_res) reg.download_full_res_async(0, full_res);   // (lands while the map is updated)
-  for (int t = 0; t < 2; t++) upd_n_sub[t] = n_sub[t];
-  const uint32_t n_sub0 = n_sub[0], n_sub1 = n_sub[1], n_in0 = n_in[0], n_in1 = n_in[1];
+  if (sw.want_full && sw.full_res) reg.download_full_res_async(0, sw.full_res);   // (lands while the map is updated)
   // createDownsizedMap (:242-264) is due on every 5th processed frame: the helper goes on to finish the update and cut the surround cloud
   if (!forced_pose) map_frame_count++;   // (insert() is not a processed frame: no surround cloud is due)
   fresh_map = false;
-  const bool surround_due = map_frame_count >= 5;
-  if (surround_due) { map_frame_count = 0; fresh_map = true; }
-  upd_pending = true;
-  const bool speculate = !forced_pose && spec_enabled;
+  sw.surround_due = map_frame_count >= 5;
+  if (sw.surround_due) { map_frame_count = 0; fresh_map = true; }
+  sw.speculate = !forced_pose && spec_enabled;
   {
     std::lock_guard<std::mutex> lk(helper.mu);
     spec_in.ready = false;
     spec_in.ok = false;
   }
-  struct SpecRelease {   // whatever happens below, the helper must not wait for this sweep's results for ever
-    Mapper* m;
-    ~SpecRelease() {
-      std::lock_guard<std::mutex> lk(m->helper.mu);
-      m->spec_in.ready = true;
-      m->helper.cv.notify_all();
-    }
-  } spec_release{this};
-  helper.post([this, n_sub0, n_sub1, n_in0, n_in1, nvalid, w, surround_due, speculate]() {
-  struct FrontDone {   // (also when the front part throws: the caller's next wait must end — it goes on to Helper::wait(), which rethrows)
-    Helper& h;
-    ~FrontDone() {
-      if (std::uncaught_exceptions() > 0) h.front_failed.store(true, std::memory_order_release);
-      h.front_done.store(true, std::memory_order_release);
-    }
-  };
-  std::unique_ptr<FrontDone> front(new FrontDone{helper});
-  static const bool htrace = getenv("LOAMX_MAP_TRACE") != nullptr;   // (helper-side stamps: a job slower than 1 ms says where it spent its time)
-  double hs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  hs[0] = htrace ? MapTrace::now() : 0.0;
-  LX_HIP(hipSetDevice(cfg.device));
-  const uint32_t n_sub[2] = {n_sub0, n_sub1}, n_in[2] = {n_in0, n_in1};
-  // (trace only: which call of the update's enqueue took longest — a job that needs milliseconds to ENQUEUE is a call that blocked)
-  double ht_prev = hs[0], ht_worst = 0;
-  const char* ht_what = "";
-  auto HT = [&](const char* what) { if (htrace) { const double n = MapTrace::now(); if (n - ht_prev > ht_worst) { ht_worst = n - ht_prev; ht_what = what; } ht_prev = n; } };
-  LX_HIP(hipStreamWaitEvent(st2, ev_fork, 0));
-  LX_HIP(hipStreamWaitEvent(st3, ev_fork, 0));
-  HT("stream waits");
-  for (int t = 1; t >= 0; t--) {   // (the surf map first: its chain is the longer one, and the host needs ~80 us to enqueue either)
-    TypeMap& T = tm[t];
-    hipStream_t st = t == 0 ? st2 : st3;
-    const int nxt = 1 - T.cur;
-    const uint32_t n_old = n_sub[t], n_slots = n_in[t], n_fin = n_old + n_slots;
-    // (the sub-map's points, cube slots and valid flags are in fin / fin_seg / fin_valid already: the partition wrote them there)
-    if (n_slots) {
-      const uint32_t nb = (n_slots + 255) / 256;
-      if (++T.chain_epoch >= (1u << 30) - 2u) {
-        LX_HIP(hipMemsetAsync(T.chain.p, 0, sizeof(unsigned long long) * T.chain.cap, st));
-        T.chain_epoch = 1;
-      }
-      hipLaunchKernelGGL(k_map_insert, dim3(nb), dim3(256), 0, st, reg.d_ds_points(), reg.d_ds_offsets(), t, n_slots, reg.d_poses(), w,
-                         slot_lut_v, n_old, T.fin.p, T.fin_seg.p, T.fin_valid.p, T.counters.p + 3, T.pts[nxt].p, T.tags[nxt].p,
-                         T.chain.p + 2 * T.chain_stride, (unsigned long long)T.chain_epoch, T.counters.p, h_err.p);
-    } else {
-      LX_HIP(hipMemsetAsync(T.counters.p + 4, 0, sizeof(uint32_t) * 2, st));
-    }
-    HT("k_map_insert");
-    const uint32_t nslots = (uint32_t)std::max(nvalid, 1);
-    const float inv = 1.0f / (t == 0 ? cfg.corner_filter_size : cfg.surf_filter_size);
-    T.vox.compute_ijk(T.fin.p, T.fin_valid.p, n_fin, nullptr, nslots, inv, inv, T.fin_seg.p);
-    HT("compute_ijk");
-    T.vox.sort_reduce(T.fin.p, T.fin_valid.p, n_fin, nullptr, nslots, T.filt.p, T.out_off.p, T.fin_seg.p);
-    HT("sort_reduce");
-    const uint32_t max_f = n_fin ? n_fin : 1;
-    hipLaunchKernelGGL(k_map_append_filtered, dim3((max_f + 255) / 256), dim3(256), 0, st, T.filt.p, T.out_off.p, nslots, slot_tag_v,
-                       max_f, T.counters.p + 3, T.counters.p + 5, T.pts[nxt].p, T.tags[nxt].p, T.counters.p + 6, T.hist.p);
-    const uint32_t max_new = T.n + n_slots + 1;
-    hipLaunchKernelGGL(k_map_hist, dim3(std::min<uint32_t>((max_new + 2047) / 2048, 256u)), dim3(256), 0, st, T.tags[nxt].p, T.counters.p + 6, max_new, w, T.hist.p);
-    HT("append + hist");
-    store_to_pinned_u32(T.h_hist.p, T.hist.p, MCUBES + 16, st);   // (histogram + the counters behind it, by a kernel: pinned_copy.hpp — the copy call blocked for milliseconds now and then)
-    HT("histogram copy");
-  }
-  static const bool trace = getenv("LOAMX_MAP_TRACE") != nullptr;
-  const double t0 = trace ? MapTrace::now() : 0.0;
-  hs[1] = t0;   // update enqueued
-  if (surround_due) complete_update();
-  const double t1 = trace ? MapTrace::now() : 0.0;
-  // (the surround cloud is cut LAST, behind the prepared partition: the next sweep waits for the partition, not for the cloud — round 6; the
-  // cloud is cut with THIS sweep's look-up table, the preparation below points sur_lut_v at the next one's)
-  const uint8_t* sur_lut_now = sur_lut_v;
-  if (speculate) {   // the next sweep's partition + index for the predicted pose (see spec_plan)
-    complete_update();
-    hs[2] = htrace ? MapTrace::now() : 0.0;   // update complete
-    SpecInputs in;
-    {
-      std::unique_lock<std::mutex> lk(helper.mu);
-      helper.cv.wait(lk, [this]() { return spec_in.ready; });
-      in = spec_in;
-    }
-    hs[3] = htrace ? MapTrace::now() : 0.0;   // the caller's results are in
-    if (in.ok) {
-      float p6[6];
-      for (int k = 0; k < 6; k++) p6[k] = in.sum6[k] + (in.sum6[k] - in.sum_prev6[k]);
-      HTwist sum_pred, incre_tmp, tobe_pred;
-      sum_pred.set(p6);
-      transform_associate_to_map(sum_pred, in.bef, in.aft, incre_tmp, tobe_pred);
-      Plan sp;
-      if (make_plan(tobe_pred, /*may_shift=*/false, sp)) {
-        enqueue_partition(sp, tab_cur ^ 1, in.n_in_room);
-        spec_room[0] = in.n_in_room[0];   // (the look-back chains of k_map_insert were sized for sweeps of at most this many points)
-        spec_room[1] = in.n_in_room[1];
-        spec_plan = std::move(sp);
-        spec_valid = true;
-      }
-    }
-  }
-  hs[4] = htrace ? MapTrace::now() : 0.0;     // partition prepared (enqueued)
-  if (htrace && hs[4] - hs[0] > 1000.0)
-    fprintf(stderr, "[map trace, slow helper job] update enqueued %.0f us (longest call: %s, %.0f us), update complete %.0f, caller's results in %.0f, partition prepared %.0f\n",
-            hs[1] - hs[0], ht_what, ht_worst, hs[2] ? hs[2] - hs[0] : -1.0, hs[3] ? hs[3] - hs[0] : -1.0, hs[4] - hs[0]);
-  front.reset();   // the next process() call may start
-  if (surround_due) {
-    const double t2 = trace ? MapTrace::now() : 0.0;
-    compute_surround(w, sur_lut_now);
-    if (trace) fprintf(stderr, "[map trace, helper] update completed %.1f us after its enqueue, surround cloud %.1f us\n", t1 - t0, MapTrace::now() - t2);
-  }
-  });
-  tr.mark("update_posted");
+  // (post() throws what the tail of the previous sweep's job left, a failed surround cloud, and does not take this job then: no update is
+  // pending — the job itself raises upd_pending — and process()'s SpecRelease hands spec_in back, so the handle goes on as if this sweep,
+  // registered but not inserted, had not come)
+  helper.post([this, a = static_cast<const UpdateArgs&>(sw)]() { run_update_job(a); });
+}
 
-  // ---- results (the registration's stream: poses, statistics, the registered cloud's copy — not the map update)
+// the results (the registration's stream: poses, statistics, the registered cloud's copy — not the map update)
+int Mapper::collect_results(const Sweep& sw) {
   float pose6[6];
   int stats4[4];
   reg.sync();
   tr.mark("synced");
   // the partition this registration read was split by a fused kernel with a look-back: had a tile given up, the sub-map would be
   // incomplete — fail THIS sweep, not the next call (the word is host-visible; the split precedes the registration on its stream)
-  if (*(volatile uint32_t*)h_err.p) { *h_err.p = 0u; throw Error(LOAMX_E_HIP, "map partition: a tile's look-back gave up waiting for the tiles before it"); }
+  if (err_raised(ERR_PARTITION + tab_cur)) throw Error(LOAMX_E_HIP, "map partition: a tile's look-back gave up waiting for the tiles before it");
   reg.download(pose6, stats4);
   LX_HIP(hipGetLastError());
   SweepStats ss;
@@ -765,25 +731,114 @@ int Mapper::process(const loamx_cloud* corner_last, const loamx_cloud* surf_last
     bef = sum;
     aft = tobe;
   }
-  if (speculate) {   // what the prediction needs of this sweep (the helper waits for it behind the update)
+  if (sw.speculate) {   // what the prediction needs of this sweep (the helper waits for it behind the update)
     std::lock_guard<std::mutex> lk(helper.mu);
     sum.get(spec_in.sum6);
     for (int k = 0; k < 6; k++) spec_in.sum_prev6[k] = have_sum_prev ? sum_prev6[k] : spec_in.sum6[k];
     spec_in.bef = bef;
     spec_in.aft = aft;
-    spec_in.n_in_room[0] = 2 * n_in[0] + 1024;
-    spec_in.n_in_room[1] = 2 * n_in[1] + 1024;
+    spec_in.n_in_room[0] = 2 * sw.n_in[0] + 1024;
+    spec_in.n_in_room[1] = 2 * sw.n_in[1] + 1024;
     spec_in.ok = true;
   }
   if (!forced_pose) { sum.get(sum_prev6); have_sum_prev = true; }
-  if (want_full && full_res) {
-    int r = reg.download_full_res(0, full_res);
+  if (sw.want_full && sw.full_res) {
+    int r = reg.download_full_res(0, sw.full_res);
     if (r != LOAMX_OK) rc = r;
   }
-
-  tr.mark("results");
-  tr.end();
   return rc;
+}
+
+// ---- the helper's job: the update's enqueue, the next sweep's partition and, on every fifth frame, the surround cloud
+void Mapper::run_update_job(const UpdateArgs& a) {
+  HelperThread::Front front(helper);
+  HelperTrace ht;
+  LX_HIP(hipSetDevice(cfg.device));
+  enqueue_update(a, ht);
+  ht.mark("update enqueued");
+  if (a.surround_due || a.speculate) {
+    complete_update();
+    ht.mark("update complete");
+  }
+  // (the surround cloud is cut LAST, behind the prepared partition: the next sweep waits for the partition, not for the cloud — round 6; the
+  // cloud is cut with THIS sweep's look-up table, the preparation points sur_lut_v at the next one's)
+  const uint8_t* sur_lut_now = sur_lut_v;
+  if (a.speculate) prepare_next_partition(ht);
+  ht.mark("partition prepared");
+  ht.report("slow helper job", 1000.0);
+  front.release();   // the next process() call may start
+  if (a.surround_due) {
+    compute_surround(a.w, sur_lut_now);
+    ht.mark("surround cloud");
+    ht.report("helper, surround frame", 0.0);
+  }
+}
+
+void Mapper::enqueue_update(const UpdateArgs& a, HelperTrace& ht) {
+  upd_pending = true;
+  for (int t = 0; t < 2; t++) upd_n_sub[t] = a.n_sub[t];
+  h_err.p[ERR_UPDATE] = 0u;   // (the update before this one has been completed: nothing on the device writes the word now)
+  LX_HIP(hipStreamWaitEvent(st2, ev_fork, 0));
+  LX_HIP(hipStreamWaitEvent(st3, ev_fork, 0));
+  ht.call("stream waits");
+  for (int t = 1; t >= 0; t--) {   // (the surf map first: its chain is the longer one, and the host needs ~80 us to enqueue either)
+    TypeMap& T = tm[t];
+    hipStream_t st = t == 0 ? st2 : st3;
+    const int nxt = 1 - T.cur;
+    const uint32_t n_old = a.n_sub[t], n_slots = a.n_in[t], n_fin = n_old + n_slots;
+    // (the sub-map's points, cube slots and valid flags are in fin / fin_seg / fin_valid already: the partition wrote them there)
+    if (n_slots) {
+      const uint32_t nb = (n_slots + 255) / 256;
+      if (++T.chain_epoch >= (1u << 30) - 2u) {
+        LX_HIP(hipMemsetAsync(T.chain.p, 0, sizeof(unsigned long long) * T.chain.cap, st));
+        T.chain_epoch = 1;
+      }
+      hipLaunchKernelGGL(k_map_insert, dim3(nb), dim3(256), 0, st, reg.d_ds_points(), reg.d_ds_offsets(), t, n_slots, reg.d_poses(), a.w,
+                         slot_lut_v, n_old, T.fin.p, T.fin_seg.p, T.fin_valid.p, T.counters.p + 3, T.pts[nxt].p, T.tags[nxt].p,
+                         T.chain.p + 2 * T.chain_stride, (unsigned long long)T.chain_epoch, T.counters.p, h_err.p + ERR_UPDATE);
+    } else {
+      LX_HIP(hipMemsetAsync(T.counters.p + 4, 0, sizeof(uint32_t) * 2, st));
+    }
+    ht.call("k_map_insert");
+    const uint32_t nslots = (uint32_t)std::max(a.nvalid, 1);
+    const float inv = 1.0f / (t == 0 ? cfg.corner_filter_size : cfg.surf_filter_size);
+    T.vox.compute_ijk(T.fin.p, T.fin_valid.p, n_fin, nullptr, nslots, inv, inv, T.fin_seg.p);
+    ht.call("compute_ijk");
+    T.vox.sort_reduce(T.fin.p, T.fin_valid.p, n_fin, nullptr, nslots, T.filt.p, T.out_off.p, T.fin_seg.p);
+    ht.call("sort_reduce");
+    const uint32_t max_f = n_fin ? n_fin : 1;
+    hipLaunchKernelGGL(k_map_append_filtered, dim3((max_f + 255) / 256), dim3(256), 0, st, T.filt.p, T.out_off.p, nslots, slot_tag_v,
+                       max_f, T.counters.p + 3, T.counters.p + 5, T.pts[nxt].p, T.tags[nxt].p, T.counters.p + 6, T.hist.p);
+    const uint32_t max_new = T.n + n_slots + 1;
+    hipLaunchKernelGGL(k_map_hist, dim3(std::min<uint32_t>((max_new + 2047) / 2048, 256u)), dim3(256), 0, st, T.tags[nxt].p, T.counters.p + 6, max_new, a.w, T.hist.p);
+    ht.call("append + hist");
+    store_to_pinned_u32(T.h_hist.p, T.hist.p, MCUBES + 16, st);   // (histogram + the counters behind it, by a kernel: pinned_copy.hpp — the copy call blocked for milliseconds now and then)
+    ht.call("histogram copy");
+  }
+}
+
+// the next sweep's partition + index for the predicted pose, on the map as the completed update has left it
+void Mapper::prepare_next_partition(HelperTrace& ht) {
+  SpecInputs in;
+  {
+    std::unique_lock<std::mutex> lk(helper.mu);
+    helper.cv.wait(lk, [this]() { return spec_in.ready; });
+    in = spec_in;
+  }
+  ht.mark("caller's results in");
+  if (!in.ok) return;
+  float p6[6];
+  for (int k = 0; k < 6; k++) p6[k] = in.sum6[k] + (in.sum6[k] - in.sum_prev6[k]);
+  HTwist sum_pred, incre_tmp, tobe_pred;
+  sum_pred.set(p6);
+  transform_associate_to_map(sum_pred, in.bef, in.aft, incre_tmp, tobe_pred);
+  Plan sp;
+  if (!make_plan(tobe_pred, /*may_shift=*/false, sp)) return;
+  enqueue_partition(sp, tab_cur ^ 1, in.n_in_room);
+  spec_room[0] = in.n_in_room[0];   // (the look-back chains of k_map_insert were sized for sweeps of at most this many points)
+  spec_room[1] = in.n_in_room[1];
+  spec_plan = std::move(sp);
+  spec_valid = true;
 }
 
 bool Mapper::make_plan(const HTwist& pose_tw, bool may_shift, Plan& out) {
@@ -845,7 +900,9 @@ bool Mapper::make_plan(const HTwist& pose_tw, bool may_shift, Plan& out) {
 void Mapper::enqueue_partition(const Plan& plan, int set, const uint32_t n_in_room[2]) {
   hipStream_t st = reg.stream();
   // the three tables travel as one block through pinned memory owned by this object (its previous copy from this set has completed:
-  // a whole sweep with its waits lies in between) — no host wait here
+  // a whole sweep with its waits lies in between) — no host wait here.  The same holds for the set's error word: the split kernels that
+  // could raise it ran in front of a registration whose results have been fetched since
+  h_err.p[ERR_PARTITION + set] = 0u;
   {
     const size_t o_sur = sizeof(short) * MCUBES, o_tag = (o_sur + MCUBES + 3) & ~(size_t)3, bytes = o_tag + sizeof(uint32_t) * 128;
     h_tables[set].reserve(bytes);
@@ -875,7 +932,7 @@ void Mapper::enqueue_partition(const Plan& plan, int set, const uint32_t n_in_ro
       }
       hipLaunchKernelGGL(k_map_split, dim3((T.n + MS_TILE - 1) / MS_TILE), dim3(256), 0, stt, T.pts[cur].p, T.tags[cur].p, T.n, w, slot_lut_v, T.fin.p,
                          T.fin_seg.p, T.fin_valid.p, T.pts[nxt].p, T.tags[nxt].p, (t == 0 ? reg.corner_index : reg.surf_index).d_bounds(),
-                         T.chain.p, T.chain.p + T.chain_stride, (unsigned long long)T.chain_epoch, T.counters.p, h_err.p);
+                         T.chain.p, T.chain.p + T.chain_stride, (unsigned long long)T.chain_epoch, T.counters.p, h_err.p + ERR_PARTITION + set);
     } else {
       LX_HIP(hipMemsetAsync(T.counters.p, 0, sizeof(uint32_t) * 4, stt));
     }
@@ -898,7 +955,7 @@ void Mapper::compute_surround(const MapWindow& w, const uint8_t* sur_lut) {
   sur_scan.reserve(room1);
   sur_valid.reserve(room2);
   sur_vox.reserve(room2, 2);
-  static const bool trace = getenv("LOAMX_MAP_TRACE") != nullptr;
+  const bool trace = map_trace_on();
   const double tq0 = trace ? MapTrace::now() : 0.0;
   double tq1 = 0;
   for (int t = 0; t < 2; t++) {
@@ -935,77 +992,8 @@ void Mapper::compute_surround(const MapWindow& w, const uint8_t* sur_lut) {
   }
 }
 
-void Mapper::Helper::post(std::function<void()> f) {
-  std::unique_lock<std::mutex> lk(mu);
-  if (!th.joinable())
-    th = std::thread([this]() {
-      std::unique_lock<std::mutex> l(mu);
-      for (;;) {
-        // a job arrives every ~0.7 ms while sweeps flow: waking from a condition variable costs tens of microseconds as a rule and ~10 ms
-        // when the thread has lost its time slice (measured: one such call per ~100 sweeps on some hosts, profiles/r06_ab.md section 8),
-        // so the helper spins for up to 2 ms on the post counter before it goes to sleep — an idle handle costs nothing after that
-        if (!(quit || (busy && job))) {
-          const uint32_t seen = posted.load(std::memory_order_acquire);
-          l.unlock();
-          const auto t_in = std::chrono::steady_clock::now();
-          for (unsigned spins = 0; posted.load(std::memory_order_acquire) == seen;) {
-            if ((++spins & 255u) == 0u && std::chrono::steady_clock::now() - t_in > std::chrono::milliseconds(2)) break;
-            __builtin_ia32_pause();
-          }
-          l.lock();
-        }
-        cv.wait(l, [this]() { return quit || (busy && job); });
-        if (quit) return;
-        std::function<void()> j = std::move(job);
-        job = nullptr;
-        l.unlock();
-        std::exception_ptr e;
-        try { j(); } catch (...) { e = std::current_exception(); }
-        l.lock();
-        err = e;
-        busy = false;
-        running.store(false, std::memory_order_release);
-        cv.notify_all();
-      }
-    });
-  cv.wait(lk, [this]() { return !busy; });
-  job = std::move(f);
-  busy = true;
-  front_failed.store(false, std::memory_order_release);
-  front_done.store(false, std::memory_order_release);
-  running.store(true, std::memory_order_release);
-  posted.fetch_add(1, std::memory_order_release);
-  cv.notify_all();
-}
-void Mapper::Helper::wait() {
-  {   // (the job is a few hundred microseconds of enqueueing as a rule: spin for it before sleeping on the condition variable)
-    const auto t_in = std::chrono::steady_clock::now();
-    for (unsigned spins = 0; running.load(std::memory_order_acquire);) {
-      if ((++spins & 255u) == 0u && std::chrono::steady_clock::now() - t_in > std::chrono::milliseconds(2)) break;
-      __builtin_ia32_pause();
-    }
-  }
-  std::unique_lock<std::mutex> lk(mu);
-  cv.wait(lk, [this]() { return !busy; });
-  if (err) { std::exception_ptr e = err; err = nullptr; std::rethrow_exception(e); }
-}
-Mapper::Helper::~Helper() {
-  {
-    std::unique_lock<std::mutex> lk(mu);
-    cv.wait(lk, [this]() { return !busy; });
-    quit = true;
-    posted.fetch_add(1, std::memory_order_release);
-    cv.notify_all();
-  }
-  if (th.joinable()) th.join();
-}
-
 void Mapper::finish_update_front() {
-  const auto t_in = std::chrono::steady_clock::now();
-  for (unsigned spins = 0; !helper.front_done.load(std::memory_order_acquire);) {
-    if ((++spins & 255u) == 0u && std::chrono::steady_clock::now() - t_in > std::chrono::milliseconds(2)) { helper.wait(); break; }
-    __builtin_ia32_pause();
-  }
+  if (!spin_until([this]() { return helper.front_done.load(std::memory_order_acquire); }, std::chrono::milliseconds(2))) helper.wait();
   // (a job that has ended or whose front part threw: take what it threw — no wait in the first case, the job's unwinding in the second)
   if (!helper.running.load(std::memory_order_acquire) || helper.front_failed.load(std::memory_order_acquire)) helper.wait();
   complete_update();   // (a job that neither cut a surround cloud nor prepared a partition has only enqueued the update)
@@ -1023,7 +1011,7 @@ void Mapper::complete_update() {
   spin_sync(st2);   // (polling, not the runtime's blocking wait: common.h)
   spin_sync(st3);   // (the histogram / counter copies are the last thing on either stream)
   for (int t = 0; t < 2; t++) tm[t].vox.check();   // (a timed-out wait inside the per-cube voxel kernel must not corrupt the map silently)
-  if (*(volatile uint32_t*)h_err.p) { *h_err.p = 0u; throw Error(LOAMX_E_HIP, "map update: a tile's look-back gave up waiting for the tiles before it"); }
+  if (err_raised(ERR_UPDATE)) throw Error(LOAMX_E_HIP, "map update: a tile's look-back gave up waiting for the tiles before it");
   for (int t = 0; t < 2; t++) {
     TypeMap& T = tm[t];
     LX_REQUIRE(T.n == 0 || T.h_hist.p[MCUBES + 1] == upd_n_sub[t], "internal: sub-map size differs from the host cube directory");

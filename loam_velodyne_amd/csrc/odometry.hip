@@ -1290,7 +1290,7 @@ struct OdometryBatch::PairOps {
     const auto t_in = std::chrono::steady_clock::now();
     for (unsigned spins = 0; behind(want);) {
       if ((++spins & 255u) == 0u && std::chrono::steady_clock::now() - t_in > std::chrono::milliseconds(20)) return false;
-      __builtin_ia32_pause();
+      cpu_relax();
     }
     return true;
   }
@@ -1339,7 +1339,7 @@ void OdometryBatch::enqueue_tail_(Pass& p) {
     last_.p = q; last_.cap = c;
   }
   h_last_off_ = h_cur_off_;
-  index_.build(last_.p, h_last_off_.data(), p.K, d_cur_off_.p, /*prepared=*/true, /*bounds_done=*/fuse_bounds && p.n_all > 0);
+  index_.build(last_.p, h_last_off_.data(), p.K, d_cur_off_.p, /*bounds_done=*/fuse_bounds && p.n_all > 0);
   if (!ev_tail_) LX_HIP(hipEventCreateWithFlags(&ev_tail_, hipEventDisableTiming));
   LX_HIP(hipEventRecord(ev_tail_, st_));
   tail_pending_ = true;

@@ -247,7 +247,7 @@ class Pipeline {
     const auto t0 = std::chrono::steady_clock::now();
     while (!ready()) {
       if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > max_us) return false;
-      __builtin_ia32_pause();
+      cpu_relax();
     }
     return true;
   }

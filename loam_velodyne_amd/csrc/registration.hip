@@ -360,7 +360,7 @@ void SubMapIndexBatch::init(hipStream_t st) {
 }
 
 // the bounding-box accumulators can be reset long before the points exist (e.g. ahead of the iterations whose result the
-// points depend on): build(..., prepared = true) then skips that launch
+// points depend on): build() then finds them reset and skips that launch
 void SubMapIndexBatch::prepare(uint32_t K) {
   LX_REQUIRE(K >= 1 && K <= 4096, "too many clouds in one index batch");
   reset_bounds_(K);
@@ -373,7 +373,7 @@ void SubMapIndexBatch::reset_bounds_(uint32_t K) {
   enc_ready_ = cap;
 }
 
-void SubMapIndexBatch::build(const float4* d_pts, const uint32_t* h_off, uint32_t K, const uint32_t* d_off_ready, bool prepared, bool bounds_done) {
+void SubMapIndexBatch::build(const float4* d_pts, const uint32_t* h_off, uint32_t K, const uint32_t* d_off_ready, bool bounds_done) {
   LX_REQUIRE(K >= 1 && K <= 4096, "too many clouds in one index batch");
   const uint32_t n = h_off[K];
   d_off_.reserve(K + 2);
@@ -393,7 +393,6 @@ void SubMapIndexBatch::build(const float4* d_pts, const uint32_t* h_off, uint32_
     cursor_.reserve((size_t)LX_MAX_CELLS + 2);
     LX_HIP(hipMemsetAsync(cursor_.p, 0, sizeof(uint32_t) * cursor_.cap, st_));
   }
-  (void)prepared;
   reset_bounds_(K);
   uint32_t max_len = 0;
   for (uint32_t c = 0; c < K; c++) max_len = std::max(max_len, h_off[c + 1] - h_off[c]);
@@ -1386,7 +1385,7 @@ bool Registrar::wait_for_mirrors() {
       if (q == hipSuccess) return false;
       if (q != hipErrorNotReady) LX_HIP(q);
     }
-    __builtin_ia32_pause();
+    cpu_relax();
   }
 }
 

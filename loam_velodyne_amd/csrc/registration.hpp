@@ -146,10 +146,9 @@ class SubMapIndexBatch {
  public:
   void init(hipStream_t st);
   // d_pts: concatenated points; h_off: K+1 host offsets.  Asynchronous on the stream.
-  // d_off_ready: the K+1 offsets already on the device (skips the upload); prepared: prepare(K) was enqueued earlier
+  // d_off_ready: the K+1 offsets already on the device (skips the upload)
   // bounds_done: the kernel that produced d_pts has folded them into d_bounds() already (cloud_bounds_update; prepare(K) came first)
-  void build(const float4* d_pts, const uint32_t* h_off, uint32_t K, const uint32_t* d_off_ready = nullptr, bool prepared = false,
-             bool bounds_done = false);
+  void build(const float4* d_pts, const uint32_t* h_off, uint32_t K, const uint32_t* d_off_ready = nullptr, bool bounds_done = false);
   void prepare(uint32_t K);
   uint32_t* d_bounds() const { return enc_.p; }
   float cell_size = 1.05f;   // initial cell edge (grown by 1.25x while the cell table would exceed its budget)
