@@ -33,15 +33,7 @@ static void apply_scanreg_config(FeatureExtractor& fx, const loamx_scanreg_confi
   const int less_sharp = c.max_corner_less_sharp == 0 ? 10 * c.max_corner_sharp : c.max_corner_less_sharp;   // BasicScanRegistration.cpp:22
   LX_REQUIRE(less_sharp >= c.max_corner_sharp, "max_corner_less_sharp must be >= max_corner_sharp");          // ScanRegistration.cpp:100-109
   LX_REQUIRE(c.imu_history_size >= 1 && c.imu_history_size <= 4096, "imu_history_size must be in [1, 4096]");    // :59-66
-  FeatParams& p = fx.params;
-  p.scan_period = c.scan_period;
-  p.n_regions = c.n_feature_regions;
-  p.curv_region = c.curvature_region;
-  p.max_sharp = c.max_corner_sharp;
-  p.max_less_sharp = less_sharp;
-  p.max_flat = c.max_surface_flat;
-  p.less_flat_leaf = c.less_flat_filter_size;
-  p.curv_thr = c.surface_curvature_threshold;
+  fx.params = feat_params_from(c);
   fx.imu_history_size = std::max(fx.imu_history_size, std::max(200, c.imu_history_size));   // ensureCapacity only grows (CircularBuffer.h:53-70)
 }
 

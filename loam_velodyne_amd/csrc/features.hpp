@@ -18,6 +18,19 @@ struct FeatParams {
   float less_flat_leaf = 0.2f;
   float curv_thr = 0.1f;
 };
+// RegistrationParams -> FeatParams (max_corner_less_sharp 0: ten times max_corner_sharp, BasicScanRegistration.cpp:22); no validation
+inline FeatParams feat_params_from(const loamx_scanreg_config& c) {
+  FeatParams p;
+  p.scan_period = c.scan_period;
+  p.n_regions = c.n_feature_regions;
+  p.curv_region = c.curvature_region;
+  p.max_sharp = c.max_corner_sharp;
+  p.max_less_sharp = c.max_corner_less_sharp == 0 ? 10 * c.max_corner_sharp : c.max_corner_less_sharp;
+  p.max_flat = c.max_surface_flat;
+  p.less_flat_leaf = c.less_flat_filter_size;
+  p.curv_thr = c.surface_curvature_threshold;
+  return p;
+}
 
 // The IMU state machine of BasicScanRegistration for ONE sensor stream, on the host (src/lib/BasicScanRegistration.cpp:55-152,
 // :258-281): history with accumulated position / velocity (updateIMUData :82-98), interpolation (interpolateIMUStateFor

@@ -11,13 +11,11 @@
 #include "registration.hpp"
 #include "hostlink.hpp"
 #include "densemap.hpp"
+#include "odom_lookahead.hpp"
 #include <atomic>
 #include <deque>
-#include <functional>
 #include <chrono>
-#include <condition_variable>
 #include <mutex>
-#include <thread>
 #include <memory>
 
 namespace loamx {
@@ -82,22 +80,42 @@ class Pipeline {
     for (auto& c : chains) { c->ob->params = op; c->ob->set_keep(OR - 2); }
     device = mc.device;
     if (getenv("LOAMX_NO_LOOKAHEAD")) prefetch = false;   // debugging / profiling: run the stages one after the other
+    const double spin_us = diag_env("LOAMX_SPIN_US") ? atof(diag_env("LOAMX_SPIN_US")) : 400.0;   // diagnostic
+    la.reset(new LookAhead(
+        n_groups, [this](uint32_t g, int k) { run_chain_step(*chains[g], (uint32_t)k); }, [this] { (void)hipSetDevice(device); },
+        std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double, std::micro>(spin_us))));
   }
   Registrar reg;
   // Look-ahead rings: what a look-ahead step leaves behind for its registration (feature offsets, odometry results, events, timers)
   // lives in slot step % OR, so the odometry may run up to OR - 2 steps ahead of the registration (ahead_depth below)
   static constexpr int OR = 16;
-  // one odometry chain: the streams [s0, s1), their batch object (own HIP stream), the host thread that drives it and its position
+  // stage timers are read lazily (an elapsed time is taken once both events have completed) so that measuring never
+  // makes the host wait for a stage
+  struct LazyTimer {
+    hipEvent_t a = nullptr, b = nullptr;
+    bool pending = false;
+    float ms = 0.f;
+    void start(hipStream_t s) {
+      if (!a) { LX_HIP(hipEventCreate(&a)); LX_HIP(hipEventCreate(&b)); }
+      pending = false;
+      LX_HIP(hipEventRecord(a, s));
+    }
+    void stop(hipStream_t s) { LX_HIP(hipEventRecord(b, s)); pending = true; }
+    bool resolve() {   // true: a time has just been taken
+      if (!pending || hipEventQuery(b) != hipSuccess) return false;
+      LX_HIP(hipEventElapsedTime(&ms, a, b));
+      pending = false;
+      return true;
+    }
+    void destroy() { if (a) { (void)hipEventDestroy(a); (void)hipEventDestroy(b); a = b = nullptr; } }
+  };
+  // one odometry chain: the streams [s0, s1) and their batch object (own HIP stream); its host thread and its position are the
+  // look-ahead gate's (`la`)
   struct OdomChain {
     uint32_t s0 = 0, s1 = 0;
     std::unique_ptr<OdometryBatch> ob;
-    std::thread worker;
-    std::atomic<int> done{-1};           // odometry of steps <= done is complete and published
-    std::atomic<int> next{0};            // next step of this chain (its worker; the calling thread only while the workers are parked)
-    std::atomic<bool> busy{false};
     hipEvent_t ev_tail[OR] = {};   // recorded behind O(k)'s tail (re-projection + index build) on the chain's stream
-    hipEvent_t tm_a[OR] = {}, tm_b[OR] = {};   // chain timer of step k % OR (this thread's own)
-    bool tm_pending[OR] = {};
+    LazyTimer tm[OR];                    // chain timer of step k % OR (the chain's thread's own)
     std::atomic<float> ms{0.f};          // length of the chain's most recent timed pass on its HIP stream
     double tr[4] = {0, 0, 0, 0};
     std::atomic<float> last_us{0.f};     // host time of the chain's most recent pass (LOAMX_PIPE_TRACE)
@@ -202,18 +220,6 @@ class Pipeline {
   std::vector<char> launched;
   PinBuf<uint32_t> h_off3[OR];
   hipEvent_t evF[OR][2] = {};
-  // stage timers are read lazily (an elapsed time is taken once both events have completed) so that measuring never
-  // makes the host wait for a stage
-  struct LazyTimer {
-    hipEvent_t a = nullptr, b = nullptr;
-    bool pending = false;
-    float ms = 0.f;
-    void create() { if (!a) { LX_HIP(hipEventCreate(&a)); LX_HIP(hipEventCreate(&b)); } }
-    void resolve() {
-      if (pending && hipEventQuery(b) == hipSuccess) { LX_HIP(hipEventElapsedTime(&ms, a, b)); pending = false; }
-    }
-    void destroy() { if (a) { (void)hipEventDestroy(a); (void)hipEventDestroy(b); a = b = nullptr; } }
-  };
   LazyTimer tmM[2];   // registration: by step parity (the odometry chains keep their own timers, OdomChain)
   float feat_ms[OR] = {};
   int f_hi = -1;                       // features of steps <= f_hi have been launched (calling thread)
@@ -230,119 +236,31 @@ class Pipeline {
   // depends on its O(k-1) and on the features F(k), never on a registration (separate ROS nodes in the reference) and never on another
   // stream, so a chain goes on to O(k+1) as soon as its O(k) is done, up to depth() steps ahead of the step being registered —
   // registration and odometry are serial chains across steps and the slowest sets the pace, not their sum.  The calling thread launches
-  // the features (the only thread that does) and raises o_limit; every chain publishes its own `done`.  Results wait in a ring of
-  // OR slots, the re-projected clouds in rotating buffers (OdometryBatch::set_keep), so step k's inputs stay valid while O(k+1) ...
-  // O(k+depth) run.  Hand-overs happen every ~0.4 ms, so both sides spin briefly before they fall back to the condition variable (a
-  // sleeping thread costs tens of microseconds to wake, on the critical path of every step).
+  // the features (the only thread that does) and raises the gate's limit; every chain publishes its own position.  Results wait in a
+  // ring of OR slots, the re-projected clouds in rotating buffers (OdometryBatch::set_keep), so step k's inputs stay valid while O(k+1)
+  // ... O(k+depth) run.  The gate itself — limit, positions, worker threads, the kept error — is odom_lookahead.hpp.
   std::vector<OdomPub> ores[OR];       // [step % OR][stream]; a chain writes its own streams only
-  std::mutex mu;
-  std::condition_variable cv;
-  std::atomic<int> o_limit{-1};        // the chains may run steps <= o_limit (raised by the calling thread only)
-  bool quit = false;
-  std::exception_ptr job_err;
-  int done_min() const { int m = INT32_MAX; for (auto& c : chains) m = std::min(m, c->done.load(std::memory_order_acquire)); return m; }
-  int done_max() const { int m = -1; for (auto& c : chains) m = std::max(m, c->done.load(std::memory_order_acquire)); return m; }
-  bool any_busy() const { for (auto& c : chains) if (c->busy.load(std::memory_order_acquire)) return true; return false; }
-  static bool spin_until(const std::function<bool()>& ready, double max_us) {
-    const auto t0 = std::chrono::steady_clock::now();
-    while (!ready()) {
-      if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > max_us) return false;
-      cpu_relax();
-    }
-    return true;
-  }
-  void worker_main(OdomChain* cp) {
-    OdomChain& c = *cp;
-    (void)hipSetDevice(device);
-    for (;;) {
-      auto ready = [&] { return c.next.load(std::memory_order_acquire) <= o_limit.load(std::memory_order_acquire); };
-      static const double spin_us = diag_env("LOAMX_SPIN_US") ? atof(diag_env("LOAMX_SPIN_US")) : 400.0;   // diagnostic
-      if (!spin_until(ready, spin_us)) {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return ready() || quit; });
-        if (quit) return;
-      }
-      {
-        std::lock_guard<std::mutex> lk(mu);   // (busy and o_limit change under the mutex: park_odometry() relies on seeing them together)
-        if (quit) return;
-        if (!ready()) continue;
-        c.busy.store(true, std::memory_order_release);
-      }
-      std::exception_ptr err;
-      const int k = c.next.load(std::memory_order_acquire);
-      try {
-        const auto tc0 = std::chrono::steady_clock::now();
-        c.tr[0] = tr_us(); run_odometry(c, (uint32_t)k); c.tr[3] = tr_us();
-        c.last_us.store((float)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tc0).count(), std::memory_order_relaxed);
-      } catch (...) { err = std::current_exception(); }
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        if (err) { if (!job_err) job_err = err; o_limit.store(-1, std::memory_order_release); }   // every chain stops; the calling thread rethrows
-        else { c.next.store(k + 1, std::memory_order_release); c.done.store(k, std::memory_order_release); }
-        c.busy.store(false, std::memory_order_release);
-      }
-      cv.notify_all();
-    }
-  }
-  // calling thread: allow the odometry chains to run up to step k
-  void allow_odometry(int k) {
-    if (k <= o_limit.load(std::memory_order_acquire)) return;
-    for (auto& c : chains)
-      if (!c->worker.joinable()) { OdomChain* cp = c.get(); c->worker = std::thread([this, cp] { worker_main(cp); }); }
-    { std::lock_guard<std::mutex> lk(mu); o_limit.store(k, std::memory_order_release); }
-    cv.notify_all();
-  }
-  // calling thread: block until O(t) of every chain is published (rethrows a failure of a worker)
-  void wait_odometry(int t) {
-    auto ready = [&] { return done_min() >= t || (!any_busy() && o_limit.load(std::memory_order_acquire) < t); };
-    if (!spin_until(ready, 2000.0)) {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, ready);
-    }
-    std::lock_guard<std::mutex> lk(mu);
-    if (job_err) { std::exception_ptr e = job_err; job_err = nullptr; std::rethrow_exception(e); }
-    LX_REQUIRE(done_min() >= t, "internal: an odometry chain stopped before the requested step");
+  std::unique_ptr<LookAhead> la;
+  // a worker's job: one step of one chain, with the chain's trace stamps
+  void run_chain_step(OdomChain& c, uint32_t k) {
+    const auto tc0 = std::chrono::steady_clock::now();
+    c.tr[0] = tr_us(); run_odometry(c, k); c.tr[3] = tr_us();
+    c.last_us.store((float)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tc0).count(), std::memory_order_relaxed);
   }
   // calling thread: block until the look-ahead has finished every step it has been allowed to run (its kernels are enqueued then:
   // a device synchronisation afterwards covers them).  Returns the last step whose odometry is published for every stream, -1 if none.
-  int drain_lookahead() {
-    const int lim = o_limit.load(std::memory_order_acquire);
-    if (prefetch && lim >= 0 && chains[0]->worker.joinable()) wait_odometry(lim);
-    return done_min();
-  }
-  // calling thread: stop the look-ahead and wait until every worker is idle.  restart >= 0: chains that have not reached that step
-  // continue there (the caller jumped); restart < 0: every chain continues where it IS — the positions are read AFTER the workers
-  // have gone idle, under the mutex (a position read before the wait is stale by the step a worker was inside: ADVICE.md round 3)
+  int drain_lookahead() { return prefetch ? la->drain() : la->done_min(); }
+  // calling thread: stop the look-ahead and wait until every worker is idle (LookAhead::park).  restart >= 0: the caller jumped
   void park_odometry(int restart) {
     if (restart >= 0) pre_t = -1;   // (a pre-staged re-projection belongs to the run that is abandoned)
-    std::unique_lock<std::mutex> lk(mu);
-    o_limit.store(-1, std::memory_order_release);
-    cv.wait(lk, [&] { return !any_busy(); });
-    if (restart >= 0)
-      for (auto& c : chains)
-        if (restart > c->done.load() && restart != c->next.load()) {
-          c->next.store(restart, std::memory_order_release);
-          c->done.store(restart - 1, std::memory_order_release);
-        }
-    job_err = nullptr;
-  }
-  // (upload / first use of the streaming ring: every chain starts over at step 0)
-  void reset_odometry() {
-    std::unique_lock<std::mutex> lk(mu);
-    o_limit.store(-1, std::memory_order_release);
-    cv.wait(lk, [&] { return !any_busy(); });
-    for (auto& c : chains) { c->next.store(0, std::memory_order_release); c->done.store(-1, std::memory_order_release); }
-    job_err = nullptr;
+    la->park(restart);
   }
 
   ~Pipeline() {
-    { std::lock_guard<std::mutex> lk(mu); quit = true; o_limit.store(-1, std::memory_order_release); }
-    cv.notify_all();   // (a worker leaves its spin phase after 0.4 ms and then sees quit)
-    for (auto& c : chains) if (c->worker.joinable()) c->worker.join();
+    la.reset();   // (joins the workers)
     for (auto& c : chains) {
       for (auto& e : c->ev_tail) if (e) (void)hipEventDestroy(e);
-      for (auto& e : c->tm_a) if (e) (void)hipEventDestroy(e);
-      for (auto& e : c->tm_b) if (e) (void)hipEventDestroy(e);
+      for (auto& tm : c->tm) tm.destroy();
     }
     fx.clear();
     for (auto& a : evF) for (auto& e : a) if (e) (void)hipEventDestroy(e);
@@ -367,85 +285,74 @@ class Pipeline {
     }
     PinBuf<uint32_t>& hb = h_off3[t % OR];
     hb.reserve(3 * (ns + 1) + nring + 2);
-    uint32_t* ho[3] = {hb.p, hb.p + (ns + 1), hb.p + 2 * (ns + 1)};
-    uint32_t* hlf = hb.p + 3 * (ns + 1);
     for (auto& e : evF[t % OR]) if (!e) LX_HIP(hipEventCreate(&e));
     LX_HIP(hipEventRecord(evF[t % OR][0], fstream));
     F.run_async();
-    // (the four offset tables lie back to back on the device in exactly this host layout: one copy)
-    (void)ho; (void)hlf;
+    // (the four offset tables lie back to back on the device in the host layout run_odometry() reads: one copy)
     LX_REQUIRE(F.n_offsets() == 3 * (ns + 1) + nring + 1, "internal: offset table layout");
     store_to_pinned_u32(hb.p, F.d_offsets(), F.n_offsets(), fstream);   // (by a kernel: a small device-to-host hipMemcpyAsync blocks its caller for milliseconds now and then — pinned_copy.hpp)
     LX_HIP(hipEventRecord(evF[t % OR][1], fstream));
     LA(t) = 1;
   }
 
-  void upload(uint32_t n_steps, const loamx_cloud* clouds, const uint32_t* const* ring_size, const uint32_t* n_rings) {
-    LX_REQUIRE(n_steps >= 1 && clouds && ring_size && n_rings, "invalid argument");
-    LX_HIP(hipSetDevice(device));
+  std::unique_ptr<FeatureExtractor> new_extractor_() {
+    auto f = std::make_unique<FeatureExtractor>(device, fstream);
+    f->params = feat_params_from(fcfg);
+    return f;
+  }
+  // (upload / first use of the streaming ring) the feature stream, idle, and no extractor left on it
+  void feature_stream_() {
     if (!fstream) fstream = create_stream(env_priority("LOAMX_PRIO_FEAT", -1), diag_env("LOAMX_FEAT_CU_STRIDE") ? atoi(diag_env("LOAMX_FEAT_CU_STRIDE")) : 0, /*part=*/1);
     LX_HIP(hipStreamSynchronize(fstream));
     fx.clear();
-    streaming = false;
+  }
+  // ... and the input starts over with n_slots slots: every chain back to step 0
+  void restart_input_(uint32_t n_slots, bool ring) {
+    streaming = ring;
     staged_hi = 0;
     last_step = -1;
-    launched.assign(n_steps, 0);
-    reset_odometry();
+    launched.assign(n_slots, 0);
+    la->reset();
     f_hi = -1;
+  }
+
+  void upload(uint32_t n_steps, const loamx_cloud* clouds, const uint32_t* const* ring_size, const uint32_t* n_rings) {
+    LX_REQUIRE(n_steps >= 1 && clouds && ring_size && n_rings, "invalid argument");
+    LX_HIP(hipSetDevice(device));
+    feature_stream_();
+    restart_input_(n_steps, false);
     for (uint32_t t = 0; t < n_steps; t++) {
-      auto f = std::make_unique<FeatureExtractor>(device, fstream);
-      FeatParams& p = f->params;
-      p.scan_period = fcfg.scan_period;
-      p.n_regions = fcfg.n_feature_regions;
-      p.curv_region = fcfg.curvature_region;
-      p.max_sharp = fcfg.max_corner_sharp;
-      p.max_less_sharp = fcfg.max_corner_less_sharp == 0 ? 10 * fcfg.max_corner_sharp : fcfg.max_corner_less_sharp;
-      p.max_flat = fcfg.max_surface_flat;
-      p.less_flat_leaf = fcfg.less_flat_filter_size;
-      p.curv_thr = fcfg.surface_curvature_threshold;
+      auto f = new_extractor_();
       f->upload(n_streams_, clouds + (size_t)t * n_streams_, ring_size + (size_t)t * n_streams_, n_rings + (size_t)t * n_streams_);
       fx.push_back(std::move(f));
     }
   }
 
-  void ensure_streaming_(uint32_t t) {
+  // what stage_step*(t) requires before it touches slot t % RING (`entry` names the entry point in the error text)
+  void begin_staging_(uint32_t t, const char* entry) {
+    LX_HIP(hipSetDevice(device));
     if (!streaming) {   // first use: switch to the ring of slots
       LX_REQUIRE(t == 0, "streaming input starts at step 0");
-      if (!fstream) fstream = create_stream(env_priority("LOAMX_PRIO_FEAT", -1), diag_env("LOAMX_FEAT_CU_STRIDE") ? atoi(diag_env("LOAMX_FEAT_CU_STRIDE")) : 0, /*part=*/1);
-      LX_HIP(hipStreamSynchronize(fstream));
-      fx.clear();
-      for (uint32_t k = 0; k < RING; k++) {
-        auto f = std::make_unique<FeatureExtractor>(device, fstream);
-        FeatParams& p = f->params;
-        p.scan_period = fcfg.scan_period;
-        p.n_regions = fcfg.n_feature_regions;
-        p.curv_region = fcfg.curvature_region;
-        p.max_sharp = fcfg.max_corner_sharp;
-        p.max_less_sharp = fcfg.max_corner_less_sharp == 0 ? 10 * fcfg.max_corner_sharp : fcfg.max_corner_less_sharp;
-        p.max_flat = fcfg.max_surface_flat;
-        p.less_flat_leaf = fcfg.less_flat_filter_size;
-        p.curv_thr = fcfg.surface_curvature_threshold;
-        fx.push_back(std::move(f));
-      }
-      launched.assign(RING, 0);
+      feature_stream_();
+      for (uint32_t k = 0; k < RING; k++) fx.push_back(new_extractor_());
       if (!cstream) cstream = create_stream(0);
       for (auto& e : ev_stage) if (!e) LX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      streaming = true;
-      staged_hi = 0;
-      last_step = -1;
-      reset_odometry();
-      f_hi = -1;
+      restart_input_(RING, true);   // (streaming is set once the ring stands: a failure above leaves the set-up to be done again)
     }
+    LX_REQUIRE(t == staged_hi.load(), "steps must be staged in order");
+    LX_REQUIRE(t < RING || last_step.load() + (long)RING >= (long)t, std::string(entry) + "(t) needs step(t - 8) to have run: only eight steps can be in flight");
+  }
+  // ... and its end: step t is published to step() (release) after everything of it is enqueued
+  void publish_staged_(uint32_t t) {
+    LA(t) = 0;
+    staged_hi.store(t + 1, std::memory_order_release);
   }
 
   // Streaming input: stage ONE step (sweep s of the step = clouds[s]) without blocking; steps arrive in order.  Slot t % RING
   // is free once step t - RING has been registered, which the caller's own order of calls guarantees (stage(t) after step(t - RING)).
   void stage_step(uint32_t t, const loamx_cloud* clouds, const uint32_t* const* ring_size, const uint32_t* n_rings) {
     LX_REQUIRE(clouds && ring_size && n_rings, "invalid argument");
-    LX_HIP(hipSetDevice(device));
-    ensure_streaming_(t);
-    LX_REQUIRE(t == staged_hi.load(), "steps must be staged in order");
-    LX_REQUIRE(t < RING || last_step.load() + (long)RING >= (long)t, "stage_step(t) needs step(t - 8) to have run: only eight steps can be in flight");
+    begin_staging_(t, "stage_step");
     TraceRange trace_range("loamx:pipeline:stage_step");
     if (t > 0) finalize_raw(t - 1);
     rawslot[t % RING].raw = false;
@@ -486,8 +393,7 @@ class Pipeline {
     } else {
       fx[slot]->upload_async(n_streams_, clouds, ring_size, n_rings, cstream, ev_stage[slot]);
     }
-    LA(t) = 0;
-    staged_hi.store(t + 1, std::memory_order_release);
+    publish_staged_(t);
   }
 
   // Raw input: step t as the sensor delivered it — per stream one revolution of (x, y, z) records in sensor axes and firing
@@ -514,10 +420,7 @@ class Pipeline {
   }
   void stage_records_(uint32_t t, const void* const* raw_xyz, const uint32_t* counts, uint32_t stride, const SensorParams& model,
                       const double* scan_time) {
-    LX_HIP(hipSetDevice(device));
-    ensure_streaming_(t);
-    LX_REQUIRE(t == staged_hi.load(), "steps must be staged in order");
-    LX_REQUIRE(t < RING || last_step.load() + (long)RING >= (long)t, "stage_step_raw(t) needs step(t - 8) to have run: only eight steps can be in flight");
+    begin_staging_(t, "stage_step_raw");
     TraceRange trace_range("loamx:pipeline:stage_step_raw");
     if (t > 0) finalize_raw(t - 1);   // the IMU state machine advances sweep by sweep: this step's table needs the previous reset
     const uint32_t ns = n_streams_, nr = model.M.n_rings;
@@ -596,8 +499,7 @@ class Pipeline {
     LX_HIP(hipMemcpyAsync(R.h_ring_cnt.p, R.d_ring_cnt.p, sizeof(uint32_t) * ns * nr, hipMemcpyDeviceToHost, cstream));
     LX_HIP(hipMemcpyAsync(R.h_last.p, R.d_last.p, sizeof(ImuLast) * ns, hipMemcpyDeviceToHost, cstream));
     LX_HIP(hipEventRecord(R.ev_ingest, cstream));
-    LA(t) = 0;
-    staged_hi.store(t + 1, std::memory_order_release);
+    publish_staged_(t);
   }
 
   // second half of a raw step's staging, once its binning has finished (long before it is needed in steady state): the IMU
@@ -716,28 +618,16 @@ class Pipeline {
                                F.d_feat(2) + ho[2][s], ho[2][s + 1] - ho[2][s], F.d_less_flat() + la, lb - la};
     }
     const int slot = (int)(t % OR);
-    if (timed) {   // this chain's own event pair for this step: both ends are recorded by this thread in this call
-      if (!c.tm_a[slot]) { LX_HIP(hipEventCreate(&c.tm_a[slot])); LX_HIP(hipEventCreate(&c.tm_b[slot])); }
-      c.tm_pending[slot] = false;
-      LX_HIP(hipEventRecord(c.tm_a[slot], odom.stream()));
-    }
+    if (timed) c.tm[slot].start(odom.stream());   // this chain's own event pair for this step: both ends are recorded by this thread in this call
     if (streaming && rawslot[t % RING].raw)   // imuTrans of this sweep (ScanRegistration publishes it with the clouds; LaserOdometry.cpp:239-248)
       for (uint32_t s = c.s0; s < c.s1; s++) odom.update_imu(s - c.s0, &rawslot[t % RING].imu_trans[12 * (size_t)s]);
     odom.process(in.data(), rc.data(), true);   // returns once the poses are known; clouds ready at odom.tail_event()
     c.tr[2] = tr_us();
     if (!c.ev_tail[slot]) LX_HIP(hipEventCreateWithFlags(&c.ev_tail[slot], hipEventDisableTiming));
     LX_HIP(hipEventRecord(c.ev_tail[slot], odom.stream()));   // behind the tail that process() enqueued
-    if (timed) {   // the chain of step t = everything process() enqueued, tail included
-      LX_HIP(hipEventRecord(c.tm_b[slot], odom.stream()));
-      c.tm_pending[slot] = true;
-    }
-    for (int k = 0; k < OR; k++)   // (the elapsed time of an older step is taken once its events have completed: measuring never waits)
-      if (c.tm_pending[k] && hipEventQuery(c.tm_b[k]) == hipSuccess) {
-        float ms = 0.f;
-        LX_HIP(hipEventElapsedTime(&ms, c.tm_a[k], c.tm_b[k]));
-        c.tm_pending[k] = false;
-        c.ms.store(ms, std::memory_order_relaxed);
-      }
+    if (timed) c.tm[slot].stop(odom.stream());   // the chain of step t = everything process() enqueued, tail included
+    for (auto& tm : c.tm)   // (the elapsed time of an older step is taken once its events have completed: measuring never waits)
+      if (tm.resolve()) c.ms.store(tm.ms, std::memory_order_relaxed);
     for (uint32_t s = c.s0; s < c.s1; s++) {
       const uint32_t l = s - c.s0;
       OdomStream& O = odom.stream_state(l);
@@ -760,7 +650,7 @@ class Pipeline {
     static const bool off = !(diag_env("LOAMX_PRESTAGE") && atoi(diag_env("LOAMX_PRESTAGE")) != 0);   // measured: no gain (15.44 k with, 15.51 k without; profiles/r04_ab.md) — the step is not bound by this copy + kernel; opt-in
     if (off || !prefetch || pre_t == tn || tn > last_staged || tn < 1) return;
     const uint32_t ns = n_streams_;
-    if (done_min() < tn) return;
+    if (la->done_min() < tn) return;
     FeatureExtractor& F = FX((uint32_t)tn);
     std::vector<const float4*> fsrc;
     std::vector<uint32_t> nfr;
@@ -794,187 +684,195 @@ class Pipeline {
   std::chrono::steady_clock::time_point tr0, tr_exit = std::chrono::steady_clock::now();
   double tr_us() const { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tr0).count(); }
 
-  int step(uint32_t t) {
-    TraceRange trace_range("loamx:pipeline:step");
-    LX_REQUIRE(t < n_staged(), "step index beyond the staged sweeps");
-    LX_REQUIRE(!streaming || t + RING >= staged_hi.load(), "this step's slot has been re-staged already");   // (slot t % RING is rewritten by staging step t + RING)
-    const auto t_entry = std::chrono::steady_clock::now();
-    const double gap_us = std::chrono::duration<double, std::micro>(t_entry - tr_exit).count();   // the caller's time between two steps
-    tr0 = t_entry;
-    double trM[6] = {0, 0, 0, 0, 0, 0};
-    LX_HIP(hipSetDevice(device));
-    hipStream_t s_ = reg.stream();
-    const uint32_t ns = n_streams_;
-    // ---- this step's odometry: published by the look-ahead (the normal case), or run now
-    const int ti = (int)t, last_staged = (int)n_staged() - 1;
-    {
-      bool jump = false;   // a chain for which this is neither a finished step nor its next one: the caller jumped, the chains restart here
-      for (auto& c : chains) jump = jump || (ti > c->done.load(std::memory_order_acquire) && ti != c->next.load(std::memory_order_acquire));
-      if (jump) {
-        park_odometry(ti);
-        f_hi = ti - 1;
-      }
-      LX_REQUIRE(ti + (OR - 2) >= done_max(), "this step's odometry results have been overwritten: steps run in order");
+  // what the stages of one step() share
+  struct Step {
+    uint32_t t = 0;
+    int ti = 0, last_staged = -1;
+    LookaheadWindow w;               // how far features / odometry are released at each point of this step (odom_lookahead.hpp)
+    bool late_pending = false;       // the late release is still to come
+    hipStream_t s_ = nullptr;        // the registrar's stream
+    std::vector<uint32_t> who;       // the streams that are registered (a stream's first sweep only initialises the odometry), in
+    std::vector<const float4*> cl, sl, fsrc;   // order; everything below is indexed like it
+    std::vector<uint32_t> ncl, nsl, nfr;
+    std::vector<float> guess;
+    std::vector<ToEndParams> to_end;
+    uint32_t nw = 0;                 // = who.size()
+    float f_ms = 0.f;
+    double gap_us = 0, tr[5] = {0, 0, 0, 0, 0};   // trace marks: M-start, M-enqueued, M-downloaded, O-joined, download-wait
+  };
+  // features of the steps up to k (launched by the calling thread only, in step order)
+  void launch_features_upto(int k) {
+    while (f_hi < k) { ++f_hi; if (!LA((uint32_t)f_hi)) launch_features((uint32_t)f_hi); }
+  }
+
+  // 1. this step's odometry: published by the look-ahead (the normal case), or run now
+  void join_odometry_(Step& S) {
+    const uint32_t t = S.t;
+    const int ti = S.ti;
+    if (la->jumped(ti)) {   // for some chain this is neither a finished step nor its next one: the caller jumped, the chains restart here
+      park_odometry(ti);
+      f_hi = ti - 1;
     }
-    auto launch_upto = [&](int k) {   // features of the steps up to k (launched by this thread only, in step order)
-      if (k > last_staged) k = last_staged;
-      while (f_hi < k) { ++f_hi; if (!LA((uint32_t)f_hi)) launch_features((uint32_t)f_hi); }
-    };
-    if (ti > done_min()) {
-      launch_upto(prefetch ? ti + 1 : ti);
+    LX_REQUIRE(ti + (OR - 2) >= la->done_max(), "this step's odometry results have been overwritten: steps run in order");
+    if (ti > la->done_min()) {
+      launch_features_upto(S.w.feat_join);
       if (prefetch) {
-        allow_odometry(std::min(ti + 1, last_staged));
-        wait_odometry(ti);
+        la->allow(S.w.odom_join);
+        la->wait(ti);
       } else {
-        if (o_limit.load(std::memory_order_acquire) >= 0) park_odometry(-1);   // the look-ahead was switched off: the chains go on here
-        for (auto& c : chains)
-          if (ti > c->done.load(std::memory_order_acquire)) {
-            run_odometry(*c, t);
-            c->next.store(ti + 1, std::memory_order_release);
-            c->done.store(ti, std::memory_order_release);
-          }
+        if (la->limit() >= 0) park_odometry(-1);   // the look-ahead was switched off: the chains go on here
+        for (uint32_t g = 0; g < n_groups; g++)
+          if (ti > la->done(g)) { run_odometry(*chains[g], t); la->ran_inline(g, ti); }
       }
     }
     LA(t) = 0;   // every chain has consumed the step's features (a restart at this step extracts them again: their offsets' slot is reused by step t + 3)
-    for (uint32_t s = 0; s < ns; s++) st[s].cur = ores[t % OR][s];
-    FeatureExtractor& F = FX(t);
-    const float f_ms = feat_ms[t % OR];
+    for (uint32_t s = 0; s < n_streams_; s++) st[s].cur = ores[t % OR][s];
+    S.f_ms = feat_ms[t % OR];
     // the re-projected "last" clouds of THIS sweep are produced at the tails of the odometry chains
-    for (auto& c : chains) LX_HIP(hipStreamWaitEvent(s_, c->ev_tail[t % OR], 0));
-    // ---- look-ahead while M(t) runs: the odometry chain may go on to step t+1 now and — once M(t) is enqueued and the features
-    // of step t+2 are launched (while this thread waits for M(t)'s first look at the flags) — to step t+2
-    // (D steps of odometry look-ahead, FD >= 2 of features: in steady state the first two calls find nothing to do — the previous
-    // step's launch_f2 went that far — and the one new step of features / odometry is released by launch_f2, off M(t)'s critical path)
-    const int D = depth(), FD = std::max(D, 2);
-    if (prefetch) {
-      launch_upto(ti + FD - 1);
-      allow_odometry(std::min(ti + std::min(D, FD - 1), last_staged));
+    for (auto& c : chains) LX_HIP(hipStreamWaitEvent(S.s_, c->ev_tail[t % OR], 0));
+  }
+  // 2. look-ahead while M(t) runs: the odometry chains may go on now, and further once M(t) is enqueued (release_late_).  In steady
+  // state this call and the one in join_odometry_ find nothing to do — the previous step's late release went that far — and the one
+  // new step of features / odometry is released by release_late_, off M(t)'s critical path
+  void release_lookahead_(Step& S) {
+    launch_features_upto(S.w.feat_reg);
+    la->allow(S.w.odom_reg);
+    S.late_pending = S.w.late;
+  }
+  // ... the late part: reached from the registration's first host wait (reg.on_first_wait) and again behind run_async(); once in effect
+  void release_late_(Step& S) {
+    if (!S.late_pending) return;
+    S.late_pending = false;
+    launch_features_upto(S.w.feat_late);
+    la->allow(S.w.odom_late);
+  }
+  // 3. what the registration of the registered streams reads: the odometry's clouds, the initial guesses, the full-resolution sources
+  void gather_inputs_(Step& S) {
+    S.tr[0] = tr_us();
+    if (timing) tmM[S.t & 1].start(S.s_);
+    const uint32_t ns = n_streams_;
+    FeatureExtractor& F = FX(S.t);
+    S.cl.resize(ns); S.sl.resize(ns); S.fsrc.resize(ns);
+    S.ncl.resize(ns); S.nsl.resize(ns); S.nfr.resize(ns);
+    for (uint32_t s = 0; s < ns; s++) {
+      PipeStreamState& P = st[s];
+      if (P.cur.rc != LOAMX_OK) continue;   // a stream's first sweep only initialises the odometry
+      transform_associate_to_map(P.cur.transform_sum, P.bef, P.aft, P.incre, P.tobe);
+      float g[6];
+      P.tobe.get(g);
+      S.guess.insert(S.guess.end(), g, g + 6);
+      const uint32_t k = (uint32_t)S.who.size();
+      S.cl[k] = P.cur.last_corner; S.ncl[k] = P.cur.n_last_corner;
+      S.sl[k] = P.cur.last_surf; S.nsl[k] = P.cur.n_last_surf;
+      S.fsrc[k] = F.d_cloud() + F.point_base(s);
+      S.nfr[k] = F.point_base(s + 1) - F.point_base(s);
+      S.to_end.push_back(P.cur.to_end);
+      S.who.push_back(s);
     }
-    bool f2_pending = prefetch && ti + 2 <= last_staged;
-    auto launch_f2 = [&]() {
-      if (f2_pending) { f2_pending = false; launch_upto(ti + FD); if (D >= 2) allow_odometry(std::min(ti + D, last_staged)); }
-    };
+    S.nw = (uint32_t)S.who.size();
+  }
+  // 4. the full-resolution clouds are re-projected to the sweep end before they are registered (LaserOdometry.cpp:326): one fused
+  // kernel writes them straight into the registrar's staging area — unless the previous step pre-staged them (prestage_gather)
+  void stage_full_res_(Step& S) {
+    if (!S.nw) { last_full_off.clear(); last_who.clear(); return; }
+    const uint32_t nw = S.nw;
+    std::vector<uint32_t> foff(nw + 1, 0);
+    for (uint32_t k = 0; k < nw; k++) foff[k + 1] = foff[k] + S.nfr[k];
+    const bool adopted = pre_t == S.ti && reg.adopt_full_next(nw, S.nfr.data());   // re-projected already, behind the previous step's first iterations
+    pre_t = -1;
+    if (!adopted) {
+      if (reg.double_buffer_full) {   // this run reuses the buffer of the run before last: its download must have finished
+        const int par = (int)(run_count & 1);
+        const double tw0 = trace ? tr_us() : 0.0;
+        hostlink.wait(par);   // (two steps old: landed long ago)
+        if (trace) S.tr[4] = tr_us() - tw0;
+        if (d2h_pending[par]) { LX_HIP(hipStreamWaitEvent(S.s_, ev_d2h[par], 0)); d2h_pending[par] = false; }
+      }
+      float4* full_dst = reg.stage_full(nw, S.nfr.data());
+      chains[0]->ob->to_end_gather(full_dst, foff.data(), S.fsrc.data(), S.to_end.data(), nw, S.s_);
+    }
+    last_full_off = foff;
+    last_who = S.who;
+    run_count++;
+  }
+  // 5. registration against the frozen sub-map: enqueue everything for M(t)
+  void enqueue_registration_(Step& S) {
+    if (!S.nw) return;
+    const uint32_t nw = S.nw;
+    const RawSlot& R = rawslot[S.t % RING];
+    reg.upload_device(nw, S.cl.data(), S.ncl.data(), S.sl.data(), S.nsl.data(), nullptr, nullptr, S.guess.data());
+    // transformUpdate's IMU blend (BasicLaserMapping.cpp:171-200) changes transformTobeMapped BEFORE the full-resolution cloud is
+    // registered (:235-240): a step with mapping-side IMU data for any of its streams registers its clouds after the blend
+    bool blend = false;
+    static const bool no_blend = diag_env("LOAMX_NO_MAP_IMU_BLEND") != nullptr;   // (tests: what the poses would be without the blend)
+    if (!no_blend && streaming && R.raw && !R.scan_time.empty())
+      for (uint32_t k = 0; k < nw; k++) blend = blend || R.map_imu_upto[S.who[k]] > 0;
+    reg.defer_full = blend;
+    reg.on_first_wait = [&]() { release_late_(S); prestage_gather(S.ti + 1, S.last_staged, S.s_); };
+    reg.run_async();
+    reg.on_first_wait = nullptr;
+    if (blend) {
+      std::vector<float> p6(6 * (size_t)nw);
+      reg.download(p6.data(), nullptr);
+      if (reg.submap_sufficient())   // (transformUpdate is only reached when the optimisation ran, :628-629)
+        for (uint32_t k = 0; k < nw; k++)
+          (void)map_imu_blend(S.who[k], R.map_imu_upto[S.who[k]], R.scan_time[S.who[k]], fcfg.scan_period, &p6[6 * (size_t)k]);
+      reg.finish_with_poses(p6.data());
+      reg.defer_full = false;
+    }
+    if (reg.double_buffer_full) {
+      if (!ev_reg_done) LX_HIP(hipEventCreateWithFlags(&ev_reg_done, hipEventDisableTiming));
+      LX_HIP(hipEventRecord(ev_reg_done, S.s_));
+    }
+  }
+  // 6. what may follow M(t)'s launches: the late release and the next step's pre-staging (no-ops when the first wait's callback did them)
+  void release_behind_registration_(Step& S) {
+    release_late_(S);
+    if (S.nw) prestage_gather(S.ti + 1, S.last_staged, S.s_);
+    if (timing) tmM[S.t & 1].stop(S.s_);
+    S.tr[1] = tr_us();
+  }
+  // 7. finish M(t): poses and statistics of the registered streams
+  int collect_(Step& S) {
     int ret = LOAMX_SKIPPED;
-    try {
-      trM[0] = tr_us();
-      // ---- registration against the frozen sub-map: enqueue everything for M(t)
-      LazyTimer& tm = tmM[t & 1];
-      if (timing) {
-        tm.create();
-        tm.pending = false;
-        LX_HIP(hipEventRecord(tm.a, s_));
-      }
-      std::vector<const float4*> cl(ns), sl(ns), fsrc(ns);
-      std::vector<uint32_t> ncl(ns), nsl(ns), nfr(ns), who;
-      std::vector<float> guess;
-      std::vector<ToEndParams> tep;
-      for (uint32_t s = 0; s < ns; s++) {
-        PipeStreamState& P = st[s];
-        if (P.cur.rc != LOAMX_OK) continue;   // a stream's first sweep only initialises the odometry
-        transform_associate_to_map(P.cur.transform_sum, P.bef, P.aft, P.incre, P.tobe);
-        float g[6];
-        P.tobe.get(g);
-        guess.insert(guess.end(), g, g + 6);
-        const uint32_t k = (uint32_t)who.size();
-        cl[k] = P.cur.last_corner; ncl[k] = P.cur.n_last_corner;
-        sl[k] = P.cur.last_surf; nsl[k] = P.cur.n_last_surf;
-        fsrc[k] = F.d_cloud() + F.point_base(s);
-        nfr[k] = F.point_base(s + 1) - F.point_base(s);
-        tep.push_back(P.cur.to_end);
-        who.push_back(s);
-      }
-      const uint32_t nw = (uint32_t)who.size();
-      if (nw) {
-        // the full-resolution clouds are re-projected to the sweep end before they are registered (LaserOdometry.cpp:326):
-        // one fused kernel writes them straight into the registrar's staging area
-        std::vector<uint32_t> foff(nw + 1, 0);
-        for (uint32_t k = 0; k < nw; k++) foff[k + 1] = foff[k] + nfr[k];
-        const bool adopted = pre_t == ti && reg.adopt_full_next(nw, nfr.data());   // re-projected already, behind the previous step's first iterations
-        pre_t = -1;
-        if (!adopted) {
-          if (reg.double_buffer_full) {   // this run reuses the buffer of the run before last: its download must have finished
-            const int par = (int)(run_count & 1);
-            const double tw0 = trace ? tr_us() : 0.0;
-            hostlink.wait(par);   // (two steps old: landed long ago)
-            if (trace) trM[4] = tr_us() - tw0;
-            if (d2h_pending[par]) { LX_HIP(hipStreamWaitEvent(s_, ev_d2h[par], 0)); d2h_pending[par] = false; }
-          }
-          float4* full_dst = reg.stage_full(nw, nfr.data());
-          chains[0]->ob->to_end_gather(full_dst, foff.data(), fsrc.data(), tep.data(), nw, s_);
+    if (S.nw) {
+      std::vector<float> poses(6 * (size_t)S.nw);
+      std::vector<SweepStats> ss(S.nw);
+      reg.download(poses.data(), nullptr);
+      reg.download_stats(ss.data());
+      for (uint32_t k = 0; k < S.nw; k++) {
+        PipeStreamState& P = st[S.who[k]];
+        P.map_stats = ss[k];
+        P.mapped = true;
+        if (reg.submap_sufficient()) {   // transformUpdate (BasicLaserMapping.cpp:171-203, :628-629)
+          P.tobe.set(&poses[6 * (size_t)k]);
+          P.bef = P.cur.transform_sum;
+          P.aft = P.tobe;
         }
-        last_full_off = foff;
-        last_who = who;
-        run_count++;
-        reg.upload_device(nw, cl.data(), ncl.data(), sl.data(), nsl.data(), nullptr, nullptr, guess.data());
-        // transformUpdate's IMU blend (BasicLaserMapping.cpp:171-200) changes transformTobeMapped BEFORE the full-resolution cloud is
-        // registered (:235-240): a step with mapping-side IMU data for any of its streams registers its clouds after the blend
-        bool blend = false;
-        static const bool no_blend = diag_env("LOAMX_NO_MAP_IMU_BLEND") != nullptr;   // (tests: what the poses would be without the blend)
-        if (!no_blend && streaming && rawslot[t % RING].raw && !rawslot[t % RING].scan_time.empty())
-          for (uint32_t k = 0; k < nw; k++) blend = blend || rawslot[t % RING].map_imu_upto[who[k]] > 0;
-        reg.defer_full = blend;
-        reg.on_first_wait = [&]() { launch_f2(); prestage_gather(ti + 1, last_staged, s_); };
-        reg.run_async();
-        reg.on_first_wait = nullptr;
-        if (blend) {
-          std::vector<float> p6(6 * (size_t)nw);
-          reg.download(p6.data(), nullptr);
-          if (reg.submap_sufficient())   // (transformUpdate is only reached when the optimisation ran, :628-629)
-            for (uint32_t k = 0; k < nw; k++)
-              (void)map_imu_blend(who[k], rawslot[t % RING].map_imu_upto[who[k]], rawslot[t % RING].scan_time[who[k]], fcfg.scan_period, &p6[6 * (size_t)k]);
-          reg.finish_with_poses(p6.data());
-          reg.defer_full = false;
-        }
-        if (reg.double_buffer_full) {
-          if (!ev_reg_done) LX_HIP(hipEventCreateWithFlags(&ev_reg_done, hipEventDisableTiming));
-          LX_HIP(hipEventRecord(ev_reg_done, s_));
-        }
-      } else {
-        last_full_off.clear();
-        last_who.clear();
       }
-      launch_f2();
-      if (nw) prestage_gather(ti + 1, last_staged, s_);   // (no-op when the first wait's callback did it)
-      if (timing) {
-        LX_HIP(hipEventRecord(tm.b, s_));
-        tm.pending = true;
-      }
-      trM[1] = tr_us();
-      // ---- finish M(t)
-      if (nw) {
-        std::vector<float> poses(6 * nw);
-        std::vector<SweepStats> ss(nw);
-        reg.download(poses.data(), nullptr);
-        reg.download_stats(ss.data());
-        for (uint32_t k = 0; k < nw; k++) {
-          PipeStreamState& P = st[who[k]];
-          P.map_stats = ss[k];
-          P.mapped = true;
-          if (reg.submap_sufficient()) {   // transformUpdate (BasicLaserMapping.cpp:171-203, :628-629)
-            P.tobe.set(&poses[6 * k]);
-            P.bef = P.cur.transform_sum;
-            P.aft = P.tobe;
-          }
-        }
-        ret = LOAMX_OK;
-      }
-      trM[2] = tr_us();
-    } catch (...) {
-      throw;
+      ret = LOAMX_OK;
     }
-    trM[3] = tr_us();
+    S.tr[2] = tr_us();
+    return ret;
+  }
+  // 8. the step has run: trace line (LOAMX_PIPE_TRACE) and stage times
+  void finish_step_(Step& S) {
+    const uint32_t t = S.t;
+    S.tr[3] = tr_us();
     last_step = (long)t;
     tr_exit = std::chrono::steady_clock::now();
     if (trace) {
-      fprintf(stderr, "[pipe t=%u] caller gap %.0f | M-start %.0f  M-enqueued %.0f  M-downloaded %.0f  O-joined %.0f  (download-wait %.0f) |", t, gap_us, trM[0], trM[1], trM[2], trM[3], trM[4]);
-      for (auto& c : chains)   // (each chain's most recent pass, whichever step that was: start, features ready, process() returned, end)
-        fprintf(stderr, " O[%u-%u): %.0f %.0f %.0f %.0f done %d pass %.0f us |", c->s0, c->s1, c->tr[0], c->tr[1], c->tr[2], c->tr[3], c->done.load(), (double)c->last_us.load());
-      fprintf(stderr, " f_hi %d o_limit %d staged %u", f_hi, o_limit.load(), n_staged());
+      fprintf(stderr, "[pipe t=%u] caller gap %.0f | M-start %.0f  M-enqueued %.0f  M-downloaded %.0f  O-joined %.0f  (download-wait %.0f) |", t, S.gap_us, S.tr[0], S.tr[1], S.tr[2], S.tr[3], S.tr[4]);
+      for (uint32_t g = 0; g < n_groups; g++) {   // (each chain's most recent pass, whichever step that was: start, features ready, process() returned, end)
+        const OdomChain& c = *chains[g];
+        fprintf(stderr, " O[%u-%u): %.0f %.0f %.0f %.0f done %d pass %.0f us |", c.s0, c.s1, c.tr[0], c.tr[1], c.tr[2], c.tr[3], la->done(g), (double)c.last_us.load());
+      }
+      fprintf(stderr, " f_hi %d o_limit %d staged %u", f_hi, la->limit(), n_staged());
       fprintf(stderr, "\n");
     }
     if (timing) {
       for (auto& x : tmM) x.resolve();
-      last_ms[0] = f_ms;               // on the feature stream (overlapped)
+      last_ms[0] = S.f_ms;             // on the feature stream (overlapped)
       {   // the odometry chains (overlapped with the registrations): the longest chain's most recent timed pass
         float m = 0.f;
         for (auto& c : chains) m = std::max(m, c->ms.load(std::memory_order_relaxed));
@@ -983,6 +881,30 @@ class Pipeline {
       last_ms[2] = tmM[t & 1].pending ? tmM[(t + 1) & 1].ms : tmM[t & 1].ms;   // the previous step's while this one is in flight
       last_ms[3] = last_ms[2];
     }
+  }
+
+  int step(uint32_t t) {
+    TraceRange trace_range("loamx:pipeline:step");
+    LX_REQUIRE(t < n_staged(), "step index beyond the staged sweeps");
+    LX_REQUIRE(!streaming || t + RING >= staged_hi.load(), "this step's slot has been re-staged already");   // (slot t % RING is rewritten by staging step t + RING)
+    Step S;
+    const auto t_entry = std::chrono::steady_clock::now();
+    S.gap_us = std::chrono::duration<double, std::micro>(t_entry - tr_exit).count();   // the caller's time between two steps
+    tr0 = t_entry;
+    LX_HIP(hipSetDevice(device));
+    S.t = t;
+    S.ti = (int)t;
+    S.s_ = reg.stream();
+    S.last_staged = (int)n_staged() - 1;
+    S.w = lookahead_window(S.ti, depth(), S.last_staged, prefetch);
+    join_odometry_(S);
+    release_lookahead_(S);
+    gather_inputs_(S);
+    stage_full_res_(S);
+    enqueue_registration_(S);
+    release_behind_registration_(S);
+    const int ret = collect_(S);
+    finish_step_(S);
     return ret;
   }
 };
