@@ -22,398 +22,6 @@
 namespace loamx {
 
 // ----------------------------------------------------------------------------------------------------------------
-// small helpers
-// ----------------------------------------------------------------------------------------------------------------
-
-__global__ void k_init_bbox(uint32_t* scratch) {
-  const uint32_t t = threadIdx.x;
-  if (t < 3) scratch[t] = 0xffffffffu;
-  else if (t < 16) scratch[t] = 0u;
-}
-__global__ void k_zero_u32_dn(uint32_t* p, const uint32_t* d_n) {
-  const uint32_t n = *d_n;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0u;
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// SubMapIndex: bounding box -> grid descriptor -> cell histogram -> exclusive scan -> scatter
-// scratch layout (uint32): [0..5] encoded min xyz / max xyz, [6] ncell+1, [7] scan total, [8] ncell
-// ----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_bbox(const float4* __restrict__ pts, uint32_t n, uint32_t* __restrict__ enc) {
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    float4 p = pts[i];
-    mn[0] = fminf(mn[0], p.x); mx[0] = fmaxf(mx[0], p.x);
-    mn[1] = fminf(mn[1], p.y); mx[1] = fmaxf(mx[1], p.y);
-    mn[2] = fminf(mn[2], p.z); mx[2] = fmaxf(mx[2], p.z);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-      mn[a] = fminf(mn[a], __shfl_xor(mn[a], d, 64));
-      mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], d, 64));
-    }
-  }
-  __shared__ float red[4][6];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) { red[wid][a] = mn[a]; red[wid][3 + a] = mx[a]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const int a = threadIdx.x;
-    float v = red[0][a];
-    for (int w = 1; w < 4; w++) v = a < 3 ? fminf(v, red[w][a]) : fmaxf(v, red[w][a]);
-    if (a < 3) atomicMin(&enc[a], enc_f32(v)); else atomicMax(&enc[a], enc_f32(v));
-  }
-}
-
-// grid descriptor from the bounds (k_bbox, or the producer of the points through SubMapIndex::d_bounds()): the cell edge starts at
-// 1.05 m and grows by 1.25x while the table would not fit (a coarser grid is still exact: the 27-cell neighbourhood only grows)
-__device__ inline GridDesc grid_from_bounds(const uint32_t* __restrict__ scratch, uint32_t max_cells) {
-  float mn[3], mx[3];
-  for (int a = 0; a < 3; a++) { mn[a] = dec_f32(scratch[a]); mx[a] = dec_f32(scratch[3 + a]); }
-  float h = 1.05f;
-  GridDesc g;
-  for (;;) {
-    g.inv_h = 1.0f / h;
-    g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
-    g.nx = (int)floorf((mx[0] - mn[0]) * g.inv_h) + 1;
-    g.ny = (int)floorf((mx[1] - mn[1]) * g.inv_h) + 1;
-    g.nz = (int)floorf((mx[2] - mn[2]) * g.inv_h) + 1;
-    unsigned long long nc = (unsigned long long)g.nx * g.ny * g.nz;
-    if (nc <= max_cells) { g.ncell = (uint32_t)nc; break; }
-    h *= 1.25f;
-  }
-  return g;
-}
-
-// count: every workgroup derives the descriptor itself (the same arithmetic everywhere; workgroup 0 records it and the scan's count);
-// a point's rank inside its cell is the counter's value before its run's bump, so the scatter needs no atomics and the counters can
-// be cleared behind the scan (rounds 1-4: k_init_bbox, k_grid_setup and k_zero_u32_dn were three launches of their own)
-__global__ __launch_bounds__(256) void k_cell_count(const float4* __restrict__ pts, uint32_t n, uint32_t* __restrict__ scratch, GridDesc* __restrict__ desc,
-                                                    uint32_t max_cells, uint32_t* __restrict__ cell_of, uint32_t* __restrict__ counts,
-                                                    uint32_t* __restrict__ rank_of) {
-  __shared__ GridDesc s_g;
-  if (threadIdx.x == 0) {
-    s_g = grid_from_bounds(scratch, max_cells);
-    if (blockIdx.x == 0) {
-      *desc = s_g;
-      scratch[6] = s_g.ncell + 1;
-      scratch[8] = s_g.ncell;
-    }
-  }
-  __syncthreads();
-  const GridDesc g = s_g;
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = i < n;
-  uint32_t c = 0;
-  if (active) {
-    const float4 p = pts[i];
-    int cx, cy, cz;
-    cell_coords(g, p.x, p.y, p.z, cx, cy, cz);
-    c = ((uint32_t)cz * g.ny + cy) * g.nx + cx;
-    cell_of[i] = c;
-  }
-  int head, len;
-  wave_runs(c, active, head, len);
-  uint32_t base = 0;
-  if (active && head == (int)__lane_id()) base = atomicAdd(&counts[c], (uint32_t)len);
-  base = __shfl(base, head, 64);
-  if (active) rank_of[i] = base + (uint32_t)((int)__lane_id() - head);
-}
-
-// scatter; its first thread leaves the bounds accumulators reset for the next build
-__global__ __launch_bounds__(256) void k_cell_scatter(const float4* __restrict__ pts, uint32_t n, const uint32_t* __restrict__ cell_of,
-                                                      const uint32_t* __restrict__ rank_of, const uint32_t* __restrict__ cell_start,
-                                                      float4* __restrict__ sorted, uint32_t* __restrict__ scratch) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) {
-#pragma unroll
-    for (int a = 0; a < 6; a++) scratch[a] = a < 3 ? 0xffffffffu : 0u;
-  }
-  if (i >= n) return;
-  float4 p = pts[i];
-  p.w = __uint_as_float(i);   // original index: kNN ties are broken on it, so the slot order inside a cell is irrelevant
-  sorted[cell_start[cell_of[i]] + rank_of[i]] = p;
-}
-
-void SubMapIndex::init(hipStream_t st) {
-  st_ = st;
-  scratch_.reserve(16);
-  hipLaunchKernelGGL(k_init_bbox, dim3(1), dim3(16), 0, st, scratch_.p);   // (once: every build's scatter leaves the bounds reset)
-  d_desc_.reserve(1);
-  tile_sums_.reserve(SCAN_SCRATCH_WORDS);
-  LX_HIP(hipMemsetAsync(tile_sums_.p, 0, sizeof(uint32_t) * tile_sums_.cap, st));
-}
-
-void SubMapIndex::swap(SubMapIndex& o) {
-  std::swap(n_, o.n_);
-  auto sw = [](auto& a, auto& b) { std::swap(a.p, b.p); std::swap(a.cap, b.cap); };
-  sw(sorted_, o.sorted_); sw(cell_of_, o.cell_of_); sw(rank_of_, o.rank_of_); sw(cell_start_, o.cell_start_); sw(cursor_, o.cursor_);
-  sw(tile_sums_, o.tile_sums_); sw(scratch_, o.scratch_); sw(d_desc_, o.d_desc_);
-}
-
-void SubMapIndex::build(const float4* d_pts, uint32_t n, bool bounds_done) {
-  n_ = n;
-  if (n == 0) return;
-  sorted_.reserve(n);
-  cell_of_.reserve(n);
-  rank_of_.reserve(n);
-  cell_start_.reserve((size_t)LX_MAX_CELLS + 2);
-  if (!cursor_.p) {   // the cell counters: cleared once, kept clear by every build (the scan clears them behind itself)
-    cursor_.reserve((size_t)LX_MAX_CELLS + 2);
-    LX_HIP(hipMemsetAsync(cursor_.p, 0, sizeof(uint32_t) * cursor_.cap, st_));
-  }
-  const uint32_t nb = (n + 255) / 256;
-  // bounds (unless the kernel that produced the points folded them into d_bounds() as it wrote them) -> count (+ grid set-up) -> scan
-  // (+ counters cleared) -> scatter (+ bounds reset): 3 - 4 launches (rounds 1-4: 7)
-  if (!bounds_done) hipLaunchKernelGGL(k_bbox, dim3(nb < 128 ? nb : 128), dim3(256), 0, st_, d_pts, n, scratch_.p);
-  hipLaunchKernelGGL(k_cell_count, dim3(nb), dim3(256), 0, st_, d_pts, n, scratch_.p, d_desc_.p, LX_MAX_CELLS, cell_of_.p, cursor_.p, rank_of_.p);
-  exclusive_scan_u32(cursor_.p, cell_start_.p, tile_sums_.p, scratch_.p + 8, scratch_.p + 7, LX_MAX_CELLS, st_, nullptr, cursor_.p);
-  hipLaunchKernelGGL(k_cell_scatter, dim3(nb), dim3(256), 0, st_, d_pts, n, cell_of_.p, rank_of_.p, cell_start_.p, sorted_.p, scratch_.p);
-  LX_HIP(hipGetLastError());
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// SubMapIndexBatch: the same counting-sort build for K clouds with one set of launches
-// scratch: [0] total cells + 1, [1] scan total, [2] total cells
-// ----------------------------------------------------------------------------------------------------------------
-__global__ void k_bb_init(uint32_t* enc, uint32_t K) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < 6 * K) enc[i * BB_STRIDE] = (i % 6) < 3 ? 0xffffffffu : 0u;
-}
-// grid = (blocks, K)
-__global__ __launch_bounds__(256) void k_bb_bbox(const float4* __restrict__ pts, const uint32_t* __restrict__ off, uint32_t* __restrict__ enc) {
-  const uint32_t c = blockIdx.y;
-  const uint32_t a0 = off[c], a1 = off[c + 1];
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  for (uint32_t i = a0 + blockIdx.x * blockDim.x + threadIdx.x; i < a1; i += gridDim.x * blockDim.x) {
-    const float4 p = pts[i];
-    mn[0] = fminf(mn[0], p.x); mx[0] = fmaxf(mx[0], p.x);
-    mn[1] = fminf(mn[1], p.y); mx[1] = fmaxf(mx[1], p.y);
-    mn[2] = fminf(mn[2], p.z); mx[2] = fmaxf(mx[2], p.z);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-      mn[a] = fminf(mn[a], __shfl_xor(mn[a], d, 64));
-      mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], d, 64));
-    }
-  }
-  __shared__ float red[4][6];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) { red[wid][a] = mn[a]; red[wid][3 + a] = mx[a]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 6 && a1 > a0 + blockIdx.x * blockDim.x) {
-    const int a = threadIdx.x;
-    float v = red[0][a];
-    for (int w = 1; w < 4; w++) v = a < 3 ? fminf(v, red[w][a]) : fmaxf(v, red[w][a]);
-    if (a < 3) atomicMin(&enc[bb_word(c, a)], enc_f32(v)); else atomicMax(&enc[bb_word(c, a)], enc_f32(v));
-  }
-}
-// grid descriptor of cloud c from its accumulated bounds, within the per-cloud cell budget (cell_base is the caller's scan)
-__device__ inline GridDescB bb_make_desc(const uint32_t* __restrict__ enc, const uint32_t* __restrict__ off, uint32_t c, uint32_t budget, float cell0) {
-  GridDescB d;
-  d.g.ox = d.g.oy = d.g.oz = 0.f; d.g.inv_h = 1.f; d.g.nx = d.g.ny = d.g.nz = 1;
-  d.pt_base = off[c];
-  d.cell_base = 0;
-  d.g.ncell = 1;   // an empty cloud: a 1-cell grid
-  if (off[c + 1] != off[c]) {
-    float mn[3], mx[3];
-    for (int a = 0; a < 3; a++) { mn[a] = dec_f32(enc[bb_word(c, a)]); mx[a] = dec_f32(enc[bb_word(c, 3 + a)]); }
-    float h = cell0;
-    for (;;) {
-      d.g.inv_h = 1.0f / h;
-      d.g.ox = mn[0]; d.g.oy = mn[1]; d.g.oz = mn[2];
-      d.g.nx = (int)floorf((mx[0] - mn[0]) * d.g.inv_h) + 1;
-      d.g.ny = (int)floorf((mx[1] - mn[1]) * d.g.inv_h) + 1;
-      d.g.nz = (int)floorf((mx[2] - mn[2]) * d.g.inv_h) + 1;
-      const unsigned long long nc = (unsigned long long)d.g.nx * d.g.ny * d.g.nz;
-      if (nc <= budget) { d.g.ncell = (uint32_t)nc; break; }
-      h *= 1.25f;
-    }
-  }
-  return d;
-}
-// one thread per cloud (one workgroup, K <= 4096 in rounds of 1024): grid descriptors within the per-cloud cell budget, table bases by a scan
-// (leaves the bounds accumulators reset for the next build: k_bb_init runs only when K grows)
-__global__ __launch_bounds__(1024) void k_bb_setup(uint32_t* __restrict__ enc, const uint32_t* __restrict__ off, uint32_t K, GridDescB* __restrict__ desc,
-                                                   uint32_t* __restrict__ scratch, uint32_t max_cells_total, float cell0) {
-  __shared__ uint32_t lds[17];
-  const uint32_t budget = max_cells_total / (K ? K : 1);
-  uint32_t carry = 0;
-  for (uint32_t c0 = 0; c0 < K; c0 += 1024) {
-    const uint32_t c = c0 + threadIdx.x;
-    GridDescB d;
-    d.g.ox = d.g.oy = d.g.oz = 0.f; d.g.inv_h = 1.f; d.g.nx = d.g.ny = d.g.nz = 1; d.g.ncell = 0;
-    d.pt_base = 0; d.cell_base = 0;
-    if (c < K) {
-      d = bb_make_desc(enc, off, c, budget, cell0);
-#pragma unroll
-      for (int a = 0; a < 6; a++) enc[bb_word(c, a)] = a < 3 ? 0xffffffffu : 0u;
-    }
-    uint32_t tot;
-    const uint32_t ex = block_excl_scan(c < K ? d.g.ncell : 0u, lds, tot);
-    if (c < K) {
-      d.cell_base = carry + ex;
-      desc[c] = d;
-    }
-    carry += tot;
-  }
-  if (threadIdx.x == 0) {
-    scratch[0] = carry + 1;
-    scratch[2] = carry;
-  }
-}
-// Round 6: for a handful of clouds (K <= BB_FUSE_MAXK: the odometry's 2 x streams of a chain) the set-up above is folded into the count —
-// every workgroup derives the K descriptors from the bounds itself (a few dependent loads, in parallel over the workgroups), workgroup 0
-// publishes them and the table size; the bounds accumulators are reset by the scatter, the build's last kernel.  One launch (and one
-// dependent-launch gap) less in the tail of every odometry pass.
-constexpr uint32_t BB_FUSE_MAXK = 64;
-template <bool FUSED>
-__global__ __launch_bounds__(256) void k_bb_count(const float4* __restrict__ pts, uint32_t n, const uint32_t* __restrict__ off, uint32_t K,
-                                                  GridDescB* __restrict__ desc, uint32_t* __restrict__ cell_of,
-                                                  uint32_t* __restrict__ counts, uint32_t* __restrict__ rank_of, const uint32_t* __restrict__ enc,
-                                                  uint32_t* __restrict__ scratch, uint32_t max_cells_total, float cell0) {
-  __shared__ GridDescB s_desc[FUSED ? BB_FUSE_MAXK : 1];
-  if (FUSED) {
-    __shared__ uint32_t lds[17];
-    const uint32_t cc = threadIdx.x;
-    GridDescB d;
-    d.g.ncell = 0;
-    if (cc < K) d = bb_make_desc(enc, off, cc, max_cells_total / (K ? K : 1), cell0);
-    uint32_t tot;
-    const uint32_t ex = block_excl_scan(cc < K ? d.g.ncell : 0u, lds, tot);
-    if (cc < K) {
-      d.cell_base = ex;
-      s_desc[cc] = d;
-      if (blockIdx.x == 0) desc[cc] = d;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { scratch[0] = tot + 1; scratch[2] = tot; }
-    __syncthreads();
-  }
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = i < n;
-  uint32_t c = 0;
-  if (active) {
-    uint32_t lo = 0, hi = K;
-    while (hi - lo > 1) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    const GridDescB d = FUSED ? s_desc[lo] : desc[lo];
-    const float4 p = pts[i];
-    int cx, cy, cz;
-    cell_coords(d.g, p.x, p.y, p.z, cx, cy, cz);
-    c = d.cell_base + ((uint32_t)cz * d.g.ny + cy) * d.g.nx + cx;
-    cell_of[i] = c;
-  }
-  // the counter's value before a run's bump is where the run's points go inside their cell: the scatter needs no atomics of its own
-  int head, len;
-  wave_runs(c, active, head, len);
-  uint32_t base = 0;
-  if (active && head == (int)__lane_id()) base = atomicAdd(&counts[c], (uint32_t)len);
-  base = __shfl(base, head, 64);
-  if (active) rank_of[i] = base + (uint32_t)((int)__lane_id() - head);
-}
-
-__global__ __launch_bounds__(256) void k_bb_scatter(const float4* __restrict__ pts, uint32_t n, const uint32_t* __restrict__ off, uint32_t K,
-                                                    const uint32_t* __restrict__ cell_of, const uint32_t* __restrict__ rank_of,
-                                                    const uint32_t* __restrict__ cell_start, float4* __restrict__ sorted, int pack_ring,
-                                                    uint32_t* __restrict__ enc_reset) {
-  if (enc_reset && blockIdx.x == 0 && threadIdx.x < K) {   // (the fused set-up: every workgroup of the count has read the bounds by now)
-#pragma unroll
-    for (int a = 0; a < 6; a++) enc_reset[bb_word(threadIdx.x, a)] = a < 3 ? 0xffffffffu : 0u;
-  }
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint32_t lo = 0, hi = K;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid;
-  }
-  float4 p = pts[i];
-  const uint32_t li = i - off[lo];      // index inside its own cloud
-  // pack_ring (the odometry's clouds: .w = ring id): the top byte carries the ring so that a search can filter by ring without a
-  // second gather; 255 = unknown (ring id or index too large for the packing — its user then falls back, odometry.hip)
-  uint32_t w = li;
-  if (pack_ring) {
-    const int ring = (int)p.w;
-    w = (li <= 0xffffffu && ring >= 0 && ring < 255) ? (((uint32_t)ring << 24) | li) : (0xff000000u | (li & 0xffffffu));
-  }
-  p.w = __uint_as_float(w);
-  sorted[cell_start[cell_of[i]] + rank_of[i]] = p;
-}
-
-void SubMapIndexBatch::init(hipStream_t st) {
-  st_ = st;
-  scratch_.reserve(16);
-  tile_sums_.reserve(SCAN_SCRATCH_WORDS);
-  LX_HIP(hipMemsetAsync(tile_sums_.p, 0, sizeof(uint32_t) * tile_sums_.cap, st));
-}
-
-// the bounding-box accumulators can be reset long before the points exist (e.g. ahead of the iterations whose result the
-// points depend on): build() then finds them reset and skips that launch
-void SubMapIndexBatch::prepare(uint32_t K) {
-  LX_REQUIRE(K >= 1 && K <= 4096, "too many clouds in one index batch");
-  reset_bounds_(K);
-}
-void SubMapIndexBatch::reset_bounds_(uint32_t K) {
-  if (K <= enc_ready_) return;   // every build's k_bb_setup leaves the accumulators of its K clouds reset
-  const uint32_t cap = std::max<uint32_t>(K, 64u);
-  enc_.reserve(((size_t)6 * cap + 6) * BB_STRIDE);   // (growing discards the contents: all of it is initialised below)
-  hipLaunchKernelGGL(k_bb_init, dim3((6 * cap + 255) / 256), dim3(256), 0, st_, enc_.p, cap);
-  enc_ready_ = cap;
-}
-
-void SubMapIndexBatch::build(const float4* d_pts, const uint32_t* h_off, uint32_t K, const uint32_t* d_off_ready, bool bounds_done) {
-  LX_REQUIRE(K >= 1 && K <= 4096, "too many clouds in one index batch");
-  const uint32_t n = h_off[K];
-  d_off_.reserve(K + 2);
-  d_desc_.reserve(K + 1);
-  const uint32_t* d_off = d_off_ready;   // the caller may already hold the offsets on the device
-  if (!d_off) {
-    h_off_pin_.reserve(K + 2);
-    memcpy(h_off_pin_.p, h_off, sizeof(uint32_t) * (K + 1));
-    LX_HIP(hipMemcpyAsync(d_off_.p, h_off_pin_.p, sizeof(uint32_t) * (K + 1), hipMemcpyHostToDevice, st_));
-    d_off = d_off_.p;
-  }
-  sorted_.reserve((size_t)n + 1);
-  cell_of_.reserve((size_t)n + 1);
-  rank_of_.reserve((size_t)n + 1);
-  cell_start_.reserve((size_t)LX_MAX_CELLS + 2);
-  if (!cursor_.p) {   // the cell counters: cleared once, kept clear by every build
-    cursor_.reserve((size_t)LX_MAX_CELLS + 2);
-    LX_HIP(hipMemsetAsync(cursor_.p, 0, sizeof(uint32_t) * cursor_.cap, st_));
-  }
-  reset_bounds_(K);
-  uint32_t max_len = 0;
-  for (uint32_t c = 0; c < K; c++) max_len = std::max(max_len, h_off[c + 1] - h_off[c]);
-  const uint32_t nbx = std::min<uint32_t>(std::max<uint32_t>((max_len + 255) / 256, 1u), 32u);
-  if (!bounds_done) hipLaunchKernelGGL(k_bb_bbox, dim3(nbx, K), dim3(256), 0, st_, d_pts, d_off, enc_.p);
-  const bool fused = n > 0 && K <= BB_FUSE_MAXK;   // (see k_bb_count: set-up folded into the count, bounds reset by the scatter)
-  if (!fused) hipLaunchKernelGGL(k_bb_setup, dim3(1), dim3(1024), 0, st_, enc_.p, d_off, K, d_desc_.p, scratch_.p, LX_MAX_CELLS, cell_size);
-  if (n) {
-    if (fused) hipLaunchKernelGGL(k_bb_count<true>, dim3((n + 255) / 256), dim3(256), 0, st_, d_pts, n, d_off, K, d_desc_.p, cell_of_.p, cursor_.p, rank_of_.p,
-                                  enc_.p, scratch_.p, LX_MAX_CELLS, cell_size);
-    else hipLaunchKernelGGL(k_bb_count<false>, dim3((n + 255) / 256), dim3(256), 0, st_, d_pts, n, d_off, K, d_desc_.p, cell_of_.p, cursor_.p, rank_of_.p,
-                            enc_.p, scratch_.p, LX_MAX_CELLS, cell_size);
-  }
-  // (the cell counters are cleared behind the scan: they are empty again when the next build starts)
-  exclusive_scan_u32(cursor_.p, cell_start_.p, tile_sums_.p, scratch_.p + 2, scratch_.p + 1, LX_MAX_CELLS, st_, nullptr, cursor_.p);
-  if (n) hipLaunchKernelGGL(k_bb_scatter, dim3((n + 255) / 256), dim3(256), 0, st_, d_pts, n, d_off, K, cell_of_.p, rank_of_.p, cell_start_.p, sorted_.p, pack_ring ? 1 : 0,
-                            fused ? enc_.p : nullptr);
-  LX_HIP(hipGetLastError());
-}
-
-// ----------------------------------------------------------------------------------------------------------------
 // stack round trip + voxel keys
 // ----------------------------------------------------------------------------------------------------------------
 // seg_minmax: per segment min ix,iy,iz / max ix,iy,iz
@@ -1049,9 +657,6 @@ Registrar::Registrar(int device, uint32_t max_sweeps) : device_(device), max_swe
   arrive_.reserve(max_sweeps);
   LX_HIP(hipMemsetAsync(arrive_.p, 0, sizeof(uint32_t) * max_sweeps, st_));
   guess_.reserve((size_t)6 * max_sweeps);
-  h_guess_.reserve((size_t)64 * max_sweeps + 64);
-  seg_off_.reserve(2 * max_sweeps + 2);
-  full_off_.reserve(max_sweeps + 2);
   ds_off_.reserve(2 * max_sweeps + 2);
   vox_.init(st_);
   vb_.init(st_);
@@ -1159,34 +764,76 @@ void Registrar::swap_submap() {
   swapped_once_ = true;
 }
 
-void Registrar::upload(uint32_t n_sweeps, const loamx_cloud* corner_last, const loamx_cloud* surf_last, const loamx_cloud* full_res,
-                       const float* guess6, bool wait) {
+// off[0] = 0, off[s + 1] = off[s] + count(s)
+template <class Count> static void prefix_offsets(std::vector<uint32_t>& off, uint32_t n, Count&& count) {
+  off.assign(n + 1, 0);
+  for (uint32_t s = 0; s < n; s++) off[s + 1] = off[s] + count(s);
+}
+
+// What both uploads decide before a byte moves.  count(s, k): points of sweep s's corner (0) / surf (1) / full-resolution (2) cloud, asked
+// for in this order; staged: h_full_off_ / n_full_ stand as stage_full() or adopt_full_next() left them
+template <class Count> void Registrar::plan_inputs_(uint32_t n_sweeps, bool staged, Count&& count) {
   LX_REQUIRE(n_sweeps >= 1 && n_sweeps <= max_sweeps_, "n_sweeps out of range for this handle");
-  LX_REQUIRE(corner_last && surf_last && guess6, "NULL input");
   LX_HIP(hipSetDevice(device_));
   n_sweeps_ = n_sweeps;
   h_seg_off_.assign(2 * n_sweeps + 1, 0);
-  h_full_off_.assign(n_sweeps + 1, 0);
+  if (!staged) h_full_off_.assign(n_sweeps + 1, 0);
   max_q_per_sweep_ = 0;
   for (uint32_t s = 0; s < n_sweeps; s++) {
-    check_cloud(&corner_last[s], false);
-    check_cloud(&surf_last[s], false);
-    h_seg_off_[2 * s + 1] = h_seg_off_[2 * s] + corner_last[s].count;
-    h_seg_off_[2 * s + 2] = h_seg_off_[2 * s + 1] + surf_last[s].count;
-    max_q_per_sweep_ = std::max(max_q_per_sweep_, corner_last[s].count + surf_last[s].count);
-    if (full_res) {
-      check_cloud(&full_res[s], false);
-      h_full_off_[s + 1] = h_full_off_[s] + full_res[s].count;
-    }
+    const uint32_t nc = count(s, 0), nf = count(s, 1);
+    h_seg_off_[2 * s + 1] = h_seg_off_[2 * s] + nc;
+    h_seg_off_[2 * s + 2] = h_seg_off_[2 * s + 1] + nf;
+    max_q_per_sweep_ = std::max(max_q_per_sweep_, nc + nf);
+    if (!staged) h_full_off_[s + 1] = h_full_off_[s] + count(s, 2);
   }
   n_in_ = h_seg_off_[2 * n_sweeps];
-  n_full_ = h_full_off_[n_sweeps];
-  h_in_.reserve(n_in_ + 1);
+  if (!staged) n_full_ = h_full_off_[n_sweeps];
   in_.reserve(n_in_ + 1);
   stack_.reserve(n_in_ + 1);
   ds_pts_.reserve(n_in_ + 1);
   vox_.reserve(n_in_ + 1, 2 * n_sweeps);
   LX_REQUIRE(n_in_ < SCAN_MAX_N, "too many feature points in one batch");
+  if (n_full_) full_.reserve(n_full_);
+  nblk_ = max_q_per_sweep_ / GN_TILE + 2;   // >= ceil(corner / tile) + ceil(surf / tile) of every sweep
+  partials_.reserve((size_t)n_sweeps * nblk_ * LX_NSUM);
+}
+
+// Guesses / offsets (/ source pointers, when the inputs are device-resident: 2 per sweep, then the full-resolution ones) as ONE block in
+// pinned memory owned by this object (copies from pageable vectors were staged by the runtime, one wait each), and the four views of
+// its device copy.  Returns the block's size; the caller sends it.
+size_t Registrar::write_param_block_(const float* guess6, const float4* const* corner_src, const float4* const* surf_src, const float4* const* full_src) {
+  const uint32_t ns = n_sweeps_;
+  const size_t nseg = 2 * (size_t)ns;
+  const size_t o_off = sizeof(float) * 6 * ns, o_full = o_off + sizeof(uint32_t) * (nseg + 1);
+  const size_t end_full = o_full + sizeof(uint32_t) * (ns + 1), o_src = (end_full + 15) & ~(size_t)15;
+  const size_t bytes = corner_src ? o_src + sizeof(float4*) * (nseg + ns) : end_full;
+  h_blob_.reserve(bytes + 16);
+  blob_.reserve(bytes + 16);
+  memcpy(h_blob_.p, guess6, sizeof(float) * 6 * ns);
+  memcpy(h_blob_.p + o_off, h_seg_off_.data(), sizeof(uint32_t) * (nseg + 1));
+  memcpy(h_blob_.p + o_full, h_full_off_.data(), sizeof(uint32_t) * (ns + 1));
+  if (corner_src) {
+    const float4** hsrc = (const float4**)(h_blob_.p + o_src);
+    for (uint32_t s = 0; s < ns; s++) { hsrc[2 * s] = corner_src[s]; hsrc[2 * s + 1] = surf_src[s]; }
+    for (uint32_t s = 0; s < ns; s++) hsrc[nseg + s] = full_src ? full_src[s] : nullptr;
+  }
+  d_guess_ = (const float*)blob_.p;
+  d_seg_off_ = (const uint32_t*)(blob_.p + o_off);
+  d_full_off_ = (const uint32_t*)(blob_.p + o_full);
+  d_src_ = corner_src ? (const float4* const*)(blob_.p + o_src) : nullptr;
+  return bytes;
+}
+
+void Registrar::upload(uint32_t n_sweeps, const loamx_cloud* corner_last, const loamx_cloud* surf_last, const loamx_cloud* full_res,
+                       const float* guess6, bool wait) {
+  LX_REQUIRE(corner_last && surf_last && guess6, "NULL input");
+  plan_inputs_(n_sweeps, false, [&](uint32_t s, int k) {
+    const loamx_cloud* c = k == 0 ? &corner_last[s] : k == 1 ? &surf_last[s] : full_res ? &full_res[s] : nullptr;
+    if (!c) return 0u;
+    check_cloud(c, false);
+    return c->count;
+  });
+  h_in_.reserve(n_in_ + 1);
   for (uint32_t s = 0; s < n_sweeps; s++) {
     pack_cloud(&corner_last[s], h_in_.p + h_seg_off_[2 * s]);
     pack_cloud(&surf_last[s], h_in_.p + h_seg_off_[2 * s + 1]);
@@ -1196,28 +843,11 @@ void Registrar::upload(uint32_t n_sweeps, const loamx_cloud* corner_last, const 
   fetch_from_pinned(in_.p, h_in_.p, n_in_, st_);   // (single-sweep sizes by kernel, a batch's MiB by the copy engine: pinned_copy.hpp)
   if (n_full_) {
     h_full_.reserve(n_full_);
-    full_.reserve(n_full_);
     for (uint32_t s = 0; s < n_sweeps; s++) pack_cloud(&full_res[s], h_full_.p + h_full_off_[s]);
     fetch_from_pinned(full_.p, h_full_.p, n_full_, st_);
   }
-  {   // guesses / offsets travel as ONE block through pinned memory owned by this object (as in upload_device; copies from the
-      // pageable vectors were staged by the runtime, one wait each)
-    const size_t nseg = 2 * (size_t)n_sweeps;
-    const size_t o_off = sizeof(float) * 6 * n_sweeps, o_full = o_off + sizeof(uint32_t) * (nseg + 1);
-    const size_t bytes = o_full + sizeof(uint32_t) * (n_sweeps + 1);
-    h_blob_.reserve(bytes + 16);
-    blob_.reserve(bytes + 16);
-    memcpy(h_blob_.p, guess6, sizeof(float) * 6 * n_sweeps);
-    memcpy(h_blob_.p + o_off, h_seg_off_.data(), sizeof(uint32_t) * (nseg + 1));
-    memcpy(h_blob_.p + o_full, h_full_off_.data(), sizeof(uint32_t) * (n_sweeps + 1));
-    LX_HIP(hipMemcpyAsync(blob_.p, h_blob_.p, bytes, hipMemcpyHostToDevice, st_));
-    d_guess_ = (const float*)blob_.p;
-    d_seg_off_ = (const uint32_t*)(blob_.p + o_off);
-    d_full_off_ = (const uint32_t*)(blob_.p + o_full);
-    d_src_ = nullptr;
-  }
-  nblk_ = max_q_per_sweep_ / GN_TILE + 2;   // >= ceil(corner / tile) + ceil(surf / tile) of every sweep
-  partials_.reserve((size_t)n_sweeps * nblk_ * LX_NSUM);
+  const size_t bytes = write_param_block_(guess6, nullptr, nullptr, nullptr);
+  LX_HIP(hipMemcpyAsync(blob_.p, h_blob_.p, bytes, hipMemcpyHostToDevice, st_));
   // the copies read this object's pinned staging, which the next upload() rewrites: a caller that does not synchronise with the
   // stream before then (loamx_batch_upload twice in a row) needs the wait; Mapper::process always ends synchronised
   if (wait) LX_HIP(hipStreamSynchronize(st_));
@@ -1226,8 +856,7 @@ void Registrar::upload(uint32_t n_sweeps, const loamx_cloud* corner_last, const 
 float4* Registrar::stage_full(uint32_t n_sweeps, const uint32_t* n_full) {
   LX_REQUIRE(n_sweeps >= 1 && n_sweeps <= max_sweeps_, "n_sweeps out of range for this handle");
   full_next_staged_ = false;   // (a pre-staged buffer that was not adopted is simply dropped)
-  h_full_off_.assign(n_sweeps + 1, 0);
-  for (uint32_t s = 0; s < n_sweeps; s++) h_full_off_[s + 1] = h_full_off_[s] + n_full[s];
+  prefix_offsets(h_full_off_, n_sweeps, [&](uint32_t s) { return n_full[s]; });
   n_full_ = h_full_off_[n_sweeps];
   if (double_buffer_full) {   // the previous run's registered clouds stay readable (an asynchronous download may still be copying them)
     std::swap(full_.p, full_alt_.p);
@@ -1244,8 +873,7 @@ float4* Registrar::stage_full(uint32_t n_sweeps, const uint32_t* n_full) {
 float4* Registrar::stage_full_next(uint32_t n_sweeps, const uint32_t* n_full) {
   LX_REQUIRE(double_buffer_full, "internal: pre-staging needs the second full-resolution buffer");
   LX_REQUIRE(n_sweeps >= 1 && n_sweeps <= max_sweeps_, "n_sweeps out of range for this handle");
-  next_full_off_.assign(n_sweeps + 1, 0);
-  for (uint32_t s = 0; s < n_sweeps; s++) next_full_off_[s + 1] = next_full_off_[s] + n_full[s];
+  prefix_offsets(next_full_off_, n_sweeps, [&](uint32_t s) { return n_full[s]; });
   if ((size_t)next_full_off_[n_sweeps] + 1 > full_alt_.cap) return nullptr;   // (growing would free a buffer a download may still read: the caller stages at the usual time)
   full_next_staged_ = true;
   return full_alt_.p;
@@ -1266,45 +894,10 @@ bool Registrar::adopt_full_next(uint32_t n_sweeps, const uint32_t* n_full) {
 void Registrar::upload_device(uint32_t n_sweeps, const float4* const* corner_last, const uint32_t* n_corner,
                               const float4* const* surf_last, const uint32_t* n_surf, const float4* const* full_res,
                               const uint32_t* n_full, const float* guess6) {
-  LX_REQUIRE(n_sweeps >= 1 && n_sweeps <= max_sweeps_, "n_sweeps out of range for this handle");
-  LX_HIP(hipSetDevice(device_));
-  n_sweeps_ = n_sweeps;
   const bool staged = full_staged_ && !full_res;   // the caller wrote the full-resolution clouds through stage_full()
   full_staged_ = false;
-  h_seg_off_.assign(2 * n_sweeps + 1, 0);
-  if (!staged) h_full_off_.assign(n_sweeps + 1, 0);
-  max_q_per_sweep_ = 0;
-  for (uint32_t s = 0; s < n_sweeps; s++) {
-    h_seg_off_[2 * s + 1] = h_seg_off_[2 * s] + n_corner[s];
-    h_seg_off_[2 * s + 2] = h_seg_off_[2 * s + 1] + n_surf[s];
-    max_q_per_sweep_ = std::max(max_q_per_sweep_, n_corner[s] + n_surf[s]);
-    if (!staged) h_full_off_[s + 1] = h_full_off_[s] + (full_res ? n_full[s] : 0u);
-  }
-  n_in_ = h_seg_off_[2 * n_sweeps];
-  if (!staged) n_full_ = h_full_off_[n_sweeps];
-  in_.reserve(n_in_ + 1);
-  stack_.reserve(n_in_ + 1);
-  ds_pts_.reserve(n_in_ + 1);
-  vox_.reserve(n_in_ + 1, 2 * n_sweeps);
-  LX_REQUIRE(n_in_ < SCAN_MAX_N, "too many feature points in one batch");
-  // guesses / offsets / source pointers travel as ONE block through pinned memory owned by this object
-  const size_t nseg = 2 * (size_t)n_sweeps;
-  const size_t o_off = sizeof(float) * 6 * n_sweeps, o_full = o_off + sizeof(uint32_t) * (nseg + 1);
-  const size_t o_src = (o_full + sizeof(uint32_t) * (n_sweeps + 1) + 15) & ~(size_t)15;
-  const size_t bytes = o_src + sizeof(float4*) * (nseg + n_sweeps);
-  h_blob_.reserve(bytes + 16);
-  blob_.reserve(bytes + 16);
-  memcpy(h_blob_.p, guess6, sizeof(float) * 6 * n_sweeps);
-  memcpy(h_blob_.p + o_off, h_seg_off_.data(), sizeof(uint32_t) * (nseg + 1));
-  memcpy(h_blob_.p + o_full, h_full_off_.data(), sizeof(uint32_t) * (n_sweeps + 1));
-  const float4** hsrc = (const float4**)(h_blob_.p + o_src);
-  for (uint32_t s = 0; s < n_sweeps; s++) { hsrc[2 * s] = corner_last[s]; hsrc[2 * s + 1] = surf_last[s]; }
-  for (uint32_t s = 0; s < n_sweeps; s++) hsrc[nseg + s] = full_res ? full_res[s] : nullptr;
-  d_guess_ = (const float*)blob_.p;
-  d_seg_off_ = (const uint32_t*)(blob_.p + o_off);
-  d_full_off_ = (const uint32_t*)(blob_.p + o_full);
-  d_src_ = (const float4* const*)(blob_.p + o_src);
-  if (n_full_) full_.reserve(n_full_);
+  plan_inputs_(n_sweeps, staged, [&](uint32_t s, int k) { return k == 0 ? n_corner[s] : k == 1 ? n_surf[s] : full_res ? n_full[s] : 0u; });
+  const size_t bytes = write_param_block_(guess6, corner_last, surf_last, full_res);
   if (n_sweeps == 1 && n_full_ && !staged && bytes == sizeof(ParamBlock1)) {   // the block travels in the gather's arguments (k_gather_one)
     ParamBlock1 pb1;
     memcpy(pb1.w, h_blob_.p, sizeof(pb1));
@@ -1312,22 +905,28 @@ void Registrar::upload_device(uint32_t n_sweeps, const float4* const* corner_las
   } else {
     LX_HIP(hipMemcpyAsync(blob_.p, h_blob_.p, bytes, hipMemcpyHostToDevice, st_));
     if (n_full_ && !staged)
-      hipLaunchKernelGGL(k_gather_segments, dim3((n_full_ + 255) / 256), dim3(256), 0, st_, full_.p, d_full_off_, n_sweeps, d_src_ + nseg,
+      hipLaunchKernelGGL(k_gather_segments, dim3((n_full_ + 255) / 256), dim3(256), 0, st_, full_.p, d_full_off_, n_sweeps, d_src_ + 2 * (size_t)n_sweeps,
                          n_full_);
   }
-  nblk_ = max_q_per_sweep_ / GN_TILE + 2;   // >= ceil(corner / tile) + ceil(surf / tile) of every sweep
-  partials_.reserve((size_t)n_sweeps * nblk_ * LX_NSUM);
 }
 
 static double host_us() {
   return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+struct Registrar::RunTrace {
+  bool on;
+  double t0, front = 0, first_gn = 0, callback = 0;   // us: run_async() entered, voxel stage enqueued, first look marked, hand-off done
+  int looks = 0;
+};
+#ifdef LOAMX_PROF_GN
+static DevBuf<unsigned long long> g_gn_dbg;
+#endif
 
 // transformFullResToMap (BasicLaserMapping.cpp:235-240); mode as in k_transform_full
 void Registrar::enqueue_full(int mode) {
   if (!n_full_) return;
   if (mode == 1 && ++full_tag_ == 0u) full_tag_ = 1u;
-  const uint32_t* skip = vb_unchecked_ ? vb_.d_fail_word() : nullptr;   // an unverified bucketed voxel stage may have given up
+  const uint32_t* skip = run_.vb_unchecked ? vb_.d_fail_word() : nullptr;   // an unverified bucketed voxel stage may have given up
   hipLaunchKernelGGL(k_transform_full, dim3((n_full_ + 255) / 256), dim3(256), 0, st_, full_.p, n_full_, d_full_off_, n_sweeps_, poses_.p,
                      stats_.p, full_done_.p, mode, full_tag_, skip, vb_.epoch());
 }
@@ -1352,12 +951,6 @@ void Registrar::enqueue_front(bool legacy) {
   }
 }
 
-// The Gauss-Newton iterations: one k_gn_iter launch each.  Converged sweeps turn the remaining launches into no-ops on the
-// device (stats.done), which keeps run_async() free of host round trips.  A blocking caller (early_exit) enqueues one launch
-// more than the previous call needed (a launch over converged sweeps costs a few microseconds, a host round trip in the middle
-// of the chain ~90) together with the registration of the full-resolution clouds of the sweeps that converge within them, looks
-// at the flags (mirrored into pinned memory by the update step), and only goes on launching while some sweep is not done.
-// Returns true when the host, at its first look, finds that the bucketed voxel stage gave up: the caller runs again.
 // Blocks until every sweep's mirror says "done" (polled: the flags are written by the update step of the launch that
 // converged, ahead of the launches enqueued behind it) or until the stream reaches ev_look_.  Returns true when the flags
 // ended the wait.  A mirror counts only when its check word matches the pose / statistics words read after the flag.
@@ -1389,10 +982,11 @@ bool Registrar::wait_for_mirrors() {
   }
 }
 
-bool Registrar::run_iterations(bool trace, double& th2, double& th3) {
+// The Gauss-Newton iterations and the full-resolution launches that go with them, in the order reg_schedule() decides (reg_schedule.hpp:
+// what is enqueued ahead of the first look, when the host looks, which launch closes the run).  This function is the schedule's Ops —
+// the launches with their timing events, the looks at the pinned mirrors with the voxel stage's verdict — and takes the outcome over.
+RegOutcome Registrar::run_iterations(RunTrace& tr) {
   TraceRange trace_range("loamx:registration:gauss-newton");
-  const uint32_t ns = n_sweeps_;
-  struct ProfDump { std::function<void()> f; ~ProfDump() { if (f) f(); } } prof_dump;
   GnArgs a;
   a.ds_pts = ds_pts_.p; a.ds_off = ds_off_.p; a.poses = poses_.p; a.stats = stats_.p;
   a.cdesc = corner_index.desc(); a.cpts = corner_index.sorted(); a.cstart = corner_index.cell_start();
@@ -1400,155 +994,151 @@ bool Registrar::run_iterations(bool trace, double& th2, double& th3) {
   a.partials = partials_.p; a.arrive = arrive_.p; a.matP = matP_.p;
   a.host_stats = h_stats_.p; a.host_poses = h_poses_.p;
   a.nblk = nblk_; a.delta_t_abort = params.delta_t_abort; a.delta_r_abort = params.delta_r_abort;
-  const dim3 grid(8 * ((nblk_ + 7) / 8 + 1), ns);
   a.dbg = nullptr;
-  a.skip_word = vb_unchecked_ ? vb_.d_fail_word() : nullptr;   // (offsets of a run that gave up part-way may be a mix)
+  a.skip_word = run_.vb_unchecked ? vb_.d_fail_word() : nullptr;   // (offsets of a run that gave up part-way may be a mix)
   a.skip_value = vb_.epoch();
 #ifdef LOAMX_PROF_GN
-  static DevBuf<unsigned long long> dbg;
-  dbg.reserve((size_t)nblk_ * 8 + 64);
-  LX_HIP(hipMemsetAsync(dbg.p, 0, sizeof(unsigned long long) * ((size_t)nblk_ * 8 + 64), st_));
-  a.dbg = dbg.p;
-  prof_dump.f = [&]() {
-    std::vector<unsigned long long> h((size_t)nblk_ * 8);
-    (void)hipStreamSynchronize(st_);
-    (void)hipMemcpy(h.data(), dbg.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost);
-    unsigned long long t0 = ~0ull;
-    for (uint32_t t = 0; t < nblk_; t++) if (h[8 * t]) t0 = std::min(t0, h[8 * t]);
-    fprintf(stderr, "[gn iter 0, sweep 0: tile: start / search / rows / reduce us (+solve)]");
-    for (uint32_t t = 0; t < nblk_; t++) {
-      const unsigned long long* v = &h[8 * t];
-      if (!v[0]) continue;
-      if (t % 16 == 0 || v[5]) fprintf(stderr, " %u:%.0f/%.0f/%.0f/%.0f", t, (v[0] - t0) * 0.01, (v[1] - v[0]) * 0.01, (v[2] - v[1]) * 0.01, (v[3] - v[2]) * 0.01);
-      if (v[5]) fprintf(stderr, "(+solve %.0f, ends at %.0f)", (v[5] - v[4]) * 0.01, (v[5] - t0) * 0.01);
+  g_gn_dbg.reserve((size_t)nblk_ * 8 + 64);
+  LX_HIP(hipMemsetAsync(g_gn_dbg.p, 0, sizeof(unsigned long long) * ((size_t)nblk_ * 8 + 64), st_));
+  a.dbg = g_gn_dbg.p;
+#endif
+  struct Ops {
+    Registrar& r;
+    GnArgs& a;
+    RunTrace& tr;
+    const dim3 grid;   // per XCD: ceil(corner tiles / 8) + ceil(surf tiles / 8) workgroups at most
+    void gn(int it) {
+      const bool tm = r.timing_ && r.launch_timing_ && r.n_res_launch_ < 64;
+      if (tm) LX_HIP(hipEventRecord(r.ev_[2 + 2 * r.n_res_launch_], r.st_));
+      a.iter = it;
+#ifdef LOAMX_DIAG
+      if (r.jacobi_eig_) hipLaunchKernelGGL(k_gn_iter_jacobi, grid, dim3(LX_RES_THREADS), 0, r.st_, a);
+      else
+#endif
+      hipLaunchKernelGGL(k_gn_iter, grid, dim3(LX_RES_THREADS), 0, r.st_, a);
+      if (tm) {
+        LX_HIP(hipEventRecord(r.ev_[3 + 2 * r.n_res_launch_], r.st_));
+        r.n_res_launch_++;
+      }
     }
-    fprintf(stderr, "\n");
-    unsigned long long ts[16];
-    (void)hipMemcpyFromSymbol(ts, HIP_SYMBOL(g_solve_ts), sizeof(ts));
-    fprintf(stderr, "[solve_sweep, us since entry] partial sums %.1f  sums+AtA %.1f  qr %.1f  projector %.1f  trig %.1f  update+stores %.1f\n", (ts[1] - ts[0]) * 0.01,
-            (ts[2] - ts[0]) * 0.01, (ts[3] - ts[0]) * 0.01, (ts[4] - ts[0]) * 0.01, (ts[5] - ts[0]) * 0.01, (ts[6] - ts[0]) * 0.01);
-  };
-#endif   // per XCD: ceil(corner tiles / 8) + ceil(surf tiles / 8) workgroups at most
-  int it = 0;
-  bool waited = false, spec_full = false, all_done = false;
-  const int maxit = params.max_iterations;
-  const bool want_full = n_full_ && !defer_full;
+    void full(int mode) { r.enqueue_full(mode); }
+    // the host waits for THIS point of the stream, not for the stream: the caller's on_first_wait may enqueue work of the next run
+    // behind it (the pipeline's pre-staged re-projection), which must not hold this run's results back
+    void mark() {
+      if (tr.on && tr.first_gn == 0) tr.first_gn = host_us();
+      if (!r.ev_look_) LX_HIP(hipEventCreateWithFlags(&r.ev_look_, hipEventDisableTiming));
+      LX_HIP(hipEventRecord(r.ev_look_, r.st_));
+    }
+    void first_wait() {   // host work that overlaps the wait
+      if (r.on_first_wait) { r.on_first_wait(); r.on_first_wait = nullptr; }
+    }
+    RegLook look() {
+      if (tr.on && tr.callback == 0) tr.callback = host_us();
+      r.wait_for_mirrors();
+      RegLook l{r.bucket_stage_gave_up_(), true, 0};
+      for (uint32_t k = 0; k < r.n_sweeps_ && !l.gave_up; k++) {
+        l.all_done = l.all_done && r.h_stats_.p[k].done;
+        l.need = std::max(l.need, r.h_stats_.p[k].iterations);
+      }
+      return l;
+    }
+  } ops{*this, a, tr, dim3(8 * ((nblk_ + 7) / 8 + 1), n_sweeps_)};
   // (LOAMX_GN_AHEAD, diagnostic: launches enqueued beyond the previous call's need — 1 by default; a launch over converged sweeps costs ~4 us
   // of the stream, a host round trip for a launch that turns out to be missing ~20)
   static const int ahead = diag_env("LOAMX_GN_AHEAD") ? std::max(0, atoi(diag_env("LOAMX_GN_AHEAD"))) : 1;
-  int chunk = early_exit ? std::min(std::max(pred_iters_ + ahead, 2), maxit) : maxit;
-  while (it < maxit) {
-    const int end = std::min(maxit, it + chunk);
-    for (; it < end; it++) {
-      const bool tm = timing_ && launch_timing_ && n_res_launch_ < 64;
-      if (tm) LX_HIP(hipEventRecord(ev_[2 + 2 * n_res_launch_], st_));
-      a.iter = it;
-#ifdef LOAMX_DIAG
-      if (jacobi_eig_) hipLaunchKernelGGL(k_gn_iter_jacobi, grid, dim3(LX_RES_THREADS), 0, st_, a);
-      else
+  const RegOutcome o = reg_schedule(ops, RegPlan{early_exit, params.max_iterations, pred_iters_, ahead, n_full_ != 0 && !defer_full});
+  pred_iters_ = o.pred_iters_next;
+  // every sweep done at a look: poses / stats are final and on the host; the clouds registered by the full-resolution launches are behind
+  // them in the stream (every reader of the clouds goes through the stream or an event recorded on it), and so may be a converged launch or two
+  run_.mirrors_written = run_.results_final = o.all_done;
+  tr.looks = o.looks;
+#ifdef LOAMX_PROF_GN
+  dump_gn_profile_();
 #endif
-      hipLaunchKernelGGL(k_gn_iter, grid, dim3(LX_RES_THREADS), 0, st_, a);
-      if (tm) {
-        LX_HIP(hipEventRecord(ev_[3 + 2 * n_res_launch_], st_));
-        n_res_launch_++;
-      }
-    }
-    if (!early_exit) break;
-    if (!spec_full && want_full) { enqueue_full(1); spec_full = true; }
-    if (it >= maxit) break;
-    if (trace && th2 == 0) th2 = host_us();
-    // the host waits for THIS point of the stream, not for the stream: the caller's on_first_wait may enqueue work of the next run
-    // behind it (the pipeline's pre-staged re-projection), which must not hold this run's results back
-    if (!ev_look_) LX_HIP(hipEventCreateWithFlags(&ev_look_, hipEventDisableTiming));
-    LX_HIP(hipEventRecord(ev_look_, st_));
-    if (on_first_wait && !waited) { waited = true; on_first_wait(); on_first_wait = nullptr; }   // host work that overlaps the wait
-    if (trace && th3 == 0) th3 = host_us();
-    const bool polled = wait_for_mirrors();
-    if (vb_unchecked_) {
-      vb_unchecked_ = false;
-      if (vb_.failed()) { note_bucket_give_up(); return true; }
-    }
-    int need = 0;
-    all_done = true;
-    for (uint32_t k = 0; k < ns; k++) {
-      all_done = all_done && h_stats_.p[k].done;
-      need = std::max(need, h_stats_.p[k].iterations);
-    }
-    // poses / stats are final and on the host; the clouds registered by the speculative launch are behind them in the stream
-    // (every reader of the clouds goes through the stream or an event recorded on it), and so may be a converged launch or two
-    if (all_done) { pred_iters_ = need; mirrors_written_ = true; results_final_ = spec_full || !want_full; (void)polled; break; }
-    pred_iters_ = it + 1;
-    chunk = 1;
-  }
-  if (early_exit && want_full) {
-    if (!spec_full) enqueue_full(0);
-    else if (!all_done) enqueue_full(2);   // the sweeps that were not done when the first launch looked
-    full_enqueued_ = true;
-  }
-  return false;
+  return o;
 }
 
-void Registrar::run_async() {
+#ifdef LOAMX_PROF_GN
+void Registrar::dump_gn_profile_() {
+  std::vector<unsigned long long> h((size_t)nblk_ * 8);
+  (void)hipStreamSynchronize(st_);
+  (void)hipMemcpy(h.data(), g_gn_dbg.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost);
+  unsigned long long t0 = ~0ull;
+  for (uint32_t t = 0; t < nblk_; t++) if (h[8 * t]) t0 = std::min(t0, h[8 * t]);
+  fprintf(stderr, "[gn iter 0, sweep 0: tile: start / search / rows / reduce us (+solve)]");
+  for (uint32_t t = 0; t < nblk_; t++) {
+    const unsigned long long* v = &h[8 * t];
+    if (!v[0]) continue;
+    if (t % 16 == 0 || v[5]) fprintf(stderr, " %u:%.0f/%.0f/%.0f/%.0f", t, (v[0] - t0) * 0.01, (v[1] - v[0]) * 0.01, (v[2] - v[1]) * 0.01, (v[3] - v[2]) * 0.01);
+    if (v[5]) fprintf(stderr, "(+solve %.0f, ends at %.0f)", (v[5] - v[4]) * 0.01, (v[5] - t0) * 0.01);
+  }
+  fprintf(stderr, "\n");
+  unsigned long long ts[16];
+  (void)hipMemcpyFromSymbol(ts, HIP_SYMBOL(g_solve_ts), sizeof(ts));
+  fprintf(stderr, "[solve_sweep, us since entry] partial sums %.1f  sums+AtA %.1f  qr %.1f  projector %.1f  trig %.1f  update+stores %.1f\n", (ts[1] - ts[0]) * 0.01,
+          (ts[2] - ts[0]) * 0.01, (ts[3] - ts[0]) * 0.01, (ts[4] - ts[0]) * 0.01, (ts[5] - ts[0]) * 0.01, (ts[6] - ts[0]) * 0.01);
+}
+#endif
+
+// an attempt starts from a clean slate: timing, mirrors, and everything the host believes about the run
+void Registrar::begin_attempt_(bool legacy) {
+  if (timing_) LX_HIP(hipEventRecord(ev_[0], st_));   // (per attempt: a run repeated through the general voxel kernel reports the attempt that counted — ADVICE.md round 3)
+  n_res_launch_ = 0;
+  if (early_exit) memset(h_stats_.p, 0, sizeof(SweepStats) * n_sweeps_);   // mirrors of sweeps that never reach an update stay "not done"
+  run_ = Run{};
+  run_.vb_unchecked = !legacy && n_in_ > 0;
+}
+
+void Registrar::run_async(bool force_general) {
   LX_REQUIRE(n_sweeps_ > 0, "run() before upload()");
   TraceRange trace_range("loamx:registration");
   static const bool trace = getenv("LOAMX_REG_TRACE") != nullptr;
-  const double th0 = trace ? host_us() : 0.0;
-  double th1 = 0, th2 = 0, th3 = 0;
+  RunTrace tr{trace, trace ? host_us() : 0.0};
   LX_HIP(hipSetDevice(device_));
-  const uint32_t ns = n_sweeps_, nseg = 2 * ns, n = n_in_;
-  const bool can_bucket = !vb_disabled_ && VoxBucket::fits(n, nseg);
-  for (int attempt = 0; attempt < 2; attempt++) {
+  const bool can_bucket = !force_general && !vb_disabled_ && VoxBucket::fits(n_in_, 2 * n_sweeps_);
+  RegOutcome o;
+  for (int attempt = 0; attempt < 2; attempt++) {   // (the second: the bucketed voxel stage gave up, again through the general kernel)
     const bool legacy = attempt == 1 || !can_bucket;
-    if (timing_) LX_HIP(hipEventRecord(ev_[0], st_));   // (per attempt: a run repeated through the general voxel kernel reports the attempt that counted — ADVICE.md round 3)
-    n_res_launch_ = 0;
-    if (early_exit) memset(h_stats_.p, 0, sizeof(SweepStats) * ns);   // mirrors of sweeps that never reach an update stay "not done"
-    vb_unchecked_ = !legacy && n > 0;
-    full_dl_sweep_ = -1;
-    full_enqueued_ = false;
-    results_final_ = false;
+    begin_attempt_(legacy);
     enqueue_front(legacy);
-    if (trace) th1 = host_us();
-    mirrors_written_ = false;
-    bool again = false;
-    if (submap_sufficient() && n > 0) {   // BasicLaserMapping.cpp:628-629 guard
-      again = run_iterations(trace, th2, th3);
-      if (trace && th2 == 0) th2 = host_us();
+    if (trace) tr.front = host_us();
+    o = RegOutcome{};
+    if (submap_sufficient() && n_in_ > 0) {   // BasicLaserMapping.cpp:628-629 guard
+      o = run_iterations(tr);
+      if (trace && tr.first_gn == 0) tr.first_gn = host_us();
     }
-    if (!again && early_exit && vb_unchecked_) {   // a blocking caller goes on to use the voxel stage's output: look at its verdict now
+    bool again = o.gave_up;
+    if (!again && early_exit && run_.vb_unchecked) {   // a blocking caller goes on to use the voxel stage's output: look at its verdict now
       LX_HIP(hipStreamSynchronize(st_));
-      vb_unchecked_ = false;
-      again = vb_.failed();
-      if (again) note_bucket_give_up();
+      again = bucket_stage_gave_up_();
     }
     if (!again) break;
   }
-  if (n_full_ && !defer_full && !full_enqueued_) enqueue_full(0);
+  if (n_full_ && !defer_full && !o.full_enqueued) enqueue_full(0);
   if (timing_) { LX_HIP(hipEventRecord(ev_[1], st_)); timed_run_ = true; }
   LX_HIP(hipGetLastError());
   if (on_first_wait) on_first_wait();   // host work of the caller that overlaps the device work enqueued above
-  if (trace && th3 == 0) th3 = host_us();
+  if (trace && tr.callback == 0) tr.callback = host_us();
   if (trace)
-    fprintf(stderr, "[reg] voxel stage enqueued %.0f us, first iterations enqueued %.0f, callback done %.0f, run_async returns %.0f\n", th1 - th0,
-            th2 - th0, th3 - th0, host_us() - th0);
+    fprintf(stderr, "[reg] voxel stage enqueued %.0f us, first iterations enqueued %.0f, callback done %.0f, run_async returns %.0f, looks %d\n",
+            tr.front - tr.t0, tr.first_gn - tr.t0, tr.callback - tr.t0, host_us() - tr.t0, tr.looks);
 }
 
-void Registrar::note_bucket_give_up() {
-  vb_give_ups_++;
+// the verdict of a bucketed voxel stage that has not been looked at yet (the caller has waited for a point of the stream behind the
+// stage): true when it gave up — it left an empty query set and the full-resolution clouds untouched, the sweeps are run again
+bool Registrar::bucket_stage_gave_up_() {
+  if (!run_.vb_unchecked) return false;
+  run_.vb_unchecked = false;
+  if (!vb_.failed()) return false;
   static const bool trace = getenv("LOAMX_VB_TRACE") != nullptr;
   if (trace) fprintf(stderr, "[voxbucket] gave up (reason mask 0x%x, %u points, %u sweeps): repeating through the general kernel\n", vb_.why(), n_in_, n_sweeps_);
+  return true;
 }
 
-// after a stream synchronisation: a bucketed voxel stage that gave up left an empty query set (and the full-resolution clouds
-// untouched); run the sweeps again through the general kernel
+// after a stream synchronisation
 void Registrar::redo_if_bucket_path_failed() {
-  if (!vb_unchecked_) return;
-  vb_unchecked_ = false;
-  if (!vb_.failed()) return;
-  note_bucket_give_up();
-  const bool keep = vb_disabled_;
-  vb_disabled_ = true;
-  try { run_async(); } catch (...) { vb_disabled_ = keep; throw; }
-  vb_disabled_ = keep;
+  if (!bucket_stage_gave_up_()) return;
+  run_async(/*force_general=*/true);
   LX_HIP(hipStreamSynchronize(st_));
 }
 
@@ -1562,9 +1152,11 @@ void Registrar::finish_with_poses(const float* poses6) {
   LX_HIP(hipMemcpyAsync(guess_.p, h_guess_.p, sizeof(float) * 6 * ns, hipMemcpyHostToDevice, st_));
   hipLaunchKernelGGL(k_pose_set, dim3((ns + 63) / 64), dim3(64), 0, st_, guess_.p, ns, poses_.p);
   enqueue_full(0);
-  full_dl_sweep_ = -1;
-  mirrors_written_ = false;   // the device poses were replaced
-  results_final_ = false;     // ... and new device work was enqueued: the next fetch waits for the stream
+  // the device poses were replaced and new device work was enqueued: the next fetch waits for the stream and copies, an enqueued
+  // download is stale; only the voxel stage's verdict is still owed
+  const bool owed = run_.vb_unchecked;
+  run_ = Run{};
+  run_.vb_unchecked = owed;
   LX_HIP(hipGetLastError());
 }
 
@@ -1680,17 +1272,18 @@ void Registrar::sync() { wait_stream(st_); }
 // final poses / statistics on the host: an early-exit run that saw every sweep converge already holds them (the update
 // step mirrors them into pinned memory), anything else is copied
 void Registrar::fetch_results() {
-  if (results_final_ && !vb_unchecked_) { vox_.check(); vb_.check(); scan_check_errors(); return; }   // run_iterations saw everything complete at its event: no need to wait for what has been enqueued since
-  LX_HIP(hipStreamSynchronize(st_));
+  const bool seen_final = run_.results_final && !run_.vb_unchecked;   // run_iterations saw everything complete at its event: no need to wait for what has been enqueued since
+  if (!seen_final) LX_HIP(hipStreamSynchronize(st_));
   vox_.check();
   vb_.check();
   scan_check_errors();
+  if (seen_final) return;
   redo_if_bucket_path_failed();
-  if (!mirrors_written_) {
+  if (!run_.mirrors_written) {
     LX_HIP(hipMemcpyAsync(h_poses_.p, poses_.p, sizeof(Pose) * n_sweeps_, hipMemcpyDeviceToHost, st_));
     LX_HIP(hipMemcpyAsync(h_stats_.p, stats_.p, sizeof(SweepStats) * n_sweeps_, hipMemcpyDeviceToHost, st_));
     LX_HIP(hipStreamSynchronize(st_));
-    mirrors_written_ = true;
+    run_.mirrors_written = true;
   }
 }
 
@@ -1724,16 +1317,16 @@ void Registrar::download_full_res_async(uint32_t sweep, const loamx_cloud* into)
   const uint32_t a = h_full_off_[sweep], b = h_full_off_[sweep + 1];
   // a landing area of packed records in runtime-pinned memory with room for the cloud takes the copy itself (download_full_res() then
   // only waits); anything else goes through this object's pinned block and is unpacked there
-  full_dl_direct_ = nullptr;
+  run_.full_dl_direct = nullptr;
   if (into && b > a && into->count >= b - a && packed_layout(into) && host_pinned(into->data, sizeof(float4) * (b - a))) {
     // (a kernel storing to the pinned block instead of this copy was measured: 8 us slower per sweep — profiles/r05_ab.md section 6)
     LX_HIP(hipMemcpyAsync(into->data, full_.p + a, sizeof(float4) * (b - a), hipMemcpyDeviceToHost, st_));
-    full_dl_direct_ = into->data;
+    run_.full_dl_direct = into->data;
   } else {
     h_full_dl_.reserve((size_t)(b - a) + 1);
     if (b > a) LX_HIP(hipMemcpyAsync(h_full_dl_.p, full_.p + a, sizeof(float4) * (b - a), hipMemcpyDeviceToHost, st_));
   }
-  full_dl_sweep_ = (int)sweep;
+  run_.full_dl_sweep = (int)sweep;
 }
 
 int Registrar::download_full_res(uint32_t sweep, loamx_cloud* out) {
@@ -1741,13 +1334,13 @@ int Registrar::download_full_res(uint32_t sweep, loamx_cloud* out) {
   check_cloud(out, false);
   fetch_results();
   const uint32_t a = h_full_off_[sweep], b = h_full_off_[sweep + 1];
-  const bool landed = full_dl_sweep_ == (int)sweep && full_dl_direct_ && full_dl_direct_ == out->data;   // the copy went straight into `out`
-  if (full_dl_sweep_ != (int)sweep || (full_dl_direct_ && !landed)) {   // not asked for ahead of time (or the clouds were registered again since, or into other memory): copy now
+  const bool landed = run_.full_dl_sweep == (int)sweep && run_.full_dl_direct && run_.full_dl_direct == out->data;   // the copy went straight into `out`
+  if (run_.full_dl_sweep != (int)sweep || (run_.full_dl_direct && !landed)) {   // not asked for ahead of time (or the clouds were registered again since, or into other memory): copy now
     h_full_dl_.reserve((size_t)(b - a) + 1);   // (pinned: a copy into pageable memory is staged by the runtime)
     if (b > a) LX_HIP(hipMemcpyAsync(h_full_dl_.p, full_.p + a, sizeof(float4) * (b - a), hipMemcpyDeviceToHost, st_));
   }
-  full_dl_sweep_ = -1;
-  full_dl_direct_ = nullptr;
+  run_.full_dl_sweep = -1;
+  run_.full_dl_direct = nullptr;
   wait_stream(st_);
   if (landed) { out->count = b - a; return LOAMX_OK; }
   return unpack_cloud(h_full_dl_.p, b - a, out);

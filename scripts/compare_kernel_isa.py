@@ -1,8 +1,10 @@
 """Compare the gfx950 instruction streams of the kernels two builds of one object file hold (e.g. ingest.o of two commits):
-python scripts/compare_kernel_isa.py OLD.o NEW.o [name-substring ...]
+python scripts/compare_kernel_isa.py OLD.o NEW.o[,NEW2.o ...] [name-substring ...]
+(several NEW objects, comma-separated: kernels that moved to a file of their own are looked up in all of them)
 
 Each object's device code is unbundled (clang-offload-bundler) and disassembled (llvm-objdump); per kernel present in OLD the
-instructions are compared with branch-target labels and the trailing alignment padding stripped.  Exit status 1 when a kernel differs."""
+instructions are compared with branch-target labels and the trailing alignment padding stripped.  Exit status 1 when a kernel differs,
+is missing from NEW, or exists only in NEW."""
 import os
 import re
 import subprocess
@@ -36,9 +38,15 @@ def main():
     old_obj, new_obj, pats = sys.argv[1], sys.argv[2], sys.argv[3:]
     with tempfile.TemporaryDirectory() as tmp:
         os.makedirs(os.path.join(tmp, "old"))
-        os.makedirs(os.path.join(tmp, "new"))
-        a, b = kernels(old_obj, os.path.join(tmp, "old")), kernels(new_obj, os.path.join(tmp, "new"))
+        a, b = kernels(old_obj, os.path.join(tmp, "old")), {}
+        for k, obj in enumerate(new_obj.split(",")):
+            os.makedirs(os.path.join(tmp, f"new{k}"))
+            b.update(kernels(obj, os.path.join(tmp, f"new{k}")))
     bad = 0
+    for name in sorted(set(b) - set(a)):
+        if not pats or any(p in name for p in pats):
+            bad += 1
+            print("ONLY IN NEW " + name, 0, len(b[name]))
     for name in sorted(a):
         if pats and not any(p in name for p in pats):
             continue

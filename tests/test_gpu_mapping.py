@@ -359,3 +359,57 @@ def test_epoch_merge_insert_equals_the_map_side_of_process(orc, small_world):
     assert grew >= n - 1
     # a handle that went through process() itself holds the same map as the one that was only told the poses
     print(f"epoch merge: worst matched map-point distance {worst:.2e} over {n} inserts")
+
+
+def test_full_res_registered_when_a_sweep_converges_after_the_first_look(orc, small_world):
+    """One handle, two sweeps.  Sweep 1 starts from its true pose and converges at once, so the registration's first chunk for sweep 2
+    is max(it1 + 1, 2) launches (csrc/reg_schedule.hpp); sweep 2 starts 1 m off and needs more than that but fewer than the bound: it
+    converges at a LATER look, behind the speculative full-resolution launch, which passed it over.  Its cloud must still come back in
+    the map frame (the closing mode-2 launch); left out, the points stay in the sensor frame, off by the whole pose.  The displacement
+    was chosen with the oracle, whose counts for it are it1 = 1, it2 = 5."""
+    n = 5
+    poses = synth.trajectory(n)
+    osr, ood, omp = op.ScanRegistration(orc), op.LaserOdometry(orc), op.LaserMapping(orc)
+    steps = []
+    for k in range(n):
+        sw = synth.make_sweep(small_world, "VLP-16", poses[k], poses[k + 1], seed=k, az_steps=1200)
+        ood.set_features(osr.process(sw.points, sw.ring_sizes))
+        ood.process()
+        cubes = (omp.cloud("corner_cubes"), omp.cloud("surf_cubes"))
+        inputs = (ood.last_corner(), ood.last_surf(), ood.full_to_end(), ood.transform_sum)
+        omp.set_inputs(*inputs)
+        assert omp.process()
+        steps.append((cubes, inputs, omp.transform("aft")))
+    displacement = np.array([0.0, 0.05, 0.0, 1.0, 0.0, 0.6], np.float32)
+    max_iterations = 10
+    o, g = op.LaserMapping(orc), loamx.LaserMapping()
+    o.load_cubes(*steps[3][0])
+    g.load_cubes(*steps[3][0])
+    iters, full = {}, None
+    for k, off in ((3, 0 * displacement), (4, displacement)):
+        _, (lc, ls, full_end, ts), true_pose = steps[k]
+        for h in (o, g):                       # the guess is aft o (bef^-1 o sum): with bef = sum it is aft itself
+            h.set_transform("aft", true_pose + off)
+            h.set_transform("bef", ts)
+        o.set_inputs(lc, ls, full_end, ts)
+        assert o.process()
+        g.update_odometry(ts)
+        rc, full = g.process(lc, ls, full_end)
+        assert rc == loamx.OK
+        iters[k] = (o.stats()["iterations"], g.stats()["iterations"])
+    print(f"iterations (oracle, device): sweep 1 {iters[3]}, sweep 2 {iters[4]}")
+    for side in (0, 1):
+        it1, it2 = iters[3][side], iters[4][side]
+        assert max(it1 + 1, 2) < it2 < max_iterations, (side, it1, it2)
+    # the input cloud under the returned pose (rotateZXY + translation, BasicLaserMapping.cpp:282-292), in double
+    rx, ry, rz, tx, ty, tz = (float(v) for v in g.transform("aft"))
+    x, y, z = steps[4][1][2][:, :3].astype(np.float64).T
+    x, y = np.cos(rz) * x - np.sin(rz) * y, np.sin(rz) * x + np.cos(rz) * y
+    y, z = np.cos(rx) * y - np.sin(rx) * z, np.sin(rx) * y + np.cos(rx) * z
+    x, z = np.cos(ry) * x + np.sin(ry) * z, np.cos(ry) * z - np.sin(ry) * x
+    want = np.stack([x + tx, y + ty, z + tz], 1)
+    assert len(full) == len(want)
+    d = float(np.abs(full[:, :3] - want).max())
+    print(f"registered full-resolution cloud of sweep 2 against the input under the returned pose: {d:.2e}")
+    assert d < 2e-5, d   # (as the other full-resolution comparisons of this scene; the oracle's own cloud is 9e-6 from the double product)
+    assert np.abs(g.transform("aft") - o.transform("aft")).max() < POSE_TOL
