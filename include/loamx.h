@@ -411,6 +411,26 @@ int loamx_batch_xrec_stress(loamx_batch* h, uint32_t pairs, uint32_t rounds, uin
  * pcl::VoxelGrid's output order).  count fields: capacity in, size out; LOAMX_E_CAPACITY when a cloud does not fit. */
 int loamx_batch_download_ds(loamx_batch* h, uint32_t sweep, loamx_cloud* corner_ds, loamx_cloud* surf_ds);
 
+/* Parity hook for the segmented voxel grid on its own (pcl::VoxelGrid per segment; test use): n packed x y z intensity points in nseg
+ * segments, given EITHER as contiguous ranges seg_off[nseg + 1] (seg_off[0] = 0, seg_off[nseg] = n) OR as one segment id per point
+ * seg_ids[n] (the other pointer is NULL); valid (optional): one byte per point, 0 = the point is ignored.  Even segments are filtered
+ * with leaf_even, odd ones with leaf_odd.  out_xyzi (room for n points) receives the voxel means of segment 0, 1, ... back to back in
+ * PCL's output order, out_off[nseg + 1] the running count: segment s owns out_xyzi[out_off[s] .. out_off[s + 1]).  The stage runs
+ * as the library's own callers run it (index computation, then the sort and reduction, the kernel chosen by the same dispatch) on
+ * one pipeline and stream per process, whose buffers live on from call to call.  LOAMX_E_HIP when a wait inside the kernels timed out. */
+int loamx_voxel_probe(const float* pts_xyzi, uint32_t n, const uint32_t* seg_off, const uint32_t* seg_ids, const uint8_t* valid, uint32_t nseg,
+                      float leaf_even, float leaf_odd, float* out_xyzi, uint32_t* out_off);
+/* Parity hook for the device-wide exclusive scan of uint32 (test use), on one state buffer per process that is cleared once and
+ * never again.  len = max(n, max_n).  in[len] is uploaded whole; out[len + 1] (and out2[len + 1] when given: a second copy of the
+ * result) are uploaded too, scanned into and read back whole, so the caller sees exactly which words were written: out[0 .. n) = the
+ * exclusive prefix sums of in[0 .. n) mod 2^32, out[n] = *total = their sum.  flags: */
+#define LOAMX_SCAN_COUNT_ON_DEVICE 1u /* the kernel reads n from device memory and the launch covers max_n elements; an n beyond max_n
+                                       * is cut to the launch and answered with LOAMX_E_HIP (the buffers are still read back).
+                                       * Without it n travels as a kernel argument and max_n only sizes the buffers */
+#define LOAMX_SCAN_IN_PLACE 2u        /* the input is scanned inside the result buffer */
+#define LOAMX_SCAN_ZERO_IN 4u         /* the scan clears the input it has read; in[len] receives the input buffer as the scan left it */
+int loamx_scan_probe(uint32_t* in, uint32_t n, uint32_t max_n, uint32_t flags, uint32_t* out, uint32_t* total, uint32_t* out2);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Streaming pipeline: n independent streams, each advancing one sweep per step through feature extraction ->
  * odometry -> registration against the frozen sub-map.  A stream keeps the reference's sequential state (odometry

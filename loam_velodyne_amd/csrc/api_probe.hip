@@ -1,0 +1,132 @@
+// C-ABI: parity hooks for two device primitives that otherwise only run inside whole pipelines — the segmented voxel grid
+// (voxel.hpp) and the chained scan (scan.hpp).  Host glue only: each hook stages the caller's arrays, runs the primitive the way
+// its callers do, waits, checks the error word and copies the results back.  Both keep ONE object per process (never freed, guarded
+// by a mutex), so consecutive calls reuse its buffers and its state — which is part of what the tests look at.
+#include <mutex>
+#include "voxel.hpp"
+
+using namespace loamx;
+
+namespace {
+
+hipStream_t probe_stream() {   // (under the caller's lock)
+  static hipStream_t st = nullptr;
+  if (!st) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+    select_device(dev);
+    st = create_stream(0);
+  }
+  return st;
+}
+
+struct VoxelProbe {
+  VoxelPipeline vox;
+  DevBuf<float4> pts, out;
+  DevBuf<uint8_t> valid;
+  DevBuf<uint32_t> seg, out_off;
+  bool ready = false;
+};
+
+struct ScanProbe {
+  DevBuf<unsigned long long> state;   // zero-filled once: the scan's epoch-tagged words live on from call to call
+  DevBuf<uint32_t> in, out, out2, words;   // words: [0] the count, [1] the total
+  bool ready = false;
+};
+
+template <class T> void upload(T* dst, const T* src, size_t n, hipStream_t st) {
+  if (n) LX_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, st));
+}
+template <class T> void download(T* dst, const T* src, size_t n, hipStream_t st) {
+  if (n) LX_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, st));
+}
+
+}  // namespace
+
+extern "C" {
+
+int loamx_voxel_probe(const float* pts_xyzi, uint32_t n, const uint32_t* seg_off, const uint32_t* seg_ids, const uint8_t* valid, uint32_t nseg,
+                      float leaf_even, float leaf_odd, float* out_xyzi, uint32_t* out_off) {
+  return guard([&]() {
+    LX_REQUIRE(out_off && (out_xyzi || n == 0) && (pts_xyzi || n == 0), "NULL argument");
+    LX_REQUIRE((seg_off != nullptr) != (seg_ids != nullptr), "exactly one of seg_off / seg_ids must be given");
+    LX_REQUIRE(nseg >= 1 && nseg < (1u << 20), "nseg must be in [1, 2^20)");
+    LX_REQUIRE(n + 1 < SCAN_MAX_N, "too many points for one voxel pass");
+    LX_REQUIRE(leaf_even > 0.f && leaf_odd > 0.f && std::isfinite(leaf_even) && std::isfinite(leaf_odd), "leaf sizes must be positive");
+    if (seg_off) {
+      LX_REQUIRE(seg_off[0] == 0u && seg_off[nseg] == n, "seg_off must run from 0 to n");
+      for (uint32_t s = 0; s < nseg; s++) LX_REQUIRE(seg_off[s] <= seg_off[s + 1], "seg_off must not decrease");
+    } else {
+      for (uint32_t i = 0; i < n; i++) LX_REQUIRE(seg_ids[i] < nseg, "segment id out of range");
+    }
+    LX_REQUIRE(packed_all_finite(reinterpret_cast<const float4*>(pts_xyzi), n), "non-finite coordinate");
+    static std::mutex mu;
+    static VoxelProbe* P = nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    hipStream_t st = probe_stream();
+    if (!P) P = new VoxelProbe;
+    if (!P->ready) { P->vox.init(st); P->ready = true; }
+    P->pts.reserve((size_t)n + 1); P->out.reserve((size_t)n + 1);
+    P->valid.reserve((size_t)n + 1);
+    P->seg.reserve(std::max<size_t>(n, (size_t)nseg + 1) + 1);
+    P->out_off.reserve((size_t)nseg + 2);
+    P->vox.reserve(n + 1, nseg);
+    upload(P->pts.p, reinterpret_cast<const float4*>(pts_xyzi), n, st);
+    if (valid) upload(P->valid.p, valid, n, st);
+    upload(P->seg.p, seg_off ? seg_off : seg_ids, seg_off ? (size_t)nseg + 1 : (size_t)n, st);
+    const uint8_t* d_valid = valid ? P->valid.p : nullptr;
+    const uint32_t* d_off = seg_off ? P->seg.p : nullptr;
+    const uint32_t* d_ids = seg_ids ? P->seg.p : nullptr;
+    P->vox.compute_ijk(P->pts.p, d_valid, n, d_off, nseg, 1.0f / leaf_even, 1.0f / leaf_odd, d_ids);
+    LX_HIP(hipGetLastError());
+    P->vox.sort_reduce(P->pts.p, d_valid, n, d_off, nseg, P->out.p, P->out_off.p, d_ids);
+    download(reinterpret_cast<float4*>(out_xyzi), P->out.p, n, st);
+    download(out_off, P->out_off.p, (size_t)nseg + 1, st);
+    LX_HIP(hipStreamSynchronize(st));
+    P->vox.check();
+    return LOAMX_OK;
+  });
+}
+
+int loamx_scan_probe(uint32_t* in, uint32_t n, uint32_t max_n, uint32_t flags, uint32_t* out, uint32_t* total, uint32_t* out2) {
+  return guard([&]() {
+    const bool on_device = (flags & LOAMX_SCAN_COUNT_ON_DEVICE) != 0, in_place = (flags & LOAMX_SCAN_IN_PLACE) != 0,
+               zero_in = (flags & LOAMX_SCAN_ZERO_IN) != 0;
+    const size_t len = std::max(n, max_n);
+    LX_REQUIRE((flags & ~7u) == 0u, "unknown flag");
+    LX_REQUIRE(out && total && (in || len == 0), "NULL argument");
+    LX_REQUIRE(!(in_place && zero_in), "zero_in needs an input buffer of its own");
+    LX_REQUIRE(len <= (size_t)CHAINED_SCAN_MAX_TILES * SCAN_TILE, "too many elements for one scan");
+    static std::mutex mu;
+    static ScanProbe* P = nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    hipStream_t st = probe_stream();
+    if (!P) P = new ScanProbe;
+    if (!P->ready) {
+      P->state.reserve(chained_scan_state_words());
+      LX_HIP(hipMemsetAsync(P->state.p, 0, sizeof(unsigned long long) * chained_scan_state_words(), st));
+      P->words.reserve(2);
+      P->ready = true;
+    }
+    P->in.reserve(len + 1); P->out.reserve(len + 1); P->out2.reserve(len + 1);
+    // the result buffers start from the caller's contents, so that the caller sees which words the scan wrote
+    upload(P->out.p, out, len + 1, st);
+    if (out2) upload(P->out2.p, out2, len + 1, st);
+    uint32_t* d_in = in_place ? P->out.p : P->in.p;
+    upload(d_in, in, len, st);
+    const uint32_t h_words[2] = {n, 0xdeadbeefu};
+    upload(P->words.p, h_words, 2, st);
+    exclusive_scan_u32_chained(d_in, P->out.p, P->state.p, P->words.p, P->words.p + 1, max_n, st, out2 ? P->out2.p : nullptr,
+                               zero_in ? d_in : nullptr, on_device ? 0xffffffffu : n);
+    LX_HIP(hipGetLastError());
+    download(out, P->out.p, len + 1, st);
+    if (out2) download(out2, P->out2.p, len + 1, st);
+    if (zero_in) download(in, P->in.p, len, st);
+    download(total, P->words.p + 1, 1, st);
+    LX_HIP(hipStreamSynchronize(st));
+    scan_check_errors();
+    return LOAMX_OK;
+  });
+}
+
+}  // extern "C"

@@ -6,6 +6,12 @@
 // Voxel membership = floor(p * (1/leaf)) per axis (PCL multiplies by the reciprocal leaf); output order inside a
 // segment = ascending (iz, iy, ix) = PCL's ascending voxel index; the mean covers x, y, z and intensity.  PCL's
 // unstable std::sort leaves the summation order inside a voxel unspecified; here it is input order (stable radix sort).
+// The voxel index relative to the box's corner is computed in integers here, whereas PCL subtracts in float
+// (floor(p * inv) - (float)min_b): the two agree while every axis extent is <= 2^24 voxels and split beyond that (by reading, not
+// run: x in {-2, 2^25 + 4, 2^25 + 8} at leaf 1 — PCL's float difference merges the last two, the kernels keep them apart).  No
+// caller comes near that extent and the tests stay inside it (tests/test_voxel_cases_cpu.py asserts so for every case).
+// A second difference by reading: a pass-through segment comes out as (0 + x) / 1 per point, which equals PCL's copy except that a
+// coordinate or intensity of -0.0 comes out as +0.0.
 #pragma once
 #include <algorithm>
 #include "common.h"

@@ -263,6 +263,46 @@ class Batch:
         return int(lib().loamx_batch_stream(self.h) or 0)
 
 
+SCAN_COUNT_ON_DEVICE, SCAN_IN_PLACE, SCAN_ZERO_IN = 1, 2, 4
+
+
+def voxel_probe(points, nseg, leaf_even, leaf_odd=None, seg_off=None, seg_ids=None, valid=None):
+    """parity hook: the segmented voxel grid on its own (loamx_voxel_probe) -> (voxel means of all segments back to back, out_off[nseg + 1]).
+    Exactly one of seg_off (contiguous ranges, nseg + 1 offsets) / seg_ids (one id per point); valid: optional mask, 0 = ignored."""
+    p = as_points(np.asarray(points, np.float32).reshape(-1, 4))
+    n = len(p)
+    off = None if seg_off is None else np.ascontiguousarray(seg_off, np.uint32)
+    ids = None if seg_ids is None else np.ascontiguousarray(seg_ids, np.uint32)
+    val = None if valid is None else np.ascontiguousarray(valid, np.uint8)
+    assert off is None or len(off) == nseg + 1
+    assert ids is None or len(ids) == n
+    assert val is None or len(val) == n
+    out = np.zeros((max(n, 1), 4), np.float32)
+    out_off = np.zeros(nseg + 1, np.uint32)
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    _check(lib().loamx_voxel_probe(ptr(p), C.c_uint32(n), ptr(off), ptr(ids), ptr(val), C.c_uint32(nseg), C.c_float(leaf_even),
+                                   C.c_float(leaf_even if leaf_odd is None else leaf_odd), ptr(out), ptr(out_off)))
+    return out[:int(out_off[-1])].copy(), out_off
+
+
+def scan_probe(values, n, max_n=0, flags=0, out_fill=0, want_out2=False):
+    """parity hook: the chained exclusive scan on the process's state buffer (loamx_scan_probe).  values: the whole input buffer,
+    max(n, max_n) words.  The result buffers start filled with out_fill.  Returns dict(rc, out, total, out2, input_after): rc is the
+    call's code (E_HIP after a cut count: the buffers are returned all the same), input_after the input buffer as the scan left it
+    (with SCAN_ZERO_IN)."""
+    length = max(n, max_n)
+    v = np.ascontiguousarray(values, np.uint32).copy()
+    assert v.shape == (length,)
+    out = np.full(length + 1, out_fill, np.uint32)
+    out2 = np.full(length + 1, out_fill, np.uint32) if want_out2 else None
+    total = np.zeros(1, np.uint32)
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    rc = lib().loamx_scan_probe(ptr(v), C.c_uint32(n), C.c_uint32(max_n), C.c_uint32(flags), ptr(out), ptr(total), ptr(out2))
+    if rc < 0 and rc != E_HIP:
+        _check(rc)
+    return dict(rc=rc, out=out, total=int(total[0]), out2=out2, input_after=v if flags & SCAN_ZERO_IN else None)
+
+
 class TransformMaintenance:
     """loamx_tm_*: BasicTransformMaintenance (host arithmetic, no device)."""
 

@@ -68,9 +68,11 @@ def test_gives_up_cleanly_and_repeats_through_the_general_kernel(orc, monkeypatc
         "dense_blob": ([cl[0], cl[1]], [np.concatenate([sl[0], blob]), sl[1]], guesses[:2], {}),
         "ragged": ([cl[0], cl[1][:0], cl[2][:7]], [sl[0], sl[1][:0], sl[2][:5]], guesses, {}),
     }
+    first = {}
     for name, (c, s, g, cfg) in cases.items():
         monkeypatch.delenv("LOAMX_VOX_LEGACY", raising=False)
         p0, s0, d0 = _run(cm, sm, c, s, g, **cfg)
+        first[name] = d0
         monkeypatch.setenv("LOAMX_VOX_LEGACY", "1")
         p1, s1, d1 = _run(cm, sm, c, s, g, **cfg)
         assert np.array_equal(p0, p1) and np.array_equal(s0, s1), name
@@ -82,3 +84,9 @@ def test_gives_up_cleanly_and_repeats_through_the_general_kernel(orc, monkeypatc
     _, _, d = _run(cm, sm, c, s, g)
     oc, osf = _oracle_ds(orc, cm, sm, c[0], s[0], g[0])
     assert np.array_equal(d[0][0], oc) and np.array_equal(d[0][1], osf)
+    # the pass-through clouds are the oracle's too (device against device alone would let both paths be wrong together)
+    c, s, g, cfg = cases["tiny_leaf"]
+    for k in range(len(c)):
+        oc, osf = _oracle_ds(orc, cm, sm, c[k], s[k], g[k], cornerLeaf=cfg["corner_filter_size"], surfLeaf=cfg["surf_filter_size"])
+        assert len(oc) == len(c[k]) and len(osf) == len(s[k])   # (nothing was filtered)
+        assert np.array_equal(first["tiny_leaf"][k][0], oc) and np.array_equal(first["tiny_leaf"][k][1], osf), k
