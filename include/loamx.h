@@ -430,6 +430,26 @@ int loamx_voxel_probe(const float* pts_xyzi, uint32_t n, const uint32_t* seg_off
 #define LOAMX_SCAN_IN_PLACE 2u        /* the input is scanned inside the result buffer */
 #define LOAMX_SCAN_ZERO_IN 4u         /* the scan clears the input it has read; in[len] receives the input buffer as the scan left it */
 int loamx_scan_probe(uint32_t* in, uint32_t n, uint32_t max_n, uint32_t flags, uint32_t* out, uint32_t* total, uint32_t* out2);
+/* Parity hook for the counting-sorted grid index on its own (test use): n packed points (x y z w) in K clouds, cloud c =
+ * [off[c], off[c + 1]) with off[0] = 0, off[K] = n, K <= 4096, empty clouds allowed; cell_edge: the initial cell edge, 0.25 .. 16 (it
+ * grows by 1.25x while a cloud's cell table exceeds its budget: 16 M - 2048 cells over K).  One single index and one batch index per
+ * process live on the probes' stream from call to call, with the state every build leaves behind.  flags: */
+#define LOAMX_INDEX_SINGLE 1u      /* the single-cloud index of the registration: K = 1, n >= 1, cell_edge 1.05f, no ring packing */
+#define LOAMX_INDEX_PACK_RING 2u   /* .w of a sorted point = (ring << 24) | index, ring = (int) of the input's .w; 255 = does not fit */
+#define LOAMX_INDEX_FOLD_BOUNDS 4u /* a kernel copies the points and folds them into the index's bounds accumulators as the library's
+                                    * producers do; the build then skips its own bounding-box pass */
+typedef struct loamx_index_desc {
+  float ox, oy, oz, inv_h; /* origin (the cloud's minimum) and 1 / cell edge */
+  int32_t nx, ny, nz;
+  uint32_t ncell;          /* nx * ny * nz (an empty cloud: one cell) */
+  uint32_t cell_base;      /* the cloud's first entry in the cell table */
+  uint32_t pt_base;        /* off[c] */
+} loamx_index_desc;
+/* desc[K]; table[table_cap] receives *table_len = total cells + 1 entries (LOAMX_E_CAPACITY, with *table_len set, when it does not
+ * fit): cell j of cloud c holds sorted points [table[cell_base + j], table[cell_base + j + 1]); sorted_xyzw: room for n points, .w =
+ * the point's index inside its cloud (bit pattern), with the ring byte under LOAMX_INDEX_PACK_RING. */
+int loamx_index_probe(const float* pts_xyzw, uint32_t n, const uint32_t* off, uint32_t K, float cell_edge, uint32_t flags, loamx_index_desc* desc,
+                      uint32_t* table, uint32_t table_cap, uint32_t* table_len, float* sorted_xyzw);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Streaming pipeline: n independent streams, each advancing one sweep per step through feature extraction ->

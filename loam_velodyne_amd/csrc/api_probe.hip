@@ -1,8 +1,10 @@
-// C-ABI: parity hooks for two device primitives that otherwise only run inside whole pipelines — the segmented voxel grid
-// (voxel.hpp) and the chained scan (scan.hpp).  Host glue only: each hook stages the caller's arrays, runs the primitive the way
-// its callers do, waits, checks the error word and copies the results back.  Both keep ONE object per process (never freed, guarded
-// by a mutex), so consecutive calls reuse its buffers and its state — which is part of what the tests look at.
+// C-ABI: parity hooks for three device primitives that otherwise only run inside whole pipelines — the segmented voxel grid
+// (voxel.hpp), the chained scan (scan.hpp) and the sub-map grid index (submap_index.hpp).  Host glue only (plus one small kernel that
+// stands in for the producers which fold the index's bounds): each hook stages the caller's arrays, runs the primitive the way its
+// callers do, waits, checks the error word and copies the results back.  Each keeps ONE object per process (never freed, guarded by a
+// mutex), so consecutive calls reuse its buffers and its state — which is part of what the tests look at.
 #include <mutex>
+#include "submap_index.hpp"
 #include "voxel.hpp"
 
 using namespace loamx;
@@ -33,6 +35,44 @@ struct ScanProbe {
   DevBuf<uint32_t> in, out, out2, words;   // words: [0] the count, [1] the total
   bool ready = false;
 };
+
+struct IndexProbe {
+  SubMapIndex single;
+  SubMapIndexBatch batch;
+  DevBuf<float4> pts, folded;
+  DevBuf<uint32_t> off;
+  std::vector<GridDescB> h_desc;
+  bool ready = false;
+};
+static_assert(sizeof(GridDescB) == sizeof(loamx_index_desc) && sizeof(GridDesc) == 32, "loamx_index_desc mirrors GridDescB");
+
+// The producer of an index's points as the probe plays it: copies the points and folds them into the bounds accumulators the way
+// k_transform_to_end_batch does for SubMapIndexBatch (one thread per point, the cloud by the same binary search, every thread of the
+// workgroup calling cloud_bounds_update) or, for the single index, with the six atomics k_map_split sends to SubMapIndex::d_bounds().
+__global__ __launch_bounds__(256) void k_probe_fold(const float4* __restrict__ src, float4* __restrict__ dst, uint32_t n, const uint32_t* __restrict__ off,
+                                                    uint32_t K, uint32_t* __restrict__ bounds, int single) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = i < n;
+  uint32_t lo = 0;
+  float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (active) {
+    uint32_t hi = K;
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (off[mid] <= i) lo = mid; else hi = mid;
+    }
+    q = src[i];
+    dst[i] = q;
+  }
+  if (single) {
+    if (active) {
+      atomicMin(&bounds[0], enc_f32(q.x)); atomicMin(&bounds[1], enc_f32(q.y)); atomicMin(&bounds[2], enc_f32(q.z));
+      atomicMax(&bounds[3], enc_f32(q.x)); atomicMax(&bounds[4], enc_f32(q.y)); atomicMax(&bounds[5], enc_f32(q.z));
+    }
+  } else {
+    cloud_bounds_update(bounds, active, lo, q.x, q.y, q.z);
+  }
+}
 
 template <class T> void upload(T* dst, const T* src, size_t n, hipStream_t st) {
   if (n) LX_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, st));
@@ -125,6 +165,72 @@ int loamx_scan_probe(uint32_t* in, uint32_t n, uint32_t max_n, uint32_t flags, u
     download(total, P->words.p + 1, 1, st);
     LX_HIP(hipStreamSynchronize(st));
     scan_check_errors();
+    return LOAMX_OK;
+  });
+}
+
+int loamx_index_probe(const float* pts_xyzw, uint32_t n, const uint32_t* off, uint32_t K, float cell_edge, uint32_t flags, loamx_index_desc* desc,
+                      uint32_t* table, uint32_t table_cap, uint32_t* table_len, float* sorted_xyzw) {
+  return guard([&]() {
+    const bool single = (flags & LOAMX_INDEX_SINGLE) != 0, pack_ring = (flags & LOAMX_INDEX_PACK_RING) != 0, fold = (flags & LOAMX_INDEX_FOLD_BOUNDS) != 0;
+    LX_REQUIRE((flags & ~7u) == 0u, "unknown flag");
+    LX_REQUIRE(off && desc && table && table_len && (pts_xyzw || n == 0) && (sorted_xyzw || n == 0), "NULL argument");
+    LX_REQUIRE(K >= 1 && K <= 4096, "K must be in [1, 4096]");
+    LX_REQUIRE(n <= (1u << 24), "too many points for one probe");
+    LX_REQUIRE(off[0] == 0u && off[K] == n, "offsets must run from 0 to n");
+    for (uint32_t c = 0; c < K; c++) LX_REQUIRE(off[c] <= off[c + 1], "offsets must not decrease");
+    LX_REQUIRE(std::isfinite(cell_edge) && cell_edge >= 0.25f && cell_edge <= 16.f, "cell edge must be in [0.25, 16]");
+    LX_REQUIRE(!single || (K == 1 && n >= 1 && cell_edge == 1.05f && !pack_ring), "the single index: one non-empty cloud, cell edge 1.05, no ring packing");
+    LX_REQUIRE(packed_all_finite(reinterpret_cast<const float4*>(pts_xyzw), n), "non-finite coordinate");
+    static std::mutex mu;
+    static IndexProbe* P = nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    hipStream_t st = probe_stream();
+    if (!P) P = new IndexProbe;
+    if (!P->ready) { P->single.init(st); P->batch.init(st); P->ready = true; }
+    P->pts.reserve((size_t)n + 1); P->folded.reserve((size_t)n + 1);
+    P->off.reserve((size_t)K + 2);
+    upload(P->pts.p, reinterpret_cast<const float4*>(pts_xyzw), n, st);
+    const float4* d_pts = P->pts.p;
+    const uint32_t nb = (n + 255) / 256;
+    uint32_t total = 0;
+    if (single) {
+      if (fold) {
+        upload(P->off.p, off, (size_t)K + 1, st);
+        hipLaunchKernelGGL(k_probe_fold, dim3(nb), dim3(256), 0, st, P->pts.p, P->folded.p, n, P->off.p, K, P->single.d_bounds(), 1);
+        LX_HIP(hipGetLastError());
+        d_pts = P->folded.p;
+      }
+      P->single.build(d_pts, n, fold);
+      GridDesc g;
+      download(&g, P->single.desc(), 1, st);
+      LX_HIP(hipStreamSynchronize(st));
+      memcpy(&desc[0], &g, sizeof(g));
+      desc[0].cell_base = 0; desc[0].pt_base = 0;
+      total = g.ncell;
+    } else {
+      P->batch.cell_size = cell_edge;
+      P->batch.pack_ring = pack_ring;
+      if (fold) {
+        P->batch.prepare(K);
+        upload(P->off.p, off, (size_t)K + 1, st);
+        if (n) hipLaunchKernelGGL(k_probe_fold, dim3(nb), dim3(256), 0, st, P->pts.p, P->folded.p, n, P->off.p, K, P->batch.d_bounds(), 0);
+        LX_HIP(hipGetLastError());
+        d_pts = P->folded.p;
+      }
+      P->batch.build(d_pts, off, K, fold ? P->off.p : nullptr, fold);
+      P->h_desc.resize(K);
+      download(P->h_desc.data(), P->batch.desc(0), K, st);
+      LX_HIP(hipStreamSynchronize(st));
+      memcpy(desc, P->h_desc.data(), sizeof(GridDescB) * K);
+      total = P->h_desc[K - 1].cell_base + P->h_desc[K - 1].g.ncell;
+    }
+    *table_len = total + 1;
+    if (total > LX_MAX_CELLS) throw Error(LOAMX_E_HIP, "the descriptors name more cells than the table holds");
+    if (total + 1 > table_cap) throw Error(LOAMX_E_CAPACITY, "table_cap is smaller than the cell table");
+    download(table, single ? P->single.cell_start() : P->batch.cell_table(), (size_t)total + 1, st);
+    download(reinterpret_cast<float4*>(sorted_xyzw), single ? P->single.sorted() : P->batch.sorted(), n, st);
+    LX_HIP(hipStreamSynchronize(st));
     return LOAMX_OK;
   });
 }

@@ -56,23 +56,11 @@ __global__ __launch_bounds__(256) void k_bbox(const float4* __restrict__ pts, ui
 }
 
 // grid descriptor from the bounds (k_bbox, or the producer of the points through SubMapIndex::d_bounds()): the cell edge starts at
-// 1.05 m and grows by 1.25x while the table would not fit (a coarser grid is still exact: the 27-cell neighbourhood only grows)
+// 1.05 m and grows by 1.25x while the table would not fit (grid_fit.hpp)
 __device__ inline GridDesc grid_from_bounds(const uint32_t* __restrict__ scratch, uint32_t max_cells) {
   float mn[3], mx[3];
   for (int a = 0; a < 3; a++) { mn[a] = dec_f32(scratch[a]); mx[a] = dec_f32(scratch[3 + a]); }
-  float h = 1.05f;
-  GridDesc g;
-  for (;;) {
-    g.inv_h = 1.0f / h;
-    g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
-    g.nx = (int)floorf((mx[0] - mn[0]) * g.inv_h) + 1;
-    g.ny = (int)floorf((mx[1] - mn[1]) * g.inv_h) + 1;
-    g.nz = (int)floorf((mx[2] - mn[2]) * g.inv_h) + 1;
-    unsigned long long nc = (unsigned long long)g.nx * g.ny * g.nz;
-    if (nc <= max_cells) { g.ncell = (uint32_t)nc; break; }
-    h *= 1.25f;
-  }
-  return g;
+  return grid_fit(mn, mx, 1.05f, max_cells);
 }
 
 // count: every workgroup derives the descriptor itself (the same arithmetic everywhere; workgroup 0 records it and the scan's count);
@@ -213,17 +201,7 @@ __device__ inline GridDescB bb_make_desc(const uint32_t* __restrict__ enc, const
   if (off[c + 1] != off[c]) {
     float mn[3], mx[3];
     for (int a = 0; a < 3; a++) { mn[a] = dec_f32(enc[bb_word(c, a)]); mx[a] = dec_f32(enc[bb_word(c, 3 + a)]); }
-    float h = cell0;
-    for (;;) {
-      d.g.inv_h = 1.0f / h;
-      d.g.ox = mn[0]; d.g.oy = mn[1]; d.g.oz = mn[2];
-      d.g.nx = (int)floorf((mx[0] - mn[0]) * d.g.inv_h) + 1;
-      d.g.ny = (int)floorf((mx[1] - mn[1]) * d.g.inv_h) + 1;
-      d.g.nz = (int)floorf((mx[2] - mn[2]) * d.g.inv_h) + 1;
-      const unsigned long long nc = (unsigned long long)d.g.nx * d.g.ny * d.g.nz;
-      if (nc <= budget) { d.g.ncell = (uint32_t)nc; break; }
-      h *= 1.25f;
-    }
+    d.g = grid_fit(mn, mx, cell0, budget);
   }
   return d;
 }

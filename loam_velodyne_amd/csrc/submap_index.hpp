@@ -3,16 +3,9 @@
 #pragma once
 #include <cfloat>
 #include "common.h"
+#include "grid_fit.hpp"   // GridDesc, grid_fit()
 
 namespace loamx {
-
-// uniform grid over a sub-map: cell edge >= 1.05 m so the 3x3x3 neighbourhood of a query's cell contains every
-// point within the 1 m gate of BasicLaserMapping.cpp:671/:760.
-struct GridDesc {
-  float ox, oy, oz, inv_h;
-  int nx, ny, nz;
-  uint32_t ncell;
-};
 
 constexpr uint32_t LX_MAX_CELLS = 16u * 1024 * 1024 - 2048;   // scan limit (scan.hpp)
 

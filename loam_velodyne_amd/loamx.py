@@ -303,6 +303,31 @@ def scan_probe(values, n, max_n=0, flags=0, out_fill=0, want_out2=False):
     return dict(rc=rc, out=out, total=int(total[0]), out2=out2, input_after=v if flags & SCAN_ZERO_IN else None)
 
 
+INDEX_SINGLE, INDEX_PACK_RING, INDEX_FOLD_BOUNDS = 1, 2, 4
+INDEX_MAX_CELLS = 16 * 1024 * 1024 - 2048
+INDEX_DESC = np.dtype([("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("inv_h", "<f4"), ("nx", "<i4"), ("ny", "<i4"), ("nz", "<i4"),
+                       ("ncell", "<u4"), ("cell_base", "<u4"), ("pt_base", "<u4")])
+_index_table = None
+
+
+def index_probe(points, off, cell_edge=1.05, flags=0):
+    """parity hook: the counting-sorted grid index on its own (loamx_index_probe) on the process's single / batch index ->
+    dict(desc: K records of INDEX_DESC, table: total cells + 1 entries, sorted: (n, 4) float32 whose .w words are indices)."""
+    global _index_table
+    p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 4))
+    off = np.ascontiguousarray(off, np.uint32)
+    n, K = len(p), len(off) - 1
+    if _index_table is None:
+        _index_table = np.empty(INDEX_MAX_CELLS + 2, np.uint32)   # (the largest table there is; pages are touched as far as a build writes)
+    desc = np.zeros(max(K, 1), INDEX_DESC)
+    out = np.zeros((max(n, 1), 4), np.float32)
+    tlen = np.zeros(1, np.uint32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(lib().loamx_index_probe(ptr(p), C.c_uint32(n), ptr(off), C.c_uint32(K), C.c_float(cell_edge), C.c_uint32(flags), ptr(desc),
+                                   ptr(_index_table), C.c_uint32(len(_index_table)), ptr(tlen), ptr(out)))
+    return dict(desc=desc[:K], table=_index_table[:int(tlen[0])].copy(), sorted=out[:n])
+
+
 class TransformMaintenance:
     """loamx_tm_*: BasicTransformMaintenance (host arithmetic, no device)."""
 
