@@ -668,6 +668,64 @@ int loamx_densemap_save_pcd(loamx_densemap* h, const char* path, int axes);
 /* host only: any cloud as a binary PCD v0.7 file, fields x y z intensity (F 4); axes as above */
 int loamx_write_pcd(const char* path, const loamx_cloud* c, int axes);
 
+/* Free-space carving (optional, off by default: a handle that never enables it behaves, allocates and exports as described above).
+ * A sweep ray that reaches a far surface proves the voxels it crossed empty; counting those crossings per voxel is what lets an
+ * export drop the returns of cars and pedestrians, which otherwise stay in the map as smears along their paths.
+ *
+ * loamx_densemap_enable_carving is allowed only on an empty map (a fresh handle, or right after reset; otherwise LOAMX_E_INVALID
+ * and the handle is unchanged).  It allocates two uint32_t words per slot beside the table: miss, the number of rays that crossed
+ * the voxel, and stamp, the sequence number of the last add call that put a point into it.  Carving stays on until the handle is
+ * destroyed; reset clears both words of every slot.
+ * Per add call (add, add_from_map, add_from_pipeline alike, on the same stream as the insert): the call takes the next sequence
+ * number seq (1, 2, ...), inserts as above while storing stamp = seq into every voxel it adds a point to, and then traces rays.
+ * The ray of point i of the call (i its index in the call's cloud) is traced iff all of these hold, tested in this order, each failed
+ * test counting in a statistic of its own:  the point was added (range and key filters above; no statistic);  i % ray_stride == 0;
+ * max_range == 0 or d2 <= max_range^2 (d2 as above, the square in f32);  the origin's cell passes |i| < 2^20 on every axis and
+ * n_steps <= max_steps (one statistic for the two).
+ * The traversal, in voxel units, f32, no fused multiply-add, / correctly rounded.  Per axis a:  so = o_a*inv, sp = p_a*inv;
+ * c0 = (int)floorf(so), c1 = (int)floorf(sp);  rem_a = |c1 - c0|, s_a = sign(c1 - c0);  d = sp - so;  and, where rem_a > 0,
+ * b = (float)(c0 + (s_a > 0 ? 1 : 0)), tmax_a = (b - so)/d, tdelta_a = 1.0f/fabsf(d).  n_steps = rem_x + rem_y + rem_z.
+ * One step: among the axes with rem_a > 0 the one with the smallest tmax_a (ties: x before y before z) moves its cell index by s_a,
+ * rem_a -= 1, tmax_a = tmax_a + tdelta_a.  After exactly n_steps steps the walk stands in the point's cell whatever the rounding
+ * did: the step count ends the walk, not a float comparison.
+ * Cell k is the cell after k steps (cell 0 the origin's).  The cells k = 0 .. n_steps - 1 - end_margin are visited (none when that
+ * is negative; the end cell never is).  A visited cell is looked up in the table, read-only; if it is there and its stamp != seq, its
+ * miss goes up by one.  A voxel hit by the same call is not carved by that call ("occupied wins": this keeps ground seen at a
+ * grazing angle); cells that are not in the table are free space already.
+ * Determinism: n, Sx, Sy, Sz keep their property (they depend on neither order nor call boundaries).  miss depends on neither the
+ * thread schedule nor the order of the points within a call (the stride picks by index: with ray_stride > 1 the order decides
+ * WHICH rays are traced).  miss does depend on how the points are split into calls and on the order of the calls, by definition: a
+ * call carves what the earlier calls left, plus its own inserts through the stamp.
+ * Rule: a voxel is dynamic iff miss >= min_misses and (uint64)miss * den > n * num (n the voxel's 64-bit point count); den == 0 is
+ * LOAMX_E_INVALID, a NULL rule is the default rule.  download_static / save_pcd_static export as download / save_pcd minus the
+ * dynamic voxels.  prune removes them from the table on the device (survivors keep n, S*, miss and stamp; adds go on as before).
+ * With carving off every function below except enable_carving and the three host-only helpers answers LOAMX_E_INVALID. */
+typedef struct loamx_densemap_carve_config {
+  float max_range;      /* rays longer than this are not traced; 0 = no limit (default 0) */
+  uint32_t ray_stride;  /* trace the points whose index in the call's cloud is a multiple of it, >= 1 (default 1): the cost knob */
+  uint32_t end_margin;  /* cells before the end cell that are left alone (default 1) */
+  uint32_t max_steps;   /* rays with more steps are not traced, 1..65536 (default 4096) */
+} loamx_densemap_carve_config;
+typedef struct loamx_densemap_static_rule {
+  uint32_t min_misses;  /* default 3 */
+  uint32_t num, den;    /* default 1, 1: more crossings than points */
+} loamx_densemap_static_rule;
+void loamx_densemap_carve_default_config(loamx_densemap_carve_config* cfg);   /* host only */
+void loamx_densemap_static_rule_default(loamx_densemap_static_rule* rule);    /* host only */
+/* host only: the rule on one voxel's n and miss, 1 dynamic / 0 static (LOAMX_E_INVALID: NULL or den == 0) */
+int loamx_densemap_rule_is_dynamic(const loamx_densemap_static_rule* rule, uint64_t n, uint32_t miss);
+int loamx_densemap_enable_carving(loamx_densemap* h, const loamx_densemap_carve_config* cfg /* NULL: the defaults */);
+/* waits for the adds as get_stats does.  stats: rays traced, not traced by stride, by range, by step count or origin key; cells
+ * visited; misses recorded */
+int loamx_densemap_get_carve_stats(loamx_densemap* h, uint64_t stats[6]);
+/* the miss word per voxel in the record order of loamx_densemap_download; *n = voxels (LOAMX_E_CAPACITY, nothing written, when
+ * capacity < *n) */
+int loamx_densemap_download_misses(loamx_densemap* h, uint32_t* out, uint64_t capacity, uint64_t* n);
+int loamx_densemap_download_static(loamx_densemap* h, loamx_cloud* out, int axes, const loamx_densemap_static_rule* rule);
+int loamx_densemap_save_pcd_static(loamx_densemap* h, const char* path, int axes, const loamx_densemap_static_rule* rule);
+/* removed (may be NULL): the number of voxels that left */
+int loamx_densemap_prune(loamx_densemap* h, const loamx_densemap_static_rule* rule, uint64_t* removed);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Place recognition (not in the reference): a database of rotation-invariant sweep descriptors in device memory (Scan Context: a
  * ring x sector polar grid of maximum heights around the sensor) and an exhaustive search for the earlier entries that look like a

@@ -4,6 +4,10 @@
 // accumulation, in one pass over the cloud.  The host keeps an upper bound of the occupancy (last known count + points enqueued since)
 // and enqueues a rehash into a table twice the size before that bound could pass half the slots — no wait for the device.  The known
 // count is refreshed by a kernel store into pinned memory (pinned_copy.hpp), read once an event shows it has landed.
+//
+// Carving (loamx_densemap_enable_carving): two more 32-bit words per slot, miss and stamp.  The insert stamps the voxels of its call; a
+// second kernel behind it walks each sweep ray from the origin towards its point through the voxel grid and counts a miss in every
+// voxel of the table it crosses that the same call did not hit.  The walk only looks keys up: it never claims a slot.
 #include "densemap.hpp"
 #include "pinned_copy.hpp"
 #include "scan.hpp"
@@ -19,8 +23,17 @@ struct DmFilter {
 };
 
 // counters: [0] occupied slots, [1] dropped by range, [2] dropped outside the key range, [3] probe overflow (never set while the host's
-// load rule holds: a guard against hanging the device, reported by the next reading call)
-constexpr int DM_CTR_WORDS = 4;
+// load rule holds: a guard against hanging the device, reported by the next reading call); carving: [4] rays traced, not traced by
+// [5] stride, [6] range, [7] step count or origin key, [8] cells visited, [9] misses recorded
+constexpr int DM_CTR_WORDS = 10;
+
+// what the ray kernel needs beyond the insert's filter (include/loamx.h, loamx_densemap_carve_config)
+struct DmCarve {
+  float max2;
+  int use_max;
+  uint32_t stride, end_margin, max_steps, seq;
+};
+// aux: 2 words per slot beside the table, [2 * slot] miss, [2 * slot + 1] stamp
 
 __device__ inline unsigned long long dm_hash(unsigned long long key, uint32_t shift) {
   return (key * 0x9E3779B97F4A7C15ull) >> shift;
@@ -44,18 +57,45 @@ __device__ inline bool dm_find_or_claim(unsigned long long* __restrict__ keys, u
   return false;
 }
 
+// the probe loop above without the CAS: 1 the key is at `slot`, 0 it is absent, -1 the probe bound was reached
+__device__ inline int dm_find(const unsigned long long* keys, uint32_t mask, uint32_t shift, unsigned long long key, uint32_t& slot) {
+  uint32_t h = (uint32_t)dm_hash(key, shift);
+  for (uint32_t probe = 0; probe <= mask; probe++) {
+    const unsigned long long cur = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == key) { slot = h; return 1; }
+    if (cur == DM_EMPTY) return 0;
+    h = (h + 1u) & mask;
+  }
+  return -1;
+}
+
 // wave-aggregated add of this lane's `c` to a 64-bit counter
 __device__ inline void dm_wave_count(unsigned long long* ctr, bool c) {
   const unsigned long long m = __ballot(c);
   if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(ctr, (unsigned long long)__popcll(m));
 }
+// the same for a count per lane (the wave's sum must fit 32 bits)
+__device__ inline void dm_wave_sum(unsigned long long* ctr, uint32_t v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+  if (v && (threadIdx.x & 63) == 0) atomicAdd(ctr, (unsigned long long)v);
+}
+
+// true when the insert adds p (its range filter and key rule, the same expressions); d2 as the insert computes it
+__device__ inline bool dm_added(const float4 p, const DmFilter& F, float& d2) {
+  const float dx = p.x - F.ox, dy = p.y - F.oy, dz = p.z - F.oz;
+  d2 = (dx * dx + dy * dy) + dz * dz;
+  if (!(d2 >= F.min2 && (!F.use_max || d2 <= F.max2))) return false;
+  return fabsf(floorf(p.x * F.inv)) < DM_IMAX && fabsf(floorf(p.y * F.inv)) < DM_IMAX && fabsf(floorf(p.z * F.inv)) < DM_IMAX;
+}
 
 // one point per thread.  vals: 4 words per slot (n, Sx, Sy, Sz).  COMBINE: equal keys of a wave are summed in LDS first, and one lane
-// per distinct key touches the table (the sweep is in firing order: neighbouring lanes share voxels)
-template <bool COMBINE>
+// per distinct key touches the table (the sweep is in firing order: neighbouring lanes share voxels).  STAMP (carving): that lane also
+// stores the call's sequence number into the slot's stamp word (every writer of a call stores the same value)
+template <bool COMBINE, bool STAMP>
 __global__ __launch_bounds__(256) void k_dm_insert(const float4* __restrict__ pts, uint32_t n, DmFilter F, unsigned long long* __restrict__ keys,
                                                    unsigned long long* __restrict__ vals, uint32_t mask, uint32_t shift,
-                                                   unsigned long long* __restrict__ ctr) {
+                                                   unsigned long long* __restrict__ ctr, uint32_t* __restrict__ aux, uint32_t seq) {
   __shared__ uint32_t acc[4][64][3];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
@@ -127,24 +167,142 @@ __global__ __launch_bounds__(256) void k_dm_insert(const float4* __restrict__ pt
     atomicAdd(&v[1], (unsigned long long)q[0]);
     atomicAdd(&v[2], (unsigned long long)q[1]);
     atomicAdd(&v[3], (unsigned long long)q[2]);
+    if (STAMP) __hip_atomic_store(&aux[2ull * slot + 1], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
-// every occupied slot of the old table into the new one (keys are unique: claim the first empty slot of the probe sequence)
+// One axis of the voxel walk (include/loamx.h): the origin's and the point's cell, the cells between them, and the ray parameter at
+// which the walk next leaves its cell along this axis.  Voxel units, f32, no fused multiply-add (the file is built without contraction).
+struct DmAxis {
+  int c, s;
+  uint32_t rem;
+  float tmax, tdelta;
+};
+__device__ inline bool dm_axis_setup(float o, float p, float inv, DmAxis& A) {
+  const float so = o * inv, sp = p * inv;
+  const float fo = floorf(so);
+  A.c = 0; A.s = 0; A.rem = 0u; A.tmax = 0.f; A.tdelta = 0.f;
+  if (!(fabsf(fo) < DM_IMAX)) return false;   // the origin's cell fails the key rule (NaN too)
+  const int c0 = (int)fo, c1 = (int)floorf(sp);   // (the point was added: |c1| < 2^20)
+  A.c = c0;
+  A.s = c1 > c0 ? 1 : (c1 < c0 ? -1 : 0);
+  A.rem = (uint32_t)(c1 > c0 ? c1 - c0 : c0 - c1);
+  if (A.rem) {
+    const float d = sp - so;   // (not 0: the floors differ)
+    const float b = (float)(c0 + (A.s > 0 ? 1 : 0));
+    A.tmax = (b - so) / d;
+    A.tdelta = 1.0f / fabsf(d);
+  }
+  return true;
+}
+__device__ inline void dm_axis_step(DmAxis& A) {
+  A.c += A.s;
+  A.rem -= 1u;
+  A.tmax = A.tmax + A.tdelta;
+}
+
+// Free-space update behind an insert: one ray per lane.  A block owns 256 * stride consecutive points: every lane first counts the
+// added points of that span that the stride leaves out (coalesced), then lane t walks the ray of point base + t * stride.  Rays of a
+// wave differ in length, so the wave runs as long as its longest ray; each step is one dependent random probe of the key array, and
+// the rays of the other waves on the CU are what hides that latency.  Every loop is bounded by an integer: the span, n_steps <=
+// max_steps, mask + 1 probes.
+__global__ __launch_bounds__(256) void k_dm_carve(const float4* __restrict__ pts, uint32_t n, DmFilter F, DmCarve R,
+                                                  const unsigned long long* keys, uint32_t* aux, uint32_t mask, uint32_t shift,
+                                                  unsigned long long* __restrict__ ctr) {
+  const unsigned long long span = 256ull * R.stride, base = (unsigned long long)blockIdx.x * span;
+  uint32_t left_out = 0u;
+  if (R.stride > 1u) {
+    const unsigned long long end = base + span < (unsigned long long)n ? base + span : (unsigned long long)n;
+    for (unsigned long long j = base + threadIdx.x; j < end; j += 256ull) {
+      float d2;
+      if (j % R.stride != 0ull && dm_added(pts[j], F, d2)) left_out++;
+    }
+  }
+  const unsigned long long i = base + (unsigned long long)threadIdx.x * R.stride;
+  bool traced = false, skip_range = false, skip_steps = false, overflow = false;
+  uint32_t visited = 0u, missed = 0u;
+  if (i < (unsigned long long)n) {
+    const float4 p = pts[i];
+    float d2;
+    if (dm_added(p, F, d2)) {
+      if (R.use_max && !(d2 <= R.max2)) {
+        skip_range = true;
+      } else {
+        DmAxis X, Y, Z;
+        const bool okx = dm_axis_setup(F.ox, p.x, F.inv, X), oky = dm_axis_setup(F.oy, p.y, F.inv, Y), okz = dm_axis_setup(F.oz, p.z, F.inv, Z);
+        const uint32_t n_steps = X.rem + Y.rem + Z.rem;   // (each < 2^21)
+        if (!(okx && oky && okz) || n_steps > R.max_steps) {
+          skip_steps = true;
+        } else {
+          traced = true;
+          // cells k = 0 .. n_steps - 1 - end_margin are visited; cell k is the cell after k steps
+          const uint32_t n_visit = n_steps > R.end_margin ? n_steps - R.end_margin : 0u;
+          for (uint32_t k = 0; k < n_visit; k++) {
+            const unsigned long long key = (unsigned long long)(uint32_t)(X.c + (1 << DM_QBITS)) |
+                                           ((unsigned long long)(uint32_t)(Y.c + (1 << DM_QBITS)) << DM_KBITS) |
+                                           ((unsigned long long)(uint32_t)(Z.c + (1 << DM_QBITS)) << (2 * DM_KBITS));
+            uint32_t slot = 0u;
+            const int f = dm_find(keys, mask, shift, key, slot);
+            visited++;
+            if (f < 0) overflow = true;
+            if (f > 0 && aux[2ull * slot + 1] != R.seq) {   // occupied wins: a voxel this call hit is left alone
+              atomicAdd(&aux[2ull * slot], 1u);
+              missed++;
+            }
+            // the axis with the smallest tmax among those with cells left, ties to the lower axis
+            int ax = -1;
+            float tb = 0.f;
+            if (X.rem) { ax = 0; tb = X.tmax; }
+            if (Y.rem && (ax < 0 || Y.tmax < tb)) { ax = 1; tb = Y.tmax; }
+            if (Z.rem && (ax < 0 || Z.tmax < tb)) { ax = 2; tb = Z.tmax; }
+            if (ax == 0) dm_axis_step(X);
+            else if (ax == 1) dm_axis_step(Y);
+            else dm_axis_step(Z);   // (k < n_steps: some axis has cells left)
+          }
+        }
+      }
+    }
+  }
+  if (overflow) ctr[3] = 1ull;
+  dm_wave_count(&ctr[4], traced);
+  dm_wave_sum(&ctr[5], left_out);
+  dm_wave_count(&ctr[6], skip_range);
+  dm_wave_count(&ctr[7], skip_steps);
+  dm_wave_sum(&ctr[8], visited);
+  dm_wave_sum(&ctr[9], missed);
+}
+
+// include/loamx.h, loamx_densemap_static_rule: the voxel with n points and `miss` crossings is dynamic
+__host__ __device__ inline bool dm_dynamic(const loamx_densemap_static_rule& r, unsigned long long n, uint32_t miss) {
+  return miss >= r.min_misses && (unsigned long long)miss * r.den > n * r.num;
+}
+
+// every occupied slot of the old table into the new one (keys are unique: claim the first empty slot of the probe sequence).  AUX: the
+// slot's miss and stamp words travel with it.  PRUNE (with AUX): the voxels the rule calls dynamic stay behind, and the survivors are
+// counted into ctr[0] (zeroed before the launch)
+template <bool AUX, bool PRUNE>
 __global__ __launch_bounds__(256) void k_dm_rehash(const unsigned long long* __restrict__ okeys, const unsigned long long* __restrict__ ovals,
                                                    uint32_t on, unsigned long long* __restrict__ keys, unsigned long long* __restrict__ vals,
-                                                   uint32_t mask, uint32_t shift, unsigned long long* __restrict__ ctr) {
+                                                   uint32_t mask, uint32_t shift, unsigned long long* __restrict__ ctr,
+                                                   const uint32_t* __restrict__ oaux, uint32_t* __restrict__ aux, loamx_densemap_static_rule rule) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= on) return;
-  const unsigned long long key = okeys[i];
-  if (key == DM_EMPTY) return;
+  const unsigned long long key = i < on ? okeys[i] : DM_EMPTY;
+  bool live = key != DM_EMPTY;
+  if (PRUNE && live) live = !dm_dynamic(rule, ovals[4ull * i], oaux[2ull * i]);
   uint32_t slot = 0;
   bool won = false;
-  if (!dm_find_or_claim(keys, mask, shift, key, slot, won)) { ctr[3] = 1ull; return; }
-  const ulonglong2* s = (const ulonglong2*)(ovals + 4ull * i);
-  ulonglong2* d = (ulonglong2*)(vals + 4ull * slot);
-  d[0] = s[0];
-  d[1] = s[1];
+  if (live) {
+    if (dm_find_or_claim(keys, mask, shift, key, slot, won)) {
+      const ulonglong2* s = (const ulonglong2*)(ovals + 4ull * i);
+      ulonglong2* d = (ulonglong2*)(vals + 4ull * slot);
+      d[0] = s[0];
+      d[1] = s[1];
+      if (AUX) *(uint2*)(aux + 2ull * slot) = *(const uint2*)(oaux + 2ull * i);
+    } else {
+      ctr[3] = 1ull;
+    }
+  }
+  if (PRUNE) dm_wave_count(&ctr[0], won);
 }
 
 // compaction of the occupied slots in slot order: occupied slots per 256-slot block (ballot), then (behind an exclusive scan of those
@@ -158,9 +316,12 @@ __global__ __launch_bounds__(256) void k_dm_count(const unsigned long long* __re
   if (threadIdx.x == 0) blk[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
 }
 
+// (AUX: the slot's miss word too)
+template <bool AUX>
 __global__ __launch_bounds__(256) void k_dm_compact(const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ vals,
                                                     uint32_t slots, const uint32_t* __restrict__ blk_off, unsigned long long* __restrict__ okeys,
-                                                    unsigned long long* __restrict__ ovals) {
+                                                    unsigned long long* __restrict__ ovals, const uint32_t* __restrict__ aux,
+                                                    uint32_t* __restrict__ omiss) {
   __shared__ uint32_t wc[4];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
@@ -176,6 +337,7 @@ __global__ __launch_bounds__(256) void k_dm_compact(const unsigned long long* __
   ulonglong2* d = (ulonglong2*)(ovals + 4ull * pos);
   d[0] = s[0];
   d[1] = s[1];
+  if (AUX) omiss[pos] = aux[2ull * i];
 }
 
 static uint32_t log2u(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }
@@ -204,6 +366,7 @@ class DenseMap {
     free_graveyard();
     (void)hipFree(keys_);
     (void)hipFree(vals_);
+    (void)hipFree(aux_);
     (void)hipEventDestroy(ev_last_);
     (void)hipEventDestroy(ev_snap_);
     (void)hipEventDestroy(ev_staged_);
@@ -246,40 +409,60 @@ class DenseMap {
     out[3] = offered_ - drop_range_ - drop_key_; out[4] = drop_range_; out[5] = drop_key_;
   }
 
-  // the voxels as records (axes 0: LOAM frame, 1: sensor axes), ascending key order
-  void records(std::vector<float4>& out, int axes) {
+  // the occupied slots on the host: keys, values and (carving) miss words, and idx = their ascending key order
+  struct Snapshot {
+    std::vector<unsigned long long> k, v;
+    std::vector<uint32_t> miss, idx;
+  };
+  void snapshot(Snapshot& S) {
     read_counters();
     const uint32_t slots = slots_, nblk = (slots + 255) / 256;
-    DevBuf<uint32_t> blk, scratch;
+    DevBuf<uint32_t> blk, scratch, omiss;
     DevBuf<unsigned long long> tiles, okeys, ovals;
     blk.reserve((size_t)nblk + 1);
     scratch.reserve(2);
     tiles.reserve(SCAN_SCRATCH_WORDS / 2);
     okeys.reserve(occ_ + 1);
     ovals.reserve(4 * (occ_ + 1));
+    if (aux_) omiss.reserve(occ_ + 1);
     LX_HIP(hipMemsetAsync(tiles.p, 0, sizeof(unsigned long long) * (SCAN_SCRATCH_WORDS / 2), own_));
     hipLaunchKernelGGL(k_dm_count, dim3(nblk), dim3(256), 0, own_, keys_, slots, blk.p);
     exclusive_scan_u32_n(blk.p, blk.p, (uint32_t*)tiles.p, scratch.p, nblk, own_);
-    hipLaunchKernelGGL(k_dm_compact, dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p);
+    if (aux_)
+      hipLaunchKernelGGL(k_dm_compact<true>, dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p, aux_, omiss.p);
+    else
+      hipLaunchKernelGGL(k_dm_compact<false>, dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p, nullptr, nullptr);
     LX_HIP(hipGetLastError());
-    std::vector<unsigned long long> hk(occ_), hv(4 * (size_t)occ_);
+    S.k.resize(occ_);
+    S.v.resize(4 * (size_t)occ_);
+    S.miss.assign(aux_ ? occ_ : 0, 0u);
     uint32_t total = 0;
     LX_HIP(hipMemcpyAsync(&total, blk.p + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, own_));
     if (occ_) {
-      LX_HIP(hipMemcpyAsync(hk.data(), okeys.p, sizeof(unsigned long long) * occ_, hipMemcpyDeviceToHost, own_));
-      LX_HIP(hipMemcpyAsync(hv.data(), ovals.p, sizeof(unsigned long long) * 4 * occ_, hipMemcpyDeviceToHost, own_));
+      LX_HIP(hipMemcpyAsync(S.k.data(), okeys.p, sizeof(unsigned long long) * occ_, hipMemcpyDeviceToHost, own_));
+      LX_HIP(hipMemcpyAsync(S.v.data(), ovals.p, sizeof(unsigned long long) * 4 * occ_, hipMemcpyDeviceToHost, own_));
+      if (aux_) LX_HIP(hipMemcpyAsync(S.miss.data(), omiss.p, sizeof(uint32_t) * occ_, hipMemcpyDeviceToHost, own_));
     }
     LX_HIP(hipStreamSynchronize(own_));
     scan_check_errors();
     LX_REQUIRE(total == occ_, "dense map: the compaction disagrees with the occupancy count");
-    std::vector<uint32_t> idx(occ_);
-    std::iota(idx.begin(), idx.end(), 0u);
-    std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return hk[a] < hk[b]; });
-    out.resize(occ_);
+    S.idx.resize(occ_);
+    std::iota(S.idx.begin(), S.idx.end(), 0u);
+    std::sort(S.idx.begin(), S.idx.end(), [&](uint32_t a, uint32_t b) { return S.k[a] < S.k[b]; });
+  }
+
+  // the voxels as records (axes 0: LOAM frame, 1: sensor axes), ascending key order; with a rule, without the voxels it calls dynamic
+  void records(std::vector<float4>& out, int axes, const loamx_densemap_static_rule* rule = nullptr) {
+    Snapshot S;
+    snapshot(S);
+    const std::vector<unsigned long long>&hk = S.k, &hv = S.v;
+    out.clear();
+    out.reserve(S.idx.size());
     const double leaf = (double)cfg.leaf, qs = (double)(1u << DM_QBITS);
     const unsigned long long km = (1ull << DM_KBITS) - 1ull;
-    for (size_t r = 0; r < idx.size(); r++) {
-      const uint32_t j = idx[r];
+    for (size_t r = 0; r < S.idx.size(); r++) {
+      const uint32_t j = S.idx[r];
+      if (rule && dm_dynamic(*rule, hv[4 * (size_t)j], S.miss[j])) continue;
       const unsigned long long k = hk[j];
       const double cnt = (double)hv[4 * (size_t)j];
       float v[3];
@@ -287,8 +470,58 @@ class DenseMap {
         const double ia = (double)((long long)((k >> (DM_KBITS * a)) & km) - (1ll << DM_QBITS));
         v[a] = (float)((ia + (double)hv[4 * (size_t)j + 1 + a] / (cnt * qs)) * leaf);
       }
-      out[r] = axes == 1 ? make_float4(v[2], v[0], v[1], (float)cnt) : make_float4(v[0], v[1], v[2], (float)cnt);
+      out.push_back(axes == 1 ? make_float4(v[2], v[0], v[1], (float)cnt) : make_float4(v[0], v[1], v[2], (float)cnt));
     }
+  }
+
+  // the miss word per voxel in the order of records()
+  void misses(std::vector<uint32_t>& out) {
+    Snapshot S;
+    snapshot(S);
+    out.resize(S.idx.size());
+    for (size_t r = 0; r < S.idx.size(); r++) out[r] = S.miss[S.idx[r]];
+  }
+
+  bool carving() const { return aux_ != nullptr; }
+
+  // allowed while nothing has been offered since creation / reset; the handle is unchanged when refused
+  void enable_carving(const loamx_densemap_carve_config& c) {
+    read_counters();
+    LX_REQUIRE(occ_ == 0 && offered_ == 0, "carving can only be enabled on an empty map (a fresh handle, or right after reset)");
+    if (!aux_) {
+      LX_HIP(hipMalloc((void**)&aux_, sizeof(uint32_t) * 2 * (size_t)slots_));
+      LX_HIP(hipMemsetAsync(aux_, 0, sizeof(uint32_t) * 2 * (size_t)slots_, own_));
+      LX_HIP(hipStreamSynchronize(own_));
+    }
+    carve_ = c;
+  }
+
+  // [rays traced, not traced by stride, by range, by steps or origin key, cells visited, misses recorded]
+  void carve_stats(uint64_t out[6]) {
+    read_counters();
+    for (int k = 0; k < 6; k++) out[k] = carve_ctr_[k];
+  }
+
+  // the dynamic voxels leave the table: a rehash with the rule as predicate into a fresh table of the same size
+  uint64_t prune(const loamx_densemap_static_rule& rule) {
+    read_counters();
+    const uint64_t before = occ_;
+    unsigned long long *nk = nullptr, *nv = nullptr;
+    uint32_t* na = nullptr;
+    alloc_table(slots_, nk, nv, &na);
+    LX_HIP(hipMemsetAsync(nk, 0xff, sizeof(unsigned long long) * slots_, own_));
+    LX_HIP(hipMemsetAsync(nv, 0, sizeof(unsigned long long) * 4 * slots_, own_));
+    LX_HIP(hipMemsetAsync(na, 0, sizeof(uint32_t) * 2 * (size_t)slots_, own_));
+    LX_HIP(hipMemsetAsync(ctr_.p, 0, sizeof(unsigned long long), own_));   // (the occupancy: recounted by the kernel)
+    hipLaunchKernelGGL((k_dm_rehash<true, true>), dim3((slots_ + 255) / 256), dim3(256), 0, own_, keys_, vals_, slots_, nk, nv, slots_ - 1u,
+                       64u - log2u(slots_), ctr_.p, aux_, na, rule);
+    LX_HIP(hipGetLastError());
+    retire_table();
+    keys_ = nk;
+    vals_ = nv;
+    aux_ = na;
+    read_counters();
+    return before - occ_;
   }
 
   void reset() {
@@ -298,6 +531,8 @@ class DenseMap {
     LX_HIP(hipStreamSynchronize(own_));
     occ_ = pend_ = pend_snap_ = 0;
     offered_ = drop_range_ = drop_key_ = 0;
+    for (uint64_t& c : carve_ctr_) c = 0;
+    seq_ = 0;
   }
 
   bool combine = true;   // (bench A/B: the in-wave combining of equal keys)
@@ -310,6 +545,10 @@ class DenseMap {
   bool snap_pending_ = false, staged_pending_ = false;
   unsigned long long* keys_ = nullptr;
   unsigned long long* vals_ = nullptr;
+  uint32_t* aux_ = nullptr;   // carving: miss and stamp per slot (nullptr: carving is off)
+  loamx_densemap_carve_config carve_ = {0.f, 1u, 1u, 4096u};
+  uint32_t seq_ = 0;          // sequence number of the last add call (stamp values; 0 = never stamped)
+  uint64_t carve_ctr_[6] = {0, 0, 0, 0, 0, 0};
   uint32_t slots_ = 0;
   float inv_ = 10.f;
   DevBuf<unsigned long long> ctr_;
@@ -322,13 +561,21 @@ class DenseMap {
   uint64_t occ_ = 0, pend_ = 0, pend_snap_ = 0;
   uint64_t offered_ = 0, drop_range_ = 0, drop_key_ = 0;
 
-  void alloc_table(uint64_t slots, unsigned long long*& k, unsigned long long*& v) {
+  void alloc_table(uint64_t slots, unsigned long long*& k, unsigned long long*& v, uint32_t** aux = nullptr) {
     LX_HIP(hipMalloc((void**)&k, sizeof(unsigned long long) * slots));
     LX_HIP(hipMalloc((void**)&v, sizeof(unsigned long long) * 4 * slots));
+    if (aux) LX_HIP(hipMalloc((void**)aux, sizeof(uint32_t) * 2 * slots));
+  }
+  // the current table (and its auxiliary words) to the graveyard
+  void retire_table() {
+    graveyard_.push_back(keys_);
+    graveyard_.push_back(vals_);
+    if (aux_) graveyard_.push_back(aux_);
   }
   void clear(hipStream_t st) {
     LX_HIP(hipMemsetAsync(keys_, 0xff, sizeof(unsigned long long) * slots_, st));
     LX_HIP(hipMemsetAsync(vals_, 0, sizeof(unsigned long long) * 4 * slots_, st));
+    if (aux_) LX_HIP(hipMemsetAsync(aux_, 0, sizeof(uint32_t) * 2 * (size_t)slots_, st));
     LX_HIP(hipMemsetAsync(ctr_.p, 0, sizeof(unsigned long long) * DM_CTR_WORDS, st));
   }
   void free_graveyard() {
@@ -354,6 +601,7 @@ class DenseMap {
     const unsigned long long* c = (const unsigned long long*)h_ctr_.p;
     LX_REQUIRE(c[3] == 0ull, "dense map: hash table overflow");
     occ_ = c[0]; drop_range_ = c[1]; drop_key_ = c[2];
+    for (int k = 0; k < 6; k++) carve_ctr_[k] = c[4 + k];
     pend_ = pend_snap_ = 0;
   }
   // the occupancy snapshot that has landed, if any
@@ -381,15 +629,24 @@ class DenseMap {
     LX_REQUIRE(want <= (1ull << 31), "dense map: more voxels than the table can index");
     if (want != slots_) {
       unsigned long long *nk = nullptr, *nv = nullptr;
-      alloc_table(want, nk, nv);
+      uint32_t* na = nullptr;
+      alloc_table(want, nk, nv, aux_ ? &na : nullptr);
       LX_HIP(hipMemsetAsync(nk, 0xff, sizeof(unsigned long long) * want, st));
       LX_HIP(hipMemsetAsync(nv, 0, sizeof(unsigned long long) * 4 * want, st));   // (slots claimed later accumulate from zero)
       const uint32_t sh = 64u - log2u(want);
-      hipLaunchKernelGGL(k_dm_rehash, dim3((slots_ + 255) / 256), dim3(256), 0, st, keys_, vals_, slots_, nk, nv, (uint32_t)(want - 1), sh, ctr_.p);
-      graveyard_.push_back(keys_);
-      graveyard_.push_back(vals_);
+      const loamx_densemap_static_rule none = {0u, 0u, 0u};
+      if (aux_) {
+        LX_HIP(hipMemsetAsync(na, 0, sizeof(uint32_t) * 2 * want, st));
+        hipLaunchKernelGGL((k_dm_rehash<true, false>), dim3((slots_ + 255) / 256), dim3(256), 0, st, keys_, vals_, slots_, nk, nv,
+                           (uint32_t)(want - 1), sh, ctr_.p, aux_, na, none);
+      } else {
+        hipLaunchKernelGGL((k_dm_rehash<false, false>), dim3((slots_ + 255) / 256), dim3(256), 0, st, keys_, vals_, slots_, nk, nv,
+                           (uint32_t)(want - 1), sh, ctr_.p, nullptr, nullptr, none);
+      }
+      retire_table();
       keys_ = nk;
       vals_ = nv;
+      aux_ = na;
       slots_ = (uint32_t)want;
       rehashes++;
     }
@@ -401,10 +658,26 @@ class DenseMap {
       F.use_max = cfg.max_range > 0.f ? 1 : 0;
       F.ox = origin[0]; F.oy = origin[1]; F.oz = origin[2];
       const uint32_t sh = 64u - log2u(slots_);
-      if (combine)
-        hipLaunchKernelGGL(k_dm_insert<true>, dim3((n + 255) / 256), dim3(256), 0, st, pts, n, F, keys_, vals_, slots_ - 1u, sh, ctr_.p);
-      else
-        hipLaunchKernelGGL(k_dm_insert<false>, dim3((n + 255) / 256), dim3(256), 0, st, pts, n, F, keys_, vals_, slots_ - 1u, sh, ctr_.p);
+      const dim3 grid((n + 255) / 256), block(256);
+      if (!aux_) {
+        if (combine)
+          hipLaunchKernelGGL((k_dm_insert<true, false>), grid, block, 0, st, pts, n, F, keys_, vals_, slots_ - 1u, sh, ctr_.p, nullptr, 0u);
+        else
+          hipLaunchKernelGGL((k_dm_insert<false, false>), grid, block, 0, st, pts, n, F, keys_, vals_, slots_ - 1u, sh, ctr_.p, nullptr, 0u);
+      } else {
+        // carving: the insert stamps its voxels with the call's sequence number, and the rays are traced behind it
+        seq_++;
+        if (combine)
+          hipLaunchKernelGGL((k_dm_insert<true, true>), grid, block, 0, st, pts, n, F, keys_, vals_, slots_ - 1u, sh, ctr_.p, aux_, seq_);
+        else
+          hipLaunchKernelGGL((k_dm_insert<false, true>), grid, block, 0, st, pts, n, F, keys_, vals_, slots_ - 1u, sh, ctr_.p, aux_, seq_);
+        DmCarve R;
+        R.max2 = carve_.max_range * carve_.max_range;
+        R.use_max = carve_.max_range > 0.f ? 1 : 0;
+        R.stride = carve_.ray_stride; R.end_margin = carve_.end_margin; R.max_steps = carve_.max_steps; R.seq = seq_;
+        const uint64_t span = 256ull * R.stride;
+        hipLaunchKernelGGL(k_dm_carve, dim3((uint32_t)((n + span - 1) / span)), block, 0, st, pts, n, F, R, keys_, aux_, slots_ - 1u, sh, ctr_.p);
+      }
     }
     LX_HIP(hipGetLastError());
     offered_ += n;
@@ -535,6 +808,106 @@ int loamx_write_pcd(const char* path, const loamx_cloud* c, int axes) {
     if (axes == 1)
       for (float4& r : rec) r = make_float4(r.z, r.x, r.y, r.w);
     write_pcd_records(path, rec.data(), rec.size());
+    return LOAMX_OK;
+  });
+}
+
+void loamx_densemap_carve_default_config(loamx_densemap_carve_config* cfg) {
+  if (!cfg) return;
+  memset(cfg, 0, sizeof(*cfg));
+  cfg->max_range = 0.f;
+  cfg->ray_stride = 1u;
+  cfg->end_margin = 1u;
+  cfg->max_steps = 4096u;
+}
+void loamx_densemap_static_rule_default(loamx_densemap_static_rule* rule) {
+  if (!rule) return;
+  rule->min_misses = 3u;
+  rule->num = 1u;
+  rule->den = 1u;
+}
+int loamx_densemap_rule_is_dynamic(const loamx_densemap_static_rule* rule, uint64_t n, uint32_t miss) {
+  return guard([&]() {
+    LX_REQUIRE(rule, "NULL argument");
+    LX_REQUIRE(rule->den != 0u, "the rule's den must not be 0");
+    return dm_dynamic(*rule, n, miss) ? 1 : 0;
+  });
+}
+
+// the rule of a call, checked (NULL: the default rule)
+static loamx_densemap_static_rule checked_rule(const loamx_densemap_static_rule* rule) {
+  loamx_densemap_static_rule r;
+  if (rule) r = *rule; else loamx_densemap_static_rule_default(&r);
+  LX_REQUIRE(r.den != 0u, "the rule's den must not be 0");
+  return r;
+}
+#define LX_REQUIRE_CARVING(h) LX_REQUIRE((h)->d.carving(), "carving is not enabled")
+
+int loamx_densemap_enable_carving(loamx_densemap* h, const loamx_densemap_carve_config* cfg) {
+  return guard([&]() {
+    LX_REQUIRE(h, "NULL handle");
+    loamx_densemap_carve_config c;
+    if (cfg) c = *cfg; else loamx_densemap_carve_default_config(&c);
+    LX_REQUIRE(c.max_range >= 0.f && std::isfinite(c.max_range), "max_range must be >= 0");
+    LX_REQUIRE(c.ray_stride >= 1u, "ray_stride must be >= 1");
+    LX_REQUIRE(c.max_steps >= 1u && c.max_steps <= 65536u, "max_steps must be in [1, 65536]");
+    h->d.enable_carving(c);
+    return LOAMX_OK;
+  });
+}
+int loamx_densemap_get_carve_stats(loamx_densemap* h, uint64_t stats[6]) {
+  return guard([&]() {
+    LX_REQUIRE(h && stats, "NULL argument");
+    LX_REQUIRE_CARVING(h);
+    h->d.carve_stats(stats);
+    return LOAMX_OK;
+  });
+}
+int loamx_densemap_download_misses(loamx_densemap* h, uint32_t* out, uint64_t capacity, uint64_t* n) {
+  return guard([&]() {
+    LX_REQUIRE(h && n && (out || !capacity), "NULL argument");
+    LX_REQUIRE_CARVING(h);
+    std::vector<uint32_t> m;
+    h->d.misses(m);
+    *n = m.size();
+    if (m.size() > capacity) return LOAMX_E_CAPACITY;
+    if (!m.empty()) memcpy(out, m.data(), sizeof(uint32_t) * m.size());
+    return LOAMX_OK;
+  });
+}
+int loamx_densemap_download_static(loamx_densemap* h, loamx_cloud* out, int axes, const loamx_densemap_static_rule* rule) {
+  return guard([&]() {
+    LX_REQUIRE(h && out, "NULL argument");
+    LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+    const loamx_densemap_static_rule r = checked_rule(rule);
+    LX_REQUIRE_CARVING(h);
+    check_cloud(out, false);
+    std::vector<float4> rec;
+    h->d.records(rec, axes, &r);
+    if (rec.size() > out->count) { out->count = (uint32_t)rec.size(); return LOAMX_E_CAPACITY; }
+    return unpack_cloud(rec.data(), (uint32_t)rec.size(), out);
+  });
+}
+int loamx_densemap_save_pcd_static(loamx_densemap* h, const char* path, int axes, const loamx_densemap_static_rule* rule) {
+  return guard([&]() {
+    LX_REQUIRE(h && path, "NULL argument");
+    LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+    const loamx_densemap_static_rule r = checked_rule(rule);
+    LX_REQUIRE_CARVING(h);
+    std::vector<float4> rec;
+    h->d.records(rec, axes, &r);
+    write_pcd_records(path, rec.data(), rec.size());
+    return LOAMX_OK;
+  });
+}
+int loamx_densemap_prune(loamx_densemap* h, const loamx_densemap_static_rule* rule, uint64_t* removed) {
+  return guard([&]() {
+    LX_REQUIRE(h, "NULL handle");
+    const loamx_densemap_static_rule r = checked_rule(rule);
+    LX_REQUIRE_CARVING(h);
+    LX_HIP(hipSetDevice(h->d.cfg.device));
+    const uint64_t gone = h->d.prune(r);
+    if (removed) *removed = gone;
     return LOAMX_OK;
   });
 }

@@ -970,6 +970,27 @@ class DenseMapConfig(C.Structure):
                 ("initial_slots", C.c_uint32), ("device", C.c_int)]
 
 
+class DenseMapCarveConfig(C.Structure):
+    _fields_ = [("max_range", C.c_float), ("ray_stride", C.c_uint32), ("end_margin", C.c_uint32), ("max_steps", C.c_uint32)]
+
+
+class StaticRule(C.Structure):
+    """loamx_densemap_static_rule: a voxel is dynamic iff miss >= min_misses and miss * den > n * num.  StaticRule() is the default
+    rule (3, 1, 1)."""
+    _fields_ = [("min_misses", C.c_uint32), ("num", C.c_uint32), ("den", C.c_uint32)]
+
+    def __init__(self, min_misses=None, num=None, den=None):
+        super().__init__()
+        lib().loamx_densemap_static_rule_default(C.byref(self))
+        for k, v in (("min_misses", min_misses), ("num", num), ("den", den)):
+            if v is not None:
+                setattr(self, k, v)
+
+    def is_dynamic(self, n: int, miss: int) -> bool:
+        """the rule on one voxel (host only)"""
+        return bool(_check(lib().loamx_densemap_rule_is_dynamic(C.byref(self), C.c_uint64(n), C.c_uint32(miss))))
+
+
 _AXES = {"loam": 0, "sensor": 1}
 
 
@@ -1033,22 +1054,60 @@ class DenseMap:
     def __len__(self):
         return self.stats()["voxels"]
 
-    def points(self, axes="loam"):
-        """(n, 4) float32: one record per voxel in ascending key order — the mean position, intensity = the voxel's point count"""
+    def points(self, axes="loam", static=None):
+        """(n, 4) float32: one record per voxel in ascending key order — the mean position, intensity = the voxel's point count.
+        static (a StaticRule; needs carving): without the voxels the rule calls dynamic"""
         n = len(self)
         while True:
             out = np.zeros((max(n, 1), 4), np.float32)
             c = cloud_of(out)
             c.count = n
-            rc = lib().loamx_densemap_download(self.h, C.byref(c), _axes(axes))
+            if static is None:
+                rc = lib().loamx_densemap_download(self.h, C.byref(c), _axes(axes))
+            else:
+                rc = lib().loamx_densemap_download_static(self.h, C.byref(c), _axes(axes), C.byref(static))
             if rc == E_CAPACITY:
                 n = int(c.count)
                 continue
             _check(rc)
             return out[:c.count]
 
-    def save_pcd(self, path: str, axes="loam"):
-        _check(lib().loamx_densemap_save_pcd(self.h, os.fsencode(path), _axes(axes)))
+    def save_pcd(self, path: str, axes="loam", static=None):
+        if static is None:
+            _check(lib().loamx_densemap_save_pcd(self.h, os.fsencode(path), _axes(axes)))
+        else:
+            _check(lib().loamx_densemap_save_pcd_static(self.h, os.fsencode(path), _axes(axes), C.byref(static)))
+
+    def enable_carving(self, max_range=0.0, ray_stride=1, end_margin=1, max_steps=4096):
+        """free-space carving (include/loamx.h): from now on every add also traces its rays from the origin and counts, per voxel, the
+        rays that crossed it.  Only on an empty map (fresh, or right after reset); ray_stride is the cost knob."""
+        c = _cfg(DenseMapCarveConfig, "loamx_densemap_carve_default_config", max_range=max_range, ray_stride=ray_stride,
+                 end_margin=end_margin, max_steps=max_steps)
+        _check(lib().loamx_densemap_enable_carving(self.h, C.byref(c)))
+
+    def carve_stats(self):
+        s = (C.c_uint64 * 6)()
+        _check(lib().loamx_densemap_get_carve_stats(self.h, s))
+        keys = ("traced", "skipped_stride", "skipped_range", "skipped_steps", "cells_visited", "misses")
+        return dict(zip(keys, (int(v) for v in s)))
+
+    def misses(self):
+        """(n,) uint32: the miss count per voxel, in the order of points()"""
+        n = C.c_uint64(len(self))
+        while True:
+            out = np.zeros(max(int(n.value), 1), np.uint32)
+            rc = lib().loamx_densemap_download_misses(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(int(n.value)), C.byref(n))
+            if rc == E_CAPACITY:
+                continue
+            _check(rc)
+            return out[:int(n.value)]
+
+    def prune(self, rule=None) -> int:
+        """remove the voxels the rule (default: StaticRule()) calls dynamic from the table; returns how many left"""
+        rule = StaticRule() if rule is None else rule
+        removed = C.c_uint64(0)
+        _check(lib().loamx_densemap_prune(self.h, C.byref(rule), C.byref(removed)))
+        return int(removed.value)
 
     def reset(self):
         _check(lib().loamx_densemap_reset(self.h))
