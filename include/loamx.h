@@ -726,6 +726,57 @@ int loamx_densemap_save_pcd_static(loamx_densemap* h, const char* path, int axes
 /* removed (may be NULL): the number of voxels that left */
 int loamx_densemap_prune(loamx_densemap* h, const loamx_densemap_static_rule* rule, uint64_t* removed);
 
+/* Second moments and surfels (optional, off by default: a handle that never enables it behaves, allocates and exports as described
+ * above).  With the sums of the products of the offsets beside the sums of the offsets, a voxel holds a mean, a covariance and a
+ * normal: the map becomes a surfel / normal-distribution map, from the points it held on the device when they were inserted.
+ *
+ * loamx_densemap_enable_moments is allowed only on an empty map (a fresh handle, or right after reset; otherwise LOAMX_E_INVALID
+ * and the handle is unchanged).  It allocates nine uint64_t words per slot beside the table (72 bytes per slot) and stays on until
+ * the handle is destroyed; reset clears the words.  It is independent of carving: either, both or neither, enabled in either order.
+ * Per point that an add inserts (add, add_from_map, add_from_pipeline alike; the same filters and the same q_x, q_y, q_z as above),
+ * nine integers are added to the words of its voxel, in this order:
+ *   Mxx += q_x*q_x, Myy, Mzz, Mxy += q_x*q_y, Mxz, Myz:  each product is an exact integer below 2^40; the sums are unsigned, modulo
+ *     2^64, and exact while the voxel holds fewer than 2^24 points.
+ *   Vx, Vy, Vz:  with d = p - origin per component in f32 (the d of the range filter),
+ *     w_a = (int32_t)fminf(fmaxf(d_a * 1024.0f, -2^30), 2^30) (the conversion truncates toward zero), V_a += w_a as a signed 64-bit
+ *     sum (two's complement in the word).  V points from the sensor positions to the voxel's points.
+ * All nine are integer sums: like n, Sx, Sy, Sz they depend neither on the thread schedule, nor on the order of the points, nor on
+ * how the points are split into calls.  prune and the table's growth carry them.
+ * The surfel of a voxel is computed on the host, in double, when it is exported:
+ *   N_ab = n*M_ab - S_a*S_b as an exact (128-bit) integer, converted to double once;  C_ab = N_ab / ((double)n * (double)n), the
+ *   covariance of the offsets in units of (leaf / 2^20)^2;  l0 <= l1 <= l2 the eigenvalues of the symmetric 3x3 C (cyclic Jacobi).
+ *   normal = the unit eigenvector of l0, with the sign that makes normal . V <= 0 (it faces the sensors; the dot product in double);
+ *   when that dot product is exactly 0, the sign that makes its first non-zero component positive.
+ *   curvature = l0 / (l0 + l1 + l2).
+ *   A voxel has a surfel iff n >= min_points, the exact integer Nxx + Nyy + Nzz > 0, and l1 >= min_planar_ratio * l2 (the ratio
+ *   widened to double).  Otherwise its normal is (0, 0, 0) and its curvature 0.
+ *   x, y, z, intensity are the bytes loamx_densemap_download gives; with axes 1 the normal is permuted like the position.
+ * With moments off every function below except enable_moments and the two host-only helpers answers LOAMX_E_INVALID. */
+typedef struct loamx_surfel {
+  float x, y, z, intensity, normal_x, normal_y, normal_z, curvature;   /* the order of pcl::PointXYZINormal's fields */
+} loamx_surfel;
+typedef struct loamx_densemap_surfel_config {
+  uint32_t min_points;     /* voxels with fewer points have no surfel, >= 3 (default 5) */
+  float min_planar_ratio;  /* >= 0 (default 0.01): below l1 / l2 of it the points form a line */
+} loamx_densemap_surfel_config;
+void loamx_densemap_surfel_default_config(loamx_densemap_surfel_config* cfg);   /* host only */
+/* host only, no device: the surfel of one voxel from its integer words.  idx = the voxel indices ix, iy, iz; vals = n, Sx, Sy, Sz;
+ * mom = the nine words in the order above; cfg NULL: the defaults.  LOAMX_E_INVALID: a NULL argument, leaf <= 0, n == 0,
+ * min_points < 3, a negative (or NaN) ratio, axes not 0 / 1 */
+int loamx_densemap_surfel_of(float leaf, const int32_t idx[3], const uint64_t vals[4], const uint64_t mom[9],
+                             const loamx_densemap_surfel_config* cfg, int axes, loamx_surfel* out);
+int loamx_densemap_enable_moments(loamx_densemap* h);
+/* nine words per voxel in the record order of loamx_densemap_download; *n = voxels (LOAMX_E_CAPACITY, nothing written, when
+ * capacity < *n; capacity counts voxels) */
+int loamx_densemap_download_moments(loamx_densemap* h, uint64_t* out, uint64_t capacity, uint64_t* n);
+/* one surfel per voxel in the record order; capacity / *n as above.  rule NULL: every voxel; a rule requires carving and leaves
+ * out the voxels it calls dynamic, as download_static does.  cfg NULL: the defaults */
+int loamx_densemap_download_surfels(loamx_densemap* h, loamx_surfel* out, uint64_t capacity, uint64_t* n, int axes,
+                                    const loamx_densemap_surfel_config* cfg, const loamx_densemap_static_rule* rule);
+/* binary PCD v0.7, fields x y z intensity normal_x normal_y normal_z curvature (F 4) */
+int loamx_densemap_save_pcd_surfels(loamx_densemap* h, const char* path, int axes, const loamx_densemap_surfel_config* cfg,
+                                    const loamx_densemap_static_rule* rule);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Place recognition (not in the reference): a database of rotation-invariant sweep descriptors in device memory (Scan Context: a
  * ring x sector polar grid of maximum heights around the sensor) and an exhaustive search for the earlier entries that look like a

@@ -8,7 +8,12 @@
 // Carving (loamx_densemap_enable_carving): two more 32-bit words per slot, miss and stamp.  The insert stamps the voxels of its call; a
 // second kernel behind it walks each sweep ray from the origin towards its point through the voxel grid and counts a miss in every
 // voxel of the table it crosses that the same call did not hit.  The walk only looks keys up: it never claims a slot.
+//
+// Moments (loamx_densemap_enable_moments): nine more 64-bit words per slot in an array of their own, the sums of the products of the
+// offsets and of the fixed-point vectors from the origin.  The insert adds them with the voxel's other sums; the surfel of a voxel
+// (covariance, normal, curvature) is computed on the host at export.
 #include "densemap.hpp"
+#include "host_math.h"
 #include "pinned_copy.hpp"
 #include "scan.hpp"
 #include <algorithm>
@@ -34,6 +39,9 @@ struct DmCarve {
   uint32_t stride, end_margin, max_steps, seq;
 };
 // aux: 2 words per slot beside the table, [2 * slot] miss, [2 * slot + 1] stamp
+// mom: 9 words per slot beside the table, [9 * slot + k]: Mxx, Myy, Mzz, Mxy, Mxz, Myz, Vx, Vy, Vz (include/loamx.h)
+constexpr int DM_MOM_WORDS = 9;
+constexpr int DM_VBITS = 26;   // the combine packs a lane's w_a above its q_a: 64 lanes' q sum stays below 2^26
 
 __device__ inline unsigned long long dm_hash(unsigned long long key, uint32_t shift) {
   return (key * 0x9E3779B97F4A7C15ull) >> shift;
@@ -91,16 +99,22 @@ __device__ inline bool dm_added(const float4 p, const DmFilter& F, float& d2) {
 
 // one point per thread.  vals: 4 words per slot (n, Sx, Sy, Sz).  COMBINE: equal keys of a wave are summed in LDS first, and one lane
 // per distinct key touches the table (the sweep is in firing order: neighbouring lanes share voxels).  STAMP (carving): that lane also
-// stores the call's sequence number into the slot's stamp word (every writer of a call stores the same value)
-template <bool COMBINE, bool STAMP>
+// stores the call's sequence number into the slot's stamp word (every writer of a call stores the same value).  MOMENTS: the nine sums
+// of mom ride along.  Their combine runs in 64-bit LDS words, one atomic per word and lane: six for the products (64 x 2^40 does not
+// fit 32 bits) and three that carry w_a * 2^26 + q_a, the signed viewpoint term above the offset (|64 x 2^30 x 2^26| < 2^63, and the
+// low field, a sum of non-negative terms below 2^26, never borrows from the high one).  9 x 64 x 8 B per wave, 18 KiB per block: eight
+// blocks of 256 threads still fit a CU's LDS, and the 32-bit accumulators are not allocated in that instantiation.  Word-major layout:
+// the lanes of one instruction go to consecutive 8-byte words unless they share a leader
+template <bool COMBINE, bool STAMP, bool MOMENTS>
 __global__ __launch_bounds__(256) void k_dm_insert(const float4* __restrict__ pts, uint32_t n, DmFilter F, unsigned long long* __restrict__ keys,
                                                    unsigned long long* __restrict__ vals, uint32_t mask, uint32_t shift,
-                                                   unsigned long long* __restrict__ ctr, uint32_t* __restrict__ aux, uint32_t seq) {
-  __shared__ uint32_t acc[4][64][3];
+                                                   unsigned long long* __restrict__ ctr, uint32_t* __restrict__ aux, uint32_t seq,
+                                                   unsigned long long* __restrict__ mom) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
   unsigned long long key = DM_EMPTY;
   uint32_t q[3] = {0u, 0u, 0u};
+  int w[3] = {0, 0, 0};   // (MOMENTS) the fixed-point vector from the origin
   bool drop_range = false, drop_key = false;
   if (i < n) {
     const float4 p = pts[i];
@@ -123,6 +137,11 @@ __global__ __launch_bounds__(256) void k_dm_insert(const float4* __restrict__ pt
         k |= (unsigned long long)ia << (DM_KBITS * a);
       }
       if (!drop_key) key = k;
+      if (MOMENTS) {
+        const float d[3] = {dx, dy, dz};
+#pragma unroll
+        for (int a = 0; a < 3; a++) w[a] = (int)fminf(fmaxf(d[a] * 1024.0f, -1073741824.0f), 1073741824.0f);
+      }
     }
   }
   dm_wave_count(&ctr[1], drop_range);
@@ -130,6 +149,14 @@ __global__ __launch_bounds__(256) void k_dm_insert(const float4* __restrict__ pt
   const bool valid = key != DM_EMPTY;
   uint32_t cnt = valid ? 1u : 0u;
   bool owner = valid;
+  unsigned long long ms[DM_MOM_WORDS] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};   // (constant indices only: registers)
+  if (MOMENTS) {
+    const unsigned long long qx = q[0], qy = q[1], qz = q[2];
+    ms[0] = qx * qx; ms[1] = qy * qy; ms[2] = qz * qz;
+    ms[3] = qx * qy; ms[4] = qx * qz; ms[5] = qy * qz;
+#pragma unroll
+    for (int a = 0; a < 3; a++) ms[6 + a] = (unsigned long long)(long long)w[a];
+  }
   if (COMBINE) {
     // group the lanes by key: the lowest lane of each group (its leader) collects the group's count and sums
     int leader = -1;
@@ -146,15 +173,43 @@ __global__ __launch_bounds__(256) void k_dm_insert(const float4* __restrict__ pt
       todo &= ~m;
     }
     owner = valid && leader == lane;
-    if (owner) { acc[wid][lane][0] = 0u; acc[wid][lane][1] = 0u; acc[wid][lane][2] = 0u; }
-    __syncthreads();
-    if (valid) {   // (integer adds: the order does not matter; <= 64 x 2^20 fits 32 bits)
-      atomicAdd(&acc[wid][leader][0], q[0]);
-      atomicAdd(&acc[wid][leader][1], q[1]);
-      atomicAdd(&acc[wid][leader][2], q[2]);
+    if constexpr (MOMENTS) {
+      __shared__ unsigned long long macc[4][DM_MOM_WORDS][64];
+      if (owner) {
+#pragma unroll
+        for (int k = 0; k < DM_MOM_WORDS; k++) macc[wid][k][lane] = 0ull;
+      }
+      __syncthreads();
+      if (valid) {   // (integer adds modulo 2^64: the order does not matter)
+#pragma unroll
+        for (int k = 0; k < 6; k++) atomicAdd(&macc[wid][k][leader], ms[k]);
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+          atomicAdd(&macc[wid][6 + a][leader], (unsigned long long)((long long)w[a] * (1ll << DM_VBITS) + (long long)q[a]));
+      }
+      __syncthreads();
+      if (owner) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) ms[k] = macc[wid][k][lane];
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+          const unsigned long long pk = macc[wid][6 + a][lane];
+          q[a] = (uint32_t)(pk & ((1ull << DM_VBITS) - 1ull));
+          ms[6 + a] = (unsigned long long)((long long)pk >> DM_VBITS);   // (arithmetic shift: floor, and the low field is >= 0)
+        }
+      }
+    } else {
+      __shared__ uint32_t acc[4][64][3];
+      if (owner) { acc[wid][lane][0] = 0u; acc[wid][lane][1] = 0u; acc[wid][lane][2] = 0u; }
+      __syncthreads();
+      if (valid) {   // (integer adds: the order does not matter; <= 64 x 2^20 fits 32 bits)
+        atomicAdd(&acc[wid][leader][0], q[0]);
+        atomicAdd(&acc[wid][leader][1], q[1]);
+        atomicAdd(&acc[wid][leader][2], q[2]);
+      }
+      __syncthreads();
+      if (owner) { q[0] = acc[wid][lane][0]; q[1] = acc[wid][lane][1]; q[2] = acc[wid][lane][2]; }
     }
-    __syncthreads();
-    if (owner) { q[0] = acc[wid][lane][0]; q[1] = acc[wid][lane][1]; q[2] = acc[wid][lane][2]; }
   }
   uint32_t slot = 0;
   bool won = false, ok = true;
@@ -168,6 +223,11 @@ __global__ __launch_bounds__(256) void k_dm_insert(const float4* __restrict__ pt
     atomicAdd(&v[2], (unsigned long long)q[1]);
     atomicAdd(&v[3], (unsigned long long)q[2]);
     if (STAMP) __hip_atomic_store(&aux[2ull * slot + 1], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (MOMENTS) {
+      unsigned long long* mm = mom + (unsigned long long)DM_MOM_WORDS * slot;
+#pragma unroll
+      for (int k = 0; k < DM_MOM_WORDS; k++) atomicAdd(&mm[k], ms[k]);   // (results unused: no-return atomics)
+    }
   }
 }
 
@@ -279,12 +339,13 @@ __host__ __device__ inline bool dm_dynamic(const loamx_densemap_static_rule& r, 
 
 // every occupied slot of the old table into the new one (keys are unique: claim the first empty slot of the probe sequence).  AUX: the
 // slot's miss and stamp words travel with it.  PRUNE (with AUX): the voxels the rule calls dynamic stay behind, and the survivors are
-// counted into ctr[0] (zeroed before the launch)
-template <bool AUX, bool PRUNE>
+// counted into ctr[0] (zeroed before the launch).  MOM: the slot's nine moment words travel with it
+template <bool AUX, bool PRUNE, bool MOM>
 __global__ __launch_bounds__(256) void k_dm_rehash(const unsigned long long* __restrict__ okeys, const unsigned long long* __restrict__ ovals,
                                                    uint32_t on, unsigned long long* __restrict__ keys, unsigned long long* __restrict__ vals,
                                                    uint32_t mask, uint32_t shift, unsigned long long* __restrict__ ctr,
-                                                   const uint32_t* __restrict__ oaux, uint32_t* __restrict__ aux, loamx_densemap_static_rule rule) {
+                                                   const uint32_t* __restrict__ oaux, uint32_t* __restrict__ aux, loamx_densemap_static_rule rule,
+                                                   const unsigned long long* __restrict__ omom, unsigned long long* __restrict__ mom) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const unsigned long long key = i < on ? okeys[i] : DM_EMPTY;
   bool live = key != DM_EMPTY;
@@ -298,6 +359,12 @@ __global__ __launch_bounds__(256) void k_dm_rehash(const unsigned long long* __r
       d[0] = s[0];
       d[1] = s[1];
       if (AUX) *(uint2*)(aux + 2ull * slot) = *(const uint2*)(oaux + 2ull * i);
+      if (MOM) {
+        const unsigned long long* ms = omom + (unsigned long long)DM_MOM_WORDS * i;
+        unsigned long long* md = mom + (unsigned long long)DM_MOM_WORDS * slot;
+#pragma unroll
+        for (int k = 0; k < DM_MOM_WORDS; k++) md[k] = ms[k];
+      }
     } else {
       ctr[3] = 1ull;
     }
@@ -316,12 +383,13 @@ __global__ __launch_bounds__(256) void k_dm_count(const unsigned long long* __re
   if (threadIdx.x == 0) blk[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
 }
 
-// (AUX: the slot's miss word too)
-template <bool AUX>
+// (AUX: the slot's miss word too; MOM: its nine moment words)
+template <bool AUX, bool MOM>
 __global__ __launch_bounds__(256) void k_dm_compact(const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ vals,
                                                     uint32_t slots, const uint32_t* __restrict__ blk_off, unsigned long long* __restrict__ okeys,
                                                     unsigned long long* __restrict__ ovals, const uint32_t* __restrict__ aux,
-                                                    uint32_t* __restrict__ omiss) {
+                                                    uint32_t* __restrict__ omiss, const unsigned long long* __restrict__ mom,
+                                                    unsigned long long* __restrict__ omom) {
   __shared__ uint32_t wc[4];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
@@ -338,9 +406,62 @@ __global__ __launch_bounds__(256) void k_dm_compact(const unsigned long long* __
   d[0] = s[0];
   d[1] = s[1];
   if (AUX) omiss[pos] = aux[2ull * i];
+  if (MOM) {
+    const unsigned long long* ms = mom + (unsigned long long)DM_MOM_WORDS * i;
+    unsigned long long* md = omom + (unsigned long long)DM_MOM_WORDS * pos;
+#pragma unroll
+    for (int k = 0; k < DM_MOM_WORDS; k++) md[k] = ms[k];
+  }
 }
 
 static uint32_t log2u(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }
+
+// the exported position of a voxel (include/loamx.h): its indices and its words n, Sx, Sy, Sz; f64 arithmetic, one f32 rounding
+static void dm_position(double leaf, const long long ia[3], const unsigned long long* v4, float out[3]) {
+  const double cnt = (double)v4[0], qs = (double)(1u << DM_QBITS);
+  for (int a = 0; a < 3; a++) out[a] = (float)(((double)ia[a] + (double)v4[1 + a] / (cnt * qs)) * leaf);
+}
+
+// the surfel of a voxel (include/loamx.h): the scatter n*M_ab - S_a*S_b as an exact integer, the rest in double
+static void dm_surfel(double leaf, const long long ia[3], const unsigned long long* v4, const unsigned long long* m9,
+                      const loamx_densemap_surfel_config& c, int axes, loamx_surfel& out) {
+  typedef __int128 i128;
+  float p[3];
+  dm_position(leaf, ia, v4, p);
+  double nrm[3] = {0.0, 0.0, 0.0}, curv = 0.0;
+  const unsigned long long n = v4[0];
+  static const int A[6] = {0, 1, 2, 0, 0, 1}, B[6] = {0, 1, 2, 1, 2, 2};   // Mxx, Myy, Mzz, Mxy, Mxz, Myz
+  i128 N[6];
+  for (int k = 0; k < 6; k++) N[k] = (i128)n * (i128)m9[k] - (i128)v4[1 + A[k]] * (i128)v4[1 + B[k]];
+  if (n >= c.min_points && N[0] + N[1] + N[2] > 0) {
+    const double nn = (double)n * (double)n;
+    double a[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, w[3], v[3][3];
+    for (int k = 0; k < 6; k++) a[A[k]][B[k]] = a[B[k]][A[k]] = (double)N[k] / nn;
+    jacobi_eig3(a, w, v);
+    if (w[1] >= (double)c.min_planar_ratio * w[2]) {
+      const double e[3] = {v[0][0], v[1][0], v[2][0]};
+      const double dot = (e[0] * (double)(long long)m9[6] + e[1] * (double)(long long)m9[7]) + e[2] * (double)(long long)m9[8];
+      bool flip = dot > 0.0;
+      if (dot == 0.0) {
+        const double first = e[0] != 0.0 ? e[0] : (e[1] != 0.0 ? e[1] : e[2]);
+        flip = first < 0.0;
+      }
+      for (int k = 0; k < 3; k++) nrm[k] = (flip ? -e[k] : e[k]) + 0.0;   // (+ 0.0: no negative zero in the output)
+      curv = w[0] / ((w[0] + w[1]) + w[2]);
+    }
+  }
+  const int o[3] = {axes == 1 ? 2 : 0, axes == 1 ? 0 : 1, axes == 1 ? 1 : 2};   // (sensor axes: x_s = z, y_s = x, z_s = y)
+  out.x = p[o[0]]; out.y = p[o[1]]; out.z = p[o[2]];
+  out.intensity = (float)(double)n;
+  out.normal_x = (float)nrm[o[0]]; out.normal_y = (float)nrm[o[1]]; out.normal_z = (float)nrm[o[2]];
+  out.curvature = (float)curv;
+}
+
+// the indices of a key
+static void dm_key_indices(unsigned long long k, long long ia[3]) {
+  const unsigned long long km = (1ull << DM_KBITS) - 1ull;
+  for (int a = 0; a < 3; a++) ia[a] = (long long)((k >> (DM_KBITS * a)) & km) - (1ll << DM_QBITS);
+}
 
 class DenseMap {
  public:
@@ -367,6 +488,7 @@ class DenseMap {
     (void)hipFree(keys_);
     (void)hipFree(vals_);
     (void)hipFree(aux_);
+    (void)hipFree(mom_);
     (void)hipEventDestroy(ev_last_);
     (void)hipEventDestroy(ev_snap_);
     (void)hipEventDestroy(ev_staged_);
@@ -409,39 +531,54 @@ class DenseMap {
     out[3] = offered_ - drop_range_ - drop_key_; out[4] = drop_range_; out[5] = drop_key_;
   }
 
-  // the occupied slots on the host: keys, values and (carving) miss words, and idx = their ascending key order
+  // the occupied slots on the host: keys, values, (carving) miss words and (on request, moments) the nine moment words, and idx =
+  // their ascending key order
   struct Snapshot {
-    std::vector<unsigned long long> k, v;
+    std::vector<unsigned long long> k, v, mom;
     std::vector<uint32_t> miss, idx;
   };
-  void snapshot(Snapshot& S) {
+  void snapshot(Snapshot& S, bool want_mom = false) {
     read_counters();
     const uint32_t slots = slots_, nblk = (slots + 255) / 256;
     DevBuf<uint32_t> blk, scratch, omiss;
-    DevBuf<unsigned long long> tiles, okeys, ovals;
+    DevBuf<unsigned long long> tiles, okeys, ovals, omom;
     blk.reserve((size_t)nblk + 1);
     scratch.reserve(2);
     tiles.reserve(SCAN_SCRATCH_WORDS / 2);
     okeys.reserve(occ_ + 1);
     ovals.reserve(4 * (occ_ + 1));
     if (aux_) omiss.reserve(occ_ + 1);
+    if (want_mom) omom.reserve(DM_MOM_WORDS * (occ_ + 1));
     LX_HIP(hipMemsetAsync(tiles.p, 0, sizeof(unsigned long long) * (SCAN_SCRATCH_WORDS / 2), own_));
     hipLaunchKernelGGL(k_dm_count, dim3(nblk), dim3(256), 0, own_, keys_, slots, blk.p);
     exclusive_scan_u32_n(blk.p, blk.p, (uint32_t*)tiles.p, scratch.p, nblk, own_);
-    if (aux_)
-      hipLaunchKernelGGL(k_dm_compact<true>, dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p, aux_, omiss.p);
+    const unsigned long long* no_mom = nullptr;
+    unsigned long long* no_omom = nullptr;
+    if (want_mom && aux_)
+      hipLaunchKernelGGL((k_dm_compact<true, true>), dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p, aux_, omiss.p,
+                         mom_, omom.p);
+    else if (want_mom)
+      hipLaunchKernelGGL((k_dm_compact<false, true>), dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p, nullptr,
+                         nullptr, mom_, omom.p);
+    else if (aux_)
+      hipLaunchKernelGGL((k_dm_compact<true, false>), dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p, aux_, omiss.p,
+                         no_mom, no_omom);
     else
-      hipLaunchKernelGGL(k_dm_compact<false>, dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p, nullptr, nullptr);
+      hipLaunchKernelGGL((k_dm_compact<false, false>), dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p, nullptr,
+                         nullptr, no_mom, no_omom);
     LX_HIP(hipGetLastError());
     S.k.resize(occ_);
     S.v.resize(4 * (size_t)occ_);
     S.miss.assign(aux_ ? occ_ : 0, 0u);
+    S.mom.resize(want_mom ? DM_MOM_WORDS * (size_t)occ_ : 0);
     uint32_t total = 0;
     LX_HIP(hipMemcpyAsync(&total, blk.p + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, own_));
     if (occ_) {
       LX_HIP(hipMemcpyAsync(S.k.data(), okeys.p, sizeof(unsigned long long) * occ_, hipMemcpyDeviceToHost, own_));
       LX_HIP(hipMemcpyAsync(S.v.data(), ovals.p, sizeof(unsigned long long) * 4 * occ_, hipMemcpyDeviceToHost, own_));
       if (aux_) LX_HIP(hipMemcpyAsync(S.miss.data(), omiss.p, sizeof(uint32_t) * occ_, hipMemcpyDeviceToHost, own_));
+      if (want_mom)
+        LX_HIP(hipMemcpyAsync(S.mom.data(), omom.p, sizeof(unsigned long long) * DM_MOM_WORDS * occ_, hipMemcpyDeviceToHost, own_));
     }
     LX_HIP(hipStreamSynchronize(own_));
     scan_check_errors();
@@ -458,19 +595,56 @@ class DenseMap {
     const std::vector<unsigned long long>&hk = S.k, &hv = S.v;
     out.clear();
     out.reserve(S.idx.size());
-    const double leaf = (double)cfg.leaf, qs = (double)(1u << DM_QBITS);
-    const unsigned long long km = (1ull << DM_KBITS) - 1ull;
+    const double leaf = (double)cfg.leaf;
     for (size_t r = 0; r < S.idx.size(); r++) {
       const uint32_t j = S.idx[r];
       if (rule && dm_dynamic(*rule, hv[4 * (size_t)j], S.miss[j])) continue;
-      const unsigned long long k = hk[j];
       const double cnt = (double)hv[4 * (size_t)j];
+      long long ia[3];
       float v[3];
-      for (int a = 0; a < 3; a++) {
-        const double ia = (double)((long long)((k >> (DM_KBITS * a)) & km) - (1ll << DM_QBITS));
-        v[a] = (float)((ia + (double)hv[4 * (size_t)j + 1 + a] / (cnt * qs)) * leaf);
-      }
+      dm_key_indices(hk[j], ia);
+      dm_position(leaf, ia, &hv[4 * (size_t)j], v);
       out.push_back(axes == 1 ? make_float4(v[2], v[0], v[1], (float)cnt) : make_float4(v[0], v[1], v[2], (float)cnt));
+    }
+  }
+
+  bool moments() const { return mom_ != nullptr; }
+
+  // allowed while nothing has been offered since creation / reset; the handle is unchanged when refused
+  void enable_moments() {
+    read_counters();
+    LX_REQUIRE(occ_ == 0 && offered_ == 0, "moments can only be enabled on an empty map (a fresh handle, or right after reset)");
+    if (!mom_) {
+      LX_HIP(hipMalloc((void**)&mom_, sizeof(unsigned long long) * DM_MOM_WORDS * (size_t)slots_));
+      LX_HIP(hipMemsetAsync(mom_, 0, sizeof(unsigned long long) * DM_MOM_WORDS * (size_t)slots_, own_));
+      LX_HIP(hipStreamSynchronize(own_));
+    }
+  }
+
+  // the nine moment words per voxel in the order of records()
+  void moment_words(std::vector<unsigned long long>& out) {
+    Snapshot S;
+    snapshot(S, true);
+    out.resize(DM_MOM_WORDS * S.idx.size());
+    for (size_t r = 0; r < S.idx.size(); r++)
+      memcpy(&out[DM_MOM_WORDS * r], &S.mom[DM_MOM_WORDS * (size_t)S.idx[r]], sizeof(unsigned long long) * DM_MOM_WORDS);
+  }
+
+  // the voxels as surfels in the order of records(); with a rule, without the voxels it calls dynamic
+  void surfels(std::vector<loamx_surfel>& out, int axes, const loamx_densemap_surfel_config& sc, const loamx_densemap_static_rule* rule) {
+    Snapshot S;
+    snapshot(S, true);
+    out.clear();
+    out.reserve(S.idx.size());
+    const double leaf = (double)cfg.leaf;
+    for (size_t r = 0; r < S.idx.size(); r++) {
+      const size_t j = S.idx[r];
+      if (rule && dm_dynamic(*rule, S.v[4 * j], S.miss[j])) continue;
+      long long ia[3];
+      loamx_surfel s;
+      dm_key_indices(S.k[j], ia);
+      dm_surfel(leaf, ia, &S.v[4 * j], &S.mom[DM_MOM_WORDS * j], sc, axes, s);
+      out.push_back(s);
     }
   }
 
@@ -506,20 +680,21 @@ class DenseMap {
   uint64_t prune(const loamx_densemap_static_rule& rule) {
     read_counters();
     const uint64_t before = occ_;
-    unsigned long long *nk = nullptr, *nv = nullptr;
+    unsigned long long *nk = nullptr, *nv = nullptr, *nm = nullptr;
     uint32_t* na = nullptr;
-    alloc_table(slots_, nk, nv, &na);
+    alloc_table(slots_, nk, nv, &na, mom_ ? &nm : nullptr);
     LX_HIP(hipMemsetAsync(nk, 0xff, sizeof(unsigned long long) * slots_, own_));
     LX_HIP(hipMemsetAsync(nv, 0, sizeof(unsigned long long) * 4 * slots_, own_));
     LX_HIP(hipMemsetAsync(na, 0, sizeof(uint32_t) * 2 * (size_t)slots_, own_));
+    if (nm) LX_HIP(hipMemsetAsync(nm, 0, sizeof(unsigned long long) * DM_MOM_WORDS * (size_t)slots_, own_));
     LX_HIP(hipMemsetAsync(ctr_.p, 0, sizeof(unsigned long long), own_));   // (the occupancy: recounted by the kernel)
-    hipLaunchKernelGGL((k_dm_rehash<true, true>), dim3((slots_ + 255) / 256), dim3(256), 0, own_, keys_, vals_, slots_, nk, nv, slots_ - 1u,
-                       64u - log2u(slots_), ctr_.p, aux_, na, rule);
+    launch_rehash<true, true>(own_, nk, nv, slots_, na, nm, rule);
     LX_HIP(hipGetLastError());
     retire_table();
     keys_ = nk;
     vals_ = nv;
     aux_ = na;
+    mom_ = nm;
     read_counters();
     return before - occ_;
   }
@@ -546,6 +721,7 @@ class DenseMap {
   unsigned long long* keys_ = nullptr;
   unsigned long long* vals_ = nullptr;
   uint32_t* aux_ = nullptr;   // carving: miss and stamp per slot (nullptr: carving is off)
+  unsigned long long* mom_ = nullptr;   // moments: nine words per slot (nullptr: moments are off)
   loamx_densemap_carve_config carve_ = {0.f, 1u, 1u, 4096u};
   uint32_t seq_ = 0;          // sequence number of the last add call (stamp values; 0 = never stamped)
   uint64_t carve_ctr_[6] = {0, 0, 0, 0, 0, 0};
@@ -561,21 +737,54 @@ class DenseMap {
   uint64_t occ_ = 0, pend_ = 0, pend_snap_ = 0;
   uint64_t offered_ = 0, drop_range_ = 0, drop_key_ = 0;
 
-  void alloc_table(uint64_t slots, unsigned long long*& k, unsigned long long*& v, uint32_t** aux = nullptr) {
+  void alloc_table(uint64_t slots, unsigned long long*& k, unsigned long long*& v, uint32_t** aux = nullptr, unsigned long long** mom = nullptr) {
     LX_HIP(hipMalloc((void**)&k, sizeof(unsigned long long) * slots));
     LX_HIP(hipMalloc((void**)&v, sizeof(unsigned long long) * 4 * slots));
     if (aux) LX_HIP(hipMalloc((void**)aux, sizeof(uint32_t) * 2 * slots));
+    if (mom) LX_HIP(hipMalloc((void**)mom, sizeof(unsigned long long) * DM_MOM_WORDS * slots));
   }
-  // the current table (and its auxiliary words) to the graveyard
+  // the current table (and its auxiliary and moment words) to the graveyard
   void retire_table() {
     graveyard_.push_back(keys_);
     graveyard_.push_back(vals_);
     if (aux_) graveyard_.push_back(aux_);
+    if (mom_) graveyard_.push_back(mom_);
+  }
+  // the current table into (nk, nv, na, nm) of `want` slots on st; the moment words travel when the map has them
+  template <bool AUX, bool PRUNE>
+  void launch_rehash(hipStream_t st, unsigned long long* nk, unsigned long long* nv, uint64_t want, uint32_t* na, unsigned long long* nm,
+                     const loamx_densemap_static_rule& rule) {
+    const dim3 grid((slots_ + 255) / 256), block(256);
+    const uint32_t mask = (uint32_t)(want - 1), sh = 64u - log2u(want);
+    const uint32_t* oa = aux_;
+    const unsigned long long* om = mom_;
+    if (mom_)
+      hipLaunchKernelGGL((k_dm_rehash<AUX, PRUNE, true>), grid, block, 0, st, keys_, vals_, slots_, nk, nv, mask, sh, ctr_.p, oa, na, rule, om, nm);
+    else
+      hipLaunchKernelGGL((k_dm_rehash<AUX, PRUNE, false>), grid, block, 0, st, keys_, vals_, slots_, nk, nv, mask, sh, ctr_.p, oa, na, rule, om, nm);
+  }
+  // the insert of one add; the combine by the bench hook, the moment words when the map has them
+  template <bool STAMP>
+  void launch_insert(hipStream_t st, const float4* pts, uint32_t n, const DmFilter& F, uint32_t sh, uint32_t seq) {
+    const dim3 grid((n + 255) / 256), block(256);
+    const uint32_t mask = slots_ - 1u;
+    if (!mom_) {
+      if (combine)
+        hipLaunchKernelGGL((k_dm_insert<true, STAMP, false>), grid, block, 0, st, pts, n, F, keys_, vals_, mask, sh, ctr_.p, aux_, seq, mom_);
+      else
+        hipLaunchKernelGGL((k_dm_insert<false, STAMP, false>), grid, block, 0, st, pts, n, F, keys_, vals_, mask, sh, ctr_.p, aux_, seq, mom_);
+    } else {
+      if (combine)
+        hipLaunchKernelGGL((k_dm_insert<true, STAMP, true>), grid, block, 0, st, pts, n, F, keys_, vals_, mask, sh, ctr_.p, aux_, seq, mom_);
+      else
+        hipLaunchKernelGGL((k_dm_insert<false, STAMP, true>), grid, block, 0, st, pts, n, F, keys_, vals_, mask, sh, ctr_.p, aux_, seq, mom_);
+    }
   }
   void clear(hipStream_t st) {
     LX_HIP(hipMemsetAsync(keys_, 0xff, sizeof(unsigned long long) * slots_, st));
     LX_HIP(hipMemsetAsync(vals_, 0, sizeof(unsigned long long) * 4 * slots_, st));
     if (aux_) LX_HIP(hipMemsetAsync(aux_, 0, sizeof(uint32_t) * 2 * (size_t)slots_, st));
+    if (mom_) LX_HIP(hipMemsetAsync(mom_, 0, sizeof(unsigned long long) * DM_MOM_WORDS * (size_t)slots_, st));
     LX_HIP(hipMemsetAsync(ctr_.p, 0, sizeof(unsigned long long) * DM_CTR_WORDS, st));
   }
   void free_graveyard() {
@@ -628,25 +837,24 @@ class DenseMap {
     while (occ_ + pend_ + n > want / 2) want *= 2;
     LX_REQUIRE(want <= (1ull << 31), "dense map: more voxels than the table can index");
     if (want != slots_) {
-      unsigned long long *nk = nullptr, *nv = nullptr;
+      unsigned long long *nk = nullptr, *nv = nullptr, *nm = nullptr;
       uint32_t* na = nullptr;
-      alloc_table(want, nk, nv, aux_ ? &na : nullptr);
+      alloc_table(want, nk, nv, aux_ ? &na : nullptr, mom_ ? &nm : nullptr);
       LX_HIP(hipMemsetAsync(nk, 0xff, sizeof(unsigned long long) * want, st));
       LX_HIP(hipMemsetAsync(nv, 0, sizeof(unsigned long long) * 4 * want, st));   // (slots claimed later accumulate from zero)
-      const uint32_t sh = 64u - log2u(want);
+      if (nm) LX_HIP(hipMemsetAsync(nm, 0, sizeof(unsigned long long) * DM_MOM_WORDS * want, st));
       const loamx_densemap_static_rule none = {0u, 0u, 0u};
       if (aux_) {
         LX_HIP(hipMemsetAsync(na, 0, sizeof(uint32_t) * 2 * want, st));
-        hipLaunchKernelGGL((k_dm_rehash<true, false>), dim3((slots_ + 255) / 256), dim3(256), 0, st, keys_, vals_, slots_, nk, nv,
-                           (uint32_t)(want - 1), sh, ctr_.p, aux_, na, none);
+        launch_rehash<true, false>(st, nk, nv, want, na, nm, none);
       } else {
-        hipLaunchKernelGGL((k_dm_rehash<false, false>), dim3((slots_ + 255) / 256), dim3(256), 0, st, keys_, vals_, slots_, nk, nv,
-                           (uint32_t)(want - 1), sh, ctr_.p, nullptr, nullptr, none);
+        launch_rehash<false, false>(st, nk, nv, want, na, nm, none);
       }
       retire_table();
       keys_ = nk;
       vals_ = nv;
       aux_ = na;
+      mom_ = nm;
       slots_ = (uint32_t)want;
       rehashes++;
     }
@@ -658,19 +866,13 @@ class DenseMap {
       F.use_max = cfg.max_range > 0.f ? 1 : 0;
       F.ox = origin[0]; F.oy = origin[1]; F.oz = origin[2];
       const uint32_t sh = 64u - log2u(slots_);
-      const dim3 grid((n + 255) / 256), block(256);
+      const dim3 block(256);
       if (!aux_) {
-        if (combine)
-          hipLaunchKernelGGL((k_dm_insert<true, false>), grid, block, 0, st, pts, n, F, keys_, vals_, slots_ - 1u, sh, ctr_.p, nullptr, 0u);
-        else
-          hipLaunchKernelGGL((k_dm_insert<false, false>), grid, block, 0, st, pts, n, F, keys_, vals_, slots_ - 1u, sh, ctr_.p, nullptr, 0u);
+        launch_insert<false>(st, pts, n, F, sh, 0u);
       } else {
         // carving: the insert stamps its voxels with the call's sequence number, and the rays are traced behind it
         seq_++;
-        if (combine)
-          hipLaunchKernelGGL((k_dm_insert<true, true>), grid, block, 0, st, pts, n, F, keys_, vals_, slots_ - 1u, sh, ctr_.p, aux_, seq_);
-        else
-          hipLaunchKernelGGL((k_dm_insert<false, true>), grid, block, 0, st, pts, n, F, keys_, vals_, slots_ - 1u, sh, ctr_.p, aux_, seq_);
+        launch_insert<true>(st, pts, n, F, sh, seq_);
         DmCarve R;
         R.max2 = carve_.max_range * carve_.max_range;
         R.use_max = carve_.max_range > 0.f ? 1 : 0;
@@ -702,6 +904,18 @@ static void write_pcd_records(const char* path, const float4* rec, size_t n) {
                          "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity\nSIZE 4 4 4 4\nTYPE F F F F\n"
                          "COUNT 1 1 1 1\nWIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %zu\nDATA binary\n", n, n);
   const bool ok = hl > 0 && (n == 0 || fwrite(rec, sizeof(float4), n, f) == n);
+  const bool closed = fclose(f) == 0;
+  LX_REQUIRE(ok && closed, std::string("write to ") + path + " failed");
+}
+
+static void write_pcd_surfels(const char* path, const loamx_surfel* rec, size_t n) {
+  FILE* f = fopen(path, "wb");
+  LX_REQUIRE(f, std::string("cannot open ") + path + " for writing");
+  const int hl = fprintf(f,
+                         "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity normal_x normal_y normal_z curvature\n"
+                         "SIZE 4 4 4 4 4 4 4 4\nTYPE F F F F F F F F\nCOUNT 1 1 1 1 1 1 1 1\nWIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\n"
+                         "POINTS %zu\nDATA binary\n", n, n);
+  const bool ok = hl > 0 && (n == 0 || fwrite(rec, sizeof(loamx_surfel), n, f) == n);
   const bool closed = fclose(f) == 0;
   LX_REQUIRE(ok && closed, std::string("write to ") + path + " failed");
 }
@@ -908,6 +1122,95 @@ int loamx_densemap_prune(loamx_densemap* h, const loamx_densemap_static_rule* ru
     LX_HIP(hipSetDevice(h->d.cfg.device));
     const uint64_t gone = h->d.prune(r);
     if (removed) *removed = gone;
+    return LOAMX_OK;
+  });
+}
+
+void loamx_densemap_surfel_default_config(loamx_densemap_surfel_config* cfg) {
+  if (!cfg) return;
+  memset(cfg, 0, sizeof(*cfg));
+  cfg->min_points = 5u;
+  cfg->min_planar_ratio = 0.01f;
+}
+
+// the surfel settings of a call, checked (NULL: the defaults)
+static loamx_densemap_surfel_config checked_surfel_config(const loamx_densemap_surfel_config* cfg) {
+  loamx_densemap_surfel_config c;
+  if (cfg) c = *cfg; else loamx_densemap_surfel_default_config(&c);
+  LX_REQUIRE(c.min_points >= 3u, "min_points must be >= 3");
+  LX_REQUIRE(c.min_planar_ratio >= 0.f, "min_planar_ratio must be >= 0");   // (NaN too)
+  return c;
+}
+#define LX_REQUIRE_MOMENTS(h) LX_REQUIRE((h)->d.moments(), "moments are not enabled")
+
+int loamx_densemap_surfel_of(float leaf, const int32_t idx[3], const uint64_t vals[4], const uint64_t mom[9],
+                             const loamx_densemap_surfel_config* cfg, int axes, loamx_surfel* out) {
+  return guard([&]() {
+    LX_REQUIRE(idx && vals && mom && out, "NULL argument");
+    LX_REQUIRE(leaf > 0.f && std::isfinite(leaf), "leaf must be positive");
+    LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+    LX_REQUIRE(vals[0] != 0ull, "a voxel holds at least one point");
+    const loamx_densemap_surfel_config c = checked_surfel_config(cfg);
+    const long long ia[3] = {idx[0], idx[1], idx[2]};
+    const unsigned long long v4[4] = {vals[0], vals[1], vals[2], vals[3]};
+    unsigned long long m9[DM_MOM_WORDS];
+    for (int k = 0; k < DM_MOM_WORDS; k++) m9[k] = mom[k];
+    dm_surfel((double)leaf, ia, v4, m9, c, axes, *out);
+    return LOAMX_OK;
+  });
+}
+int loamx_densemap_enable_moments(loamx_densemap* h) {
+  return guard([&]() {
+    LX_REQUIRE(h, "NULL handle");
+    h->d.enable_moments();
+    return LOAMX_OK;
+  });
+}
+int loamx_densemap_download_moments(loamx_densemap* h, uint64_t* out, uint64_t capacity, uint64_t* n) {
+  return guard([&]() {
+    LX_REQUIRE(h && n && (out || !capacity), "NULL argument");
+    LX_REQUIRE_MOMENTS(h);
+    std::vector<unsigned long long> m;
+    h->d.moment_words(m);
+    *n = m.size() / DM_MOM_WORDS;
+    if (*n > capacity) return LOAMX_E_CAPACITY;
+    if (!m.empty()) memcpy(out, m.data(), sizeof(uint64_t) * m.size());
+    return LOAMX_OK;
+  });
+}
+// the surfels of a call: arguments checked in the order of download_static (a rule needs carving)
+static void surfels_of_call(loamx_densemap* h, int axes, const loamx_densemap_surfel_config* cfg, const loamx_densemap_static_rule* rule,
+                            std::vector<loamx_surfel>& out) {
+  LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+  const loamx_densemap_surfel_config c = checked_surfel_config(cfg);
+  LX_REQUIRE_MOMENTS(h);
+  if (rule) {
+    const loamx_densemap_static_rule r = checked_rule(rule);
+    LX_REQUIRE_CARVING(h);
+    h->d.surfels(out, axes, c, &r);
+  } else {
+    h->d.surfels(out, axes, c, nullptr);
+  }
+}
+int loamx_densemap_download_surfels(loamx_densemap* h, loamx_surfel* out, uint64_t capacity, uint64_t* n, int axes,
+                                    const loamx_densemap_surfel_config* cfg, const loamx_densemap_static_rule* rule) {
+  return guard([&]() {
+    LX_REQUIRE(h && n && (out || !capacity), "NULL argument");
+    std::vector<loamx_surfel> s;
+    surfels_of_call(h, axes, cfg, rule, s);
+    *n = s.size();
+    if (s.size() > capacity) return LOAMX_E_CAPACITY;
+    if (!s.empty()) memcpy(out, s.data(), sizeof(loamx_surfel) * s.size());
+    return LOAMX_OK;
+  });
+}
+int loamx_densemap_save_pcd_surfels(loamx_densemap* h, const char* path, int axes, const loamx_densemap_surfel_config* cfg,
+                                    const loamx_densemap_static_rule* rule) {
+  return guard([&]() {
+    LX_REQUIRE(h && path, "NULL argument");
+    std::vector<loamx_surfel> s;
+    surfels_of_call(h, axes, cfg, rule, s);
+    write_pcd_surfels(path, s.data(), s.size());
     return LOAMX_OK;
   });
 }

@@ -4,8 +4,10 @@
 //   accumulate_rotation        <-> src/lib/BasicLaserOdometry.cpp:155-179
 //   plugin_imu_rotation        <-> src/lib/BasicLaserOdometry.cpp:91-151
 //   transform_associate_to_map <-> src/lib/BasicLaserMapping.cpp:103-167
+// and, not from the reference, jacobi_eig3: the symmetric 3x3 eigen-solver of the dense map's surfel export (densemap.hip).
 #pragma once
 #include <cmath>
+#include <utility>
 #include "dev_math.hpp"
 
 namespace loamx {
@@ -135,6 +137,53 @@ inline void transform_associate_to_map(const HTwist& sum, const HTwist& bef, con
   HVec3 v = incre.pos;
   h_rot_zxy(v, tobe.rot_z, tobe.rot_x, tobe.rot_y);
   tobe.pos = {aft.pos.x - v.x, aft.pos.y - v.y, aft.pos.z - v.z};
+}
+
+// Eigen-decomposition of a symmetric 3x3 matrix in double by cyclic Jacobi rotations (the dense map's surfel export, once per voxel
+// on request).  a: the matrix (its upper triangle is read; overwritten).  On return w[0] <= w[1] <= w[2] and column k of v, that is
+// v[0][k], v[1][k], v[2][k], is the unit eigenvector of w[k].  An off-diagonal element that is exactly 0 is left alone, so an axis-aligned
+// matrix gives exact unit axes.  The sweep count is bounded (convergence is quadratic: a handful of sweeps reach the last bit).
+inline void jacobi_eig3(double a[3][3], double w[3], double v[3][3]) {
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) v[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 32; sweep++) {
+    const double off = std::fabs(a[0][1]) + std::fabs(a[0][2]) + std::fabs(a[1][2]);
+    const double diag = std::fabs(a[0][0]) + std::fabs(a[1][1]) + std::fabs(a[2][2]);
+    if (off == 0.0 || off <= 1e-300 + diag * 1e-22) break;
+    for (int p = 0; p < 2; p++)
+      for (int q = p + 1; q < 3; q++) {
+        if (a[p][q] == 0.0) continue;
+        // the rotation that annihilates a[p][q]: t = tan of its angle, the smaller root
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        const double apq = a[p][q];
+        a[p][p] -= t * apq;
+        a[q][q] += t * apq;
+        a[p][q] = 0.0;
+        const int r = 3 - p - q;   // the third index
+        const double arp = r < p ? a[r][p] : a[p][r], arq = r < q ? a[r][q] : a[q][r];
+        const double nrp = c * arp - s * arq, nrq = s * arp + c * arq;
+        if (r < p) a[r][p] = nrp; else a[p][r] = nrp;
+        if (r < q) a[r][q] = nrq; else a[q][r] = nrq;
+        for (int k = 0; k < 3; k++) {
+          const double vp = v[k][p], vq = v[k][q];
+          v[k][p] = c * vp - s * vq;
+          v[k][q] = s * vp + c * vq;
+        }
+      }
+  }
+  int o[3] = {0, 1, 2};   // ascending eigenvalues (ties keep the index order)
+  if (a[o[1]][o[1]] < a[o[0]][o[0]]) std::swap(o[0], o[1]);
+  if (a[o[2]][o[2]] < a[o[1]][o[1]]) std::swap(o[1], o[2]);
+  if (a[o[1]][o[1]] < a[o[0]][o[0]]) std::swap(o[0], o[1]);
+  double vs[3][3];
+  for (int k = 0; k < 3; k++) {
+    w[k] = a[o[k]][o[k]];
+    for (int i = 0; i < 3; i++) vs[i][k] = v[i][o[k]];
+  }
+  for (int i = 0; i < 3; i++)
+    for (int k = 0; k < 3; k++) v[i][k] = vs[i][k];
 }
 
 }  // namespace loamx

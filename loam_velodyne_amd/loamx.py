@@ -991,12 +991,39 @@ class StaticRule(C.Structure):
         return bool(_check(lib().loamx_densemap_rule_is_dynamic(C.byref(self), C.c_uint64(n), C.c_uint32(miss))))
 
 
+class SurfelConfig(C.Structure):
+    """loamx_densemap_surfel_config: a voxel has a surfel iff n >= min_points, its points are not all equal, and the middle
+    eigenvalue of their covariance is at least min_planar_ratio times the largest.  SurfelConfig() holds the defaults (5, 0.01)."""
+    _fields_ = [("min_points", C.c_uint32), ("min_planar_ratio", C.c_float)]
+
+    def __init__(self, min_points=None, min_planar_ratio=None):
+        super().__init__()
+        lib().loamx_densemap_surfel_default_config(C.byref(self))
+        for k, v in (("min_points", min_points), ("min_planar_ratio", min_planar_ratio)):
+            if v is not None:
+                setattr(self, k, v)
+
+
+SURFEL_FIELDS = ("x", "y", "z", "intensity", "normal_x", "normal_y", "normal_z", "curvature")   # loamx_surfel, PCL PointXYZINormal order
+
 _AXES = {"loam": 0, "sensor": 1}
 
 
 def _axes(axes) -> int:
     assert axes in _AXES, f"axes must be one of {tuple(_AXES)}"
     return _AXES[axes]
+
+
+def surfel_of(leaf, idx, vals, mom, axes="loam", min_points=None, min_planar_ratio=None) -> np.ndarray:
+    """loamx_densemap_surfel_of (host only): the surfel of one voxel from its integer words — idx = (ix, iy, iz), vals = (n, Sx, Sy,
+    Sz), mom = the nine moment words (Python integers are taken modulo 2^64).  Returns (8,) float32 in the order of SURFEL_FIELDS."""
+    i = (C.c_int32 * 3)(*[int(v) for v in idx])
+    v = (C.c_uint64 * 4)(*[int(x) % (1 << 64) for x in vals])
+    m = (C.c_uint64 * 9)(*[int(x) % (1 << 64) for x in mom])
+    c = SurfelConfig(min_points, min_planar_ratio)
+    out = np.zeros(8, np.float32)
+    _check(lib().loamx_densemap_surfel_of(C.c_float(leaf), i, v, m, C.byref(c), _axes(axes), out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def write_pcd(path: str, points, axes="loam"):
@@ -1072,8 +1099,13 @@ class DenseMap:
             _check(rc)
             return out[:c.count]
 
-    def save_pcd(self, path: str, axes="loam", static=None):
-        if static is None:
+    def save_pcd(self, path: str, axes="loam", static=None, surfels=False, min_points=None, min_planar_ratio=None):
+        """the map as a binary PCD v0.7 file: x y z intensity, or with surfels=True (needs moments) the eight fields of surfels()"""
+        if surfels:
+            c = SurfelConfig(min_points, min_planar_ratio)
+            _check(lib().loamx_densemap_save_pcd_surfels(self.h, os.fsencode(path), _axes(axes), C.byref(c),
+                                                         C.byref(static) if static is not None else None))
+        elif static is None:
             _check(lib().loamx_densemap_save_pcd(self.h, os.fsencode(path), _axes(axes)))
         else:
             _check(lib().loamx_densemap_save_pcd_static(self.h, os.fsencode(path), _axes(axes), C.byref(static)))
@@ -1108,6 +1140,36 @@ class DenseMap:
         removed = C.c_uint64(0)
         _check(lib().loamx_densemap_prune(self.h, C.byref(rule), C.byref(removed)))
         return int(removed.value)
+
+    def enable_moments(self):
+        """second moments (include/loamx.h): from now on every add also accumulates, per voxel, the sums of the products of the offsets
+        and the vector from the sensor — nine 64-bit words, 72 bytes per slot.  Only on an empty map (fresh, or right after reset)."""
+        _check(lib().loamx_densemap_enable_moments(self.h))
+
+    def moments(self):
+        """(n, 9) uint64: Mxx, Myy, Mzz, Mxy, Mxz, Myz, Vx, Vy, Vz per voxel (V as two's complement), in the order of points()"""
+        n = C.c_uint64(len(self))
+        while True:
+            out = np.zeros((max(int(n.value), 1), 9), np.uint64)
+            rc = lib().loamx_densemap_download_moments(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(int(n.value)), C.byref(n))
+            if rc == E_CAPACITY:
+                continue
+            _check(rc)
+            return out[:int(n.value)]
+
+    def surfels(self, axes="loam", min_points=None, min_planar_ratio=None, static=None):
+        """(n, 8) float32 in the order of SURFEL_FIELDS: the record of points() plus the unit normal facing the sensors and the
+        curvature, zeros where the voxel has no surfel.  static (a StaticRule; needs carving): without the dynamic voxels"""
+        c = SurfelConfig(min_points, min_planar_ratio)
+        n = C.c_uint64(len(self))
+        while True:
+            out = np.zeros((max(int(n.value), 1), 8), np.float32)
+            rc = lib().loamx_densemap_download_surfels(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(int(n.value)), C.byref(n),
+                                                       _axes(axes), C.byref(c), C.byref(static) if static is not None else None)
+            if rc == E_CAPACITY:
+                continue
+            _check(rc)
+            return out[:int(n.value)]
 
     def reset(self):
         _check(lib().loamx_densemap_reset(self.h))

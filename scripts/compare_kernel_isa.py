@@ -1,6 +1,9 @@
 """Compare the gfx950 instruction streams of the kernels two builds of one object file hold (e.g. ingest.o of two commits):
-python scripts/compare_kernel_isa.py OLD.o NEW.o[,NEW2.o ...] [name-substring ...]
-(several NEW objects, comma-separated: kernels that moved to a file of their own are looked up in all of them)
+python scripts/compare_kernel_isa.py OLD.o NEW.o[,NEW2.o ...] [name-substring | OLDNAME=NEWNAME ...]
+(several NEW objects, comma-separated: kernels that moved to a file of their own are looked up in all of them; OLDNAME=NEWNAME, both
+mangled names in full: a kernel whose signature changed, e.g. by a new template parameter, is compared under its new name;
+--ignore-kernarg-offsets: the offsets of the scalar loads from the kernel-argument segment, s[0:1], are left out of the comparison,
+which a new trailing argument moves for the hidden arguments behind it)
 
 Each object's device code is unbundled (clang-offload-bundler) and disassembled (llvm-objdump); per kernel present in OLD the
 instructions are compared with branch-target labels and the trailing alignment padding stripped.  Exit status 1 when a kernel differs,
@@ -35,13 +38,23 @@ def kernels(obj, tmp):
 
 
 def main():
-    old_obj, new_obj, pats = sys.argv[1], sys.argv[2], sys.argv[3:]
+    args = [a for a in sys.argv[1:] if a != "--ignore-kernarg-offsets"]
+    old_obj, new_obj = args[0], args[1]
+    renamed = dict(a.split("=", 1) for a in args[2:] if "=" in a)
+    pats = [a for a in args[2:] if "=" not in a] + list(renamed)
     with tempfile.TemporaryDirectory() as tmp:
         os.makedirs(os.path.join(tmp, "old"))
         a, b = kernels(old_obj, os.path.join(tmp, "old")), {}
         for k, obj in enumerate(new_obj.split(",")):
             os.makedirs(os.path.join(tmp, f"new{k}"))
             b.update(kernels(obj, os.path.join(tmp, f"new{k}")))
+    if len(args) < len(sys.argv) - 1:
+        for ks in (a, b):
+            for name in ks:
+                ks[name] = [re.sub(r"^(s_load_dword\w* s\S+ s\[0:1\], )0x[0-9a-f]+$", r"\1<offset>", i) for i in ks[name]]
+    for old, new in renamed.items():   # (the new kernel is looked at under the old one's name)
+        if new in b:
+            b[old] = b.pop(new)
     bad = 0
     for name in sorted(set(b) - set(a)):
         if not pats or any(p in name for p in pats):
