@@ -450,6 +450,33 @@ typedef struct loamx_index_desc {
  * the point's index inside its cloud (bit pattern), with the ring byte under LOAMX_INDEX_PACK_RING. */
 int loamx_index_probe(const float* pts_xyzw, uint32_t n, const uint32_t* off, uint32_t K, float cell_edge, uint32_t flags, loamx_index_desc* desc,
                       uint32_t* table, uint32_t table_cap, uint32_t* table_len, float* sorted_xyzw);
+/* Parity hook for the bucketed voxel grid of the registration's stack clouds on its own (test use): n >= 1 packed x y z intensity
+ * points (n < 2^24) in nseg <= 4096 contiguous segments seg_off[nseg + 1] (seg_off[0] = 0, seg_off[nseg] = n, empty ones allowed);
+ * segment k belongs to sweep k / 2 and is filtered with leaf_even / leaf_odd by its parity.  poses12: 12 words per sweep,
+ * (nseg + 1) / 2 sweeps — rx ry rz tx ty tz sin(rx) cos(rx) sin(ry) cos(ry) sin(rz) cos(rz), the sine / cosine words used as given.
+ * Non-finite and far coordinates are NOT refused: they are the stage's own give-up case.  The stage runs as the registration runs it
+ * (plan, round trip + bucket search, reduction; one object and stream per process, whose buffers, counters and epoch live on from
+ * call to call), then the stream is waited for.  There is no fallback: after a give-up the arrays hold what the kernels left.
+ * stack_xyzi[n]: every point after the map -> sensor round trip; out_xyzi[n] / out_off[nseg + 1]: the voxel means of segment 0, 1, ...
+ * back to back in PCL's output order and the running count; segs[nseg], lo[bucket_cap], cnt[bucket_cap]: the plan — per segment its
+ * first bucket, bucket count and position bits, per bucket the smallest voxel key it takes ((iz + 2^20) << 42 | (iy + 2^20) << 21 |
+ * (ix + 2^20)) and the number of points that arrived.  A segment of m points owns max(1, ceil(m / 2048)) buckets; LOAMX_E_CAPACITY
+ * (status->buckets set, nothing run) when bucket_cap is smaller than their sum.  LOAMX_E_HIP when a wait inside the kernels timed out. */
+#define LOAMX_VOXBUCKET_SRC_POINTERS 1u /* the kernels read segment k through a device table of one pointer per segment (the
+                                         * registration's device-resident inputs) instead of the concatenated array */
+typedef struct loamx_voxbucket_seg {
+  uint32_t bucket0, nbuckets, pos_bits, pad; /* nbuckets = 0: the plan gave the segment up */
+} loamx_voxbucket_seg;
+typedef struct loamx_voxbucket_status {
+  uint32_t gave_up; /* 1: the run raised its fail word (the registration would repeat it through the general kernel) */
+  uint32_t why;     /* bit r: reason r — 0 coordinate beyond +-2^20 voxels or not finite, 1 more than 512 buckets in a segment,
+                     * 2 segment box beyond INT_MAX voxels, 3 bucket box beyond 63 sort bits, 5 bucket over its 4096 slots */
+  uint32_t buckets; /* buckets of the run */
+  uint32_t pad;
+} loamx_voxbucket_status;
+int loamx_voxbucket_probe(const float* pts_xyzi, uint32_t n, const uint32_t* seg_off, uint32_t nseg, const float* poses12, float leaf_even,
+                          float leaf_odd, uint32_t flags, float* stack_xyzi, float* out_xyzi, uint32_t* out_off,
+                          loamx_voxbucket_status* status, loamx_voxbucket_seg* segs, uint64_t* lo, uint32_t* cnt, uint32_t bucket_cap);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Streaming pipeline: n independent streams, each advancing one sweep per step through feature extraction ->

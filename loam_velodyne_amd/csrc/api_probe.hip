@@ -1,10 +1,11 @@
-// C-ABI: parity hooks for three device primitives that otherwise only run inside whole pipelines — the segmented voxel grid
-// (voxel.hpp), the chained scan (scan.hpp) and the sub-map grid index (submap_index.hpp).  Host glue only (plus one small kernel that
+// C-ABI: parity hooks for four device primitives that otherwise only run inside whole pipelines — the segmented voxel grid
+// (voxel.hpp), the chained scan (scan.hpp), the sub-map grid index (submap_index.hpp) and the bucketed voxel grid (voxbucket.hpp).  Host glue only (plus one small kernel that
 // stands in for the producers which fold the index's bounds): each hook stages the caller's arrays, runs the primitive the way its
 // callers do, waits, checks the error word and copies the results back.  Each keeps ONE object per process (never freed, guarded by a
 // mutex), so consecutive calls reuse its buffers and its state — which is part of what the tests look at.
 #include <mutex>
 #include "submap_index.hpp"
+#include "voxbucket.hpp"
 #include "voxel.hpp"
 
 using namespace loamx;
@@ -73,6 +74,17 @@ __global__ __launch_bounds__(256) void k_probe_fold(const float4* __restrict__ s
     cloud_bounds_update(bounds, active, lo, q.x, q.y, q.z);
   }
 }
+
+struct VoxBucketProbe {
+  VoxBucket vb;
+  DevBuf<float4> pts, src, stack, out;   // src: the segments once more, last segment first (what the pointer table points into)
+  DevBuf<uint32_t> seg_off, out_off;
+  DevBuf<Pose> poses;
+  DevBuf<const float4*> table;
+  std::vector<const float4*> h_table;
+  bool ready = false;
+};
+static_assert(sizeof(Pose) == 48 && sizeof(VbSeg) == sizeof(loamx_voxbucket_seg), "poses12 / loamx_voxbucket_seg mirror Pose / VbSeg");
 
 template <class T> void upload(T* dst, const T* src, size_t n, hipStream_t st) {
   if (n) LX_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, st));
@@ -231,6 +243,69 @@ int loamx_index_probe(const float* pts_xyzw, uint32_t n, const uint32_t* off, ui
     download(table, single ? P->single.cell_start() : P->batch.cell_table(), (size_t)total + 1, st);
     download(reinterpret_cast<float4*>(sorted_xyzw), single ? P->single.sorted() : P->batch.sorted(), n, st);
     LX_HIP(hipStreamSynchronize(st));
+    return LOAMX_OK;
+  });
+}
+
+int loamx_voxbucket_probe(const float* pts_xyzi, uint32_t n, const uint32_t* seg_off, uint32_t nseg, const float* poses12, float leaf_even,
+                          float leaf_odd, uint32_t flags, float* stack_xyzi, float* out_xyzi, uint32_t* out_off,
+                          loamx_voxbucket_status* status, loamx_voxbucket_seg* segs, uint64_t* lo, uint32_t* cnt, uint32_t bucket_cap) {
+  return guard([&]() {
+    const bool by_pointer = (flags & LOAMX_VOXBUCKET_SRC_POINTERS) != 0;
+    LX_REQUIRE((flags & ~1u) == 0u, "unknown flag");
+    LX_REQUIRE(pts_xyzi && seg_off && poses12 && stack_xyzi && out_xyzi && out_off && status && segs && lo && cnt, "NULL argument");
+    LX_REQUIRE(VoxBucket::fits(n, nseg), "n must be in [1, 2^24) and nseg in [1, 4096]");
+    LX_REQUIRE(leaf_even > 0.f && leaf_odd > 0.f && std::isfinite(leaf_even) && std::isfinite(leaf_odd), "leaf sizes must be positive");
+    LX_REQUIRE(seg_off[0] == 0u && seg_off[nseg] == n, "seg_off must run from 0 to n");
+    uint32_t nb = 0;
+    for (uint32_t s = 0; s < nseg; s++) {
+      LX_REQUIRE(seg_off[s] <= seg_off[s + 1], "seg_off must not decrease");
+      const uint32_t m = seg_off[s + 1] - seg_off[s];
+      nb += m ? (m + VB_T - 1) / VB_T : 1u;
+    }
+    status->gave_up = 0u; status->why = 0u; status->buckets = nb; status->pad = 0u;
+    if (nb > bucket_cap) throw Error(LOAMX_E_CAPACITY, "bucket_cap is smaller than the run's bucket count");
+    static std::mutex mu;
+    static VoxBucketProbe* P = nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    hipStream_t st = probe_stream();
+    if (!P) P = new VoxBucketProbe;
+    if (!P->ready) { P->vb.init(st); P->ready = true; }
+    const uint32_t nsweep = (nseg + 1) / 2;
+    P->pts.reserve((size_t)n + 1); P->stack.reserve((size_t)n + 1); P->out.reserve((size_t)n + 1);
+    P->seg_off.reserve((size_t)nseg + 2); P->out_off.reserve((size_t)nseg + 2);
+    P->poses.reserve(nsweep);
+    upload(P->seg_off.p, seg_off, (size_t)nseg + 1, st);
+    upload(P->poses.p, reinterpret_cast<const Pose*>(poses12), nsweep, st);
+    const float4* const* d_src = nullptr;
+    if (by_pointer) {
+      // as the registration's device-resident inputs: every segment lives where its producer left it (here: the segments in reverse
+      // order in a buffer of their own) and the concatenated array holds nothing of use (here: all-ones words, NaN)
+      P->src.reserve((size_t)n + 1);
+      P->table.reserve(nseg);
+      P->h_table.resize(nseg);
+      for (uint32_t s = 0; s < nseg; s++) {
+        P->h_table[s] = P->src.p + (n - seg_off[s + 1]);
+        upload(P->src.p + (n - seg_off[s + 1]), reinterpret_cast<const float4*>(pts_xyzi) + seg_off[s], (size_t)(seg_off[s + 1] - seg_off[s]), st);
+      }
+      upload(P->table.p, P->h_table.data(), nseg, st);
+      LX_HIP(hipMemsetAsync(P->pts.p, 0xff, sizeof(float4) * (size_t)n, st));
+      d_src = P->table.p;
+    } else {
+      upload(P->pts.p, reinterpret_cast<const float4*>(pts_xyzi), n, st);
+    }
+    P->vb.run(P->pts.p, d_src, n, P->seg_off.p, seg_off, nseg, P->poses.p, 1.0f / leaf_even, 1.0f / leaf_odd, P->stack.p, P->out.p, P->out_off.p);
+    download(reinterpret_cast<float4*>(stack_xyzi), P->stack.p, n, st);
+    download(reinterpret_cast<float4*>(out_xyzi), P->out.p, n, st);
+    download(out_off, P->out_off.p, (size_t)nseg + 1, st);
+    download(reinterpret_cast<VbSeg*>(segs), P->vb.d_segs(), nseg, st);
+    download(reinterpret_cast<unsigned long long*>(lo), P->vb.d_lo(), nb, st);
+    download(cnt, P->vb.d_cnt(), nb, st);
+    LX_HIP(hipStreamSynchronize(st));
+    P->vb.check();
+    status->gave_up = P->vb.failed() ? 1u : 0u;
+    status->why = P->vb.why();
+    status->buckets = P->vb.last_buckets();
     return LOAMX_OK;
   });
 }

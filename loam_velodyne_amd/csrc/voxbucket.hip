@@ -16,7 +16,7 @@ struct VbArgs {
   int* box;                     // [nseg][6]
   uint32_t* cnt;
   uint32_t* heads;
-  uint32_t* ctl;                // [0] fail epoch
+  uint32_t* ctl;                // [0] fail epoch, [1] buckets of k_vb_reduce that have arrived (back to 0 when the last one has)
   uint32_t* h_fail;             // pinned: [0] fail epoch, [1] timeout, [2 + r] epoch of the last run that met reason r
   uint32_t* elems;
   float4* stack;
@@ -35,6 +35,29 @@ __device__ inline void vb_fail(const VbArgs& A, int reason) {
   A.ctl[0] = A.epoch;      // (every writer stores the same value)
   A.h_fail[0] = A.epoch;
   A.h_fail[2 + reason] = A.epoch;
+}
+// a give-up raised INSIDE k_vb_reduce, by one thread of the bucket: the device word also goes out write-through (agent scope), so that the
+// bucket that arrives last (vb_arrive) sees it whichever XCD raised it; a plain store would stay in the raising XCD's L2 until the
+// kernel ends.  (k_vb_plan and k_vb_stack end before k_vb_reduce starts: their plain stores are visible to it.)
+__device__ inline void vb_fail_reduce(const VbArgs& A, int reason) {
+  vb_fail(A, reason);
+  __hip_atomic_store(&A.ctl[0], A.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// "The kernels leave an empty result": every bucket of k_vb_reduce arrives ONCE (ctl[1]), after its offsets and its give-up, if any,
+// have been stored write-through and have completed; the bucket that arrives last therefore stores behind every other bucket's
+// offsets, and zeroes them when the run has given up.  (Before, only a bucket that found the fail word up when it STARTED zeroed
+// them: a give-up raised inside the kernel — reason 2, by the last bucket, at its end; reason 3 — left the offsets of a run that
+// looked complete.  The registration never read them: it tests the fail word.)  One thread per bucket; vb_arrive_last() by the same
+// thread, later, with the value vb_arrive() returned.
+__device__ inline uint32_t vb_arrive(const VbArgs& A) {
+  xchg_stores_done();
+  return __hip_atomic_fetch_add(&A.ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ inline void vb_arrive_last(const VbArgs& A, uint32_t before) {
+  if (before + 1u != A.nb) return;
+  __hip_atomic_store(&A.ctl[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (for the next run)
+  if (__hip_atomic_load(&A.ctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != A.epoch) return;
+  for (uint32_t s = 0; s <= A.nseg; s++) __hip_atomic_store(&A.out_off[s], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // voxel coordinate of one axis exactly as pcl::VoxelGrid forms it: floor(v * inverse leaf), float arithmetic
 constexpr int VB_OFF = 1 << 20;
@@ -220,11 +243,12 @@ __global__ __launch_bounds__(VB_THREADS) void k_vb_reduce(const VbArgs A) {
   VB_TS(0);
   if (__hip_atomic_load(&A.ctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == A.epoch) {   // given up: an empty, well-formed result
     //  EVERY bucket publishes a count — a bucket that started before the give-up may be looking back at this one —
-    // and the offsets are zeroed by the first AND the last bucket: whichever buckets ran to the end before the fail word was raised
-    // may have written some, and the Gauss-Newton launches already enqueued behind this kernel read them
-    if (tid == 0) __hip_atomic_store(&A.heads[b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (b == 0 || b + 1u == A.nb)
-      for (uint32_t s = (uint32_t)tid; s <= A.nseg; s += VB_THREADS) A.out_off[s] = 0u;
+    // and arrives: the offsets are zeroed by whichever bucket arrives last (vb_arrive), behind every bucket that ran to its end and
+    // wrote some — the Gauss-Newton launches already enqueued behind this kernel read them
+    if (tid == 0) {
+      __hip_atomic_store(&A.heads[b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      vb_arrive_last(A, vb_arrive(A));
+    }
     return;
   }
   const uint32_t seg = A.bseg[b];
@@ -292,7 +316,7 @@ __global__ __launch_bounds__(VB_THREADS) void k_vb_reduce(const VbArgs A) {
   const uint32_t key_bits = vb_bits(dimx * dimy * dimz - 1ull);   // each extent < 2^21
   const uint32_t total_bits = (key_bits ? key_bits : 1u) + pbits;
   if (total_bits > 63u) {   // (block-uniform) a box this sparse cannot be sorted on one word: give up
-    if (tid == 0) vb_fail(A, 3);
+    if (tid == 0) vb_fail_reduce(A, 3);
   }
   const uint32_t npass = total_bits > 63u ? 0u : (total_bits + 7u) / 8u;
   // sort word: voxel index inside the bucket's box << pos_bits | input position inside the segment — all distinct
@@ -434,21 +458,24 @@ __global__ __launch_bounds__(VB_THREADS) void k_vb_reduce(const VbArgs A) {
   VB_TS(12);
   uint32_t base;
   (void)block_excl_scan(part, s_scan, base);   // voxels emitted by all earlier buckets
-  if (tid == 0) {
-    if (P.bucket0 == b) A.out_off[seg] = base;
-    if (b + 1u == A.nb) A.out_off[A.nseg] = base + tot;
+  if (tid == 0) {   // (write-through: vb_arrive)
+    if (P.bucket0 == b) __hip_atomic_store(&A.out_off[seg], base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (b + 1u == A.nb) __hip_atomic_store(&A.out_off[A.nseg], base + tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   if (b + 1u == A.nb) {   // the last bucket has seen every other bucket's count, hence every segment's final box: PCL's pass-through test
+    int through = 0;
     for (uint32_t s = (uint32_t)tid; s < A.nseg; s += VB_THREADS) {
       int bb[6];
 #pragma unroll
       for (int k = 0; k < 6; k++) bb[k] = __hip_atomic_load(&A.box[6 * s + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (bb[3] >= bb[0]) {
         const long long dx = (long long)bb[3] - bb[0] + 1, dy = (long long)bb[4] - bb[1] + 1, dz = (long long)bb[5] - bb[2] + 1;
-        if (dx * dy > 2147483647LL || dx * dy * dz > 2147483647LL) vb_fail(A, 2);   // (each extent < 2^21)
+        if (dx * dy > 2147483647LL || dx * dy * dz > 2147483647LL) through = 1;   // (each extent < 2^21)
       }
     }
+    if (__syncthreads_or(through) && tid == 0) vb_fail_reduce(A, 2);   // (block-uniform branch; thread 0 raises it, and arrives behind it)
   }
+  const uint32_t arrived = tid == 0 ? vb_arrive(A) : 0u;
   uint32_t pos = base + ex;
 #pragma unroll
   for (int j = 0; j < 8; j++) {
@@ -485,6 +512,7 @@ __global__ __launch_bounds__(VB_THREADS) void k_vb_reduce(const VbArgs A) {
       pos++;
     }
   }
+  if (tid == 0) vb_arrive_last(A, arrived);
   VB_TS(13);
 }
 

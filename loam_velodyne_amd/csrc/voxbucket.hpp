@@ -51,6 +51,10 @@ class VoxBucket {
   uint32_t why() const;   // after failed(): bit mask of the give-up reasons (voxbucket.hip, vb_fail)
   void check();   // throws when a look-back wait timed out
   uint32_t last_buckets() const { return nb_; }
+  // the last run's plan, read-only (loamx_voxbucket_probe): one VbSeg per segment, per bucket its splitter and its point count
+  const VbSeg* d_segs() const { return segs_.p; }
+  const unsigned long long* d_lo() const { return lo_.p; }
+  const uint32_t* d_cnt() const { return cnt_.p; }
 
  private:
   hipStream_t st_ = nullptr;
@@ -58,7 +62,7 @@ class VoxBucket {
   DevBuf<unsigned long long> lo_;          // per bucket: the smallest voxel key it takes (the first bucket of a segment: 0)
   DevBuf<uint32_t> bseg_;                  // per bucket: its segment
   DevBuf<int> box_;                        // [nseg][6] voxel bounds of the stack points (k_vb_reduce; PCL's pass-through test)
-  DevBuf<uint32_t> cnt_, heads_, ctl_;     // per bucket: points, run heads + 1 once published; ctl: [0] fail epoch
+  DevBuf<uint32_t> cnt_, heads_, ctl_;     // per bucket: points, run heads + 1 once published; ctl: [0] fail epoch, [1] arrivals of k_vb_reduce
   DevBuf<uint32_t> elems_;                 // [buckets][VB_CAP] input positions inside the segment, in arrival order
   PinBuf<uint32_t> h_fail_;                // [0] fail epoch (host-visible copy), [1] timeout, [2..] epoch of the last run that met reason r
   uint32_t epoch_ = 0, nb_ = 0;

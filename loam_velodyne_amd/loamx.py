@@ -328,6 +328,36 @@ def index_probe(points, off, cell_edge=1.05, flags=0):
     return dict(desc=desc[:K], table=_index_table[:int(tlen[0])].copy(), sorted=out[:n])
 
 
+VOXBUCKET_SRC_POINTERS = 1
+VOXBUCKET_SEG = np.dtype([("bucket0", "<u4"), ("nbuckets", "<u4"), ("pos_bits", "<u4"), ("pad", "<u4")])
+
+
+def voxbucket_probe(points, seg_off, poses12, leaf_even, leaf_odd=None, flags=0):
+    """parity hook: the bucketed voxel grid of the stack clouds on its own (loamx_voxbucket_probe), on the process's one object ->
+    dict(stack, out (the rows out_off counts), out_off, gave_up, why, buckets, segs: VOXBUCKET_SEG records, lo, cnt).  poses12: one row
+    of 12 float32 words per sweep (two segments): rx ry rz tx ty tz and the sine / cosine words as the kernels are to use them."""
+    p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 4))
+    off = np.ascontiguousarray(seg_off, np.uint32)
+    poses = np.ascontiguousarray(np.asarray(poses12, np.float32).reshape(-1, 12))
+    n, nseg = len(p), len(off) - 1
+    assert len(poses) == (nseg + 1) // 2
+    m = np.diff(off.astype(np.int64))
+    cap = int(np.maximum(1, -(-m // 2048)).sum()) if nseg >= 1 and (m >= 0).all() else 1
+    stack = np.zeros((max(n, 1), 4), np.float32)
+    out = np.zeros((max(n, 1), 4), np.float32)
+    out_off = np.zeros(nseg + 1, np.uint32)
+    status = np.zeros(4, np.uint32)
+    segs = np.zeros(max(nseg, 1), VOXBUCKET_SEG)
+    lo = np.zeros(cap, np.uint64)
+    cnt = np.zeros(cap, np.uint32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(lib().loamx_voxbucket_probe(ptr(p), C.c_uint32(n), ptr(off), C.c_uint32(nseg), ptr(poses), C.c_float(leaf_even),
+                                       C.c_float(leaf_even if leaf_odd is None else leaf_odd), C.c_uint32(flags), ptr(stack), ptr(out),
+                                       ptr(out_off), ptr(status), ptr(segs), ptr(lo), ptr(cnt), C.c_uint32(cap)))
+    return dict(stack=stack[:n], out=out[:min(int(out_off[-1]), n)].copy(), out_off=out_off, gave_up=int(status[0]), why=int(status[1]),
+                buckets=int(status[2]), segs=segs[:nseg], lo=lo, cnt=cnt)
+
+
 class TransformMaintenance:
     """loamx_tm_*: BasicTransformMaintenance (host arithmetic, no device)."""
 

@@ -9,95 +9,12 @@ pcl::VoxelGrid restatement bit for bit.  What the kernels' correctness argument 
   * every give-up condition is detected: a coordinate beyond +-2^20 voxels, more than VB_CAP points in a bucket, a bucket box that needs
     more than 63 sort bits, PCL's pass-through case (segment box beyond INT_MAX voxels).
 
-The device itself is compared with the oracle in tests/test_gpu_voxbucket.py; this file pins the ALGORITHM."""
+The device itself is compared with the oracle in tests/test_gpu_voxbucket.py and, kernel by kernel at edge shapes, in
+tests/test_gpu_voxbucket_probe.py; this file pins the ALGORITHM, which tests/voxbucket_model.py states."""
 import numpy as np
 import pytest
 
-VB_CAP, VB_T, VB_SAMPLE, VB_OFF = 4096, 2048, 512, 1 << 20
-
-
-class GiveUp(Exception):
-    def __init__(self, reason):
-        super().__init__(f"give-up reason {reason}")
-        self.reason = reason
-
-
-def _bits(v):
-    return int(v).bit_length()
-
-
-def _voxels(pts, leaf):
-    """floor(v * inverse leaf) in float arithmetic, as pcl::VoxelGrid and vb_voxel() form it; reason 0 beyond +-2^20 or not finite"""
-    inv = np.float32(1.0) / np.float32(leaf)
-    f = np.floor(pts[:, :3] * inv)
-    if not np.all(np.abs(f) < np.float32(VB_OFF)):   # (also catches NaN / inf)
-        raise GiveUp(0)
-    return f.astype(np.int64)
-
-
-def _key(v):
-    """vb_key(): (iz, iy, ix) lexicographically, 21 bits each"""
-    return [((int(z) + VB_OFF) << 42) | ((int(y) + VB_OFF) << 21) | (int(x) + VB_OFF) for x, y, z in v]
-
-
-def plan_splitters(pts, leaf):
-    """k_vb_plan: ceil(n / VB_T) buckets; VB_SAMPLE evenly spaced points ranked by voxel key, every (m / buckets)-th one a splitter"""
-    n = len(pts)
-    nb = max(1, -(-n // VB_T))
-    if nb > VB_SAMPLE:
-        raise GiveUp(1)
-    if nb == 1:
-        return [0]
-    m = min(n, VB_SAMPLE)
-    sample = pts[[(t * n) // m for t in range(m)]]
-    keys = sorted(_key(_voxels(sample, leaf)))
-    return [0] + [keys[(k * m) // nb] for k in range(1, nb)]
-
-
-def bucketed_voxel_grid(pts, leaf, splitters=None, rng=None):
-    """one segment through k_vb_plan / k_vb_stack / k_vb_reduce; rng: shuffles the arrival order inside every bucket"""
-    pts = np.ascontiguousarray(pts, np.float32)
-    n = len(pts)
-    if n == 0:
-        return np.zeros((0, 4), np.float32)
-    lo = plan_splitters(pts, leaf) if splitters is None else list(splitters)
-    assert lo[0] == 0 and all(a <= b for a, b in zip(lo, lo[1:]))
-    v = _voxels(pts, leaf)                                   # k_vb_stack: exact voxel of every point (reason 0)
-    keys = _key(v)
-    lo_arr = np.array(lo, dtype=object)
-    # bucket = the last splitter <= key (the binary search of k_vb_stack: "if (s[mid] <= key) lo = mid; else hi = mid")
-    bucket = np.array([int(np.searchsorted(lo_arr, k, side="right")) - 1 for k in keys])
-    pos_bits = max(1, _bits(n - 1))
-    # PCL's own pass-through test on the segment's box (the last bucket does it on the device, reason 2)
-    dims = v.max(0) - v.min(0) + 1
-    if int(dims[0]) * int(dims[1]) * int(dims[2]) > 2147483647:
-        raise GiveUp(2)
-    out = []
-    for b in range(len(lo)):
-        el = np.flatnonzero(bucket == b)                     # input positions, in arrival order (any)
-        if len(el) > VB_CAP:
-            raise GiveUp(5)
-        if rng is not None:
-            el = rng.permutation(el)
-        if not len(el):
-            continue
-        vb = v[el]
-        b0 = vb.min(0)
-        dx, dy, dz = (int(d) for d in (vb.max(0) - b0 + 1))
-        key_bits = _bits(dx * dy * dz - 1)
-        if max(key_bits, 1) + pos_bits > 63:
-            raise GiveUp(3)
-        lin = [(int(x) - int(b0[0])) + dx * ((int(y) - int(b0[1])) + dy * (int(z) - int(b0[2]))) for x, y, z in vb]
-        words = sorted((l << pos_bits) | int(p) for l, p in zip(lin, el))   # the LSD radix sort's result: ascending words, all distinct
-        s = 0
-        while s < len(words):                                # run heads -> one mean per voxel, summed in sorted = input order
-            e, acc = s, np.zeros(4, np.float32)
-            while e < len(words) and words[e] >> pos_bits == words[s] >> pos_bits:
-                acc = (acc + pts[words[e] & ((1 << pos_bits) - 1)]).astype(np.float32)
-                e += 1
-            out.append(acc / np.float32(e - s))
-            s = e
-    return np.array(out, np.float32).reshape(-1, 4)
+from voxbucket_model import VB_CAP, GiveUp, _key, _voxels, bucketed_voxel_grid, plan_splitters
 
 
 def _sweep_like(rng, n, extent):
