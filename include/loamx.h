@@ -804,6 +804,81 @@ int loamx_densemap_download_surfels(loamx_densemap* h, loamx_surfel* out, uint64
 int loamx_densemap_save_pcd_surfels(loamx_densemap* h, const char* path, int axes, const loamx_densemap_surfel_config* cfg,
                                     const loamx_densemap_static_rule* rule);
 
+/* Frozen snapshot and alignment (optional: a handle that never freezes behaves, allocates and exports as described above).  The
+ * surfels are what a point-to-plane registration needs; a frozen copy of them on the device turns the map into something a cloud
+ * can be aligned to: a loop-closure candidate verified as a 6-DOF constraint, or a sweep with a rough pose re-localised.
+ *
+ * loamx_densemap_freeze needs moments (a non-NULL rule also carving; otherwise LOAMX_E_INVALID).  It waits for the adds as
+ * download_surfels does and computes the surfels on the host exactly as download_surfels does in axes 0 with the same cfg / rule
+ * (seconds on a map of millions of voxels: freeze every N sweeps, not every sweep).  The voxels that have a surfel (a non-zero normal)
+ * and that the rule does not call dynamic go into a second open-addressing table on the device, independent of the map's: the key is
+ * the voxel's key in the map's table, the payload the six f32 mean x, y, z, normal x, y, z with the bytes download_surfels gives.
+ * One entry is 32 bytes; the table has the smallest power of two of slots that is >= 2 * count and >= 1024.  A second freeze replaces
+ * the first; reset and destroy drop the snapshot; adds, growth, prune and enable_* never touch it: the snapshot is what the map looked
+ * like when it was frozen (a loop closure must not match against the drifted recent sweeps).  *n_surfels (may be NULL) = entries.
+ *
+ * loamx_densemap_align_step: one linearisation of the point-to-plane problem about the pose (R, t) with centre c, rtc = R row-major,
+ * t, c.  Per point p, independently, in f32, no fused multiply-add, in this order:
+ *   d = p - c per component;  a_k = (R_k0*d_x + R_k1*d_y) + R_k2*d_z;  p' = a + t.  (With c = t_in, a is the lever arm about the sensor.)
+ *   If not (|a_k| < 1024 for every k): the point counts as FAR (NaN too) and is done.
+ *   i_k = floorf(p'_k * inv), inv = 1.0f / leaf as in the insert.  If not (|i_k| < 2^20 for every k): OUTSIDE, done.
+ *   Candidate cells: neighbourhood 0: the cell (i_x, i_y, i_z); 1: the 27 cells (i_x+dx, i_y+dy, i_z+dz), dz the outer loop, then
+ *   dy, then dx, each running -1, 0, 1; a cell with an index outside the key range is skipped.  Any other value: LOAMX_E_INVALID.
+ *   For each candidate found in the snapshot: e = p' - mean, d2 = (e_x*e_x + e_y*e_y) + e_z*e_z.  The smallest d2 wins, a tie goes
+ *   to the earlier candidate (strict <).  No candidate found: UNMATCHED, done.
+ *   r = (n_x*e_x + n_y*e_y) + n_z*e_z.  If not (fabsf(r) <= max_residual): REJECTED, done.  Otherwise MATCHED.
+ *   (max_residual outside (0, 16]: LOAMX_E_INVALID.)
+ *   J = (a_y*n_z - a_z*n_y, a_z*n_x - a_x*n_z, a_x*n_y - a_y*n_x, n_x, n_y, n_z): d r / d (w, v) for R <- exp([w]) R, t <- t + v.
+ *   A matched point adds 28 integers to sums: the 21 products J_k*J_l, k <= l, row-major upper triangle, each as
+ *   (int64)rintf(prod * 65536.0f);  the six J_k*r as (int64)rintf(prod * 16777216.0f);  r*r as (int64)rintf(prod * 16777216.0f).
+ *   Every product is one f32 multiply and the scaling by a power of two is exact.  Bounds: |a_k| < 2^10 and |n| = 1 give
+ *   |J_k| < 2^11, |r| <= 2^4, so a term is at most 2^38 (J J), 2^39 (J r), 2^32 (r r): the 64-bit sums are exact for clouds below
+ *   2^20 points (and far beyond).
+ * counts = FAR, OUTSIDE, UNMATCHED, REJECTED, MATCHED; they add up to the cloud's count.  sums and counts are integer sums: they
+ * depend on neither the thread schedule nor the order of the points.  The call blocks until the 33 words are back.
+ *
+ * loamx_densemap_align_solve (host only): in double, H = sums[0..21) / 2^16 (symmetric 6x6), g = sums[21..27) / 2^24; the
+ * eigen-decomposition of H (cyclic Jacobi); directions with l <= degenerate_ratio * l_max (or l <= 0) are dropped from the update
+ * and counted in *dropped (LOAM's degeneracy handling);  x = - sum over the kept directions of v (v . g) / l.  degenerate_ratio
+ * outside [0, 1): LOAMX_E_INVALID.
+ *
+ * loamx_densemap_align: Gauss-Newton over align_step and align_solve from pose_in (row-major 3x4, map <- cloud: x -> R x + t').  The
+ * host keeps R, t in double, t = R c + t'_in with c = centre (NULL: 0), rounds them to f32 for each step, updates
+ * R <- exp([x_0..2]) R (Rodrigues), t <- t + x_3..5, and ends as converged (status 0) when |x_0..2| < eps_rot and |x_3..5| < eps_trans.
+ * A step with fewer than min_matched matches ends the loop with status 2 and the pose of the last good iteration (the input pose
+ * when it is the first).  pose reports t' = t - R c.  The loop BLOCKS the caller: one launch and one small readback per iteration.
+ * The from_* forms read the registered cloud of a mapper / a pipeline slot where it lies (as add_from_map / add_from_pipeline do),
+ * behind an event on its stream, with its origin as the centre; pose_in NULL: identity.  LOAMX_SKIPPED when there is no cloud,
+ * LOAMX_E_INVALID on another device.  Without a snapshot align_step and the three align forms answer LOAMX_E_INVALID. */
+int loamx_densemap_freeze(loamx_densemap* h, const loamx_densemap_surfel_config* cfg, const loamx_densemap_static_rule* rule,
+                          uint64_t* n_surfels);
+int loamx_densemap_frozen_size(loamx_densemap* h, uint64_t* n_surfels);   /* 0 when nothing is frozen */
+int loamx_densemap_align_step(loamx_densemap* h, const loamx_cloud* points, const float rtc[15], uint32_t neighbourhood,
+                              float max_residual, int64_t sums[28], uint64_t counts[5]);
+typedef struct loamx_densemap_align_config {
+  uint32_t max_iterations;   /* 1..1000 (default 20) */
+  uint32_t neighbourhood;    /* 0 or 1 (default 1) */
+  float max_residual;        /* metres, (0, 16]; 0 = the leaf (default 0) */
+  uint32_t min_matched;      /* default 50 */
+  float eps_rot, eps_trans;  /* default 1e-5 rad, 1e-5 m */
+  float degenerate_ratio;    /* [0, 1) (default 1e-4) */
+} loamx_densemap_align_config;
+typedef struct loamx_densemap_align_result {
+  double pose[12];           /* row-major 3x4, map <- cloud: x -> R x + t' */
+  uint32_t iterations, degenerate_dims;   /* steps run; directions dropped by the last solve */
+  int status;                /* 0 converged, 1 max_iterations reached, 2 fewer than min_matched matches */
+  double rms;                /* sqrt(sum r^2 / matched) of the last step (0 without a match) */
+  uint64_t counts[5];        /* of the last step */
+} loamx_densemap_align_result;
+void loamx_densemap_align_default_config(loamx_densemap_align_config* cfg);   /* host only */
+int loamx_densemap_align_solve(const int64_t sums[28], float degenerate_ratio, double x[6], uint32_t* dropped);   /* host only */
+int loamx_densemap_align(loamx_densemap* h, const loamx_cloud* points, const double pose_in[12], const float centre[3] /* NULL: 0 */,
+                         const loamx_densemap_align_config* cfg /* NULL: the defaults */, loamx_densemap_align_result* out);
+int loamx_densemap_align_from_map(loamx_densemap* h, loamx_map* m, const double pose_in[12] /* NULL: identity */,
+                                  const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out);
+int loamx_densemap_align_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot, const double pose_in[12],
+                                       const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Place recognition (not in the reference): a database of rotation-invariant sweep descriptors in device memory (Scan Context: a
  * ring x sector polar grid of maximum heights around the sensor) and an exhaustive search for the earlier entries that look like a

@@ -12,6 +12,9 @@
 // Moments (loamx_densemap_enable_moments): nine more 64-bit words per slot in an array of their own, the sums of the products of the
 // offsets and of the fixed-point vectors from the origin.  The insert adds them with the voxel's other sums; the surfel of a voxel
 // (covariance, normal, curvature) is computed on the host at export.
+//
+// Freeze (loamx_densemap_freeze): the surfels of that export, computed once, go into a second table on the device that the alignment
+// of densemap_align.hip reads; the table above never learns of it.
 #include "densemap.hpp"
 #include "host_math.h"
 #include "pinned_copy.hpp"
@@ -42,10 +45,6 @@ struct DmCarve {
 // mom: 9 words per slot beside the table, [9 * slot + k]: Mxx, Myy, Mzz, Mxy, Mxz, Myz, Vx, Vy, Vz (include/loamx.h)
 constexpr int DM_MOM_WORDS = 9;
 constexpr int DM_VBITS = 26;   // the combine packs a lane's w_a above its q_a: 64 lanes' q sum stays below 2^26
-
-__device__ inline unsigned long long dm_hash(unsigned long long key, uint32_t shift) {
-  return (key * 0x9E3779B97F4A7C15ull) >> shift;
-}
 
 // the slot of `key` (claimed when absent); won: this call claimed it.  false: the table is full (cannot happen at a load <= 1/2)
 __device__ inline bool dm_find_or_claim(unsigned long long* __restrict__ keys, uint32_t mask, uint32_t shift, unsigned long long key,
@@ -648,6 +647,32 @@ class DenseMap {
     }
   }
 
+  // the snapshot the alignment reads (densemap_align.hip): the voxels that have a surfel and that the rule does not call dynamic, each
+  // under its key of the table, with the six f32 of its record as surfels() gives them in axes 0.  Replaces an earlier snapshot
+  uint64_t freeze(const loamx_densemap_surfel_config& sc, const loamx_densemap_static_rule* rule) {
+    Snapshot S;
+    snapshot(S, true);
+    std::vector<unsigned long long> keys;
+    std::vector<float> rec;
+    const double leaf = (double)cfg.leaf;
+    for (size_t r = 0; r < S.idx.size(); r++) {
+      const size_t j = S.idx[r];
+      if (rule && dm_dynamic(*rule, S.v[4 * j], S.miss[j])) continue;
+      long long ia[3];
+      loamx_surfel s;
+      dm_key_indices(S.k[j], ia);
+      dm_surfel(leaf, ia, &S.v[4 * j], &S.mom[DM_MOM_WORDS * j], sc, 0, s);
+      if (s.normal_x == 0.f && s.normal_y == 0.f && s.normal_z == 0.f) continue;
+      keys.push_back(S.k[j]);
+      const float six[6] = {s.x, s.y, s.z, s.normal_x, s.normal_y, s.normal_z};
+      rec.insert(rec.end(), six, six + 6);
+    }
+    frozen.build(keys.data(), rec.data(), keys.size(), own_);
+    return frozen.size();
+  }
+  DmFrozen frozen;
+  hipStream_t own_stream() const { return own_; }
+
   // the miss word per voxel in the order of records()
   void misses(std::vector<uint32_t>& out) {
     Snapshot S;
@@ -704,6 +729,7 @@ class DenseMap {
     wait_adds();
     clear(own_);
     LX_HIP(hipStreamSynchronize(own_));
+    frozen.drop();
     occ_ = pend_ = pend_snap_ = 0;
     offered_ = drop_range_ = drop_key_ = 0;
     for (uint64_t& c : carve_ctr_) c = 0;
@@ -1215,6 +1241,32 @@ int loamx_densemap_save_pcd_surfels(loamx_densemap* h, const char* path, int axe
   });
 }
 
+int loamx_densemap_freeze(loamx_densemap* h, const loamx_densemap_surfel_config* cfg, const loamx_densemap_static_rule* rule,
+                          uint64_t* n_surfels) {
+  return guard([&]() {
+    LX_REQUIRE(h, "NULL handle");
+    const loamx_densemap_surfel_config c = checked_surfel_config(cfg);
+    LX_REQUIRE_MOMENTS(h);
+    uint64_t n = 0;
+    if (rule) {
+      const loamx_densemap_static_rule r = checked_rule(rule);
+      LX_REQUIRE_CARVING(h);
+      n = h->d.freeze(c, &r);
+    } else {
+      n = h->d.freeze(c, nullptr);
+    }
+    if (n_surfels) *n_surfels = n;
+    return LOAMX_OK;
+  });
+}
+int loamx_densemap_frozen_size(loamx_densemap* h, uint64_t* n_surfels) {
+  return guard([&]() {
+    LX_REQUIRE(h && n_surfels, "NULL argument");
+    *n_surfels = h->d.frozen.valid() ? h->d.frozen.size() : 0;
+    return LOAMX_OK;
+  });
+}
+
 // bench / test hooks (not in include/loamx.h): the in-wave combining of equal keys on or off, and the number of rehashes so far
 int loamx_densemap_set_combine(loamx_densemap* h, int on) {
   return guard([&]() { LX_REQUIRE(h, "NULL handle"); h->d.combine = on != 0; return LOAMX_OK; });
@@ -1222,3 +1274,7 @@ int loamx_densemap_set_combine(loamx_densemap* h, int on) {
 uint64_t loamx_densemap_rehashes(loamx_densemap* h) { return h ? h->d.rehashes : 0; }
 
 }  // extern "C"
+
+DmFrozen& loamx_densemap_frozen(loamx_densemap* h) { return h->d.frozen; }
+hipStream_t loamx_densemap_own_stream(loamx_densemap* h) { return h->d.own_stream(); }
+const loamx_densemap_config& loamx_densemap_cfg(loamx_densemap* h) { return h->d.cfg; }

@@ -23,7 +23,54 @@ struct DenseSource {
   bool has_cloud = false;    // false: the last call produced no registered cloud (the add is LOAMX_SKIPPED)
 };
 
+// the home slot of a key in a table of 2^(64 - shift) slots (the map's table and the frozen snapshot's)
+__device__ inline unsigned long long dm_hash(unsigned long long key, uint32_t shift) {
+  return (key * 0x9E3779B97F4A7C15ull) >> shift;
+}
+
+// Frozen surfel snapshot (include/loamx.h, loamx_densemap_freeze / loamx_densemap_align_*; densemap_align.hip): an open-addressing
+// table of its own, one 32-byte entry per slot — the voxel's key and the six f32 of its surfel record — so that a probe that hits
+// reads one 32-byte sector.  Built once per freeze, read-only afterwards; the live map never touches it.
+struct DmFrozenEntry {
+  unsigned long long key;   // DM_EMPTY: a free slot
+  float mean[3], normal[3];
+};
+static_assert(sizeof(DmFrozenEntry) == 32, "one entry, one 32-byte sector");
+
+class DmFrozen {
+ public:
+  DmFrozen() = default;
+  DmFrozen(const DmFrozen&) = delete;
+  DmFrozen& operator=(const DmFrozen&) = delete;
+  ~DmFrozen() { drop(); }
+  bool valid() const { return tab_ != nullptr; }
+  uint64_t size() const { return count_; }
+  uint32_t slots() const { return slots_; }
+  void drop();
+  // replaces the snapshot by the n voxels (keys[i], rec[6 * i ..]); blocks until the table stands
+  void build(const unsigned long long* keys, const float* rec, size_t n, hipStream_t st);
+  // the cloud of the steps that follow, from the host (staged) or where it lies on the device
+  const float4* stage(const loamx_cloud* c, hipStream_t st);
+  // one linearisation (include/loamx.h, loamx_densemap_align_step); blocks until the 33 words are back
+  void step(const float4* pts, uint32_t n, const float rtc[15], float inv, uint32_t neighbourhood, float max_residual, hipStream_t st,
+            int64_t sums[28], uint64_t counts[5]);
+
+ private:
+  DmFrozenEntry* tab_ = nullptr;
+  uint32_t slots_ = 0;
+  uint64_t count_ = 0;
+  DevBuf<unsigned long long> acc_;
+  PinBuf<uint32_t> h_acc_;
+  PinBuf<float4> h_pts_;
+  DevBuf<float4> d_pts_;
+};
+
 }  // namespace loamx
+
+// internal accessors of the dense map's handle for densemap_align.hip: its snapshot, its own stream and its configuration
+loamx::DmFrozen& loamx_densemap_frozen(loamx_densemap* h);
+hipStream_t loamx_densemap_own_stream(loamx_densemap* h);
+const loamx_densemap_config& loamx_densemap_cfg(loamx_densemap* h);
 
 // internal accessors (not exported in include/loamx.h): the registered cloud of the mapper's last process() / process_linked(), and of
 // the slot-th stream registered in the pipeline's last step (LOAMX_E_INVALID for a slot beyond them)

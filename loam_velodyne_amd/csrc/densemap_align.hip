@@ -1,0 +1,465 @@
+// Alignment of a cloud to the dense map's frozen surfel snapshot (include/loamx.h, loamx_densemap_freeze / loamx_densemap_align_*).
+//
+// The snapshot (densemap.hpp, DmFrozen) is an open-addressing table of 32-byte entries: key, mean, normal.  k_dm_freeze_insert fills it
+// once per freeze; after that it is only read.
+//
+// One Gauss-Newton linearisation is one launch of k_dm_align_step, one point per thread: transform, the point's cell, one or 27
+// dependent random probes of the table (the other waves of the CU hide their latency: 68 VGPRs, seven waves per SIMD, no scratch),
+// the point-to-plane residual and the 28 fixed-point terms of J^T J, J^T r and r^2.  All 33 words are integers: they are summed in the wave (shuffles), then in the block
+// (LDS), and one lane per word adds the block's sum to the global accumulator, so the result depends on no order.  The words come back
+// through pinned memory; the 6x6 solve and the pose update are the host's, in double.
+#include "densemap.hpp"
+#include "pinned_copy.hpp"
+
+namespace loamx {
+
+constexpr int DM_ALIGN_SUMS = 28, DM_ALIGN_COUNTS = 5, DM_ALIGN_WORDS = DM_ALIGN_SUMS + DM_ALIGN_COUNTS;
+constexpr float DM_ALIGN_FAR = 1024.0f;          // |a_k| must stay below this
+constexpr float DM_ALIGN_HSCALE = 65536.0f;      // 2^16: J_k * J_l
+constexpr float DM_ALIGN_GSCALE = 16777216.0f;   // 2^24: J_k * r and r * r
+
+struct DmAlign {
+  float R[9], t[3], c[3];
+  float inv, max_residual;
+  int nb;
+};
+
+// keys are unique: the first free slot of the probe sequence is claimed and its payload written (read by later launches only)
+__global__ __launch_bounds__(256) void k_dm_freeze_insert(const unsigned long long* __restrict__ keys, const float* __restrict__ rec, uint32_t n,
+                                                          DmFrozenEntry* __restrict__ tab, uint32_t mask, uint32_t shift,
+                                                          unsigned long long* __restrict__ overflow) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long key = keys[i];
+  uint32_t h = (uint32_t)dm_hash(key, shift);
+  for (uint32_t probe = 0; probe <= mask; probe++) {
+    if (atomicCAS(&tab[h].key, DM_EMPTY, key) == DM_EMPTY) {
+      const float* r = rec + 6ull * i;
+      tab[h].mean[0] = r[0]; tab[h].mean[1] = r[1]; tab[h].mean[2] = r[2];
+      tab[h].normal[0] = r[3]; tab[h].normal[1] = r[4]; tab[h].normal[2] = r[5];
+      return;
+    }
+    h = (h + 1u) & mask;
+  }
+  *overflow = 1ull;   // (cannot happen at a load <= 1/2)
+}
+
+__device__ inline unsigned long long dm_wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, 64);
+    v += ((unsigned long long)hi << 32) | lo;
+  }
+  return v;
+}
+
+// dm_find's loop on the snapshot's entries: the first 16 bytes of an entry (key, mean x, y) in one load.  false: the key is absent
+__device__ inline bool dm_frozen_find(const DmFrozenEntry* tab, uint32_t mask, uint32_t shift, unsigned long long key, uint32_t& slot,
+                                      float& mx, float& my) {
+  uint32_t h = (uint32_t)dm_hash(key, shift);
+  for (uint32_t probe = 0; probe <= mask; probe++) {
+    const uint4 w = *(const uint4*)(tab + h);
+    const unsigned long long cur = ((unsigned long long)w.y << 32) | w.x;
+    if (cur == key) { slot = h; mx = __uint_as_float(w.z); my = __uint_as_float(w.w); return true; }
+    if (cur == DM_EMPTY) return false;
+    h = (h + 1u) & mask;
+  }
+  return false;
+}
+
+// acc: [0, 28) the sums (two's complement), [28, 33) far, outside, unmatched, rejected, matched.  f32, no fused multiply-add (the
+// file is built without contraction): the expressions are those of include/loamx.h, in its order
+__global__ __launch_bounds__(256) void k_dm_align_step(const float4* __restrict__ pts, uint32_t n, DmAlign A, const DmFrozenEntry* __restrict__ tab,
+                                                       uint32_t mask, uint32_t shift, unsigned long long* __restrict__ acc) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
+  int cls = -1;   // the counter this point goes to (-1: no point)
+  long long s[DM_ALIGN_SUMS];
+#pragma unroll
+  for (int k = 0; k < DM_ALIGN_SUMS; k++) s[k] = 0ll;
+  if (i < n) {
+    const float4 p = pts[i];
+    const float dx = p.x - A.c[0], dy = p.y - A.c[1], dz = p.z - A.c[2];
+    float a[3], pp[3], fi[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      a[k] = (A.R[3 * k] * dx + A.R[3 * k + 1] * dy) + A.R[3 * k + 2] * dz;
+      pp[k] = a[k] + A.t[k];
+      fi[k] = floorf(pp[k] * A.inv);
+    }
+    if (!(fabsf(a[0]) < DM_ALIGN_FAR && fabsf(a[1]) < DM_ALIGN_FAR && fabsf(a[2]) < DM_ALIGN_FAR)) {
+      cls = 0;   // (NaN too)
+    } else if (!(fabsf(fi[0]) < DM_IMAX && fabsf(fi[1]) < DM_IMAX && fabsf(fi[2]) < DM_IMAX)) {
+      cls = 1;
+    } else {
+      const int ic[3] = {(int)fi[0], (int)fi[1], (int)fi[2]};
+      const int lim = 1 << DM_QBITS;
+      bool found = false;
+      float best = 0.f, e[3] = {0.f, 0.f, 0.f};
+      uint32_t at = 0u;
+      for (int oz = -A.nb; oz <= A.nb; oz++)
+        for (int oy = -A.nb; oy <= A.nb; oy++)
+          for (int ox = -A.nb; ox <= A.nb; ox++) {
+            const int cx = ic[0] + ox, cy = ic[1] + oy, cz = ic[2] + oz;
+            if (cx <= -lim || cx >= lim || cy <= -lim || cy >= lim || cz <= -lim || cz >= lim) continue;   // outside the key range
+            const unsigned long long key = (unsigned long long)(uint32_t)(cx + lim) | ((unsigned long long)(uint32_t)(cy + lim) << DM_KBITS) |
+                                           ((unsigned long long)(uint32_t)(cz + lim) << (2 * DM_KBITS));
+            uint32_t slot = 0u;
+            float mx = 0.f, my = 0.f;
+            if (!dm_frozen_find(tab, mask, shift, key, slot, mx, my)) continue;
+            const float ex = pp[0] - mx, ey = pp[1] - my, ez = pp[2] - tab[slot].mean[2];
+            const float d2 = (ex * ex + ey * ey) + ez * ez;
+            if (!found || d2 < best) {
+              found = true; best = d2; at = slot;
+              e[0] = ex; e[1] = ey; e[2] = ez;
+            }
+          }
+      if (!found) {
+        cls = 2;
+      } else {
+        const float4 w = *(const float4*)&tab[at].mean[2];   // mean z and the normal: the entry's second 16 bytes
+        const float nx = w.y, ny = w.z, nz = w.w;
+        const float r = (nx * e[0] + ny * e[1]) + nz * e[2];
+        if (!(fabsf(r) <= A.max_residual)) {
+          cls = 3;
+        } else {
+          cls = 4;
+          const float J[6] = {a[1] * nz - a[2] * ny, a[2] * nx - a[0] * nz, a[0] * ny - a[1] * nx, nx, ny, nz};
+          int w_ = 0;
+#pragma unroll
+          for (int k = 0; k < 6; k++)
+#pragma unroll
+            for (int l = k; l < 6; l++) s[w_++] = (long long)rintf((J[k] * J[l]) * DM_ALIGN_HSCALE);
+#pragma unroll
+          for (int k = 0; k < 6; k++) s[21 + k] = (long long)rintf((J[k] * r) * DM_ALIGN_GSCALE);
+          s[27] = (long long)rintf((r * r) * DM_ALIGN_GSCALE);
+        }
+      }
+    }
+  }
+  __shared__ unsigned long long part[4][DM_ALIGN_WORDS];
+  const bool any_matched = __ballot(cls == 4) != 0ull;   // (wave-uniform: a wave without a match has nothing but zeros to sum)
+#pragma unroll
+  for (int k = 0; k < DM_ALIGN_SUMS; k++) {
+    const unsigned long long v = any_matched ? dm_wave_sum_u64((unsigned long long)s[k]) : 0ull;
+    if (lane == 0) part[wid][k] = v;
+  }
+#pragma unroll
+  for (int k = 0; k < DM_ALIGN_COUNTS; k++) {
+    const unsigned long long m = __ballot(cls == k);
+    if (lane == 0) part[wid][DM_ALIGN_SUMS + k] = (unsigned long long)__popcll(m);
+  }
+  __syncthreads();
+  if (threadIdx.x < (uint32_t)DM_ALIGN_WORDS) {
+    const unsigned long long v = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
+    if (v) atomicAdd(&acc[threadIdx.x], v);   // (integer, modulo 2^64: the order does not matter)
+  }
+}
+
+static uint32_t log2u(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }
+
+void DmFrozen::drop() {
+  if (tab_) (void)hipFree(tab_);
+  tab_ = nullptr;
+  slots_ = 0;
+  count_ = 0;
+}
+
+void DmFrozen::build(const unsigned long long* keys, const float* rec, size_t n, hipStream_t st) {
+  uint64_t slots = 1024;
+  while (slots < 2 * (uint64_t)n) slots *= 2;
+  LX_REQUIRE(slots <= (1ull << 31), "dense map: more surfels than the snapshot can index");
+  DmFrozenEntry* tab = nullptr;
+  LX_HIP(hipMalloc((void**)&tab, sizeof(DmFrozenEntry) * slots));
+  try {
+    DevBuf<unsigned long long> d_keys, d_flag;
+    DevBuf<float> d_rec;
+    d_flag.reserve(1);
+    unsigned long long flag = 0ull;
+    LX_HIP(hipMemsetAsync(tab, 0xff, sizeof(DmFrozenEntry) * slots, st));   // (every key EMPTY; a free slot's payload is never read)
+    LX_HIP(hipMemsetAsync(d_flag.p, 0, sizeof(unsigned long long), st));
+    if (n) {
+      d_keys.reserve(n);
+      d_rec.reserve(6 * n);
+      LX_HIP(hipMemcpyAsync(d_keys.p, keys, sizeof(unsigned long long) * n, hipMemcpyHostToDevice, st));
+      LX_HIP(hipMemcpyAsync(d_rec.p, rec, sizeof(float) * 6 * n, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_dm_freeze_insert, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, d_keys.p, d_rec.p, (uint32_t)n, tab,
+                         (uint32_t)(slots - 1), 64u - log2u(slots), d_flag.p);
+      LX_HIP(hipGetLastError());
+    }
+    LX_HIP(hipMemcpyAsync(&flag, d_flag.p, sizeof(flag), hipMemcpyDeviceToHost, st));
+    LX_HIP(hipStreamSynchronize(st));
+    LX_REQUIRE(flag == 0ull, "dense map: snapshot table overflow");
+  } catch (...) {
+    (void)hipFree(tab);
+    throw;
+  }
+  drop();
+  tab_ = tab;
+  slots_ = (uint32_t)slots;
+  count_ = n;
+}
+
+const float4* DmFrozen::stage(const loamx_cloud* c, hipStream_t st) {
+  check_cloud(c, false);
+  const uint32_t n = c->count;
+  h_pts_.reserve((size_t)n + 1);
+  d_pts_.reserve((size_t)n + 1);
+  if (n) {
+    pack_cloud(c, h_pts_.p);
+    fetch_from_pinned(d_pts_.p, h_pts_.p, n, st);
+  }
+  return d_pts_.p;
+}
+
+void DmFrozen::step(const float4* pts, uint32_t n, const float rtc[15], float inv, uint32_t neighbourhood, float max_residual, hipStream_t st,
+                    int64_t sums[28], uint64_t counts[5]) {
+  LX_REQUIRE(valid(), "nothing is frozen (loamx_densemap_freeze)");
+  acc_.reserve(DM_ALIGN_WORDS);
+  h_acc_.reserve(2 * DM_ALIGN_WORDS);
+  LX_HIP(hipMemsetAsync(acc_.p, 0, sizeof(unsigned long long) * DM_ALIGN_WORDS, st));
+  if (n) {
+    DmAlign A;
+    for (int k = 0; k < 9; k++) A.R[k] = rtc[k];
+    for (int k = 0; k < 3; k++) { A.t[k] = rtc[9 + k]; A.c[k] = rtc[12 + k]; }
+    A.inv = inv;
+    A.max_residual = max_residual;
+    A.nb = (int)neighbourhood;
+    hipLaunchKernelGGL(k_dm_align_step, dim3((n + 255u) / 256u), dim3(256), 0, st, pts, n, A, tab_, slots_ - 1u, 64u - log2u(slots_), acc_.p);
+    LX_HIP(hipGetLastError());
+  }
+  store_to_pinned_u32(h_acc_.p, (const uint32_t*)acc_.p, 2 * DM_ALIGN_WORDS, st);
+  LX_HIP(hipStreamSynchronize(st));
+  const unsigned long long* w = (const unsigned long long*)h_acc_.p;
+  for (int k = 0; k < DM_ALIGN_SUMS; k++) sums[k] = (int64_t)w[k];
+  for (int k = 0; k < DM_ALIGN_COUNTS; k++) counts[k] = w[DM_ALIGN_SUMS + k];
+}
+
+// Eigen-decomposition of a symmetric 6x6 matrix in double by cyclic Jacobi rotations (host_math.h's jacobi_eig3 at n = 6): a is
+// overwritten, its diagonal becomes the eigenvalues (unsorted), column k of v the unit eigenvector of a[k][k].  An off-diagonal
+// element that is exactly 0 is left alone, so a coordinate the matrix does not touch stays an exact unit axis
+static void jacobi_eig6(double a[6][6], double v[6][6]) {
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 6; j++) v[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 64; sweep++) {
+    double off = 0.0, diag = 0.0;
+    for (int i = 0; i < 6; i++) {
+      diag += std::fabs(a[i][i]);
+      for (int j = i + 1; j < 6; j++) off += std::fabs(a[i][j]);
+    }
+    if (off == 0.0 || off <= 1e-300 + diag * 1e-22) break;
+    for (int p = 0; p < 5; p++)
+      for (int q = p + 1; q < 6; q++) {
+        if (a[p][q] == 0.0) continue;
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c, apq = a[p][q];
+        a[p][p] -= t * apq;
+        a[q][q] += t * apq;
+        a[p][q] = a[q][p] = 0.0;
+        for (int r = 0; r < 6; r++) {
+          if (r == p || r == q) continue;
+          const double arp = a[r][p], arq = a[r][q];
+          a[r][p] = a[p][r] = c * arp - s * arq;
+          a[r][q] = a[q][r] = s * arp + c * arq;
+        }
+        for (int k = 0; k < 6; k++) {
+          const double vp = v[k][p], vq = v[k][q];
+          v[k][p] = c * vp - s * vq;
+          v[k][q] = s * vp + c * vq;
+        }
+      }
+  }
+}
+
+// include/loamx.h, loamx_densemap_align_solve
+static void align_solve(const int64_t sums[28], double ratio, double x[6], uint32_t& dropped) {
+  double H[6][6], V[6][6], g[6];
+  int w = 0;
+  for (int k = 0; k < 6; k++)
+    for (int l = k; l < 6; l++) H[k][l] = H[l][k] = (double)sums[w++] / 65536.0;
+  for (int k = 0; k < 6; k++) g[k] = (double)sums[21 + k] / 16777216.0;
+  jacobi_eig6(H, V);
+  double lmax = 0.0;
+  for (int k = 0; k < 6; k++) lmax = std::max(lmax, H[k][k]);
+  dropped = 0;
+  for (int k = 0; k < 6; k++) x[k] = 0.0;
+  for (int k = 0; k < 6; k++) {
+    const double lam = H[k][k];
+    if (!(lam > 0.0 && lam > ratio * lmax)) { dropped++; continue; }
+    double vg = 0.0;
+    for (int i = 0; i < 6; i++) vg += V[i][k] * g[i];
+    for (int i = 0; i < 6; i++) x[i] -= V[i][k] * (vg / lam);
+  }
+}
+
+// R <- exp([w]) R (Rodrigues), row-major
+static void rotate_left(double R[9], const double w[3]) {
+  const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2], th = std::sqrt(th2);
+  // sin(th)/th and (1 - cos(th))/th^2, by their series where th is small
+  const double A = th < 1e-4 ? 1.0 - th2 / 6.0 : std::sin(th) / th, B = th < 1e-4 ? 0.5 - th2 / 24.0 : (1.0 - std::cos(th)) / th2;
+  const double K[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
+  double E[9], out[9];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      double kk = 0.0;
+      for (int m = 0; m < 3; m++) kk += K[3 * i + m] * K[3 * m + j];
+      E[3 * i + j] = (i == j ? 1.0 : 0.0) + A * K[3 * i + j] + B * kk;
+    }
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) out[3 * i + j] = (E[3 * i] * R[j] + E[3 * i + 1] * R[3 + j]) + E[3 * i + 2] * R[6 + j];
+  for (int k = 0; k < 9; k++) R[k] = out[k];
+}
+
+static loamx_densemap_align_config checked_align_config(const loamx_densemap_align_config* cfg, float leaf) {
+  loamx_densemap_align_config c;
+  if (cfg) c = *cfg; else loamx_densemap_align_default_config(&c);
+  LX_REQUIRE(c.max_iterations >= 1u && c.max_iterations <= 1000u, "max_iterations must be in [1, 1000]");
+  LX_REQUIRE(c.neighbourhood <= 1u, "neighbourhood must be 0 or 1");
+  if (c.max_residual == 0.f) c.max_residual = leaf;
+  LX_REQUIRE(c.max_residual > 0.f && c.max_residual <= 16.f, "max_residual must be in (0, 16] (0: the leaf)");
+  LX_REQUIRE(c.eps_rot >= 0.f && c.eps_trans >= 0.f, "eps_rot and eps_trans must be >= 0");
+  LX_REQUIRE(c.degenerate_ratio >= 0.f && c.degenerate_ratio < 1.f, "degenerate_ratio must be in [0, 1)");
+  return c;
+}
+
+// the loop of include/loamx.h over a cloud that lies on the device; pose_in NULL: identity
+static int align_loop(loamx_densemap* h, const float4* pts, uint32_t n, const double pose_in[12], const float centre[3],
+                      const loamx_densemap_align_config& c, hipStream_t st, loamx_densemap_align_result* out) {
+  static const double ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  const double* P = pose_in ? pose_in : ident;
+  for (int k = 0; k < 12; k++) LX_REQUIRE(std::isfinite(P[k]), "the pose must be finite");
+  const double cc[3] = {centre ? (double)centre[0] : 0.0, centre ? (double)centre[1] : 0.0, centre ? (double)centre[2] : 0.0};
+  double R[9], t[3];
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) R[3 * i + j] = P[4 * i + j];
+    t[i] = ((R[3 * i] * cc[0] + R[3 * i + 1] * cc[1]) + R[3 * i + 2] * cc[2]) + P[4 * i + 3];
+  }
+  memset(out, 0, sizeof(*out));
+  for (int k = 0; k < 12; k++) out->pose[k] = P[k];
+  out->status = 1;
+  DmFrozen& F = loamx_densemap_frozen(h);
+  const float inv = 1.0f / loamx_densemap_cfg(h).leaf;
+  for (uint32_t it = 0; it < c.max_iterations; it++) {
+    float rtc[15];
+    for (int k = 0; k < 9; k++) rtc[k] = (float)R[k];
+    for (int k = 0; k < 3; k++) { rtc[9 + k] = (float)t[k]; rtc[12 + k] = (float)cc[k]; }
+    int64_t sums[28];
+    F.step(pts, n, rtc, inv, c.neighbourhood, c.max_residual, st, sums, out->counts);
+    out->iterations = it + 1;
+    const uint64_t matched = out->counts[4];
+    out->rms = matched ? std::sqrt(((double)sums[27] / 16777216.0) / (double)matched) : 0.0;
+    if (matched < c.min_matched) { out->status = 2; break; }
+    double x[6];
+    align_solve(sums, (double)c.degenerate_ratio, x, out->degenerate_dims);
+    rotate_left(R, x);
+    for (int k = 0; k < 3; k++) t[k] += x[3 + k];
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) out->pose[4 * i + j] = R[3 * i + j];
+      out->pose[4 * i + 3] = t[i] - ((R[3 * i] * cc[0] + R[3 * i + 1] * cc[1]) + R[3 * i + 2] * cc[2]);
+    }
+    const double wn = std::sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]), vn = std::sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]);
+    if (wn < (double)c.eps_rot && vn < (double)c.eps_trans) { out->status = 0; break; }
+  }
+  return LOAMX_OK;
+}
+
+// the cloud of a mapper / a pipeline where it lies: the handle's own stream runs behind the stream that wrote it
+static int align_from_source(loamx_densemap* h, const DenseSource& s, const double pose_in[12], const loamx_densemap_align_config* cfg,
+                             loamx_densemap_align_result* out) {
+  const loamx_densemap_config& mc = loamx_densemap_cfg(h);
+  LX_REQUIRE(s.device == mc.device, "the dense map and its source live on different devices");
+  const loamx_densemap_align_config c = checked_align_config(cfg, mc.leaf);
+  LX_REQUIRE(loamx_densemap_frozen(h).valid(), "nothing is frozen (loamx_densemap_freeze)");
+  if (!s.has_cloud) return LOAMX_SKIPPED;
+  LX_HIP(hipSetDevice(mc.device));
+  hipStream_t st = loamx_densemap_own_stream(h);
+  hipEvent_t ev = nullptr;
+  LX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ev, s.stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
+  (void)hipEventDestroy(ev);   // (the wait keeps what it needs)
+  LX_HIP(e);
+  return align_loop(h, s.pts, s.n, pose_in, s.origin, c, st, out);
+}
+
+}  // namespace loamx
+
+using namespace loamx;
+
+extern "C" {
+
+void loamx_densemap_align_default_config(loamx_densemap_align_config* cfg) {
+  if (!cfg) return;
+  memset(cfg, 0, sizeof(*cfg));
+  cfg->max_iterations = 20u;
+  cfg->neighbourhood = 1u;
+  cfg->max_residual = 0.f;
+  cfg->min_matched = 50u;
+  cfg->eps_rot = 1e-5f;
+  cfg->eps_trans = 1e-5f;
+  cfg->degenerate_ratio = 1e-4f;
+}
+
+int loamx_densemap_align_solve(const int64_t sums[28], float degenerate_ratio, double x[6], uint32_t* dropped) {
+  return guard([&]() {
+    LX_REQUIRE(sums && x && dropped, "NULL argument");
+    LX_REQUIRE(degenerate_ratio >= 0.f && degenerate_ratio < 1.f, "degenerate_ratio must be in [0, 1)");   // (NaN too)
+    align_solve(sums, (double)degenerate_ratio, x, *dropped);
+    return LOAMX_OK;
+  });
+}
+
+int loamx_densemap_align_step(loamx_densemap* h, const loamx_cloud* points, const float rtc[15], uint32_t neighbourhood, float max_residual,
+                              int64_t sums[28], uint64_t counts[5]) {
+  return guard([&]() {
+    LX_REQUIRE(h && points && rtc && sums && counts, "NULL argument");
+    LX_REQUIRE(neighbourhood <= 1u, "neighbourhood must be 0 or 1");
+    LX_REQUIRE(max_residual > 0.f && max_residual <= 16.f, "max_residual must be in (0, 16]");   // (NaN too)
+    DmFrozen& F = loamx_densemap_frozen(h);
+    LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
+    const loamx_densemap_config& mc = loamx_densemap_cfg(h);
+    LX_HIP(hipSetDevice(mc.device));
+    hipStream_t st = loamx_densemap_own_stream(h);
+    const float4* pts = F.stage(points, st);
+    F.step(pts, points->count, rtc, 1.0f / mc.leaf, neighbourhood, max_residual, st, sums, counts);
+    return LOAMX_OK;
+  });
+}
+
+int loamx_densemap_align(loamx_densemap* h, const loamx_cloud* points, const double pose_in[12], const float centre[3],
+                         const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out) {
+  return guard([&]() {
+    LX_REQUIRE(h && points && pose_in && out, "NULL argument");
+    const loamx_densemap_config& mc = loamx_densemap_cfg(h);
+    const loamx_densemap_align_config c = checked_align_config(cfg, mc.leaf);
+    DmFrozen& F = loamx_densemap_frozen(h);
+    LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
+    LX_HIP(hipSetDevice(mc.device));
+    hipStream_t st = loamx_densemap_own_stream(h);
+    const float4* pts = F.stage(points, st);
+    return align_loop(h, pts, points->count, pose_in, centre, c, st, out);
+  });
+}
+
+int loamx_densemap_align_from_map(loamx_densemap* h, loamx_map* m, const double pose_in[12], const loamx_densemap_align_config* cfg,
+                                  loamx_densemap_align_result* out) {
+  return guard([&]() {
+    LX_REQUIRE(h && m && out, "NULL argument");
+    DenseSource s;
+    loamx_map_dense_source(m, s);
+    return align_from_source(h, s, pose_in, cfg, out);
+  });
+}
+
+int loamx_densemap_align_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot, const double pose_in[12],
+                                       const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out) {
+  return guard([&]() {
+    LX_REQUIRE(h && p && out, "NULL argument");
+    DenseSource s;
+    loamx_pipeline_dense_source(p, slot, s);
+    return align_from_source(h, s, pose_in, cfg, out);
+  });
+}
+
+}  // extern "C"

@@ -1056,6 +1056,53 @@ def surfel_of(leaf, idx, vals, mom, axes="loam", min_points=None, min_planar_rat
     return out
 
 
+class AlignConfig(C.Structure):
+    """loamx_densemap_align_config; AlignConfig() holds the defaults (20 iterations, neighbourhood 1, max_residual 0 = the leaf, 50
+    matches, 1e-5 rad / 1e-5 m, degenerate_ratio 1e-4)."""
+    _fields_ = [("max_iterations", C.c_uint32), ("neighbourhood", C.c_uint32), ("max_residual", C.c_float), ("min_matched", C.c_uint32),
+                ("eps_rot", C.c_float), ("eps_trans", C.c_float), ("degenerate_ratio", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().loamx_densemap_align_default_config(C.byref(self))
+        for k, v in kw.items():
+            assert hasattr(self, k), k
+            if v is not None:
+                setattr(self, k, v)
+
+
+class AlignResult(C.Structure):
+    """loamx_densemap_align_result: pose (row-major 3x4, map <- cloud), iterations, degenerate_dims, status (0 converged, 1
+    max_iterations reached, 2 fewer than min_matched matches), rms and counts of the last step"""
+    _fields_ = [("pose", C.c_double * 12), ("iterations", C.c_uint32), ("degenerate_dims", C.c_uint32), ("status", C.c_int),
+                ("rms", C.c_double), ("counts", C.c_uint64 * 5)]
+
+    def as_dict(self) -> dict:
+        return dict(pose=np.array(self.pose[:], np.float64).reshape(3, 4), iterations=int(self.iterations),
+                    degenerate_dims=int(self.degenerate_dims), status=int(self.status), rms=float(self.rms),
+                    counts=dict(zip(ALIGN_COUNTS, (int(v) for v in self.counts))))
+
+
+ALIGN_COUNTS = ("far", "outside", "unmatched", "rejected", "matched")   # counts[5] of loamx_densemap_align_step
+
+
+def align_solve(sums, degenerate_ratio=1e-4):
+    """loamx_densemap_align_solve (host only): (x (6,) float64, dropped) from the 28 integer sums of an align_step"""
+    s = np.ascontiguousarray(sums, np.int64)
+    assert s.shape == (28,)
+    x = np.zeros(6, np.float64)
+    dropped = C.c_uint32(0)
+    _check(lib().loamx_densemap_align_solve(s.ctypes.data_as(C.c_void_p), C.c_float(degenerate_ratio), x.ctypes.data_as(C.c_void_p),
+                                            C.byref(dropped)))
+    return x, int(dropped.value)
+
+
+def _pose12(pose):
+    p = np.ascontiguousarray(pose, np.float64)
+    assert p.shape == (3, 4) or p.shape == (12,), "a pose is a row-major 3x4 matrix"
+    return p.reshape(12)
+
+
 def write_pcd(path: str, points, axes="loam"):
     """loamx_write_pcd: an (N, 4) / (N, 8) float32 cloud as a binary PCD v0.7 file (x y z intensity); axes="sensor" writes the sensor
     axes ingestion started from (x_s = z, y_s = x, z_s = y).  Host only."""
@@ -1200,6 +1247,63 @@ class DenseMap:
                 continue
             _check(rc)
             return out[:int(n.value)]
+
+    def freeze(self, min_points=None, min_planar_ratio=None, static=None) -> int:
+        """loamx_densemap_freeze: the surfels of surfels(min_points, min_planar_ratio, static) that have a normal, frozen into a
+        table of their own on the device for align*; replaces an earlier snapshot.  Returns their number.  Needs moments."""
+        c = SurfelConfig(min_points, min_planar_ratio)
+        n = C.c_uint64(0)
+        _check(lib().loamx_densemap_freeze(self.h, C.byref(c), C.byref(static) if static is not None else None, C.byref(n)))
+        return int(n.value)
+
+    @property
+    def frozen_size(self) -> int:
+        n = C.c_uint64(0)
+        _check(lib().loamx_densemap_frozen_size(self.h, C.byref(n)))
+        return int(n.value)
+
+    def align_step(self, points, rtc, neighbourhood=1, max_residual=None):
+        """loamx_densemap_align_step: one linearisation about rtc = (R row-major, t, c), 15 float32.  Returns (sums (28,) int64,
+        counts (5,) uint64 in the order of ALIGN_COUNTS); max_residual None: the leaf"""
+        a = as_points(points)
+        c = cloud_of(a)
+        r = np.ascontiguousarray(rtc, np.float32)
+        assert r.shape == (15,)
+        sums, counts = np.zeros(28, np.int64), np.zeros(5, np.uint64)
+        mr = self._c.leaf if max_residual is None else max_residual
+        _check(lib().loamx_densemap_align_step(self.h, C.byref(c), r.ctypes.data_as(C.c_void_p), C.c_uint32(neighbourhood), C.c_float(mr),
+                                               sums.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
+        return sums, counts
+
+    def align(self, points, pose=np.eye(3, 4), centre=None, **cfg) -> dict:
+        """loamx_densemap_align: Gauss-Newton point-to-plane alignment of (N, 4) / (N, 8) points to the frozen snapshot from pose
+        (3x4, map <- cloud), rotating about centre (default 0).  cfg: the fields of AlignConfig.  Blocks; returns AlignResult.as_dict()"""
+        a = as_points(points)
+        c = cloud_of(a)
+        p = _pose12(pose)
+        ctr = None if centre is None else np.ascontiguousarray(centre, np.float32)
+        assert ctr is None or ctr.shape == (3,)
+        k, out = AlignConfig(**cfg), AlignResult()
+        _check(lib().loamx_densemap_align(self.h, C.byref(c), p.ctypes.data_as(C.c_void_p),
+                                          None if ctr is None else ctr.ctypes.data_as(C.c_void_p), C.byref(k), C.byref(out)))
+        return out.as_dict()
+
+    def align_from(self, mapping, pose=None, **cfg):
+        """loamx_densemap_align_from_map: the registered cloud of mapping's last process, where it lies, about its origin; pose None:
+        identity.  Returns (status code OK / SKIPPED, AlignResult.as_dict())"""
+        p = None if pose is None else _pose12(pose)
+        k, out = AlignConfig(**cfg), AlignResult()
+        rc = _check(lib().loamx_densemap_align_from_map(self.h, mapping.h, None if p is None else p.ctypes.data_as(C.c_void_p),
+                                                        C.byref(k), C.byref(out)))
+        return rc, out.as_dict()
+
+    def align_from_pipeline(self, pipeline, slot: int, pose=None, **cfg):
+        """loamx_densemap_align_from_pipeline: the same for the slot-th stream registered in pipeline's last step"""
+        p = None if pose is None else _pose12(pose)
+        k, out = AlignConfig(**cfg), AlignResult()
+        rc = _check(lib().loamx_densemap_align_from_pipeline(self.h, pipeline.h, C.c_uint32(slot),
+                                                             None if p is None else p.ctypes.data_as(C.c_void_p), C.byref(k), C.byref(out)))
+        return rc, out.as_dict()
 
     def reset(self):
         _check(lib().loamx_densemap_reset(self.h))
