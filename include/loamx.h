@@ -879,6 +879,66 @@ int loamx_densemap_align_from_map(loamx_densemap* h, loamx_map* m, const double 
 int loamx_densemap_align_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot, const double pose_in[12],
                                        const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out);
 
+/* A prior map: native save / load, and the exact merge of two maps (optional: a handle that never calls them runs the kernels it
+ * ran).  Every word of a voxel is an integer sum, so the map can be written out and read back without loss, and two maps of the same
+ * leaf can be combined by adding words per key.
+ *
+ * File ('LXDM', version 1), little-endian, of exactly this size (no trailing bytes).  Header, 128 bytes:
+ *     0 "LXDM"            4 u32 version = 1        8 u32 flags (1 carving, 2 moments)        12 f32 leaf
+ *    16 u64 count        24 u64 points offered    32 u64 dropped by range                    40 u64 dropped outside the key range
+ *    48 u64 carve_stats[6] in the order of get_carve_stats       96 f32 carve max_range, u32 ray_stride, end_margin, max_steps
+ *   112 16 reserved bytes, zero.        Without carving the bytes 48 .. 111 are zero.
+ * Body, every array in ascending key order (the record order of loamx_densemap_download):  u64 keys[count];  u64 vals[4 * count]
+ * (n, Sx, Sy, Sz per voxel);  with carving u32 miss[count], zero-padded to a multiple of 8 bytes;  with moments u64 mom[9 * count],
+ * the words loamx_densemap_download_moments gives.  Stamps and the sequence number of the calls are not stored: a stamp only matters
+ * while it equals the sequence number of the call in progress, so a loaded or merged-in voxel gets stamp 0, which is equivalent for
+ * every add that follows.
+ * Determinism: the file has the same bytes whatever the thread schedule, the order of the points, the split into calls (for
+ * everything but miss, as above), the size of the table and the number of rehashes behind the map.
+ *
+ * loamx_densemap_save waits for the adds as download does, writes to a temporary name beside `path` and renames it: a save that
+ * fails leaves nothing under `path`.  Pruned voxels are not in the file.  The frozen snapshot is not saved: the surfels are a function
+ * of the words, so a freeze after a load reproduces it bit for bit.
+ *
+ * loamx_densemap_file_info (host only, no device): the header of a file.  deep == 0 checks the header and the exact size of the
+ * file: magic, version, flags within {1, 2}, leaf finite and > 0, reserved bytes zero, with carving a configuration that
+ * enable_carving accepts (without: zero bytes), count <= 2^30.  deep != 0 also reads every record: keys strictly ascending, each
+ * < 2^63 with each of its three 21-bit fields in [1, 2^21 - 1], every n >= 1.  Any failure: LOAMX_E_INVALID with a message that names
+ * the field.  load and merge_file run the deep check before anything touches the device.
+ *
+ * loamx_densemap_load: h must be empty (fresh, or right after reset) and its leaf must have the bits of the file's.  load enables on h
+ * whichever of carving and moments the file has and h has not, and h carves with the file's configuration from then on; a handle
+ * that has a feature the file lacks: LOAMX_E_INVALID.  count > max_voxels (with a cap): LOAMX_E_CAPACITY.  A refused load leaves the
+ * handle unchanged.  The table gets the smallest power of two of slots that is >= initial_slots and >= 2 * count.  Afterwards
+ * get_stats (but for slots), get_carve_stats and every export (download*, save_pcd*, download_moments, download_misses,
+ * download_surfels, save) give what the saving handle gave, and later adds behave as they would have on the saving handle.
+ *
+ * loamx_densemap_merge(dst, src): per key of src the voxel of dst (created when absent) receives n += n, S* += S* and the nine moment
+ * words modulo 2^64 and miss += miss modulo 2^32; it keeps its stamp (0 for a new voxel).  dst's three point statistics and six
+ * carve statistics grow by src's.  src is only read; the frozen snapshots of both stay as they are.  n, S* and the moment words of
+ * the result are those of one map fed with every add of both maps, in any order.  The miss words are the SUMS of the two maps' miss
+ * words, which is not what carving the joint sequence of calls would have counted: neither map's rays saw the other's voxels.
+ * LOAMX_E_INVALID, dst unchanged: dst and src are the same handle, live on different devices, differ in a bit of the leaf, or do not
+ * have the same features enabled (carving on in both or off in both; moments alike).  LOAMX_E_CAPACITY, dst unchanged: with a cap,
+ * voxels(dst) + voxels(src) > max_voxels (the bound before common keys are known, as an add counts its points before filtering).
+ * The call waits for the adds of both handles and returns when dst holds the result.  Growth follows the add's rule: the table
+ * doubles on the device, before the merge, until voxels(dst) + voxels(src) is at most one half of the slots.
+ * loamx_densemap_merge_file(dst, path): the same with the records of a file as the source (its flags must equal dst's features); the
+ * records go up through pinned memory.  load is merge_file into an empty handle plus the enabling. */
+struct loamx_densemap_file_info {   /* (a struct tag only: the name is the function's) */
+  uint32_t version, flags;          /* flags: 1 carving, 2 moments */
+  float leaf;
+  uint64_t voxels;
+  uint64_t offered, dropped_range, dropped_key;
+  uint64_t carve_stats[6];
+  loamx_densemap_carve_config carve;
+};
+int loamx_densemap_save(loamx_densemap* h, const char* path);
+int loamx_densemap_load(loamx_densemap* h, const char* path);
+int loamx_densemap_merge(loamx_densemap* dst, loamx_densemap* src);
+int loamx_densemap_merge_file(loamx_densemap* dst, const char* path);
+int loamx_densemap_file_info(const char* path, struct loamx_densemap_file_info* info, int deep);   /* host only, no device */
+
 /* ------------------------------------------------------------------------------------------------------------
  * Place recognition (not in the reference): a database of rotation-invariant sweep descriptors in device memory (Scan Context: a
  * ring x sector polar grid of maximum heights around the sensor) and an exhaustive search for the earlier entries that look like a

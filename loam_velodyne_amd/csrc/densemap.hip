@@ -16,6 +16,7 @@
 // Freeze (loamx_densemap_freeze): the surfels of that export, computed once, go into a second table on the device that the alignment
 // of densemap_align.hip reads; the table above never learns of it.
 #include "densemap.hpp"
+#include "densemap_file.hpp"
 #include "host_math.h"
 #include "pinned_copy.hpp"
 #include "scan.hpp"
@@ -369,6 +370,62 @@ __global__ __launch_bounds__(256) void k_dm_rehash(const unsigned long long* __r
     }
   }
   if (PRUNE) dm_wave_count(&ctr[0], won);
+}
+
+// the statistics a merge adds to dst's counters: [0] dropped by range, [1] dropped outside the key range, [2..8) the six of carving
+struct DmCtrAdd {
+  unsigned long long v[8];
+};
+
+// Merge (include/loamx.h, loamx_densemap_merge / merge_file): every record of a source is added into the live table, its voxel claimed
+// when absent.  The source is another map's table (sn slots, the DM_EMPTY ones skipped, miss at smiss[2 * i]: miss_stride 2) or the
+// compact arrays of a file (sn records, miss_stride 1).  AUX: the miss word is added too, the stamp of dst stays (0 in a fresh slot: the
+// words beside a free slot are zero).  MOM: the nine moment words.
+// Only the key claim is atomic.  The keys of one source are unique, so within the launch one thread at most holds a given slot of
+// dst, and nothing else writes dst meanwhile: the launch runs on dst's stream behind its adds, and the host waits for it before it
+// returns.  The up to 14 value words are therefore plain loads, integer adds and plain stores (16 bytes at a time for n, Sx, Sy, Sz;
+// the 72-byte moment rows are only 8-byte aligned) instead of 14 atomics that each make a trip to the memory side; a slot the CAS
+// has just claimed reads as the zeros that the memset of an earlier launch left there.  Integer adds modulo 2^64 (miss: 2^32); no floating point anywhere.
+// ctr[0] counts the slots claimed, as the insert does; ctr[3] reports a probe loop that ran out.  The first thread also adds the
+// source's statistics to dst's counters
+template <bool AUX, bool MOM>
+__global__ __launch_bounds__(256) void k_dm_merge(const unsigned long long* __restrict__ skeys, const unsigned long long* __restrict__ svals,
+                                                  uint32_t sn, const uint32_t* __restrict__ smiss, uint32_t miss_stride,
+                                                  const unsigned long long* __restrict__ smom, unsigned long long* __restrict__ keys,
+                                                  unsigned long long* __restrict__ vals, uint32_t mask, uint32_t shift,
+                                                  unsigned long long* __restrict__ ctr, uint32_t* __restrict__ aux,
+                                                  unsigned long long* __restrict__ mom, DmCtrAdd add) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned long long key = i < sn ? skeys[i] : DM_EMPTY;
+  const bool live = key != DM_EMPTY;
+  uint32_t slot = 0;
+  bool won = false, ok = true;
+  if (live) ok = dm_find_or_claim(keys, mask, shift, key, slot, won);
+  dm_wave_count(&ctr[0], won);
+  if (live && !ok) ctr[3] = 1ull;
+  if (live && ok) {
+    const ulonglong2* s = (const ulonglong2*)(svals + 4ull * i);
+    ulonglong2* d = (ulonglong2*)(vals + 4ull * slot);
+    const ulonglong2 s0 = s[0], s1 = s[1];
+    ulonglong2 d0 = d[0], d1 = d[1];
+    d0.x += s0.x; d0.y += s0.y; d1.x += s1.x; d1.y += s1.y;
+    d[0] = d0;
+    d[1] = d1;
+    if (AUX) aux[2ull * slot] += smiss[(unsigned long long)miss_stride * i];
+    if (MOM) {
+      const unsigned long long* ms = smom + (unsigned long long)DM_MOM_WORDS * i;
+      unsigned long long* md = mom + (unsigned long long)DM_MOM_WORDS * slot;
+#pragma unroll
+      for (int k = 0; k < DM_MOM_WORDS; k++) md[k] += ms[k];
+    }
+  }
+  if (i == 0) {
+    if (add.v[0]) atomicAdd(&ctr[1], add.v[0]);
+    if (add.v[1]) atomicAdd(&ctr[2], add.v[1]);
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+      if (add.v[2 + k]) atomicAdd(&ctr[4 + k], add.v[2 + k]);
+  }
 }
 
 // compaction of the occupied slots in slot order: occupied slots per 256-slot block (ballot), then (behind an exclusive scan of those
@@ -736,6 +793,114 @@ class DenseMap {
     seq_ = 0;
   }
 
+  // the features of the handle as the file's flags
+  uint32_t flags() const { return (aux_ ? DMF_CARVING : 0u) | (mom_ ? DMF_MOMENTS : 0u); }
+
+  // include/loamx.h, loamx_densemap_save: the records of snapshot() in ascending key order, with the statistics
+  void save(const char* path) {
+    Snapshot S;
+    snapshot(S, mom_ != nullptr);
+    const size_t n = S.idx.size();
+    DmFileHeader H;
+    H.flags = flags();
+    H.leaf = cfg.leaf;
+    H.count = n;
+    H.offered = offered_; H.dropped_range = drop_range_; H.dropped_key = drop_key_;
+    if (aux_) {
+      for (int k = 0; k < 6; k++) H.carve_stats[k] = carve_ctr_[k];
+      H.carve_max_range = carve_.max_range;
+      H.ray_stride = carve_.ray_stride; H.end_margin = carve_.end_margin; H.max_steps = carve_.max_steps;
+    }
+    std::vector<uint64_t> k(n), v(4 * n), m(mom_ ? DM_MOM_WORDS * n : 0);
+    std::vector<uint32_t> ms(aux_ ? n : 0);
+    for (size_t r = 0; r < n; r++) {
+      const size_t j = S.idx[r];
+      k[r] = S.k[j];
+      for (int a = 0; a < 4; a++) v[4 * r + a] = S.v[4 * j + a];
+      if (aux_) ms[r] = S.miss[j];
+      if (mom_)
+        for (int a = 0; a < DM_MOM_WORDS; a++) m[DM_MOM_WORDS * r + a] = S.mom[DM_MOM_WORDS * j + a];
+    }
+    const std::string e = dmf_write(path, H, k.data(), v.data(), aux_ ? ms.data() : nullptr, mom_ ? m.data() : nullptr);
+    LX_REQUIRE(e.empty(), e);
+  }
+
+  // include/loamx.h, loamx_densemap_merge
+  int merge(DenseMap& src) {
+    LX_REQUIRE(&src != this, "a dense map cannot be merged into itself");
+    LX_REQUIRE(src.cfg.device == cfg.device, "the two dense maps live on different devices");
+    LX_REQUIRE(memcmp(&src.cfg.leaf, &cfg.leaf, sizeof(float)) == 0, "the two dense maps differ in their leaf");
+    LX_REQUIRE(src.flags() == flags(), "the two dense maps do not have the same features enabled (carving, moments)");
+    src.read_counters();
+    read_counters();
+    if (cfg.max_voxels && occ_ + src.occ_ > cfg.max_voxels) return LOAMX_E_CAPACITY;
+    DmCtrAdd add;
+    add.v[0] = src.drop_range_; add.v[1] = src.drop_key_;
+    for (int k = 0; k < 6; k++) add.v[2 + k] = src.carve_ctr_[k];
+    merge_records(src.keys_, src.vals_, src.slots_, src.occ_, src.aux_, 2u, src.mom_, add, src.offered_);
+    return LOAMX_OK;
+  }
+
+  // include/loamx.h, loamx_densemap_merge_file, and with `loading` loamx_densemap_load.  The file is validated on the host before the
+  // device is touched; every refusal comes before the first change of the handle
+  int merge_file(const char* path, bool loading) {
+    DmFile F;
+    const std::string e = dmf_read(path, true, F);
+    LX_REQUIRE(e.empty(), std::string(path) + ": " + e);
+    LX_REQUIRE(memcmp(&F.h.leaf, &cfg.leaf, sizeof(float)) == 0, "the file's leaf differs from the dense map's");
+    const uint64_t n = F.h.count;
+    read_counters();
+    if (loading) {
+      LX_REQUIRE(occ_ == 0 && offered_ == 0, "a file can only be loaded into an empty map (a fresh handle, or right after reset)");
+      LX_REQUIRE((flags() & ~F.h.flags) == 0u, "the dense map has a feature enabled (carving, moments) that the file lacks");
+      if (cfg.max_voxels && n > cfg.max_voxels) return LOAMX_E_CAPACITY;
+      if (F.h.flags & DMF_CARVING) {
+        const loamx_densemap_carve_config c = {F.h.carve_max_range, F.h.ray_stride, F.h.end_margin, F.h.max_steps};
+        enable_carving(c);
+      }
+      if (F.h.flags & DMF_MOMENTS) enable_moments();
+      // the smallest table the file's voxels fit at a load of one half (a handle reset after it grew holds a larger one)
+      uint64_t target = cfg.initial_slots;
+      while (target < 2 * n) target *= 2;
+      if (slots_ > target) {
+        unsigned long long *nk = nullptr, *nv = nullptr, *nm = nullptr;
+        uint32_t* na = nullptr;
+        alloc_table(target, nk, nv, aux_ ? &na : nullptr, mom_ ? &nm : nullptr);
+        LX_HIP(hipStreamSynchronize(own_));
+        retire_table();
+        keys_ = nk; vals_ = nv; aux_ = na; mom_ = nm;
+        slots_ = (uint32_t)target;
+        clear(own_);
+      }
+    } else {
+      LX_REQUIRE(F.h.flags == flags(), "the file and the dense map do not have the same features (carving, moments)");
+      if (cfg.max_voxels && occ_ + n > cfg.max_voxels) return LOAMX_E_CAPACITY;
+    }
+    // one pinned block, one copy: values (first: the kernel reads them 16 bytes at a time), moment words, keys, then the 32-bit miss words
+    const size_t nn = (size_t)n, w_mom = mom_ ? DM_MOM_WORDS * nn : 0, w_miss = aux_ ? (nn + 1) / 2 : 0;
+    const size_t o_mom = 4 * nn, o_keys = o_mom + w_mom, o_miss = o_keys + nn, words = o_miss + w_miss;
+    PinBuf<unsigned long long> h_up;
+    DevBuf<unsigned long long> d_up;
+    h_up.reserve(words + 1);
+    d_up.reserve(words + 1);
+    if (nn) {
+      for (size_t i = 0; i < 4 * nn; i++) h_up.p[i] = F.vals[i];
+      for (size_t i = 0; i < w_mom; i++) h_up.p[o_mom + i] = F.mom[i];
+      for (size_t i = 0; i < nn; i++) h_up.p[o_keys + i] = F.keys[i];
+      if (aux_) {
+        h_up.p[words - 1] = 0ull;
+        memcpy(h_up.p + o_miss, F.miss.data(), sizeof(uint32_t) * nn);
+      }
+      LX_HIP(hipMemcpyAsync(d_up.p, h_up.p, sizeof(unsigned long long) * words, hipMemcpyHostToDevice, own_));
+    }
+    DmCtrAdd add;
+    add.v[0] = F.h.dropped_range; add.v[1] = F.h.dropped_key;
+    for (int k = 0; k < 6; k++) add.v[2 + k] = F.h.carve_stats[k];
+    const unsigned long long* d = d_up.p;
+    merge_records(d + o_keys, d, (uint32_t)n, n, (const uint32_t*)(d + o_miss), 1u, d + o_mom, add, F.h.offered);
+    return LOAMX_OK;
+  }
+
   bool combine = true;   // (bench A/B: the in-wave combining of equal keys)
   uint64_t rehashes = 0;
 
@@ -857,8 +1022,9 @@ class DenseMap {
     read_counters();
     return occ_ + n <= cfg.max_voxels;
   }
-  void enqueue_add(const float4* pts, uint32_t n, const float origin[3], hipStream_t st) {
-    // growth: keep the load at most one half even if every point enqueued since the last count made a voxel of its own
+  // growth: keep the load at most one half even if every one of n records, and every point enqueued since the last count, made a voxel
+  // of its own.  The rehash into the larger table is enqueued on st; the host does not wait
+  void grow_for(uint64_t n, hipStream_t st) {
     uint64_t want = slots_;
     while (occ_ + pend_ + n > want / 2) want *= 2;
     LX_REQUIRE(want <= (1ull << 31), "dense map: more voxels than the table can index");
@@ -884,6 +1050,33 @@ class DenseMap {
       slots_ = (uint32_t)want;
       rehashes++;
     }
+  }
+  // the tail of merge / merge_file, behind a read_counters() (every add waited for, occ_ exact): sn source slots or records holding
+  // s_occ voxels go into the table on own_; returns when the table holds the result
+  void merge_records(const unsigned long long* skeys, const unsigned long long* svals, uint32_t sn, uint64_t s_occ, const uint32_t* smiss,
+                     uint32_t miss_stride, const unsigned long long* smom, const DmCtrAdd& add, uint64_t s_offered) {
+    grow_for(s_occ, own_);
+    const dim3 grid(sn ? (sn + 255u) / 256u : 1u), block(256);   // (one block at least: its first thread adds the statistics)
+    const uint32_t mask = slots_ - 1u, sh = 64u - log2u(slots_);
+    if (aux_ && mom_)
+      hipLaunchKernelGGL((k_dm_merge<true, true>), grid, block, 0, own_, skeys, svals, sn, smiss, miss_stride, smom, keys_, vals_, mask, sh,
+                         ctr_.p, aux_, mom_, add);
+    else if (aux_)
+      hipLaunchKernelGGL((k_dm_merge<true, false>), grid, block, 0, own_, skeys, svals, sn, smiss, miss_stride, smom, keys_, vals_, mask, sh,
+                         ctr_.p, aux_, mom_, add);
+    else if (mom_)
+      hipLaunchKernelGGL((k_dm_merge<false, true>), grid, block, 0, own_, skeys, svals, sn, smiss, miss_stride, smom, keys_, vals_, mask, sh,
+                         ctr_.p, aux_, mom_, add);
+    else
+      hipLaunchKernelGGL((k_dm_merge<false, false>), grid, block, 0, own_, skeys, svals, sn, smiss, miss_stride, smom, keys_, vals_, mask, sh,
+                         ctr_.p, aux_, mom_, add);
+    LX_HIP(hipGetLastError());
+    offered_ += s_offered;
+    LX_HIP(hipStreamSynchronize(own_));   // (the rehash of a growth still read the table that read_counters is about to free)
+    read_counters();
+  }
+  void enqueue_add(const float4* pts, uint32_t n, const float origin[3], hipStream_t st) {
+    grow_for(n, st);
     if (n) {
       DmFilter F;
       F.inv = inv_;
@@ -1263,6 +1456,49 @@ int loamx_densemap_frozen_size(loamx_densemap* h, uint64_t* n_surfels) {
   return guard([&]() {
     LX_REQUIRE(h && n_surfels, "NULL argument");
     *n_surfels = h->d.frozen.valid() ? h->d.frozen.size() : 0;
+    return LOAMX_OK;
+  });
+}
+
+int loamx_densemap_save(loamx_densemap* h, const char* path) {
+  return guard([&]() {
+    LX_REQUIRE(h && path, "NULL argument");
+    h->d.save(path);
+    return LOAMX_OK;
+  });
+}
+int loamx_densemap_load(loamx_densemap* h, const char* path) {
+  return guard([&]() {
+    LX_REQUIRE(h && path, "NULL argument");
+    return h->d.merge_file(path, true);
+  });
+}
+int loamx_densemap_merge(loamx_densemap* dst, loamx_densemap* src) {
+  return guard([&]() {
+    LX_REQUIRE(dst && src, "NULL argument");
+    return dst->d.merge(src->d);
+  });
+}
+int loamx_densemap_merge_file(loamx_densemap* dst, const char* path) {
+  return guard([&]() {
+    LX_REQUIRE(dst && path, "NULL argument");
+    return dst->d.merge_file(path, false);
+  });
+}
+int loamx_densemap_file_info(const char* path, struct loamx_densemap_file_info* info, int deep) {
+  return guard([&]() {
+    LX_REQUIRE(path && info, "NULL argument");
+    DmFile F;
+    const std::string e = dmf_read(path, deep != 0, F);
+    LX_REQUIRE(e.empty(), std::string(path) + ": " + e);
+    memset(info, 0, sizeof(*info));
+    info->version = F.h.version; info->flags = F.h.flags;
+    info->leaf = F.h.leaf;
+    info->voxels = F.h.count;
+    info->offered = F.h.offered; info->dropped_range = F.h.dropped_range; info->dropped_key = F.h.dropped_key;
+    for (int k = 0; k < 6; k++) info->carve_stats[k] = F.h.carve_stats[k];
+    info->carve.max_range = F.h.carve_max_range;
+    info->carve.ray_stride = F.h.ray_stride; info->carve.end_margin = F.h.end_margin; info->carve.max_steps = F.h.max_steps;
     return LOAMX_OK;
   });
 }

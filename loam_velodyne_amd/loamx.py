@@ -1004,6 +1004,25 @@ class DenseMapCarveConfig(C.Structure):
     _fields_ = [("max_range", C.c_float), ("ray_stride", C.c_uint32), ("end_margin", C.c_uint32), ("max_steps", C.c_uint32)]
 
 
+class DenseMapFileInfo(C.Structure):
+    """struct loamx_densemap_file_info: the header of a dense map file (flags: 1 carving, 2 moments)"""
+    _fields_ = [("version", C.c_uint32), ("flags", C.c_uint32), ("leaf", C.c_float), ("voxels", C.c_uint64), ("offered", C.c_uint64),
+                ("dropped_range", C.c_uint64), ("dropped_key", C.c_uint64), ("carve_stats", C.c_uint64 * 6), ("carve", DenseMapCarveConfig)]
+
+
+def densemap_file_info(path: str, deep: bool = False) -> dict:
+    """loamx_densemap_file_info (host only): the header of a dense map file as a dict.  The header and the exact size of the file
+    are checked; deep=True also validates every record.  LoamxError E_INVALID names the offending field."""
+    i = DenseMapFileInfo()
+    _check(lib().loamx_densemap_file_info(os.fsencode(path), C.byref(i), 1 if deep else 0))
+    carving = bool(i.flags & 1)
+    return dict(version=int(i.version), flags=int(i.flags), carving=carving, moments=bool(i.flags & 2), leaf=float(i.leaf),
+                voxels=int(i.voxels), offered=int(i.offered), dropped_range=int(i.dropped_range), dropped_key=int(i.dropped_key),
+                carve_stats=[int(v) for v in i.carve_stats],
+                carve=dict(max_range=float(i.carve.max_range), ray_stride=int(i.carve.ray_stride), end_margin=int(i.carve.end_margin),
+                           max_steps=int(i.carve.max_steps)) if carving else None)
+
+
 class StaticRule(C.Structure):
     """loamx_densemap_static_rule: a voxel is dynamic iff miss >= min_misses and miss * den > n * num.  StaticRule() is the default
     rule (3, 1, 1)."""
@@ -1304,6 +1323,25 @@ class DenseMap:
         rc = _check(lib().loamx_densemap_align_from_pipeline(self.h, pipeline.h, C.c_uint32(slot),
                                                              None if p is None else p.ctypes.data_as(C.c_void_p), C.byref(k), C.byref(out)))
         return rc, out.as_dict()
+
+    def save(self, path: str):
+        """loamx_densemap_save: every word of the map as an 'LXDM' file (include/loamx.h), written beside path and renamed.  The
+        bytes depend on neither the order of the points nor the table behind the map"""
+        _check(lib().loamx_densemap_save(self.h, os.fsencode(path)))
+
+    def load(self, path: str):
+        """loamx_densemap_load: the file's map into this empty handle (same leaf); enables the carving / moments the file has.
+        Afterwards every export, freeze and align give what the saving handle gave"""
+        _check(lib().loamx_densemap_load(self.h, os.fsencode(path)))
+
+    def merge(self, other: "DenseMap"):
+        """loamx_densemap_merge: other's voxels added into this map on the device, word for word (same leaf, device and features).
+        n, S and the moments become those of one map fed with both maps' sweeps; the miss counts are summed, not re-carved"""
+        _check(lib().loamx_densemap_merge(self.h, other.h))
+
+    def merge_file(self, path: str):
+        """loamx_densemap_merge_file: the same with a saved map as the source"""
+        _check(lib().loamx_densemap_merge_file(self.h, os.fsencode(path)))
 
     def reset(self):
         _check(lib().loamx_densemap_reset(self.h))
