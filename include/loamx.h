@@ -939,6 +939,69 @@ int loamx_densemap_merge(loamx_densemap* dst, loamx_densemap* src);
 int loamx_densemap_merge_file(loamx_densemap* dst, const char* path);
 int loamx_densemap_file_info(const char* path, struct loamx_densemap_file_info* info, int deep);   /* host only, no device */
 
+/* Ray casts (optional: a handle that never casts a ray runs the kernels it ran, allocates what it allocated and exports the same
+ * bytes).  "From here, in this direction, what is the first surface of the map, and how far?" answered on the device, without a
+ * download: a live sweep checked against a prior map (a return that stops in front of the mapped surface is a new object, one that
+ * goes through it a removed one), a line of sight between two poses, the range image a lidar would see from a pose.
+ *
+ * Ray i runs from origin to ends[i], both in the map frame: a sweep and its sensor position, exactly as loamx_densemap_add takes
+ * them.  Per ray, independently, in f32, no fused multiply-add, / and sqrtf correctly rounded, inv = 1.0f / leaf, in this order:
+ *   If a component of the end is not finite, or the end's cell fails |floorf(p_a * inv)| < 2^20 on some axis: NOT_TRACED, done.
+ *   The walk of the carving section above runs, unchanged: the same so, sp, c0, c1, rem, s, tmax, tdelta, the same tie rule, and
+ *   exactly n_steps integer steps.  If the origin's cell fails the key rule, or n_steps > max_steps: NOT_TRACED, done.
+ *   Cell k is the cell after k steps.  The cells k = skip_steps .. n_steps are looked up in the live table, read-only: unlike
+ *   carving, the end cell is included.  No cell is looked up when skip_steps > n_steps.
+ *   The first cell k that is in the table, holds n >= min_points points and, with a rule, is not dynamic under it (the rule of the
+ *   carving section, on the voxel's n and miss) ends the ray: HIT when k < n_steps, HIT_END when k == n_steps.
+ *   No such cell: MISS.
+ * The record of a hit: key = the voxel's key;  x, y, z = its exported position, computed on the device in double exactly as the
+ * export does, x = (float)(((double)ix + (double)Sx / ((double)n * 2^20)) * (double)leaf) (y, z alike): the bytes
+ * loamx_densemap_download gives in axes 0;  with d = p - o and e = (x, y, z) - o per component, L2 = (d_x*d_x + d_y*d_y) + d_z*d_z,
+ * range = L2 == 0 ? 0 : ((d_x*e_x + d_y*e_y) + d_z*e_z) / sqrtf(L2): the metres along the ray to the foot of that position (it may
+ * be negative for a hit in the origin's own cell);  n = the voxel's point count, saturated at 2^32 - 1;  miss = its miss word (0 with
+ * carving off);  steps = k.  The position is the MEAN of the voxel's points, not a surface: range is good to about half a leaf.
+ * Without a hit key, x, y, z, range, n and miss are 0, and steps is the number of cells looked up (0 when NOT_TRACED).
+ * counts = NOT_TRACED, MISS, HIT, HIT_END, cells looked up (over all rays, those of a hit up to and including its cell).  The
+ * first four add up to the cloud's count.  All five are integer sums: they depend on neither the thread schedule nor the order of the
+ * rays.  Records and counts depend on the map's words only, not on the table's size, the number of rehashes or the order of the adds
+ * (miss depends on the call history, as documented above).  An empty map is valid: every traced ray is a MISS.
+ * Ordering: the call waits for the adds as download does, runs on the map's own stream and blocks until the five words and, with
+ * out != NULL, the records are back (through pinned memory): out[i] belongs to ray i.  out may be NULL: counts only.  An empty
+ * cloud: LOAMX_OK, zero counts, no launch.  The from_* forms read the registered cloud of a mapper / a pipeline slot where it lies,
+ * with its origin, behind an event on its stream (as add_from_map / add_from_pipeline pick it); LOAMX_SKIPPED when there is no cloud,
+ * LOAMX_E_INVALID on another device.
+ * LOAMX_E_INVALID, with a message that names the argument: NULL h, ends (m, p), origin or counts;  max_steps outside 1..65536;
+ * min_points == 0;  a rule with den == 0;  a rule on a handle without carving.  LOAMX_E_CAPACITY, nothing written: out != NULL and
+ * capacity < the cloud's count.  A refused call leaves the map as it was. */
+#define LOAMX_RAY_NOT_TRACED 0
+#define LOAMX_RAY_MISS 1
+#define LOAMX_RAY_HIT 2
+#define LOAMX_RAY_HIT_END 3
+typedef struct loamx_ray_hit {      /* 40 bytes */
+  uint64_t key;                     /* the hit voxel's key; 0 without a hit */
+  float x, y, z;                    /* its position: the bytes loamx_densemap_download gives in axes 0; 0 without a hit */
+  float range;                      /* metres along the ray to the foot of that position; 0 without a hit */
+  uint32_t n;                       /* its point count, saturated at 2^32 - 1 */
+  uint32_t miss;                    /* its miss word (0 with carving off) */
+  uint32_t steps;                   /* k of the hit cell; without a hit: cells looked up */
+  uint32_t status;                  /* 0 NOT_TRACED, 1 MISS, 2 HIT (before the end cell), 3 HIT_END (in the end cell) */
+} loamx_ray_hit;
+typedef struct loamx_densemap_raycast_config {
+  uint32_t max_steps;    /* rays with more steps are not traced, 1..65536 (default 4096) */
+  uint32_t skip_steps;   /* cells k < skip_steps are not looked up (the sensor's own voxels) (default 0) */
+  uint32_t min_points;   /* a voxel with fewer points is transparent, >= 1 (default 1) */
+} loamx_densemap_raycast_config;
+void loamx_densemap_raycast_default_config(loamx_densemap_raycast_config* cfg);   /* host only */
+int loamx_densemap_raycast(loamx_densemap* h, const loamx_cloud* ends, const float origin[3],
+                           const loamx_densemap_raycast_config* cfg /* NULL: the defaults */,
+                           const loamx_densemap_static_rule* rule /* NULL: every voxel; else needs carving */,
+                           loamx_ray_hit* out /* may be NULL: counts only */, uint64_t capacity, uint64_t counts[5]);
+int loamx_densemap_raycast_from_map(loamx_densemap* h, loamx_map* m, const loamx_densemap_raycast_config* cfg,
+                                    const loamx_densemap_static_rule* rule, loamx_ray_hit* out, uint64_t capacity, uint64_t counts[5]);
+int loamx_densemap_raycast_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot,
+                                         const loamx_densemap_raycast_config* cfg, const loamx_densemap_static_rule* rule,
+                                         loamx_ray_hit* out, uint64_t capacity, uint64_t counts[5]);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Place recognition (not in the reference): a database of rotation-invariant sweep descriptors in device memory (Scan Context: a
  * ring x sector polar grid of maximum heights around the sensor) and an exhaustive search for the earlier entries that look like a

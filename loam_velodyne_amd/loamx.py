@@ -1122,6 +1122,40 @@ def _pose12(pose):
     return p.reshape(12)
 
 
+class RayHit(C.Structure):
+    """loamx_ray_hit, 40 bytes: the first voxel a ray meets — its key, its exported position (the bytes of points()), the range along
+    the ray to the foot of that position, its point count and miss word, steps (k of the hit cell; without a hit the cells looked up)
+    and status (RAY_NOT_TRACED, RAY_MISS, RAY_HIT, RAY_HIT_END)"""
+    _fields_ = [("key", C.c_uint64), ("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("range", C.c_float), ("n", C.c_uint32),
+                ("miss", C.c_uint32), ("steps", C.c_uint32), ("status", C.c_uint32)]
+
+
+class RaycastConfig(C.Structure):
+    """loamx_densemap_raycast_config; the defaults are 4096, 0, 1"""
+    _fields_ = [("max_steps", C.c_uint32), ("skip_steps", C.c_uint32), ("min_points", C.c_uint32)]
+
+
+RAY_NOT_TRACED, RAY_MISS, RAY_HIT, RAY_HIT_END = range(4)                         # loamx_ray_hit.status
+RAY_COUNTS = ("not_traced", "miss", "hit", "hit_end", "cells")                    # counts[5] of loamx_densemap_raycast
+RAY_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in RayHit._fields_])              # the records as a structured numpy array
+
+
+def range_image_ends(pose, elevations_deg, n_azimuth: int, max_range: float) -> np.ndarray:
+    """the end points of the rays of a lidar at pose (3x4, map <- sensor, LOAM axes: x left, y up, z forward): one ring per
+    elevation, n_azimuth rays per ring at the azimuths 2 pi j / n_azimuth from +z towards +x, each max_range long.  Returns
+    (rings * n_azimuth, 4) float32, ring-major, intensity = the ring's index; computed in float64 and rounded once.  numpy only.
+    A rendered range image is DenseMap.raycast(ends, origin=pose[:, 3])[0]["range"].reshape(rings, n_azimuth)."""
+    P = np.asarray(pose, np.float64).reshape(3, 4)
+    el = np.deg2rad(np.asarray(elevations_deg, np.float64).reshape(-1))
+    az = 2.0 * np.pi * np.arange(int(n_azimuth)) / int(n_azimuth)
+    ce, se = np.cos(el)[:, None], np.sin(el)[:, None]
+    d = np.stack([ce * np.sin(az)[None, :], se * np.ones_like(az)[None, :], ce * np.cos(az)[None, :]], axis=2).reshape(-1, 3)
+    out = np.zeros((len(d), 4), np.float32)
+    out[:, :3] = (d * float(max_range)) @ P[:, :3].T + P[:, 3]
+    out[:, 3] = np.repeat(np.arange(len(el)), int(n_azimuth))
+    return out
+
+
 def write_pcd(path: str, points, axes="loam"):
     """loamx_write_pcd: an (N, 4) / (N, 8) float32 cloud as a binary PCD v0.7 file (x y z intensity); axes="sensor" writes the sensor
     axes ingestion started from (x_s = z, y_s = x, z_s = y).  Host only."""
@@ -1323,6 +1357,53 @@ class DenseMap:
         rc = _check(lib().loamx_densemap_align_from_pipeline(self.h, pipeline.h, C.c_uint32(slot),
                                                              None if p is None else p.ctypes.data_as(C.c_void_p), C.byref(k), C.byref(out)))
         return rc, out.as_dict()
+
+    def _raycast(self, fn, head, n, max_steps, skip_steps, min_points, static, records):
+        k = _cfg(RaycastConfig, "loamx_densemap_raycast_default_config", max_steps=max_steps, skip_steps=skip_steps, min_points=min_points)
+        out = np.zeros(max(n, 1), RAY_DTYPE) if records else None
+        counts = np.zeros(5, np.uint64)
+        rc = _check(fn(self.h, *head, C.byref(k), C.byref(static) if static is not None else None,
+                       out.ctypes.data_as(C.c_void_p) if records else None, C.c_uint64(n), counts.ctypes.data_as(C.c_void_p)))
+        return rc, (out[:n] if records else None), dict(zip(RAY_COUNTS, (int(v) for v in counts)))
+
+    def raycast(self, ends, origin=(0.0, 0.0, 0.0), max_steps=4096, skip_steps=0, min_points=1, static=None, records=True):
+        """loamx_densemap_raycast: ray i from origin to ends[i] ((N, 4) / (N, 8), map frame) through the live map, to the first voxel
+        with at least min_points points that static (a StaticRule; needs carving) does not call dynamic; the cells before skip_steps
+        are not looked up.  Returns (records, counts): a structured array of RAY_DTYPE, one record per ray (None with
+        records=False), and a dict in the order of RAY_COUNTS.  Blocks."""
+        a = as_points(ends)
+        c = cloud_of(a)
+        o = np.ascontiguousarray(origin, np.float32)
+        assert o.shape == (3,)
+        _, out, counts = self._raycast(lib().loamx_densemap_raycast, (C.byref(c), o.ctypes.data_as(C.c_void_p)), len(a), max_steps,
+                                       skip_steps, min_points, static, records)
+        return out, counts
+
+    def _raycast_device(self, fn, head, capacity, max_steps, skip_steps, min_points, static, records):
+        # (the registered cloud's count is the device's to know: the room for the records doubles until they fit, each refusal
+        # coming before anything is launched; the first four counts add up to the count)
+        while True:
+            try:
+                rc, out, counts = self._raycast(fn, head, int(capacity), max_steps, skip_steps, min_points, static, records)
+            except LoamxError as e:
+                if e.code != E_CAPACITY:
+                    raise
+                capacity = 2 * int(capacity)
+                continue
+            n = sum(counts[k] for k in RAY_COUNTS[:4])
+            return rc, (out[:n] if records else None), counts
+
+    def raycast_from(self, mapping, max_steps=4096, skip_steps=0, min_points=1, static=None, records=True, capacity=1 << 17):
+        """loamx_densemap_raycast_from_map: the rays of the registered cloud of mapping's last process, where it lies, from its
+        origin; capacity = the room for the records to start with.  Returns (status code OK / SKIPPED, records, counts)"""
+        return self._raycast_device(lib().loamx_densemap_raycast_from_map, (mapping.h,), capacity, max_steps, skip_steps, min_points,
+                                    static, records)
+
+    def raycast_from_pipeline(self, pipeline, slot: int, max_steps=4096, skip_steps=0, min_points=1, static=None, records=True,
+                              capacity=1 << 17):
+        """loamx_densemap_raycast_from_pipeline: the same for the slot-th stream registered in pipeline's last step"""
+        return self._raycast_device(lib().loamx_densemap_raycast_from_pipeline, (pipeline.h, C.c_uint32(slot)), capacity, max_steps,
+                                    skip_steps, min_points, static, records)
 
     def save(self, path: str):
         """loamx_densemap_save: every word of the map as an 'LXDM' file (include/loamx.h), written beside path and renamed.  The
