@@ -879,6 +879,63 @@ int loamx_densemap_align_from_map(loamx_densemap* h, loamx_map* m, const double 
 int loamx_densemap_align_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot, const double pose_in[12],
                                        const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out);
 
+/* Many start poses at once (optional: a handle that never calls these runs the kernels it ran and allocates what it allocated).  The
+ * basin of loamx_densemap_align is a few leaves wide; a loop candidate of loamx_place (a yaw hint quantised to 2 pi / n_sectors, no
+ * translation) or a sweep to be re-localised in a loaded map needs many starts tried and the best kept.  Every hypothesis is
+ * independent and every word of a step is an integer sum, so the batched forms are defined by the single ones, to the bit.
+ *
+ * loamx_densemap_align_step_many: the linearisation of align_step about n_poses poses, rtc[15 k ..] = R row-major, t, c of pose k
+ * (1 <= n_poses <= LOAMX_ALIGN_MAX_POSES).  The cloud is staged once; one memset, ONE launch (kernel k_dm_align_step_many: the poses
+ * lie in a table in device memory, a second grid dimension runs over them) and one readback through pinned memory cover all poses.
+ * sums[28 k ..] and counts[5 k ..] are exactly the words loamx_densemap_align_step gives for rtc[15 k ..]: the same f32 expressions in
+ * the same order, the same candidate order and tie rule, the same fixed-point scaling.  The order of the poses changes nothing but the
+ * order of the outputs.  An empty cloud gives zeros and no launch.
+ *
+ * loamx_densemap_align_many: the Gauss-Newton loop of loamx_densemap_align for the n_poses start poses poses_in[12 k ..] in lockstep.
+ * In iteration it = 0, 1, ... the hypotheses that have not ended — a hypothesis ends when it converged, when a step gave it fewer than
+ * min_matched matches, or after max_iterations steps — are compacted in ascending index; the f32 roundings of their R, t, c go up in
+ * one copy, one launch linearises them, one readback of 33 * n_active words returns, and the host solves and updates each one in double
+ * with the functions of the single loop.  out[k] is byte for byte what loamx_densemap_align returns for poses_in[12 k ..] with the same
+ * cloud, centre and cfg: pose, iterations, degenerate_dims, status, rms and counts.  A call whose longest hypothesis runs I iterations
+ * costs I launches and I blocking readbacks, whatever n_poses.
+ * The from_* forms read the registered cloud where it lies, behind an event, as align_from_* do, with its origin as the centre;
+ * poses_in NULL is allowed only with n_poses == 1 and means the identity.  LOAMX_SKIPPED without a cloud, LOAMX_E_INVALID on another
+ * device.
+ *
+ * loamx_densemap_align_best (host only): the candidates are the results with status != 2; the best is the one with the largest
+ * counts[4] (matched), then the smallest rms, then the smallest index.  *best = UINT32_MAX when there is no candidate (n == 0
+ * included), which is still LOAMX_OK.  align_many and its from_* forms write the same value to *best (may be NULL).
+ * A CONVERGED STATUS IS NOT EVIDENCE OF A CORRECT POSE: a start in the wrong basin converges too (a box's half-turn look-alike
+ * converges with every point matched).  The inlier count and the rms are the evidence; which threshold on them accepts a loop is the
+ * host's decision.
+ *
+ * loamx_densemap_get_align_stats: three counters that run from the handle's creation (reset does not clear them), counted by the
+ * single-pose functions too: stats[0] launches of either step kernel, stats[1] readbacks of accumulator words, stats[2] pose-steps
+ * (the sum of n_active over the launches; a single step counts 1).
+ *
+ * Refused with LOAMX_E_INVALID, a message that names the argument, and nothing written: a NULL argument (centre, cfg, best and the
+ * from_* forms' poses_in as stated above excepted); n_poses == 0 or > LOAMX_ALIGN_MAX_POSES; neighbourhood, max_residual and cfg as for
+ * the single forms; a start pose that is not finite (the whole call); no snapshot.
+ *
+ * Start poses for a place-recognition match (Python: loamx.pose_grid): with the stored entry's sweep registered at P_e = (R_e, t_e),
+ * sensor origin o_e, and a query whose loamx_place match reports yaw_hint, the query's pose is near R = Ry(+yaw_hint) R_e, Ry = rot_y
+ * of the pose convention (about +y, turning +z towards +x), with the sensor origin at o_e: shift k of a match corresponds to the
+ * query cloud being the stored cloud rotated by -k * 2 pi / S about +y, that is to the query sensor having turned by +k * 2 pi / S.
+ * The hint is used as it is, with its sign (a cloud rotated by +k steps gets shift S - k).  Exact for a levelled stored pose (R_e a
+ * rotation about +y), to first order in its pitch and roll otherwise. */
+#define LOAMX_ALIGN_MAX_POSES 4096
+int loamx_densemap_align_step_many(loamx_densemap* h, const loamx_cloud* points, const float* rtc /* 15 * n_poses */, uint32_t n_poses,
+                                   uint32_t neighbourhood, float max_residual, int64_t* sums /* 28 * n_poses */, uint64_t* counts /* 5 * n_poses */);
+int loamx_densemap_align_many(loamx_densemap* h, const loamx_cloud* points, const double* poses_in /* 12 * n_poses */, uint32_t n_poses,
+                              const float centre[3] /* NULL: 0 */, const loamx_densemap_align_config* cfg,
+                              loamx_densemap_align_result* out /* n_poses */, uint32_t* best /* may be NULL */);
+int loamx_densemap_align_many_from_map(loamx_densemap* h, loamx_map* m, const double* poses_in, uint32_t n_poses,
+                                       const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out, uint32_t* best);
+int loamx_densemap_align_many_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot, const double* poses_in, uint32_t n_poses,
+                                            const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out, uint32_t* best);
+int loamx_densemap_align_best(const loamx_densemap_align_result* results, uint32_t n, uint32_t* best);   /* host only, no device */
+int loamx_densemap_get_align_stats(loamx_densemap* h, uint64_t stats[3]);
+
 /* A prior map: native save / load, and the exact merge of two maps (optional: a handle that never calls them runs the kernels it
  * ran).  Every word of a voxel is an integer sum, so the map can be written out and read back without loss, and two maps of the same
  * leaf can be combined by adding words per key.

@@ -54,6 +54,14 @@ class DmFrozen {
   // one linearisation (include/loamx.h, loamx_densemap_align_step); blocks until the 33 words are back
   void step(const float4* pts, uint32_t n, const float rtc[15], float inv, uint32_t neighbourhood, float max_residual, hipStream_t st,
             int64_t sums[28], uint64_t counts[5]);
+  // the same about n_poses poses in one memset, one launch and one readback (loamx_densemap_align_step_many): pose_table() hands out
+  // room for n_poses records of 16 floats in pinned memory (R, t, c, one unused), to be filled before the call; the result is the 33
+  // words per pose in pinned memory, valid until the next step of either kind
+  float* pose_table(uint32_t n_poses);
+  const unsigned long long* step_many(const float4* pts, uint32_t n, uint32_t n_poses, float inv, uint32_t neighbourhood, float max_residual,
+                                      hipStream_t st);
+  // launches of either step kernel, readbacks of accumulator words, pose-steps (loamx_densemap_get_align_stats); never cleared
+  const uint64_t* stats() const { return stats_; }
 
  private:
   DmFrozenEntry* tab_ = nullptr;
@@ -63,6 +71,9 @@ class DmFrozen {
   PinBuf<uint32_t> h_acc_;
   PinBuf<float4> h_pts_;
   DevBuf<float4> d_pts_;
+  PinBuf<float4> h_poses_;
+  DevBuf<float4> d_poses_;
+  uint64_t stats_[3] = {0, 0, 0};
 };
 
 }  // namespace loamx

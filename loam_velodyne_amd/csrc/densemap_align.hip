@@ -8,6 +8,10 @@
 // the point-to-plane residual and the 28 fixed-point terms of J^T J, J^T r and r^2.  All 33 words are integers: they are summed in the wave (shuffles), then in the block
 // (LDS), and one lane per word adds the block's sum to the global accumulator, so the result depends on no order.  The words come back
 // through pinned memory; the 6x6 solve and the pose update are the host's, in double.
+//
+// k_dm_align_step_many is the same linearisation about many poses at once, a second grid dimension over a table of poses in device
+// memory: one launch and one readback per iteration for all the start poses of loamx_densemap_align_many, which runs the Gauss-Newton
+// loops of its hypotheses in lockstep.  Both kernels compile from one text (dm_align_step_body.inc), so every word equals the single step's.
 #include "densemap.hpp"
 #include "pinned_copy.hpp"
 
@@ -23,6 +27,12 @@ struct DmAlign {
   float inv, max_residual;
   int nb;
 };
+
+// one pose of k_dm_align_step_many's table: 64 bytes, so that a table is a whole number of float4 for the pinned-memory fetch
+struct DmAlignPose {
+  float R[9], t[3], c[3], pad;
+};
+static_assert(sizeof(DmAlignPose) == 64, "a pose is four float4");
 
 // keys are unique: the first free slot of the probe sequence is claimed and its payload written (read by later launches only)
 __global__ __launch_bounds__(256) void k_dm_freeze_insert(const unsigned long long* __restrict__ keys, const float* __restrict__ rec, uint32_t n,
@@ -67,93 +77,28 @@ __device__ inline bool dm_frozen_find(const DmFrozenEntry* tab, uint32_t mask, u
   return false;
 }
 
-// acc: [0, 28) the sums (two's complement), [28, 33) far, outside, unmatched, rejected, matched.  f32, no fused multiply-add (the
-// file is built without contraction): the expressions are those of include/loamx.h, in its order
 __global__ __launch_bounds__(256) void k_dm_align_step(const float4* __restrict__ pts, uint32_t n, DmAlign A, const DmFrozenEntry* __restrict__ tab,
                                                        uint32_t mask, uint32_t shift, unsigned long long* __restrict__ acc) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
-  int cls = -1;   // the counter this point goes to (-1: no point)
-  long long s[DM_ALIGN_SUMS];
+#include "dm_align_step_body.inc"
+}
+
+// The same linearisation about gridDim.y poses in one launch: block (x, y) takes the points of block x about poses[y] and adds its 33
+// words to acc[33 * y ..].  The pose is uniform in the block, so its 15 floats arrive by scalar loads as the kernel arguments of
+// k_dm_align_step do; registers and occupancy are those of the single step, and the poses fill the CUs a small cloud leaves idle
+__global__ __launch_bounds__(256) void k_dm_align_step_many(const float4* __restrict__ pts, uint32_t n, const DmAlignPose* __restrict__ poses,
+                                                            float inv, float max_residual, int nb, const DmFrozenEntry* __restrict__ tab,
+                                                            uint32_t mask, uint32_t shift, unsigned long long* __restrict__ acc_all) {
+  const DmAlignPose& P = poses[blockIdx.y];
+  DmAlign A;
 #pragma unroll
-  for (int k = 0; k < DM_ALIGN_SUMS; k++) s[k] = 0ll;
-  if (i < n) {
-    const float4 p = pts[i];
-    const float dx = p.x - A.c[0], dy = p.y - A.c[1], dz = p.z - A.c[2];
-    float a[3], pp[3], fi[3];
+  for (int k = 0; k < 9; k++) A.R[k] = P.R[k];
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-      a[k] = (A.R[3 * k] * dx + A.R[3 * k + 1] * dy) + A.R[3 * k + 2] * dz;
-      pp[k] = a[k] + A.t[k];
-      fi[k] = floorf(pp[k] * A.inv);
-    }
-    if (!(fabsf(a[0]) < DM_ALIGN_FAR && fabsf(a[1]) < DM_ALIGN_FAR && fabsf(a[2]) < DM_ALIGN_FAR)) {
-      cls = 0;   // (NaN too)
-    } else if (!(fabsf(fi[0]) < DM_IMAX && fabsf(fi[1]) < DM_IMAX && fabsf(fi[2]) < DM_IMAX)) {
-      cls = 1;
-    } else {
-      const int ic[3] = {(int)fi[0], (int)fi[1], (int)fi[2]};
-      const int lim = 1 << DM_QBITS;
-      bool found = false;
-      float best = 0.f, e[3] = {0.f, 0.f, 0.f};
-      uint32_t at = 0u;
-      for (int oz = -A.nb; oz <= A.nb; oz++)
-        for (int oy = -A.nb; oy <= A.nb; oy++)
-          for (int ox = -A.nb; ox <= A.nb; ox++) {
-            const int cx = ic[0] + ox, cy = ic[1] + oy, cz = ic[2] + oz;
-            if (cx <= -lim || cx >= lim || cy <= -lim || cy >= lim || cz <= -lim || cz >= lim) continue;   // outside the key range
-            const unsigned long long key = (unsigned long long)(uint32_t)(cx + lim) | ((unsigned long long)(uint32_t)(cy + lim) << DM_KBITS) |
-                                           ((unsigned long long)(uint32_t)(cz + lim) << (2 * DM_KBITS));
-            uint32_t slot = 0u;
-            float mx = 0.f, my = 0.f;
-            if (!dm_frozen_find(tab, mask, shift, key, slot, mx, my)) continue;
-            const float ex = pp[0] - mx, ey = pp[1] - my, ez = pp[2] - tab[slot].mean[2];
-            const float d2 = (ex * ex + ey * ey) + ez * ez;
-            if (!found || d2 < best) {
-              found = true; best = d2; at = slot;
-              e[0] = ex; e[1] = ey; e[2] = ez;
-            }
-          }
-      if (!found) {
-        cls = 2;
-      } else {
-        const float4 w = *(const float4*)&tab[at].mean[2];   // mean z and the normal: the entry's second 16 bytes
-        const float nx = w.y, ny = w.z, nz = w.w;
-        const float r = (nx * e[0] + ny * e[1]) + nz * e[2];
-        if (!(fabsf(r) <= A.max_residual)) {
-          cls = 3;
-        } else {
-          cls = 4;
-          const float J[6] = {a[1] * nz - a[2] * ny, a[2] * nx - a[0] * nz, a[0] * ny - a[1] * nx, nx, ny, nz};
-          int w_ = 0;
-#pragma unroll
-          for (int k = 0; k < 6; k++)
-#pragma unroll
-            for (int l = k; l < 6; l++) s[w_++] = (long long)rintf((J[k] * J[l]) * DM_ALIGN_HSCALE);
-#pragma unroll
-          for (int k = 0; k < 6; k++) s[21 + k] = (long long)rintf((J[k] * r) * DM_ALIGN_GSCALE);
-          s[27] = (long long)rintf((r * r) * DM_ALIGN_GSCALE);
-        }
-      }
-    }
-  }
-  __shared__ unsigned long long part[4][DM_ALIGN_WORDS];
-  const bool any_matched = __ballot(cls == 4) != 0ull;   // (wave-uniform: a wave without a match has nothing but zeros to sum)
-#pragma unroll
-  for (int k = 0; k < DM_ALIGN_SUMS; k++) {
-    const unsigned long long v = any_matched ? dm_wave_sum_u64((unsigned long long)s[k]) : 0ull;
-    if (lane == 0) part[wid][k] = v;
-  }
-#pragma unroll
-  for (int k = 0; k < DM_ALIGN_COUNTS; k++) {
-    const unsigned long long m = __ballot(cls == k);
-    if (lane == 0) part[wid][DM_ALIGN_SUMS + k] = (unsigned long long)__popcll(m);
-  }
-  __syncthreads();
-  if (threadIdx.x < (uint32_t)DM_ALIGN_WORDS) {
-    const unsigned long long v = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
-    if (v) atomicAdd(&acc[threadIdx.x], v);   // (integer, modulo 2^64: the order does not matter)
-  }
+  for (int k = 0; k < 3; k++) { A.t[k] = P.t[k]; A.c[k] = P.c[k]; }
+  A.inv = inv;
+  A.max_residual = max_residual;
+  A.nb = nb;
+  unsigned long long* __restrict__ acc = acc_all + (size_t)DM_ALIGN_WORDS * blockIdx.y;
+#include "dm_align_step_body.inc"
 }
 
 static uint32_t log2u(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }
@@ -227,12 +172,44 @@ void DmFrozen::step(const float4* pts, uint32_t n, const float rtc[15], float in
     A.nb = (int)neighbourhood;
     hipLaunchKernelGGL(k_dm_align_step, dim3((n + 255u) / 256u), dim3(256), 0, st, pts, n, A, tab_, slots_ - 1u, 64u - log2u(slots_), acc_.p);
     LX_HIP(hipGetLastError());
+    stats_[0]++;
+    stats_[2]++;
   }
   store_to_pinned_u32(h_acc_.p, (const uint32_t*)acc_.p, 2 * DM_ALIGN_WORDS, st);
   LX_HIP(hipStreamSynchronize(st));
+  stats_[1]++;
   const unsigned long long* w = (const unsigned long long*)h_acc_.p;
   for (int k = 0; k < DM_ALIGN_SUMS; k++) sums[k] = (int64_t)w[k];
   for (int k = 0; k < DM_ALIGN_COUNTS; k++) counts[k] = w[DM_ALIGN_SUMS + k];
+}
+
+float* DmFrozen::pose_table(uint32_t n_poses) {
+  h_poses_.reserve(4 * (size_t)n_poses);
+  return (float*)h_poses_.p;
+}
+
+const unsigned long long* DmFrozen::step_many(const float4* pts, uint32_t n, uint32_t n_poses, float inv, uint32_t neighbourhood,
+                                              float max_residual, hipStream_t st) {
+  LX_REQUIRE(valid(), "nothing is frozen (loamx_densemap_freeze)");
+  LX_REQUIRE(n_poses >= 1u && n_poses <= LOAMX_ALIGN_MAX_POSES && h_poses_.cap >= 4 * (size_t)n_poses, "align: pose table out of range");
+  const size_t words = (size_t)DM_ALIGN_WORDS * n_poses;
+  acc_.reserve(words);
+  h_acc_.reserve(2 * words);
+  LX_HIP(hipMemsetAsync(acc_.p, 0, sizeof(unsigned long long) * words, st));
+  if (n) {
+    d_poses_.reserve(4 * (size_t)n_poses);
+    fetch_from_pinned(d_poses_.p, h_poses_.p, 4 * (size_t)n_poses, st);
+    // (grid y = n_poses <= 4096 records of the table just fetched; acc_ holds 33 words for each of them)
+    hipLaunchKernelGGL(k_dm_align_step_many, dim3((n + 255u) / 256u, n_poses), dim3(256), 0, st, pts, n, (const DmAlignPose*)d_poses_.p, inv,
+                       max_residual, (int)neighbourhood, tab_, slots_ - 1u, 64u - log2u(slots_), acc_.p);
+    LX_HIP(hipGetLastError());
+    stats_[0]++;
+    stats_[2] += n_poses;
+  }
+  store_to_pinned_u32(h_acc_.p, (const uint32_t*)acc_.p, 2 * words, st);
+  LX_HIP(hipStreamSynchronize(st));
+  stats_[1]++;
+  return (const unsigned long long*)h_acc_.p;
 }
 
 // Eigen-decomposition of a symmetric 6x6 matrix in double by cyclic Jacobi rotations (host_math.h's jacobi_eig3 at n = 6): a is
@@ -323,33 +300,34 @@ static loamx_densemap_align_config checked_align_config(const loamx_densemap_ali
   return c;
 }
 
-// the loop of include/loamx.h over a cloud that lies on the device; pose_in NULL: identity
-static int align_loop(loamx_densemap* h, const float4* pts, uint32_t n, const double pose_in[12], const float centre[3],
-                      const loamx_densemap_align_config& c, hipStream_t st, loamx_densemap_align_result* out) {
-  static const double ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  const double* P = pose_in ? pose_in : ident;
-  for (int k = 0; k < 12; k++) LX_REQUIRE(std::isfinite(P[k]), "the pose must be finite");
-  const double cc[3] = {centre ? (double)centre[0] : 0.0, centre ? (double)centre[1] : 0.0, centre ? (double)centre[2] : 0.0};
+// One hypothesis of the Gauss-Newton loop of include/loamx.h: the host's pose in double, about the centre cc.  begin() and update() are
+// the whole arithmetic of the loop, shared by the single alignment and the lockstep loop over many start poses
+struct AlignHyp {
   double R[9], t[3];
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) R[3 * i + j] = P[4 * i + j];
-    t[i] = ((R[3 * i] * cc[0] + R[3 * i + 1] * cc[1]) + R[3 * i + 2] * cc[2]) + P[4 * i + 3];
+
+  // pose_in NULL: identity
+  void begin(const double pose_in[12], const double cc[3], loamx_densemap_align_result* out) {
+    static const double ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    const double* P = pose_in ? pose_in : ident;
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) R[3 * i + j] = P[4 * i + j];
+      t[i] = ((R[3 * i] * cc[0] + R[3 * i + 1] * cc[1]) + R[3 * i + 2] * cc[2]) + P[4 * i + 3];
+    }
+    memset(out, 0, sizeof(*out));
+    for (int k = 0; k < 12; k++) out->pose[k] = P[k];
+    out->status = 1;
   }
-  memset(out, 0, sizeof(*out));
-  for (int k = 0; k < 12; k++) out->pose[k] = P[k];
-  out->status = 1;
-  DmFrozen& F = loamx_densemap_frozen(h);
-  const float inv = 1.0f / loamx_densemap_cfg(h).leaf;
-  for (uint32_t it = 0; it < c.max_iterations; it++) {
-    float rtc[15];
-    for (int k = 0; k < 9; k++) rtc[k] = (float)R[k];
-    for (int k = 0; k < 3; k++) { rtc[9 + k] = (float)t[k]; rtc[12 + k] = (float)cc[k]; }
-    int64_t sums[28];
-    F.step(pts, n, rtc, inv, c.neighbourhood, c.max_residual, st, sums, out->counts);
+  // the f32 roundings a step takes: R, t, c
+  void rtc(const double cc[3], float out[15]) const {
+    for (int k = 0; k < 9; k++) out[k] = (float)R[k];
+    for (int k = 0; k < 3; k++) { out[9 + k] = (float)t[k]; out[12 + k] = (float)cc[k]; }
+  }
+  // iteration `it` from the sums of its step (out->counts hold its counts already); true: the loop of this hypothesis has ended
+  bool update(uint32_t it, const int64_t sums[28], const double cc[3], const loamx_densemap_align_config& c, loamx_densemap_align_result* out) {
     out->iterations = it + 1;
     const uint64_t matched = out->counts[4];
     out->rms = matched ? std::sqrt(((double)sums[27] / 16777216.0) / (double)matched) : 0.0;
-    if (matched < c.min_matched) { out->status = 2; break; }
+    if (matched < c.min_matched) { out->status = 2; return true; }
     double x[6];
     align_solve(sums, (double)c.degenerate_ratio, x, out->degenerate_dims);
     rotate_left(R, x);
@@ -359,28 +337,128 @@ static int align_loop(loamx_densemap* h, const float4* pts, uint32_t n, const do
       out->pose[4 * i + 3] = t[i] - ((R[3 * i] * cc[0] + R[3 * i + 1] * cc[1]) + R[3 * i + 2] * cc[2]);
     }
     const double wn = std::sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]), vn = std::sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]);
-    if (wn < (double)c.eps_rot && vn < (double)c.eps_trans) { out->status = 0; break; }
+    if (wn < (double)c.eps_rot && vn < (double)c.eps_trans) { out->status = 0; return true; }
+    return it + 1 >= c.max_iterations;
+  }
+};
+
+static void pose_must_be_finite(const double* P, size_t n_words) {
+  for (size_t k = 0; k < n_words; k++) LX_REQUIRE(std::isfinite(P[k]), "the pose must be finite");
+}
+
+// the loop of include/loamx.h over a cloud that lies on the device; pose_in NULL: identity
+static int align_loop(loamx_densemap* h, const float4* pts, uint32_t n, const double pose_in[12], const float centre[3],
+                      const loamx_densemap_align_config& c, hipStream_t st, loamx_densemap_align_result* out) {
+  if (pose_in) pose_must_be_finite(pose_in, 12);
+  const double cc[3] = {centre ? (double)centre[0] : 0.0, centre ? (double)centre[1] : 0.0, centre ? (double)centre[2] : 0.0};
+  AlignHyp hyp;
+  hyp.begin(pose_in, cc, out);
+  DmFrozen& F = loamx_densemap_frozen(h);
+  const float inv = 1.0f / loamx_densemap_cfg(h).leaf;
+  for (uint32_t it = 0; it < c.max_iterations; it++) {
+    float rtc[15];
+    hyp.rtc(cc, rtc);
+    int64_t sums[28];
+    F.step(pts, n, rtc, inv, c.neighbourhood, c.max_residual, st, sums, out->counts);
+    if (hyp.update(it, sums, cc, c, out)) break;
   }
   return LOAMX_OK;
 }
 
-// the cloud of a mapper / a pipeline where it lies: the handle's own stream runs behind the stream that wrote it
-static int align_from_source(loamx_densemap* h, const DenseSource& s, const double pose_in[12], const loamx_densemap_align_config* cfg,
-                             loamx_densemap_align_result* out) {
+// loamx_densemap_align_best
+static uint32_t align_best(const loamx_densemap_align_result* r, uint32_t n) {
+  uint32_t best = UINT32_MAX;
+  for (uint32_t k = 0; k < n; k++) {
+    if (r[k].status == 2) continue;
+    if (best == UINT32_MAX || r[k].counts[4] > r[best].counts[4] || (r[k].counts[4] == r[best].counts[4] && r[k].rms < r[best].rms)) best = k;
+  }
+  return best;
+}
+
+// The loops of n_poses hypotheses in lockstep (include/loamx.h, loamx_densemap_align_many): per iteration the hypotheses still running,
+// compacted in ascending index, go up as one table and come back as 33 words each.  The poses have been checked; poses_in NULL
+// (n_poses 1): identity
+static int align_many_loop(loamx_densemap* h, const float4* pts, uint32_t n, const double* poses_in, uint32_t n_poses, const float centre[3],
+                           const loamx_densemap_align_config& c, hipStream_t st, loamx_densemap_align_result* out, uint32_t* best) {
+  const double cc[3] = {centre ? (double)centre[0] : 0.0, centre ? (double)centre[1] : 0.0, centre ? (double)centre[2] : 0.0};
+  std::vector<AlignHyp> hyp(n_poses);
+  std::vector<uint32_t> active(n_poses);
+  for (uint32_t k = 0; k < n_poses; k++) {
+    hyp[k].begin(poses_in ? poses_in + 12 * (size_t)k : nullptr, cc, out + k);
+    active[k] = k;
+  }
+  DmFrozen& F = loamx_densemap_frozen(h);
+  const float inv = 1.0f / loamx_densemap_cfg(h).leaf;
+  for (uint32_t it = 0; it < c.max_iterations && !active.empty(); it++) {
+    const uint32_t n_active = (uint32_t)active.size();
+    float* table = F.pose_table(n_active);
+    for (uint32_t a = 0; a < n_active; a++) {
+      hyp[active[a]].rtc(cc, table + 16 * (size_t)a);
+      table[16 * (size_t)a + 15] = 0.f;
+    }
+    const unsigned long long* w = F.step_many(pts, n, n_active, inv, c.neighbourhood, c.max_residual, st);
+    size_t kept = 0;
+    for (uint32_t a = 0; a < n_active; a++) {
+      const uint32_t k = active[a];
+      const unsigned long long* wk = w + (size_t)DM_ALIGN_WORDS * a;
+      int64_t sums[28];
+      for (int j = 0; j < DM_ALIGN_SUMS; j++) sums[j] = (int64_t)wk[j];
+      for (int j = 0; j < DM_ALIGN_COUNTS; j++) out[k].counts[j] = wk[DM_ALIGN_SUMS + j];
+      if (!hyp[k].update(it, sums, cc, c, out + k)) active[kept++] = k;
+    }
+    active.resize(kept);
+  }
+  if (best) *best = align_best(out, n_poses);
+  return LOAMX_OK;
+}
+
+// the cloud of a mapper / a pipeline where it lies: the handle's own stream runs behind the stream that wrote it.  false: no cloud
+static bool align_source_ready(loamx_densemap* h, const DenseSource& s, const loamx_densemap_align_config* cfg, loamx_densemap_align_config& c,
+                               hipStream_t& st) {
   const loamx_densemap_config& mc = loamx_densemap_cfg(h);
   LX_REQUIRE(s.device == mc.device, "the dense map and its source live on different devices");
-  const loamx_densemap_align_config c = checked_align_config(cfg, mc.leaf);
+  c = checked_align_config(cfg, mc.leaf);
   LX_REQUIRE(loamx_densemap_frozen(h).valid(), "nothing is frozen (loamx_densemap_freeze)");
-  if (!s.has_cloud) return LOAMX_SKIPPED;
+  if (!s.has_cloud) return false;
   LX_HIP(hipSetDevice(mc.device));
-  hipStream_t st = loamx_densemap_own_stream(h);
+  st = loamx_densemap_own_stream(h);
   hipEvent_t ev = nullptr;
   LX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   hipError_t e = hipEventRecord(ev, s.stream);
   if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
   (void)hipEventDestroy(ev);   // (the wait keeps what it needs)
   LX_HIP(e);
+  return true;
+}
+
+static int align_from_source(loamx_densemap* h, const DenseSource& s, const double pose_in[12], const loamx_densemap_align_config* cfg,
+                             loamx_densemap_align_result* out) {
+  loamx_densemap_align_config c;
+  hipStream_t st = nullptr;
+  if (!align_source_ready(h, s, cfg, c, st)) return LOAMX_SKIPPED;
   return align_loop(h, s.pts, s.n, pose_in, s.origin, c, st, out);
+}
+
+static void not_null(const void* p, const char* name) {
+  if (!p) throw Error(LOAMX_E_INVALID, std::string("NULL argument: ") + name);
+}
+
+static void check_start_poses(const double* poses_in, uint32_t n_poses, bool null_is_identity) {
+  LX_REQUIRE(n_poses >= 1u && n_poses <= LOAMX_ALIGN_MAX_POSES, "n_poses must be in [1, LOAMX_ALIGN_MAX_POSES]");
+  if (!poses_in) {
+    LX_REQUIRE(null_is_identity && n_poses == 1u, "poses_in may be NULL (the identity) only with n_poses == 1");
+    return;
+  }
+  pose_must_be_finite(poses_in, 12 * (size_t)n_poses);
+}
+
+static int align_many_from_source(loamx_densemap* h, const DenseSource& s, const double* poses_in, uint32_t n_poses,
+                                  const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out, uint32_t* best) {
+  check_start_poses(poses_in, n_poses, true);
+  loamx_densemap_align_config c;
+  hipStream_t st = nullptr;
+  if (!align_source_ready(h, s, cfg, c, st)) return LOAMX_SKIPPED;
+  return align_many_loop(h, s.pts, s.n, poses_in, n_poses, s.origin, c, st, out, best);
 }
 
 }  // namespace loamx
@@ -439,6 +517,99 @@ int loamx_densemap_align(loamx_densemap* h, const loamx_cloud* points, const dou
     hipStream_t st = loamx_densemap_own_stream(h);
     const float4* pts = F.stage(points, st);
     return align_loop(h, pts, points->count, pose_in, centre, c, st, out);
+  });
+}
+
+int loamx_densemap_align_step_many(loamx_densemap* h, const loamx_cloud* points, const float* rtc, uint32_t n_poses, uint32_t neighbourhood,
+                                   float max_residual, int64_t* sums, uint64_t* counts) {
+  return guard([&]() {
+    not_null(h, "h");
+    not_null(points, "points");
+    not_null(rtc, "rtc");
+    not_null(sums, "sums");
+    not_null(counts, "counts");
+    LX_REQUIRE(n_poses >= 1u && n_poses <= LOAMX_ALIGN_MAX_POSES, "n_poses must be in [1, LOAMX_ALIGN_MAX_POSES]");
+    LX_REQUIRE(neighbourhood <= 1u, "neighbourhood must be 0 or 1");
+    LX_REQUIRE(max_residual > 0.f && max_residual <= 16.f, "max_residual must be in (0, 16]");   // (NaN too)
+    DmFrozen& F = loamx_densemap_frozen(h);
+    LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
+    const loamx_densemap_config& mc = loamx_densemap_cfg(h);
+    LX_HIP(hipSetDevice(mc.device));
+    hipStream_t st = loamx_densemap_own_stream(h);
+    const float4* pts = F.stage(points, st);
+    float* table = F.pose_table(n_poses);
+    for (uint32_t k = 0; k < n_poses; k++) {
+      for (int j = 0; j < 15; j++) table[16 * (size_t)k + j] = rtc[15 * (size_t)k + j];
+      table[16 * (size_t)k + 15] = 0.f;
+    }
+    const unsigned long long* w = F.step_many(pts, points->count, n_poses, 1.0f / mc.leaf, neighbourhood, max_residual, st);
+    for (uint32_t k = 0; k < n_poses; k++) {
+      for (int j = 0; j < DM_ALIGN_SUMS; j++) sums[DM_ALIGN_SUMS * (size_t)k + j] = (int64_t)w[DM_ALIGN_WORDS * (size_t)k + j];
+      for (int j = 0; j < DM_ALIGN_COUNTS; j++) counts[DM_ALIGN_COUNTS * (size_t)k + j] = w[DM_ALIGN_WORDS * (size_t)k + DM_ALIGN_SUMS + j];
+    }
+    return LOAMX_OK;
+  });
+}
+
+int loamx_densemap_align_many(loamx_densemap* h, const loamx_cloud* points, const double* poses_in, uint32_t n_poses, const float centre[3],
+                              const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out, uint32_t* best) {
+  return guard([&]() {
+    not_null(h, "h");
+    not_null(points, "points");
+    not_null(poses_in, "poses_in");
+    not_null(out, "out");
+    check_start_poses(poses_in, n_poses, false);
+    const loamx_densemap_config& mc = loamx_densemap_cfg(h);
+    const loamx_densemap_align_config c = checked_align_config(cfg, mc.leaf);
+    DmFrozen& F = loamx_densemap_frozen(h);
+    LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
+    LX_HIP(hipSetDevice(mc.device));
+    hipStream_t st = loamx_densemap_own_stream(h);
+    const float4* pts = F.stage(points, st);
+    return align_many_loop(h, pts, points->count, poses_in, n_poses, centre, c, st, out, best);
+  });
+}
+
+int loamx_densemap_align_many_from_map(loamx_densemap* h, loamx_map* m, const double* poses_in, uint32_t n_poses,
+                                       const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out, uint32_t* best) {
+  return guard([&]() {
+    not_null(h, "h");
+    not_null(m, "m");
+    not_null(out, "out");
+    DenseSource s;
+    loamx_map_dense_source(m, s);
+    return align_many_from_source(h, s, poses_in, n_poses, cfg, out, best);
+  });
+}
+
+int loamx_densemap_align_many_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot, const double* poses_in, uint32_t n_poses,
+                                            const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out, uint32_t* best) {
+  return guard([&]() {
+    not_null(h, "h");
+    not_null(p, "p");
+    not_null(out, "out");
+    DenseSource s;
+    loamx_pipeline_dense_source(p, slot, s);
+    return align_many_from_source(h, s, poses_in, n_poses, cfg, out, best);
+  });
+}
+
+int loamx_densemap_align_best(const loamx_densemap_align_result* results, uint32_t n, uint32_t* best) {
+  return guard([&]() {
+    not_null(results, "results");
+    not_null(best, "best");
+    *best = align_best(results, n);
+    return LOAMX_OK;
+  });
+}
+
+int loamx_densemap_get_align_stats(loamx_densemap* h, uint64_t stats[3]) {
+  return guard([&]() {
+    not_null(h, "h");
+    not_null(stats, "stats");
+    const uint64_t* s = loamx_densemap_frozen(h).stats();
+    for (int k = 0; k < 3; k++) stats[k] = s[k];
+    return LOAMX_OK;
   });
 }
 

@@ -1116,6 +1116,44 @@ def align_solve(sums, degenerate_ratio=1e-4):
     return x, int(dropped.value)
 
 
+ALIGN_MAX_POSES = 4096   # LOAMX_ALIGN_MAX_POSES
+
+
+def align_best(results):
+    """loamx_densemap_align_best (host only): the index of the best of a list of AlignResult / an (n,) ctypes array of them — status
+    != 2, most matched, then the smallest rms, then the smallest index — or None when there is no candidate.  A converged status is
+    not evidence of a correct pose: judge the winner by its matched count and rms"""
+    arr = results if isinstance(results, C.Array) else (AlignResult * max(len(results), 1))(*results)
+    n = len(results)
+    best = C.c_uint32(0)
+    _check(lib().loamx_densemap_align_best(arr, C.c_uint32(n), C.byref(best)))
+    return None if best.value == 0xFFFFFFFF else int(best.value)
+
+
+def pose_grid(base, centre=None, yaws=(0,), offsets=((0, 0, 0),)) -> np.ndarray:
+    """Start poses for DenseMap.align_many around base (3x4, map <- cloud): for each yaw a (rad; rot_y of the pose convention, about
+    the image of centre, default 0) and each map-frame offset o, R = Ry(a) R_base and t' = (R_base c + t_base + o) - R c, so the image
+    of centre moves by exactly o.  Returns (len(yaws) * len(offsets), 3, 4) float64, yaw-major.  numpy only.
+    For a loamx_place match pass the stored entry's pose as base, its sensor origin as centre and the match's yaw_hint as it is
+    (yaws = yaw_hint + a few steps of 2 pi / n_sectors either side): shift k means the query sensor has turned by +k 2 pi / S."""
+    P = np.asarray(base, np.float64).reshape(3, 4)
+    c = np.zeros(3) if centre is None else np.asarray(centre, np.float64).reshape(3)
+    ys = np.asarray(yaws, np.float64).reshape(-1)
+    os_ = np.asarray(offsets, np.float64).reshape(-1, 3)
+    anchor = P[:, :3] @ c + P[:, 3]
+    out = np.zeros((len(ys) * len(os_), 3, 4), np.float64)
+    for i, a in enumerate(ys):
+        if a == 0.0:
+            R = P[:, :3].copy()   # (bit for bit the base)
+        else:
+            ca, sa = np.cos(a), np.sin(a)
+            R = np.array([[ca, 0.0, sa], [0.0, 1.0, 0.0], [-sa, 0.0, ca]]) @ P[:, :3]
+        for j, o in enumerate(os_):
+            out[i * len(os_) + j, :, :3] = R
+            out[i * len(os_) + j, :, 3] = P[:, 3] if a == 0.0 and not o.any() else (anchor + o) - R @ c
+    return out
+
+
 def _pose12(pose):
     p = np.ascontiguousarray(pose, np.float64)
     assert p.shape == (3, 4) or p.shape == (12,), "a pose is a row-major 3x4 matrix"
@@ -1357,6 +1395,72 @@ class DenseMap:
         rc = _check(lib().loamx_densemap_align_from_pipeline(self.h, pipeline.h, C.c_uint32(slot),
                                                              None if p is None else p.ctypes.data_as(C.c_void_p), C.byref(k), C.byref(out)))
         return rc, out.as_dict()
+
+    def align_step_many(self, points, rtc, neighbourhood=1, max_residual=None):
+        """loamx_densemap_align_step_many: the linearisation of align_step about the K poses rtc (K, 15) float32 in one launch.
+        Returns (sums (K, 28) int64, counts (K, 5) uint64): row k holds the words of align_step(points, rtc[k])"""
+        a = as_points(points)
+        c = cloud_of(a)
+        r = np.ascontiguousarray(rtc, np.float32)
+        assert r.ndim == 2 and r.shape[1] == 15
+        k = len(r)
+        sums, counts = np.zeros((max(k, 1), 28), np.int64), np.zeros((max(k, 1), 5), np.uint64)
+        mr = self._c.leaf if max_residual is None else max_residual
+        _check(lib().loamx_densemap_align_step_many(self.h, C.byref(c), r.ctypes.data_as(C.c_void_p), C.c_uint32(k), C.c_uint32(neighbourhood),
+                                                    C.c_float(mr), sums.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
+        return sums[:k], counts[:k]
+
+    @staticmethod
+    def _poses(poses):
+        p = np.ascontiguousarray(poses, np.float64)
+        assert p.ndim >= 2 and p.size == len(p) * 12, "start poses are (K, 3, 4) or (K, 12)"
+        return p.reshape(len(p), 12)
+
+    @staticmethod
+    def _many_out(rc, out, k, best, raw):
+        b = None if best.value == 0xFFFFFFFF else int(best.value)
+        return rc, (out if raw else [out[i].as_dict() for i in range(k)]), b
+
+    def align_many(self, points, poses, centre=None, raw=False, **cfg):
+        """loamx_densemap_align_many: align() from each of the K start poses (K, 3, 4), their Gauss-Newton loops in lockstep: one
+        launch and one readback per iteration for all of them.  Returns (results, best): results[k] is what align(points, poses[k],
+        centre, **cfg) returns (raw=True: the ctypes array of AlignResult instead of dicts), best the index align_best picks or None"""
+        a = as_points(points)
+        c = cloud_of(a)
+        p = self._poses(poses)
+        ctr = None if centre is None else np.ascontiguousarray(centre, np.float32)
+        assert ctr is None or ctr.shape == (3,)
+        k, out, best = AlignConfig(**cfg), (AlignResult * max(len(p), 1))(), C.c_uint32(0xFFFFFFFF)
+        rc = _check(lib().loamx_densemap_align_many(self.h, C.byref(c), p.ctypes.data_as(C.c_void_p), C.c_uint32(len(p)),
+                                                    None if ctr is None else ctr.ctypes.data_as(C.c_void_p), C.byref(k), out, C.byref(best)))
+        return self._many_out(rc, out, len(p), best, raw)[1:]
+
+    def align_many_from(self, mapping, poses=None, raw=False, **cfg):
+        """loamx_densemap_align_many_from_map: the same for the registered cloud of mapping's last process, where it lies, about its
+        origin; poses None: the identity alone.  Returns (status code OK / SKIPPED, results, best)"""
+        p = None if poses is None else self._poses(poses)
+        n = 1 if p is None else len(p)
+        k, out, best = AlignConfig(**cfg), (AlignResult * max(n, 1))(), C.c_uint32(0xFFFFFFFF)
+        rc = _check(lib().loamx_densemap_align_many_from_map(self.h, mapping.h, None if p is None else p.ctypes.data_as(C.c_void_p),
+                                                             C.c_uint32(n), C.byref(k), out, C.byref(best)))
+        return self._many_out(rc, out, n, best, raw)
+
+    def align_many_from_pipeline(self, pipeline, slot: int, poses=None, raw=False, **cfg):
+        """loamx_densemap_align_many_from_pipeline: the same for the slot-th stream registered in pipeline's last step"""
+        p = None if poses is None else self._poses(poses)
+        n = 1 if p is None else len(p)
+        k, out, best = AlignConfig(**cfg), (AlignResult * max(n, 1))(), C.c_uint32(0xFFFFFFFF)
+        rc = _check(lib().loamx_densemap_align_many_from_pipeline(self.h, pipeline.h, C.c_uint32(slot),
+                                                                  None if p is None else p.ctypes.data_as(C.c_void_p), C.c_uint32(n),
+                                                                  C.byref(k), out, C.byref(best)))
+        return self._many_out(rc, out, n, best, raw)
+
+    def align_stats(self) -> dict:
+        """loamx_densemap_get_align_stats: launches of either step kernel, readbacks of accumulator words and pose-steps (the sum of
+        the poses linearised over the launches) since the handle was created"""
+        s = (C.c_uint64 * 3)()
+        _check(lib().loamx_densemap_get_align_stats(self.h, s))
+        return dict(launches=int(s[0]), readbacks=int(s[1]), pose_steps=int(s[2]))
 
     def _raycast(self, fn, head, n, max_steps, skip_steps, min_points, static, records):
         k = _cfg(RaycastConfig, "loamx_densemap_raycast_default_config", max_steps=max_steps, skip_steps=skip_steps, min_points=min_points)
