@@ -22,6 +22,7 @@
 #include "scan.hpp"
 #include <algorithm>
 #include <numeric>
+#include <type_traits>
 
 namespace loamx {
 
@@ -43,8 +44,7 @@ struct DmCarve {
   uint32_t stride, end_margin, max_steps, seq;
 };
 // aux: 2 words per slot beside the table, [2 * slot] miss, [2 * slot + 1] stamp
-// mom: 9 words per slot beside the table, [9 * slot + k]: Mxx, Myy, Mzz, Mxy, Mxz, Myz, Vx, Vy, Vz (include/loamx.h)
-constexpr int DM_MOM_WORDS = 9;
+// mom: DM_MOM_WORDS per slot beside the table, [9 * slot + k]: Mxx, Myy, Mzz, Mxy, Mxz, Myz, Vx, Vy, Vz (include/loamx.h)
 constexpr int DM_VBITS = 26;   // the combine packs a lane's w_a above its q_a: 64 lanes' q sum stays below 2^26
 
 // the slot of `key` (claimed when absent); won: this call claimed it.  false: the table is full (cannot happen at a load <= 1/2)
@@ -89,12 +89,17 @@ __device__ inline void dm_wave_sum(unsigned long long* ctr, uint32_t v) {
   if (v && (threadIdx.x & 63) == 0) atomicAdd(ctr, (unsigned long long)v);
 }
 
+// the key rule of a point: its cell's indices stay inside the key (a NaN or an infinite component fails it too)
+__device__ inline bool dm_in_key_range(const float4 p, float inv) {
+  return fabsf(floorf(p.x * inv)) < DM_IMAX && fabsf(floorf(p.y * inv)) < DM_IMAX && fabsf(floorf(p.z * inv)) < DM_IMAX;
+}
+
 // true when the insert adds p (its range filter and key rule, the same expressions); d2 as the insert computes it
 __device__ inline bool dm_added(const float4 p, const DmFilter& F, float& d2) {
   const float dx = p.x - F.ox, dy = p.y - F.oy, dz = p.z - F.oz;
   d2 = (dx * dx + dy * dy) + dz * dz;
   if (!(d2 >= F.min2 && (!F.use_max || d2 <= F.max2))) return false;
-  return fabsf(floorf(p.x * F.inv)) < DM_IMAX && fabsf(floorf(p.y * F.inv)) < DM_IMAX && fabsf(floorf(p.z * F.inv)) < DM_IMAX;
+  return dm_in_key_range(p, F.inv);
 }
 
 // one point per thread.  vals: 4 words per slot (n, Sx, Sy, Sz).  COMBINE: equal keys of a wave are summed in LDS first, and one lane
@@ -261,6 +266,9 @@ __device__ inline void dm_axis_step(DmAxis& A) {
   A.tmax = A.tmax + A.tdelta;
 }
 
+// (Both ray kernels write out the three dm_axis_setup calls and the n_steps sum.  A function around them — a struct of the three axes
+// with a setup member, or a free function over three DmAxis in any of four shapes — inlines to the same instructions in another order
+// in both kernels, so the one-object comparison with the kernels as they stood no longer holds; the walk's step and the key are shared.)
 // one step of the walk: the axis with the smallest tmax among those with cells left moves, ties to the lower axis.  The caller has
 // cells left on some axis
 __device__ inline void dm_walk_step(DmAxis& X, DmAxis& Y, DmAxis& Z) {
@@ -311,11 +319,8 @@ __global__ __launch_bounds__(256) void k_dm_carve(const float4* __restrict__ pts
           // cells k = 0 .. n_steps - 1 - end_margin are visited; cell k is the cell after k steps
           const uint32_t n_visit = n_steps > R.end_margin ? n_steps - R.end_margin : 0u;
           for (uint32_t k = 0; k < n_visit; k++) {
-            const unsigned long long key = (unsigned long long)(uint32_t)(X.c + (1 << DM_QBITS)) |
-                                           ((unsigned long long)(uint32_t)(Y.c + (1 << DM_QBITS)) << DM_KBITS) |
-                                           ((unsigned long long)(uint32_t)(Z.c + (1 << DM_QBITS)) << (2 * DM_KBITS));
             uint32_t slot = 0u;
-            const int f = dm_find(keys, mask, shift, key, slot);
+            const int f = dm_find(keys, mask, shift, dm_key(X.c, Y.c, Z.c), slot);
             visited++;
             if (f < 0) overflow = true;
             if (f > 0 && aux[2ull * slot + 1] != R.seq) {   // occupied wins: a voxel this call hit is left alone
@@ -373,8 +378,7 @@ __global__ __launch_bounds__(256) void k_dm_raycast(const float4* __restrict__ p
   bool overflow = false;
   if (i < n) {
     const float4 p = pts[i];
-    // the end's cell passes the key rule (a NaN or an infinite component fails it too)
-    if (fabsf(floorf(p.x * C.inv)) < DM_IMAX && fabsf(floorf(p.y * C.inv)) < DM_IMAX && fabsf(floorf(p.z * C.inv)) < DM_IMAX) {
+    if (dm_in_key_range(p, C.inv)) {   // (the end's cell)
       DmAxis X, Y, Z;
       const bool okx = dm_axis_setup(C.ox, p.x, C.inv, X), oky = dm_axis_setup(C.oy, p.y, C.inv, Y), okz = dm_axis_setup(C.oz, p.z, C.inv, Z);
       const uint32_t n_steps = X.rem + Y.rem + Z.rem;   // (each < 2^21)
@@ -384,9 +388,7 @@ __global__ __launch_bounds__(256) void k_dm_raycast(const float4* __restrict__ p
         if (C.skip_steps <= n_steps) {
           for (uint32_t k = 0; k <= n_steps; k++) {
             if (k >= C.skip_steps) {
-              const unsigned long long key = (unsigned long long)(uint32_t)(X.c + (1 << DM_QBITS)) |
-                                             ((unsigned long long)(uint32_t)(Y.c + (1 << DM_QBITS)) << DM_KBITS) |
-                                             ((unsigned long long)(uint32_t)(Z.c + (1 << DM_QBITS)) << (2 * DM_KBITS));
+              const unsigned long long key = dm_key(X.c, Y.c, Z.c);
               uint32_t slot = 0u;
               const int f = dm_find(keys, mask, shift, key, slot);
               looked++;
@@ -562,8 +564,6 @@ __global__ __launch_bounds__(256) void k_dm_compact(const unsigned long long* __
   }
 }
 
-static uint32_t log2u(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }
-
 // the exported position of a voxel (include/loamx.h): its indices and its words n, Sx, Sy, Sz; f64 arithmetic, one f32 rounding
 static void dm_position(double leaf, const long long ia[3], const unsigned long long* v4, float out[3]) {
   const double cnt = (double)v4[0], qs = (double)(1u << DM_QBITS);
@@ -605,10 +605,10 @@ static void dm_surfel(double leaf, const long long ia[3], const unsigned long lo
   out.curvature = (float)curv;
 }
 
-// the indices of a key
-static void dm_key_indices(unsigned long long k, long long ia[3]) {
-  const unsigned long long km = (1ull << DM_KBITS) - 1ull;
-  for (int a = 0; a < 3; a++) ia[a] = (long long)((k >> (DM_KBITS * a)) & km) - (1ll << DM_QBITS);
+// two runtime booleans as the two std::bool_constant arguments of f: the kernels' feature switches are template parameters
+template <class F> static void dm_dispatch2(bool a, bool b, F&& f) {
+  if (a) { if (b) f(std::true_type(), std::true_type()); else f(std::true_type(), std::false_type()); }
+  else { if (b) f(std::false_type(), std::true_type()); else f(std::false_type(), std::false_type()); }
 }
 
 class DenseMap {
@@ -623,8 +623,7 @@ class DenseMap {
     h_ctr_.reserve(2 * DM_CTR_WORDS);
     h_snap_.reserve(2);
     inv_ = 1.0f / cfg.leaf;
-    alloc_table(cfg.initial_slots, keys_, vals_);
-    slots_ = cfg.initial_slots;
+    tab_.alloc(cfg.initial_slots, false, false);
     clear(own_);
     LX_HIP(hipStreamSynchronize(own_));
   }
@@ -633,10 +632,7 @@ class DenseMap {
     if (last_st_) (void)hipEventSynchronize(ev_last_);
     (void)hipStreamSynchronize(own_);
     free_graveyard();
-    (void)hipFree(keys_);
-    (void)hipFree(vals_);
-    (void)hipFree(aux_);
-    (void)hipFree(mom_);
+    DmTable().swap(tab_);
     (void)hipEventDestroy(ev_last_);
     (void)hipEventDestroy(ev_snap_);
     (void)hipEventDestroy(ev_staged_);
@@ -675,7 +671,7 @@ class DenseMap {
   // [voxels, slots, offered, added, dropped by range, dropped by key]
   void stats(uint64_t out[6]) {
     read_counters();
-    out[0] = occ_; out[1] = slots_; out[2] = offered_;
+    out[0] = occ_.occ; out[1] = tab_.slots; out[2] = offered_;
     out[3] = offered_ - drop_range_ - drop_key_; out[4] = drop_range_; out[5] = drop_key_;
   }
 
@@ -687,84 +683,82 @@ class DenseMap {
   };
   void snapshot(Snapshot& S, bool want_mom = false) {
     read_counters();
-    const uint32_t slots = slots_, nblk = (slots + 255) / 256;
+    const DmTable& T = tab_;
+    const uint64_t occ = occ_.occ;
+    const uint32_t nblk = (T.slots + 255) / 256;
     DevBuf<uint32_t> blk, scratch, omiss;
     DevBuf<unsigned long long> tiles, okeys, ovals, omom;
     blk.reserve((size_t)nblk + 1);
     scratch.reserve(2);
     tiles.reserve(SCAN_SCRATCH_WORDS / 2);
-    okeys.reserve(occ_ + 1);
-    ovals.reserve(4 * (occ_ + 1));
-    if (aux_) omiss.reserve(occ_ + 1);
-    if (want_mom) omom.reserve(DM_MOM_WORDS * (occ_ + 1));
+    okeys.reserve(occ + 1);
+    ovals.reserve(4 * (occ + 1));
+    if (T.aux) omiss.reserve(occ + 1);
+    if (want_mom) omom.reserve(DM_MOM_WORDS * (occ + 1));
     LX_HIP(hipMemsetAsync(tiles.p, 0, sizeof(unsigned long long) * (SCAN_SCRATCH_WORDS / 2), own_));
-    hipLaunchKernelGGL(k_dm_count, dim3(nblk), dim3(256), 0, own_, keys_, slots, blk.p);
+    hipLaunchKernelGGL(k_dm_count, dim3(nblk), dim3(256), 0, own_, T.keys, T.slots, blk.p);
     exclusive_scan_u32_n(blk.p, blk.p, (uint32_t*)tiles.p, scratch.p, nblk, own_);
-    const unsigned long long* no_mom = nullptr;
-    unsigned long long* no_omom = nullptr;
-    if (want_mom && aux_)
-      hipLaunchKernelGGL((k_dm_compact<true, true>), dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p, aux_, omiss.p,
-                         mom_, omom.p);
-    else if (want_mom)
-      hipLaunchKernelGGL((k_dm_compact<false, true>), dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p, nullptr,
-                         nullptr, mom_, omom.p);
-    else if (aux_)
-      hipLaunchKernelGGL((k_dm_compact<true, false>), dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p, aux_, omiss.p,
-                         no_mom, no_omom);
-    else
-      hipLaunchKernelGGL((k_dm_compact<false, false>), dim3(nblk), dim3(256), 0, own_, keys_, vals_, slots, blk.p, okeys.p, ovals.p, nullptr,
-                         nullptr, no_mom, no_omom);
+    dm_dispatch2(T.aux != nullptr, want_mom, [&](auto A, auto M) {   // (an array that is off is not read: omiss.p, omom.p are NULL then)
+      hipLaunchKernelGGL((k_dm_compact<decltype(A)::value, decltype(M)::value>), dim3(nblk), dim3(256), 0, own_, T.keys, T.vals, T.slots, blk.p,
+                         okeys.p, ovals.p, T.aux, omiss.p, T.mom, omom.p);
+    });
     LX_HIP(hipGetLastError());
-    S.k.resize(occ_);
-    S.v.resize(4 * (size_t)occ_);
-    S.miss.assign(aux_ ? occ_ : 0, 0u);
-    S.mom.resize(want_mom ? DM_MOM_WORDS * (size_t)occ_ : 0);
+    S.k.resize(occ);
+    S.v.resize(4 * (size_t)occ);
+    S.miss.assign(T.aux ? occ : 0, 0u);
+    S.mom.resize(want_mom ? DM_MOM_WORDS * (size_t)occ : 0);
     uint32_t total = 0;
     LX_HIP(hipMemcpyAsync(&total, blk.p + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, own_));
-    if (occ_) {
-      LX_HIP(hipMemcpyAsync(S.k.data(), okeys.p, sizeof(unsigned long long) * occ_, hipMemcpyDeviceToHost, own_));
-      LX_HIP(hipMemcpyAsync(S.v.data(), ovals.p, sizeof(unsigned long long) * 4 * occ_, hipMemcpyDeviceToHost, own_));
-      if (aux_) LX_HIP(hipMemcpyAsync(S.miss.data(), omiss.p, sizeof(uint32_t) * occ_, hipMemcpyDeviceToHost, own_));
+    if (occ) {
+      LX_HIP(hipMemcpyAsync(S.k.data(), okeys.p, sizeof(unsigned long long) * occ, hipMemcpyDeviceToHost, own_));
+      LX_HIP(hipMemcpyAsync(S.v.data(), ovals.p, sizeof(unsigned long long) * 4 * occ, hipMemcpyDeviceToHost, own_));
+      if (T.aux) LX_HIP(hipMemcpyAsync(S.miss.data(), omiss.p, sizeof(uint32_t) * occ, hipMemcpyDeviceToHost, own_));
       if (want_mom)
-        LX_HIP(hipMemcpyAsync(S.mom.data(), omom.p, sizeof(unsigned long long) * DM_MOM_WORDS * occ_, hipMemcpyDeviceToHost, own_));
+        LX_HIP(hipMemcpyAsync(S.mom.data(), omom.p, sizeof(unsigned long long) * DM_MOM_WORDS * occ, hipMemcpyDeviceToHost, own_));
     }
     LX_HIP(hipStreamSynchronize(own_));
     scan_check_errors();
-    LX_REQUIRE(total == occ_, "dense map: the compaction disagrees with the occupancy count");
-    S.idx.resize(occ_);
+    LX_REQUIRE(total == occ, "dense map: the compaction disagrees with the occupancy count");
+    S.idx.resize(occ);
     std::iota(S.idx.begin(), S.idx.end(), 0u);
     std::sort(S.idx.begin(), S.idx.end(), [&](uint32_t a, uint32_t b) { return S.k[a] < S.k[b]; });
+  }
+  // the voxels of a snapshot in ascending key order, without those a rule (NULL: none) calls dynamic: f(j, ia) with j the voxel's
+  // place in S.k (4 * j in S.v, 9 * j in S.mom) and ia its indices
+  template <class F> static void for_each_voxel(const Snapshot& S, const loamx_densemap_static_rule* rule, F&& f) {
+    for (size_t r = 0; r < S.idx.size(); r++) {
+      const size_t j = S.idx[r];
+      if (rule && dm_dynamic(*rule, S.v[4 * j], S.miss[j])) continue;
+      long long ia[3];
+      dm_key_indices(S.k[j], ia);
+      f(j, ia);
+    }
   }
 
   // the voxels as records (axes 0: LOAM frame, 1: sensor axes), ascending key order; with a rule, without the voxels it calls dynamic
   void records(std::vector<float4>& out, int axes, const loamx_densemap_static_rule* rule = nullptr) {
     Snapshot S;
     snapshot(S);
-    const std::vector<unsigned long long>&hk = S.k, &hv = S.v;
     out.clear();
     out.reserve(S.idx.size());
     const double leaf = (double)cfg.leaf;
-    for (size_t r = 0; r < S.idx.size(); r++) {
-      const uint32_t j = S.idx[r];
-      if (rule && dm_dynamic(*rule, hv[4 * (size_t)j], S.miss[j])) continue;
-      const double cnt = (double)hv[4 * (size_t)j];
-      long long ia[3];
+    for_each_voxel(S, rule, [&](size_t j, const long long ia[3]) {
+      const double cnt = (double)S.v[4 * j];
       float v[3];
-      dm_key_indices(hk[j], ia);
-      dm_position(leaf, ia, &hv[4 * (size_t)j], v);
+      dm_position(leaf, ia, &S.v[4 * j], v);
       out.push_back(axes == 1 ? make_float4(v[2], v[0], v[1], (float)cnt) : make_float4(v[0], v[1], v[2], (float)cnt));
-    }
+    });
   }
 
-  bool moments() const { return mom_ != nullptr; }
+  bool moments() const { return tab_.mom != nullptr; }
 
   // allowed while nothing has been offered since creation / reset; the handle is unchanged when refused
   void enable_moments() {
     read_counters();
-    LX_REQUIRE(occ_ == 0 && offered_ == 0, "moments can only be enabled on an empty map (a fresh handle, or right after reset)");
-    if (!mom_) {
-      LX_HIP(hipMalloc((void**)&mom_, sizeof(unsigned long long) * DM_MOM_WORDS * (size_t)slots_));
-      LX_HIP(hipMemsetAsync(mom_, 0, sizeof(unsigned long long) * DM_MOM_WORDS * (size_t)slots_, own_));
+    LX_REQUIRE(occ_.occ == 0 && offered_ == 0, "moments can only be enabled on an empty map (a fresh handle, or right after reset)");
+    if (!tab_.mom) {   // (no new table: the empty one that stands gets the array, zeroed like the rest of it)
+      tab_.add_mom();
+      tab_.clear_mom(own_);
       LX_HIP(hipStreamSynchronize(own_));
     }
   }
@@ -773,9 +767,9 @@ class DenseMap {
   void moment_words(std::vector<unsigned long long>& out) {
     Snapshot S;
     snapshot(S, true);
-    out.resize(DM_MOM_WORDS * S.idx.size());
-    for (size_t r = 0; r < S.idx.size(); r++)
-      memcpy(&out[DM_MOM_WORDS * r], &S.mom[DM_MOM_WORDS * (size_t)S.idx[r]], sizeof(unsigned long long) * DM_MOM_WORDS);
+    out.clear();
+    out.reserve(DM_MOM_WORDS * S.idx.size());
+    for_each_voxel(S, nullptr, [&](size_t j, const long long*) { out.insert(out.end(), &S.mom[DM_MOM_WORDS * j], &S.mom[DM_MOM_WORDS * j] + DM_MOM_WORDS); });
   }
 
   // the voxels as surfels in the order of records(); with a rule, without the voxels it calls dynamic
@@ -785,15 +779,11 @@ class DenseMap {
     out.clear();
     out.reserve(S.idx.size());
     const double leaf = (double)cfg.leaf;
-    for (size_t r = 0; r < S.idx.size(); r++) {
-      const size_t j = S.idx[r];
-      if (rule && dm_dynamic(*rule, S.v[4 * j], S.miss[j])) continue;
-      long long ia[3];
+    for_each_voxel(S, rule, [&](size_t j, const long long ia[3]) {
       loamx_surfel s;
-      dm_key_indices(S.k[j], ia);
       dm_surfel(leaf, ia, &S.v[4 * j], &S.mom[DM_MOM_WORDS * j], sc, axes, s);
       out.push_back(s);
-    }
+    });
   }
 
   // the snapshot the alignment reads (densemap_align.hip): the voxels that have a surfel and that the rule does not call dynamic, each
@@ -804,18 +794,14 @@ class DenseMap {
     std::vector<unsigned long long> keys;
     std::vector<float> rec;
     const double leaf = (double)cfg.leaf;
-    for (size_t r = 0; r < S.idx.size(); r++) {
-      const size_t j = S.idx[r];
-      if (rule && dm_dynamic(*rule, S.v[4 * j], S.miss[j])) continue;
-      long long ia[3];
+    for_each_voxel(S, rule, [&](size_t j, const long long ia[3]) {
       loamx_surfel s;
-      dm_key_indices(S.k[j], ia);
       dm_surfel(leaf, ia, &S.v[4 * j], &S.mom[DM_MOM_WORDS * j], sc, 0, s);
-      if (s.normal_x == 0.f && s.normal_y == 0.f && s.normal_z == 0.f) continue;
+      if (s.normal_x == 0.f && s.normal_y == 0.f && s.normal_z == 0.f) return;
       keys.push_back(S.k[j]);
       const float six[6] = {s.x, s.y, s.z, s.normal_x, s.normal_y, s.normal_z};
       rec.insert(rec.end(), six, six + 6);
-    }
+    });
     frozen.build(keys.data(), rec.data(), keys.size(), own_);
     return frozen.size();
   }
@@ -826,19 +812,20 @@ class DenseMap {
   void misses(std::vector<uint32_t>& out) {
     Snapshot S;
     snapshot(S);
-    out.resize(S.idx.size());
-    for (size_t r = 0; r < S.idx.size(); r++) out[r] = S.miss[S.idx[r]];
+    out.clear();
+    out.reserve(S.idx.size());
+    for_each_voxel(S, nullptr, [&](size_t j, const long long*) { out.push_back(S.miss[j]); });
   }
 
-  bool carving() const { return aux_ != nullptr; }
+  bool carving() const { return tab_.aux != nullptr; }
 
   // allowed while nothing has been offered since creation / reset; the handle is unchanged when refused
   void enable_carving(const loamx_densemap_carve_config& c) {
     read_counters();
-    LX_REQUIRE(occ_ == 0 && offered_ == 0, "carving can only be enabled on an empty map (a fresh handle, or right after reset)");
-    if (!aux_) {
-      LX_HIP(hipMalloc((void**)&aux_, sizeof(uint32_t) * 2 * (size_t)slots_));
-      LX_HIP(hipMemsetAsync(aux_, 0, sizeof(uint32_t) * 2 * (size_t)slots_, own_));
+    LX_REQUIRE(occ_.occ == 0 && offered_ == 0, "carving can only be enabled on an empty map (a fresh handle, or right after reset)");
+    if (!tab_.aux) {   // (as in enable_moments)
+      tab_.add_aux();
+      tab_.clear_aux(own_);
       LX_HIP(hipStreamSynchronize(own_));
     }
     carve_ = c;
@@ -853,24 +840,16 @@ class DenseMap {
   // the dynamic voxels leave the table: a rehash with the rule as predicate into a fresh table of the same size
   uint64_t prune(const loamx_densemap_static_rule& rule) {
     read_counters();
-    const uint64_t before = occ_;
-    unsigned long long *nk = nullptr, *nv = nullptr, *nm = nullptr;
-    uint32_t* na = nullptr;
-    alloc_table(slots_, nk, nv, &na, mom_ ? &nm : nullptr);
-    LX_HIP(hipMemsetAsync(nk, 0xff, sizeof(unsigned long long) * slots_, own_));
-    LX_HIP(hipMemsetAsync(nv, 0, sizeof(unsigned long long) * 4 * slots_, own_));
-    LX_HIP(hipMemsetAsync(na, 0, sizeof(uint32_t) * 2 * (size_t)slots_, own_));
-    if (nm) LX_HIP(hipMemsetAsync(nm, 0, sizeof(unsigned long long) * DM_MOM_WORDS * (size_t)slots_, own_));
+    const uint64_t before = occ_.occ;
+    DmTable nt;
+    nt.alloc(tab_.slots, true, tab_.mom != nullptr);   // (aux whatever the map has: the callers require carving)
+    nt.clear(own_);
     LX_HIP(hipMemsetAsync(ctr_.p, 0, sizeof(unsigned long long), own_));   // (the occupancy: recounted by the kernel)
-    launch_rehash<true, true>(own_, nk, nv, slots_, na, nm, rule);
+    launch_rehash<true>(own_, nt, rule);
     LX_HIP(hipGetLastError());
-    retire_table();
-    keys_ = nk;
-    vals_ = nv;
-    aux_ = na;
-    mom_ = nm;
+    replace_table(nt);
     read_counters();
-    return before - occ_;
+    return before - occ_.occ;
   }
 
   void reset() {
@@ -879,41 +858,42 @@ class DenseMap {
     clear(own_);
     LX_HIP(hipStreamSynchronize(own_));
     frozen.drop();
-    occ_ = pend_ = pend_snap_ = 0;
+    occ_.reset();
     offered_ = drop_range_ = drop_key_ = 0;
     for (uint64_t& c : carve_ctr_) c = 0;
     seq_ = 0;
   }
 
   // the features of the handle as the file's flags
-  uint32_t flags() const { return (aux_ ? DMF_CARVING : 0u) | (mom_ ? DMF_MOMENTS : 0u); }
+  uint32_t flags() const { return (tab_.aux ? DMF_CARVING : 0u) | (tab_.mom ? DMF_MOMENTS : 0u); }
 
   // include/loamx.h, loamx_densemap_save: the records of snapshot() in ascending key order, with the statistics
   void save(const char* path) {
     Snapshot S;
-    snapshot(S, mom_ != nullptr);
+    const bool aux = carving(), mom = moments();
+    snapshot(S, mom);
     const size_t n = S.idx.size();
     DmFileHeader H;
     H.flags = flags();
     H.leaf = cfg.leaf;
     H.count = n;
     H.offered = offered_; H.dropped_range = drop_range_; H.dropped_key = drop_key_;
-    if (aux_) {
+    if (aux) {
       for (int k = 0; k < 6; k++) H.carve_stats[k] = carve_ctr_[k];
       H.carve_max_range = carve_.max_range;
       H.ray_stride = carve_.ray_stride; H.end_margin = carve_.end_margin; H.max_steps = carve_.max_steps;
     }
-    std::vector<uint64_t> k(n), v(4 * n), m(mom_ ? DM_MOM_WORDS * n : 0);
-    std::vector<uint32_t> ms(aux_ ? n : 0);
-    for (size_t r = 0; r < n; r++) {
-      const size_t j = S.idx[r];
-      k[r] = S.k[j];
-      for (int a = 0; a < 4; a++) v[4 * r + a] = S.v[4 * j + a];
-      if (aux_) ms[r] = S.miss[j];
-      if (mom_)
-        for (int a = 0; a < DM_MOM_WORDS; a++) m[DM_MOM_WORDS * r + a] = S.mom[DM_MOM_WORDS * j + a];
-    }
-    const std::string e = dmf_write(path, H, k.data(), v.data(), aux_ ? ms.data() : nullptr, mom_ ? m.data() : nullptr);
+    std::vector<uint64_t> k, v, m;
+    std::vector<uint32_t> ms;
+    k.reserve(n);
+    v.reserve(4 * n);
+    for_each_voxel(S, nullptr, [&](size_t j, const long long*) {
+      k.push_back(S.k[j]);
+      v.insert(v.end(), &S.v[4 * j], &S.v[4 * j] + 4);
+      if (aux) ms.push_back(S.miss[j]);
+      if (mom) m.insert(m.end(), &S.mom[DM_MOM_WORDS * j], &S.mom[DM_MOM_WORDS * j] + DM_MOM_WORDS);
+    });
+    const std::string e = dmf_write(path, H, k.data(), v.data(), aux ? ms.data() : nullptr, mom ? m.data() : nullptr);
     LX_REQUIRE(e.empty(), e);
   }
 
@@ -925,11 +905,11 @@ class DenseMap {
     LX_REQUIRE(src.flags() == flags(), "the two dense maps do not have the same features enabled (carving, moments)");
     src.read_counters();
     read_counters();
-    if (cfg.max_voxels && occ_ + src.occ_ > cfg.max_voxels) return LOAMX_E_CAPACITY;
+    if (!occ_.admits_exact(src.occ_.occ, cfg.max_voxels)) return LOAMX_E_CAPACITY;
     DmCtrAdd add;
     add.v[0] = src.drop_range_; add.v[1] = src.drop_key_;
     for (int k = 0; k < 6; k++) add.v[2 + k] = src.carve_ctr_[k];
-    merge_records(src.keys_, src.vals_, src.slots_, src.occ_, src.aux_, 2u, src.mom_, add, src.offered_);
+    merge_records(src.tab_.keys, src.tab_.vals, src.tab_.slots, src.occ_.occ, src.tab_.aux, 2u, src.tab_.mom, add, src.offered_);
     return LOAMX_OK;
   }
 
@@ -943,33 +923,31 @@ class DenseMap {
     const uint64_t n = F.h.count;
     read_counters();
     if (loading) {
-      LX_REQUIRE(occ_ == 0 && offered_ == 0, "a file can only be loaded into an empty map (a fresh handle, or right after reset)");
+      LX_REQUIRE(occ_.occ == 0 && offered_ == 0, "a file can only be loaded into an empty map (a fresh handle, or right after reset)");
       LX_REQUIRE((flags() & ~F.h.flags) == 0u, "the dense map has a feature enabled (carving, moments) that the file lacks");
-      if (cfg.max_voxels && n > cfg.max_voxels) return LOAMX_E_CAPACITY;
+      if (!occ_.admits_exact(n, cfg.max_voxels)) return LOAMX_E_CAPACITY;   // (occ is 0)
       if (F.h.flags & DMF_CARVING) {
         const loamx_densemap_carve_config c = {F.h.carve_max_range, F.h.ray_stride, F.h.end_margin, F.h.max_steps};
         enable_carving(c);
       }
       if (F.h.flags & DMF_MOMENTS) enable_moments();
       // the smallest table the file's voxels fit at a load of one half (a handle reset after it grew holds a larger one)
-      uint64_t target = cfg.initial_slots;
-      while (target < 2 * n) target *= 2;
-      if (slots_ > target) {
-        unsigned long long *nk = nullptr, *nv = nullptr, *nm = nullptr;
-        uint32_t* na = nullptr;
-        alloc_table(target, nk, nv, aux_ ? &na : nullptr, mom_ ? &nm : nullptr);
+      const uint64_t target = dm_slots_for(cfg.initial_slots, n);
+      if (tab_.slots > target) {
+        // (not the sequence of the other replacements, and kept: the host waits for own_ before the old table retires, and the new
+        // one is cleared together with the counters once it is the map's)
+        DmTable nt;
+        nt.alloc(target, tab_.aux != nullptr, tab_.mom != nullptr);
         LX_HIP(hipStreamSynchronize(own_));
-        retire_table();
-        keys_ = nk; vals_ = nv; aux_ = na; mom_ = nm;
-        slots_ = (uint32_t)target;
+        replace_table(nt);
         clear(own_);
       }
     } else {
       LX_REQUIRE(F.h.flags == flags(), "the file and the dense map do not have the same features (carving, moments)");
-      if (cfg.max_voxels && occ_ + n > cfg.max_voxels) return LOAMX_E_CAPACITY;
+      if (!occ_.admits_exact(n, cfg.max_voxels)) return LOAMX_E_CAPACITY;
     }
     // one pinned block, one copy: values (first: the kernel reads them 16 bytes at a time), moment words, keys, then the 32-bit miss words
-    const size_t nn = (size_t)n, w_mom = mom_ ? DM_MOM_WORDS * nn : 0, w_miss = aux_ ? (nn + 1) / 2 : 0;
+    const size_t nn = (size_t)n, w_mom = moments() ? DM_MOM_WORDS * nn : 0, w_miss = carving() ? (nn + 1) / 2 : 0;
     const size_t o_mom = 4 * nn, o_keys = o_mom + w_mom, o_miss = o_keys + nn, words = o_miss + w_miss;
     PinBuf<unsigned long long> h_up;
     DevBuf<unsigned long long> d_up;
@@ -979,7 +957,7 @@ class DenseMap {
       for (size_t i = 0; i < 4 * nn; i++) h_up.p[i] = F.vals[i];
       for (size_t i = 0; i < w_mom; i++) h_up.p[o_mom + i] = F.mom[i];
       for (size_t i = 0; i < nn; i++) h_up.p[o_keys + i] = F.keys[i];
-      if (aux_) {
+      if (carving()) {
         h_up.p[words - 1] = 0ull;
         memcpy(h_up.p + o_miss, F.miss.data(), sizeof(uint32_t) * nn);
       }
@@ -1019,14 +997,7 @@ class DenseMap {
     if (out && capacity < s.n) throw Error(LOAMX_E_CAPACITY, "capacity is smaller than the cloud's count");
     LX_HIP(hipSetDevice(cfg.device));
     wait_adds();
-    if (s.n) {
-      hipEvent_t ev = nullptr;
-      LX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      hipError_t e = hipEventRecord(ev, s.stream);
-      if (e == hipSuccess) e = hipStreamWaitEvent(own_, ev, 0);
-      (void)hipEventDestroy(ev);   // (the wait keeps what it needs)
-      LX_HIP(e);
-    }
+    if (s.n) dm_stream_behind(own_, s.stream);
     cast(s.pts, s.n, s.origin, c, rule, out, counts);
     return LOAMX_OK;
   }
@@ -1038,15 +1009,11 @@ class DenseMap {
   hipStream_t own_ = nullptr;      // host-fed adds, rehash of those, exports
   hipStream_t last_st_ = nullptr;  // the stream of the last enqueued add (ev_last_ recorded behind it)
   hipEvent_t ev_last_ = nullptr, ev_snap_ = nullptr, ev_staged_ = nullptr;
-  bool snap_pending_ = false, staged_pending_ = false;
-  unsigned long long* keys_ = nullptr;
-  unsigned long long* vals_ = nullptr;
-  uint32_t* aux_ = nullptr;   // carving: miss and stamp per slot (nullptr: carving is off)
-  unsigned long long* mom_ = nullptr;   // moments: nine words per slot (nullptr: moments are off)
+  bool staged_pending_ = false;
+  DmTable tab_;   // (aux NULL: carving is off; mom NULL: moments are off)
   loamx_densemap_carve_config carve_ = {0.f, 1u, 1u, 4096u};
   uint32_t seq_ = 0;          // sequence number of the last add call (stamp values; 0 = never stamped)
   uint64_t carve_ctr_[6] = {0, 0, 0, 0, 0, 0};
-  uint32_t slots_ = 0;
   float inv_ = 10.f;
   DevBuf<unsigned long long> ctr_;
   PinBuf<uint32_t> h_ctr_, h_snap_;
@@ -1057,59 +1024,35 @@ class DenseMap {
   DevBuf<loamx_ray_hit> d_hits_;
   PinBuf<uint32_t> h_rc_, h_hits_;
   std::vector<void*> graveyard_;   // tables replaced by a rehash: freed at the next point where the host waits anyway
-  // occupancy: occ_ exact as of the last snapshot; pend_ points enqueued since (the bound is occ_ + pend_); pend_snap_ those enqueued
-  // behind the snapshot in flight
-  uint64_t occ_ = 0, pend_ = 0, pend_snap_ = 0;
+  DmOccupancy occ_;   // the bound of the occupancy that growth and admission are decided on (densemap_growth.hpp)
   uint64_t offered_ = 0, drop_range_ = 0, drop_key_ = 0;
 
-  void alloc_table(uint64_t slots, unsigned long long*& k, unsigned long long*& v, uint32_t** aux = nullptr, unsigned long long** mom = nullptr) {
-    LX_HIP(hipMalloc((void**)&k, sizeof(unsigned long long) * slots));
-    LX_HIP(hipMalloc((void**)&v, sizeof(unsigned long long) * 4 * slots));
-    if (aux) LX_HIP(hipMalloc((void**)aux, sizeof(uint32_t) * 2 * slots));
-    if (mom) LX_HIP(hipMalloc((void**)mom, sizeof(unsigned long long) * DM_MOM_WORDS * slots));
+  // nt becomes the map's table; the one it replaces goes to the graveyard
+  void replace_table(DmTable& nt) {
+    tab_.swap(nt);
+    nt.retire(graveyard_);
   }
-  // the current table (and its auxiliary and moment words) to the graveyard
-  void retire_table() {
-    graveyard_.push_back(keys_);
-    graveyard_.push_back(vals_);
-    if (aux_) graveyard_.push_back(aux_);
-    if (mom_) graveyard_.push_back(mom_);
-  }
-  // the current table into (nk, nv, na, nm) of `want` slots on st; the moment words travel when the map has them
-  template <bool AUX, bool PRUNE>
-  void launch_rehash(hipStream_t st, unsigned long long* nk, unsigned long long* nv, uint64_t want, uint32_t* na, unsigned long long* nm,
-                     const loamx_densemap_static_rule& rule) {
-    const dim3 grid((slots_ + 255) / 256), block(256);
-    const uint32_t mask = (uint32_t)(want - 1), sh = 64u - log2u(want);
-    const uint32_t* oa = aux_;
-    const unsigned long long* om = mom_;
-    if (mom_)
-      hipLaunchKernelGGL((k_dm_rehash<AUX, PRUNE, true>), grid, block, 0, st, keys_, vals_, slots_, nk, nv, mask, sh, ctr_.p, oa, na, rule, om, nm);
-    else
-      hipLaunchKernelGGL((k_dm_rehash<AUX, PRUNE, false>), grid, block, 0, st, keys_, vals_, slots_, nk, nv, mask, sh, ctr_.p, oa, na, rule, om, nm);
+  // the current table into nt on st, under the map's features; PRUNE (carving is on): the rule's dynamic voxels stay behind
+  template <bool PRUNE> void launch_rehash(hipStream_t st, const DmTable& nt, const loamx_densemap_static_rule& rule) {
+    const DmTable& T = tab_;
+    dm_dispatch2(T.aux != nullptr, T.mom != nullptr, [&](auto A, auto M) {
+      constexpr bool AUX = decltype(A)::value, MOM = decltype(M)::value;
+      if constexpr (AUX || !PRUNE)
+        hipLaunchKernelGGL((k_dm_rehash<AUX, PRUNE, MOM>), dim3((T.slots + 255) / 256), dim3(256), 0, st, T.keys, T.vals, T.slots, nt.keys, nt.vals,
+                           nt.mask(), nt.shift(), ctr_.p, T.aux, nt.aux, rule, T.mom, nt.mom);
+    });
   }
   // the insert of one add; the combine by the bench hook, the moment words when the map has them
-  template <bool STAMP>
-  void launch_insert(hipStream_t st, const float4* pts, uint32_t n, const DmFilter& F, uint32_t sh, uint32_t seq) {
-    const dim3 grid((n + 255) / 256), block(256);
-    const uint32_t mask = slots_ - 1u;
-    if (!mom_) {
-      if (combine)
-        hipLaunchKernelGGL((k_dm_insert<true, STAMP, false>), grid, block, 0, st, pts, n, F, keys_, vals_, mask, sh, ctr_.p, aux_, seq, mom_);
-      else
-        hipLaunchKernelGGL((k_dm_insert<false, STAMP, false>), grid, block, 0, st, pts, n, F, keys_, vals_, mask, sh, ctr_.p, aux_, seq, mom_);
-    } else {
-      if (combine)
-        hipLaunchKernelGGL((k_dm_insert<true, STAMP, true>), grid, block, 0, st, pts, n, F, keys_, vals_, mask, sh, ctr_.p, aux_, seq, mom_);
-      else
-        hipLaunchKernelGGL((k_dm_insert<false, STAMP, true>), grid, block, 0, st, pts, n, F, keys_, vals_, mask, sh, ctr_.p, aux_, seq, mom_);
-    }
+  template <bool STAMP> void launch_insert(hipStream_t st, const float4* pts, uint32_t n, const DmFilter& F, uint32_t seq) {
+    const DmTable& T = tab_;
+    dm_dispatch2(combine, T.mom != nullptr, [&](auto C, auto M) {
+      hipLaunchKernelGGL((k_dm_insert<decltype(C)::value, STAMP, decltype(M)::value>), dim3((n + 255) / 256), dim3(256), 0, st, pts, n, F, T.keys,
+                         T.vals, T.mask(), T.shift(), ctr_.p, T.aux, seq, T.mom);
+    });
   }
+  // the table and the counters (the one place that zeroes both)
   void clear(hipStream_t st) {
-    LX_HIP(hipMemsetAsync(keys_, 0xff, sizeof(unsigned long long) * slots_, st));
-    LX_HIP(hipMemsetAsync(vals_, 0, sizeof(unsigned long long) * 4 * slots_, st));
-    if (aux_) LX_HIP(hipMemsetAsync(aux_, 0, sizeof(uint32_t) * 2 * (size_t)slots_, st));
-    if (mom_) LX_HIP(hipMemsetAsync(mom_, 0, sizeof(unsigned long long) * DM_MOM_WORDS * (size_t)slots_, st));
+    tab_.clear(st);
     LX_HIP(hipMemsetAsync(ctr_.p, 0, sizeof(unsigned long long) * DM_CTR_WORDS, st));
   }
   void free_graveyard() {
@@ -1123,7 +1066,7 @@ class DenseMap {
   void wait_adds() {
     if (last_st_) LX_HIP(hipEventSynchronize(ev_last_));
     if (staged_pending_) { LX_HIP(hipEventSynchronize(ev_staged_)); staged_pending_ = false; }
-    snap_pending_ = false;
+    occ_.snapshot_abandoned();
     free_graveyard();
   }
   // exact counters, after every add
@@ -1134,54 +1077,36 @@ class DenseMap {
     LX_HIP(hipStreamSynchronize(own_));
     const unsigned long long* c = (const unsigned long long*)h_ctr_.p;
     LX_REQUIRE(c[3] == 0ull, "dense map: hash table overflow");
-    occ_ = c[0]; drop_range_ = c[1]; drop_key_ = c[2];
+    occ_.exact(c[0]);
+    drop_range_ = c[1]; drop_key_ = c[2];
     for (int k = 0; k < 6; k++) carve_ctr_[k] = c[4 + k];
-    pend_ = pend_snap_ = 0;
   }
   // the occupancy snapshot that has landed, if any
   void poll_snapshot() {
-    if (!snap_pending_) return;
+    if (!occ_.snap_pending) return;
     const hipError_t e = hipEventQuery(ev_snap_);
     if (e == hipErrorNotReady) return;
     LX_HIP(e);
-    occ_ = h_snap_.p[0] | ((uint64_t)h_snap_.p[1] << 32);
-    pend_ = pend_snap_;
-    snap_pending_ = false;
+    occ_.snapshot_landed(h_snap_.p[0] | ((uint64_t)h_snap_.p[1] << 32));
   }
   // capacity rule (include/loamx.h): decided before anything is enqueued; the exact count is waited for only near the cap
   bool admit(uint32_t n) {
     poll_snapshot();
-    if (!cfg.max_voxels) return true;
-    if (occ_ + pend_ + n <= cfg.max_voxels) return true;
+    if (occ_.admits_by_bound(n, cfg.max_voxels)) return true;
     read_counters();
-    return occ_ + n <= cfg.max_voxels;
+    return occ_.admits_exact(n, cfg.max_voxels);
   }
   // growth: keep the load at most one half even if every one of n records, and every point enqueued since the last count, made a voxel
   // of its own.  The rehash into the larger table is enqueued on st; the host does not wait
   void grow_for(uint64_t n, hipStream_t st) {
-    uint64_t want = slots_;
-    while (occ_ + pend_ + n > want / 2) want *= 2;
+    const uint64_t want = occ_.slots_wanted(tab_.slots, n);
     LX_REQUIRE(want <= (1ull << 31), "dense map: more voxels than the table can index");
-    if (want != slots_) {
-      unsigned long long *nk = nullptr, *nv = nullptr, *nm = nullptr;
-      uint32_t* na = nullptr;
-      alloc_table(want, nk, nv, aux_ ? &na : nullptr, mom_ ? &nm : nullptr);
-      LX_HIP(hipMemsetAsync(nk, 0xff, sizeof(unsigned long long) * want, st));
-      LX_HIP(hipMemsetAsync(nv, 0, sizeof(unsigned long long) * 4 * want, st));   // (slots claimed later accumulate from zero)
-      if (nm) LX_HIP(hipMemsetAsync(nm, 0, sizeof(unsigned long long) * DM_MOM_WORDS * want, st));
-      const loamx_densemap_static_rule none = {0u, 0u, 0u};
-      if (aux_) {
-        LX_HIP(hipMemsetAsync(na, 0, sizeof(uint32_t) * 2 * want, st));
-        launch_rehash<true, false>(st, nk, nv, want, na, nm, none);
-      } else {
-        launch_rehash<false, false>(st, nk, nv, want, na, nm, none);
-      }
-      retire_table();
-      keys_ = nk;
-      vals_ = nv;
-      aux_ = na;
-      mom_ = nm;
-      slots_ = (uint32_t)want;
+    if (want != tab_.slots) {
+      DmTable nt;
+      nt.alloc(want, tab_.aux != nullptr, tab_.mom != nullptr);
+      nt.clear(st);
+      launch_rehash<false>(st, nt, loamx_densemap_static_rule{0u, 0u, 0u});
+      replace_table(nt);
       rehashes++;
     }
   }
@@ -1191,19 +1116,11 @@ class DenseMap {
                      uint32_t miss_stride, const unsigned long long* smom, const DmCtrAdd& add, uint64_t s_offered) {
     grow_for(s_occ, own_);
     const dim3 grid(sn ? (sn + 255u) / 256u : 1u), block(256);   // (one block at least: its first thread adds the statistics)
-    const uint32_t mask = slots_ - 1u, sh = 64u - log2u(slots_);
-    if (aux_ && mom_)
-      hipLaunchKernelGGL((k_dm_merge<true, true>), grid, block, 0, own_, skeys, svals, sn, smiss, miss_stride, smom, keys_, vals_, mask, sh,
-                         ctr_.p, aux_, mom_, add);
-    else if (aux_)
-      hipLaunchKernelGGL((k_dm_merge<true, false>), grid, block, 0, own_, skeys, svals, sn, smiss, miss_stride, smom, keys_, vals_, mask, sh,
-                         ctr_.p, aux_, mom_, add);
-    else if (mom_)
-      hipLaunchKernelGGL((k_dm_merge<false, true>), grid, block, 0, own_, skeys, svals, sn, smiss, miss_stride, smom, keys_, vals_, mask, sh,
-                         ctr_.p, aux_, mom_, add);
-    else
-      hipLaunchKernelGGL((k_dm_merge<false, false>), grid, block, 0, own_, skeys, svals, sn, smiss, miss_stride, smom, keys_, vals_, mask, sh,
-                         ctr_.p, aux_, mom_, add);
+    const DmTable& T = tab_;
+    dm_dispatch2(T.aux != nullptr, T.mom != nullptr, [&](auto A, auto M) {
+      hipLaunchKernelGGL((k_dm_merge<decltype(A)::value, decltype(M)::value>), grid, block, 0, own_, skeys, svals, sn, smiss, miss_stride, smom, T.keys,
+                         T.vals, T.mask(), T.shift(), ctr_.p, T.aux, T.mom, add);
+    });
     LX_HIP(hipGetLastError());
     offered_ += s_offered;
     LX_HIP(hipStreamSynchronize(own_));   // (the rehash of a growth still read the table that read_counters is about to free)
@@ -1230,8 +1147,8 @@ class DenseMap {
     C.use_rule = rule ? 1 : 0;
     C.rule = rule ? *rule : loamx_densemap_static_rule{0u, 0u, 0u};
     LX_HIP(hipMemsetAsync(rc_.p, 0, sizeof(unsigned long long) * 5, own_));
-    hipLaunchKernelGGL(k_dm_raycast, dim3((n + 255u) / 256u), dim3(256), 0, own_, pts, n, C, keys_, vals_, aux_, slots_ - 1u,
-                       64u - log2u(slots_), ctr_.p, rc_.p, out ? d_hits_.p : nullptr);
+    hipLaunchKernelGGL(k_dm_raycast, dim3((n + 255u) / 256u), dim3(256), 0, own_, pts, n, C, tab_.keys, tab_.vals, tab_.aux, tab_.mask(),
+                       tab_.shift(), ctr_.p, rc_.p, out ? d_hits_.p : nullptr);
     LX_HIP(hipGetLastError());
     store_to_pinned_u32(h_rc_.p, (const uint32_t*)rc_.p, 10, own_);
     if (out) store_to_pinned_u32(h_hits_.p, (const uint32_t*)d_hits_.p, HIT_WORDS * n, own_);
@@ -1249,32 +1166,26 @@ class DenseMap {
       F.max2 = cfg.max_range * cfg.max_range;
       F.use_max = cfg.max_range > 0.f ? 1 : 0;
       F.ox = origin[0]; F.oy = origin[1]; F.oz = origin[2];
-      const uint32_t sh = 64u - log2u(slots_);
-      const dim3 block(256);
-      if (!aux_) {
-        launch_insert<false>(st, pts, n, F, sh, 0u);
+      if (!tab_.aux) {
+        launch_insert<false>(st, pts, n, F, 0u);
       } else {
         // carving: the insert stamps its voxels with the call's sequence number, and the rays are traced behind it
         seq_++;
-        launch_insert<true>(st, pts, n, F, sh, seq_);
+        launch_insert<true>(st, pts, n, F, seq_);
         DmCarve R;
         R.max2 = carve_.max_range * carve_.max_range;
         R.use_max = carve_.max_range > 0.f ? 1 : 0;
         R.stride = carve_.ray_stride; R.end_margin = carve_.end_margin; R.max_steps = carve_.max_steps; R.seq = seq_;
         const uint64_t span = 256ull * R.stride;
-        hipLaunchKernelGGL(k_dm_carve, dim3((uint32_t)((n + span - 1) / span)), block, 0, st, pts, n, F, R, keys_, aux_, slots_ - 1u, sh, ctr_.p);
+        hipLaunchKernelGGL(k_dm_carve, dim3((uint32_t)((n + span - 1) / span)), dim3(256), 0, st, pts, n, F, R, tab_.keys, tab_.aux, tab_.mask(),
+                           tab_.shift(), ctr_.p);
       }
     }
     LX_HIP(hipGetLastError());
     offered_ += n;
-    pend_ += n;
-    if (snap_pending_) {
-      pend_snap_ += n;
-    } else {
+    if (occ_.enqueued(n)) {   // the occupancy snapshot behind this add
       store_to_pinned_u32(h_snap_.p, (const uint32_t*)ctr_.p, 2, st);
       LX_HIP(hipEventRecord(ev_snap_, st));
-      snap_pending_ = true;
-      pend_snap_ = 0;
     }
     LX_HIP(hipEventRecord(ev_last_, st));
     last_st_ = st;
@@ -1312,6 +1223,8 @@ struct loamx_densemap {
   DenseMap d;
   explicit loamx_densemap(const loamx_densemap_config& c) : d(c) {}
 };
+
+static void checked_axes(int axes) { LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)"); }
 
 extern "C" {
 
@@ -1378,7 +1291,7 @@ int loamx_densemap_get_stats(loamx_densemap* h, uint64_t stats[6]) {
 int loamx_densemap_download(loamx_densemap* h, loamx_cloud* out, int axes) {
   return guard([&]() {
     LX_REQUIRE(h && out, "NULL argument");
-    LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+    checked_axes(axes);
     check_cloud(out, false);
     std::vector<float4> rec;
     h->d.records(rec, axes);
@@ -1389,7 +1302,7 @@ int loamx_densemap_download(loamx_densemap* h, loamx_cloud* out, int axes) {
 int loamx_densemap_save_pcd(loamx_densemap* h, const char* path, int axes) {
   return guard([&]() {
     LX_REQUIRE(h && path, "NULL argument");
-    LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+    checked_axes(axes);
     std::vector<float4> rec;
     h->d.records(rec, axes);
     write_pcd_records(path, rec.data(), rec.size());
@@ -1399,7 +1312,7 @@ int loamx_densemap_save_pcd(loamx_densemap* h, const char* path, int axes) {
 int loamx_write_pcd(const char* path, const loamx_cloud* c, int axes) {
   return guard([&]() {
     LX_REQUIRE(path && c, "NULL argument");
-    LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+    checked_axes(axes);
     check_cloud(c, false);
     std::vector<float4> rec(c->count);
     pack_cloud(c, rec.data());
@@ -1440,6 +1353,14 @@ static loamx_densemap_static_rule checked_rule(const loamx_densemap_static_rule*
   return r;
 }
 #define LX_REQUIRE_CARVING(h) LX_REQUIRE((h)->d.carving(), "carving is not enabled")
+// the optional rule of a call: NULL stays NULL (every voxel); a rule is checked into `r` and needs carving
+static const loamx_densemap_static_rule* checked_optional_rule(loamx_densemap* h, const loamx_densemap_static_rule* rule,
+                                                               loamx_densemap_static_rule& r) {
+  if (!rule) return nullptr;
+  r = checked_rule(rule);
+  LX_REQUIRE_CARVING(h);
+  return &r;
+}
 
 int loamx_densemap_enable_carving(loamx_densemap* h, const loamx_densemap_carve_config* cfg) {
   return guard([&]() {
@@ -1476,7 +1397,7 @@ int loamx_densemap_download_misses(loamx_densemap* h, uint32_t* out, uint64_t ca
 int loamx_densemap_download_static(loamx_densemap* h, loamx_cloud* out, int axes, const loamx_densemap_static_rule* rule) {
   return guard([&]() {
     LX_REQUIRE(h && out, "NULL argument");
-    LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+    checked_axes(axes);
     const loamx_densemap_static_rule r = checked_rule(rule);
     LX_REQUIRE_CARVING(h);
     check_cloud(out, false);
@@ -1489,7 +1410,7 @@ int loamx_densemap_download_static(loamx_densemap* h, loamx_cloud* out, int axes
 int loamx_densemap_save_pcd_static(loamx_densemap* h, const char* path, int axes, const loamx_densemap_static_rule* rule) {
   return guard([&]() {
     LX_REQUIRE(h && path, "NULL argument");
-    LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+    checked_axes(axes);
     const loamx_densemap_static_rule r = checked_rule(rule);
     LX_REQUIRE_CARVING(h);
     std::vector<float4> rec;
@@ -1532,7 +1453,7 @@ int loamx_densemap_surfel_of(float leaf, const int32_t idx[3], const uint64_t va
   return guard([&]() {
     LX_REQUIRE(idx && vals && mom && out, "NULL argument");
     LX_REQUIRE(leaf > 0.f && std::isfinite(leaf), "leaf must be positive");
-    LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+    checked_axes(axes);
     LX_REQUIRE(vals[0] != 0ull, "a voxel holds at least one point");
     const loamx_densemap_surfel_config c = checked_surfel_config(cfg);
     const long long ia[3] = {idx[0], idx[1], idx[2]};
@@ -1565,16 +1486,11 @@ int loamx_densemap_download_moments(loamx_densemap* h, uint64_t* out, uint64_t c
 // the surfels of a call: arguments checked in the order of download_static (a rule needs carving)
 static void surfels_of_call(loamx_densemap* h, int axes, const loamx_densemap_surfel_config* cfg, const loamx_densemap_static_rule* rule,
                             std::vector<loamx_surfel>& out) {
-  LX_REQUIRE(axes == 0 || axes == 1, "axes must be 0 (LOAM frame) or 1 (sensor axes)");
+  checked_axes(axes);
   const loamx_densemap_surfel_config c = checked_surfel_config(cfg);
   LX_REQUIRE_MOMENTS(h);
-  if (rule) {
-    const loamx_densemap_static_rule r = checked_rule(rule);
-    LX_REQUIRE_CARVING(h);
-    h->d.surfels(out, axes, c, &r);
-  } else {
-    h->d.surfels(out, axes, c, nullptr);
-  }
+  loamx_densemap_static_rule r;
+  h->d.surfels(out, axes, c, checked_optional_rule(h, rule, r));
 }
 int loamx_densemap_download_surfels(loamx_densemap* h, loamx_surfel* out, uint64_t capacity, uint64_t* n, int axes,
                                     const loamx_densemap_surfel_config* cfg, const loamx_densemap_static_rule* rule) {
@@ -1605,14 +1521,8 @@ int loamx_densemap_freeze(loamx_densemap* h, const loamx_densemap_surfel_config*
     LX_REQUIRE(h, "NULL handle");
     const loamx_densemap_surfel_config c = checked_surfel_config(cfg);
     LX_REQUIRE_MOMENTS(h);
-    uint64_t n = 0;
-    if (rule) {
-      const loamx_densemap_static_rule r = checked_rule(rule);
-      LX_REQUIRE_CARVING(h);
-      n = h->d.freeze(c, &r);
-    } else {
-      n = h->d.freeze(c, nullptr);
-    }
+    loamx_densemap_static_rule r;
+    const uint64_t n = h->d.freeze(c, checked_optional_rule(h, rule, r));
     if (n_surfels) *n_surfels = n;
     return LOAMX_OK;
   });

@@ -3,6 +3,8 @@
 // 20-bit fixed-point offsets inside the voxel, so the table does not depend on the order of the additions).
 #pragma once
 #include "common.h"
+#include "densemap_growth.hpp"
+#include <vector>
 
 namespace loamx {
 
@@ -11,6 +13,82 @@ constexpr int DM_QBITS = 20;              // fixed-point bits of the offset insi
 constexpr int DM_KBITS = 21;              // bits per axis of the key: i + 2^20, |i| < 2^20
 constexpr float DM_QSCALE = 1048576.f;    // 2^20
 constexpr float DM_IMAX = 1048576.f;      // |i| must stay below this
+constexpr int DM_MOM_WORDS = 9;           // moments: 64-bit words per slot (densemap.hip)
+
+// the key of the voxel (ix, iy, iz), each |i| < 2^20, and its inverse
+__host__ __device__ inline unsigned long long dm_key(int ix, int iy, int iz) {
+  return (unsigned long long)(uint32_t)(ix + (1 << DM_QBITS)) | ((unsigned long long)(uint32_t)(iy + (1 << DM_QBITS)) << DM_KBITS) |
+         ((unsigned long long)(uint32_t)(iz + (1 << DM_QBITS)) << (2 * DM_KBITS));
+}
+inline void dm_key_indices(unsigned long long k, long long ia[3]) {
+  const unsigned long long km = (1ull << DM_KBITS) - 1ull;
+  for (int a = 0; a < 3; a++) ia[a] = (long long)((k >> (DM_KBITS * a)) & km) - (1ll << DM_QBITS);
+}
+
+inline uint32_t log2u(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }
+
+// `behind` runs behind whatever `ahead` holds now
+inline void dm_stream_behind(hipStream_t behind, hipStream_t ahead) {
+  hipEvent_t ev = nullptr;
+  LX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ev, ahead);
+  if (e == hipSuccess) e = hipStreamWaitEvent(behind, ev, 0);
+  (void)hipEventDestroy(ev);   // (the wait keeps what it needs)
+  LX_HIP(e);
+}
+
+// The map's table in HBM: `slots` (a power of two) keys, four value words per slot and, where the feature is on, aux (carving: 2 x 32
+// bits per slot, [2 * slot] miss, [2 * slot + 1] stamp) and mom (moments: nine words per slot).  Owns its arrays; the kernels take them
+// as scalar arguments, expanded at the launch sites
+struct DmTable {
+  unsigned long long *keys = nullptr, *vals = nullptr, *mom = nullptr;
+  uint32_t* aux = nullptr;
+  uint32_t slots = 0;
+
+  DmTable() = default;
+  DmTable(const DmTable&) = delete;
+  DmTable& operator=(const DmTable&) = delete;
+  ~DmTable() { (void)hipFree(keys); (void)hipFree(vals); (void)hipFree(aux); (void)hipFree(mom); }
+  void swap(DmTable& o) {
+    std::swap(keys, o.keys); std::swap(vals, o.vals); std::swap(mom, o.mom); std::swap(aux, o.aux); std::swap(slots, o.slots);
+  }
+  uint32_t mask() const { return slots - 1u; }
+  uint32_t shift() const { return 64u - log2u(slots); }   // (dm_hash)
+
+  // an empty table becomes one of n <= 2^31 slots, its contents undefined; nothing is kept when an allocation fails
+  void alloc(uint64_t n, bool with_aux, bool with_mom) {
+    slots = (uint32_t)n;
+    try {
+      LX_HIP(hipMalloc((void**)&keys, sizeof(unsigned long long) * n));
+      LX_HIP(hipMalloc((void**)&vals, sizeof(unsigned long long) * 4 * n));
+      if (with_aux) add_aux();
+      if (with_mom) add_mom();
+    } catch (...) {
+      DmTable().swap(*this);   // (freed by the temporary)
+      throw;
+    }
+  }
+  // a feature's array beside a table that stands; the caller clears it
+  void add_aux() { LX_HIP(hipMalloc((void**)&aux, sizeof(uint32_t) * 2 * (size_t)slots)); }
+  void add_mom() { LX_HIP(hipMalloc((void**)&mom, sizeof(unsigned long long) * DM_MOM_WORDS * (size_t)slots)); }
+  void clear_aux(hipStream_t st) { LX_HIP(hipMemsetAsync(aux, 0, sizeof(uint32_t) * 2 * (size_t)slots, st)); }
+  void clear_mom(hipStream_t st) { LX_HIP(hipMemsetAsync(mom, 0, sizeof(unsigned long long) * DM_MOM_WORDS * (size_t)slots, st)); }
+  // every key EMPTY, every word zero (slots claimed later accumulate from zero), enqueued on st
+  void clear(hipStream_t st) {
+    LX_HIP(hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * (size_t)slots, st));
+    LX_HIP(hipMemsetAsync(vals, 0, sizeof(unsigned long long) * 4 * (size_t)slots, st));
+    if (mom) clear_mom(st);
+    if (aux) clear_aux(st);
+  }
+  // the arrays go to the graveyard (work enqueued earlier may still read them: freed where the host waits anyway); the table is empty
+  void retire(std::vector<void*>& graveyard) {
+    for (void* p : {(void*)keys, (void*)vals, (void*)aux, (void*)mom})
+      if (p) graveyard.push_back(p);
+    keys = vals = mom = nullptr;
+    aux = nullptr;
+    slots = 0;
+  }
+};
 
 // Where a device-side add reads: a registered cloud that some other handle keeps in HBM, the stream that wrote it, and the pose of the
 // sweep.  Filled by the internal accessors of mapping.hip / pipeline.hip (the handle structs stay where they are).

@@ -101,8 +101,6 @@ __global__ __launch_bounds__(256) void k_dm_align_step_many(const float4* __rest
 #include "dm_align_step_body.inc"
 }
 
-static uint32_t log2u(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }
-
 void DmFrozen::drop() {
   if (tab_) (void)hipFree(tab_);
   tab_ = nullptr;
@@ -111,8 +109,7 @@ void DmFrozen::drop() {
 }
 
 void DmFrozen::build(const unsigned long long* keys, const float* rec, size_t n, hipStream_t st) {
-  uint64_t slots = 1024;
-  while (slots < 2 * (uint64_t)n) slots *= 2;
+  const uint64_t slots = dm_slots_for(1024, n);
   LX_REQUIRE(slots <= (1ull << 31), "dense map: more surfels than the snapshot can index");
   DmFrozenEntry* tab = nullptr;
   LX_HIP(hipMalloc((void**)&tab, sizeof(DmFrozenEntry) * slots));
@@ -422,12 +419,7 @@ static bool align_source_ready(loamx_densemap* h, const DenseSource& s, const lo
   if (!s.has_cloud) return false;
   LX_HIP(hipSetDevice(mc.device));
   st = loamx_densemap_own_stream(h);
-  hipEvent_t ev = nullptr;
-  LX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  hipError_t e = hipEventRecord(ev, s.stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
-  (void)hipEventDestroy(ev);   // (the wait keeps what it needs)
-  LX_HIP(e);
+  dm_stream_behind(st, s.stream);
   return true;
 }
 

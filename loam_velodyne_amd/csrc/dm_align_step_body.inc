@@ -34,11 +34,9 @@
           for (int ox = -A.nb; ox <= A.nb; ox++) {
             const int cx = ic[0] + ox, cy = ic[1] + oy, cz = ic[2] + oz;
             if (cx <= -lim || cx >= lim || cy <= -lim || cy >= lim || cz <= -lim || cz >= lim) continue;   // outside the key range
-            const unsigned long long key = (unsigned long long)(uint32_t)(cx + lim) | ((unsigned long long)(uint32_t)(cy + lim) << DM_KBITS) |
-                                           ((unsigned long long)(uint32_t)(cz + lim) << (2 * DM_KBITS));
             uint32_t slot = 0u;
             float mx = 0.f, my = 0.f;
-            if (!dm_frozen_find(tab, mask, shift, key, slot, mx, my)) continue;
+            if (!dm_frozen_find(tab, mask, shift, dm_key(cx, cy, cz), slot, mx, my)) continue;
             const float ex = pp[0] - mx, ey = pp[1] - my, ez = pp[2] - tab[slot].mean[2];
             const float d2 = (ex * ex + ey * ey) + ez * ez;
             if (!found || d2 < best) {
