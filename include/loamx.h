@@ -1059,6 +1059,75 @@ int loamx_densemap_raycast_from_pipeline(loamx_densemap* h, loamx_pipeline* p, u
                                          const loamx_densemap_raycast_config* cfg, const loamx_densemap_static_rule* rule,
                                          loamx_ray_hit* out, uint64_t capacity, uint64_t counts[5]);
 
+/* Sweep log and rebuild (optional: a handle that never calls loamx_densemap_enable_history runs the kernels it ran, allocates what
+ * it allocated and exports the same bytes).  The map keeps sums per voxel, not sweeps; with history on it also keeps every added
+ * cloud in device memory, and loamx_densemap_rebuild replays that log under one rigid correction per logged call into a fresh
+ * table: after a loop closure (loamx_place -> loamx_densemap_align_many -> the host's pose graph) the map is made consistent with
+ * the corrected poses without a point crossing PCIe.
+ *
+ * The log.  loamx_densemap_enable_history is allowed only on an empty map (a fresh handle, or right after reset; otherwise
+ * LOAMX_E_INVALID and the handle is unchanged), in any order with enable_carving / enable_moments, and stays on until destroy; reset
+ * empties the log and keeps history on.  Every add call that reaches the insert is logged (add, add_from_map, add_from_pipeline):
+ * its whole cloud as offered, x, y, z, w byte for byte, including the points the range and key filters drop and non-finite ones.
+ * Empty clouds, LOAMX_SKIPPED and refused calls are not logged.  The append is a device-to-device copy on the stream of the insert,
+ * behind whatever wrote the cloud; the caller is not blocked.  Per logged call the host keeps the first point, the count and the
+ * origin; the call index is the running count of logged calls (the carving sequence number minus one).  The log is never rewritten:
+ * it holds the points as they were added.  It grows by doubling from initial_points (a new block, a device-to-device copy on the
+ * add's stream, the old block freed where the host next waits), never beyond max_bytes: with max_bytes an add whose cloud would take
+ * the log past max_bytes / 16 points is refused with LOAMX_E_CAPACITY before anything is enqueued, map and log unchanged.  Point
+ * indices are 64-bit.  A map that has no sweeps behind it cannot be rebuilt: loamx_densemap_load and loamx_densemap_merge_file
+ * into a handle with history, and loamx_densemap_merge with such a handle as dst, answer LOAMX_E_INVALID (handle unchanged); such a
+ * handle as src is fine.  The 'LXDM' file stays at version 1 and does not carry the log.
+ * loamx_densemap_history_size: logged calls and logged points.  loamx_densemap_history_download waits for the adds as download
+ * does and returns, through pinned memory, the logged bytes of that call (out->count in = capacity, out = the call's count) and its
+ * origin; LOAMX_E_CAPACITY when the cloud does not fit (out->count = the call's count, nothing else written), LOAMX_E_INVALID for a
+ * call beyond the log or a handle without history.
+ *
+ * The correction.  A correction is a row-major 3x4 matrix R | t from the map frame to the map frame, x -> R x + t; for logged call k
+ * the host computes it in double as P_k(now) * P_k(when added)^-1.  Its 12 doubles must be finite; nothing else is checked (the host
+ * answers for R being a rotation).  It is rounded to f32 once, entry by entry, and applied per point in f32, no fused multiply-add,
+ * in this order:  p'_a = ((R_a0*x + R_a1*y) + R_a2*z) + t_a;  w is untouched.  The call's origin goes through the same expression.
+ * A correction whose 12 rounded entries compare equal (==) to the identity's is the identity: that call is replayed from its logged
+ * bytes without any arithmetic (non-finite points, signed zeros and payloads stay as they were).  loamx_densemap_correct (host
+ * only, no device) is this definition for n packed x, y, z triples (xyz_out may be xyz_in); LOAMX_E_INVALID, nothing written, for a
+ * non-finite entry.
+ *
+ * loamx_densemap_rebuild(h, corrections, n_calls): afterwards the handle holds the map, the three point statistics, the six carve
+ * statistics and the sequence number that a fresh handle of the same configuration and features would hold after
+ * add(correct(C_k, points_k), correct(C_k, origin_k)) for k = 0, 1, ... in order (corrections NULL: every C_k the identity).  The
+ * replay always starts from the logged originals: a second rebuild does not compose with the first, and the log itself is
+ * unchanged.  Adds after a rebuild go on as on that fresh handle and are logged as given.  The frozen snapshot is not touched (it
+ * still shows the map as it was frozen: freeze again); voxels removed by prune come back (they are in the log: prune again).
+ * With carving off every word is independent of the order, and the whole log is replayed in one launch whatever the number of
+ * calls: a thread finds its call from its 64-bit point index in a per-call table in device memory (first point, f32 correction,
+ * identity flag, corrected origin), transforms in registers and inserts with the range filter about that call's corrected origin.
+ * With carving on the calls are replayed in order, one insert launch (stamp k + 1) and one carve launch per call, enqueued back to
+ * back.  No transformed copy of the log is made.  The replay goes into a fresh table with its own counter words, of the smallest
+ * size, by doubling from initial_slots, that holds the voxels the map has now at a load of one half.  Before probing, a kernel reads
+ * the running occupancy; once it exceeds half the slots it sets a "too small" word and returns without inserting, so a table that is
+ * too small costs bounded work.  The host waits and reads the words: the attempt has failed iff the occupancy exceeds half the
+ * slots or the "too small" or the overflow word is set (all three mean: more voxels than half the slots), and is repeated with
+ * twice the slots, up to 2^31.  On success the table has the smallest power of two of slots that is >= initial_slots, >= 2 x the
+ * voxels before and >= 2 x the voxels after; peak memory is the old table plus the new one.
+ * The call waits for the adds as download does, runs on the map's own stream and blocks until the new map stands.
+ * LOAMX_E_INVALID, with a message that names the argument: no history; n_calls different from the log's count (with corrections
+ * NULL too); a non-finite entry.  LOAMX_E_CAPACITY: with max_voxels, the rebuilt map holds more voxels than the cap.  Any refusal
+ * or failure, a failed allocation of the second table included, leaves the handle with its old map, statistics and log.
+ * loamx_densemap_get_rebuild_stats: rebuilds that succeeded, tables tried, replay launches, points replayed (the last three over
+ * every attempt); they run from the handle's creation and are never cleared. */
+typedef struct loamx_densemap_history_config {
+  uint64_t max_bytes;       /* cap on the log's device memory; 0 = bounded by device memory only (default 0) */
+  uint64_t initial_points;  /* capacity at enabling, >= 1 (default 1 << 20) */
+} loamx_densemap_history_config;
+void loamx_densemap_history_default_config(loamx_densemap_history_config* cfg);   /* host only */
+int loamx_densemap_enable_history(loamx_densemap* h, const loamx_densemap_history_config* cfg /* NULL: the defaults */);
+int loamx_densemap_history_size(loamx_densemap* h, uint64_t* calls, uint64_t* points);
+int loamx_densemap_history_download(loamx_densemap* h, uint64_t call, loamx_cloud* out /* count in = capacity */, float origin[3]);
+int loamx_densemap_correct(const double correction[12], const float* xyz_in, float* xyz_out, uint64_t n);   /* host only, no device */
+int loamx_densemap_rebuild(loamx_densemap* h, const double* corrections /* 12 * n_calls; NULL: every call the identity */,
+                           uint64_t n_calls);
+int loamx_densemap_get_rebuild_stats(loamx_densemap* h, uint64_t stats[4]);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Place recognition (not in the reference): a database of rotation-invariant sweep descriptors in device memory (Scan Context: a
  * ring x sector polar grid of maximum heights around the sensor) and an exhaustive search for the earlier entries that look like a

@@ -15,8 +15,13 @@
 //
 // Freeze (loamx_densemap_freeze): the surfels of that export, computed once, go into a second table on the device that the alignment
 // of densemap_align.hip reads; the table above never learns of it.
+//
+// History (loamx_densemap_enable_history, densemap_history.hpp): every add also appends its cloud to a log in HBM, and
+// loamx_densemap_rebuild replays that log, each call under a rigid correction, into a fresh table with the insert's and the carve
+// kernel's own bodies (dm_insert_body.inc, dm_carve_body.inc); the table that stands is replaced only when the replay has succeeded.
 #include "densemap.hpp"
 #include "densemap_file.hpp"
+#include "densemap_history.hpp"
 #include "host_math.h"
 #include "pinned_copy.hpp"
 #include "scan.hpp"
@@ -117,123 +122,11 @@ __global__ __launch_bounds__(256) void k_dm_insert(const float4* __restrict__ pt
                                                    unsigned long long* __restrict__ mom) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
-  unsigned long long key = DM_EMPTY;
-  uint32_t q[3] = {0u, 0u, 0u};
-  int w[3] = {0, 0, 0};   // (MOMENTS) the fixed-point vector from the origin
-  bool drop_range = false, drop_key = false;
-  if (i < n) {
-    const float4 p = pts[i];
-    const float dx = p.x - F.ox, dy = p.y - F.oy, dz = p.z - F.oz;
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    if (!(d2 >= F.min2 && (!F.use_max || d2 <= F.max2))) {
-      drop_range = true;
-    } else {
-      const float c[3] = {p.x, p.y, p.z};
-      unsigned long long k = 0ull;
-#pragma unroll
-      for (int a = 0; a < 3; a++) {
-        const float t = c[a] * F.inv;
-        const float fi = floorf(t);
-        if (!(fabsf(fi) < DM_IMAX)) drop_key = true;   // (NaN too)
-        const float f = t - fi;
-        const uint32_t qa = (uint32_t)(f * DM_QSCALE);
-        q[a] = drop_key ? 0u : (qa < (1u << DM_QBITS) - 1u ? qa : (1u << DM_QBITS) - 1u);
-        const uint32_t ia = drop_key ? 0u : (uint32_t)((int)fi + (1 << DM_QBITS));
-        k |= (unsigned long long)ia << (DM_KBITS * a);
-      }
-      if (!drop_key) key = k;
-      if (MOMENTS) {
-        const float d[3] = {dx, dy, dz};
-#pragma unroll
-        for (int a = 0; a < 3; a++) w[a] = (int)fminf(fmaxf(d[a] * 1024.0f, -1073741824.0f), 1073741824.0f);
-      }
-    }
-  }
-  dm_wave_count(&ctr[1], drop_range);
-  dm_wave_count(&ctr[2], drop_key);
-  const bool valid = key != DM_EMPTY;
-  uint32_t cnt = valid ? 1u : 0u;
-  bool owner = valid;
-  unsigned long long ms[DM_MOM_WORDS] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};   // (constant indices only: registers)
-  if (MOMENTS) {
-    const unsigned long long qx = q[0], qy = q[1], qz = q[2];
-    ms[0] = qx * qx; ms[1] = qy * qy; ms[2] = qz * qz;
-    ms[3] = qx * qy; ms[4] = qx * qz; ms[5] = qy * qz;
-#pragma unroll
-    for (int a = 0; a < 3; a++) ms[6 + a] = (unsigned long long)(long long)w[a];
-  }
-  if (COMBINE) {
-    // group the lanes by key: the lowest lane of each group (its leader) collects the group's count and sums
-    int leader = -1;
-    unsigned long long todo = __ballot(valid);
-    while (todo) {
-      const int src = __builtin_ctzll(todo);
-      const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)key, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(key >> 32), src, 64);
-      const unsigned long long k0 = ((unsigned long long)hi << 32) | lo;
-      const unsigned long long m = __ballot(valid && key == k0);
-      if (valid && key == k0) {
-        leader = src;
-        if (lane == src) cnt = (uint32_t)__popcll(m);
-      }
-      todo &= ~m;
-    }
-    owner = valid && leader == lane;
-    if constexpr (MOMENTS) {
-      __shared__ unsigned long long macc[4][DM_MOM_WORDS][64];
-      if (owner) {
-#pragma unroll
-        for (int k = 0; k < DM_MOM_WORDS; k++) macc[wid][k][lane] = 0ull;
-      }
-      __syncthreads();
-      if (valid) {   // (integer adds modulo 2^64: the order does not matter)
-#pragma unroll
-        for (int k = 0; k < 6; k++) atomicAdd(&macc[wid][k][leader], ms[k]);
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-          atomicAdd(&macc[wid][6 + a][leader], (unsigned long long)((long long)w[a] * (1ll << DM_VBITS) + (long long)q[a]));
-      }
-      __syncthreads();
-      if (owner) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) ms[k] = macc[wid][k][lane];
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-          const unsigned long long pk = macc[wid][6 + a][lane];
-          q[a] = (uint32_t)(pk & ((1ull << DM_VBITS) - 1ull));
-          ms[6 + a] = (unsigned long long)((long long)pk >> DM_VBITS);   // (arithmetic shift: floor, and the low field is >= 0)
-        }
-      }
-    } else {
-      __shared__ uint32_t acc[4][64][3];
-      if (owner) { acc[wid][lane][0] = 0u; acc[wid][lane][1] = 0u; acc[wid][lane][2] = 0u; }
-      __syncthreads();
-      if (valid) {   // (integer adds: the order does not matter; <= 64 x 2^20 fits 32 bits)
-        atomicAdd(&acc[wid][leader][0], q[0]);
-        atomicAdd(&acc[wid][leader][1], q[1]);
-        atomicAdd(&acc[wid][leader][2], q[2]);
-      }
-      __syncthreads();
-      if (owner) { q[0] = acc[wid][lane][0]; q[1] = acc[wid][lane][1]; q[2] = acc[wid][lane][2]; }
-    }
-  }
-  uint32_t slot = 0;
-  bool won = false, ok = true;
-  if (owner) ok = dm_find_or_claim(keys, mask, shift, key, slot, won);
-  dm_wave_count(&ctr[0], won);
-  if (owner && !ok) ctr[3] = 1ull;
-  if (owner && ok) {
-    unsigned long long* v = vals + 4ull * slot;
-    atomicAdd(&v[0], (unsigned long long)cnt);
-    atomicAdd(&v[1], (unsigned long long)q[0]);
-    atomicAdd(&v[2], (unsigned long long)q[1]);
-    atomicAdd(&v[3], (unsigned long long)q[2]);
-    if (STAMP) __hip_atomic_store(&aux[2ull * slot + 1], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (MOMENTS) {
-      unsigned long long* mm = mom + (unsigned long long)DM_MOM_WORDS * slot;
-#pragma unroll
-      for (int k = 0; k < DM_MOM_WORDS; k++) atomicAdd(&mm[k], ms[k]);   // (results unused: no-return atomics)
-    }
-  }
+#define DM_INSERT_HAS_POINT i < n
+#define DM_INSERT_POINT pts[i]
+#include "dm_insert_body.inc"
+#undef DM_INSERT_HAS_POINT
+#undef DM_INSERT_POINT
 }
 
 // One axis of the voxel walk (include/loamx.h): the origin's and the point's cell, the cells between them, and the ray parameter at
@@ -290,56 +183,81 @@ __device__ inline void dm_walk_step(DmAxis& X, DmAxis& Y, DmAxis& Z) {
 __global__ __launch_bounds__(256) void k_dm_carve(const float4* __restrict__ pts, uint32_t n, DmFilter F, DmCarve R,
                                                   const unsigned long long* keys, uint32_t* aux, uint32_t mask, uint32_t shift,
                                                   unsigned long long* __restrict__ ctr) {
-  const unsigned long long span = 256ull * R.stride, base = (unsigned long long)blockIdx.x * span;
-  uint32_t left_out = 0u;
-  if (R.stride > 1u) {
-    const unsigned long long end = base + span < (unsigned long long)n ? base + span : (unsigned long long)n;
-    for (unsigned long long j = base + threadIdx.x; j < end; j += 256ull) {
-      float d2;
-      if (j % R.stride != 0ull && dm_added(pts[j], F, d2)) left_out++;
+#define DM_CARVE_POINT(j) pts[j]
+#include "dm_carve_body.inc"
+#undef DM_CARVE_POINT
+}
+
+// Replay (include/loamx.h, loamx_densemap_rebuild): the two kernels above over the sweep log, each point transformed in registers by
+// the correction of its call.  calls: one DmReplayCall per logged call, first points ascending.  A replay goes into a fresh table
+// whose size is a guess: before any probe a block reads the running occupancy, and once that has passed one half of the slots it sets
+// small[0] and returns (the whole block, before the body's barriers), so a table that is too small costs bounded work and no probe
+// loop ever runs in a full table for longer than its mask + 1 steps.  A replay that succeeds never took that exit in any block: the
+// occupancy only grows
+
+// true for the whole block when the table is too small; says so in small[0]
+__device__ inline bool dm_replay_too_small(const unsigned long long* ctr, uint32_t mask, unsigned long long* small) {
+  const unsigned long long occ = __hip_atomic_load(&ctr[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!__syncthreads_or(occ > ((unsigned long long)mask + 1ull) / 2ull ? 1 : 0)) return false;
+  if (threadIdx.x == 0) small[0] = 1ull;
+  return true;
+}
+// point idx of the log under the record of its call
+__device__ inline float4 dm_replay_point(const float4* __restrict__ log, unsigned long long idx, const DmReplayCall& c) {
+  float4 p = log[idx];
+  dm_replayed(c, p.x, p.y, p.z);
+  return p;
+}
+
+// the insert of the n points from `first` on, which belong to the calls [call_lo, call_hi): one launch for the whole log when no
+// word depends on the order of the calls (carving off: equal keys combine inside a wave across call boundaries, each point with the
+// range filter about its own call's corrected origin), one launch per call otherwise (STAMP: the stamp is the call's index + 1).
+// F0: the map's filter; its origin is not read
+template <bool COMBINE, bool STAMP, bool MOMENTS>
+__global__ __launch_bounds__(256) void k_dm_rebuild(const float4* __restrict__ log, unsigned long long first, unsigned long long n,
+                                                    const DmReplayCall* __restrict__ calls, uint32_t call_lo, uint32_t call_hi, DmFilter F0,
+                                                    unsigned long long* __restrict__ keys, unsigned long long* __restrict__ vals,
+                                                    uint32_t mask, uint32_t shift, unsigned long long* __restrict__ ctr,
+                                                    uint32_t* __restrict__ aux, unsigned long long* __restrict__ mom,
+                                                    unsigned long long* __restrict__ small) {
+  if (dm_replay_too_small(ctr, mask, small)) return;
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
+  DmFilter F = F0;
+  float4 pt = make_float4(0.f, 0.f, 0.f, 0.f);
+  uint32_t seq = 0u;
+  if (i < n) {
+    // the last call that starts at or before the point (call_lo does: the launch starts inside it)
+    const unsigned long long idx = first + i;
+    uint32_t lo = call_lo, hi = call_hi;
+    while (hi - lo > 1u) {
+      const uint32_t mid = lo + (hi - lo) / 2u;
+      if (calls[mid].first <= idx) lo = mid; else hi = mid;
     }
+    const DmReplayCall& c = calls[lo];
+    pt = dm_replay_point(log, idx, c);
+    F.ox = c.o[0]; F.oy = c.o[1]; F.oz = c.o[2];
+    seq = lo + 1u;
   }
-  const unsigned long long i = base + (unsigned long long)threadIdx.x * R.stride;
-  bool traced = false, skip_range = false, skip_steps = false, overflow = false;
-  uint32_t visited = 0u, missed = 0u;
-  if (i < (unsigned long long)n) {
-    const float4 p = pts[i];
-    float d2;
-    if (dm_added(p, F, d2)) {
-      if (R.use_max && !(d2 <= R.max2)) {
-        skip_range = true;
-      } else {
-        DmAxis X, Y, Z;
-        const bool okx = dm_axis_setup(F.ox, p.x, F.inv, X), oky = dm_axis_setup(F.oy, p.y, F.inv, Y), okz = dm_axis_setup(F.oz, p.z, F.inv, Z);
-        const uint32_t n_steps = X.rem + Y.rem + Z.rem;   // (each < 2^21)
-        if (!(okx && oky && okz) || n_steps > R.max_steps) {
-          skip_steps = true;
-        } else {
-          traced = true;
-          // cells k = 0 .. n_steps - 1 - end_margin are visited; cell k is the cell after k steps
-          const uint32_t n_visit = n_steps > R.end_margin ? n_steps - R.end_margin : 0u;
-          for (uint32_t k = 0; k < n_visit; k++) {
-            uint32_t slot = 0u;
-            const int f = dm_find(keys, mask, shift, dm_key(X.c, Y.c, Z.c), slot);
-            visited++;
-            if (f < 0) overflow = true;
-            if (f > 0 && aux[2ull * slot + 1] != R.seq) {   // occupied wins: a voxel this call hit is left alone
-              atomicAdd(&aux[2ull * slot], 1u);
-              missed++;
-            }
-            dm_walk_step(X, Y, Z);   // (k < n_steps: some axis has cells left)
-          }
-        }
-      }
-    }
-  }
-  if (overflow) ctr[3] = 1ull;
-  dm_wave_count(&ctr[4], traced);
-  dm_wave_sum(&ctr[5], left_out);
-  dm_wave_count(&ctr[6], skip_range);
-  dm_wave_count(&ctr[7], skip_steps);
-  dm_wave_sum(&ctr[8], visited);
-  dm_wave_sum(&ctr[9], missed);
+#define DM_INSERT_HAS_POINT i < n
+#define DM_INSERT_POINT pt
+#include "dm_insert_body.inc"
+#undef DM_INSERT_HAS_POINT
+#undef DM_INSERT_POINT
+}
+
+// the rays of one call behind its insert: k_dm_carve over the n points of *call in the log, from its corrected origin
+__global__ __launch_bounds__(256) void k_dm_rebuild_carve(const float4* __restrict__ log, const DmReplayCall* __restrict__ call, uint32_t n,
+                                                          DmFilter F0, DmCarve R, const unsigned long long* keys, uint32_t* aux, uint32_t mask,
+                                                          uint32_t shift, unsigned long long* __restrict__ ctr,
+                                                          unsigned long long* __restrict__ small) {
+  if (dm_replay_too_small(ctr, mask, small)) return;
+  const DmReplayCall c = *call;
+  DmFilter F = F0;
+  F.ox = c.o[0]; F.oy = c.o[1]; F.oz = c.o[2];
+#define DM_CARVE_POINT(j) dm_replay_point(log, c.first + (j), c)
+#include "dm_carve_body.inc"
+#undef DM_CARVE_POINT
 }
 
 // include/loamx.h, loamx_densemap_static_rule: the voxel with n points and `miss` crossings is dynamic
@@ -632,6 +550,7 @@ class DenseMap {
     if (last_st_) (void)hipEventSynchronize(ev_last_);
     (void)hipStreamSynchronize(own_);
     free_graveyard();
+    (void)hipFree(log_);
     DmTable().swap(tab_);
     (void)hipEventDestroy(ev_last_);
     (void)hipEventDestroy(ev_snap_);
@@ -644,7 +563,7 @@ class DenseMap {
     check_cloud(c, false);
     LX_HIP(hipSetDevice(cfg.device));
     const uint32_t n = c->count;
-    if (!admit(n)) return LOAMX_E_CAPACITY;
+    if (!admit(n) || !hist_.admits(n)) return LOAMX_E_CAPACITY;
     if (!n) return LOAMX_OK;
     if (staged_pending_) { LX_HIP(hipEventSynchronize(ev_staged_)); staged_pending_ = false; }   // (the staging block is still being read)
     h_stage_.reserve(n);
@@ -662,7 +581,7 @@ class DenseMap {
     LX_REQUIRE(s.device == cfg.device, "the dense map and its source live on different devices");
     if (!s.has_cloud) return LOAMX_SKIPPED;
     LX_HIP(hipSetDevice(cfg.device));
-    if (!admit(s.n)) return LOAMX_E_CAPACITY;
+    if (!admit(s.n) || !hist_.admits(s.n)) return LOAMX_E_CAPACITY;
     order_behind(s.stream);
     enqueue_add(s.pts, s.n, s.origin, s.stream);
     return LOAMX_OK;
@@ -862,6 +781,7 @@ class DenseMap {
     offered_ = drop_range_ = drop_key_ = 0;
     for (uint64_t& c : carve_ctr_) c = 0;
     seq_ = 0;
+    hist_.clear();
   }
 
   // the features of the handle as the file's flags
@@ -900,6 +820,7 @@ class DenseMap {
   // include/loamx.h, loamx_densemap_merge
   int merge(DenseMap& src) {
     LX_REQUIRE(&src != this, "a dense map cannot be merged into itself");
+    LX_REQUIRE(!history_, "the destination keeps a sweep log (loamx_densemap_enable_history): a merged map has no sweeps behind it to rebuild from");
     LX_REQUIRE(src.cfg.device == cfg.device, "the two dense maps live on different devices");
     LX_REQUIRE(memcmp(&src.cfg.leaf, &cfg.leaf, sizeof(float)) == 0, "the two dense maps differ in their leaf");
     LX_REQUIRE(src.flags() == flags(), "the two dense maps do not have the same features enabled (carving, moments)");
@@ -916,6 +837,7 @@ class DenseMap {
   // include/loamx.h, loamx_densemap_merge_file, and with `loading` loamx_densemap_load.  The file is validated on the host before the
   // device is touched; every refusal comes before the first change of the handle
   int merge_file(const char* path, bool loading) {
+    LX_REQUIRE(!history_, "the dense map keeps a sweep log (loamx_densemap_enable_history): a map from a file has no sweeps behind it to rebuild from");
     DmFile F;
     const std::string e = dmf_read(path, true, F);
     LX_REQUIRE(e.empty(), std::string(path) + ": " + e);
@@ -1002,6 +924,88 @@ class DenseMap {
     return LOAMX_OK;
   }
 
+  // include/loamx.h, loamx_densemap_enable_history: allowed while nothing has been offered; the handle is unchanged when refused
+  void enable_history(const loamx_densemap_history_config& c) {
+    read_counters();
+    LX_REQUIRE(occ_.occ == 0 && offered_ == 0, "history can only be enabled on an empty map (a fresh handle, or right after reset)");
+    DmHistory h;
+    LX_REQUIRE(h.configure(c.max_bytes, c.initial_points), "initial_points must be >= 1, and max_bytes 0 or at least one point (16 bytes)");
+    float4* nb = nullptr;
+    LX_HIP(hipMalloc((void**)&nb, DMH_POINT_BYTES * h.capacity));
+    (void)hipFree(log_);   // (enabled before: the log is empty and every add was waited for)
+    log_ = nb;
+    hist_ = h;
+    history_ = true;
+  }
+  bool history() const { return history_; }
+  void history_size(uint64_t* calls, uint64_t* points) const { *calls = hist_.calls.size(); *points = hist_.points; }
+
+  // the logged bytes of one call and its origin
+  int history_download(uint64_t call, loamx_cloud* out, float origin[3]) {
+    LX_REQUIRE(history_, "history is not enabled (loamx_densemap_enable_history)");
+    LX_REQUIRE(call < hist_.calls.size(), "call is beyond the log");
+    check_cloud(out, false);
+    const DmHistoryCall c = hist_.calls[call];
+    if (c.count > out->count) { out->count = c.count; return LOAMX_E_CAPACITY; }
+    LX_HIP(hipSetDevice(cfg.device));
+    wait_adds();
+    h_stage_.reserve(c.count);   // (free: the adds were waited for)
+    store_to_pinned_u32((uint32_t*)h_stage_.p, (const uint32_t*)(log_ + c.first), 4 * (size_t)c.count, own_);
+    LX_HIP(hipStreamSynchronize(own_));
+    for (int a = 0; a < 3; a++) origin[a] = c.origin[a];
+    return unpack_cloud(h_stage_.p, c.count, out);
+  }
+
+  // include/loamx.h, loamx_densemap_rebuild.  Everything is built beside the handle (table, counter words) and swapped in at the end:
+  // a refusal or a failure on the way leaves the handle as it was
+  int rebuild(const double* corrections, uint64_t n_calls) {
+    LX_REQUIRE(history_, "history is not enabled (loamx_densemap_enable_history)");
+    LX_REQUIRE(n_calls == hist_.calls.size(), "n_calls differs from the number of logged calls (loamx_densemap_history_size)");
+    LX_REQUIRE((hist_.points + 255) / 256 < (1ull << 31), "the log holds more points than one launch covers");
+    h_calls_.reserve(n_calls + 1);
+    for (uint64_t k = 0; k < n_calls; k++)
+      LX_REQUIRE(dm_replay_call(hist_.calls[k], corrections ? corrections + 12 * k : nullptr, h_calls_.p[k]),
+                 "corrections: the correction of call " + std::to_string(k) + " has an entry that is not finite");
+    read_counters();   // (waits for the adds; the occupancy is exact)
+    const uint64_t before = occ_.occ;
+    const bool aux = tab_.aux != nullptr, mom = tab_.mom != nullptr;
+    DevBuf<unsigned long long> nctr;
+    nctr.reserve(DM_CTR_WORDS + 1);
+    h_rb_.reserve(2 * (DM_CTR_WORDS + 1));
+    d_calls_.reserve(n_calls + 1);
+    if (n_calls) LX_HIP(hipMemcpyAsync(d_calls_.p, h_calls_.p, sizeof(DmReplayCall) * n_calls, hipMemcpyHostToDevice, own_));
+    const unsigned long long* w = (const unsigned long long*)h_rb_.p;
+    DmTable nt;
+    for (uint64_t slots = dm_rebuild_first_slots(cfg.initial_slots, before);; slots *= 2) {
+      LX_REQUIRE(slots <= DM_MAX_SLOTS, "dense map: the rebuilt map has more voxels than the table can index");
+      DmTable().swap(nt);   // (a failed attempt's table: the host waited for it)
+      nt.alloc(slots, aux, mom);
+      nt.clear(own_);
+      LX_HIP(hipMemsetAsync(nctr.p, 0, sizeof(unsigned long long) * (DM_CTR_WORDS + 1), own_));
+      rebuild_stats_[1]++;
+      if (hist_.points) launch_replay(nt, nctr.p);
+      LX_HIP(hipGetLastError());
+      store_to_pinned_u32(h_rb_.p, (const uint32_t*)nctr.p, 2 * (DM_CTR_WORDS + 1), own_);
+      LX_HIP(hipStreamSynchronize(own_));
+      if (!dm_rebuild_attempt_failed(slots, w[0], w[DM_CTR_WORDS], w[3])) break;
+      if (cfg.max_voxels && slots / 2 >= cfg.max_voxels) return LOAMX_E_CAPACITY;   // (more voxels than half the slots)
+    }
+    if (cfg.max_voxels && w[0] > cfg.max_voxels) return LOAMX_E_CAPACITY;
+    replace_table(nt);
+    std::swap(ctr_.p, nctr.p);
+    std::swap(ctr_.cap, nctr.cap);
+    free_graveyard();   // (the host has waited: nothing reads the old table any more)
+    occ_.reset();
+    occ_.exact(w[0]);
+    offered_ = hist_.points;
+    drop_range_ = w[1]; drop_key_ = w[2];
+    for (int k = 0; k < 6; k++) carve_ctr_[k] = w[4 + k];
+    seq_ = aux ? (uint32_t)n_calls : 0u;
+    rebuild_stats_[0]++;
+    return LOAMX_OK;
+  }
+  void rebuild_stats(uint64_t out[4]) const { for (int k = 0; k < 4; k++) out[k] = rebuild_stats_[k]; }
+
   bool combine = true;   // (bench A/B: the in-wave combining of equal keys)
   uint64_t rehashes = 0;
 
@@ -1026,6 +1030,67 @@ class DenseMap {
   std::vector<void*> graveyard_;   // tables replaced by a rehash: freed at the next point where the host waits anyway
   DmOccupancy occ_;   // the bound of the occupancy that growth and admission are decided on (densemap_growth.hpp)
   uint64_t offered_ = 0, drop_range_ = 0, drop_key_ = 0;
+  // the sweep log (densemap_history.hpp): off unless enabled; hist_ then admits everything and log_ stays NULL
+  bool history_ = false;
+  DmHistory hist_;
+  float4* log_ = nullptr;
+  PinBuf<DmReplayCall> h_calls_;
+  DevBuf<DmReplayCall> d_calls_;
+  PinBuf<uint32_t> h_rb_;
+  uint64_t rebuild_stats_[4] = {0, 0, 0, 0};
+
+  // room for n more points in the log: a block of the doubled capacity, the logged points copied over on st, the old block to the
+  // graveyard (earlier work may still read it)
+  void log_reserve(uint64_t n, hipStream_t st) {
+    const uint64_t want = hist_.capacity_for(n);
+    if (want == hist_.capacity) return;
+    float4* nb = nullptr;
+    LX_HIP(hipMalloc((void**)&nb, DMH_POINT_BYTES * want));
+    if (hist_.points) {
+      const hipError_t e = hipMemcpyAsync(nb, log_, DMH_POINT_BYTES * hist_.points, hipMemcpyDeviceToDevice, st);
+      if (e != hipSuccess) { (void)hipFree(nb); LX_HIP(e); }
+    }
+    graveyard_.push_back(log_);
+    log_ = nb;
+    hist_.capacity = want;
+  }
+  // one attempt of a rebuild: the log under the records of d_calls_ into nt with the counter words nctr ([DM_CTR_WORDS]: too small),
+  // enqueued on own_ without a host wait
+  void launch_replay(const DmTable& nt, unsigned long long* nctr) {
+    const uint32_t n_calls = (uint32_t)hist_.calls.size();
+    DmFilter F;
+    F.inv = inv_;
+    F.min2 = cfg.min_range * cfg.min_range;
+    F.max2 = cfg.max_range * cfg.max_range;
+    F.use_max = cfg.max_range > 0.f ? 1 : 0;
+    F.ox = F.oy = F.oz = 0.f;
+    unsigned long long* small = nctr + DM_CTR_WORDS;
+    dm_dispatch2(combine, nt.mom != nullptr, [&](auto C, auto M) {
+      constexpr bool CB = decltype(C)::value, MM = decltype(M)::value;
+      if (!nt.aux) {
+        const uint64_t n = hist_.points;
+        hipLaunchKernelGGL((k_dm_rebuild<CB, false, MM>), dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, own_, log_, 0ull, n, d_calls_.p, 0u,
+                           n_calls, F, nt.keys, nt.vals, nt.mask(), nt.shift(), nctr, nt.aux, nt.mom, small);
+        rebuild_stats_[2]++;
+        return;
+      }
+      DmCarve R;
+      R.max2 = carve_.max_range * carve_.max_range;
+      R.use_max = carve_.max_range > 0.f ? 1 : 0;
+      R.stride = carve_.ray_stride; R.end_margin = carve_.end_margin; R.max_steps = carve_.max_steps;
+      const uint64_t span = 256ull * R.stride;
+      for (uint32_t k = 0; k < n_calls; k++) {
+        const DmHistoryCall& c = hist_.calls[k];
+        R.seq = k + 1u;
+        hipLaunchKernelGGL((k_dm_rebuild<CB, true, MM>), dim3((c.count + 255u) / 256u), dim3(256), 0, own_, log_, c.first,
+                           (unsigned long long)c.count, d_calls_.p, k, k + 1u, F, nt.keys, nt.vals, nt.mask(), nt.shift(), nctr, nt.aux, nt.mom, small);
+        hipLaunchKernelGGL(k_dm_rebuild_carve, dim3((uint32_t)((c.count + span - 1) / span)), dim3(256), 0, own_, log_, d_calls_.p + k, c.count, F,
+                           R, nt.keys, nt.aux, nt.mask(), nt.shift(), nctr, small);
+        rebuild_stats_[2] += 2;
+      }
+    });
+    rebuild_stats_[3] += hist_.points;
+  }
 
   // nt becomes the map's table; the one it replaces goes to the graveyard
   void replace_table(DmTable& nt) {
@@ -1158,6 +1223,7 @@ class DenseMap {
     if (out) memcpy(out, h_hits_.p, sizeof(loamx_ray_hit) * n);
   }
   void enqueue_add(const float4* pts, uint32_t n, const float origin[3], hipStream_t st) {
+    if (history_ && n) log_reserve(n, st);   // (a failed allocation leaves map and log as they were)
     grow_for(n, st);
     if (n) {
       DmFilter F;
@@ -1182,6 +1248,10 @@ class DenseMap {
       }
     }
     LX_HIP(hipGetLastError());
+    if (history_ && n) {   // the whole cloud as offered, behind whatever wrote it
+      LX_HIP(hipMemcpyAsync(log_ + hist_.points, pts, DMH_POINT_BYTES * n, hipMemcpyDeviceToDevice, st));
+      hist_.append(n, origin);
+    }
     offered_ += n;
     if (occ_.enqueued(n)) {   // the occupancy snapshot behind this add
       store_to_pinned_u32(h_snap_.p, (const uint32_t*)ctr_.p, 2, st);
@@ -1574,6 +1644,68 @@ int loamx_densemap_file_info(const char* path, struct loamx_densemap_file_info* 
     for (int k = 0; k < 6; k++) info->carve_stats[k] = F.h.carve_stats[k];
     info->carve.max_range = F.h.carve_max_range;
     info->carve.ray_stride = F.h.ray_stride; info->carve.end_margin = F.h.end_margin; info->carve.max_steps = F.h.max_steps;
+    return LOAMX_OK;
+  });
+}
+
+void loamx_densemap_history_default_config(loamx_densemap_history_config* cfg) {
+  if (!cfg) return;
+  memset(cfg, 0, sizeof(*cfg));
+  cfg->max_bytes = 0;
+  cfg->initial_points = 1ull << 20;
+}
+int loamx_densemap_enable_history(loamx_densemap* h, const loamx_densemap_history_config* cfg) {
+  return guard([&]() {
+    LX_REQUIRE(h, "NULL handle");
+    loamx_densemap_history_config c;
+    if (cfg) c = *cfg; else loamx_densemap_history_default_config(&c);
+    h->d.enable_history(c);
+    return LOAMX_OK;
+  });
+}
+int loamx_densemap_history_size(loamx_densemap* h, uint64_t* calls, uint64_t* points) {
+  return guard([&]() {
+    LX_REQUIRE(h && calls && points, "NULL argument");
+    LX_REQUIRE(h->d.history(), "history is not enabled (loamx_densemap_enable_history)");
+    h->d.history_size(calls, points);
+    return LOAMX_OK;
+  });
+}
+int loamx_densemap_history_download(loamx_densemap* h, uint64_t call, loamx_cloud* out, float origin[3]) {
+  return guard([&]() {
+    LX_REQUIRE(h && out && origin, "NULL argument");
+    return h->d.history_download(call, out, origin);
+  });
+}
+int loamx_densemap_correct(const double correction[12], const float* xyz_in, float* xyz_out, uint64_t n) {
+  return guard([&]() {
+    LX_REQUIRE(correction, "correction is NULL");
+    LX_REQUIRE((xyz_in && xyz_out) || !n, "xyz_in or xyz_out is NULL");
+    DmCorrection c;
+    LX_REQUIRE(dm_correction_from(correction, c), "correction has an entry that is not finite");
+    if (c.identity) {
+      if (n && xyz_out != xyz_in) memmove(xyz_out, xyz_in, sizeof(float) * 3 * n);
+      return LOAMX_OK;
+    }
+    for (uint64_t i = 0; i < n; i++) {
+      float o[3];
+      dm_correct(c.m, xyz_in[3 * i], xyz_in[3 * i + 1], xyz_in[3 * i + 2], o);
+      xyz_out[3 * i] = o[0]; xyz_out[3 * i + 1] = o[1]; xyz_out[3 * i + 2] = o[2];
+    }
+    return LOAMX_OK;
+  });
+}
+int loamx_densemap_rebuild(loamx_densemap* h, const double* corrections, uint64_t n_calls) {
+  return guard([&]() {
+    LX_REQUIRE(h, "h is NULL");
+    LX_HIP(hipSetDevice(h->d.cfg.device));
+    return h->d.rebuild(corrections, n_calls);
+  });
+}
+int loamx_densemap_get_rebuild_stats(loamx_densemap* h, uint64_t stats[4]) {
+  return guard([&]() {
+    LX_REQUIRE(h && stats, "NULL argument");
+    h->d.rebuild_stats(stats);
     return LOAMX_OK;
   });
 }

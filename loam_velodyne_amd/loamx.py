@@ -1202,6 +1202,26 @@ def write_pcd(path: str, points, axes="loam"):
     _check(lib().loamx_write_pcd(os.fsencode(path), C.byref(c), _axes(axes)))
 
 
+class DenseMapHistoryConfig(C.Structure):
+    _fields_ = [("max_bytes", C.c_uint64), ("initial_points", C.c_uint64)]
+
+
+def correct(correction, xyz) -> np.ndarray:
+    """loamx_densemap_correct (host only): the rigid correction (row-major 3x4 or 4x4, float64) applied to (N, 3) points, or to the
+    x, y, z of (N, 4) points (w untouched), in f32 exactly as rebuild() applies it on the device"""
+    m = np.ascontiguousarray(np.asarray(correction, np.float64)[:3, :4])
+    assert m.shape == (3, 4)
+    a = np.array(xyz, np.float32, ndmin=2)
+    assert a.ndim == 2 and a.shape[1] in (3, 4), "xyz must be (N, 3) or (N, 4)"
+    src = np.ascontiguousarray(a[:, :3])
+    dst = np.empty_like(src)
+    _check(lib().loamx_densemap_correct(m.ctypes.data_as(C.c_void_p), src.ctypes.data_as(C.c_void_p), dst.ctypes.data_as(C.c_void_p),
+                                        C.c_uint64(len(src))))
+    out = a.copy()
+    out[:, :3] = dst
+    return out
+
+
 class DenseMap:
     """loamx_densemap_*: a sparse voxel map of the whole run in device memory, fed with registered sweeps where they lie (add_from: a
     LaserMapping's last process; add_from_pipeline: a Pipeline's last step) or with map-frame points from the host (add)."""
@@ -1527,6 +1547,51 @@ class DenseMap:
     def merge_file(self, path: str):
         """loamx_densemap_merge_file: the same with a saved map as the source"""
         _check(lib().loamx_densemap_merge_file(self.h, os.fsencode(path)))
+
+    def enable_history(self, max_bytes=0, initial_points=1 << 20):
+        """the sweep log (include/loamx.h): from now on every add also appends its whole cloud, as offered, to a block in device
+        memory that rebuild() replays.  Only on an empty map (fresh, or right after reset); max_bytes caps the block (an add past it
+        raises E_CAPACITY), initial_points is its first capacity"""
+        c = _cfg(DenseMapHistoryConfig, "loamx_densemap_history_default_config", max_bytes=max_bytes, initial_points=initial_points)
+        _check(lib().loamx_densemap_enable_history(self.h, C.byref(c)))
+
+    def history_size(self):
+        """(logged calls, logged points)"""
+        calls, points = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().loamx_densemap_history_size(self.h, C.byref(calls), C.byref(points)))
+        return int(calls.value), int(points.value)
+
+    def history(self, k: int):
+        """logged call k: ((n, 4) float32, the bytes that were added; (3,) float32, the origin it was added with)"""
+        n = 0
+        origin = np.zeros(3, np.float32)
+        while True:
+            out = np.zeros((max(n, 1), 4), np.float32)
+            c = cloud_of(out)
+            c.count = n
+            rc = lib().loamx_densemap_history_download(self.h, C.c_uint64(k), C.byref(c), origin.ctypes.data_as(C.c_void_p))
+            if rc == E_CAPACITY:
+                n = int(c.count)
+                continue
+            _check(rc)
+            return out[:c.count], origin
+
+    def rebuild(self, corrections=None):
+        """loamx_densemap_rebuild: the map becomes what a fresh handle fed with the logged sweeps would hold, sweep k moved by
+        corrections[k] (row-major 3x4 or 4x4, map <- map, float64; None: every sweep where it was) — on the device, from the log.
+        Blocks until the new map stands; freeze() again afterwards"""
+        if corrections is None:
+            calls, _ = self.history_size()
+            return _check(lib().loamx_densemap_rebuild(self.h, None, C.c_uint64(calls)))
+        a = np.asarray(corrections, np.float64)
+        a = np.ascontiguousarray(a.reshape(-1, *a.shape[-2:])[:, :3, :4] if a.size else a.reshape(0, 3, 4))
+        assert a.ndim == 3 and a.shape[1:] == (3, 4), "corrections must be (n_calls, 3, 4) or (n_calls, 4, 4)"
+        return _check(lib().loamx_densemap_rebuild(self.h, a.ctypes.data_as(C.c_void_p), C.c_uint64(a.shape[0])))
+
+    def rebuild_stats(self) -> dict:
+        s = (C.c_uint64 * 4)()
+        _check(lib().loamx_densemap_get_rebuild_stats(self.h, s))
+        return dict(zip(("rebuilds", "tables_tried", "launches", "points_replayed"), (int(v) for v in s)))
 
     def reset(self):
         _check(lib().loamx_densemap_reset(self.h))
