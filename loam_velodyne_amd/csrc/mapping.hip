@@ -723,6 +723,14 @@ int Mapper::collect_results(const Sweep& sw) {
   LX_HIP(hipGetLastError());
   SweepStats ss;
   reg.download_stats(&ss);
+  if (ss.iterations == 0) {
+    // the sizes of the down-sized clouds reach the statistics through the Gauss-Newton update; a sweep without one (insert(), a sub-map
+    // too small to register against: BasicLaserMapping.cpp:628-629) reported 0 / 0 for clouds it went on to insert — read the offsets
+    uint32_t q[2];
+    reg.download_ds_counts(0, q);
+    ss.corner_q = (int)q[0];
+    ss.surf_q = (int)q[1];
+  }
   last_stats = ss;
   int rc = LOAMX_OK;
   if (last_optimized) {

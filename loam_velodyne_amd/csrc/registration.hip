@@ -1361,6 +1361,16 @@ void Registrar::download_ds(uint32_t sweep, std::vector<float4>& corner_ds, std:
   LX_HIP(hipStreamSynchronize(st_));
 }
 
+void Registrar::download_ds_counts(uint32_t sweep, uint32_t counts[2]) {
+  LX_REQUIRE(sweep < n_sweeps_ && counts, "sweep index out of range");
+  fetch_results();
+  uint32_t off[3];
+  LX_HIP(hipMemcpyAsync(off, ds_off_.p + 2 * sweep, sizeof(off), hipMemcpyDeviceToHost, st_));
+  LX_HIP(hipStreamSynchronize(st_));
+  counts[0] = off[1] - off[0];
+  counts[1] = off[2] - off[1];
+}
+
 void Registrar::get_timing(float ms[4], uint64_t counts[4]) {
   for (int k = 0; k < 4; k++) { ms[k] = 0.f; counts[k] = 0; }
   if (!timing_ || !timed_run_) return;

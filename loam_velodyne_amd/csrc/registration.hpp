@@ -80,6 +80,8 @@ class Registrar {
   void set_submap_device_split(const float4* d_corner, uint32_t nc, hipStream_t corner_stream, const float4* d_surf, uint32_t ns, bool bounds_done = false);
   // down-sampled query clouds of a sweep (device pointers valid until the next run); counts need a sync'd download
   void download_ds(uint32_t sweep, std::vector<float4>& corner_ds, std::vector<float4>& surf_ds);
+  // their sizes alone (corner, surf): what SweepStats::corner_q / surf_q hold once a Gauss-Newton update has run — a run without one leaves them unwritten
+  void download_ds_counts(uint32_t sweep, uint32_t counts[2]);
   // registered (final-pose) DS clouds, for map insertion: device array + offsets
   const float4* d_ds_points() const { return ds_pts_.p; }
   const uint32_t* d_ds_offsets() const { return ds_off_.p; }
