@@ -1128,6 +1128,86 @@ int loamx_densemap_rebuild(loamx_densemap* h, const double* corrections /* 12 * 
                            uint64_t n_calls);
 int loamx_densemap_get_rebuild_stats(loamx_densemap* h, uint64_t stats[4]);
 
+/* Navigation grid (optional: a handle that never calls loamx_densemap_grid runs the kernels it ran, allocates what it allocated and
+ * exports the same bytes).  "Where can I drive?": a window of the map projected along the up axis to a 2-D grid of ground height,
+ * obstacle count, overhead clearance, class and squared distance to the nearest obstacle, computed on the device from the table
+ * where it lies; only nx * nz records of 24 bytes come back.
+ *
+ * Up is +y of the LOAM frame (z_s of the sensor axes).  A cell is a square of k = cell_leaves voxels on a side in x and z: voxel
+ * (ix, iy, iz) lies in cell (cx, cz) = (floor(ix / k), floor(iz / k)) — floor, not truncation: ix = -1, k = 3 gives cx = -1.  The
+ * window is the nx * nz cells cx in [x0, x0 + nx), cz in [z0, z0 + nz); cell (cx, cz) is record (cz - z0) * nx + (cx - x0).
+ * A voxel qualifies when it lies in the window, holds n >= min_points points, has y_min <= iy <= y_max and, with a rule, is not
+ * dynamic under it (the rule of the carving section, on the voxel's n and miss: loamx_densemap_rule_is_dynamic).
+ * Per cell, over its qualifying voxels:
+ *   ground    = the smallest iy (INT32_MAX: the cell has none).  The ground is the LOWEST voxel, not a fitted surface: one
+ *               qualifying voxel under the road lowers it (min_points, y_min and the rule are the guards against that).
+ *   elevation = (float)(((double)ground + (double)SSy / ((double)SSn * 2^20)) * (double)leaf), SSn and SSy the 64-bit sums of n and
+ *               Sy over the qualifying voxels with iy == ground: the export expression of loamx_densemap_download on the pooled
+ *               ground layer.  0.0f without a ground.
+ *   obstacles = the number of qualifying voxels with band_lo <= iy - ground <= band_hi (the leaves above the ground that the
+ *               vehicle's body occupies).
+ *   overhead  = the smallest iy of a qualifying voxel with iy - ground > band_hi (INT32_MAX: none): what the vehicle passes under.
+ *   cls       = UNKNOWN when the cell has no qualifying voxel;  otherwise OBSTACLE when obstacles >= min_obstacle_voxels;  otherwise
+ *               STEP when some 4-neighbour (cx +- 1, cz), (cx, cz +- 1) inside the window is not UNKNOWN and
+ *               |ground - ground_nb| > max_step;  otherwise FREE.  Both sides of a step are marked.  A step beyond the window's edge
+ *               is not seen: the cells of the outermost ring are compared with their neighbours inside the window only.
+ *   clear2    = with R = clear_max and D = the smallest dx*dx + dz*dz (in cells) to a cell of the window with cls >= 2:  D when
+ *               D <= R*R, else (R+1)*(R+1).  An OBSTACLE or STEP cell has 0.  Cells outside the window are not obstacles.  With
+ *               R = 0 this is 0 on obstacles and 1 elsewhere, with no special case.
+ * Every field is an integer, or one f32 rounding of an expression over integers: the grid depends on neither the thread schedule,
+ * the order of the points, the split into add calls (without a rule: the miss words depend on the call history, as documented
+ * above) nor the table's size or the number of rehashes.
+ * Ordering: the call waits for the adds as download does, runs four kernels on the map's own stream (ground: atomic minimum per
+ * cell; fill: the sums, counts and overhead against the final ground; classify; clear) behind one memset, and blocks until the
+ * records are back through pinned memory.  Integer atomics only.  It changes nothing in the map.  The device planes live in the
+ * handle, grow to the largest window asked for and are freed on destroy.  An empty map is valid: every cell is UNKNOWN.
+ * LOAMX_E_INVALID, with a message that names the argument, nothing written to out: NULL h or out;  a configuration that fails
+ * loamx_densemap_grid_check;  a rule with den == 0;  a rule on a handle without carving.
+ *
+ * loamx_densemap_grid_check (host only): LOAMX_OK, or LOAMX_E_INVALID with a message that names the first field out of its bounds.
+ * loamx_densemap_grid_window (host only): x0, nx, z0, nz of the window about a centre with a half extent, both in metres, for
+ * cfg->cell_leaves; in double, e = (double)leaf * k, lo = floor(((double)c - (double)h) / e), hi = floor(((double)c + (double)h) / e),
+ * x0 = lo, nx = hi - lo + 1 (z alike).  LOAMX_E_INVALID, cfg unchanged, when an argument is not finite, leaf <= 0, half_extent < 0
+ * or the result breaks a bound of loamx_densemap_grid_check.
+ * loamx_grid_occupancy (host only): the classes as nav_msgs/OccupancyGrid values, -1 UNKNOWN, 0 FREE, 100 OBSTACLE or STEP
+ * (LOAMX_E_INVALID, nothing written, for a cls above 3).
+ * loamx_write_grid_pgm (host only): stem.pgm and stem.yaml as ROS map_server reads them, in the sensor axes (x_s = LOAM z,
+ * y_s = LOAM x).  stem.pgm is binary P5, maxval 255, width nz, height nx; file row r, column u is cell (cx, cz) =
+ * (x0 + nx - 1 - r, z0 + u); 0 for OBSTACLE or STEP, 254 for FREE, 205 for UNKNOWN.  stem.yaml holds image (the file name of
+ * stem.pgm without its directory), resolution = (double)leaf * k, origin: [z0 * resolution, x0 * resolution, 0], negate: 0,
+ * occupied_thresh: 0.65, free_thresh: 0.196; numbers are printed with %.9g. */
+#define LOAMX_GRID_UNKNOWN 0
+#define LOAMX_GRID_FREE 1
+#define LOAMX_GRID_OBSTACLE 2
+#define LOAMX_GRID_STEP 3
+typedef struct loamx_densemap_grid_config {
+  uint32_t cell_leaves;          /* k, 1..64 (default 2) */
+  int32_t  x0, z0;               /* first cell of the window, |x0|, |z0| <= 2^21 (default 0, 0) */
+  uint32_t nx, nz;               /* 1..8192 each, nx * nz <= 2^26 (default 256, 256) */
+  uint32_t min_points;           /* a voxel qualifies when n >= min_points, >= 1 (default 2) */
+  int32_t  y_min, y_max;         /* and y_min <= iy <= y_max (default -2^20, 2^20): one storey, or a cut under the road */
+  uint32_t band_lo, band_hi;     /* leaves above the ground that the vehicle's body occupies, 1 <= band_lo <= band_hi (default 3, 20) */
+  uint32_t min_obstacle_voxels;  /* >= 1 (default 1) */
+  uint32_t max_step;             /* leaves (default 2) */
+  uint32_t clear_max;            /* R, cells, 0..64 (default 10) */
+} loamx_densemap_grid_config;
+typedef struct loamx_grid_cell {   /* 24 bytes */
+  int32_t  ground;      /* iy of the lowest qualifying voxel of the cell; INT32_MAX: none */
+  float    elevation;   /* metres; 0.0f when ground is INT32_MAX */
+  uint32_t obstacles;   /* qualifying voxels with band_lo <= iy - ground <= band_hi */
+  int32_t  overhead;    /* lowest iy of a qualifying voxel with iy - ground > band_hi; INT32_MAX: none */
+  uint32_t clear2;      /* squared distance in cells to the nearest OBSTACLE or STEP cell of the window, capped: see above */
+  uint32_t cls;         /* 0 UNKNOWN, 1 FREE, 2 OBSTACLE, 3 STEP */
+} loamx_grid_cell;
+void loamx_densemap_grid_default_config(loamx_densemap_grid_config* cfg);   /* host only */
+int loamx_densemap_grid_check(const loamx_densemap_grid_config* cfg);        /* host only */
+int loamx_densemap_grid_window(float leaf, float centre_x, float centre_z, float half_extent, loamx_densemap_grid_config* cfg);   /* host only */
+int loamx_densemap_grid(loamx_densemap* h, const loamx_densemap_grid_config* cfg /* NULL: the defaults */,
+                        const loamx_densemap_static_rule* rule /* NULL: every voxel; else needs carving */,
+                        loamx_grid_cell* out /* nx * nz */);
+int loamx_grid_occupancy(const loamx_grid_cell* cells, uint64_t n, int8_t* out);   /* host only */
+int loamx_write_grid_pgm(const char* stem, const loamx_grid_cell* cells, const loamx_densemap_grid_config* cfg, float leaf);   /* host only */
+
 /* ------------------------------------------------------------------------------------------------------------
  * Place recognition (not in the reference): a database of rotation-invariant sweep descriptors in device memory (Scan Context: a
  * ring x sector polar grid of maximum heights around the sensor) and an exhaustive search for the earlier entries that look like a

@@ -19,6 +19,9 @@
 // History (loamx_densemap_enable_history, densemap_history.hpp): every add also appends its cloud to a log in HBM, and
 // loamx_densemap_rebuild replays that log, each call under a rigid correction, into a fresh table with the insert's and the carve
 // kernel's own bodies (dm_insert_body.inc, dm_carve_body.inc); the table that stands is replaced only when the replay has succeeded.
+//
+// Navigation grid (loamx_densemap_grid, densemap_grid.hip): a window of the table projected to 2-D cells by kernels of their own that
+// only read it; the handle owns their planes.
 #include "densemap.hpp"
 #include "densemap_file.hpp"
 #include "densemap_history.hpp"
@@ -258,11 +261,6 @@ __global__ __launch_bounds__(256) void k_dm_rebuild_carve(const float4* __restri
 #define DM_CARVE_POINT(j) dm_replay_point(log, c.first + (j), c)
 #include "dm_carve_body.inc"
 #undef DM_CARVE_POINT
-}
-
-// include/loamx.h, loamx_densemap_static_rule: the voxel with n points and `miss` crossings is dynamic
-__host__ __device__ inline bool dm_dynamic(const loamx_densemap_static_rule& r, unsigned long long n, uint32_t miss) {
-  return miss >= r.min_misses && (unsigned long long)miss * r.den > n * r.num;
 }
 
 // what a ray cast needs (include/loamx.h, loamx_densemap_raycast): the origin, the checked configuration and, with use_rule, the rule
@@ -1006,6 +1004,14 @@ class DenseMap {
   }
   void rebuild_stats(uint64_t out[4]) const { for (int k = 0; k < 4; k++) out[k] = rebuild_stats_[k]; }
 
+  // include/loamx.h, loamx_densemap_grid: a checked configuration, a checked rule or none; the table is only read
+  void grid(const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, loamx_grid_cell* out) {
+    LX_HIP(hipSetDevice(cfg.device));
+    wait_adds();
+    const loamx_grid_cell* cells = grid_.run(tab_, c, rule, (double)cfg.leaf, own_);
+    memcpy(out, cells, sizeof(loamx_grid_cell) * (size_t)c.nx * c.nz);
+  }
+
   bool combine = true;   // (bench A/B: the in-wave combining of equal keys)
   uint64_t rehashes = 0;
 
@@ -1038,6 +1044,7 @@ class DenseMap {
   DevBuf<DmReplayCall> d_calls_;
   PinBuf<uint32_t> h_rb_;
   uint64_t rebuild_stats_[4] = {0, 0, 0, 0};
+  DmGrid grid_;   // the navigation grid's planes (densemap_grid.hip): allocated by the first grid
 
   // room for n more points in the log: a block of the doubled capacity, the logged points copied over on st, the old block to the
   // graveyard (earlier work may still read it)
@@ -1764,6 +1771,23 @@ int loamx_densemap_raycast_from_pipeline(loamx_densemap* h, loamx_pipeline* p, u
     DenseSource s;
     loamx_pipeline_dense_source(p, slot, s);
     return h->d.raycast_device(s, c, rule, out, capacity, counts);
+  });
+}
+
+int loamx_densemap_grid(loamx_densemap* h, const loamx_densemap_grid_config* cfg, const loamx_densemap_static_rule* rule,
+                        loamx_grid_cell* out) {
+  return guard([&]() {
+    LX_REQUIRE(h, "h is NULL");
+    LX_REQUIRE(out, "out is NULL");
+    loamx_densemap_grid_config c;
+    if (cfg) c = *cfg; else loamx_densemap_grid_default_config(&c);
+    dm_grid_check(c);
+    if (rule) {
+      LX_REQUIRE(rule->den != 0u, "the rule's den must not be 0");
+      LX_REQUIRE(h->d.carving(), "a rule needs carving, which is not enabled");
+    }
+    h->d.grid(c, rule, out);
+    return LOAMX_OK;
   });
 }
 

@@ -106,6 +106,11 @@ __device__ inline unsigned long long dm_hash(unsigned long long key, uint32_t sh
   return (key * 0x9E3779B97F4A7C15ull) >> shift;
 }
 
+// include/loamx.h, loamx_densemap_static_rule: the voxel with n points and `miss` crossings is dynamic
+__host__ __device__ inline bool dm_dynamic(const loamx_densemap_static_rule& r, unsigned long long n, uint32_t miss) {
+  return miss >= r.min_misses && (unsigned long long)miss * r.den > n * r.num;
+}
+
 // Frozen surfel snapshot (include/loamx.h, loamx_densemap_freeze / loamx_densemap_align_*; densemap_align.hip): an open-addressing
 // table of its own, one 32-byte entry per slot — the voxel's key and the six f32 of its surfel record — so that a probe that hits
 // reads one 32-byte sector.  Built once per freeze, read-only afterwards; the live map never touches it.
@@ -153,6 +158,27 @@ class DmFrozen {
   DevBuf<float4> d_poses_;
   uint64_t stats_[3] = {0, 0, 0};
 };
+
+// Navigation grid (include/loamx.h, loamx_densemap_grid; densemap_grid.hip): the accumulator planes of a window and its records on the
+// device, and the pinned block the records come back through.  Grow to the largest window asked for; the live map is only read.
+class DmGrid {
+ public:
+  DmGrid() = default;
+  DmGrid(const DmGrid&) = delete;
+  DmGrid& operator=(const DmGrid&) = delete;
+  // the grid of a checked configuration over the table T (every add waited for) on st: one memset, the four kernels, one readback;
+  // blocks until the c.nx * c.nz records are in pinned memory and returns them, valid until the next run
+  const loamx_grid_cell* run(const DmTable& T, const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, double leaf,
+                             hipStream_t st);
+
+ private:
+  DevBuf<uint32_t> planes_;   // DM_GRID_PLANE_WORDS 32-bit words per cell, plane after plane (densemap_grid.hip)
+  DevBuf<loamx_grid_cell> cells_;
+  PinBuf<uint32_t> h_cells_;
+};
+
+// include/loamx.h, loamx_densemap_grid_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
+void dm_grid_check(const loamx_densemap_grid_config& c);
 
 }  // namespace loamx
 

@@ -1194,6 +1194,79 @@ def range_image_ends(pose, elevations_deg, n_azimuth: int, max_range: float) -> 
     return out
 
 
+class GridConfig(C.Structure):
+    """loamx_densemap_grid_config: the window (cell_leaves, x0, z0, nx, nz) and the rules of the navigation grid.  GridConfig() holds
+    the defaults (2; 0, 0; 256 x 256; min_points 2; y in [-2^20, 2^20]; band 3..20; 1 obstacle voxel; max_step 2; clear_max 10);
+    keyword arguments replace them."""
+    _fields_ = [("cell_leaves", C.c_uint32), ("x0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_uint32), ("nz", C.c_uint32),
+                ("min_points", C.c_uint32), ("y_min", C.c_int32), ("y_max", C.c_int32), ("band_lo", C.c_uint32), ("band_hi", C.c_uint32),
+                ("min_obstacle_voxels", C.c_uint32), ("max_step", C.c_uint32), ("clear_max", C.c_uint32)]
+
+    def __init__(self, **fields):
+        super().__init__()
+        lib().loamx_densemap_grid_default_config(C.byref(self))
+        self.update(**fields)
+
+    def update(self, **fields):
+        for k, v in fields.items():
+            assert hasattr(self, k), k
+            setattr(self, k, v)
+        return self
+
+    def copy(self, **fields):
+        c = GridConfig()
+        C.memmove(C.byref(c), C.byref(self), C.sizeof(GridConfig))
+        return c.update(**fields)
+
+    def check(self):
+        """loamx_densemap_grid_check (host only): LoamxError E_INVALID names the first field out of its bounds"""
+        _check(lib().loamx_densemap_grid_check(C.byref(self)))
+        return self
+
+
+class GridCell(C.Structure):
+    """loamx_grid_cell, 24 bytes: ground (iy of the lowest qualifying voxel; GRID_NONE: none), elevation (metres), obstacles (voxels in
+    the body band), overhead (lowest iy above the band; GRID_NONE: none), clear2 (capped squared distance in cells to the nearest
+    OBSTACLE or STEP cell) and cls (GRID_UNKNOWN, GRID_FREE, GRID_OBSTACLE, GRID_STEP)"""
+    _fields_ = [("ground", C.c_int32), ("elevation", C.c_float), ("obstacles", C.c_uint32), ("overhead", C.c_int32),
+                ("clear2", C.c_uint32), ("cls", C.c_uint32)]
+
+
+GRID_UNKNOWN, GRID_FREE, GRID_OBSTACLE, GRID_STEP = range(4)                      # loamx_grid_cell.cls
+GRID_NONE = 0x7fffffff                                                            # ground / overhead of a cell without one
+GRID_CELL = np.dtype([(n, np.dtype(t)) for n, t in GridCell._fields_])            # the records as a structured numpy array
+
+
+def grid_window(leaf, centre_x, centre_z, half_extent, cell_leaves=2) -> GridConfig:
+    """loamx_densemap_grid_window (host only): a GridConfig (defaults otherwise) whose window covers centre +- half_extent metres in
+    x and z (LOAM frame) with cells of cell_leaves voxels.  LoamxError E_INVALID when the window breaks a bound of the check."""
+    c = GridConfig(cell_leaves=cell_leaves)
+    _check(lib().loamx_densemap_grid_window(C.c_float(leaf), C.c_float(centre_x), C.c_float(centre_z), C.c_float(half_extent), C.byref(c)))
+    return c
+
+
+def _grid_cells(cells) -> np.ndarray:
+    a = np.ascontiguousarray(cells)
+    assert a.dtype == GRID_CELL, "cells must be an array of GRID_CELL records"
+    return a
+
+
+def grid_occupancy(cells) -> np.ndarray:
+    """loamx_grid_occupancy (host only): int8 of the cells' shape, -1 UNKNOWN, 0 FREE, 100 OBSTACLE or STEP (nav_msgs/OccupancyGrid)"""
+    a = _grid_cells(cells)
+    out = np.zeros(a.shape, np.int8)
+    _check(lib().loamx_grid_occupancy(a.ctypes.data_as(C.c_void_p), C.c_uint64(a.size), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def write_grid_pgm(stem: str, cells, cfg: GridConfig, leaf: float):
+    """loamx_write_grid_pgm (host only): stem.pgm and stem.yaml as ROS map_server reads them, in the sensor axes (image columns run
+    along LOAM z = x_s, image rows against LOAM x = y_s).  cells: the (nz, nx) array of DenseMap.grid(cfg)."""
+    a = _grid_cells(cells)
+    assert a.size == cfg.nx * cfg.nz, "cells does not have the configuration's nx * nz records"
+    _check(lib().loamx_write_grid_pgm(os.fsencode(stem), a.ctypes.data_as(C.c_void_p), C.byref(cfg), C.c_float(leaf)))
+
+
 def write_pcd(path: str, points, axes="loam"):
     """loamx_write_pcd: an (N, 4) / (N, 8) float32 cloud as a binary PCD v0.7 file (x y z intensity); axes="sensor" writes the sensor
     axes ingestion started from (x_s = z, y_s = x, z_s = y).  Host only."""
@@ -1528,6 +1601,16 @@ class DenseMap:
         """loamx_densemap_raycast_from_pipeline: the same for the slot-th stream registered in pipeline's last step"""
         return self._raycast_device(lib().loamx_densemap_raycast_from_pipeline, (pipeline.h, C.c_uint32(slot)), capacity, max_steps,
                                     skip_steps, min_points, static, records)
+
+    def grid(self, cfg=None, static=None, **fields):
+        """loamx_densemap_grid: the navigation grid of a window of the map, computed on the device — an (nz, nx) array of GRID_CELL
+        records, [cz - z0, cx - x0].  cfg: a GridConfig (None: the defaults; grid_window() makes one around a position); fields
+        replace members of a copy of it.  static (a StaticRule; needs carving): without the voxels the rule calls dynamic."""
+        c = (GridConfig() if cfg is None else cfg).copy(**fields).check()
+        out = np.zeros((c.nz, c.nx), GRID_CELL)
+        _check(lib().loamx_densemap_grid(self.h, C.byref(c), C.byref(static) if static is not None else None,
+                                         out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def save(self, path: str):
         """loamx_densemap_save: every word of the map as an 'LXDM' file (include/loamx.h), written beside path and renamed.  The
