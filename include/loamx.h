@@ -55,6 +55,7 @@ extern "C" {
 #define LOAMX_E_HIP (-3)
 #define LOAMX_E_NOGPU (-4)
 #define LOAMX_E_UNSUPPORTED (-5) /* an optional dependency was left out of this build (the multi-GPU exchanges without RCCL) */
+#define LOAMX_E_INTERNAL (-6)    /* a bound that the library's own invariants exclude was reached (the route's round cap) */
 
 /* caller-owned cloud description (input or output) */
 typedef struct loamx_cloud {
@@ -1207,6 +1208,90 @@ int loamx_densemap_grid(loamx_densemap* h, const loamx_densemap_grid_config* cfg
                         loamx_grid_cell* out /* nx * nz */);
 int loamx_grid_occupancy(const loamx_grid_cell* cells, uint64_t n, int8_t* out);   /* host only */
 int loamx_write_grid_pgm(const char* stem, const loamx_grid_cell* cells, const loamx_densemap_grid_config* cfg, float leaf);   /* host only */
+
+/* Routing on the navigation grid (optional: a handle that never routes runs the kernels it ran and allocates what it allocated;
+ * loamx_densemap_grid returns the bytes it returned).  "How do I get there?": the cost-to-go of every cell of a window towards a set
+ * of goal cells, the next step per cell, and routes traced from many starts, computed on the device from the grid where it lies;
+ * only what is asked for comes back.  The input is integer (cls, clear2) and so is the answer: shortest-path costs over integer
+ * move costs are a unique fixed point that depends on neither the thread schedule nor the number of relaxation rounds.
+ *
+ * Cell coordinates are window-relative: rx = cx - x0 in [0, nx), rz = cz - z0 in [0, nz), record rz * nx + rx.
+ * Weight of a cell, w(c), 0 = blocked, otherwise 1..32: 0 unless clear2 >= min_clear2 and either cls == FREE, or cls == UNKNOWN
+ * with unknown_weight > 0; otherwise w = 1 + p + u, p = floor(soft_weight * (soft_clear2 - clear2) / soft_clear2) when
+ * clear2 < soft_clear2, else 0; u = unknown_weight for an UNKNOWN cell, else 0.  loamx_grid_route_weight (host only) is this
+ * expression: 0..32, or a negative error for NULL or a configuration that fails its check.
+ * Moves: direction d = 0..7 is (dx, dz) = (1,0), (1,1), (0,1), (-1,1), (-1,0), (-1,-1), (0,-1), (1,-1); even d is axial, odd d is
+ * diagonal and exists only with connectivity == 8.  A move a -> b is legal when b lies in the window, w(a) > 0 and w(b) > 0 and,
+ * for a diagonal, both cells (ax + dx, az) and (ax, az + dz) have w > 0 (no corner cutting).  Its cost is s * (w(a) + w(b)),
+ * s = 5 axial, 7 diagonal: 10 / 14 on unit weights, and symmetric, so the cost to the goal is also the cost from it.
+ * Goals: n_goals pairs (rx, rz), 1 <= n_goals <= 4096.  A pair outside the window or on a blocked cell is ignored and not counted
+ * in stats[2]; a cell named twice counts twice.  With no goal left every cell is unreachable and the call is still LOAMX_OK.
+ * Field: one loamx_route_cell per cell.  cost = the smallest sum of move costs to any used goal, LOAMX_ROUTE_UNREACHABLE for a
+ * blocked cell or one with no path.  next = LOAMX_ROUTE_GOAL when cost == 0, LOAMX_ROUTE_NONE when unreachable, otherwise the
+ * smallest d whose move c -> nb is legal and has cost[nb] + move == cost[c]; it is derived from the final costs in a pass of its
+ * own and does not depend on the schedule either.
+ * Routing needs nx * nz <= 2^22: a path visits each cell at most once and a move costs at most 7 * 64 = 448, so
+ * cost < 2^22 * 448 < 2^31.  A larger window is LOAMX_E_INVALID.
+ * stats[6]: traversable cells (w > 0);  reachable cells;  goals used;  the largest finite cost (0: none);  relaxation rounds
+ * launched;  tile runs that did work.  The first four are part of the definition and exact, the last two describe the schedule.
+ *
+ * loamx_densemap_route: runs the grid of grid_cfg / rule exactly as loamx_densemap_grid does, then routes on it, in one call and
+ * with nothing stale; the 24-byte records only come back when out_cells is given.
+ * loamx_densemap_route_cells: the same on a grid of the caller's (edited, painted with keep-out zones, or hand-made), uploaded to
+ * a buffer of the route's own; nothing that loamx_densemap_grid keeps is replaced or disturbed.
+ * loamx_densemap_route_trace: routes over the field of this handle's last successful route call, traced on the device; only the
+ * routes come back.  A route is the list of cells from the start, following next, up to and including the goal cell.  lengths[i]
+ * is the full number of cells of route i, 0 when the start is outside the window or unreachable.  Of a route longer than capacity
+ * only the first capacity pairs are written; lengths[i] still holds the full length, so the caller can ask again.  Start i's
+ * slice of out_xz begins at 2 * capacity * i; the words beyond its route are left untouched.
+ * loamx_grid_route_trace (host only): the same walk over a field the caller holds, the same bytes.  It stops with
+ * LOAMX_E_INVALID, nothing written, on a field that is not one of ours: a next above 9, a step that leaves the window, a step to
+ * a cell whose cost is not strictly smaller (which also bounds the walk by nx * nz steps).
+ * loamx_grid_route_points (host only): metres for a route, LOAM frame: x = (float)(((double)x0 + rx + 0.5) * (double)leaf * k),
+ * z alike, y = the cell's elevation (0 for an UNKNOWN cell or when cells is NULL).
+ * loamx_densemap_grid_cell_of (host only): the cell of a position: in double, rx = floor((double)x / ((double)leaf * k)) - x0,
+ * z alike; *inside = 0, rx and rz untouched, when the cell is outside the window.
+ * Ordering: the route calls wait for the adds as loamx_densemap_grid does, run on the map's own stream, change nothing in the map
+ * and block until what was asked for is back through pinned memory.  Integer atomics only.  The planes live in the handle, are
+ * allocated by the first route call, grow to the largest window asked for and are freed on destroy.
+ * LOAMX_E_INVALID, with a message that names the argument, nothing written to any output: NULL h, goals_xz, starts_xz, lengths, or
+ * out_xz with capacity > 0;  n_goals or n_starts outside 1..4096;  a configuration that fails loamx_grid_route_check;  everything
+ * loamx_densemap_grid refuses (but for its out);  nx * nz > 2^22;  cells NULL in route_cells;  a cls above 3 in uploaded cells;
+ * route_trace on a handle that has no field yet.  LOAMX_E_INTERNAL: the relaxation did not settle within nx * nz + 2 rounds, which
+ * the kernel's invariant excludes. */
+#define LOAMX_ROUTE_UNREACHABLE 0xffffffffu
+#define LOAMX_ROUTE_GOAL 8u
+#define LOAMX_ROUTE_NONE 9u
+typedef struct loamx_grid_route_config {
+  uint32_t connectivity;     /* neighbours used for moves, 4 or 8 (default 8) */
+  uint32_t min_clear2;       /* smallest clear2 of a traversable cell, >= 1: OBSTACLE and STEP cells (clear2 0) never qualify (default 1) */
+  uint32_t soft_clear2;      /* clear2 below which a cell pays a penalty, 0..4225 (default 0) */
+  uint32_t soft_weight;      /* largest penalty, 0..15 (default 0) */
+  uint32_t unknown_weight;   /* 0: UNKNOWN cells are blocked; 1..16: they can be driven at that extra weight (default 0) */
+} loamx_grid_route_config;
+typedef struct loamx_route_cell {   /* 8 bytes */
+  uint32_t cost;   /* LOAMX_ROUTE_UNREACHABLE: blocked, or no path */
+  uint32_t next;   /* 0..7: the direction of the next step; LOAMX_ROUTE_GOAL; LOAMX_ROUTE_NONE */
+} loamx_route_cell;
+void loamx_grid_route_default_config(loamx_grid_route_config* cfg);   /* host only */
+int loamx_grid_route_check(const loamx_grid_route_config* cfg);        /* host only */
+int loamx_grid_route_weight(const loamx_grid_cell* cell, const loamx_grid_route_config* cfg);   /* host only */
+int loamx_densemap_route(loamx_densemap* h, const loamx_densemap_grid_config* grid_cfg /* NULL: the defaults */,
+                         const loamx_densemap_static_rule* rule /* NULL: every voxel; else needs carving */,
+                         const loamx_grid_route_config* cfg /* NULL: the defaults */, const uint32_t* goals_xz, uint32_t n_goals,
+                         loamx_grid_cell* out_cells /* nx * nz; NULL: not wanted */, loamx_route_cell* out_field /* nx * nz; NULL: not wanted */,
+                         uint64_t stats[6] /* NULL: not wanted */);
+int loamx_densemap_route_cells(loamx_densemap* h, const loamx_grid_cell* cells, uint32_t nx, uint32_t nz,
+                               const loamx_grid_route_config* cfg /* NULL: the defaults */, const uint32_t* goals_xz, uint32_t n_goals,
+                               loamx_route_cell* out_field /* NULL: not wanted */, uint64_t stats[6] /* NULL: not wanted */);
+int loamx_densemap_route_trace(loamx_densemap* h, const uint32_t* starts_xz, uint32_t n_starts /* 1..4096 */,
+                               uint32_t* out_xz /* n_starts * capacity pairs */, uint32_t capacity, uint32_t* lengths /* n_starts */);
+int loamx_grid_route_trace(const loamx_route_cell* field, uint32_t nx, uint32_t nz, uint32_t start_x, uint32_t start_z,
+                           uint32_t* out_xz /* capacity pairs */, uint32_t capacity, uint32_t* length);   /* host only */
+int loamx_grid_route_points(const loamx_densemap_grid_config* grid_cfg, float leaf, const loamx_grid_cell* cells /* NULL: y = 0 */,
+                            const uint32_t* route_xz, uint32_t n, float* out_xyz /* 3 * n */);   /* host only */
+int loamx_densemap_grid_cell_of(const loamx_densemap_grid_config* grid_cfg, float leaf, float x, float z, uint32_t* rx, uint32_t* rz,
+                                int* inside);   /* host only */
 
 /* ------------------------------------------------------------------------------------------------------------
  * Place recognition (not in the reference): a database of rotation-invariant sweep descriptors in device memory (Scan Context: a

@@ -22,6 +22,9 @@
 //
 // Navigation grid (loamx_densemap_grid, densemap_grid.hip): a window of the table projected to 2-D cells by kernels of their own that
 // only read it; the handle owns their planes.
+//
+// Routing (loamx_densemap_route ..., densemap_route.hip): the cost-to-go field of that grid towards goal cells, on the records where
+// the grid's kernels leave them, and routes traced over it; planes of their own, allocated by the first route call.
 #include "densemap.hpp"
 #include "densemap_file.hpp"
 #include "densemap_history.hpp"
@@ -1012,6 +1015,39 @@ class DenseMap {
     memcpy(out, cells, sizeof(loamx_grid_cell) * (size_t)c.nx * c.nz);
   }
 
+  // include/loamx.h, loamx_densemap_route: checked configurations, a checked rule or none; the grid's kernels as grid() runs them,
+  // the route on their records where they lie; the outputs are written last, all or none
+  void route(const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, const loamx_grid_route_config& rc,
+             const uint32_t* goals_xz, uint32_t n_goals, loamx_grid_cell* out_cells, loamx_route_cell* out_field, uint64_t stats[6]) {
+    LX_HIP(hipSetDevice(cfg.device));
+    wait_adds();
+    const size_t n = (size_t)c.nx * c.nz;
+    const loamx_grid_cell* d_cells = grid_.enqueue(tab_, c, rule, (double)cfg.leaf, own_);
+    uint64_t s[6];
+    const loamx_route_cell* field = route_.run(d_cells, c.nx, c.nz, rc, goals_xz, n_goals, out_field != nullptr, s, own_);
+    const loamx_grid_cell* cells = out_cells ? grid_.fetch(d_cells, n, own_) : nullptr;
+    if (out_cells) memcpy(out_cells, cells, sizeof(loamx_grid_cell) * n);
+    if (out_field) memcpy(out_field, field, sizeof(loamx_route_cell) * n);
+    if (stats) memcpy(stats, s, sizeof(s));
+  }
+  // loamx_densemap_route_cells: the same on the caller's records (every cls checked), in a buffer of the route's own
+  void route_cells(const loamx_grid_cell* cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config& rc, const uint32_t* goals_xz,
+                   uint32_t n_goals, loamx_route_cell* out_field, uint64_t stats[6]) {
+    LX_HIP(hipSetDevice(cfg.device));
+    wait_adds();
+    const size_t n = (size_t)nx * nz;
+    uint64_t s[6];
+    const loamx_route_cell* field = route_.run(route_.upload(cells, n, own_), nx, nz, rc, goals_xz, n_goals, out_field != nullptr, s, own_);
+    if (out_field) memcpy(out_field, field, sizeof(loamx_route_cell) * n);
+    if (stats) memcpy(stats, s, sizeof(s));
+  }
+  void route_trace(const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity, uint32_t* lengths) {
+    LX_REQUIRE(route_.has_field(), "the handle has no field yet (loamx_densemap_route, loamx_densemap_route_cells)");
+    LX_HIP(hipSetDevice(cfg.device));
+    route_.trace(starts_xz, n_starts, out_xz, capacity, lengths, own_);
+  }
+  DmRoute& router() { return route_; }
+
   bool combine = true;   // (bench A/B: the in-wave combining of equal keys)
   uint64_t rehashes = 0;
 
@@ -1045,6 +1081,7 @@ class DenseMap {
   PinBuf<uint32_t> h_rb_;
   uint64_t rebuild_stats_[4] = {0, 0, 0, 0};
   DmGrid grid_;   // the navigation grid's planes (densemap_grid.hip): allocated by the first grid
+  DmRoute route_;   // the route's planes and field (densemap_route.hip): allocated by the first route
 
   // room for n more points in the log: a block of the doubled capacity, the logged points copied over on st, the old block to the
   // graveyard (earlier work may still read it)
@@ -1791,11 +1828,77 @@ int loamx_densemap_grid(loamx_densemap* h, const loamx_densemap_grid_config* cfg
   });
 }
 
+// the checks the route's entry points share: the configuration (NULL: the defaults), the goals and the window's size
+static loamx_grid_route_config checked_route(const loamx_grid_route_config* cfg, const uint32_t* goals_xz, uint32_t n_goals, uint32_t nx,
+                                             uint32_t nz) {
+  loamx_grid_route_config rc;
+  if (cfg) rc = *cfg; else loamx_grid_route_default_config(&rc);
+  dm_route_check(rc);
+  LX_REQUIRE(goals_xz, "goals_xz is NULL");
+  LX_REQUIRE(n_goals >= 1u && n_goals <= 4096u, "n_goals must be in [1, 4096]");
+  LX_REQUIRE(nx >= 1u && nz >= 1u && (uint64_t)nx * nz <= (1ull << 22), "nx * nz must be in [1, 2^22] for a route");
+  return rc;
+}
+
+int loamx_densemap_route(loamx_densemap* h, const loamx_densemap_grid_config* grid_cfg, const loamx_densemap_static_rule* rule,
+                         const loamx_grid_route_config* cfg, const uint32_t* goals_xz, uint32_t n_goals, loamx_grid_cell* out_cells,
+                         loamx_route_cell* out_field, uint64_t stats[6]) {
+  return guard([&]() {
+    LX_REQUIRE(h, "h is NULL");
+    loamx_densemap_grid_config c;
+    if (grid_cfg) c = *grid_cfg; else loamx_densemap_grid_default_config(&c);
+    dm_grid_check(c);
+    if (rule) {
+      LX_REQUIRE(rule->den != 0u, "the rule's den must not be 0");
+      LX_REQUIRE(h->d.carving(), "a rule needs carving, which is not enabled");
+    }
+    const loamx_grid_route_config rc = checked_route(cfg, goals_xz, n_goals, c.nx, c.nz);
+    h->d.route(c, rule, rc, goals_xz, n_goals, out_cells, out_field, stats);
+    return LOAMX_OK;
+  });
+}
+
+int loamx_densemap_route_cells(loamx_densemap* h, const loamx_grid_cell* cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config* cfg,
+                               const uint32_t* goals_xz, uint32_t n_goals, loamx_route_cell* out_field, uint64_t stats[6]) {
+  return guard([&]() {
+    LX_REQUIRE(h, "h is NULL");
+    LX_REQUIRE(cells, "cells is NULL");
+    const loamx_grid_route_config rc = checked_route(cfg, goals_xz, n_goals, nx, nz);
+    for (size_t i = 0; i < (size_t)nx * nz; i++)
+      LX_REQUIRE(cells[i].cls <= LOAMX_GRID_STEP, "cells: the cls of record " + std::to_string(i) + " is not a class");
+    h->d.route_cells(cells, nx, nz, rc, goals_xz, n_goals, out_field, stats);
+    return LOAMX_OK;
+  });
+}
+
+int loamx_densemap_route_trace(loamx_densemap* h, const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity,
+                               uint32_t* lengths) {
+  return guard([&]() {
+    LX_REQUIRE(h, "h is NULL");
+    LX_REQUIRE(starts_xz, "starts_xz is NULL");
+    LX_REQUIRE(n_starts >= 1u && n_starts <= 4096u, "n_starts must be in [1, 4096]");
+    LX_REQUIRE(out_xz || !capacity, "out_xz is NULL");
+    LX_REQUIRE(lengths, "lengths is NULL");
+    h->d.route_trace(starts_xz, n_starts, out_xz, capacity, lengths);
+    return LOAMX_OK;
+  });
+}
+
 // bench / test hooks (not in include/loamx.h): the in-wave combining of equal keys on or off, and the number of rehashes so far
 int loamx_densemap_set_combine(loamx_densemap* h, int on) {
   return guard([&]() { LX_REQUIRE(h, "NULL handle"); h->d.combine = on != 0; return LOAMX_OK; });
 }
 uint64_t loamx_densemap_rehashes(loamx_densemap* h) { return h ? h->d.rehashes : 0; }
+// the route's rounds per look (1..64), and the rounds of the last route in which a tile ran
+int loamx_densemap_route_set_batch(loamx_densemap* h, uint32_t batch) {
+  return guard([&]() {
+    LX_REQUIRE(h, "NULL handle");
+    LX_REQUIRE(batch >= 1u && batch <= 64u, "batch must be in [1, 64]");
+    h->d.router().batch = batch;
+    return LOAMX_OK;
+  });
+}
+uint64_t loamx_densemap_route_active_rounds(loamx_densemap* h) { return h ? h->d.router().active_rounds : 0; }
 
 }  // extern "C"
 

@@ -169,7 +169,14 @@ class DmGrid {
   // the grid of a checked configuration over the table T (every add waited for) on st: one memset, the four kernels, one readback;
   // blocks until the c.nx * c.nz records are in pinned memory and returns them, valid until the next run
   const loamx_grid_cell* run(const DmTable& T, const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, double leaf,
-                             hipStream_t st);
+                             hipStream_t st) {
+    return fetch(enqueue(T, c, rule, leaf, st), (size_t)c.nx * c.nz, st);
+  }
+  // the two halves of run (DmRoute routes on the records where enqueue leaves them): the memset and the four kernels, enqueued;
+  // returns the records on the device, valid until the next enqueue.  fetch: the readback of n of them, blocking
+  const loamx_grid_cell* enqueue(const DmTable& T, const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, double leaf,
+                                 hipStream_t st);
+  const loamx_grid_cell* fetch(const loamx_grid_cell* d_cells, size_t n, hipStream_t st);
 
  private:
   DevBuf<uint32_t> planes_;   // DM_GRID_PLANE_WORDS 32-bit words per cell, plane after plane (densemap_grid.hip)
@@ -179,6 +186,56 @@ class DmGrid {
 
 // include/loamx.h, loamx_densemap_grid_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
 void dm_grid_check(const loamx_densemap_grid_config& c);
+
+// include/loamx.h, weight of a cell under a checked configuration: 0 = blocked, otherwise 1..32 (loamx_grid_route_weight, the
+// device's k_dm_route_weights and a caller's own planner share this one expression)
+__host__ __device__ inline uint32_t dm_route_weight(uint32_t cls, uint32_t clear2, const loamx_grid_route_config& c) {
+  if (clear2 < c.min_clear2) return 0u;
+  if (cls != LOAMX_GRID_FREE && !(cls == LOAMX_GRID_UNKNOWN && c.unknown_weight > 0u)) return 0u;
+  const uint32_t p = clear2 < c.soft_clear2 ? c.soft_weight * (c.soft_clear2 - clear2) / c.soft_clear2 : 0u;   // (<= 15 * 4225)
+  return 1u + p + (cls == LOAMX_GRID_UNKNOWN ? c.unknown_weight : 0u);
+}
+// include/loamx.h, loamx_grid_route_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
+void dm_route_check(const loamx_grid_route_config& c);
+
+// Routing on the navigation grid (include/loamx.h, loamx_densemap_route ...; densemap_route.hip): the weight, cost and dirty planes of
+// a window, its field records and the pinned blocks that goals, starts, counters, field and routes cross through.  Allocated by the
+// first route call, grow to the largest window asked for; the map and the grid's own buffers are only read.
+class DmRoute {
+ public:
+  DmRoute() = default;
+  DmRoute(const DmRoute&) = delete;
+  DmRoute& operator=(const DmRoute&) = delete;
+  // the caller's nx * nz records (every cls checked) in a device buffer of the route's own, enqueued on st
+  const loamx_grid_cell* upload(const loamx_grid_cell* cells, size_t n, hipStream_t st);
+  // the field of nx * nz <= 2^22 records d_cells on the device (written by work enqueued on st) under a checked configuration towards
+  // n_goals in 1..4096 pairs: weights, seeding, the relaxation rounds of densemap_route_schedule.hpp, next and the four exact stats.
+  // Blocks; the field stays on the device for trace() and, when want_field, lies in pinned memory at the return (valid until the
+  // next run).  LOAMX_E_INTERNAL when the rounds reach their cap unsettled
+  const loamx_route_cell* run(const loamx_grid_cell* d_cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config& c,
+                              const uint32_t* goals_xz, uint32_t n_goals, bool want_field, uint64_t stats[6], hipStream_t st);
+  bool has_field() const { return valid_; }
+  // the routes of n_starts in 1..4096 starts over the field of the last run (include/loamx.h, loamx_densemap_route_trace); blocks
+  void trace(const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity, uint32_t* lengths, hipStream_t st);
+
+  uint32_t batch = 16;          // rounds per look (bench / test hook; the choice and its measurement: densemap_route.hip)
+  uint64_t active_rounds = 0;   // of the last run: rounds in which a tile ran (test hook)
+
+ private:
+  DevBuf<loamx_grid_cell> own_cells_;   // route_cells' upload
+  DevBuf<unsigned char> w_;             // weight per cell
+  DevBuf<uint32_t> cost_;               // cost per cell
+  DevBuf<uint32_t> dirty_;              // two planes of one word per tile
+  DevBuf<loamx_route_cell> field_;
+  DevBuf<uint32_t> ctr_;                // ROUTE_MAX_BATCH slots of two words (densemap_route_schedule.hpp)
+  DevBuf<unsigned long long> st_;       // the four exact stats
+  DevBuf<uint32_t> d_xz_, d_len_, d_routes_;   // goals or starts; the routes' lengths; the routes back to back
+  DevBuf<unsigned long long> d_off_;           // the first pair of each route in d_routes_
+  PinBuf<uint32_t> h_xz_, h_ctr_, h_field_, h_len_, h_routes_;
+  PinBuf<unsigned long long> h_off_;
+  uint32_t nx_ = 0, nz_ = 0;
+  bool valid_ = false;
+};
 
 }  // namespace loamx
 

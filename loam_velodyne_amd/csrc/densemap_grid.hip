@@ -159,13 +159,11 @@ __global__ __launch_bounds__(256) void k_dm_grid_clear(uint32_t nx, uint32_t nz,
   }
 }
 
-const loamx_grid_cell* DmGrid::run(const DmTable& T, const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, double leaf,
-                                   hipStream_t st) {
-  constexpr size_t CELL_WORDS = sizeof(loamx_grid_cell) / sizeof(uint32_t);
+const loamx_grid_cell* DmGrid::enqueue(const DmTable& T, const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule,
+                                       double leaf, hipStream_t st) {
   const size_t cells = (size_t)c.nx * c.nz;   // (<= 2^26)
   planes_.reserve(DM_GRID_PLANE_WORDS * cells);
   cells_.reserve(cells);
-  h_cells_.reserve(CELL_WORDS * cells);
   DmGridArgs G;
   G.k = c.cell_leaves; G.nx = c.nx; G.nz = c.nz; G.min_points = c.min_points;
   G.x0 = c.x0; G.z0 = c.z0; G.y_min = c.y_min; G.y_max = c.y_max;
@@ -187,7 +185,13 @@ const loamx_grid_cell* DmGrid::run(const DmTable& T, const loamx_densemap_grid_c
   hipLaunchKernelGGL(k_dm_grid_clear, dim3((c.nx + DM_GRID_TILE - 1) / DM_GRID_TILE, (c.nz + DM_GRID_TILE - 1) / DM_GRID_TILE), dim3(256), 0, st,
                      c.nx, c.nz, (int)c.clear_max, cells_.p);
   LX_HIP(hipGetLastError());
-  store_to_pinned_u32(h_cells_.p, (const uint32_t*)cells_.p, CELL_WORDS * cells, st);
+  return cells_.p;
+}
+
+const loamx_grid_cell* DmGrid::fetch(const loamx_grid_cell* d_cells, size_t n, hipStream_t st) {
+  constexpr size_t CELL_WORDS = sizeof(loamx_grid_cell) / sizeof(uint32_t);
+  h_cells_.reserve(CELL_WORDS * n);
+  store_to_pinned_u32(h_cells_.p, (const uint32_t*)d_cells, CELL_WORDS * n, st);
   LX_HIP(hipStreamSynchronize(st));
   return (const loamx_grid_cell*)h_cells_.p;
 }

@@ -12,7 +12,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LOAMX_LIB") or os.path.join(_HERE, "libloamx.so")   # LOAMX_LIB: a diagnostic build (time stamps inside kernels)
 
-OK, SKIPPED, E_INVALID, E_CAPACITY, E_HIP, E_NOGPU, E_UNSUPPORTED = 0, 1, -1, -2, -3, -4, -5
+OK, SKIPPED, E_INVALID, E_CAPACITY, E_HIP, E_NOGPU, E_UNSUPPORTED, E_INTERNAL = 0, 1, -1, -2, -3, -4, -5, -6
 
 
 class Cloud(C.Structure):
@@ -1267,6 +1267,106 @@ def write_grid_pgm(stem: str, cells, cfg: GridConfig, leaf: float):
     _check(lib().loamx_write_grid_pgm(os.fsencode(stem), a.ctypes.data_as(C.c_void_p), C.byref(cfg), C.c_float(leaf)))
 
 
+class RouteConfig(C.Structure):
+    """loamx_grid_route_config: how the cells of a navigation grid are weighted and joined for routing.  RouteConfig() holds the
+    defaults (connectivity 8, min_clear2 1, soft_clear2 0, soft_weight 0, unknown_weight 0); keyword arguments replace them."""
+    _fields_ = [("connectivity", C.c_uint32), ("min_clear2", C.c_uint32), ("soft_clear2", C.c_uint32), ("soft_weight", C.c_uint32),
+                ("unknown_weight", C.c_uint32)]
+
+    def __init__(self, **fields):
+        super().__init__()
+        lib().loamx_grid_route_default_config(C.byref(self))
+        self.update(**fields)
+
+    def update(self, **fields):
+        for k, v in fields.items():
+            assert hasattr(self, k), k
+            setattr(self, k, v)
+        return self
+
+    def copy(self, **fields):
+        c = RouteConfig()
+        C.memmove(C.byref(c), C.byref(self), C.sizeof(RouteConfig))
+        return c.update(**fields)
+
+    def check(self):
+        """loamx_grid_route_check (host only): LoamxError E_INVALID names the first field out of its bounds"""
+        _check(lib().loamx_grid_route_check(C.byref(self)))
+        return self
+
+
+class RouteCell(C.Structure):
+    """loamx_route_cell, 8 bytes: cost (the smallest sum of move costs to a goal; ROUTE_UNREACHABLE) and next (the direction 0..7 of
+    the next step, (dx, dz) = ROUTE_MOVES[next]; ROUTE_GOAL; ROUTE_NONE)"""
+    _fields_ = [("cost", C.c_uint32), ("next", C.c_uint32)]
+
+
+ROUTE_UNREACHABLE, ROUTE_GOAL, ROUTE_NONE = 0xffffffff, 8, 9
+ROUTE_MOVES = ((1, 0), (1, 1), (0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1))   # (dx, dz) of direction d
+ROUTE_CELL = np.dtype([(n, np.dtype(t)) for n, t in RouteCell._fields_])              # the field as a structured numpy array
+
+
+def _xz_pairs(pairs) -> np.ndarray:
+    """(n, 2) uint32, C order, of a list of (rx, rz) pairs"""
+    return np.ascontiguousarray(np.asarray(pairs, np.uint32).reshape(-1, 2))
+
+
+def _route_field(field) -> np.ndarray:
+    a = np.ascontiguousarray(field)
+    assert a.dtype == ROUTE_CELL and a.ndim == 2, "field must be an (nz, nx) array of ROUTE_CELL records"
+    return a
+
+
+def route_weight(cells, cfg: RouteConfig = None) -> np.ndarray:
+    """loamx_grid_route_weight (host only): the weight of every cell of a GRID_CELL array under cfg, uint8 of the cells' shape: 0
+    blocked, otherwise 1..32"""
+    a = _grid_cells(cells)
+    c = RouteConfig() if cfg is None else cfg
+    flat = a.reshape(-1)
+    out = np.zeros(flat.shape, np.uint8)
+    L, p, step = lib(), flat.ctypes.data, GRID_CELL.itemsize
+    for i in range(flat.size):
+        out[i] = _check(L.loamx_grid_route_weight(C.c_void_p(p + i * step), C.byref(c)))
+    return out.reshape(a.shape)
+
+
+def route_trace(field, start, capacity=None):
+    """loamx_grid_route_trace (host only): the route from start = (rx, rz) over an (nz, nx) field -> ((min(n, capacity), 2) uint32 of
+    (rx, rz) pairs up to and including the goal cell, n = the full length; 0 for a start outside the window or unreachable).
+    capacity None: the whole route.  LoamxError E_INVALID on a field that is not a route field"""
+    f = _route_field(field)
+    nz, nx = f.shape
+    n = C.c_uint32(0)
+    if capacity is None:
+        _check(lib().loamx_grid_route_trace(f.ctypes.data_as(C.c_void_p), nx, nz, C.c_uint32(start[0]), C.c_uint32(start[1]), None, 0, C.byref(n)))
+        capacity = n.value
+    out = np.zeros((capacity, 2), np.uint32)
+    _check(lib().loamx_grid_route_trace(f.ctypes.data_as(C.c_void_p), nx, nz, C.c_uint32(start[0]), C.c_uint32(start[1]),
+                                        out.ctypes.data_as(C.c_void_p), C.c_uint32(capacity), C.byref(n)))
+    return out[:min(n.value, capacity)], n.value
+
+
+def route_points(cfg: GridConfig, leaf: float, route, cells=None) -> np.ndarray:
+    """loamx_grid_route_points (host only): (n, 3) float32 metres in the LOAM frame for the (rx, rz) pairs of a route, the cell
+    centres in x and z and the cells' elevation in y (cells None: 0)"""
+    r = _xz_pairs(route)
+    a = None if cells is None else _grid_cells(cells)
+    assert a is None or a.size == cfg.nx * cfg.nz, "cells does not have the configuration's nx * nz records"
+    out = np.zeros((len(r), 3), np.float32)
+    _check(lib().loamx_grid_route_points(C.byref(cfg), C.c_float(leaf), a.ctypes.data_as(C.c_void_p) if a is not None else None,
+                                         r.ctypes.data_as(C.c_void_p), C.c_uint32(len(r)), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def grid_cell_of(cfg: GridConfig, leaf: float, x: float, z: float):
+    """loamx_densemap_grid_cell_of (host only): the window-relative cell (rx, rz) of a position in metres (LOAM x and z), or None
+    when it lies outside the window"""
+    rx, rz, inside = C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+    _check(lib().loamx_densemap_grid_cell_of(C.byref(cfg), C.c_float(leaf), C.c_float(x), C.c_float(z), C.byref(rx), C.byref(rz),
+                                             C.byref(inside)))
+    return (rx.value, rz.value) if inside.value else None
+
+
 def write_pcd(path: str, points, axes="loam"):
     """loamx_write_pcd: an (N, 4) / (N, 8) float32 cloud as a binary PCD v0.7 file (x y z intensity); axes="sensor" writes the sensor
     axes ingestion started from (x_s = z, y_s = x, z_s = y).  Host only."""
@@ -1303,6 +1403,8 @@ class DenseMap:
         L = lib()
         L.loamx_densemap_create.restype = C.c_void_p
         L.loamx_densemap_rehashes.restype = C.c_uint64
+        L.loamx_densemap_route_active_rounds.restype = C.c_uint64
+        self.route_stats = None
         self._c = _cfg(DenseMapConfig, "loamx_densemap_default_config", leaf=leaf, min_range=min_range, max_range=max_range,
                        max_voxels=max_voxels, initial_slots=initial_slots, device=device)
         self.h = C.c_void_p(L.loamx_densemap_create(C.byref(self._c)))
@@ -1611,6 +1713,65 @@ class DenseMap:
         _check(lib().loamx_densemap_grid(self.h, C.byref(c), C.byref(static) if static is not None else None,
                                          out.ctypes.data_as(C.c_void_p)))
         return out
+
+    ROUTE_STATS = ("traversable", "reachable", "goals_used", "max_cost", "rounds", "tile_runs")
+
+    def _route_stats(self, st):
+        self.route_stats = dict(zip(self.ROUTE_STATS, (int(v) for v in st)))
+
+    def route(self, goals, cfg=None, grid=None, static=None, want_cells=False, want_field=True, **fields):
+        """loamx_densemap_route: the navigation grid of a window (grid: a GridConfig, None: the defaults; static: a StaticRule)
+        and, on it where it lies on the device, the cost-to-go field towards goals, a list of window-relative (rx, rz) pairs, under
+        cfg (a RouteConfig, None: the defaults; fields replace members of a copy of it).  Returns the (nz, nx) array of ROUTE_CELL
+        records, or (field, cells) with want_cells; want_field=False leaves the field on the device for route_trace() and returns
+        None in its place.  The six stats of the call are left in route_stats."""
+        g = (GridConfig() if grid is None else grid).copy().check()
+        c = (RouteConfig() if cfg is None else cfg).copy(**fields).check()
+        xz = _xz_pairs(goals)
+        field = np.zeros((g.nz, g.nx), ROUTE_CELL) if want_field else None
+        cells = np.zeros((g.nz, g.nx), GRID_CELL) if want_cells else None
+        st = (C.c_uint64 * 6)()
+        _check(lib().loamx_densemap_route(self.h, C.byref(g), C.byref(static) if static is not None else None, C.byref(c),
+                                          xz.ctypes.data_as(C.c_void_p), C.c_uint32(len(xz)),
+                                          cells.ctypes.data_as(C.c_void_p) if want_cells else None,
+                                          field.ctypes.data_as(C.c_void_p) if want_field else None, st))
+        self._route_stats(st)
+        return (field, cells) if want_cells else field
+
+    def route_cells(self, cells, goals, cfg=None, want_field=True, **fields):
+        """loamx_densemap_route_cells: the same on an (nz, nx) array of GRID_CELL records of the caller's (edited, painted with
+        keep-out zones, or hand-made), uploaded to a buffer of the route's own"""
+        a = _grid_cells(cells)
+        assert a.ndim == 2, "cells must be an (nz, nx) array"
+        c = (RouteConfig() if cfg is None else cfg).copy(**fields).check()
+        xz = _xz_pairs(goals)
+        field = np.zeros(a.shape, ROUTE_CELL) if want_field else None
+        st = (C.c_uint64 * 6)()
+        _check(lib().loamx_densemap_route_cells(self.h, a.ctypes.data_as(C.c_void_p), C.c_uint32(a.shape[1]), C.c_uint32(a.shape[0]),
+                                                C.byref(c), xz.ctypes.data_as(C.c_void_p), C.c_uint32(len(xz)),
+                                                field.ctypes.data_as(C.c_void_p) if want_field else None, st))
+        self._route_stats(st)
+        return field
+
+    def route_trace(self, starts, capacity):
+        """loamx_densemap_route_trace: the routes from starts, a list of 1..4096 (rx, rz) pairs, over the field of the last route /
+        route_cells call, traced on the device -> (a list of (min(n_i, capacity), 2) uint32 arrays of (rx, rz) pairs up to and
+        including the goal cell, the full lengths n_i as uint32; 0: the start is outside the window or unreachable)"""
+        xz = _xz_pairs(starts)
+        out = np.zeros((len(xz), capacity, 2), np.uint32)
+        lengths = np.zeros(len(xz), np.uint32)
+        _check(lib().loamx_densemap_route_trace(self.h, xz.ctypes.data_as(C.c_void_p), C.c_uint32(len(xz)), out.ctypes.data_as(C.c_void_p),
+                                                C.c_uint32(capacity), lengths.ctypes.data_as(C.c_void_p)))
+        return [out[i, :min(int(n), capacity)] for i, n in enumerate(lengths)], lengths
+
+    @property
+    def route_active_rounds(self) -> int:
+        """test hook: the relaxation rounds of the last route call in which a tile ran"""
+        return int(lib().loamx_densemap_route_active_rounds(self.h))
+
+    def route_set_batch(self, batch: int):
+        """bench hook: the relaxation rounds launched per look at the counters (1..64)"""
+        _check(lib().loamx_densemap_route_set_batch(self.h, C.c_uint32(batch)))
 
     def save(self, path: str):
         """loamx_densemap_save: every word of the map as an 'LXDM' file (include/loamx.h), written beside path and renamed.  The
