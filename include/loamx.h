@@ -478,6 +478,39 @@ typedef struct loamx_voxbucket_status {
 int loamx_voxbucket_probe(const float* pts_xyzi, uint32_t n, const uint32_t* seg_off, uint32_t nseg, const float* poses12, float leaf_even,
                           float leaf_odd, uint32_t flags, float* stack_xyzi, float* out_xyzi, uint32_t* out_off,
                           loamx_voxbucket_status* status, loamx_voxbucket_seg* segs, uint64_t* lo, uint32_t* cnt, uint32_t bucket_cap);
+/* Parity hook for the sweep re-projection on its own (transformToEnd, BasicLaserOdometry.cpp:57-87, and its de-skew twin
+ * transformToStart, :40-53; test use): n packed points (x y z w, w = ring + time fraction, 0 <= w < 1024, finite coordinates) in K
+ * clouds, cloud c = [off[c], off[c + 1]) with off[0] = 0, off[K] = n, 1 <= K <= 4096, empty clouds allowed; cloud c belongs to
+ * stream c % ns, 1 <= ns <= K.  params[ns]: the re-projection parameters of every stream, word for word what the kernels read — the
+ * sine / cosine words are used as given, never recomputed from angles.  The library's own kernels run unmodified, on one object and
+ * stream per process whose buffers live on from call to call.  out_xyzw[n] receives the points.  The variant is flags & 7: */
+#define LOAMX_REPROJECT_BATCH 0u     /* the batch kernel in place: it also writes the ring-first table and folds the bounds */
+#define LOAMX_REPROJECT_FUSED 1u     /* the batch kernel reading points [0, n_corner_all) and [n_corner_all, n) from two source arrays
+                                      * (the fused staging copy); the array it writes starts as all-ones words */
+#define LOAMX_REPROJECT_SINGLE 2u    /* the single-cloud kernel, in place, one launch per cloud */
+#define LOAMX_REPROJECT_COPY 3u      /* the copying single-cloud kernel, one launch per cloud */
+#define LOAMX_REPROJECT_GATHER 4u    /* the gather kernel: every cloud in a buffer of its own, handed over last cloud first, with an
+                                      * explicit stream id per cloud */
+#define LOAMX_REPROJECT_TO_START 5u  /* transformToStart of every point with T and scan_period of its stream; w is handed through */
+#define LOAMX_REPROJECT_NO_RING_TABLE 8u /* the batch kernel gets no ring-first table */
+#define LOAMX_REPROJECT_NO_BOUNDS 16u    /* the batch kernel gets no bounds accumulators */
+/* Variants 2 - 4 have no pass-through of their own: clouds of a stream with enabled == 0 are copied as they are.
+ * ring_first[K * 320] and bounds[6 * K] (variants 0 and 1, unless switched off; NULL otherwise allowed) are uploaded, worked on and
+ * read back, so the caller sees which words were written.  ring_first: per cloud, word r < 319 = (epoch << 24) | index inside the
+ * cloud of the first point of a run of ring r; word 319 = epoch when the cloud is NOT ring-ordered with every ring below 255.
+ * epoch: 1 .. 255.  bounds: per cloud min x y z, max x y z of the points written, as order-preserving words (a float's bits with the
+ * sign bit set when positive, all bits flipped when negative). */
+typedef struct loamx_reproject_params {
+  float T[6];                   /* the sweep's transform: rx ry rz tx ty tz */
+  float sT[3], cT[3];           /* sine / cosine of rx ry rz */
+  float shift[3];               /* imuShiftFromStart */
+  float s_start[3], c_start[3]; /* IMU pitch, yaw, roll at the sweep's start */
+  float s_end[3], c_end[3];     /* ... and at its end */
+  float scan_period;
+  int32_t enabled;              /* 0: the batch kernel leaves the stream's clouds as they are (a first sweep) */
+} loamx_reproject_params;
+int loamx_reproject_probe(const float* pts_xyzw, uint32_t n, const uint32_t* off, uint32_t K, const loamx_reproject_params* params, uint32_t ns,
+                          uint32_t epoch, uint32_t n_corner_all, uint32_t flags, float* out_xyzw, uint32_t* ring_first, uint32_t* bounds);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Streaming pipeline: n independent streams, each advancing one sweep per step through feature extraction ->

@@ -1,9 +1,11 @@
-// C-ABI: parity hooks for four device primitives that otherwise only run inside whole pipelines — the segmented voxel grid
-// (voxel.hpp), the chained scan (scan.hpp), the sub-map grid index (submap_index.hpp) and the bucketed voxel grid (voxbucket.hpp).  Host glue only (plus one small kernel that
+// C-ABI: parity hooks for five device primitives that otherwise only run inside whole pipelines — the segmented voxel grid
+// (voxel.hpp), the chained scan (scan.hpp), the sub-map grid index (submap_index.hpp), the bucketed voxel grid (voxbucket.hpp) and the
+// sweep re-projection (odometry.hpp).  Host glue only (plus one small kernel that
 // stands in for the producers which fold the index's bounds): each hook stages the caller's arrays, runs the primitive the way its
 // callers do, waits, checks the error word and copies the results back.  Each keeps ONE object per process (never freed, guarded by a
 // mutex), so consecutive calls reuse its buffers and its state — which is part of what the tests look at.
 #include <mutex>
+#include "odometry.hpp"
 #include "submap_index.hpp"
 #include "voxbucket.hpp"
 #include "voxel.hpp"
@@ -85,6 +87,18 @@ struct VoxBucketProbe {
   bool ready = false;
 };
 static_assert(sizeof(Pose) == 48 && sizeof(VbSeg) == sizeof(loamx_voxbucket_seg), "poses12 / loamx_voxbucket_seg mirror Pose / VbSeg");
+
+struct ReprojectProbeState {
+  DevBuf<float4> pts, src, src_s, rev;   // src: the caller's points; src_s: points [n_corner_all, n) once more; rev: the clouds last cloud first
+  DevBuf<uint32_t> off, sid, rf, bounds;
+  DevBuf<ToEndParams> params;
+  DevBuf<const float4*> table;
+  std::vector<const float4*> h_table;
+  std::vector<uint32_t> h_sid, h_bounds;
+};
+static_assert(sizeof(ToEndParams) == sizeof(loamx_reproject_params) && sizeof(ToEndParams) == 29 * 4, "loamx_reproject_params mirrors ToEndParams");
+static_assert(offsetof(ToEndParams, shift) == offsetof(loamx_reproject_params, shift) && offsetof(ToEndParams, s_end) == offsetof(loamx_reproject_params, s_end) &&
+              offsetof(ToEndParams, enabled) == offsetof(loamx_reproject_params, enabled), "loamx_reproject_params mirrors ToEndParams");
 
 template <class T> void upload(T* dst, const T* src, size_t n, hipStream_t st) {
   if (n) LX_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, st));
@@ -306,6 +320,91 @@ int loamx_voxbucket_probe(const float* pts_xyzi, uint32_t n, const uint32_t* seg
     status->gave_up = P->vb.failed() ? 1u : 0u;
     status->why = P->vb.why();
     status->buckets = P->vb.last_buckets();
+    return LOAMX_OK;
+  });
+}
+
+int loamx_reproject_probe(const float* pts_xyzw, uint32_t n, const uint32_t* off, uint32_t K, const loamx_reproject_params* params, uint32_t ns,
+                          uint32_t epoch, uint32_t n_corner_all, uint32_t flags, float* out_xyzw, uint32_t* ring_first, uint32_t* bounds) {
+  return guard([&]() {
+    const uint32_t variant = flags & 7u;
+    const bool batch = variant <= LOAMX_REPROJECT_FUSED;
+    const bool with_rf = batch && !(flags & LOAMX_REPROJECT_NO_RING_TABLE), with_bounds = batch && !(flags & LOAMX_REPROJECT_NO_BOUNDS);
+    LX_REQUIRE((flags & ~31u) == 0u && variant <= LOAMX_REPROJECT_TO_START, "unknown flag or variant");
+    LX_REQUIRE(off && params && (pts_xyzw || n == 0) && (out_xyzw || n == 0), "NULL argument");
+    LX_REQUIRE((ring_first || !with_rf) && (bounds || !with_bounds), "NULL argument");
+    LX_REQUIRE(K >= 1 && K <= 4096, "K must be in [1, 4096]");
+    LX_REQUIRE(ns >= 1 && ns <= K, "ns must be in [1, K]");
+    LX_REQUIRE(epoch >= 1 && epoch <= 255, "epoch must be in [1, 255]");
+    LX_REQUIRE(n <= (1u << 24), "too many points for one probe");
+    LX_REQUIRE(off[0] == 0u && off[K] == n, "offsets must run from 0 to n");
+    for (uint32_t c = 0; c < K; c++) LX_REQUIRE(off[c] <= off[c + 1], "offsets must not decrease");
+    LX_REQUIRE(n_corner_all <= n, "n_corner_all must not exceed n");
+    const float4* h_pts = reinterpret_cast<const float4*>(pts_xyzw);
+    LX_REQUIRE(packed_all_finite(h_pts, n), "non-finite coordinate");
+    for (uint32_t i = 0; i < n; i++) LX_REQUIRE(h_pts[i].w >= 0.f && h_pts[i].w < 1024.f, "w must be in [0, 1024)");   // ((int)w is defined only for values that fit)
+    static std::mutex mu;
+    static ReprojectProbeState* P = nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    hipStream_t st = probe_stream();
+    if (!P) P = new ReprojectProbeState;
+    const ToEndParams* h_params = reinterpret_cast<const ToEndParams*>(params);
+    P->pts.reserve((size_t)n + 1); P->src.reserve((size_t)n + 1);
+    P->off.reserve((size_t)K + 2); P->params.reserve(ns);
+    upload(P->off.p, off, (size_t)K + 1, st);
+    upload(P->params.p, h_params, ns, st);
+    upload(P->src.p, h_pts, n, st);
+    ReprojectProbe a = {};
+    a.variant = (int)variant;
+    a.pts = P->pts.p; a.n = n;
+    a.d_off = P->off.p; a.h_off = off; a.K = K; a.ns = ns;
+    a.d_params = P->params.p; a.h_params = h_params;
+    a.src = P->src.p; a.n_corner_all = n_corner_all;
+    a.rf_epoch = epoch;
+    if (variant == LOAMX_REPROJECT_BATCH) {
+      upload(P->pts.p, h_pts, n, st);
+    } else if (n) {
+      LX_HIP(hipMemsetAsync(P->pts.p, 0xff, sizeof(float4) * (size_t)n, st));   // (all-ones words, NaN: nothing of use where the kernels only write)
+    }
+    if (variant == LOAMX_REPROJECT_FUSED) {
+      P->src_s.reserve((size_t)n + 1);
+      upload(P->src_s.p, h_pts + n_corner_all, (size_t)(n - n_corner_all), st);
+      a.src_s = P->src_s.p;
+    }
+    if (variant == LOAMX_REPROJECT_GATHER) {
+      P->rev.reserve((size_t)n + 1); P->table.reserve(K); P->sid.reserve(K);
+      P->h_table.resize(K); P->h_sid.resize(K);
+      for (uint32_t c = 0; c < K; c++) {
+        P->h_table[c] = P->rev.p + (n - off[c + 1]);
+        P->h_sid[c] = c % ns;
+        upload(P->rev.p + (n - off[c + 1]), h_pts + off[c], (size_t)(off[c + 1] - off[c]), st);
+      }
+      upload(P->table.p, P->h_table.data(), K, st);
+      upload(P->sid.p, P->h_sid.data(), K, st);
+      a.table = P->table.p; a.sid = P->sid.p;
+    }
+    if (with_rf) {
+      P->rf.reserve((size_t)K * OD_RF_N);
+      upload(P->rf.p, ring_first, (size_t)K * OD_RF_N, st);
+      a.ring_first = P->rf.p;
+    }
+    if (with_bounds) {   // the caller's six words per cloud, each in its own cache line as SubMapIndexBatch keeps them
+      const size_t words = (size_t)6 * K * BB_STRIDE;
+      P->bounds.reserve(words);
+      P->h_bounds.assign(words, 0u);
+      for (uint32_t c = 0; c < K; c++)
+        for (uint32_t k = 0; k < 6; k++) P->h_bounds[bb_word(c, k)] = bounds[6 * c + k];
+      upload(P->bounds.p, P->h_bounds.data(), words, st);
+      a.bounds = P->bounds.p;
+    }
+    reproject_probe_launch(a, st);
+    download(reinterpret_cast<float4*>(out_xyzw), P->pts.p, n, st);
+    if (with_rf) download(ring_first, P->rf.p, (size_t)K * OD_RF_N, st);
+    if (with_bounds) download(P->h_bounds.data(), P->bounds.p, P->h_bounds.size(), st);
+    LX_HIP(hipStreamSynchronize(st));
+    if (with_bounds)
+      for (uint32_t c = 0; c < K; c++)
+        for (uint32_t k = 0; k < 6; k++) bounds[6 * c + k] = P->h_bounds[bb_word(c, k)];
     return LOAMX_OK;
   });
 }

@@ -263,7 +263,7 @@ __device__ inline int nn1_block(const GridDesc& g, const Block27& B, const float
 //     ring-first table against the block's candidate count) only decides speed; both ways give the same ind[] triple.
 // Measured and dropped on the way (profiles/r04_corr.md): the windows staged in LDS by 32- and 8-feature workgroups (5x less L2
 // traffic, no faster: the searches are latency chains, not bandwidth).
-constexpr int OD_RF_N = 320;           // ring-first table entries per cloud: rings 0..318 (ring ids < 256: loamx.h); entry 319 = epoch of the last UNORDERED version of the cloud
+// (OD_RF_N, the ring-first table's entries per cloud: odometry.hpp)
 #ifdef LOAMX_PROF_CORR
 __device__ unsigned long long g_corr_ts[3][16];   // [corner feature / flat mid / last flat][stamp]
 #define OC_TS(k) do { if (blockIdx.y == 0 && lane == 0 && ts_slot >= 0) g_corr_ts[ts_slot][k] = wall_clock64(); } while (0)
@@ -922,6 +922,65 @@ __global__ __launch_bounds__(256) void k_to_end_gather(float4* __restrict__ dst,
     if (off[mid] <= i) lo = mid; else hi = mid;
   }
   dst[i] = to_end_point(src[lo][i - off[lo]], params[sid[lo]]);
+}
+
+// parity hook: transformToStart as k_odom_corr_grid / k_odom_lm call it, for every point of a batch with T and scan_period of its
+// cloud's stream (.w is handed through, :49)
+__global__ __launch_bounds__(256) void k_to_start_probe(float4* __restrict__ dst, const float4* __restrict__ src, uint32_t n,
+                                                        const uint32_t* __restrict__ off, uint32_t K, uint32_t ns,
+                                                        const ToEndParams* __restrict__ params) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t lo = 0, hi = K;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (off[mid] <= i) lo = mid; else hi = mid;
+  }
+  const ToEndParams& P = params[lo % ns];
+  const float4 p = src[i];
+  float x, y, z;
+  transform_to_start(P.T, P.scan_period, p, x, y, z);
+  dst[i] = make_float4(x, y, z, p.w);
+}
+
+void reproject_probe_launch(const ReprojectProbe& a, hipStream_t st) {
+  if (!a.n) return;
+  const dim3 grid((a.n + 255) / 256), block(256);
+  switch (a.variant) {
+    case 0:
+      hipLaunchKernelGGL(k_transform_to_end_batch, grid, block, 0, st, a.pts, a.n, a.d_off, a.K, a.ns, a.d_params, (const float4*)nullptr,
+                         (const float4*)nullptr, 0u, a.bounds, a.ring_first, a.rf_epoch);
+      break;
+    case 1:
+      hipLaunchKernelGGL(k_transform_to_end_batch, grid, block, 0, st, a.pts, a.n, a.d_off, a.K, a.ns, a.d_params, a.src, a.src_s,
+                         a.n_corner_all, a.bounds, a.ring_first, a.rf_epoch);
+      break;
+    case 2:
+    case 3:
+      for (uint32_t c = 0; c < a.K; c++) {
+        const uint32_t o = a.h_off[c], m = a.h_off[c + 1] - o;
+        if (!m) continue;
+        const ToEndParams& P = a.h_params[c % a.ns];
+        if (!P.enabled || a.variant == 2) LX_HIP(hipMemcpyAsync(a.pts + o, a.src + o, sizeof(float4) * m, hipMemcpyDeviceToDevice, st));
+        if (!P.enabled) continue;
+        if (a.variant == 2) hipLaunchKernelGGL(k_transform_to_end, dim3((m + 255) / 256), block, 0, st, a.pts + o, m, P);
+        else hipLaunchKernelGGL(k_transform_to_end_copy, dim3((m + 255) / 256), block, 0, st, a.pts + o, a.src + o, m, P);
+      }
+      break;
+    case 4:
+      hipLaunchKernelGGL(k_to_end_gather, grid, block, 0, st, a.pts, a.n, a.d_off, a.K, a.table, a.sid, a.d_params);
+      for (uint32_t c = 0; c < a.K; c++) {   // (behind the launch: what it wrote for a stream without re-projection is replaced)
+        const uint32_t o = a.h_off[c], m = a.h_off[c + 1] - o;
+        if (m && !a.h_params[c % a.ns].enabled) LX_HIP(hipMemcpyAsync(a.pts + o, a.src + o, sizeof(float4) * m, hipMemcpyDeviceToDevice, st));
+      }
+      break;
+    case 5:
+      hipLaunchKernelGGL(k_to_start_probe, grid, block, 0, st, a.pts, a.src, a.n, a.d_off, a.K, a.ns, a.d_params);
+      break;
+    default:
+      LX_REQUIRE(false, "unknown variant");
+  }
+  LX_HIP(hipGetLastError());
 }
 
 // ----------------------------------------------------------------------------------------------------------------

@@ -69,6 +69,24 @@ struct ToEndParams {
   int enabled;
 };
 
+constexpr int OD_RF_N = 320;           // ring-first table entries per cloud: rings 0..318 (ring ids < 256: loamx.h); entry 319 = epoch of the last UNORDERED version of the cloud
+
+// parity hook (loamx_reproject_probe): the re-projection kernels on their own, launched the way their callers launch them.  Everything
+// is device memory prepared by the caller; asynchronous on `st`.  variant: 0 k_transform_to_end_batch in place, 1 the same reading
+// src_c / src_s, 2 k_transform_to_end and 3 k_transform_to_end_copy once per cloud (src -> pts), 4 k_to_end_gather (table, sid),
+// 5 transform_to_start of every point with T and scan_period of its cloud's stream (src -> pts).  Variants 2-4 have no pass-through:
+// the clouds of a stream with enabled == 0 are copied as they are.
+struct ReprojectProbe {
+  int variant;
+  float4* pts; uint32_t n;
+  const uint32_t* d_off; const uint32_t* h_off; uint32_t K, ns;
+  const ToEndParams* d_params; const ToEndParams* h_params;
+  const float4* src; const float4* src_s; uint32_t n_corner_all;
+  uint32_t* bounds; uint32_t* ring_first; uint32_t rf_epoch;
+  const float4* const* table; const uint32_t* sid;
+};
+void reproject_probe_launch(const ReprojectProbe& a, hipStream_t st);
+
 struct OdomStream {
   bool inited = false;
   long frame = 0;

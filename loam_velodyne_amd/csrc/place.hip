@@ -257,8 +257,7 @@ class PlaceDB {
   }
   ~PlaceDB() {
     (void)hipSetDevice(cfg.device);
-    if (last_st_) (void)hipEventSynchronize(ev_last_);
-    (void)hipStreamSynchronize(own_);
+    (void)hipStreamSynchronize(own_);   // (behind every add: add())
     free_graveyard();
     (void)hipFree(desc_);
     (void)hipFree(keys_);
@@ -266,6 +265,7 @@ class PlaceDB {
     (void)hipEventDestroy(ev_staged_);
     (void)hipEventDestroy(ev_done_);
     (void)hipStreamDestroy(own_);
+    (void)hipGetLastError();   // (whatever the calls above were answered with is not the next caller's error)
   }
   loamx_place_config cfg;
   const int R, S;
@@ -390,7 +390,7 @@ class PlaceDB {
 
  private:
   hipStream_t own_ = nullptr;      // host-fed adds, queries, exports
-  hipStream_t last_st_ = nullptr;  // the stream of the last enqueued add (ev_last_ recorded behind it)
+  bool added_ = false;             // ev_last_ has been recorded: on own_, behind every add enqueued so far (add())
   hipEvent_t ev_last_ = nullptr, ev_staged_ = nullptr, ev_done_ = nullptr;
   bool staged_pending_ = false;
   float* desc_ = nullptr;          // cap_ x R*S
@@ -421,10 +421,10 @@ class PlaceDB {
   bool full() const { return cfg.max_entries && n_ + 1u > cfg.max_entries; }
   // st runs behind every add enqueued so far (on whichever stream)
   void order_behind(hipStream_t st) {
-    if (last_st_ && last_st_ != st) LX_HIP(hipStreamWaitEvent(st, ev_last_, 0));
+    if (added_ && st != own_) LX_HIP(hipStreamWaitEvent(st, ev_last_, 0));
   }
   void wait_adds() {
-    if (last_st_) LX_HIP(hipEventSynchronize(ev_last_));
+    if (added_) LX_HIP(hipEventSynchronize(ev_last_));
     if (staged_pending_) { LX_HIP(hipEventSynchronize(ev_staged_)); staged_pending_ = false; }
     free_graveyard();
   }
@@ -470,8 +470,15 @@ class PlaceDB {
       growths++;
     }
     describe(pts, n, origin, desc_ + (size_t)n_ * RS, keys_ + (size_t)n_ * R, st);
+    // The order is handed on to own_ at once: a source's stream may be destroyed before the database next waits, and an event that was
+    // last recorded on a destroyed stream must not be waited for, queried or synchronised (the runtime looks at that stream and has
+    // answered "event last recorded in a capturing stream").  Outside this function ev_last_ is an event of own_.
     LX_HIP(hipEventRecord(ev_last_, st));
-    last_st_ = st;
+    if (st != own_) {
+      LX_HIP(hipStreamWaitEvent(own_, ev_last_, 0));
+      LX_HIP(hipEventRecord(ev_last_, own_));
+    }
+    added_ = true;
     if (id) *id = n_;
     n_++;
     return LOAMX_OK;

@@ -358,6 +358,31 @@ def voxbucket_probe(points, seg_off, poses12, leaf_even, leaf_odd=None, flags=0)
                 buckets=int(status[2]), segs=segs[:nseg], lo=lo, cnt=cnt)
 
 
+REPROJECT_BATCH, REPROJECT_FUSED, REPROJECT_SINGLE, REPROJECT_COPY, REPROJECT_GATHER, REPROJECT_TO_START = 0, 1, 2, 3, 4, 5
+REPROJECT_NO_RING_TABLE, REPROJECT_NO_BOUNDS = 8, 16
+REPROJECT_RF_N = 320
+REPROJECT_PARAMS = np.dtype([("T", "<f4", 6), ("sT", "<f4", 3), ("cT", "<f4", 3), ("shift", "<f4", 3), ("s_start", "<f4", 3),
+                             ("c_start", "<f4", 3), ("s_end", "<f4", 3), ("c_end", "<f4", 3), ("scan_period", "<f4"), ("enabled", "<i4")])
+
+
+def reproject_probe(points, off, params, epoch=1, n_corner_all=0, flags=0, ring_first=None, bounds=None):
+    """parity hook: the sweep re-projection kernels on their own (loamx_reproject_probe), on the process's one object ->
+    dict(out: (n, 4) float32, ring_first: (K, 320) uint32, bounds: (K, 6) uint32 encoded words).  params: ns records of
+    REPROJECT_PARAMS, used word for word.  ring_first / bounds: what the arrays hold before the call (default: zeros / the reset
+    words, all ones for a minimum and zero for a maximum); they come back as the kernel left them."""
+    p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 4))
+    off = np.ascontiguousarray(off, np.uint32)
+    par = np.ascontiguousarray(params, REPROJECT_PARAMS).reshape(-1)
+    n, K = len(p), len(off) - 1
+    rf = np.zeros((max(K, 1), REPROJECT_RF_N), np.uint32) if ring_first is None else np.array(ring_first, np.uint32).reshape(max(K, 1), REPROJECT_RF_N)
+    bb = np.tile(np.array([0xffffffff] * 3 + [0] * 3, np.uint32), (max(K, 1), 1)) if bounds is None else np.array(bounds, np.uint32).reshape(max(K, 1), 6)
+    out = np.zeros((max(n, 1), 4), np.float32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(lib().loamx_reproject_probe(ptr(p), C.c_uint32(n), ptr(off), C.c_uint32(K), ptr(par), C.c_uint32(len(par)), C.c_uint32(epoch),
+                                       C.c_uint32(n_corner_all), C.c_uint32(flags), ptr(out), ptr(rf), ptr(bb)))
+    return dict(out=out[:n], ring_first=rf, bounds=bb)
+
+
 class TransformMaintenance:
     """loamx_tm_*: BasicTransformMaintenance (host arithmetic, no device)."""
 

@@ -212,6 +212,15 @@ int orc_odom_get_cloud(void* h, int which, float* out, int cap) {
   return from_cloud(*c[which], out, cap);
 }
 void orc_odom_transform_full_to_end(void* h) { auto* o = (LaserOdometry*)h; o->transform_to_end(o->laserCloud); }
+// transformToStart (:40-53) of n packed points with the handle's transform and scan period (out may be pts)
+void orc_odom_transform_to_start(void* h, const float* pts, int n, float* out) {
+  auto* o = (LaserOdometry*)h;
+  for (int i = 0; i < n; i++) {
+    Pt pi{pts[4 * i], pts[4 * i + 1], pts[4 * i + 2], pts[4 * i + 3]}, po;
+    o->transform_to_start(pi, po);
+    out[4 * i] = po.x; out[4 * i + 1] = po.y; out[4 * i + 2] = po.z; out[4 * i + 3] = po.i;
+  }
+}
 void orc_odom_stats(void* h, int* s3) {
   auto* o = (LaserOdometry*)h;
   s3[0] = o->lastIterCount; s3[1] = o->lastSelNum; s3[2] = (int)o->frameCount;

@@ -247,6 +247,19 @@ class LaserOdometry:
         self.o.L.orc_odom_transform_full_to_end(self.h)
         return _get_cloud(self.o.L.orc_odom_get_cloud, self.h, 2)
 
+    def to_end(self, pts):
+        """transformToEnd of any cloud with the current transform and IMU terms (through the full-resolution cloud's slot)"""
+        p = _pts(pts)
+        self.o.L.orc_odom_set_cloud(self.h, 0, p.ctypes.data_as(C.c_void_p), len(p))
+        return self.full_to_end()
+
+    def to_start(self, pts):
+        """transformToStart of every point with the current transform"""
+        p = _pts(pts)
+        out = np.zeros_like(p)
+        self.o.L.orc_odom_transform_to_start(self.h, p.ctypes.data_as(C.c_void_p), len(p), out.ctypes.data_as(C.c_void_p))
+        return out
+
     def stats(self):
         s = np.zeros(3, np.int32)
         self.o.L.orc_odom_stats(self.h, s.ctypes.data_as(C.c_void_p))
