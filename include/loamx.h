@@ -1326,6 +1326,71 @@ int loamx_grid_route_points(const loamx_densemap_grid_config* grid_cfg, float le
 int loamx_densemap_grid_cell_of(const loamx_densemap_grid_config* grid_cfg, float leaf, float x, float z, uint32_t* rx, uint32_t* rz,
                                 int* inside);   /* host only */
 
+/* Objects: connected components of the voxel map (optional: a handle that never segments runs the kernels it ran and allocates what
+ * it allocated).  "Which voxels belong together?": on the voxel lattice, Euclidean clustering with a tolerance of one leaf is
+ * connected-component labelling of the selected voxels, done on the device where the table lies; a component list and one word
+ * per voxel come back.  Every output word depends only on the set of selected voxels: not on the thread schedule, the table's
+ * size, the number of rehashes or the order of the adds.
+ *
+ * Selection: a voxel (ix, iy, iz) with n points is selected iff n >= min_points, lo[a] <= i_a <= hi[a] on every axis, and it
+ * passes `which`: ALL every such voxel; STATIC those the rule does not call dynamic; DYNAMIC those it does (the expression of
+ * loamx_densemap_rule_is_dynamic on the voxel's n and miss).
+ * Adjacency: two selected voxels are adjacent iff their index vectors differ by a non-zero d with every |d_a| <= 1 and
+ * |d_x| + |d_y| + |d_z| <= 1 (connectivity 6: a shared face), <= 2 (18: a face or an edge), <= 3 (26: a face, an edge or a
+ * corner).  It is decided on the indices, not on the packed key: a neighbour with any |i_a| >= 2^20 does not exist and is not
+ * looked up, so nothing joins across the edge of the key range.  A voxel that is not selected (outside the window, say) connects
+ * nothing.
+ * Components: the classes of the transitive closure of adjacency.  A component is kept iff it has at least min_voxels voxels;
+ * the kept ones are numbered 0 .. C-1 in ascending min_key, the smallest voxel key in them (key = (ix + 2^20) | (iy + 2^20) << 21
+ * | (iz + 2^20) << 42), and segs[c] is component c: its min_key, the number of its voxels, the sum of their n, its inclusive
+ * bounding box in voxel indices and the sum of the indices per axis, all exact integers.
+ * Labels: labels[j] belongs to voxel j in the record order of loamx_densemap_download (ascending key): the number of its
+ * component, LOAMX_SEGMENT_NONE when the voxel is not selected or its component was dropped.  *n_voxels is the map's voxel count
+ * (the length of labels), *n_segs is C.
+ * stats[6]: voxels selected;  components before min_voxels;  components kept;  voxels in kept components;  voxels of the largest
+ * component (before min_voxels; 0: none);  hook attempts that lost to another thread.  The first five are part of the definition
+ * and exact, the last describes the schedule.
+ * loamx_segment_box (host only): metres, LOAM frame: lo_m[a] = (float)((double)lo[a] * (double)leaf), hi_m[a] =
+ * (float)((double)(hi[a] + 1) * (double)leaf), centre[a] = (float)(((double)sum_idx[a] / (double)voxels + 0.5) * (double)leaf):
+ * the mean of the voxel centres.  LOAMX_E_INVALID for a NULL argument or voxels == 0.
+ * Ordering: as loamx_densemap_raycast the call waits for every add, runs on the map's own stream and blocks until the outputs are
+ * back through pinned memory.  The map is only read: every export is byte for byte what it was before the call.  Integer
+ * atomics only.  The work arrays live in the handle, are allocated by the first call, sized by the table's slots, grown when the
+ * table has grown and freed on destroy.  labels and segs may each be NULL: that output is skipped (and, without labels, the
+ * voxels' keys do not cross to the host).  An empty map is LOAMX_OK with every count zero and nothing launched beyond the read
+ * of the map's counters.
+ * LOAMX_E_INVALID, with a message that names the argument, nothing written to any output and the handle as it was: NULL h,
+ * n_voxels, n_segs or stats;  a configuration that fails loamx_densemap_segment_check (which > 2;  connectivity not 6, 18 or 26;
+ * min_points or min_voxels 0;  lo[a] > hi[a];  a bound outside +-(2^20 - 1));  which != ALL on a handle without carving;  a rule
+ * whose den is 0 (the rule is read only when which != ALL).
+ * LOAMX_E_CAPACITY: labels given and label_capacity < the map's voxels, or segs given and seg_capacity < C.  Nothing is written
+ * to labels, segs or stats; *n_voxels and *n_segs hold the needed counts. */
+#define LOAMX_SEGMENT_NONE 0xFFFFFFFFu
+#define LOAMX_SEGMENT_ALL 0u      /* every voxel that passes min_points and the window */
+#define LOAMX_SEGMENT_STATIC 1u   /* ... and is not dynamic under the rule (needs carving) */
+#define LOAMX_SEGMENT_DYNAMIC 2u  /* ... and is dynamic under the rule (needs carving) */
+typedef struct loamx_densemap_segment_config {
+  uint32_t which;          /* LOAMX_SEGMENT_ALL / _STATIC / _DYNAMIC (default ALL) */
+  uint32_t connectivity;   /* 6, 18 or 26 (default 26) */
+  uint32_t min_points;     /* a voxel with fewer points is not selected, >= 1 (default 1) */
+  uint32_t min_voxels;     /* components with fewer voxels are dropped, >= 1 (default 1) */
+  int32_t lo[3], hi[3];    /* inclusive window in voxel indices (ix, iy, iz); default -(2^20 - 1) .. 2^20 - 1: everything */
+} loamx_densemap_segment_config;
+typedef struct loamx_segment {   /* 72 bytes */
+  uint64_t min_key;        /* smallest voxel key of the component: its identity */
+  uint64_t voxels;         /* voxels in it */
+  uint64_t points;         /* sum of their n */
+  int32_t lo[3], hi[3];    /* inclusive bounding box in voxel indices */
+  int64_t sum_idx[3];      /* sum of the voxel indices per axis (the centroid's numerator) */
+} loamx_segment;
+void loamx_densemap_segment_default_config(loamx_densemap_segment_config* cfg);   /* host only */
+int loamx_densemap_segment_check(const loamx_densemap_segment_config* cfg);       /* host only */
+int loamx_densemap_segment(loamx_densemap* h, const loamx_densemap_segment_config* cfg /* NULL: the defaults */,
+                           const loamx_densemap_static_rule* rule /* NULL: the default rule; read only when which != ALL */,
+                           uint32_t* labels /* NULL: not wanted */, uint64_t label_capacity, uint64_t* n_voxels,
+                           loamx_segment* segs /* NULL: not wanted */, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[6]);
+int loamx_segment_box(const loamx_segment* s, float leaf, float lo_m[3], float hi_m[3], float centre[3]);   /* host only */
+
 /* ------------------------------------------------------------------------------------------------------------
  * Place recognition (not in the reference): a database of rotation-invariant sweep descriptors in device memory (Scan Context: a
  * ring x sector polar grid of maximum heights around the sensor) and an exhaustive search for the earlier entries that look like a

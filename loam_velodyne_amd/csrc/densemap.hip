@@ -76,18 +76,6 @@ __device__ inline bool dm_find_or_claim(unsigned long long* __restrict__ keys, u
   return false;
 }
 
-// the probe loop above without the CAS: 1 the key is at `slot`, 0 it is absent, -1 the probe bound was reached
-__device__ inline int dm_find(const unsigned long long* keys, uint32_t mask, uint32_t shift, unsigned long long key, uint32_t& slot) {
-  uint32_t h = (uint32_t)dm_hash(key, shift);
-  for (uint32_t probe = 0; probe <= mask; probe++) {
-    const unsigned long long cur = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == key) { slot = h; return 1; }
-    if (cur == DM_EMPTY) return 0;
-    h = (h + 1u) & mask;
-  }
-  return -1;
-}
-
 // wave-aggregated add of this lane's `c` to a 64-bit counter
 __device__ inline void dm_wave_count(unsigned long long* ctr, bool c) {
   const unsigned long long m = __ballot(c);
@@ -1048,6 +1036,26 @@ class DenseMap {
   }
   DmRoute& router() { return route_; }
 
+  // include/loamx.h, loamx_densemap_segment: a checked configuration and rule; the table is only read.  The outputs are written last,
+  // all or none (LOAMX_E_CAPACITY: only the two counts)
+  int segment(const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint32_t* labels, uint64_t label_capacity,
+              uint64_t* n_voxels, loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[6]) {
+    read_counters();   // (waits for every add; the exact voxel count)
+    const uint64_t occ = occ_.occ;
+    std::vector<uint32_t> lab;
+    std::vector<loamx_segment> sg;
+    uint64_t s[6] = {0, 0, 0, 0, 0, 0};
+    if (occ) segmenter().run(tab_, c, rule, occ, labels != nullptr, lab, sg, s, own_);
+    *n_voxels = occ;
+    *n_segs = sg.size();
+    if ((labels && label_capacity < occ) || (segs && seg_capacity < sg.size())) return LOAMX_E_CAPACITY;
+    if (labels && occ) memcpy(labels, lab.data(), sizeof(uint32_t) * occ);
+    if (segs && !sg.empty()) memcpy(segs, sg.data(), sizeof(loamx_segment) * sg.size());
+    memcpy(stats, s, sizeof(s));
+    return LOAMX_OK;
+  }
+  DmSegment& segmenter() { return seg_; }
+
   bool combine = true;   // (bench A/B: the in-wave combining of equal keys)
   uint64_t rehashes = 0;
 
@@ -1082,6 +1090,7 @@ class DenseMap {
   uint64_t rebuild_stats_[4] = {0, 0, 0, 0};
   DmGrid grid_;   // the navigation grid's planes (densemap_grid.hip): allocated by the first grid
   DmRoute route_;   // the route's planes and field (densemap_route.hip): allocated by the first route
+  DmSegment seg_;   // the components' work arrays (densemap_segment.hip): allocated by the first segment call
 
   // room for n more points in the log: a block of the doubled capacity, the logged points copied over on st, the old block to the
   // graveyard (earlier work may still read it)
@@ -1881,6 +1890,28 @@ int loamx_densemap_route_trace(loamx_densemap* h, const uint32_t* starts_xz, uin
     LX_REQUIRE(lengths, "lengths is NULL");
     h->d.route_trace(starts_xz, n_starts, out_xz, capacity, lengths);
     return LOAMX_OK;
+  });
+}
+
+int loamx_densemap_segment(loamx_densemap* h, const loamx_densemap_segment_config* cfg, const loamx_densemap_static_rule* rule, uint32_t* labels,
+                           uint64_t label_capacity, uint64_t* n_voxels, loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs,
+                           uint64_t stats[6]) {
+  return guard([&]() {
+    LX_REQUIRE(h, "h is NULL");
+    LX_REQUIRE(n_voxels, "n_voxels is NULL");
+    LX_REQUIRE(n_segs, "n_segs is NULL");
+    LX_REQUIRE(stats, "stats is NULL");
+    loamx_densemap_segment_config c;
+    if (cfg) c = *cfg; else loamx_densemap_segment_default_config(&c);
+    dm_segment_check(c);
+    loamx_densemap_static_rule r;
+    loamx_densemap_static_rule_default(&r);
+    if (c.which != LOAMX_SEGMENT_ALL) {
+      LX_REQUIRE(h->d.carving(), "which: a selection by the rule needs carving, which is not enabled");
+      if (rule) r = *rule;
+      LX_REQUIRE(r.den != 0u, "the rule's den must not be 0");
+    }
+    return h->d.segment(c, r, labels, label_capacity, n_voxels, segs, seg_capacity, n_segs, stats);
   });
 }
 

@@ -106,6 +106,18 @@ __device__ inline unsigned long long dm_hash(unsigned long long key, uint32_t sh
   return (key * 0x9E3779B97F4A7C15ull) >> shift;
 }
 
+// the probe loop of dm_find_or_claim (densemap.hip) without the CAS: 1 the key is at `slot`, 0 it is absent, -1 the probe bound was reached
+__device__ inline int dm_find(const unsigned long long* keys, uint32_t mask, uint32_t shift, unsigned long long key, uint32_t& slot) {
+  uint32_t h = (uint32_t)dm_hash(key, shift);
+  for (uint32_t probe = 0; probe <= mask; probe++) {
+    const unsigned long long cur = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == key) { slot = h; return 1; }
+    if (cur == DM_EMPTY) return 0;
+    h = (h + 1u) & mask;
+  }
+  return -1;
+}
+
 // include/loamx.h, loamx_densemap_static_rule: the voxel with n points and `miss` crossings is dynamic
 __host__ __device__ inline bool dm_dynamic(const loamx_densemap_static_rule& r, unsigned long long n, uint32_t miss) {
   return miss >= r.min_misses && (unsigned long long)miss * r.den > n * r.num;
@@ -235,6 +247,36 @@ class DmRoute {
   PinBuf<unsigned long long> h_off_;
   uint32_t nx_ = 0, nz_ = 0;
   bool valid_ = false;
+};
+
+// include/loamx.h, loamx_densemap_segment_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
+void dm_segment_check(const loamx_densemap_segment_config& c);
+
+// Connected components of the voxel table (include/loamx.h, loamx_densemap_segment; densemap_segment.hip): one parent word and one
+// component id per slot, the per-block counts of the two compactions, the components' accumulators, and the pinned blocks the totals,
+// the components and the (key, id) pairs come back through.  Allocated by the first call, sized by the table's slots, grown when the
+// table has grown; the map is only read.
+class DmSegment {
+ public:
+  DmSegment() = default;
+  DmSegment(const DmSegment&) = delete;
+  DmSegment& operator=(const DmSegment&) = delete;
+  // the components of the table T (every add waited for, `occ` voxels, occ >= 1) under a checked configuration and rule, on st:
+  // select, link, flatten, the two scans, ids and reduce, and the host's ordering by key.  Blocks.  segs: the kept components in
+  // ascending min_key; labels (when want_labels): one word per voxel in ascending key order; stats as in include/loamx.h
+  void run(const DmTable& T, const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint64_t occ, bool want_labels,
+           std::vector<uint32_t>& labels, std::vector<loamx_segment>& segs, uint64_t stats[6], hipStream_t st);
+
+ private:
+  DevBuf<uint32_t> parent_, rootid_;       // per slot: the union-find word (NONE: not selected); the compact id of a root
+  DevBuf<uint32_t> blk_;                   // two runs of blocks + 1 words: roots, then occupied slots, per 256-slot block
+  DevBuf<uint32_t> scratch_;               // the scans' two words
+  DevBuf<unsigned long long> tiles_;       // the scans' chain state, zeroed when allocated
+  DevBuf<unsigned long long> ctr_;         // voxels selected, hook attempts lost
+  DevBuf<loamx_segment> acc_;              // one accumulator per component, by compact id
+  DevBuf<unsigned long long> okeys_;       // with labels: the occupied slots' keys in slot order ...
+  DevBuf<uint32_t> oids_;                  // ... and their compact ids (NONE: not selected)
+  PinBuf<uint32_t> h_tot_, h_acc_, h_keys_, h_ids_;
 };
 
 }  // namespace loamx

@@ -1392,6 +1392,60 @@ def grid_cell_of(cfg: GridConfig, leaf: float, x: float, z: float):
     return (rx.value, rz.value) if inside.value else None
 
 
+SEGMENT_NONE = 0xffffffff                                                         # label of a voxel in no kept component
+SEGMENT_ALL, SEGMENT_STATIC, SEGMENT_DYNAMIC = range(3)                           # loamx_densemap_segment_config.which
+
+
+class SegmentConfig(C.Structure):
+    """loamx_densemap_segment_config: which voxels are selected (which, min_points, the inclusive window lo .. hi in voxel indices),
+    how they join (connectivity 6, 18 or 26) and which components are kept (min_voxels).  SegmentConfig() holds the defaults (ALL,
+    26, 1, 1, the whole key range); keyword arguments replace them, lo and hi as triples."""
+    _fields_ = [("which", C.c_uint32), ("connectivity", C.c_uint32), ("min_points", C.c_uint32), ("min_voxels", C.c_uint32),
+                ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
+
+    def __init__(self, **fields):
+        super().__init__()
+        lib().loamx_densemap_segment_default_config(C.byref(self))
+        self.update(**fields)
+
+    def update(self, **fields):
+        for k, v in fields.items():
+            assert hasattr(self, k), k
+            setattr(self, k, (C.c_int32 * 3)(*v) if k in ("lo", "hi") else v)
+        return self
+
+    def copy(self, **fields):
+        c = SegmentConfig()
+        C.memmove(C.byref(c), C.byref(self), C.sizeof(SegmentConfig))
+        return c.update(**fields)
+
+    def check(self):
+        """loamx_densemap_segment_check (host only): LoamxError E_INVALID names the first field out of its bounds"""
+        _check(lib().loamx_densemap_segment_check(C.byref(self)))
+        return self
+
+
+class Segment(C.Structure):
+    """loamx_segment, 72 bytes: min_key (the smallest voxel key of the component, its identity), voxels, points (the sum of their n),
+    the inclusive box lo .. hi in voxel indices and sum_idx, the sum of the indices per axis"""
+    _fields_ = [("min_key", C.c_uint64), ("voxels", C.c_uint64), ("points", C.c_uint64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
+                ("sum_idx", C.c_int64 * 3)]
+
+
+SEGMENT = np.dtype([("min_key", "<u8"), ("voxels", "<u8"), ("points", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3), ("sum_idx", "<i8", 3)])
+SEGMENT_STATS = ("selected", "components", "kept", "kept_voxels", "largest", "hooks_lost")   # stats[6] of loamx_densemap_segment
+
+
+def segment_box(seg, leaf: float):
+    """loamx_segment_box (host only): (lo_m, hi_m, centre), three float32 triples in metres, LOAM frame, of one SEGMENT record: the
+    box of its voxels and the mean of their centres.  LoamxError E_INVALID for a record without voxels."""
+    a = np.ascontiguousarray(seg, SEGMENT).reshape(1)
+    out = np.zeros((3, 3), np.float32)
+    _check(lib().loamx_segment_box(a.ctypes.data_as(C.c_void_p), C.c_float(leaf), out[0].ctypes.data_as(C.c_void_p),
+                                   out[1].ctypes.data_as(C.c_void_p), out[2].ctypes.data_as(C.c_void_p)))
+    return out[0], out[1], out[2]
+
+
 def write_pcd(path: str, points, axes="loam"):
     """loamx_write_pcd: an (N, 4) / (N, 8) float32 cloud as a binary PCD v0.7 file (x y z intensity); axes="sensor" writes the sensor
     axes ingestion started from (x_s = z, y_s = x, z_s = y).  Host only."""
@@ -1797,6 +1851,27 @@ class DenseMap:
     def route_set_batch(self, batch: int):
         """bench hook: the relaxation rounds launched per look at the counters (1..64)"""
         _check(lib().loamx_densemap_route_set_batch(self.h, C.c_uint32(batch)))
+
+    def segment(self, cfg=None, static=None, labels=True, **fields):
+        """loamx_densemap_segment: the connected components of the selected voxels, labelled on the device.  cfg: a SegmentConfig
+        (None: the defaults: every voxel, connectivity 26); fields replace members of a copy of it.  static: the StaticRule that
+        which=SEGMENT_STATIC / SEGMENT_DYNAMIC select by (None: the default rule; needs carving).  Returns (labels, segments,
+        stats): labels one uint32 per voxel in the order of points(), the number of its component or SEGMENT_NONE (None with
+        labels=False); segments the kept components as SEGMENT records in ascending min_key; stats a dict in the order of
+        SEGMENT_STATS.  Blocks; the map is only read."""
+        c = (SegmentConfig() if cfg is None else cfg).copy(**fields).check()
+        n_vox, n_seg = C.c_uint64(len(self) if labels else 0), C.c_uint64(4096)
+        st = (C.c_uint64 * 6)()
+        while True:
+            lab = np.full(max(int(n_vox.value), 1), SEGMENT_NONE, np.uint32) if labels else None
+            segs = np.zeros(max(int(n_seg.value), 1), SEGMENT)
+            rc = lib().loamx_densemap_segment(self.h, C.byref(c), C.byref(static) if static is not None else None,
+                                              lab.ctypes.data_as(C.c_void_p) if labels else None, C.c_uint64(int(n_vox.value)), C.byref(n_vox),
+                                              segs.ctypes.data_as(C.c_void_p), C.c_uint64(int(n_seg.value)), C.byref(n_seg), st)
+            if rc == E_CAPACITY:   # (the counts now hold what is needed)
+                continue
+            _check(rc)
+            return (lab[:int(n_vox.value)] if labels else None), segs[:int(n_seg.value)], dict(zip(SEGMENT_STATS, (int(v) for v in st)))
 
     def save(self, path: str):
         """loamx_densemap_save: every word of the map as an 'LXDM' file (include/loamx.h), written beside path and renamed.  The
