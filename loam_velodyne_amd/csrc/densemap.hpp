@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "densemap_growth.hpp"
+#include "pinned_copy.hpp"
 #include <vector>
 
 namespace loamx {
@@ -13,7 +14,7 @@ constexpr int DM_QBITS = 20;              // fixed-point bits of the offset insi
 constexpr int DM_KBITS = 21;              // bits per axis of the key: i + 2^20, |i| < 2^20
 constexpr float DM_QSCALE = 1048576.f;    // 2^20
 constexpr float DM_IMAX = 1048576.f;      // |i| must stay below this
-constexpr int DM_MOM_WORDS = 9;           // moments: 64-bit words per slot (densemap.hip)
+constexpr int DM_MOM_WORDS = 9;           // moments: 64-bit words per slot (dm_insert_body.inc)
 
 // the key of the voxel (ix, iy, iz), each |i| < 2^20, and its inverse
 __host__ __device__ inline unsigned long long dm_key(int ix, int iy, int iz) {
@@ -106,7 +107,7 @@ __device__ inline unsigned long long dm_hash(unsigned long long key, uint32_t sh
   return (key * 0x9E3779B97F4A7C15ull) >> shift;
 }
 
-// the probe loop of dm_find_or_claim (densemap.hip) without the CAS: 1 the key is at `slot`, 0 it is absent, -1 the probe bound was reached
+// the probe loop of dm_find_or_claim (densemap_dev.hpp) without the CAS: 1 the key is at `slot`, 0 it is absent, -1 the probe bound was reached
 __device__ inline int dm_find(const unsigned long long* keys, uint32_t mask, uint32_t shift, unsigned long long key, uint32_t& slot) {
   uint32_t h = (uint32_t)dm_hash(key, shift);
   for (uint32_t probe = 0; probe <= mask; probe++) {
@@ -163,12 +164,34 @@ class DmFrozen {
   uint32_t slots_ = 0;
   uint64_t count_ = 0;
   DevBuf<unsigned long long> acc_;
-  PinBuf<uint32_t> h_acc_;
+  PinLanding<unsigned long long> h_acc_;
   PinBuf<float4> h_pts_;
   DevBuf<float4> d_pts_;
   PinBuf<float4> h_poses_;
   DevBuf<float4> d_poses_;
   uint64_t stats_[3] = {0, 0, 0};
+};
+
+// Ray casts (include/loamx.h, loamx_densemap_raycast ...; densemap_raycast.hip): the five count words and the records on the device,
+// and the pinned blocks they come back through.  Allocated by the first cast, grow to the largest one; the live map is only read.
+class DmCaster {
+ public:
+  DmCaster() = default;
+  DmCaster(const DmCaster&) = delete;
+  DmCaster& operator=(const DmCaster&) = delete;
+  // n >= 1 rays from origin to pts (readable on st) against the table T under a checked configuration and rule (NULL: every voxel),
+  // enqueued on st: one memset, the kernel (a probe overflow goes to word 3 of map_ctr, the map's counters) and the stores of the
+  // counts and, when want_hits, of the n records.  No wait
+  void enqueue(const DmTable& T, unsigned long long* map_ctr, float inv, double leaf, const float4* pts, uint32_t n, const float origin[3],
+               const loamx_densemap_raycast_config& c, const loamx_densemap_static_rule* rule, bool want_hits, hipStream_t st);
+  // what the last enqueue stored, once the caller has waited for its stream: the five counts and, with out, the n records
+  void results(uint32_t n, loamx_ray_hit* out, uint64_t counts[5]) const;
+
+ private:
+  DevBuf<unsigned long long> rc_;
+  DevBuf<loamx_ray_hit> d_hits_;
+  PinLanding<unsigned long long> h_rc_;
+  PinLanding<loamx_ray_hit> h_hits_;
 };
 
 // Navigation grid (include/loamx.h, loamx_densemap_grid; densemap_grid.hip): the accumulator planes of a window and its records on the
@@ -193,7 +216,7 @@ class DmGrid {
  private:
   DevBuf<uint32_t> planes_;   // DM_GRID_PLANE_WORDS 32-bit words per cell, plane after plane (densemap_grid.hip)
   DevBuf<loamx_grid_cell> cells_;
-  PinBuf<uint32_t> h_cells_;
+  PinLanding<loamx_grid_cell> h_cells_;
 };
 
 // include/loamx.h, loamx_densemap_grid_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
@@ -243,7 +266,8 @@ class DmRoute {
   DevBuf<unsigned long long> st_;       // the four exact stats
   DevBuf<uint32_t> d_xz_, d_len_, d_routes_;   // goals or starts; the routes' lengths; the routes back to back
   DevBuf<unsigned long long> d_off_;           // the first pair of each route in d_routes_
-  PinBuf<uint32_t> h_xz_, h_ctr_, h_field_, h_len_, h_routes_;
+  PinBuf<uint32_t> h_xz_, h_ctr_, h_len_, h_routes_;
+  PinLanding<loamx_route_cell> h_field_;
   PinBuf<unsigned long long> h_off_;
   uint32_t nx_ = 0, nz_ = 0;
   bool valid_ = false;
@@ -276,15 +300,12 @@ class DmSegment {
   DevBuf<loamx_segment> acc_;              // one accumulator per component, by compact id
   DevBuf<unsigned long long> okeys_;       // with labels: the occupied slots' keys in slot order ...
   DevBuf<uint32_t> oids_;                  // ... and their compact ids (NONE: not selected)
-  PinBuf<uint32_t> h_tot_, h_acc_, h_keys_, h_ids_;
+  PinBuf<uint32_t> h_tot_, h_ids_;
+  PinLanding<loamx_segment> h_acc_;
+  PinLanding<unsigned long long> h_keys_;
 };
 
 }  // namespace loamx
-
-// internal accessors of the dense map's handle for densemap_align.hip: its snapshot, its own stream and its configuration
-loamx::DmFrozen& loamx_densemap_frozen(loamx_densemap* h);
-hipStream_t loamx_densemap_own_stream(loamx_densemap* h);
-const loamx_densemap_config& loamx_densemap_cfg(loamx_densemap* h);
 
 // internal accessors (not exported in include/loamx.h): the registered cloud of the mapper's last process() / process_linked(), and of
 // the slot-th stream registered in the pipeline's last step (LOAMX_E_INVALID for a slot beyond them)

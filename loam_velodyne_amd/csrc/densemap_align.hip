@@ -12,8 +12,7 @@
 // k_dm_align_step_many is the same linearisation about many poses at once, a second grid dimension over a table of poses in device
 // memory: one launch and one readback per iteration for all the start poses of loamx_densemap_align_many, which runs the Gauss-Newton
 // loops of its hypotheses in lockstep.  Both kernels compile from one text (dm_align_step_body.inc), so every word equals the single step's.
-#include "densemap.hpp"
-#include "pinned_copy.hpp"
+#include "densemap_map.hpp"
 
 namespace loamx {
 
@@ -158,7 +157,7 @@ void DmFrozen::step(const float4* pts, uint32_t n, const float rtc[15], float in
                     int64_t sums[28], uint64_t counts[5]) {
   LX_REQUIRE(valid(), "nothing is frozen (loamx_densemap_freeze)");
   acc_.reserve(DM_ALIGN_WORDS);
-  h_acc_.reserve(2 * DM_ALIGN_WORDS);
+  h_acc_.reserve(DM_ALIGN_WORDS);
   LX_HIP(hipMemsetAsync(acc_.p, 0, sizeof(unsigned long long) * DM_ALIGN_WORDS, st));
   if (n) {
     DmAlign A;
@@ -172,10 +171,9 @@ void DmFrozen::step(const float4* pts, uint32_t n, const float rtc[15], float in
     stats_[0]++;
     stats_[2]++;
   }
-  store_to_pinned_u32(h_acc_.p, (const uint32_t*)acc_.p, 2 * DM_ALIGN_WORDS, st);
+  const unsigned long long* w = h_acc_.fetch(acc_.p, DM_ALIGN_WORDS, st);
   LX_HIP(hipStreamSynchronize(st));
   stats_[1]++;
-  const unsigned long long* w = (const unsigned long long*)h_acc_.p;
   for (int k = 0; k < DM_ALIGN_SUMS; k++) sums[k] = (int64_t)w[k];
   for (int k = 0; k < DM_ALIGN_COUNTS; k++) counts[k] = w[DM_ALIGN_SUMS + k];
 }
@@ -191,7 +189,7 @@ const unsigned long long* DmFrozen::step_many(const float4* pts, uint32_t n, uin
   LX_REQUIRE(n_poses >= 1u && n_poses <= LOAMX_ALIGN_MAX_POSES && h_poses_.cap >= 4 * (size_t)n_poses, "align: pose table out of range");
   const size_t words = (size_t)DM_ALIGN_WORDS * n_poses;
   acc_.reserve(words);
-  h_acc_.reserve(2 * words);
+  h_acc_.reserve(words);
   LX_HIP(hipMemsetAsync(acc_.p, 0, sizeof(unsigned long long) * words, st));
   if (n) {
     d_poses_.reserve(4 * (size_t)n_poses);
@@ -203,10 +201,10 @@ const unsigned long long* DmFrozen::step_many(const float4* pts, uint32_t n, uin
     stats_[0]++;
     stats_[2] += n_poses;
   }
-  store_to_pinned_u32(h_acc_.p, (const uint32_t*)acc_.p, 2 * words, st);
+  const unsigned long long* w = h_acc_.fetch(acc_.p, words, st);
   LX_HIP(hipStreamSynchronize(st));
   stats_[1]++;
-  return (const unsigned long long*)h_acc_.p;
+  return w;
 }
 
 // Eigen-decomposition of a symmetric 6x6 matrix in double by cyclic Jacobi rotations (host_math.h's jacobi_eig3 at n = 6): a is
@@ -286,8 +284,7 @@ static void rotate_left(double R[9], const double w[3]) {
 }
 
 static loamx_densemap_align_config checked_align_config(const loamx_densemap_align_config* cfg, float leaf) {
-  loamx_densemap_align_config c;
-  if (cfg) c = *cfg; else loamx_densemap_align_default_config(&c);
+  loamx_densemap_align_config c = or_default(cfg, loamx_densemap_align_default_config);
   LX_REQUIRE(c.max_iterations >= 1u && c.max_iterations <= 1000u, "max_iterations must be in [1, 1000]");
   LX_REQUIRE(c.neighbourhood <= 1u, "neighbourhood must be 0 or 1");
   if (c.max_residual == 0.f) c.max_residual = leaf;
@@ -350,8 +347,8 @@ static int align_loop(loamx_densemap* h, const float4* pts, uint32_t n, const do
   const double cc[3] = {centre ? (double)centre[0] : 0.0, centre ? (double)centre[1] : 0.0, centre ? (double)centre[2] : 0.0};
   AlignHyp hyp;
   hyp.begin(pose_in, cc, out);
-  DmFrozen& F = loamx_densemap_frozen(h);
-  const float inv = 1.0f / loamx_densemap_cfg(h).leaf;
+  DmFrozen& F = h->d.frozen;
+  const float inv = 1.0f / h->d.cfg.leaf;
   for (uint32_t it = 0; it < c.max_iterations; it++) {
     float rtc[15];
     hyp.rtc(cc, rtc);
@@ -384,8 +381,8 @@ static int align_many_loop(loamx_densemap* h, const float4* pts, uint32_t n, con
     hyp[k].begin(poses_in ? poses_in + 12 * (size_t)k : nullptr, cc, out + k);
     active[k] = k;
   }
-  DmFrozen& F = loamx_densemap_frozen(h);
-  const float inv = 1.0f / loamx_densemap_cfg(h).leaf;
+  DmFrozen& F = h->d.frozen;
+  const float inv = 1.0f / h->d.cfg.leaf;
   for (uint32_t it = 0; it < c.max_iterations && !active.empty(); it++) {
     const uint32_t n_active = (uint32_t)active.size();
     float* table = F.pose_table(n_active);
@@ -412,13 +409,13 @@ static int align_many_loop(loamx_densemap* h, const float4* pts, uint32_t n, con
 // the cloud of a mapper / a pipeline where it lies: the handle's own stream runs behind the stream that wrote it.  false: no cloud
 static bool align_source_ready(loamx_densemap* h, const DenseSource& s, const loamx_densemap_align_config* cfg, loamx_densemap_align_config& c,
                                hipStream_t& st) {
-  const loamx_densemap_config& mc = loamx_densemap_cfg(h);
+  const loamx_densemap_config& mc = h->d.cfg;
   LX_REQUIRE(s.device == mc.device, "the dense map and its source live on different devices");
   c = checked_align_config(cfg, mc.leaf);
-  LX_REQUIRE(loamx_densemap_frozen(h).valid(), "nothing is frozen (loamx_densemap_freeze)");
+  LX_REQUIRE(h->d.frozen.valid(), "nothing is frozen (loamx_densemap_freeze)");
   if (!s.has_cloud) return false;
   LX_HIP(hipSetDevice(mc.device));
-  st = loamx_densemap_own_stream(h);
+  st = h->d.own_stream();
   dm_stream_behind(st, s.stream);
   return true;
 }
@@ -486,11 +483,11 @@ int loamx_densemap_align_step(loamx_densemap* h, const loamx_cloud* points, cons
     LX_REQUIRE(h && points && rtc && sums && counts, "NULL argument");
     LX_REQUIRE(neighbourhood <= 1u, "neighbourhood must be 0 or 1");
     LX_REQUIRE(max_residual > 0.f && max_residual <= 16.f, "max_residual must be in (0, 16]");   // (NaN too)
-    DmFrozen& F = loamx_densemap_frozen(h);
+    DmFrozen& F = h->d.frozen;
     LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
-    const loamx_densemap_config& mc = loamx_densemap_cfg(h);
+    const loamx_densemap_config& mc = h->d.cfg;
     LX_HIP(hipSetDevice(mc.device));
-    hipStream_t st = loamx_densemap_own_stream(h);
+    hipStream_t st = h->d.own_stream();
     const float4* pts = F.stage(points, st);
     F.step(pts, points->count, rtc, 1.0f / mc.leaf, neighbourhood, max_residual, st, sums, counts);
     return LOAMX_OK;
@@ -501,12 +498,12 @@ int loamx_densemap_align(loamx_densemap* h, const loamx_cloud* points, const dou
                          const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out) {
   return guard([&]() {
     LX_REQUIRE(h && points && pose_in && out, "NULL argument");
-    const loamx_densemap_config& mc = loamx_densemap_cfg(h);
+    const loamx_densemap_config& mc = h->d.cfg;
     const loamx_densemap_align_config c = checked_align_config(cfg, mc.leaf);
-    DmFrozen& F = loamx_densemap_frozen(h);
+    DmFrozen& F = h->d.frozen;
     LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
     LX_HIP(hipSetDevice(mc.device));
-    hipStream_t st = loamx_densemap_own_stream(h);
+    hipStream_t st = h->d.own_stream();
     const float4* pts = F.stage(points, st);
     return align_loop(h, pts, points->count, pose_in, centre, c, st, out);
   });
@@ -523,11 +520,11 @@ int loamx_densemap_align_step_many(loamx_densemap* h, const loamx_cloud* points,
     LX_REQUIRE(n_poses >= 1u && n_poses <= LOAMX_ALIGN_MAX_POSES, "n_poses must be in [1, LOAMX_ALIGN_MAX_POSES]");
     LX_REQUIRE(neighbourhood <= 1u, "neighbourhood must be 0 or 1");
     LX_REQUIRE(max_residual > 0.f && max_residual <= 16.f, "max_residual must be in (0, 16]");   // (NaN too)
-    DmFrozen& F = loamx_densemap_frozen(h);
+    DmFrozen& F = h->d.frozen;
     LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
-    const loamx_densemap_config& mc = loamx_densemap_cfg(h);
+    const loamx_densemap_config& mc = h->d.cfg;
     LX_HIP(hipSetDevice(mc.device));
-    hipStream_t st = loamx_densemap_own_stream(h);
+    hipStream_t st = h->d.own_stream();
     const float4* pts = F.stage(points, st);
     float* table = F.pose_table(n_poses);
     for (uint32_t k = 0; k < n_poses; k++) {
@@ -551,12 +548,12 @@ int loamx_densemap_align_many(loamx_densemap* h, const loamx_cloud* points, cons
     not_null(poses_in, "poses_in");
     not_null(out, "out");
     check_start_poses(poses_in, n_poses, false);
-    const loamx_densemap_config& mc = loamx_densemap_cfg(h);
+    const loamx_densemap_config& mc = h->d.cfg;
     const loamx_densemap_align_config c = checked_align_config(cfg, mc.leaf);
-    DmFrozen& F = loamx_densemap_frozen(h);
+    DmFrozen& F = h->d.frozen;
     LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
     LX_HIP(hipSetDevice(mc.device));
-    hipStream_t st = loamx_densemap_own_stream(h);
+    hipStream_t st = h->d.own_stream();
     const float4* pts = F.stage(points, st);
     return align_many_loop(h, pts, points->count, poses_in, n_poses, centre, c, st, out, best);
   });
@@ -599,7 +596,7 @@ int loamx_densemap_get_align_stats(loamx_densemap* h, uint64_t stats[3]) {
   return guard([&]() {
     not_null(h, "h");
     not_null(stats, "stats");
-    const uint64_t* s = loamx_densemap_frozen(h).stats();
+    const uint64_t* s = h->d.frozen.stats();
     for (int k = 0; k < 3; k++) stats[k] = s[k];
     return LOAMX_OK;
   });

@@ -1,5 +1,5 @@
 // The dense map's file ('LXDM', include/loamx.h: loamx_densemap_save and what follows it): reader, writer and validator.  No HIP in
-// here: densemap.hip includes it for save / load / merge_file / file_info, and tests/densemap_file_driver.cpp drives it on a CPU under
+// here: densemap_merge.hip includes it for save / load / merge_file / file_info, and tests/densemap_file_driver.cpp drives it on a CPU under
 // the sanitizers.
 //
 // The reader takes untrusted bytes.  Its order of work is what keeps it safe: the 128 header bytes are read and checked first; the size

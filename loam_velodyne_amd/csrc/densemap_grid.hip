@@ -7,7 +7,7 @@
 // separable form.  Integer atomics only, so no word depends on the schedule; the one f32 rounding is the elevation's.
 //
 // The planes are zeroed by the one memset, so the two minima are kept as iy - 2^20: always negative, 0 = no voxel yet.
-#include "densemap.hpp"
+#include "densemap_map.hpp"
 #include "pinned_copy.hpp"
 #include <climits>
 
@@ -189,11 +189,9 @@ const loamx_grid_cell* DmGrid::enqueue(const DmTable& T, const loamx_densemap_gr
 }
 
 const loamx_grid_cell* DmGrid::fetch(const loamx_grid_cell* d_cells, size_t n, hipStream_t st) {
-  constexpr size_t CELL_WORDS = sizeof(loamx_grid_cell) / sizeof(uint32_t);
-  h_cells_.reserve(CELL_WORDS * n);
-  store_to_pinned_u32(h_cells_.p, (const uint32_t*)d_cells, CELL_WORDS * n, st);
+  const loamx_grid_cell* cells = h_cells_.fetch(d_cells, n, st);
   LX_HIP(hipStreamSynchronize(st));
-  return (const loamx_grid_cell*)h_cells_.p;
+  return cells;
 }
 
 void dm_grid_check(const loamx_densemap_grid_config& c) {
@@ -222,6 +220,14 @@ static void grid_window_axis(double e, float centre, float half, const char* fir
 
 static unsigned char grid_pixel(uint32_t cls) { return cls == LOAMX_GRID_UNKNOWN ? 205 : (cls == LOAMX_GRID_FREE ? 254 : 0); }
 
+// include/loamx.h, loamx_densemap_grid
+void DenseMap::grid(const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, loamx_grid_cell* out) {
+  LX_HIP(hipSetDevice(cfg.device));
+  wait_adds();
+  const loamx_grid_cell* cells = grid_.run(tab_, c, rule, (double)cfg.leaf, own_);
+  memcpy(out, cells, sizeof(loamx_grid_cell) * (size_t)c.nx * c.nz);
+}
+
 }  // namespace loamx
 
 using namespace loamx;
@@ -248,6 +254,19 @@ int loamx_densemap_grid_check(const loamx_densemap_grid_config* cfg) {
   return guard([&]() {
     LX_REQUIRE(cfg, "cfg is NULL");
     dm_grid_check(*cfg);
+    return LOAMX_OK;
+  });
+}
+
+int loamx_densemap_grid(loamx_densemap* h, const loamx_densemap_grid_config* cfg, const loamx_densemap_static_rule* rule,
+                        loamx_grid_cell* out) {
+  return guard([&]() {
+    LX_REQUIRE(h, "h is NULL");
+    LX_REQUIRE(out, "out is NULL");
+    const loamx_densemap_grid_config c = or_default(cfg, loamx_densemap_grid_default_config);
+    dm_grid_check(c);
+    checked_optional_rule(h, rule);
+    h->d.grid(c, rule, out);
     return LOAMX_OK;
   });
 }

@@ -1,4 +1,4 @@
-// The dense map's sweep log and rebuild rule (densemap.hip; include/loamx.h, loamx_densemap_enable_history / loamx_densemap_rebuild).
+// The dense map's sweep log and rebuild rule (densemap_rebuild.hip, and densemap.hip for the adds; include/loamx.h, loamx_densemap_enable_history / loamx_densemap_rebuild).
 // Standard library only: tests/test_densemap_history_cpu.py drives it on a CPU; the two inline functions that the kernels share are
 // marked for the device only under hipcc.
 //

@@ -1,0 +1,198 @@
+// The dense map's handle (include/loamx.h, loamx_densemap): DenseMap, declarations and members only.  Each member is defined in the
+// file of its feature, named beside it; the C entry points of a feature are in the same file and reach the map through h->d.
+#pragma once
+#include "densemap.hpp"
+#include "densemap_history.hpp"
+#include <type_traits>
+
+namespace loamx {
+
+struct DmFilter;   // densemap_dev.hpp
+struct DmCarve;
+struct DmCtrAdd;   // densemap_merge.hip
+
+// two runtime booleans as the two std::bool_constant arguments of f: the kernels' feature switches are template parameters
+template <class F> static void dm_dispatch2(bool a, bool b, F&& f) {
+  if (a) { if (b) f(std::true_type(), std::true_type()); else f(std::true_type(), std::false_type()); }
+  else { if (b) f(std::false_type(), std::true_type()); else f(std::false_type(), std::false_type()); }
+}
+
+class DenseMap {
+ public:
+  // ---- densemap.hip: the table, its counters, adds, growth and admission
+  explicit DenseMap(const loamx_densemap_config& c);
+  ~DenseMap();
+  loamx_densemap_config cfg;
+  int add_host(const loamx_cloud* c, const float origin[3]);
+  int add_device(const DenseSource& s);
+  // [voxels, slots, offered, added, dropped by range, dropped by key]
+  void stats(uint64_t out[6]);
+  // the occupied slots on the host: keys, values, (carving) miss words and (on request, moments) the nine moment words, and idx =
+  // their ascending key order
+  struct Snapshot {
+    std::vector<unsigned long long> k, v, mom;
+    std::vector<uint32_t> miss, idx;
+  };
+  void snapshot(Snapshot& S, bool want_mom = false);
+  // the voxels of a snapshot in ascending key order, without those a rule (NULL: none) calls dynamic: f(j, ia) with j the voxel's
+  // place in S.k (4 * j in S.v, 9 * j in S.mom) and ia its indices
+  template <class F> static void for_each_voxel(const Snapshot& S, const loamx_densemap_static_rule* rule, F&& f) {
+    for (size_t r = 0; r < S.idx.size(); r++) {
+      const size_t j = S.idx[r];
+      if (rule && dm_dynamic(*rule, S.v[4 * j], S.miss[j])) continue;
+      long long ia[3];
+      dm_key_indices(S.k[j], ia);
+      f(j, ia);
+    }
+  }
+  bool moments() const { return tab_.mom != nullptr; }
+  bool carving() const { return tab_.aux != nullptr; }
+  // both: allowed while nothing has been offered since creation / reset; the handle is unchanged when refused
+  void enable_moments();
+  void enable_carving(const loamx_densemap_carve_config& c);
+  // [rays traced, not traced by stride, by range, by steps or origin key, cells visited, misses recorded]
+  void carve_stats(uint64_t out[6]);
+  // the dynamic voxels leave the table: a rehash with the rule as predicate into a fresh table of the same size
+  uint64_t prune(const loamx_densemap_static_rule& rule);
+  void reset();
+  hipStream_t own_stream() const { return own_; }
+  bool combine = true;   // (bench A/B: the in-wave combining of equal keys)
+  uint64_t rehashes = 0;
+
+  // ---- densemap_export.hip: the voxels on the host.  records: axes 0: LOAM frame, 1: sensor axes, ascending key order; with a rule,
+  // without the voxels it calls dynamic.  misses, moment_words, surfels: in the order of records()
+  void records(std::vector<float4>& out, int axes, const loamx_densemap_static_rule* rule = nullptr);
+  void misses(std::vector<uint32_t>& out);
+  void moment_words(std::vector<unsigned long long>& out);
+  void surfels(std::vector<loamx_surfel>& out, int axes, const loamx_densemap_surfel_config& sc, const loamx_densemap_static_rule* rule);
+  // the snapshot the alignment reads (densemap_align.hip): the voxels that have a surfel and that the rule does not call dynamic, each
+  // under its key of the table, with the six f32 of its record as surfels() gives them in axes 0.  Replaces an earlier snapshot
+  uint64_t freeze(const loamx_densemap_surfel_config& sc, const loamx_densemap_static_rule* rule);
+  DmFrozen frozen;
+
+  // ---- densemap_merge.hip: include/loamx.h, loamx_densemap_save / merge / merge_file and, with `loading`, load
+  uint32_t flags() const;   // the features of the handle as the file's flags
+  void save(const char* path);
+  int merge(DenseMap& src);
+  int merge_file(const char* path, bool loading);
+
+  // ---- densemap_raycast.hip: include/loamx.h, loamx_densemap_raycast (the ends staged from the host) and its from_* forms (the
+  // registered cloud where it lies)
+  int raycast_host(const loamx_cloud* ends, const float origin[3], const loamx_densemap_raycast_config& c,
+                   const loamx_densemap_static_rule* rule, loamx_ray_hit* out, uint64_t capacity, uint64_t counts[5]);
+  int raycast_device(const DenseSource& s, const loamx_densemap_raycast_config& c, const loamx_densemap_static_rule* rule,
+                     loamx_ray_hit* out, uint64_t capacity, uint64_t counts[5]);
+
+  // ---- densemap_rebuild.hip: the sweep log and its replay (include/loamx.h, loamx_densemap_enable_history ... rebuild)
+  void enable_history(const loamx_densemap_history_config& c);
+  bool history() const { return history_; }
+  void history_size(uint64_t* calls, uint64_t* points) const { *calls = hist_.calls.size(); *points = hist_.points; }
+  int history_download(uint64_t call, loamx_cloud* out, float origin[3]);
+  int rebuild(const double* corrections, uint64_t n_calls);
+  void rebuild_stats(uint64_t out[4]) const { for (int k = 0; k < 4; k++) out[k] = rebuild_stats_[k]; }
+
+  // ---- densemap_grid.hip, densemap_route.hip, densemap_segment.hip: checked configurations, a checked rule or none; the table is
+  // only read, and the outputs are written last, all or none
+  void grid(const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, loamx_grid_cell* out);
+  void route(const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, const loamx_grid_route_config& rc,
+             const uint32_t* goals_xz, uint32_t n_goals, loamx_grid_cell* out_cells, loamx_route_cell* out_field, uint64_t stats[6]);
+  void route_cells(const loamx_grid_cell* cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config& rc, const uint32_t* goals_xz,
+                   uint32_t n_goals, loamx_route_cell* out_field, uint64_t stats[6]);
+  void route_trace(const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity, uint32_t* lengths);
+  DmRoute& router() { return route_; }
+  int segment(const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint32_t* labels, uint64_t label_capacity,
+              uint64_t* n_voxels, loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[6]);
+
+ private:
+  // the table and its counters
+  DmTable tab_;   // (aux NULL: carving is off; mom NULL: moments are off)
+  float inv_ = 10.f;
+  DevBuf<unsigned long long> ctr_;
+  PinLanding<unsigned long long> h_ctr_, h_snap_;
+  DmOccupancy occ_;   // the bound of the occupancy that growth and admission are decided on (densemap_growth.hpp)
+  uint64_t offered_ = 0, drop_range_ = 0, drop_key_ = 0;
+  std::vector<void*> graveyard_;   // tables replaced by a rehash: freed at the next point where the host waits anyway
+  // adds
+  hipStream_t own_ = nullptr;      // host-fed adds, rehash of those, exports
+  hipStream_t last_st_ = nullptr;  // the stream of the last enqueued add (ev_last_ recorded behind it)
+  hipEvent_t ev_last_ = nullptr, ev_snap_ = nullptr, ev_staged_ = nullptr;
+  bool staged_pending_ = false;
+  PinBuf<float4> h_stage_;
+  DevBuf<float4> d_stage_;
+  // carving
+  loamx_densemap_carve_config carve_ = {0.f, 1u, 1u, 4096u};
+  uint32_t seq_ = 0;          // sequence number of the last add call (stamp values; 0 = never stamped)
+  uint64_t carve_ctr_[6] = {0, 0, 0, 0, 0, 0};
+  // the sweep log (densemap_history.hpp): off unless enabled; hist_ then admits everything and log_ stays NULL
+  bool history_ = false;
+  DmHistory hist_;
+  float4* log_ = nullptr;
+  PinBuf<DmReplayCall> h_calls_;
+  DevBuf<DmReplayCall> d_calls_;
+  PinLanding<unsigned long long> h_rb_;
+  uint64_t rebuild_stats_[4] = {0, 0, 0, 0};
+  // the features that only read the table, each with its own buffers, allocated by its first call
+  DmCaster caster_;   // densemap_raycast.hip
+  DmGrid grid_;       // densemap_grid.hip
+  DmRoute route_;     // densemap_route.hip
+  DmSegment seg_;     // densemap_segment.hip
+
+  // ---- densemap.hip
+  DmFilter filter_for(const float origin[3]) const;   // the insert's filter about an origin
+  DmCarve carve_args(uint32_t seq) const;             // the ray kernel's arguments for the call with that stamp
+  void replace_table(DmTable& nt);   // nt becomes the map's table; the one it replaces goes to the graveyard
+  template <bool PRUNE> void launch_rehash(hipStream_t st, const DmTable& nt, const loamx_densemap_static_rule& rule);
+  template <bool STAMP> void launch_insert(hipStream_t st, const float4* pts, uint32_t n, const DmFilter& F, uint32_t seq);
+  void clear(hipStream_t st);        // the table and the counters (the one place that zeroes both)
+  void free_graveyard();
+  void order_behind(hipStream_t st);   // st runs behind every add enqueued so far (on whichever stream)
+  void wait_adds();
+  void read_counters();   // exact counters, after every add
+  void poll_snapshot();   // the occupancy snapshot that has landed, if any
+  bool admit(uint32_t n);
+  void grow_for(uint64_t n, hipStream_t st);
+  void enqueue_add(const float4* pts, uint32_t n, const float origin[3], hipStream_t st);
+  // ---- densemap_merge.hip
+  void merge_records(const unsigned long long* skeys, const unsigned long long* svals, uint32_t sn, uint64_t s_occ, const uint32_t* smiss,
+                     uint32_t miss_stride, const unsigned long long* smom, const DmCtrAdd& add, uint64_t s_offered);
+  // ---- densemap_raycast.hip
+  void cast(const float4* pts, uint32_t n, const float origin[3], const loamx_densemap_raycast_config& c,
+            const loamx_densemap_static_rule* rule, loamx_ray_hit* out, uint64_t counts[5]);
+  // ---- densemap_rebuild.hip
+  void log_reserve(uint64_t n, hipStream_t st);
+  void launch_replay(const DmTable& nt, unsigned long long* nctr);
+};
+
+}  // namespace loamx
+
+struct loamx_densemap {
+  loamx::DenseMap d;
+  explicit loamx_densemap(const loamx_densemap_config& c) : d(c) {}
+};
+
+namespace loamx {
+
+// ---- what the C entry points of more than one file share
+
+// *cfg, or what its default function fills in
+template <class C> C or_default(const C* cfg, void (*default_fn)(C*)) {
+  C c;
+  if (cfg) c = *cfg; else default_fn(&c);
+  return c;
+}
+// the rule of a call, checked (NULL: the default rule)
+inline loamx_densemap_static_rule checked_rule(const loamx_densemap_static_rule* rule) {
+  const loamx_densemap_static_rule r = or_default(rule, loamx_densemap_static_rule_default);
+  LX_REQUIRE(r.den != 0u, "the rule's den must not be 0");
+  return r;
+}
+#define LX_REQUIRE_CARVING(h) LX_REQUIRE((h)->d.carving(), "carving is not enabled")
+// the optional rule of a ray cast, a grid or a route, checked where it lies: NULL is every voxel; a rule needs carving.  (The exports'
+// helper of this name with a third argument, densemap_export.hip, hands a checked copy on and has a message of its own)
+inline void checked_optional_rule(loamx_densemap* h, const loamx_densemap_static_rule* rule) {
+  if (!rule) return;
+  LX_REQUIRE(rule->den != 0u, "the rule's den must not be 0");
+  LX_REQUIRE(h->d.carving(), "a rule needs carving, which is not enabled");
+}
+
+}  // namespace loamx

@@ -20,7 +20,7 @@
 // marked and changes nothing, and no later round runs a tile: at most M + 2 rounds run a tile, M < nx * nz.
 // Inside LDS a sweep lowers at least the next cell of every unfinished cheapest path, so 32 * 32 sweeps and one that finds nothing
 // bound the loop; the bound is in the code, and a tile that ever left it unsettled would mark itself.
-#include "densemap.hpp"
+#include "densemap_map.hpp"
 #include "densemap_route_schedule.hpp"
 #include "pinned_copy.hpp"
 
@@ -272,7 +272,7 @@ const loamx_route_cell* DmRoute::run(const loamx_grid_cell* d_cells, uint32_t nx
   d_xz_.reserve(2 * DM_ROUTE_MAX_XZ);
   h_xz_.reserve(2 * DM_ROUTE_MAX_XZ);
   h_ctr_.reserve(CTR_WORDS + ST_WORDS);
-  if (want_field) h_field_.reserve(2 * (size_t)n);
+  if (want_field) h_field_.reserve(n);
   memcpy(h_xz_.p, goals_xz, sizeof(uint32_t) * 2 * n_goals);
   LX_HIP(hipMemcpyAsync(d_xz_.p, h_xz_.p, sizeof(uint32_t) * 2 * n_goals, hipMemcpyHostToDevice, st));
   LX_HIP(hipMemsetAsync(dirty_.p, 0, sizeof(uint32_t) * 2 * (size_t)tiles, st));
@@ -306,7 +306,7 @@ const loamx_route_cell* DmRoute::run(const loamx_grid_cell* d_cells, uint32_t nx
   hipLaunchKernelGGL(k_dm_route_next, per_cell, dim3(256), 0, st, nx, nz, diag, w_.p, cost_.p, field_.p, st_.p);
   LX_HIP(hipGetLastError());
   store_to_pinned_u32(h_ctr_.p + CTR_WORDS, (const uint32_t*)st_.p, ST_WORDS, st);
-  if (want_field) store_to_pinned_u32(h_field_.p, (const uint32_t*)field_.p, 2 * (size_t)n, st);
+  if (want_field) h_field_.fetch(field_.p, n, st);
   LX_HIP(hipStreamSynchronize(st));
   uint64_t s4[4];
   memcpy(s4, h_ctr_.p + CTR_WORDS, sizeof(s4));
@@ -317,7 +317,7 @@ const loamx_route_cell* DmRoute::run(const loamx_grid_cell* d_cells, uint32_t nx
   nx_ = nx;
   nz_ = nz;
   valid_ = true;
-  return want_field ? (const loamx_route_cell*)h_field_.p : nullptr;
+  return want_field ? h_field_.data() : nullptr;
 }
 
 void DmRoute::trace(const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity, uint32_t* lengths, hipStream_t st) {
@@ -358,6 +358,48 @@ void DmRoute::trace(const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_
   }
 }
 
+// include/loamx.h, loamx_densemap_route: the grid's kernels as grid() runs them, the route on their records where they lie
+void DenseMap::route(const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, const loamx_grid_route_config& rc,
+                     const uint32_t* goals_xz, uint32_t n_goals, loamx_grid_cell* out_cells, loamx_route_cell* out_field, uint64_t stats[6]) {
+  LX_HIP(hipSetDevice(cfg.device));
+  wait_adds();
+  const size_t n = (size_t)c.nx * c.nz;
+  const loamx_grid_cell* d_cells = grid_.enqueue(tab_, c, rule, (double)cfg.leaf, own_);
+  uint64_t s[6];
+  const loamx_route_cell* field = route_.run(d_cells, c.nx, c.nz, rc, goals_xz, n_goals, out_field != nullptr, s, own_);
+  const loamx_grid_cell* cells = out_cells ? grid_.fetch(d_cells, n, own_) : nullptr;
+  if (out_cells) memcpy(out_cells, cells, sizeof(loamx_grid_cell) * n);
+  if (out_field) memcpy(out_field, field, sizeof(loamx_route_cell) * n);
+  if (stats) memcpy(stats, s, sizeof(s));
+}
+// loamx_densemap_route_cells: the same on the caller's records (every cls checked), in a buffer of the route's own
+void DenseMap::route_cells(const loamx_grid_cell* cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config& rc, const uint32_t* goals_xz,
+                           uint32_t n_goals, loamx_route_cell* out_field, uint64_t stats[6]) {
+  LX_HIP(hipSetDevice(cfg.device));
+  wait_adds();
+  const size_t n = (size_t)nx * nz;
+  uint64_t s[6];
+  const loamx_route_cell* field = route_.run(route_.upload(cells, n, own_), nx, nz, rc, goals_xz, n_goals, out_field != nullptr, s, own_);
+  if (out_field) memcpy(out_field, field, sizeof(loamx_route_cell) * n);
+  if (stats) memcpy(stats, s, sizeof(s));
+}
+void DenseMap::route_trace(const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity, uint32_t* lengths) {
+  LX_REQUIRE(route_.has_field(), "the handle has no field yet (loamx_densemap_route, loamx_densemap_route_cells)");
+  LX_HIP(hipSetDevice(cfg.device));
+  route_.trace(starts_xz, n_starts, out_xz, capacity, lengths, own_);
+}
+
+// the checks the route's entry points share: the configuration (NULL: the defaults), the goals and the window's size
+static loamx_grid_route_config checked_route(const loamx_grid_route_config* cfg, const uint32_t* goals_xz, uint32_t n_goals, uint32_t nx,
+                                             uint32_t nz) {
+  const loamx_grid_route_config rc = or_default(cfg, loamx_grid_route_default_config);
+  dm_route_check(rc);
+  LX_REQUIRE(goals_xz, "goals_xz is NULL");
+  LX_REQUIRE(n_goals >= 1u && n_goals <= 4096u, "n_goals must be in [1, 4096]");
+  LX_REQUIRE(nx >= 1u && nz >= 1u && (uint64_t)nx * nz <= (1ull << 22), "nx * nz must be in [1, 2^22] for a route");
+  return rc;
+}
+
 }  // namespace loamx
 
 using namespace loamx;
@@ -389,6 +431,57 @@ int loamx_grid_route_weight(const loamx_grid_cell* cell, const loamx_grid_route_
     return (int)dm_route_weight(cell->cls, cell->clear2, *cfg);
   });
 }
+
+int loamx_densemap_route(loamx_densemap* h, const loamx_densemap_grid_config* grid_cfg, const loamx_densemap_static_rule* rule,
+                         const loamx_grid_route_config* cfg, const uint32_t* goals_xz, uint32_t n_goals, loamx_grid_cell* out_cells,
+                         loamx_route_cell* out_field, uint64_t stats[6]) {
+  return guard([&]() {
+    LX_REQUIRE(h, "h is NULL");
+    const loamx_densemap_grid_config c = or_default(grid_cfg, loamx_densemap_grid_default_config);
+    dm_grid_check(c);
+    checked_optional_rule(h, rule);
+    const loamx_grid_route_config rc = checked_route(cfg, goals_xz, n_goals, c.nx, c.nz);
+    h->d.route(c, rule, rc, goals_xz, n_goals, out_cells, out_field, stats);
+    return LOAMX_OK;
+  });
+}
+
+int loamx_densemap_route_cells(loamx_densemap* h, const loamx_grid_cell* cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config* cfg,
+                               const uint32_t* goals_xz, uint32_t n_goals, loamx_route_cell* out_field, uint64_t stats[6]) {
+  return guard([&]() {
+    LX_REQUIRE(h, "h is NULL");
+    LX_REQUIRE(cells, "cells is NULL");
+    const loamx_grid_route_config rc = checked_route(cfg, goals_xz, n_goals, nx, nz);
+    for (size_t i = 0; i < (size_t)nx * nz; i++)
+      LX_REQUIRE(cells[i].cls <= LOAMX_GRID_STEP, "cells: the cls of record " + std::to_string(i) + " is not a class");
+    h->d.route_cells(cells, nx, nz, rc, goals_xz, n_goals, out_field, stats);
+    return LOAMX_OK;
+  });
+}
+
+int loamx_densemap_route_trace(loamx_densemap* h, const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity,
+                               uint32_t* lengths) {
+  return guard([&]() {
+    LX_REQUIRE(h, "h is NULL");
+    LX_REQUIRE(starts_xz, "starts_xz is NULL");
+    LX_REQUIRE(n_starts >= 1u && n_starts <= 4096u, "n_starts must be in [1, 4096]");
+    LX_REQUIRE(out_xz || !capacity, "out_xz is NULL");
+    LX_REQUIRE(lengths, "lengths is NULL");
+    h->d.route_trace(starts_xz, n_starts, out_xz, capacity, lengths);
+    return LOAMX_OK;
+  });
+}
+
+// bench / test hooks (not in include/loamx.h): the route's rounds per look (1..64), and the rounds of the last route in which a tile ran
+int loamx_densemap_route_set_batch(loamx_densemap* h, uint32_t batch) {
+  return guard([&]() {
+    LX_REQUIRE(h, "NULL handle");
+    LX_REQUIRE(batch >= 1u && batch <= 64u, "batch must be in [1, 64]");
+    h->d.router().batch = batch;
+    return LOAMX_OK;
+  });
+}
+uint64_t loamx_densemap_route_active_rounds(loamx_densemap* h) { return h ? h->d.router().active_rounds : 0; }
 
 int loamx_grid_route_trace(const loamx_route_cell* field, uint32_t nx, uint32_t nz, uint32_t start_x, uint32_t start_z, uint32_t* out_xz,
                            uint32_t capacity, uint32_t* length) {

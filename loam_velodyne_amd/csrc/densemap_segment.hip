@@ -29,7 +29,7 @@
 //
 // The host orders the results, as loamx_densemap_download does: components by min_key, voxels by key; it applies min_voxels, maps compact
 // ids to ranks and fills the labels.  Compact ids follow the slot layout and never leave this file.
-#include "densemap.hpp"
+#include "densemap_map.hpp"
 #include "pinned_copy.hpp"
 #include "scan.hpp"
 #include <algorithm>
@@ -259,7 +259,6 @@ __global__ __launch_bounds__(256) void k_dm_seg_reduce(const unsigned long long*
 
 void DmSegment::run(const DmTable& T, const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint64_t occ,
                     bool want_labels, std::vector<uint32_t>& labels, std::vector<loamx_segment>& segs, uint64_t stats[6], hipStream_t st) {
-  constexpr size_t SEG_WORDS = sizeof(loamx_segment) / sizeof(uint32_t);
   const uint32_t slots = T.slots, nblk = (slots + 255u) / 256u;
   parent_.reserve(slots);
   rootid_.reserve(slots);
@@ -306,19 +305,17 @@ void DmSegment::run(const DmTable& T, const loamx_densemap_segment_config& c, co
       hipLaunchKernelGGL(k_dm_seg_reduce<false>, scan, block, 0, st, T.keys, T.vals, slots, parent_.p, rootid_.p, n_roots, acc_.p, blk_occ,
                          (uint32_t)occ, okeys_.p, oids_.p);
     LX_HIP(hipGetLastError());
-    h_acc_.reserve(SEG_WORDS * (size_t)n_roots);
-    store_to_pinned_u32(h_acc_.p, (const uint32_t*)acc_.p, SEG_WORDS * (size_t)n_roots, st);
+    h_acc_.fetch(acc_.p, n_roots, st);
     if (want_labels) {
-      h_keys_.reserve(2 * (size_t)occ);
       h_ids_.reserve(occ);
-      store_to_pinned_u32(h_keys_.p, (const uint32_t*)okeys_.p, 2 * (size_t)occ, st);
+      h_keys_.fetch(okeys_.p, occ, st);
       store_to_pinned_u32(h_ids_.p, oids_.p, occ, st);
     }
     LX_HIP(hipStreamSynchronize(st));
   }
 
   // the host's half: components by min_key, min_voxels, ranks; voxels by key
-  const loamx_segment* all = (const loamx_segment*)h_acc_.p;
+  const loamx_segment* all = h_acc_.data();
   std::vector<uint32_t> order(n_roots), rank(n_roots, DM_SEG_NONE);
   std::iota(order.begin(), order.end(), 0u);
   std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return all[a].min_key < all[b].min_key; });
@@ -335,7 +332,7 @@ void DmSegment::run(const DmTable& T, const loamx_densemap_segment_config& c, co
   if (total != selected) throw Error(LOAMX_E_INTERNAL, "segment: the components do not add up to the selected voxels");
   labels.clear();
   if (want_labels) {
-    const unsigned long long* k = (const unsigned long long*)h_keys_.p;
+    const unsigned long long* k = h_keys_.data();
     std::vector<std::pair<unsigned long long, uint32_t>> kv(occ);   // (key, label): sorted as records, the keys are distinct
     for (size_t j = 0; j < kv.size(); j++) {
       const uint32_t id = h_ids_.p[j];
@@ -362,6 +359,24 @@ void dm_segment_check(const loamx_densemap_segment_config& c) {
   }
 }
 
+// include/loamx.h, loamx_densemap_segment: a checked configuration and rule.  LOAMX_E_CAPACITY: only the two counts are written
+int DenseMap::segment(const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint32_t* labels, uint64_t label_capacity,
+                      uint64_t* n_voxels, loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[6]) {
+  read_counters();   // (waits for every add; the exact voxel count)
+  const uint64_t occ = occ_.occ;
+  std::vector<uint32_t> lab;
+  std::vector<loamx_segment> sg;
+  uint64_t s[6] = {0, 0, 0, 0, 0, 0};
+  if (occ) seg_.run(tab_, c, rule, occ, labels != nullptr, lab, sg, s, own_);
+  *n_voxels = occ;
+  *n_segs = sg.size();
+  if ((labels && label_capacity < occ) || (segs && seg_capacity < sg.size())) return LOAMX_E_CAPACITY;
+  if (labels && occ) memcpy(labels, lab.data(), sizeof(uint32_t) * occ);
+  if (segs && !sg.empty()) memcpy(segs, sg.data(), sizeof(loamx_segment) * sg.size());
+  memcpy(stats, s, sizeof(s));
+  return LOAMX_OK;
+}
+
 }  // namespace loamx
 
 using namespace loamx;
@@ -383,6 +398,27 @@ int loamx_densemap_segment_check(const loamx_densemap_segment_config* cfg) {
     LX_REQUIRE(cfg, "cfg is NULL");
     dm_segment_check(*cfg);
     return LOAMX_OK;
+  });
+}
+
+int loamx_densemap_segment(loamx_densemap* h, const loamx_densemap_segment_config* cfg, const loamx_densemap_static_rule* rule, uint32_t* labels,
+                           uint64_t label_capacity, uint64_t* n_voxels, loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs,
+                           uint64_t stats[6]) {
+  return guard([&]() {
+    LX_REQUIRE(h, "h is NULL");
+    LX_REQUIRE(n_voxels, "n_voxels is NULL");
+    LX_REQUIRE(n_segs, "n_segs is NULL");
+    LX_REQUIRE(stats, "stats is NULL");
+    const loamx_densemap_segment_config c = or_default(cfg, loamx_densemap_segment_default_config);
+    dm_segment_check(c);
+    loamx_densemap_static_rule r;
+    loamx_densemap_static_rule_default(&r);
+    if (c.which != LOAMX_SEGMENT_ALL) {
+      LX_REQUIRE(h->d.carving(), "which: a selection by the rule needs carving, which is not enabled");
+      if (rule) r = *rule;
+      LX_REQUIRE(r.den != 0u, "the rule's den must not be 0");
+    }
+    return h->d.segment(c, r, labels, label_capacity, n_voxels, segs, seg_capacity, n_segs, stats);
   });
 }
 

@@ -4,7 +4,7 @@
 //   accumulate_rotation        <-> src/lib/BasicLaserOdometry.cpp:155-179
 //   plugin_imu_rotation        <-> src/lib/BasicLaserOdometry.cpp:91-151
 //   transform_associate_to_map <-> src/lib/BasicLaserMapping.cpp:103-167
-// and, not from the reference, jacobi_eig3: the symmetric 3x3 eigen-solver of the dense map's surfel export (densemap.hip).
+// and, not from the reference, jacobi_eig3: the symmetric 3x3 eigen-solver of the dense map's surfel export (densemap_export.hip).
 #pragma once
 #include <cmath>
 #include <utility>

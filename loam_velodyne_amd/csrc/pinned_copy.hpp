@@ -45,4 +45,19 @@ inline void store_to_pinned_u32(uint32_t* host_dst, const uint32_t* src, size_t 
   LX_HIP(hipMemcpyAsync(host_dst, src, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
 }
 
+// The pinned block that records of type T come down into through store_to_pinned_u32: the word count is n * sizeof(T) / 4 in one
+// place, and the block reads back as T.  fetch: n records of d_src, enqueued on st; the records are valid once the caller has waited
+// for st (and until the next fetch).  reserve: room ahead of time, for a block that must not move while a fetch is in flight
+template <class T> struct PinLanding {
+  static_assert(sizeof(T) % 4 == 0, "records of whole 32-bit words");
+  PinBuf<uint32_t> words;
+  void reserve(size_t n) { words.reserve(n * (sizeof(T) / 4)); }
+  const T* data() const { return (const T*)words.p; }
+  const T* fetch(const T* d_src, size_t n, hipStream_t st) {
+    reserve(n);
+    store_to_pinned_u32(words.p, (const uint32_t*)d_src, n * (sizeof(T) / 4), st);
+    return data();
+  }
+};
+
 }  // namespace loamx

@@ -1219,17 +1219,23 @@ def range_image_ends(pose, elevations_deg, n_azimuth: int, max_range: float) -> 
     return out
 
 
-class GridConfig(C.Structure):
-    """loamx_densemap_grid_config: the window (cell_leaves, x0, z0, nx, nz) and the rules of the navigation grid.  GridConfig() holds
-    the defaults (2; 0, 0; 256 x 256; min_points 2; y in [-2^20, 2^20]; band 3..20; 1 obstacle voxel; max_step 2; clear_max 10);
-    keyword arguments replace them."""
-    _fields_ = [("cell_leaves", C.c_uint32), ("x0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_uint32), ("nz", C.c_uint32),
-                ("min_points", C.c_uint32), ("y_min", C.c_int32), ("y_max", C.c_int32), ("band_lo", C.c_uint32), ("band_hi", C.c_uint32),
-                ("min_obstacle_voxels", C.c_uint32), ("max_step", C.c_uint32), ("clear_max", C.c_uint32)]
+class _DefaultedConfig:
+    """what GridConfig, RouteConfig and SegmentConfig share, beside C.Structure: construction from the library's defaults (the
+    function named by _default) with keyword arguments on top, update, copy, and check by the function named by _checker"""
+    _default = _checker = None
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+
+        def check(self):
+            _check(getattr(lib(), cls._checker)(C.byref(self)))
+            return self
+        check.__doc__ = cls._checker + " (host only): LoamxError E_INVALID names the first field out of its bounds"
+        cls.check = check
 
     def __init__(self, **fields):
         super().__init__()
-        lib().loamx_densemap_grid_default_config(C.byref(self))
+        getattr(lib(), self._default)(C.byref(self))
         self.update(**fields)
 
     def update(self, **fields):
@@ -1239,14 +1245,20 @@ class GridConfig(C.Structure):
         return self
 
     def copy(self, **fields):
-        c = GridConfig()
-        C.memmove(C.byref(c), C.byref(self), C.sizeof(GridConfig))
+        c = type(self)()
+        C.memmove(C.byref(c), C.byref(self), C.sizeof(c))
         return c.update(**fields)
 
-    def check(self):
-        """loamx_densemap_grid_check (host only): LoamxError E_INVALID names the first field out of its bounds"""
-        _check(lib().loamx_densemap_grid_check(C.byref(self)))
-        return self
+
+class GridConfig(_DefaultedConfig, C.Structure):
+    """loamx_densemap_grid_config: the window (cell_leaves, x0, z0, nx, nz) and the rules of the navigation grid.  GridConfig() holds
+    the defaults (2; 0, 0; 256 x 256; min_points 2; y in [-2^20, 2^20]; band 3..20; 1 obstacle voxel; max_step 2; clear_max 10);
+    keyword arguments replace them."""
+    _fields_ = [("cell_leaves", C.c_uint32), ("x0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_uint32), ("nz", C.c_uint32),
+                ("min_points", C.c_uint32), ("y_min", C.c_int32), ("y_max", C.c_int32), ("band_lo", C.c_uint32), ("band_hi", C.c_uint32),
+                ("min_obstacle_voxels", C.c_uint32), ("max_step", C.c_uint32), ("clear_max", C.c_uint32)]
+
+    _default, _checker = "loamx_densemap_grid_default_config", "loamx_densemap_grid_check"
 
 
 class GridCell(C.Structure):
@@ -1292,32 +1304,13 @@ def write_grid_pgm(stem: str, cells, cfg: GridConfig, leaf: float):
     _check(lib().loamx_write_grid_pgm(os.fsencode(stem), a.ctypes.data_as(C.c_void_p), C.byref(cfg), C.c_float(leaf)))
 
 
-class RouteConfig(C.Structure):
+class RouteConfig(_DefaultedConfig, C.Structure):
     """loamx_grid_route_config: how the cells of a navigation grid are weighted and joined for routing.  RouteConfig() holds the
     defaults (connectivity 8, min_clear2 1, soft_clear2 0, soft_weight 0, unknown_weight 0); keyword arguments replace them."""
     _fields_ = [("connectivity", C.c_uint32), ("min_clear2", C.c_uint32), ("soft_clear2", C.c_uint32), ("soft_weight", C.c_uint32),
                 ("unknown_weight", C.c_uint32)]
 
-    def __init__(self, **fields):
-        super().__init__()
-        lib().loamx_grid_route_default_config(C.byref(self))
-        self.update(**fields)
-
-    def update(self, **fields):
-        for k, v in fields.items():
-            assert hasattr(self, k), k
-            setattr(self, k, v)
-        return self
-
-    def copy(self, **fields):
-        c = RouteConfig()
-        C.memmove(C.byref(c), C.byref(self), C.sizeof(RouteConfig))
-        return c.update(**fields)
-
-    def check(self):
-        """loamx_grid_route_check (host only): LoamxError E_INVALID names the first field out of its bounds"""
-        _check(lib().loamx_grid_route_check(C.byref(self)))
-        return self
+    _default, _checker = "loamx_grid_route_default_config", "loamx_grid_route_check"
 
 
 class RouteCell(C.Structure):
@@ -1396,33 +1389,17 @@ SEGMENT_NONE = 0xffffffff                                                       
 SEGMENT_ALL, SEGMENT_STATIC, SEGMENT_DYNAMIC = range(3)                           # loamx_densemap_segment_config.which
 
 
-class SegmentConfig(C.Structure):
+class SegmentConfig(_DefaultedConfig, C.Structure):
     """loamx_densemap_segment_config: which voxels are selected (which, min_points, the inclusive window lo .. hi in voxel indices),
     how they join (connectivity 6, 18 or 26) and which components are kept (min_voxels).  SegmentConfig() holds the defaults (ALL,
     26, 1, 1, the whole key range); keyword arguments replace them, lo and hi as triples."""
     _fields_ = [("which", C.c_uint32), ("connectivity", C.c_uint32), ("min_points", C.c_uint32), ("min_voxels", C.c_uint32),
                 ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
 
-    def __init__(self, **fields):
-        super().__init__()
-        lib().loamx_densemap_segment_default_config(C.byref(self))
-        self.update(**fields)
+    _default, _checker = "loamx_densemap_segment_default_config", "loamx_densemap_segment_check"
 
     def update(self, **fields):
-        for k, v in fields.items():
-            assert hasattr(self, k), k
-            setattr(self, k, (C.c_int32 * 3)(*v) if k in ("lo", "hi") else v)
-        return self
-
-    def copy(self, **fields):
-        c = SegmentConfig()
-        C.memmove(C.byref(c), C.byref(self), C.sizeof(SegmentConfig))
-        return c.update(**fields)
-
-    def check(self):
-        """loamx_densemap_segment_check (host only): LoamxError E_INVALID names the first field out of its bounds"""
-        _check(lib().loamx_densemap_segment_check(C.byref(self)))
-        return self
+        return super().update(**{k: (C.c_int32 * 3)(*v) if k in ("lo", "hi") else v for k, v in fields.items()})
 
 
 class Segment(C.Structure):

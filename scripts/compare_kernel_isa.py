@@ -20,7 +20,9 @@ TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 
 def kernels(obj, tmp):
     fat, co = os.path.join(tmp, os.path.basename(obj) + ".fat"), os.path.join(tmp, os.path.basename(obj) + ".gfx950")
-    subprocess.run(["objcopy", "--dump-section", ".hip_fatbin=" + fat, obj], check=True)
+    subprocess.run(["objcopy", "--dump-section", ".hip_fatbin=" + fat, obj], check=True, stderr=subprocess.DEVNULL)
+    if not os.path.exists(fat):   # (host code only, e.g. densemap_export.o: the object has no such section and holds no kernel)
+        return {}
     subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat, "--targets=" + TARGET,
                     "--output=" + co], check=True)
     dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], check=True, capture_output=True, text=True).stdout
