@@ -938,9 +938,7 @@ void FeatureExtractor::upload(uint32_t nsw, const loamx_cloud* clouds, const uin
 // only the ring sizes come back to the host, which needs them to lay out the per-ring work.
 void FeatureExtractor::upload_raw(const void* raw_xyz, uint32_t count, uint32_t stride, float lower_deg, float upper_deg, uint32_t n_scan_rings) {
   LX_REQUIRE(raw_xyz || count == 0, "NULL raw cloud");
-  LX_REQUIRE(stride >= 12 && stride % 4 == 0, "raw stride must be a multiple of 4 and at least 12");
-  LX_REQUIRE(n_scan_rings >= 1 && n_scan_rings <= RawBinner::MAX_RINGS, "n_scan_rings must be in [1, 256]");
-  LX_REQUIRE(upper_deg != lower_deg, "vertical bounds must differ");
+  mapper_check(lower_deg, upper_deg, n_scan_rings, stride);
   check_params_();
   LX_HIP(hipSetDevice(device_));
   h_cloud_.reserve(count + 1);
@@ -953,18 +951,20 @@ void FeatureExtractor::upload_raw(const void* raw_xyz, uint32_t count, uint32_t 
   raw_ring_cnt_.reserve(RawBinner::MAX_RINGS);
   h_raw_ring_cnt_.reserve(RawBinner::MAX_RINGS);
   if (count) LX_HIP(hipMemcpyAsync(raw_.p, h_cloud_.p, sizeof(float4) * count, hipMemcpyHostToDevice, st_));
-  MapperParams M;
-  M.lower = lower_deg; M.upper = upper_deg; M.n_rings = n_scan_rings;
-  M.factor = (float)((int)n_scan_rings - 1) / (upper_deg - lower_deg);   // (nScanRings - 1) / (upperBound - lowerBound), :41-50
+  bin_raw_(count, mapper_params(lower_deg, upper_deg, n_scan_rings));
+}
+
+// raw_ -> cloud_ (binned, de-skewed with the IMU history the handle holds) and the per-ring layout
+void FeatureExtractor::bin_raw_(uint32_t count, const SensorParams& sp) {
   binner_.init(st_);
   ImuTable I;
   const uint32_t H = stage_imu_table_(I);
-  binner_.run(raw_.p, count, M, params.scan_period, cloud_.p, raw_ring_cnt_.p, H ? &I : nullptr, H ? imu_last_.p : nullptr);
-  finish_raw_(n_scan_rings, H);
+  binner_.run(raw_.p, count, sp, params.scan_period, cloud_.p, raw_ring_cnt_.p, H ? &I : nullptr, H ? imu_last_.p : nullptr);
+  finish_raw_(sp.M.n_rings, H);
 }
 
 // The same with a sensor model (include/loamx.h, loamx_sensor_model): the record bytes go up as they are and are unpacked on the
-// device (sensor_unpack), as the pipeline's stage_step_raw does with its payloads.
+// device (unpack_records), as the pipeline's stage_step_raw does with its payloads.
 void FeatureExtractor::upload_sensor(const void* records, uint32_t count, uint32_t stride, const loamx_sensor_model& model) {
   LX_REQUIRE(records || count == 0, "NULL raw cloud");
   sensor_model_check(model, stride);
@@ -985,12 +985,8 @@ void FeatureExtractor::upload_sensor(const void* records, uint32_t count, uint32
   if (sp.ring_src == RING_FIELD) { ring_fld_.reserve(count + 1); sp.ring_fld = ring_fld_.p; }
   if (sp.time_src == TIME_FIELD) { time_fld_.reserve(count + 1); sp.time_fld = time_fld_.p; }
   if (count) LX_HIP(hipMemcpyAsync(bytes_.p, direct ? records : (const void*)h_bytes_.p, bytes, hipMemcpyHostToDevice, st_));
-  sensor_unpack(bytes_.p, stride, count, sp, raw_.p, ring_fld_.p, time_fld_.p, st_);
-  binner_.init(st_);
-  ImuTable I;
-  const uint32_t H = stage_imu_table_(I);
-  binner_.run(raw_.p, count, sp, params.scan_period, cloud_.p, raw_ring_cnt_.p, H ? &I : nullptr, H ? imu_last_.p : nullptr);
-  finish_raw_(model.n_scan_rings, H);
+  unpack_records(bytes_.p, stride, count, sp, raw_.p, st_);
+  bin_raw_(count, sp);
 }
 
 // IMU de-skew (projectPointToStartOfSweep, :231): the state the PREVIOUS reset() left behind — the reference projects the

@@ -144,6 +144,7 @@ class FeatureExtractor {
   void layout_(uint32_t nsw, const uint32_t* const* ring_size, const uint32_t* n_rings);
   void allocate_(hipStream_t table_stream = nullptr);
   PinBuf<uint32_t> h_tab_;
+  void bin_raw_(uint32_t count, const SensorParams& sp);
   uint32_t stage_imu_table_(ImuTable& I);
   void finish_raw_(uint32_t n_scan_rings, uint32_t H);
   RawBinner binner_;

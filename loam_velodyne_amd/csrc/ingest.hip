@@ -3,6 +3,9 @@
 // than pi past the start and stays set, so it is "index > j*" with j* a min-reduction — and (b) the per-ring push_back,
 // i.e. a stable split by ring id: per-workgroup ring histograms, a column scan over the workgroups, and a stable rank
 // inside the workgroup (wave ballots per distinct ring + wave-order prefix).
+// A sensor model (include/loamx.h, loamx_sensor_model) changes two things only: where a point's ring comes from (classify) and where its
+// relTime comes from (classify, IMU need, scatter).  Each source is an argument struct and the kernels are templates over them; the
+// reference's mapper is k_raw_classify<BoundsRing, AzimuthTime>, k_raw_imu_need<AzimuthTime>, k_raw_scatter<AzimuthTime>.
 #include "ingest.hpp"
 
 namespace loamx {
@@ -66,12 +69,35 @@ __global__ void k_raw_init(const float4* __restrict__ raw, uint32_t n, uint32_t*
   if (e < H) imu_first[e] = 0xffffffffu;
 }
 
-// relTime of kept point i (:209-228); x, z in the LOAM frame
-__device__ inline float rel_time_of(uint32_t i, float x, float z, float startOri, float endOri, uint32_t jstar, float scan_period) {
+// ---- where relTime comes from (TimeSrc): one argument struct and one rel_time() per source.  The kernels that need relTime are
+// templates over the struct, so a trace names the source: k_raw_scatter<AzimuthTime>, k_raw_scatter<FieldTime>.
+
+// TIME_FROM_AZIMUTH: the records and the sweep's scratch words (k_raw_init, k_raw_colscan)
+struct AzimuthTime {
+  static constexpr int src = TIME_AZIMUTH;
+  const float4* raw;
+  const uint32_t* sweep;
+};
+// relTime of kept point i (:209-228)
+__device__ inline float rel_time(const AzimuthTime& a, uint32_t i, float scan_period) {
+  const float startOri = __uint_as_float(a.sweep[2]), endOri = __uint_as_float(a.sweep[3]);
+  const float x = a.raw[i].y, z = a.raw[i].x;   // LOAM frame
   bool passes;
   float ori = ori_first_half(x, z, startOri, passes);
-  if (i > jstar) ori = ori_second_half(x, z, endOri);   // halfPassed was set by an earlier kept point
+  if (i > a.sweep[0]) ori = ori_second_half(x, z, endOri);   // halfPassed was set by an earlier kept point
   return scan_period * (ori - startOri) / (endOri - startOri);
+}
+
+// TIME_FROM_FIELD: t_i of every record (k_sensor_unpack), the sweep's t_ref (k_sns_tref), seconds per unit
+struct FieldTime {
+  static constexpr int src = TIME_FIELD;
+  const double* t;
+  const double* tref;
+  double scale;
+};
+__device__ inline float rel_time(const FieldTime& f, uint32_t i, float scan_period) {
+  const float rt = (float)((f.t[i] - *f.tref) * f.scale);
+  return rt > scan_period ? scan_period : rt;
 }
 
 // interpolateIMUStateFor's index search for one point on its own (:135-139): smallest j with dt[j] + relTime <= 0, else H-1
@@ -87,17 +113,12 @@ __device__ inline uint32_t imu_need(const ImuTable& I, float relTime) {
 // _imuIdx only ever moves forward while the points are walked in firing order: idx(i) = max(idx0, max_{kept j <= i} need(j)).
 // k_raw_imu_need records, per history index v, the first kept point that needs at least ... exactly v; the suffix minimum
 // over v turns that into "first point that needs >= v", which is non-decreasing in v and binary-searchable per point.
-__global__ __launch_bounds__(256) void k_raw_imu_need(const float4* __restrict__ raw, uint32_t n, float scan_period, const int* __restrict__ ring_of,
-                                                      const uint32_t* __restrict__ jstar, ImuTable I, uint32_t* __restrict__ first) {
+template <class Time>
+__global__ __launch_bounds__(256) void k_raw_imu_need(uint32_t n, float scan_period, const int* __restrict__ ring_of, ImuTable I,
+                                                      uint32_t* __restrict__ first, Time time) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool active = i < n && ring_of[i] >= 0;
-  uint32_t v = 0;
-  if (active) {
-    const float startOri = __uint_as_float(jstar[2]), endOri = __uint_as_float(jstar[3]);
-    const float4 r = raw[i];
-    const float relTime = rel_time_of(i, r.y, r.x, startOri, endOri, jstar[0], scan_period);
-    v = imu_need(I, relTime);
-  }
+  const uint32_t v = active ? imu_need(I, rel_time(time, i, scan_period)) : 0u;
   // neighbouring points need the same history index: only the first lane of a run of equal v (it has the run's smallest
   // point index) issues the atomic
   const int lane = threadIdx.x & 63;
@@ -176,27 +197,96 @@ __device__ inline void imu_project(const ImuTable& I, const uint32_t* __restrict
   }
 }
 
-// per workgroup: ring histogram, first point that would set halfPassed, last kept point (k_raw_colscan reduces the two
-// index arrays — thousands of atomics on ONE global word per launch serialise for tens of microseconds)
-__global__ __launch_bounds__(256) void k_raw_classify(const float4* __restrict__ raw, uint32_t n, MapperParams M, int* __restrict__ ring_of,
-                                                      uint32_t* __restrict__ blk_cnt, const uint32_t* __restrict__ jstar,
-                                                      uint32_t* __restrict__ blk_first_pass, uint32_t* __restrict__ blk_last_kept) {
+// ---- where a point's ring comes from (RingSrc): one argument struct per source (each with the ring count, n_rings), so a classify
+// instantiation is handed only what its source reads (the 1 KB table travels in the kernel arguments of k_raw_classify<TableRing, ...> alone)
+struct BoundsRing : MapperParams {   // RING_FROM_BOUNDS: the reference's linear mapper
+  static constexpr int src = RING_BOUNDS;
+};
+struct TableRing {    // RING_FROM_TABLE: the lasers' elevations (degrees, strictly increasing), max_angle_error_deg
+  static constexpr int src = RING_TABLE;
+  float table[RawBinner::MAX_RINGS];
+  float max_err;
+  uint32_t n_rings;
+};
+struct FieldRing {    // RING_FROM_FIELD: the ring field of every record (k_sensor_unpack)
+  static constexpr int src = RING_FIELD;
+  const uint32_t* ring;
+  uint32_t n_rings;
+};
+
+// :184-196 (the first half of classify): remapped point; false = rejected (NaN / zero return)
+__device__ inline bool remap_keep(const float4 r, float& x, float& y, float& z) {
+  x = r.y; y = r.z; z = r.x;
+  if (!isfinite(x) || !isfinite(y) || !isfinite(z)) return false;
+  return (double)(x * x + y * y + z * z) >= 0.0001;
+}
+
+// RING_FROM_TABLE: the entry of the sorted table `tab` (LDS) nearest to the vertical angle, in double, ties to the smaller index; -1 when
+// it is farther than max_err.  deg is taken exactly as classify() takes it.
+__device__ inline int ring_from_table(float x, float y, float z, const float* tab, uint32_t nr, float max_err) {
+  const float angle = atan_f(y / sqrtf(x * x + z * z));
+  const double deg = (double)(angle * 180) / PI_D;
+  uint32_t lo = 0, hi = nr;   // first k with tab[k] >= deg: the nearest entry is k or k - 1
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if ((double)tab[mid] < deg) lo = mid + 1; else hi = mid;
+  }
+  uint32_t k = lo < nr ? lo : nr - 1;
+  double best = fabs(deg - (double)tab[k]);
+  // (rounded distances grow weakly away from deg on either side: a tie with a smaller index can only lie further left)
+  while (k > 0 && fabs(deg - (double)tab[k - 1]) <= best) { k--; best = fabs(deg - (double)tab[k]); }
+  return best > (double)max_err ? -1 : (int)k;
+}
+
+// smallest double of a workgroup of 256 (every thread passes one value; w: 4 doubles of LDS), valid in thread 0
+__device__ inline double block_min_256(double t, double* w) {
+  for (int d = 32; d >= 1; d >>= 1) t = fmin(t, __shfl_xor(t, d, 64));
+  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = t;
+  __syncthreads();
+  return fmin(fmin(w[0], w[1]), fmin(w[2], w[3]));
+}
+
+// per workgroup: ring histogram and last kept point, and per time source: TIME_FROM_AZIMUTH the first point that would set halfPassed
+// (k_raw_colscan reduces the two index arrays — thousands of atomics on ONE global word per launch serialise for tens of
+// microseconds), TIME_FROM_FIELD the smallest time of the kept points (k_sns_tref reduces it to t_ref); a time that is not finite
+// rejects the point.  The mapper path is <BoundsRing, AzimuthTime>: no table and no time minimum in LDS, no field read.
+template <class Ring, class Time>
+__global__ __launch_bounds__(256) void k_raw_classify(const float4* __restrict__ raw, uint32_t n, Ring ring, Time time,
+                                                      int* __restrict__ ring_of, uint32_t* __restrict__ blk_cnt,
+                                                      uint32_t* __restrict__ blk_first_pass, uint32_t* __restrict__ blk_last_kept,
+                                                      double* __restrict__ blk_tmin) {
   __shared__ uint32_t hist[RawBinner::MAX_RINGS];
   __shared__ uint32_t s_first, s_last;
+  __shared__ float tab[RawBinner::MAX_RINGS];
+  __shared__ double w_tmin[4];
+  const uint32_t nr = ring.n_rings;
   if (threadIdx.x == 0) { s_first = 0xffffffffu; s_last = 0u; }
-  for (uint32_t r = threadIdx.x; r < M.n_rings; r += blockDim.x) hist[r] = 0;
+  for (uint32_t r = threadIdx.x; r < nr; r += blockDim.x) {
+    hist[r] = 0;
+    if constexpr (Ring::src == RING_TABLE) tab[r] = ring.table[r];
+  }
   __syncthreads();
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   bool kept = false, passes = false;
+  double t = HUGE_VAL;
   if (i < n) {
-    const float startOri = __uint_as_float(jstar[2]);
     float x, y, z;
-    const int id = classify(raw[i], M, x, y, z);
+    int id;
+    if constexpr (Ring::src == RING_BOUNDS) id = classify(raw[i], ring, x, y, z);
+    else if (!remap_keep(raw[i], x, y, z)) id = -1;
+    else if constexpr (Ring::src == RING_TABLE) id = ring_from_table(x, y, z, tab, nr, ring.max_err);
+    else id = ring.ring[i] < nr ? (int)ring.ring[i] : -1;
+    if constexpr (Time::src == TIME_FIELD) {
+      if (id >= 0) {
+        t = time.t[i];
+        if (!isfinite(t)) { id = -1; t = HUGE_VAL; }
+      }
+    }
     ring_of[i] = id;
     if (id >= 0) {
       kept = true;
       atomicAdd(&hist[id], 1u);
-      (void)ori_first_half(x, z, startOri, passes);
+      if constexpr (Time::src == TIME_AZIMUTH) (void)ori_first_half(x, z, __uint_as_float(time.sweep[2]), passes);
     }
   }
   // one atomic per wave: the lowest passing lane holds the wave's smallest index, the highest kept lane its largest
@@ -204,9 +294,15 @@ __global__ __launch_bounds__(256) void k_raw_classify(const float4* __restrict__
   const int lane = threadIdx.x & 63;
   if (mp && lane == __builtin_ctzll(mp)) atomicMin(&s_first, i);
   if (mk && lane == 63 - __builtin_clzll(mk)) atomicMax(&s_last, i + 1u);   // (+1: 0 = no kept point in this workgroup)
+  double tmin = 0.0;
+  if constexpr (Time::src == TIME_FIELD) tmin = block_min_256(t, w_tmin);   // (its barrier also orders the LDS atomics above)
   __syncthreads();
-  if (threadIdx.x == 0) { blk_first_pass[blockIdx.x] = s_first; blk_last_kept[blockIdx.x] = s_last; }
-  for (uint32_t r = threadIdx.x; r < M.n_rings; r += blockDim.x) blk_cnt[(size_t)blockIdx.x * M.n_rings + r] = hist[r];
+  if (threadIdx.x == 0) {
+    blk_first_pass[blockIdx.x] = s_first;
+    blk_last_kept[blockIdx.x] = s_last;
+    if constexpr (Time::src == TIME_FIELD) blk_tmin[blockIdx.x] = tmin;
+  }
+  for (uint32_t r = threadIdx.x; r < nr; r += blockDim.x) blk_cnt[(size_t)blockIdx.x * nr + r] = hist[r];
 }
 
 // one workgroup per ring: exclusive scan of the ring's column of workgroup counts
@@ -247,24 +343,10 @@ __global__ __launch_bounds__(256) void k_raw_colscan(const uint32_t* __restrict_
   if (threadIdx.x == 0) ring_cnt[r] = base;
 }
 
-__global__ __launch_bounds__(256) void k_raw_scatter(const float4* __restrict__ raw, uint32_t n, MapperParams M, float scan_period,
-                                                     const int* __restrict__ ring_of, const uint32_t* __restrict__ blk_pre,
-                                                     const uint32_t* __restrict__ ring_cnt, const uint32_t* __restrict__ jstar,
-                                                     float4* __restrict__ out, ImuTable I, const uint32_t* __restrict__ imu_first,
-                                                     ImuLast* __restrict__ d_last) {
-  __shared__ uint32_t ring_off[RawBinner::MAX_RINGS];
-  __shared__ uint32_t wcnt[4][RawBinner::MAX_RINGS];
-  // ring offsets (exclusive scan of the ring totals; <= 256 rings)
-  if (threadIdx.x == 0) {
-    uint32_t acc = 0;
-    for (uint32_t r = 0; r < M.n_rings; r++) { ring_off[r] = acc; acc += ring_cnt[r]; }
-  }
-  for (uint32_t e = threadIdx.x; e < 4 * RawBinner::MAX_RINGS; e += blockDim.x) (&wcnt[0][0])[e] = 0;
-  __syncthreads();
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int id = i < n ? ring_of[i] : -1;
-  // stable rank among the same-ring points of this wave
+// stable rank of this lane among the lanes of its wave that hold the same ring id (id < 0: not ranked): one round of ballots per
+// distinct ring in the wave; the first lane of every ring leaves the wave's count of it in wave_cnt[ring]
+__device__ inline uint32_t wave_rank(int id, uint32_t* wave_cnt) {
+  const int lane = threadIdx.x & 63;
   uint32_t rank = 0;
   unsigned long long todo = __ballot(id >= 0);
   while (todo) {
@@ -273,120 +355,42 @@ __global__ __launch_bounds__(256) void k_raw_scatter(const float4* __restrict__ 
     const unsigned long long m = __ballot(id == r0);
     if (id == r0) {
       rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      if (lane == src) wcnt[wid][r0] = (uint32_t)__popcll(m);
+      if (lane == src) wave_cnt[r0] = (uint32_t)__popcll(m);
     }
     todo &= ~m;
   }
+  return rank;
+}
+
+// every kept point to its place: ring offset + the counts of the workgroups before this one + the waves before this one + wave_rank
+template <class Time>
+__global__ __launch_bounds__(256) void k_raw_scatter(const float4* __restrict__ raw, uint32_t n, uint32_t nr, float scan_period,
+                                                     const int* __restrict__ ring_of, const uint32_t* __restrict__ blk_pre,
+                                                     const uint32_t* __restrict__ ring_cnt, const uint32_t* __restrict__ sweep,
+                                                     float4* __restrict__ out, ImuTable I, const uint32_t* __restrict__ imu_first,
+                                                     ImuLast* __restrict__ d_last, Time time) {
+  __shared__ uint32_t ring_off[RawBinner::MAX_RINGS];
+  __shared__ uint32_t wcnt[4][RawBinner::MAX_RINGS];
+  // ring offsets (exclusive scan of the ring totals; <= 256 rings)
+  if (threadIdx.x == 0) {
+    uint32_t acc = 0;
+    for (uint32_t r = 0; r < nr; r++) { ring_off[r] = acc; acc += ring_cnt[r]; }
+  }
+  for (uint32_t e = threadIdx.x; e < 4 * RawBinner::MAX_RINGS; e += blockDim.x) (&wcnt[0][0])[e] = 0;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int wid = threadIdx.x >> 6;
+  const int id = i < n ? ring_of[i] : -1;
+  uint32_t rank = wave_rank(id, wcnt[wid]);
   __syncthreads();
   if (id < 0) return;
   for (int w = 0; w < wid; w++) rank += wcnt[w][id];
-  const uint32_t pos = ring_off[id] + blk_pre[(size_t)blockIdx.x * M.n_rings + id] + rank;
-  const float startOri = __uint_as_float(jstar[2]), endOri = __uint_as_float(jstar[3]);
+  const uint32_t pos = ring_off[id] + blk_pre[(size_t)blockIdx.x * nr + id] + rank;
   const float4 r = raw[i];
   float x = r.y, y = r.z, z = r.x;
-  const float relTime = rel_time_of(i, x, z, startOri, endOri, jstar[0], scan_period);   // :228
-  if (I.H) imu_project(I, imu_first, i, relTime, x, y, z, i == jstar[1] ? d_last : nullptr);   // :231
-  out[pos] = make_float4(x, y, z, (float)id + relTime);                                  // :229
-}
-
-
-// ---- sensor models (include/loamx.h, loamx_sensor_model).  The mapper path above stays as it is; these kernels serve every other
-// combination of ring and time source.  With TIME_FROM_AZIMUTH only the classification differs (k_sns_classify), and the rest of
-// the mapper path's kernels run as they are: they read nothing but the ring ids and the sweep's first-pass / last-kept indices.
-
-// :184-196 (the first half of classify): remapped point; false = rejected (NaN / zero return)
-__device__ inline bool remap_keep(const float4 r, float& x, float& y, float& z) {
-  x = r.y; y = r.z; z = r.x;
-  if (!isfinite(x) || !isfinite(y) || !isfinite(z)) return false;
-  return (double)(x * x + y * y + z * z) >= 0.0001;
-}
-
-// RING_FROM_TABLE: the entry of the sorted table `tab` (LDS) nearest to the vertical angle, in double, ties to the smaller index; -1 when
-// it is farther than max_err.  deg is taken exactly as classify() takes it.
-__device__ inline int ring_from_table(float x, float y, float z, const float* tab, uint32_t nr, float max_err) {
-  const float angle = atan_f(y / sqrtf(x * x + z * z));
-  const double deg = (double)(angle * 180) / PI_D;
-  uint32_t lo = 0, hi = nr;   // first k with tab[k] >= deg: the nearest entry is k or k - 1
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if ((double)tab[mid] < deg) lo = mid + 1; else hi = mid;
-  }
-  uint32_t k = lo < nr ? lo : nr - 1;
-  double best = fabs(deg - (double)tab[k]);
-  // (rounded distances grow weakly away from deg on either side: a tie with a smaller index can only lie further left)
-  while (k > 0 && fabs(deg - (double)tab[k - 1]) <= best) { k--; best = fabs(deg - (double)tab[k]); }
-  return best > (double)max_err ? -1 : (int)k;
-}
-
-// TIME_FROM_FIELD: t_i of every record (sensor_unpack), the sweep's t_ref (k_sns_colscan), seconds per unit
-struct TimeField {
-  const double* t;
-  const double* tref;
-  double scale;
-};
-__device__ inline float rel_time_field(const TimeField& tf, uint32_t i, float scan_period) {
-  const float rt = (float)((tf.t[i] - *tf.tref) * tf.scale);
-  return rt > scan_period ? scan_period : rt;
-}
-// smallest double of a workgroup of 256 (every thread passes one value; w: 4 doubles of LDS), valid in thread 0
-__device__ inline double block_min_256(double t, double* w) {
-  for (int d = 32; d >= 1; d >>= 1) t = fmin(t, __shfl_xor(t, d, 64));
-  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = t;
-  __syncthreads();
-  return fmin(fmin(w[0], w[1]), fmin(w[2], w[3]));
-}
-
-// k_raw_classify for a sensor model: the ring from the model's source; with TIME_FROM_AZIMUTH the first-pass index over the points
-// this model keeps, with TIME_FROM_FIELD the smallest time of the workgroup's kept points instead (k_sns_colscan reduces it to t_ref)
-template <int RS, int TS>
-__global__ __launch_bounds__(256) void k_sns_classify(const float4* __restrict__ raw, uint32_t n, SensorParams sp, int* __restrict__ ring_of,
-                                                      uint32_t* __restrict__ blk_cnt, const uint32_t* __restrict__ jstar,
-                                                      uint32_t* __restrict__ blk_first_pass, uint32_t* __restrict__ blk_last_kept,
-                                                      double* __restrict__ blk_tmin) {
-  __shared__ uint32_t hist[RawBinner::MAX_RINGS];
-  __shared__ float tab[RawBinner::MAX_RINGS];
-  __shared__ uint32_t s_first, s_last;
-  __shared__ double w_tmin[4];
-  const uint32_t nr = sp.M.n_rings;
-  if (threadIdx.x == 0) { s_first = 0xffffffffu; s_last = 0u; }
-  for (uint32_t r = threadIdx.x; r < nr; r += blockDim.x) {
-    hist[r] = 0;
-    if (RS == RING_TABLE) tab[r] = sp.table[r];
-  }
-  __syncthreads();
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  bool kept = false, passes = false;
-  double t = HUGE_VAL;
-  if (i < n) {
-    float x, y, z;
-    int id;
-    if (RS == RING_BOUNDS) id = classify(raw[i], sp.M, x, y, z);
-    else if (!remap_keep(raw[i], x, y, z)) id = -1;
-    else if (RS == RING_TABLE) id = ring_from_table(x, y, z, tab, nr, sp.max_err);
-    else id = sp.ring_fld[i] < nr ? (int)sp.ring_fld[i] : -1;
-    if (TS == TIME_FIELD && id >= 0) {
-      t = sp.time_fld[i];
-      if (!isfinite(t)) { id = -1; t = HUGE_VAL; }
-    }
-    ring_of[i] = id;
-    if (id >= 0) {
-      kept = true;
-      atomicAdd(&hist[id], 1u);
-      if (TS == TIME_AZIMUTH) (void)ori_first_half(x, z, __uint_as_float(jstar[2]), passes);
-    }
-  }
-  const unsigned long long mp = __ballot(passes), mk = __ballot(kept);
-  const int lane = threadIdx.x & 63;
-  if (mp && lane == __builtin_ctzll(mp)) atomicMin(&s_first, i);
-  if (mk && lane == 63 - __builtin_clzll(mk)) atomicMax(&s_last, i + 1u);
-  const double tmin = TS == TIME_FIELD ? block_min_256(t, w_tmin) : 0.0;   // (its barrier also orders the LDS atomics above)
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    blk_first_pass[blockIdx.x] = s_first;
-    blk_last_kept[blockIdx.x] = s_last;
-    if (TS == TIME_FIELD) blk_tmin[blockIdx.x] = tmin;
-  }
-  for (uint32_t r = threadIdx.x; r < nr; r += blockDim.x) blk_cnt[(size_t)blockIdx.x * nr + r] = hist[r];
+  const float relTime = rel_time(time, i, scan_period);                                         // :228
+  if (I.H) imu_project(I, imu_first, i, relTime, x, y, z, i == sweep[1] ? d_last : nullptr);   // :231
+  out[pos] = make_float4(x, y, z, (float)id + relTime);                                         // :229
 }
 
 // TIME_FROM_FIELD: t_ref = the smallest time of the kept points, over the per-workgroup minima (one workgroup; k_raw_colscan reduces
@@ -398,59 +402,6 @@ __global__ __launch_bounds__(256) void k_sns_tref(const double* __restrict__ blk
   t = block_min_256(t, w);
   if (threadIdx.x == 0) *tref = t;
 }
-
-// k_raw_imu_need with the relTime of the time field
-__global__ __launch_bounds__(256) void k_sns_imu_need(uint32_t n, float scan_period, const int* __restrict__ ring_of, ImuTable I,
-                                                      uint32_t* __restrict__ first, TimeField tf) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = i < n && ring_of[i] >= 0;
-  const uint32_t v = active ? imu_need(I, rel_time_field(tf, i, scan_period)) : 0u;
-  const int lane = threadIdx.x & 63;
-  const uint32_t pv = __shfl_up(v, 1, 64);
-  const unsigned long long act = __ballot(active);
-  const bool head = active && (lane == 0 || pv != v || !((act >> (lane > 0 ? lane - 1 : 0)) & 1ull));
-  if (head && v > I.idx0) atomicMin(&first[v], i);
-}
-
-// k_raw_scatter with the relTime of the time field
-__global__ __launch_bounds__(256) void k_sns_scatter(const float4* __restrict__ raw, uint32_t n, uint32_t nr, float scan_period,
-                                                     const int* __restrict__ ring_of, const uint32_t* __restrict__ blk_pre,
-                                                     const uint32_t* __restrict__ ring_cnt, const uint32_t* __restrict__ jstar,
-                                                     float4* __restrict__ out, ImuTable I, const uint32_t* __restrict__ imu_first,
-                                                     ImuLast* __restrict__ d_last, TimeField tf) {
-  __shared__ uint32_t ring_off[RawBinner::MAX_RINGS];
-  __shared__ uint32_t wcnt[4][RawBinner::MAX_RINGS];
-  if (threadIdx.x == 0) {
-    uint32_t acc = 0;
-    for (uint32_t r = 0; r < nr; r++) { ring_off[r] = acc; acc += ring_cnt[r]; }
-  }
-  for (uint32_t e = threadIdx.x; e < 4 * RawBinner::MAX_RINGS; e += blockDim.x) (&wcnt[0][0])[e] = 0;
-  __syncthreads();
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int id = i < n ? ring_of[i] : -1;
-  uint32_t rank = 0;   // stable rank among the same-ring points of this wave
-  unsigned long long todo = __ballot(id >= 0);
-  while (todo) {
-    const int src = __builtin_ctzll(todo);
-    const int r0 = __shfl(id, src, 64);
-    const unsigned long long m = __ballot(id == r0);
-    if (id == r0) {
-      rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      if (lane == src) wcnt[wid][r0] = (uint32_t)__popcll(m);
-    }
-    todo &= ~m;
-  }
-  __syncthreads();
-  if (id < 0) return;
-  for (int w = 0; w < wid; w++) rank += wcnt[w][id];
-  const uint32_t pos = ring_off[id] + blk_pre[(size_t)blockIdx.x * nr + id] + rank;
-  const float4 r = raw[i];
-  float x = r.y, y = r.z, z = r.x;
-  const float relTime = rel_time_field(tf, i, scan_period);
-  if (I.H) imu_project(I, imu_first, i, relTime, x, y, z, i == jstar[1] ? d_last : nullptr);
-  out[pos] = make_float4(x, y, z, (float)id + relTime);
-}
 }  // namespace
 
 // raw records (x, y, z float32 at byte offsets 0 / 4 / 8, `stride` bytes apart) -> float4 (x, y, z, 0): the payload crosses PCIe as
@@ -460,9 +411,6 @@ __global__ __launch_bounds__(256) void k_raw_unpack(const char* __restrict__ byt
   if (i >= n) return;
   const float* r = (const float*)(bytes + (size_t)i * stride);
   out[i] = make_float4(r[0], r[1], r[2], 0.f);
-}
-void raw_unpack(const void* d_bytes, uint32_t stride, uint32_t n, float4* d_out, hipStream_t st) {
-  if (n) hipLaunchKernelGGL(k_raw_unpack, dim3((n + 255) / 256), dim3(256), 0, st, (const char*)d_bytes, stride, n, d_out);
 }
 
 // sensor records: as k_raw_unpack, plus the ring field (-> uint32) and the time field (-> double) where the model reads them.  Fields are
@@ -488,11 +436,14 @@ __global__ __launch_bounds__(256) void k_sensor_unpack(const char* __restrict__ 
             : __hiloint2double((int)rec_dword(rec, time_off + 4), (int)w);   // (little endian: the low word first)
   }
 }
-void sensor_unpack(const void* d_bytes, uint32_t stride, uint32_t n, const SensorParams& sp, float4* d_out, uint32_t* d_ring, double* d_time,
-                   hipStream_t st) {
+void unpack_records(const void* d_bytes, uint32_t stride, uint32_t n, const SensorParams& sp, float4* d_out, hipStream_t st) {
   if (!n) return;
-  hipLaunchKernelGGL(k_sensor_unpack, dim3((n + 255) / 256), dim3(256), 0, st, (const char*)d_bytes, stride, n, sp.ring_off, sp.ring_type,
-                     sp.time_off, sp.time_type, d_out, sp.ring_src == RING_FIELD ? d_ring : nullptr, sp.time_src == TIME_FIELD ? d_time : nullptr);
+  const dim3 grid((n + 255) / 256), block(256);
+  if (sp.ring_src != RING_FIELD && sp.time_src != TIME_FIELD)
+    hipLaunchKernelGGL(k_raw_unpack, grid, block, 0, st, (const char*)d_bytes, stride, n, d_out);
+  else
+    hipLaunchKernelGGL(k_sensor_unpack, grid, block, 0, st, (const char*)d_bytes, stride, n, sp.ring_off, sp.ring_type, sp.time_off, sp.time_type,
+                       d_out, sp.ring_src == RING_FIELD ? sp.ring_fld : nullptr, sp.time_src == TIME_FIELD ? sp.time_fld : nullptr);
 }
 
 static uint32_t field_size(uint32_t type) {
@@ -510,11 +461,22 @@ static void check_field(uint32_t off, uint32_t type, uint32_t stride, const char
   if ((uint64_t)off + sz > stride) throw Error(LOAMX_E_INVALID, std::string(what) + " field does not fit inside the record stride");
 }
 
+static void check_stride(uint32_t stride) { LX_REQUIRE(stride >= 12 && stride % 4 == 0, "raw stride must be a multiple of 4 and at least 12"); }
+static void check_ring_count(uint32_t n_rings) {
+  LX_REQUIRE(n_rings >= 1 && n_rings <= RawBinner::MAX_RINGS, "n_scan_rings must be in [1, 256]");
+}
+
+void mapper_check(float lower, float upper, uint32_t n_rings, uint32_t stride) {
+  check_stride(stride);
+  check_ring_count(n_rings);
+  LX_REQUIRE(upper != lower, "vertical bounds must differ");
+}
+
 void sensor_model_check(const loamx_sensor_model& m, uint32_t stride) {
-  LX_REQUIRE(stride >= 12 && stride % 4 == 0, "raw stride must be a multiple of 4 and at least 12");
+  check_stride(stride);
   LX_REQUIRE(m.ring_source <= LOAMX_RING_FROM_FIELD, "unknown ring source");
   LX_REQUIRE(m.time_source <= LOAMX_TIME_FROM_FIELD, "unknown time source");
-  LX_REQUIRE(m.n_scan_rings >= 1 && m.n_scan_rings <= RawBinner::MAX_RINGS, "n_scan_rings must be in [1, 256]");
+  check_ring_count(m.n_scan_rings);
   if (m.ring_source == LOAMX_RING_FROM_BOUNDS) {   // as loamx_scanreg_process_raw (MultiScanRegistration.cpp:107-127)
     LX_REQUIRE(m.upper_bound_deg > m.lower_bound_deg, "invalid vertical range (upper <= lower)");
     LX_REQUIRE(m.n_scan_rings >= 2, "invalid number of scan rings (n < 2)");
@@ -538,16 +500,18 @@ void sensor_model_check(const loamx_sensor_model& m, uint32_t stride) {
   }
 }
 
-SensorParams sensor_params(const loamx_sensor_model& m) {
+SensorParams mapper_params(float lower, float upper, uint32_t n_rings) {
   SensorParams sp;
-  sp.M.n_rings = m.n_scan_rings;
-  sp.M.lower = m.lower_bound_deg;
-  sp.M.upper = m.upper_bound_deg;
-  sp.M.factor = m.ring_source == LOAMX_RING_FROM_BOUNDS ? (float)((int)m.n_scan_rings - 1) / (m.upper_bound_deg - m.lower_bound_deg) : 0.f;
+  sp.M = {lower, upper, (float)((int)n_rings - 1) / (upper - lower), n_rings};   // (nScanRings - 1) / (upperBound - lowerBound), :41-50
+  return sp;
+}
+
+SensorParams sensor_params(const loamx_sensor_model& m) {
+  SensorParams sp = mapper_params(m.lower_bound_deg, m.upper_bound_deg, m.n_scan_rings);
+  if (m.ring_source != LOAMX_RING_FROM_BOUNDS) sp.M.factor = 0.f;   // (the bounds are not read, and not checked either)
   sp.ring_src = (int)m.ring_source;
   sp.time_src = (int)m.time_source;
-  for (uint32_t k = 0; k < RawBinner::MAX_RINGS; k++)
-    sp.table[k] = m.ring_source == LOAMX_RING_FROM_TABLE && k < m.n_scan_rings ? m.ring_angles_deg[k] : 0.f;
+  for (uint32_t k = 0; m.ring_source == LOAMX_RING_FROM_TABLE && k < m.n_scan_rings; k++) sp.table[k] = m.ring_angles_deg[k];
   sp.max_err = m.max_angle_error_deg;
   sp.ring_off = m.ring_offset; sp.ring_type = m.ring_type;
   sp.time_off = m.time_offset; sp.time_type = m.time_type;
@@ -555,83 +519,59 @@ SensorParams sensor_params(const loamx_sensor_model& m) {
   return sp;
 }
 
-void RawBinner::run(const float4* d_raw, uint32_t n, const MapperParams& m, float scan_period, float4* d_out, uint32_t* d_ring_cnt,
-                    const ImuTable* imu, ImuLast* d_last) {
-  LX_REQUIRE(m.n_rings >= 1 && m.n_rings <= MAX_RINGS, "n_scan_rings must be in [1, 256]");
-  if (n == 0) {
-    LX_HIP(hipMemsetAsync(d_ring_cnt, 0, sizeof(uint32_t) * m.n_rings, st_));
-    return;
-  }
-  const uint32_t nb = (n + 255) / 256;
-  ring_of_.reserve(n + 1);
-  blk_cnt_.reserve((size_t)nb * m.n_rings + 1);
-  blk_pre_.reserve((size_t)nb * m.n_rings + 1);
-  scratch_.reserve(8);
-  ImuTable I;
-  if (imu) I = *imu;
-  LX_REQUIRE(I.H <= 4096, "IMU history longer than 4096 states");
-  imu_first_.reserve(I.H + 1);
-  hipLaunchKernelGGL(k_raw_init, dim3((I.H + 256) / 256), dim3(256), 0, st_, d_raw, n, scratch_.p, imu_first_.p, I.H);
-  blk_idx_.reserve(2 * (size_t)nb + 2);
-  hipLaunchKernelGGL(k_raw_classify, dim3(nb), dim3(256), 0, st_, d_raw, n, m, ring_of_.p, blk_cnt_.p, scratch_.p, blk_idx_.p, blk_idx_.p + nb);
-  hipLaunchKernelGGL(k_raw_colscan, dim3(m.n_rings), dim3(256), 0, st_, blk_cnt_.p, nb, m.n_rings, blk_pre_.p, d_ring_cnt, blk_idx_.p,
-                     blk_idx_.p + nb, scratch_.p);
-  if (I.H) {
-    hipLaunchKernelGGL(k_raw_imu_need, dim3(nb), dim3(256), 0, st_, d_raw, n, scan_period, ring_of_.p, scratch_.p, I, imu_first_.p);
-    hipLaunchKernelGGL(k_raw_imu_suffix, dim3(1), dim3(1024), 0, st_, imu_first_.p, I.H);
-  }
-  hipLaunchKernelGGL(k_raw_scatter, dim3(nb), dim3(256), 0, st_, d_raw, n, m, scan_period, ring_of_.p, blk_pre_.p, d_ring_cnt, scratch_.p,
-                     d_out, I, imu_first_.p, d_last);
-  LX_HIP(hipGetLastError());
-}
-
 void RawBinner::run(const float4* d_raw, uint32_t n, const SensorParams& sp, float scan_period, float4* d_out, uint32_t* d_ring_cnt,
                     const ImuTable* imu, ImuLast* d_last) {
-  if (sp.ring_src == RING_BOUNDS && sp.time_src == TIME_AZIMUTH) return run(d_raw, n, sp.M, scan_period, d_out, d_ring_cnt, imu, d_last);
-  const MapperParams& m = sp.M;
-  LX_REQUIRE(m.n_rings >= 1 && m.n_rings <= MAX_RINGS, "n_scan_rings must be in [1, 256]");
+  const uint32_t nr = sp.M.n_rings;
+  check_ring_count(nr);
   if (n == 0) {
-    LX_HIP(hipMemsetAsync(d_ring_cnt, 0, sizeof(uint32_t) * m.n_rings, st_));
+    LX_HIP(hipMemsetAsync(d_ring_cnt, 0, sizeof(uint32_t) * nr, st_));
     return;
   }
-  const bool tfield = sp.time_src == TIME_FIELD;
-  const uint32_t nb = (n + 255) / 256;
+  const dim3 grid((n + 255) / 256), block(256);
+  const uint32_t nb = grid.x;
   ring_of_.reserve(n + 1);
-  blk_cnt_.reserve((size_t)nb * m.n_rings + 1);
-  blk_pre_.reserve((size_t)nb * m.n_rings + 1);
+  blk_cnt_.reserve((size_t)nb * nr + 1);
+  blk_pre_.reserve((size_t)nb * nr + 1);
+  blk_idx_.reserve(2 * (size_t)nb + 2);
   scratch_.reserve(8);
-  blk_tmin_.reserve((size_t)nb + 1);
-  tref_.reserve(1);
+  if (sp.time_src == TIME_FIELD) {
+    blk_tmin_.reserve((size_t)nb + 1);
+    tref_.reserve(1);
+  }
   ImuTable I;
   if (imu) I = *imu;
   LX_REQUIRE(I.H <= 4096, "IMU history longer than 4096 states");
   imu_first_.reserve(I.H + 1);
-  const TimeField tf{sp.time_fld, tref_.p, sp.time_scale};
-  hipLaunchKernelGGL(k_raw_init, dim3((I.H + 256) / 256), dim3(256), 0, st_, d_raw, n, scratch_.p, imu_first_.p, I.H);
-  blk_idx_.reserve(2 * (size_t)nb + 2);
-#define LX_SNS_CLASSIFY(RS, TS) \
-  hipLaunchKernelGGL((k_sns_classify<RS, TS>), dim3(nb), dim3(256), 0, st_, d_raw, n, sp, ring_of_.p, blk_cnt_.p, scratch_.p, blk_idx_.p, blk_idx_.p + nb, blk_tmin_.p)
-  if (sp.ring_src == RING_BOUNDS) LX_SNS_CLASSIFY(RING_BOUNDS, TIME_FIELD);   // (BOUNDS + AZIMUTH took the mapper path above)
-  else if (sp.ring_src == RING_TABLE && tfield) LX_SNS_CLASSIFY(RING_TABLE, TIME_FIELD);
-  else if (sp.ring_src == RING_TABLE) LX_SNS_CLASSIFY(RING_TABLE, TIME_AZIMUTH);
-  else if (tfield) LX_SNS_CLASSIFY(RING_FIELD, TIME_FIELD);
-  else LX_SNS_CLASSIFY(RING_FIELD, TIME_AZIMUTH);
-#undef LX_SNS_CLASSIFY
-  // (with TIME_AZIMUTH the rest is the mapper path's kernels: they only read the ring ids classify left behind)
-  if (tfield) hipLaunchKernelGGL(k_sns_tref, dim3(1), dim3(256), 0, st_, blk_tmin_.p, nb, tref_.p);
-  hipLaunchKernelGGL(k_raw_colscan, dim3(m.n_rings), dim3(256), 0, st_, blk_cnt_.p, nb, m.n_rings, blk_pre_.p, d_ring_cnt, blk_idx_.p,
-                     blk_idx_.p + nb, scratch_.p);
-  if (I.H) {
-    if (tfield) hipLaunchKernelGGL(k_sns_imu_need, dim3(nb), dim3(256), 0, st_, n, scan_period, ring_of_.p, I, imu_first_.p, tf);
-    else hipLaunchKernelGGL(k_raw_imu_need, dim3(nb), dim3(256), 0, st_, d_raw, n, scan_period, ring_of_.p, scratch_.p, I, imu_first_.p);
-    hipLaunchKernelGGL(k_raw_imu_suffix, dim3(1), dim3(1024), 0, st_, imu_first_.p, I.H);
-  }
-  if (tfield)
-    hipLaunchKernelGGL(k_sns_scatter, dim3(nb), dim3(256), 0, st_, d_raw, n, m.n_rings, scan_period, ring_of_.p, blk_pre_.p, d_ring_cnt, scratch_.p,
-                       d_out, I, imu_first_.p, d_last, tf);
-  else
-    hipLaunchKernelGGL(k_raw_scatter, dim3(nb), dim3(256), 0, st_, d_raw, n, m, scan_period, ring_of_.p, blk_pre_.p, d_ring_cnt, scratch_.p,
-                       d_out, I, imu_first_.p, d_last);
+  hipLaunchKernelGGL(k_raw_init, dim3((I.H + 256) / 256), block, 0, st_, d_raw, n, scratch_.p, imu_first_.p, I.H);
+  // the launches of one sweep, for the time source `time` (the mapper path is BoundsRing + AzimuthTime)
+  auto bin = [&](auto time) {
+    using Time = decltype(time);
+    auto classify = [&](auto ring) {
+      hipLaunchKernelGGL((k_raw_classify<decltype(ring), Time>), grid, block, 0, st_, d_raw, n, ring, time, ring_of_.p, blk_cnt_.p, blk_idx_.p,
+                         blk_idx_.p + nb, blk_tmin_.p);
+    };
+    if (sp.ring_src == RING_BOUNDS) {
+      classify(BoundsRing{sp.M});
+    } else if (sp.ring_src == RING_TABLE) {
+      TableRing tr;
+      memcpy(tr.table, sp.table, sizeof(tr.table));
+      tr.max_err = sp.max_err;
+      tr.n_rings = nr;
+      classify(tr);
+    } else {
+      classify(FieldRing{sp.ring_fld, nr});
+    }
+    if (Time::src == TIME_FIELD) hipLaunchKernelGGL(k_sns_tref, dim3(1), block, 0, st_, blk_tmin_.p, nb, tref_.p);
+    hipLaunchKernelGGL(k_raw_colscan, dim3(nr), block, 0, st_, blk_cnt_.p, nb, nr, blk_pre_.p, d_ring_cnt, blk_idx_.p, blk_idx_.p + nb, scratch_.p);
+    if (I.H) {
+      hipLaunchKernelGGL(k_raw_imu_need<Time>, grid, block, 0, st_, n, scan_period, ring_of_.p, I, imu_first_.p, time);
+      hipLaunchKernelGGL(k_raw_imu_suffix, dim3(1), dim3(1024), 0, st_, imu_first_.p, I.H);
+    }
+    hipLaunchKernelGGL(k_raw_scatter<Time>, grid, block, 0, st_, d_raw, n, nr, scan_period, ring_of_.p, blk_pre_.p, d_ring_cnt, scratch_.p, d_out, I,
+                       imu_first_.p, d_last, time);
+  };
+  if (sp.time_src == TIME_FIELD) bin(FieldTime{sp.time_fld, tref_.p, sp.time_scale});
+  else bin(AzimuthTime{d_raw, scratch_.p});
   LX_HIP(hipGetLastError());
 }
 

@@ -1,6 +1,7 @@
 // Raw-sweep ingestion: MultiScanRegistration::process, src/lib/MultiScanRegistration.cpp:160-238 —
 // axis remap, NaN / zero / out-of-field rejection, vertical angle -> ring (MultiScanMapper :41-66), azimuth -> relTime
-// with the halfPassed unwrapping, stable split into per-ring clouds.
+// with the halfPassed unwrapping, stable split into per-ring clouds.  Other lidars bring their ring from a table of elevations or a
+// ring field and their relTime from a time field (SensorParams); one set of kernels serves every combination.
 #pragma once
 #include "common.h"
 
@@ -29,38 +30,40 @@ struct ImuLast {
   uint32_t idx, valid;
 };
 
-// device-side re-striding of a raw payload (x, y, z at 0 / 4 / 8 of every `stride` bytes) into float4 records
-void raw_unpack(const void* d_bytes, uint32_t stride, uint32_t n, float4* d_out, hipStream_t st);
-
-// Sensor model (loamx_sensor_model, include/loamx.h) as the kernels see it: where a record's ring and relTime come from
+// Sensor model (loamx_sensor_model, include/loamx.h) as the kernels see it: where a record's ring and relTime come from.  The
+// reference's mapper is the model RING_BOUNDS + TIME_AZIMUTH.
 enum RingSrc : int { RING_BOUNDS = 0, RING_TABLE = 1, RING_FIELD = 2 };
 enum TimeSrc : int { TIME_AZIMUTH = 0, TIME_FIELD = 1 };
 struct SensorParams {
   MapperParams M;                        // n_rings always; lower / upper / factor for RING_BOUNDS
   int ring_src = RING_BOUNDS, time_src = TIME_AZIMUTH;
-  float table[256];                      // RING_TABLE: n_rings elevations (degrees, strictly increasing)
+  float table[256] = {};                 // RING_TABLE: n_rings elevations (degrees, strictly increasing)
   float max_err = 0;                     // RING_TABLE: max_angle_error_deg
   uint32_t ring_off = 0, ring_type = 0, time_off = 0, time_type = 0;   // field offsets in the record, LOAMX_FIELD_*
   double time_scale = 1;                 // TIME_FIELD: seconds per unit
-  const uint32_t* ring_fld = nullptr;    // [n] device: the ring field of every record (RING_FIELD; filled by sensor_unpack)
-  const double* time_fld = nullptr;      // [n] device: the time field of every record (TIME_FIELD; filled by sensor_unpack)
+  uint32_t* ring_fld = nullptr;          // [n] device: the ring field of every record (RING_FIELD; filled by unpack_records)
+  double* time_fld = nullptr;            // [n] device: the time field of every record (TIME_FIELD; filled by unpack_records)
 };
+// the checks of a raw entry point that takes the reference's mapper, and the mapper as SensorParams (MultiScanMapper::set,
+// MultiScanRegistration.cpp:41-50); throws LOAMX_E_INVALID
+void mapper_check(float lower, float upper, uint32_t n_rings, uint32_t stride);
+SensorParams mapper_params(float lower, float upper, uint32_t n_rings);
 // validated model (loamx_sensor_model_check) -> SensorParams without the device arrays; throws LOAMX_E_INVALID
 void sensor_model_check(const loamx_sensor_model& m, uint32_t stride);
 SensorParams sensor_params(const loamx_sensor_model& m);
-// records -> float4 (x, y, z, 0) and, where the model reads them, the ring field (d_ring) and the time field as a double (d_time)
-void sensor_unpack(const void* d_bytes, uint32_t stride, uint32_t n, const SensorParams& sp, float4* d_out, uint32_t* d_ring, double* d_time,
-                   hipStream_t st);
+// records (x, y, z float32 at byte offsets 0 / 4 / 8 of every `stride` bytes; the payload crosses PCIe as it came) -> float4 (x, y, z, 0)
+// and, where the model reads them, the ring field (sp.ring_fld) and the time field as a double (sp.time_fld): k_raw_unpack for a
+// model that reads no field, k_sensor_unpack otherwise
+void unpack_records(const void* d_bytes, uint32_t stride, uint32_t n, const SensorParams& sp, float4* d_out, hipStream_t st);
 
 class RawBinner {
  public:
   static constexpr uint32_t MAX_RINGS = 256;
   void init(hipStream_t st) { st_ = st; }
-  // d_raw: n records (x, y, z, unused) in sensor axes and firing order.  d_out (capacity n): the kept points in the LOAM
-  // frame, rings concatenated, intensity = ring + relTime.  d_ring_cnt[n_rings]: points per ring.  Asynchronous.
-  void run(const float4* d_raw, uint32_t n, const MapperParams& m, float scan_period, float4* d_out, uint32_t* d_ring_cnt,
-           const ImuTable* imu = nullptr, ImuLast* d_last = nullptr);
-  // the same with a sensor model (sp.ring_fld / sp.time_fld: this sweep's unpacked fields); BOUNDS + AZIMUTH runs the path above
+  // d_raw: n records (x, y, z, unused) in sensor axes and firing order; sp.ring_fld / sp.time_fld: this sweep's unpacked fields.
+  // d_out (capacity n): the kept points in the LOAM frame, rings concatenated, intensity = ring + relTime.  d_ring_cnt[n_rings]:
+  // points per ring.  Asynchronous.  Launches k_raw_init, k_raw_classify<ring, time>, (TIME_FIELD: k_sns_tref,) k_raw_colscan, (with
+  // IMU data: k_raw_imu_need<time>, k_raw_imu_suffix,) k_raw_scatter<time>.
   void run(const float4* d_raw, uint32_t n, const SensorParams& sp, float scan_period, float4* d_out, uint32_t* d_ring_cnt,
            const ImuTable* imu = nullptr, ImuLast* d_last = nullptr);
 

@@ -403,13 +403,8 @@ class Pipeline {
   void stage_step_raw(uint32_t t, const void* const* raw_xyz, const uint32_t* counts, uint32_t stride, const loamx_multiscan_mapper& mapper,
                       const double* scan_time) {
     LX_REQUIRE(raw_xyz && counts, "invalid argument");
-    LX_REQUIRE(stride >= 12 && stride % 4 == 0, "raw stride must be a multiple of 4 and at least 12");
-    LX_REQUIRE(mapper.n_scan_rings >= 1 && mapper.n_scan_rings <= RawBinner::MAX_RINGS, "n_scan_rings must be in [1, 256]");
-    LX_REQUIRE(mapper.upper_bound_deg != mapper.lower_bound_deg, "vertical bounds must differ");
-    SensorParams sp;
-    sp.M.lower = mapper.lower_bound_deg; sp.M.upper = mapper.upper_bound_deg; sp.M.n_rings = mapper.n_scan_rings;
-    sp.M.factor = (float)((int)mapper.n_scan_rings - 1) / (mapper.upper_bound_deg - mapper.lower_bound_deg);   // MultiScanRegistration.cpp:41-50
-    stage_records_(t, raw_xyz, counts, stride, sp, scan_time);
+    mapper_check(mapper.lower_bound_deg, mapper.upper_bound_deg, mapper.n_scan_rings, stride);
+    stage_records_(t, raw_xyz, counts, stride, mapper_params(mapper.lower_bound_deg, mapper.upper_bound_deg, mapper.n_scan_rings), scan_time);
   }
   // the same with a sensor model (loamx_sensor_model): ring and relTime from the model's sources, the records unpacked on the device
   void stage_step_sensor(uint32_t t, const void* const* records, const uint32_t* counts, uint32_t stride, const loamx_sensor_model& model,
@@ -424,7 +419,6 @@ class Pipeline {
     TraceRange trace_range("loamx:pipeline:stage_step_raw");
     if (t > 0) finalize_raw(t - 1);   // the IMU state machine advances sweep by sweep: this step's table needs the previous reset
     const uint32_t ns = n_streams_, nr = model.M.n_rings;
-    const bool mapper_path = model.ring_src == RING_BOUNDS && model.time_src == TIME_AZIMUTH;
     RawSlot& R = rawslot[t % RING];
     R.raw = true;
     R.finalized = false;
@@ -481,20 +475,12 @@ class Pipeline {
     for (uint32_t s = 0; s < ns; s++) {
       const uint32_t n = counts[s];
       if (n) LX_HIP(hipMemcpyAsync(R.d_bytes.p + (size_t)R.off[s] * stride, raw_xyz[s], (size_t)n * stride, hipMemcpyHostToDevice, cstream));
-      if (mapper_path) {
-        raw_unpack(R.d_bytes.p + (size_t)R.off[s] * stride, stride, n, R.d_raw4.p + R.off[s], cstream);
-        binner.run(R.d_raw4.p + R.off[s], n, model.M, fcfg.scan_period, R.d_binned.p + R.off[s], R.d_ring_cnt.p + (size_t)s * nr,
-                   R.imu_H[s] ? &tables[s] : nullptr, R.imu_H[s] ? R.d_last.p + s : nullptr);
-      } else {
-        uint32_t* d_ring = model.ring_src == RING_FIELD ? R.d_ring_fld.p + R.off[s] : nullptr;
-        double* d_time = model.time_src == TIME_FIELD ? R.d_time_fld.p + R.off[s] : nullptr;
-        SensorParams sp = model;
-        sp.ring_fld = d_ring;
-        sp.time_fld = d_time;
-        sensor_unpack(R.d_bytes.p + (size_t)R.off[s] * stride, stride, n, sp, R.d_raw4.p + R.off[s], d_ring, d_time, cstream);
-        binner.run(R.d_raw4.p + R.off[s], n, sp, fcfg.scan_period, R.d_binned.p + R.off[s], R.d_ring_cnt.p + (size_t)s * nr,
-                   R.imu_H[s] ? &tables[s] : nullptr, R.imu_H[s] ? R.d_last.p + s : nullptr);
-      }
+      SensorParams sp = model;
+      sp.ring_fld = model.ring_src == RING_FIELD ? R.d_ring_fld.p + R.off[s] : nullptr;
+      sp.time_fld = model.time_src == TIME_FIELD ? R.d_time_fld.p + R.off[s] : nullptr;
+      unpack_records(R.d_bytes.p + (size_t)R.off[s] * stride, stride, n, sp, R.d_raw4.p + R.off[s], cstream);
+      binner.run(R.d_raw4.p + R.off[s], n, sp, fcfg.scan_period, R.d_binned.p + R.off[s], R.d_ring_cnt.p + (size_t)s * nr,
+                 R.imu_H[s] ? &tables[s] : nullptr, R.imu_H[s] ? R.d_last.p + s : nullptr);
     }
     LX_HIP(hipMemcpyAsync(R.h_ring_cnt.p, R.d_ring_cnt.p, sizeof(uint32_t) * ns * nr, hipMemcpyDeviceToHost, cstream));
     LX_HIP(hipMemcpyAsync(R.h_last.p, R.d_last.p, sizeof(ImuLast) * ns, hipMemcpyDeviceToHost, cstream));

@@ -584,36 +584,24 @@ class ScanRegistration:
         """loamx_scanreg_process_raw: MultiScanRegistration::process on a raw (n,3) firing-order cloud in sensor axes.
         mapper = (lower_deg, upper_deg, n_rings) overrides the sensor preset.  Adds "full" and "ring_sizes"."""
         raw = np.ascontiguousarray(raw_xyz, np.float32).reshape(-1, 3)
-        m = MultiScanMapper()
-        if mapper is None:
-            _check(lib().loamx_multiscan_mapper_preset(sensor.encode(), C.byref(m)))
-        else:
-            m.lower_bound_deg, m.upper_bound_deg, m.n_scan_rings = float(mapper[0]), float(mapper[1]), int(mapper[2])
-        n = len(raw)
-        outs = [np.zeros((max(n, 1), 4), np.float32) for _ in range(5)]
-        cl = [cloud_of(o) for o in outs]
-        rs = np.zeros(max(int(m.n_scan_rings), 1), np.uint32)
-        _check(lib().loamx_scanreg_process_raw(self.h, C.byref(m), raw.ctypes.data_as(C.c_void_p), n, 12, C.byref(cl[4]),
-                                               rs.ctypes.data_as(C.c_void_p), C.byref(cl[0]), C.byref(cl[1]), C.byref(cl[2]),
-                                               C.byref(cl[3])))
-        res = {name: outs[k][:cl[k].count].copy() for k, name in enumerate(self.NAMES)}
-        res["full"] = outs[4][:cl[4].count].copy()
-        res["ring_sizes"] = rs.astype(np.int32)
-        return res
+        return self._process_records(lib().loamx_scanreg_process_raw, _mapper(sensor, mapper), raw.ctypes.data_as(C.c_void_p), len(raw), 12)
 
     def process_sensor(self, records, model: SensorModel):
         """loamx_scanreg_process_sensor: process_raw with a sensor model.  records: a structured array (itemsize = stride, x, y, z
         float32 first) or an (n, 3) float32 array.  Same results as process_raw."""
         a, n, stride = as_records(records)
+        return self._process_records(lib().loamx_scanreg_process_sensor, model, a.ctypes.data_as(C.c_void_p) if n else None, n, stride)
+
+    def _process_records(self, entry, model, data, n, stride):
+        """entry(handle, mapper or model, records, ...): landing buffers for n points, the call, the results as copies"""
         outs = [np.zeros((max(n, 1), 4), np.float32) for _ in range(5)]
         cl = [cloud_of(o) for o in outs]
         rs = np.zeros(max(int(model.n_scan_rings), 1), np.uint32)
-        _check(lib().loamx_scanreg_process_sensor(self.h, C.byref(model), a.ctypes.data_as(C.c_void_p) if n else None, n, stride,
-                                                  C.byref(cl[4]), rs.ctypes.data_as(C.c_void_p), C.byref(cl[0]), C.byref(cl[1]),
-                                                  C.byref(cl[2]), C.byref(cl[3])))
+        _check(entry(self.h, C.byref(model), data, n, stride, C.byref(cl[4]), rs.ctypes.data_as(C.c_void_p), C.byref(cl[0]), C.byref(cl[1]),
+                     C.byref(cl[2]), C.byref(cl[3])))
         res = {name: outs[k][:cl[k].count].copy() for k, name in enumerate(self.NAMES)}
         res["full"] = outs[4][:cl[4].count].copy()
-        res["ring_sizes"] = rs[:model.n_scan_rings].astype(np.int32)
+        res["ring_sizes"] = rs.astype(np.int32)
         return res
 
 

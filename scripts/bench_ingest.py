@@ -33,8 +33,8 @@ for imu in (() if os.environ.get("BENCH_INGEST_MODE") else (False, True)):   # (
           (imu, n, tg * 1e3, "bin+features" if imu else "bin only", to * 1e3))
 
 # sensor models (loamx_scanreg_process_sensor) on the same HDL-64E revolution, 131,072 points as PointXYZIRT-style records (stride 32)
-# or ring-major Ouster-style records (stride 48).  Binning kernels: k_raw_unpack / k_sensor_unpack, k_raw_classify /
-# k_sns_classify<ring, time>, k_raw_colscan (+ k_sns_tref), k_raw_scatter / k_sns_scatter.  For per-mode kernel times run one mode
+# or ring-major Ouster-style records (stride 48).  Binning kernels: k_raw_unpack / k_sensor_unpack, k_raw_init,
+# k_raw_classify<ring, time>, (k_sns_tref,) k_raw_colscan, k_raw_scatter<time>.  For per-mode kernel times run one mode
 # per rocprofv3 --kernel-trace --stats run: BENCH_INGEST_MODE=<mode> (the modes share kernels).
 R = synth.SENSORS["HDL-64E"][0]
 vel = synth.to_records(sw, "velodyne", bad_every=64)
