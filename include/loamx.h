@@ -970,6 +970,83 @@ int loamx_densemap_align_many_from_pipeline(loamx_densemap* h, loamx_pipeline* p
 int loamx_densemap_align_best(const loamx_densemap_align_result* results, uint32_t n, uint32_t* best);   /* host only, no device */
 int loamx_densemap_get_align_stats(loamx_densemap* h, uint64_t stats[3]);
 
+/* Coarser levels and coarse-to-fine alignment (optional: a handle that never calls these runs the kernels it ran and allocates what
+ * it allocated).  loamx_densemap_align finds its correspondences in the point's own cell or its 27 neighbours, at the map's one leaf:
+ * a start more than about a leaf and a half off matches nothing, or the wrong wall.  A coarser copy of the map has a wider basin and
+ * a blunter minimum; aligning against the coarse copy first and handing the pose down level by level has both the reach of the coarse
+ * level and the accuracy of the fine one.
+ *
+ * Levels.  A level-l voxel (l >= 1) has the leaf leaf * 2^l (one f32 multiply by a power of two) and the indices I = i >> 1 of its
+ * level-(l-1) children (level 0 is the map; the shift is arithmetic: floor for negative indices).  Its thirteen words are the sums,
+ * over the children it has, of these per-child integers, with b_a = i_a & 1 and n, S, M, V the child's words:
+ *     n'    += n
+ *     S'_a  += (S_a >> 1) + n * b_a * 2^19
+ *     M'_ab += (M_ab >> 2) + b_a * 2^18 * S_b + b_b * 2^18 * S_a + n * b_a * b_b * 2^38     (mod 2^64, as M)
+ *     V'_a  += V_a                                                                          (signed, as V)
+ * This is the child's sum of q and of q_a q_b re-expressed in the parent's own 20-bit units, q' = q/2 + b * 2^19, with one floor per
+ * child and word.  So a level-l voxel has exactly the format of a level-0 voxel whose leaf is leaf * 2^l; its offsets stay below 2^20;
+ * its sums are exact while it holds fewer than 2^24 points; loamx_densemap_surfel_of(leaf * 2^l, I, vals, mom, ...) gives its surfel;
+ * and every word is an integer sum that depends on no order.  For points whose offsets are even at every level (coordinates that are
+ * multiples of leaf / 2^(20 - l)) every floor is a no-op and level l is, word for word, the map a handle of leaf * 2^l builds.
+ * Level 1 is taken from the map's table and leaves out the voxels the rule calls dynamic (rule NULL: every voxel; a rule needs
+ * carving); level l + 1 is taken from level l.  One kernel, k_dm_coarsen, serves every level: one thread per source slot; an occupied,
+ * selected slot finds or claims its parent's key in a fresh table and adds its thirteen integers with 64-bit atomics.  The fresh table
+ * has the smallest power of two of slots that is >= 2 * the source's occupancy and >= 1024, so it never grows; a probe bound reached
+ * is LOAMX_E_INTERNAL.  The live table is only read.
+ *
+ * loamx_densemap_coarsen: waits for the adds as download does, runs the cascade up to `level` (1 .. LOAMX_PYRAMID_MAX_LEVELS - 1) and
+ * returns that level's voxels in ascending key order: keys[i], vals[4 i ..] = n, Sx, Sy, Sz, mom[9 i ..] in the order of
+ * download_moments.  *n = voxels; LOAMX_E_CAPACITY, nothing written, when capacity < *n (keys, vals, mom may be NULL with capacity 0).
+ * Needs moments.  With loamx_densemap_surfel_of it is a coarser surfel export.
+ *
+ * loamx_densemap_freeze_pyramid: `levels` snapshots (1 .. LOAMX_PYRAMID_MAX_LEVELS, default 3).  Level 0 is built by the code of
+ * loamx_densemap_freeze with the same cfg / rule and is byte for byte that snapshot; with levels == 1 the call is loamx_densemap_freeze
+ * (no further launch, no further copy).  Level l >= 1 is a snapshot of its own with the same entry format and slot rule: the voxels
+ * of level l that have a surfel under cfg at the leaf leaf * 2^l, under the level's own keys; with max_curvature > 0 a voxel whose
+ * surfel has a larger curvature gets no entry (a coarse voxel that spans a corner is no plane; 0 = no limit; level 0 is not
+ * filtered).  n_surfels (may be NULL) receives `levels` entry counts.  loamx_densemap_freeze, loamx_densemap_reset and destroy drop the
+ * coarse levels.  loamx_densemap_frozen_levels: how many levels stand, 0 = nothing frozen, 1 after a plain freeze.
+ *
+ * loamx_densemap_align_select_level: every alignment form above (align_step, align_step_many, align, align_many and their from_*
+ * forms) reads the table of the selected level, with inv = 1.0f / (leaf * 2^level) and max_residual 0 meaning that level's leaf; the
+ * kernels are the same.  The selection is 0 after every freeze of either kind and after reset; a level that does not stand is
+ * LOAMX_E_INVALID.  With the selection at 0 every word of every call above is what it was.  loamx_densemap_get_align_stats sums
+ * over the levels.
+ *
+ * loamx_densemap_align_pyramid: for level = first_level down to 0 the loop of loamx_densemap_align against that level; the start is
+ * pose_in for the first level and after that the pose the level before reported (after status 2 that is its last good pose, so a level
+ * that matched too little hands its input on).  out[k] is the result at level first_level - k (first_level + 1 results), byte for
+ * byte what loamx_densemap_align_select_level(level) + loamx_densemap_align returns from the same start: that is the definition.  cfg
+ * is applied at every level (max_residual 0: each level's leaf).  The cloud is staged once.  The selected level is neither read nor
+ * changed.  The from_* forms as align_from_*: pose_in NULL is the identity, LOAMX_SKIPPED without a cloud.
+ * A pyramid over many start poses composes from align_select_level and align_many.
+ *
+ * LOAMX_E_INVALID, with a message, nothing written and the handle unchanged: a NULL argument (rule, cfg, pyramid, centre, n_surfels
+ * and the from_* forms' pose_in excepted); level 0 or >= LOAMX_PYRAMID_MAX_LEVELS for coarsen; levels outside 1 ..
+ * LOAMX_PYRAMID_MAX_LEVELS; a negative (or NaN) max_curvature; moments off; a rule without carving; a level or first_level that does
+ * not stand; cfg as for loamx_densemap_align at any of the levels; a pose that is not finite. */
+#define LOAMX_PYRAMID_MAX_LEVELS 6
+typedef struct loamx_densemap_pyramid_config {
+  uint32_t levels;        /* snapshots to build, 1 .. LOAMX_PYRAMID_MAX_LEVELS (default 3) */
+  float max_curvature;    /* levels >= 1: no entry for a surfel with a larger curvature; >= 0, 0 = no limit (default 0) */
+} loamx_densemap_pyramid_config;
+void loamx_densemap_pyramid_default_config(loamx_densemap_pyramid_config* cfg);   /* host only */
+int loamx_densemap_coarsen(loamx_densemap* h, uint32_t level, const loamx_densemap_static_rule* rule /* NULL: every voxel */,
+                           uint64_t* keys, uint64_t* vals /* 4 per voxel */, uint64_t* mom /* 9 per voxel */, uint64_t capacity,
+                           uint64_t* n);
+int loamx_densemap_freeze_pyramid(loamx_densemap* h, const loamx_densemap_surfel_config* cfg, const loamx_densemap_static_rule* rule,
+                                  const loamx_densemap_pyramid_config* pyramid /* NULL: the defaults */, uint64_t* n_surfels /* levels */);
+int loamx_densemap_frozen_levels(loamx_densemap* h, uint32_t* levels);
+int loamx_densemap_align_select_level(loamx_densemap* h, uint32_t level);
+int loamx_densemap_align_pyramid(loamx_densemap* h, const loamx_cloud* points, const double pose_in[12], const float centre[3] /* NULL: 0 */,
+                                 const loamx_densemap_align_config* cfg, uint32_t first_level,
+                                 loamx_densemap_align_result* out /* first_level + 1 */);
+int loamx_densemap_align_pyramid_from_map(loamx_densemap* h, loamx_map* m, const double pose_in[12] /* NULL: identity */,
+                                          const loamx_densemap_align_config* cfg, uint32_t first_level, loamx_densemap_align_result* out);
+int loamx_densemap_align_pyramid_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot, const double pose_in[12],
+                                               const loamx_densemap_align_config* cfg, uint32_t first_level,
+                                               loamx_densemap_align_result* out);
+
 /* A prior map: native save / load, and the exact merge of two maps (optional: a handle that never calls them runs the kernels it
  * ran).  Every word of a voxel is an integer sum, so the map can be written out and read back without loss, and two maps of the same
  * leaf can be combined by adding words per key.

@@ -9,6 +9,7 @@
 //   densemap_raycast.hip  first hits of rays through the table (DmCaster)
 //   densemap_rebuild.hip  the sweep log and its replay under corrected poses (densemap_history.hpp)
 //   densemap_align.hip    alignment of sweeps against the frozen surfel snapshot (DmFrozen)
+//   densemap_pyramid.hip  coarser levels of the table and of the snapshot, and the coarse-to-fine alignment over them
 //   densemap_grid.hip     a window of the table projected to a 2-D navigation grid (DmGrid)
 //   densemap_route.hip    cost-to-go field and routes over that grid (DmRoute, densemap_route_schedule.hpp)
 //   densemap_segment.hip  connected components of the voxels (DmSegment)
@@ -208,8 +209,10 @@ void DenseMap::stats(uint64_t out[6]) {
 
 void DenseMap::snapshot(Snapshot& S, bool want_mom) {
   read_counters();
-  const DmTable& T = tab_;
-  const uint64_t occ = occ_.occ;
+  snapshot_of(tab_, occ_.occ, S, want_mom);
+}
+
+void DenseMap::snapshot_of(const DmTable& T, uint64_t occ, Snapshot& S, bool want_mom) {
   const uint32_t nblk = (T.slots + 255) / 256;
   DevBuf<uint32_t> blk, scratch, omiss;
   DevBuf<unsigned long long> tiles, okeys, ovals, omom;
@@ -295,6 +298,7 @@ void DenseMap::reset() {
   clear(own_);
   LX_HIP(hipStreamSynchronize(own_));
   frozen.drop();
+  drop_coarse();
   occ_.reset();
   offered_ = drop_range_ = drop_key_ = 0;
   for (uint64_t& c : carve_ctr_) c = 0;

@@ -12,6 +12,10 @@
 // k_dm_align_step_many is the same linearisation about many poses at once, a second grid dimension over a table of poses in device
 // memory: one launch and one readback per iteration for all the start poses of loamx_densemap_align_many, which runs the Gauss-Newton
 // loops of its hypotheses in lockstep.  Both kernels compile from one text (dm_align_step_body.inc), so every word equals the single step's.
+//
+// Levels (densemap_pyramid.hip builds them): every form reads the snapshot DenseMap::level(align_level) with inv = 1 / level_leaf —
+// to the kernels a level is another table and another inv.  loamx_densemap_align_pyramid is the single loop per level, coarse to
+// fine, over a cloud staged once through level 0's buffers.
 #include "densemap_map.hpp"
 
 namespace loamx {
@@ -340,15 +344,16 @@ static void pose_must_be_finite(const double* P, size_t n_words) {
   for (size_t k = 0; k < n_words; k++) LX_REQUIRE(std::isfinite(P[k]), "the pose must be finite");
 }
 
-// the loop of include/loamx.h over a cloud that lies on the device; pose_in NULL: identity
+// the loop of include/loamx.h over a cloud that lies on the device, against the snapshot of `level` (c checked with that level's leaf);
+// pose_in NULL: identity
 static int align_loop(loamx_densemap* h, const float4* pts, uint32_t n, const double pose_in[12], const float centre[3],
-                      const loamx_densemap_align_config& c, hipStream_t st, loamx_densemap_align_result* out) {
+                      const loamx_densemap_align_config& c, hipStream_t st, uint32_t level, loamx_densemap_align_result* out) {
   if (pose_in) pose_must_be_finite(pose_in, 12);
   const double cc[3] = {centre ? (double)centre[0] : 0.0, centre ? (double)centre[1] : 0.0, centre ? (double)centre[2] : 0.0};
   AlignHyp hyp;
   hyp.begin(pose_in, cc, out);
-  DmFrozen& F = h->d.frozen;
-  const float inv = 1.0f / h->d.cfg.leaf;
+  DmFrozen& F = h->d.level(level);
+  const float inv = 1.0f / h->d.level_leaf(level);
   for (uint32_t it = 0; it < c.max_iterations; it++) {
     float rtc[15];
     hyp.rtc(cc, rtc);
@@ -381,8 +386,8 @@ static int align_many_loop(loamx_densemap* h, const float4* pts, uint32_t n, con
     hyp[k].begin(poses_in ? poses_in + 12 * (size_t)k : nullptr, cc, out + k);
     active[k] = k;
   }
-  DmFrozen& F = h->d.frozen;
-  const float inv = 1.0f / h->d.cfg.leaf;
+  DmFrozen& F = h->d.level(h->d.align_level);
+  const float inv = 1.0f / h->d.level_leaf(h->d.align_level);
   for (uint32_t it = 0; it < c.max_iterations && !active.empty(); it++) {
     const uint32_t n_active = (uint32_t)active.size();
     float* table = F.pose_table(n_active);
@@ -411,7 +416,7 @@ static bool align_source_ready(loamx_densemap* h, const DenseSource& s, const lo
                                hipStream_t& st) {
   const loamx_densemap_config& mc = h->d.cfg;
   LX_REQUIRE(s.device == mc.device, "the dense map and its source live on different devices");
-  c = checked_align_config(cfg, mc.leaf);
+  c = checked_align_config(cfg, h->d.level_leaf(h->d.align_level));
   LX_REQUIRE(h->d.frozen.valid(), "nothing is frozen (loamx_densemap_freeze)");
   if (!s.has_cloud) return false;
   LX_HIP(hipSetDevice(mc.device));
@@ -425,7 +430,7 @@ static int align_from_source(loamx_densemap* h, const DenseSource& s, const doub
   loamx_densemap_align_config c;
   hipStream_t st = nullptr;
   if (!align_source_ready(h, s, cfg, c, st)) return LOAMX_SKIPPED;
-  return align_loop(h, s.pts, s.n, pose_in, s.origin, c, st, out);
+  return align_loop(h, s.pts, s.n, pose_in, s.origin, c, st, h->d.align_level, out);
 }
 
 static void not_null(const void* p, const char* name) {
@@ -448,6 +453,38 @@ static int align_many_from_source(loamx_densemap* h, const DenseSource& s, const
   hipStream_t st = nullptr;
   if (!align_source_ready(h, s, cfg, c, st)) return LOAMX_SKIPPED;
   return align_many_loop(h, s.pts, s.n, poses_in, n_poses, s.origin, c, st, out, best);
+}
+
+// Coarse to fine (include/loamx.h, loamx_densemap_align_pyramid): the settings of every level first_level .. 0, each checked with its
+// own leaf before anything runs; c[k] belongs to level first_level - k
+static void checked_pyramid_configs(loamx_densemap* h, const loamx_densemap_align_config* cfg, uint32_t first_level,
+                                    loamx_densemap_align_config c[LOAMX_PYRAMID_MAX_LEVELS]) {
+  LX_REQUIRE(h->d.frozen.valid(), "nothing is frozen (loamx_densemap_freeze_pyramid)");
+  LX_REQUIRE(first_level < h->d.frozen_levels(), "first_level must be a level that stands (loamx_densemap_frozen_levels)");
+  for (uint32_t k = 0; k <= first_level; k++) c[k] = checked_align_config(cfg, h->d.level_leaf(first_level - k));
+}
+// the loop of align_loop against level first_level, then against each finer one from the pose the level before reported (after status
+// 2 that is its last good pose, its input when it had none).  The selected level is neither read nor changed
+static int align_pyramid_loop(loamx_densemap* h, const float4* pts, uint32_t n, const double pose_in[12], const float centre[3],
+                              const loamx_densemap_align_config* c, hipStream_t st, uint32_t first_level, loamx_densemap_align_result* out) {
+  const double* pose = pose_in;
+  for (uint32_t k = 0; k <= first_level; k++) {
+    align_loop(h, pts, n, pose, centre, c[k], st, first_level - k, out + k);
+    pose = out[k].pose;
+  }
+  return LOAMX_OK;
+}
+static int align_pyramid_from_source(loamx_densemap* h, const DenseSource& s, const double pose_in[12], const loamx_densemap_align_config* cfg,
+                                     uint32_t first_level, loamx_densemap_align_result* out) {
+  LX_REQUIRE(s.device == h->d.cfg.device, "the dense map and its source live on different devices");
+  loamx_densemap_align_config c[LOAMX_PYRAMID_MAX_LEVELS];
+  checked_pyramid_configs(h, cfg, first_level, c);
+  if (pose_in) pose_must_be_finite(pose_in, 12);
+  if (!s.has_cloud) return LOAMX_SKIPPED;
+  LX_HIP(hipSetDevice(h->d.cfg.device));
+  hipStream_t st = h->d.own_stream();
+  dm_stream_behind(st, s.stream);
+  return align_pyramid_loop(h, s.pts, s.n, pose_in, s.origin, c, st, first_level, out);
 }
 
 }  // namespace loamx
@@ -483,13 +520,13 @@ int loamx_densemap_align_step(loamx_densemap* h, const loamx_cloud* points, cons
     LX_REQUIRE(h && points && rtc && sums && counts, "NULL argument");
     LX_REQUIRE(neighbourhood <= 1u, "neighbourhood must be 0 or 1");
     LX_REQUIRE(max_residual > 0.f && max_residual <= 16.f, "max_residual must be in (0, 16]");   // (NaN too)
-    DmFrozen& F = h->d.frozen;
+    DmFrozen& F = h->d.level(h->d.align_level);
     LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
     const loamx_densemap_config& mc = h->d.cfg;
     LX_HIP(hipSetDevice(mc.device));
     hipStream_t st = h->d.own_stream();
-    const float4* pts = F.stage(points, st);
-    F.step(pts, points->count, rtc, 1.0f / mc.leaf, neighbourhood, max_residual, st, sums, counts);
+    const float4* pts = h->d.frozen.stage(points, st);
+    F.step(pts, points->count, rtc, 1.0f / h->d.level_leaf(h->d.align_level), neighbourhood, max_residual, st, sums, counts);
     return LOAMX_OK;
   });
 }
@@ -499,13 +536,13 @@ int loamx_densemap_align(loamx_densemap* h, const loamx_cloud* points, const dou
   return guard([&]() {
     LX_REQUIRE(h && points && pose_in && out, "NULL argument");
     const loamx_densemap_config& mc = h->d.cfg;
-    const loamx_densemap_align_config c = checked_align_config(cfg, mc.leaf);
+    const loamx_densemap_align_config c = checked_align_config(cfg, h->d.level_leaf(h->d.align_level));
     DmFrozen& F = h->d.frozen;
     LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
     LX_HIP(hipSetDevice(mc.device));
     hipStream_t st = h->d.own_stream();
     const float4* pts = F.stage(points, st);
-    return align_loop(h, pts, points->count, pose_in, centre, c, st, out);
+    return align_loop(h, pts, points->count, pose_in, centre, c, st, h->d.align_level, out);
   });
 }
 
@@ -520,18 +557,18 @@ int loamx_densemap_align_step_many(loamx_densemap* h, const loamx_cloud* points,
     LX_REQUIRE(n_poses >= 1u && n_poses <= LOAMX_ALIGN_MAX_POSES, "n_poses must be in [1, LOAMX_ALIGN_MAX_POSES]");
     LX_REQUIRE(neighbourhood <= 1u, "neighbourhood must be 0 or 1");
     LX_REQUIRE(max_residual > 0.f && max_residual <= 16.f, "max_residual must be in (0, 16]");   // (NaN too)
-    DmFrozen& F = h->d.frozen;
+    DmFrozen& F = h->d.level(h->d.align_level);
     LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
     const loamx_densemap_config& mc = h->d.cfg;
     LX_HIP(hipSetDevice(mc.device));
     hipStream_t st = h->d.own_stream();
-    const float4* pts = F.stage(points, st);
+    const float4* pts = h->d.frozen.stage(points, st);
     float* table = F.pose_table(n_poses);
     for (uint32_t k = 0; k < n_poses; k++) {
       for (int j = 0; j < 15; j++) table[16 * (size_t)k + j] = rtc[15 * (size_t)k + j];
       table[16 * (size_t)k + 15] = 0.f;
     }
-    const unsigned long long* w = F.step_many(pts, points->count, n_poses, 1.0f / mc.leaf, neighbourhood, max_residual, st);
+    const unsigned long long* w = F.step_many(pts, points->count, n_poses, 1.0f / h->d.level_leaf(h->d.align_level), neighbourhood, max_residual, st);
     for (uint32_t k = 0; k < n_poses; k++) {
       for (int j = 0; j < DM_ALIGN_SUMS; j++) sums[DM_ALIGN_SUMS * (size_t)k + j] = (int64_t)w[DM_ALIGN_WORDS * (size_t)k + j];
       for (int j = 0; j < DM_ALIGN_COUNTS; j++) counts[DM_ALIGN_COUNTS * (size_t)k + j] = w[DM_ALIGN_WORDS * (size_t)k + DM_ALIGN_SUMS + j];
@@ -549,7 +586,7 @@ int loamx_densemap_align_many(loamx_densemap* h, const loamx_cloud* points, cons
     not_null(out, "out");
     check_start_poses(poses_in, n_poses, false);
     const loamx_densemap_config& mc = h->d.cfg;
-    const loamx_densemap_align_config c = checked_align_config(cfg, mc.leaf);
+    const loamx_densemap_align_config c = checked_align_config(cfg, h->d.level_leaf(h->d.align_level));
     DmFrozen& F = h->d.frozen;
     LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
     LX_HIP(hipSetDevice(mc.device));
@@ -596,8 +633,9 @@ int loamx_densemap_get_align_stats(loamx_densemap* h, uint64_t stats[3]) {
   return guard([&]() {
     not_null(h, "h");
     not_null(stats, "stats");
-    const uint64_t* s = h->d.frozen.stats();
-    for (int k = 0; k < 3; k++) stats[k] = s[k];
+    for (int k = 0; k < 3; k++) stats[k] = 0;
+    for (uint32_t l = 0; l <= DenseMap::COARSE_LEVELS; l++)   // (a level's counters outlive its table)
+      for (int k = 0; k < 3; k++) stats[k] += h->d.level(l).stats()[k];
     return LOAMX_OK;
   });
 }
@@ -619,6 +657,57 @@ int loamx_densemap_align_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uin
     DenseSource s;
     loamx_pipeline_dense_source(p, slot, s);
     return align_from_source(h, s, pose_in, cfg, out);
+  });
+}
+
+int loamx_densemap_align_select_level(loamx_densemap* h, uint32_t level) {
+  return guard([&]() {
+    not_null(h, "h");
+    LX_REQUIRE(level < h->d.frozen_levels(), "level must be a level that stands (loamx_densemap_frozen_levels)");
+    h->d.align_level = level;
+    return LOAMX_OK;
+  });
+}
+
+int loamx_densemap_align_pyramid(loamx_densemap* h, const loamx_cloud* points, const double pose_in[12], const float centre[3],
+                                 const loamx_densemap_align_config* cfg, uint32_t first_level, loamx_densemap_align_result* out) {
+  return guard([&]() {
+    not_null(h, "h");
+    not_null(points, "points");
+    not_null(pose_in, "pose_in");
+    not_null(out, "out");
+    loamx_densemap_align_config c[LOAMX_PYRAMID_MAX_LEVELS];
+    checked_pyramid_configs(h, cfg, first_level, c);
+    pose_must_be_finite(pose_in, 12);
+    LX_HIP(hipSetDevice(h->d.cfg.device));
+    hipStream_t st = h->d.own_stream();
+    const float4* pts = h->d.frozen.stage(points, st);   // (staged once: every level's step reads it where level 0 put it)
+    return align_pyramid_loop(h, pts, points->count, pose_in, centre, c, st, first_level, out);
+  });
+}
+
+int loamx_densemap_align_pyramid_from_map(loamx_densemap* h, loamx_map* m, const double pose_in[12], const loamx_densemap_align_config* cfg,
+                                          uint32_t first_level, loamx_densemap_align_result* out) {
+  return guard([&]() {
+    not_null(h, "h");
+    not_null(m, "m");
+    not_null(out, "out");
+    DenseSource s;
+    loamx_map_dense_source(m, s);
+    return align_pyramid_from_source(h, s, pose_in, cfg, first_level, out);
+  });
+}
+
+int loamx_densemap_align_pyramid_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot, const double pose_in[12],
+                                               const loamx_densemap_align_config* cfg, uint32_t first_level,
+                                               loamx_densemap_align_result* out) {
+  return guard([&]() {
+    not_null(h, "h");
+    not_null(p, "p");
+    not_null(out, "out");
+    DenseSource s;
+    loamx_pipeline_dense_source(p, slot, s);
+    return align_pyramid_from_source(h, s, pose_in, cfg, first_level, out);
   });
 }
 

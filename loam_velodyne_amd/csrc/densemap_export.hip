@@ -14,8 +14,8 @@ static void dm_position(double leaf, const long long ia[3], const unsigned long 
 }
 
 // the surfel of a voxel (include/loamx.h): the scatter n*M_ab - S_a*S_b as an exact integer, the rest in double
-static void dm_surfel(double leaf, const long long ia[3], const unsigned long long* v4, const unsigned long long* m9,
-                      const loamx_densemap_surfel_config& c, int axes, loamx_surfel& out) {
+void dm_surfel(double leaf, const long long ia[3], const unsigned long long* v4, const unsigned long long* m9,
+               const loamx_densemap_surfel_config& c, int axes, loamx_surfel& out) {
   typedef __int128 i128;
   float p[3];
   dm_position(leaf, ia, v4, p);
@@ -106,6 +106,7 @@ uint64_t DenseMap::freeze(const loamx_densemap_surfel_config& sc, const loamx_de
     rec.insert(rec.end(), six, six + 6);
   });
   frozen.build(keys.data(), rec.data(), keys.size(), own_);
+  drop_coarse();
   return frozen.size();
 }
 
@@ -166,16 +167,15 @@ template <class T> static int copy_out(const std::vector<T>& v, void* out, uint6
 }
 
 // the surfel settings of a call, checked (NULL: the defaults)
-static loamx_densemap_surfel_config checked_surfel_config(const loamx_densemap_surfel_config* cfg) {
+loamx_densemap_surfel_config checked_surfel_config(const loamx_densemap_surfel_config* cfg) {
   const loamx_densemap_surfel_config c = or_default(cfg, loamx_densemap_surfel_default_config);
   LX_REQUIRE(c.min_points >= 3u, "min_points must be >= 3");
   LX_REQUIRE(c.min_planar_ratio >= 0.f, "min_planar_ratio must be >= 0");   // (NaN too)
   return c;
 }
-#define LX_REQUIRE_MOMENTS(h) LX_REQUIRE((h)->d.moments(), "moments are not enabled")
 // the optional rule of a surfel call: NULL stays NULL (every voxel); a rule is checked into `r` and needs carving
-static const loamx_densemap_static_rule* checked_optional_rule(loamx_densemap* h, const loamx_densemap_static_rule* rule,
-                                                               loamx_densemap_static_rule& r) {
+const loamx_densemap_static_rule* checked_optional_rule(loamx_densemap* h, const loamx_densemap_static_rule* rule,
+                                                        loamx_densemap_static_rule& r) {
   if (!rule) return nullptr;
   r = checked_rule(rule);
   LX_REQUIRE_CARVING(h);

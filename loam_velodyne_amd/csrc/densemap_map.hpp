@@ -34,6 +34,9 @@ class DenseMap {
     std::vector<uint32_t> miss, idx;
   };
   void snapshot(Snapshot& S, bool want_mom = false);
+  // the same download for any table of the map's format that holds `occ` voxels and that nothing enqueued on another stream still
+  // writes (the map's own behind read_counters; a coarse level of densemap_pyramid.hip behind its cascade)
+  void snapshot_of(const DmTable& T, uint64_t occ, Snapshot& S, bool want_mom);
   // the voxels of a snapshot in ascending key order, without those a rule (NULL: none) calls dynamic: f(j, ia) with j the voxel's
   // place in S.k (4 * j in S.v, 9 * j in S.mom) and ia its indices
   template <class F> static void for_each_voxel(const Snapshot& S, const loamx_densemap_static_rule* rule, F&& f) {
@@ -69,6 +72,21 @@ class DenseMap {
   // under its key of the table, with the six f32 of its record as surfels() gives them in axes 0.  Replaces an earlier snapshot
   uint64_t freeze(const loamx_densemap_surfel_config& sc, const loamx_densemap_static_rule* rule);
   DmFrozen frozen;
+
+  // ---- densemap_pyramid.hip: coarser levels of the map and of the snapshot (include/loamx.h, loamx_densemap_coarsen ...
+  // loamx_densemap_align_pyramid).  `frozen` is level 0; coarse[l - 1] is level l, a snapshot of the same format whose leaf is
+  // level_leaf(l).  freeze, reset and destroy drop the coarse levels; align_level is the level every alignment form reads
+  static constexpr uint32_t COARSE_LEVELS = LOAMX_PYRAMID_MAX_LEVELS - 1;
+  DmFrozen coarse[COARSE_LEVELS];
+  uint32_t align_level = 0;
+  // the voxels of level `level` in 1..COARSE_LEVELS on the host (S.k, S.v, S.mom, S.idx); needs moments; a checked rule or none
+  void coarsen(uint32_t level, const loamx_densemap_static_rule* rule, Snapshot& S);
+  void freeze_pyramid(const loamx_densemap_surfel_config& sc, const loamx_densemap_static_rule* rule,
+                      const loamx_densemap_pyramid_config& pc, uint64_t* n_surfels);
+  void drop_coarse();   // the coarse levels go and the selection returns to level 0
+  uint32_t frozen_levels() const;
+  DmFrozen& level(uint32_t l) { return l ? coarse[l - 1] : frozen; }
+  float level_leaf(uint32_t l) const { return cfg.leaf * (float)(1u << l); }   // (one f32 multiply by a power of two)
 
   // ---- densemap_merge.hip: include/loamx.h, loamx_densemap_save / merge / merge_file and, with `loading`, load
   uint32_t flags() const;   // the features of the handle as the file's flags
@@ -158,6 +176,9 @@ class DenseMap {
   // ---- densemap_raycast.hip
   void cast(const float4* pts, uint32_t n, const float origin[3], const loamx_densemap_raycast_config& c,
             const loamx_densemap_static_rule* rule, loamx_ray_hit* out, uint64_t counts[5]);
+  // ---- densemap_pyramid.hip: the levels 1 .. top, each from the one below (level 1 from the map's table, which is only read, without
+  // the voxels the rule calls dynamic); out[l - first] = the voxels of level l for l = first .. top.  Waits for the adds; blocks
+  void cascade(uint32_t top, const loamx_densemap_static_rule* rule, uint32_t first, std::vector<Snapshot>& out);
   // ---- densemap_rebuild.hip
   void log_reserve(uint64_t n, hipStream_t st);
   void launch_replay(const DmTable& nt, unsigned long long* nctr);
@@ -194,5 +215,14 @@ inline void checked_optional_rule(loamx_densemap* h, const loamx_densemap_static
   LX_REQUIRE(rule->den != 0u, "the rule's den must not be 0");
   LX_REQUIRE(h->d.carving(), "a rule needs carving, which is not enabled");
 }
+// densemap_export.hip, shared with densemap_pyramid.hip: the surfel of a voxel from its words (include/loamx.h), the surfel settings
+// of a call, checked (NULL: the defaults), and the optional rule of a surfel call (NULL stays NULL: every voxel; a rule is checked
+// into `r` and needs carving)
+#define LX_REQUIRE_MOMENTS(h) LX_REQUIRE((h)->d.moments(), "moments are not enabled")
+void dm_surfel(double leaf, const long long ia[3], const unsigned long long* v4, const unsigned long long* m9,
+               const loamx_densemap_surfel_config& c, int axes, loamx_surfel& out);
+loamx_densemap_surfel_config checked_surfel_config(const loamx_densemap_surfel_config* cfg);
+const loamx_densemap_static_rule* checked_optional_rule(loamx_densemap* h, const loamx_densemap_static_rule* rule,
+                                                        loamx_densemap_static_rule& r);
 
 }  // namespace loamx

@@ -1130,6 +1130,13 @@ def align_solve(sums, degenerate_ratio=1e-4):
 
 
 ALIGN_MAX_POSES = 4096   # LOAMX_ALIGN_MAX_POSES
+PYRAMID_MAX_LEVELS = 6   # LOAMX_PYRAMID_MAX_LEVELS
+
+
+class PyramidConfig(C.Structure):
+    """loamx_densemap_pyramid_config: levels (1 .. PYRAMID_MAX_LEVELS, default 3) and max_curvature (levels >= 1: a surfel with a larger
+    curvature gets no entry; 0 = no limit, the default)"""
+    _fields_ = [("levels", C.c_uint32), ("max_curvature", C.c_float)]
 
 
 def align_best(results):
@@ -1449,6 +1456,7 @@ class DenseMap:
         L.loamx_densemap_rehashes.restype = C.c_uint64
         L.loamx_densemap_route_active_rounds.restype = C.c_uint64
         self.route_stats = None
+        self._level = 0   # the level select_level chose (loamx_densemap_align_select_level)
         self._c = _cfg(DenseMapConfig, "loamx_densemap_default_config", leaf=leaf, min_range=min_range, max_range=max_range,
                        max_voxels=max_voxels, initial_slots=initial_slots, device=device)
         self.h = C.c_void_p(L.loamx_densemap_create(C.byref(self._c)))
@@ -1584,6 +1592,7 @@ class DenseMap:
         c = SurfelConfig(min_points, min_planar_ratio)
         n = C.c_uint64(0)
         _check(lib().loamx_densemap_freeze(self.h, C.byref(c), C.byref(static) if static is not None else None, C.byref(n)))
+        self._level = 0
         return int(n.value)
 
     @property
@@ -1600,7 +1609,7 @@ class DenseMap:
         r = np.ascontiguousarray(rtc, np.float32)
         assert r.shape == (15,)
         sums, counts = np.zeros(28, np.int64), np.zeros(5, np.uint64)
-        mr = self._c.leaf if max_residual is None else max_residual
+        mr = self.level_leaf() if max_residual is None else max_residual
         _check(lib().loamx_densemap_align_step(self.h, C.byref(c), r.ctypes.data_as(C.c_void_p), C.c_uint32(neighbourhood), C.c_float(mr),
                                                sums.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
         return sums, counts
@@ -1644,7 +1653,7 @@ class DenseMap:
         assert r.ndim == 2 and r.shape[1] == 15
         k = len(r)
         sums, counts = np.zeros((max(k, 1), 28), np.int64), np.zeros((max(k, 1), 5), np.uint64)
-        mr = self._c.leaf if max_residual is None else max_residual
+        mr = self.level_leaf() if max_residual is None else max_residual
         _check(lib().loamx_densemap_align_step_many(self.h, C.byref(c), r.ctypes.data_as(C.c_void_p), C.c_uint32(k), C.c_uint32(neighbourhood),
                                                     C.c_float(mr), sums.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
         return sums[:k], counts[:k]
@@ -1700,6 +1709,91 @@ class DenseMap:
         s = (C.c_uint64 * 3)()
         _check(lib().loamx_densemap_get_align_stats(self.h, s))
         return dict(launches=int(s[0]), readbacks=int(s[1]), pose_steps=int(s[2]))
+
+    def coarsen(self, level: int, static=None):
+        """loamx_densemap_coarsen: the voxels of level `level` (1 .. PYRAMID_MAX_LEVELS - 1; leaf * 2^level) in ascending key order as
+        (keys (n,) uint64, vals (n, 4) uint64, mom (n, 9) uint64), computed on the device from the map's table; static (a StaticRule;
+        needs carving): without the voxels the rule calls dynamic.  Needs moments.  With surfel_of(leaf * 2^level, ...) a coarser
+        surfel export"""
+        n, cap = C.c_uint64(0), 0
+        while True:
+            keys, vals, mom = np.zeros(max(cap, 1), np.uint64), np.zeros((max(cap, 1), 4), np.uint64), np.zeros((max(cap, 1), 9), np.uint64)
+            rc = lib().loamx_densemap_coarsen(self.h, C.c_uint32(level), C.byref(static) if static is not None else None,
+                                              keys.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p), mom.ctypes.data_as(C.c_void_p),
+                                              C.c_uint64(cap), C.byref(n))
+            if rc == E_CAPACITY:
+                cap = int(n.value)
+                continue
+            _check(rc)
+            return keys[:int(n.value)], vals[:int(n.value)], mom[:int(n.value)]
+
+    def freeze_pyramid(self, levels=None, max_curvature=None, min_points=None, min_planar_ratio=None, static=None):
+        """loamx_densemap_freeze_pyramid: freeze() as level 0 and, for l = 1 .. levels - 1, a snapshot of the voxels of level l (leaf *
+        2^l) that have a surfel, without those whose curvature exceeds max_curvature (0: no limit).  levels None: 3.  Returns the
+        entry counts per level.  The selected level returns to 0"""
+        c = SurfelConfig(min_points, min_planar_ratio)
+        pc = _cfg(PyramidConfig, "loamx_densemap_pyramid_default_config",
+                  **{k: v for k, v in (("levels", levels), ("max_curvature", max_curvature)) if v is not None})
+        n = (C.c_uint64 * PYRAMID_MAX_LEVELS)()
+        _check(lib().loamx_densemap_freeze_pyramid(self.h, C.byref(c), C.byref(static) if static is not None else None, C.byref(pc), n))
+        self._level = 0
+        return [int(v) for v in n[:pc.levels]]
+
+    @property
+    def frozen_levels(self) -> int:
+        """loamx_densemap_frozen_levels: 0 = nothing frozen, 1 after freeze(), the pyramid's levels after freeze_pyramid()"""
+        n = C.c_uint32(0)
+        _check(lib().loamx_densemap_frozen_levels(self.h, C.byref(n)))
+        return int(n.value)
+
+    def select_level(self, level: int):
+        """loamx_densemap_align_select_level: align_step, align_step_many, align, align_many and their from forms read the snapshot of
+        `level` from now on (max_residual None / 0: that level's leaf); every freeze and reset select level 0 again"""
+        _check(lib().loamx_densemap_align_select_level(self.h, C.c_uint32(level)))
+        self._level = int(level)
+
+    def level_leaf(self, level=None) -> float:
+        """the leaf of a level (default: the selected one) as the library computes it: one f32 multiply by a power of two"""
+        return float(np.float32(self._c.leaf) * np.float32(1 << (self._level if level is None else level)))
+
+    @staticmethod
+    def _pyramid_out(out, first_level):
+        return [out[k].as_dict() for k in range(first_level + 1)]
+
+    def align_pyramid(self, points, pose=np.eye(3, 4), centre=None, first_level=None, **cfg):
+        """loamx_densemap_align_pyramid: align() against level first_level (default: the coarsest that stands), then against each
+        finer level from the pose the level before reported.  Returns first_level + 1 result dicts, coarsest first; the last one is
+        level 0's.  Each is what select_level(level) + align() returns from the same start; the selected level is left alone"""
+        a = as_points(points)
+        c = cloud_of(a)
+        p = _pose12(pose)
+        ctr = None if centre is None else np.ascontiguousarray(centre, np.float32)
+        assert ctr is None or ctr.shape == (3,)
+        first = max(self.frozen_levels - 1, 0) if first_level is None else int(first_level)
+        k, out = AlignConfig(**cfg), (AlignResult * PYRAMID_MAX_LEVELS)()
+        _check(lib().loamx_densemap_align_pyramid(self.h, C.byref(c), p.ctypes.data_as(C.c_void_p),
+                                                  None if ctr is None else ctr.ctypes.data_as(C.c_void_p), C.byref(k), C.c_uint32(first), out))
+        return self._pyramid_out(out, first)
+
+    def align_pyramid_from(self, mapping, pose=None, first_level=None, **cfg):
+        """loamx_densemap_align_pyramid_from_map: the same for the registered cloud of mapping's last process, where it lies, about its
+        origin; pose None: identity.  Returns (status code OK / SKIPPED, results)"""
+        p = None if pose is None else _pose12(pose)
+        first = max(self.frozen_levels - 1, 0) if first_level is None else int(first_level)
+        k, out = AlignConfig(**cfg), (AlignResult * PYRAMID_MAX_LEVELS)()
+        rc = _check(lib().loamx_densemap_align_pyramid_from_map(self.h, mapping.h, None if p is None else p.ctypes.data_as(C.c_void_p),
+                                                                C.byref(k), C.c_uint32(first), out))
+        return rc, self._pyramid_out(out, first)
+
+    def align_pyramid_from_pipeline(self, pipeline, slot: int, pose=None, first_level=None, **cfg):
+        """loamx_densemap_align_pyramid_from_pipeline: the same for the slot-th stream registered in pipeline's last step"""
+        p = None if pose is None else _pose12(pose)
+        first = max(self.frozen_levels - 1, 0) if first_level is None else int(first_level)
+        k, out = AlignConfig(**cfg), (AlignResult * PYRAMID_MAX_LEVELS)()
+        rc = _check(lib().loamx_densemap_align_pyramid_from_pipeline(self.h, pipeline.h, C.c_uint32(slot),
+                                                                     None if p is None else p.ctypes.data_as(C.c_void_p), C.byref(k),
+                                                                     C.c_uint32(first), out))
+        return rc, self._pyramid_out(out, first)
 
     def _raycast(self, fn, head, n, max_steps, skip_steps, min_points, static, records):
         k = _cfg(RaycastConfig, "loamx_densemap_raycast_default_config", max_steps=max_steps, skip_steps=skip_steps, min_points=min_points)
@@ -1904,6 +1998,7 @@ class DenseMap:
 
     def reset(self):
         _check(lib().loamx_densemap_reset(self.h))
+        self._level = 0
 
     def set_combine(self, on: bool):
         """bench hook: the in-wave combining of equal keys before the table is touched (default on; results are the same)"""
