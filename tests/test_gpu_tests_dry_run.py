@@ -1,5 +1,5 @@
 """CPU: a dry run of the opt-in GPU tests' LOGIC.  tests/test_gpu_next.py and the C-ABI half of tests/test_gpu_nodes.py were written
-without a GPU at hand; here their bodies run with the ctypes binding pointed (for these tests only) at the oracle-backed test double
+without a GPU at hand, and tests/test_gpu_lfvoxel.py rests on a configuration trick worth checking first; here their bodies run with the ctypes binding pointed (for these tests only) at the oracle-backed test double
 of the C-ABI (oracle/mock_loamx_capi.cpp).  Device arithmetic is not exercised — the double IS the oracle — but a wrong method name,
 argument order, state hand-over or expectation in those tests shows up now instead of on the GPU box."""
 import ctypes as C
@@ -29,6 +29,17 @@ def test_next_round_cases(orc, small_world, over_the_mock):
     T.test_degenerate_corridor_odometry_and_registration(orc)
     T.test_odometry_too_few_rows(orc, small_world)
     T.test_mapping_too_few_rows(orc, small_world)
+
+
+def test_less_flat_voxel_grid_cases(orc, over_the_mock):
+    """tests/test_gpu_lfvoxel.py: every case, the dispatch boundary and the reuse of one handle (configure from case to case) — the
+    double's scan registration is the oracle's, so this checks the cases' configuration, the comparison and the expectations.  The
+    linked test stays out: the double has no linked entry points."""
+    import test_gpu_lfvoxel as V
+    for case in V.CASES:
+        V.check_case(orc, case)
+    V.check_dispatch_boundary(orc)
+    V.check_handle_reuse(orc)
 
 
 def test_c_abi_node_graph(small_world, over_the_mock):
