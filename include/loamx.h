@@ -1468,6 +1468,87 @@ int loamx_densemap_segment(loamx_densemap* h, const loamx_densemap_segment_confi
                            loamx_segment* segs /* NULL: not wanted */, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[6]);
 int loamx_segment_box(const loamx_segment* s, float leaf, float lo_m[3], float hi_m[3], float centre[3]);   /* host only */
 
+/* Objects of a sweep that is not in the map (optional, as above).  "What stands in this sweep that the map does not know?": the
+ * points of a cloud are tested against the live map, the ones that pass are clustered on the voxel lattice of the map, and every
+ * point gets the number of its object.  The map is only read, and nothing of the cloud stays in the handle.  Every output word but
+ * stats[12] depends only on the multiset of points and on the words of the map: not on the thread schedule, the size of either
+ * table or the order of the adds.
+ *
+ * The cloud and origin are in the map frame, exactly as loamx_densemap_add takes them.
+ * Admission: point i is admitted iff loamx_densemap_add on this handle would add it: the same range filter about origin (the
+ * handle's min_range / max_range) and the same key rule (every |floor(c * (1 / leaf))| < 2^20; NaN and infinities fail), by the
+ * same f32 expressions.  The cell c of an admitted point is the cell add would put it in.
+ * Mapped: a voxel of the map is mapped iff it is in the live table, holds n >= map_min_points and, when a rule is given, is not
+ * dynamic under it (the expression of loamx_densemap_rule_is_dynamic on its n and miss).
+ * Near: an admitted point is near iff some cell c' with max_a |c'_a - c_a| <= margin is mapped.  It is decided on the indices:
+ * a cell with any |i_a| >= 2^20 does not exist and is not looked up.
+ * Selection by `which`: LOAMX_CLOUD_ALL enters every admitted point (no lookup); _NEW the admitted points that are not near;
+ * _KNOWN those that are.  The entered points go into a scratch table of the map's own format (the same key, the same fixed-point
+ * sums n, Sx, Sy, Sz): its words are those of a fresh handle of this configuration fed with exactly the entered points.
+ * Clustering: the voxels of the scratch table are grouped exactly as loamx_densemap_segment with which = LOAMX_SEGMENT_ALL groups
+ * a map's: the same connectivity, min_points (of entered points in a voxel OF THE CLOUD), window, min_voxels and record struct;
+ * the kept components are numbered in ascending min_key.
+ * Outputs: segs: the kept components, byte for byte what loamx_densemap_segment returns for that fresh handle.  labels[i], in
+ * point order: the number of the component of point i's voxel, LOAMX_SEGMENT_NONE when the point did not enter, its voxel was not
+ * selected or its component was dropped.  *n_points is the cloud's count (the length of labels), *n_segs the kept components.
+ * stats[13]: [0] points offered;  [1] dropped by range;  [2] dropped by the key rule;  [3] admitted but rejected by the map
+ * test;  [4] entered ([0] = [1] + [2] + [3] + [4]);  [5] voxels of the scratch table;  [6] selected voxels;  [7] components
+ * before min_voxels;  [8] components kept;  [9] voxels in kept components;  [10] voxels of the largest component;  [11] points
+ * with a label other than NONE;  [12] hook attempts that lost to another thread.  [0..11] are part of the definition and exact,
+ * [12] describes the schedule.
+ * The from_map / from_pipeline forms take the registered cloud of m's last process() / of the slot-th stream of p's last step
+ * where it lies on the device, about that sweep's origin, as loamx_densemap_raycast_from_map does; LOAMX_SKIPPED, nothing
+ * written, when that call produced no registered cloud.
+ * Ordering: as loamx_densemap_raycast and loamx_densemap_segment the call waits for every add, runs on the map's own stream, only
+ * reads the live table and blocks until the outputs are back through pinned memory; every export of the map is byte for byte what
+ * it was before.  Integer atomics only.  The scratch table (a power of two of at least twice the cloud's count, at least 1024
+ * slots), one key and one id word per point and the staging blocks live in the handle, are allocated by the first call, grow to
+ * the largest cloud and are freed on destroy; loamx_densemap_segment's work arrays are shared.  labels and segs may each be NULL:
+ * that output is skipped (without labels the second kernel does not run).  Outputs are written last, all or none.  An empty
+ * cloud is LOAMX_OK with every count zero and nothing launched; an empty map is valid: nothing is near.  Any `which` works on a
+ * handle without carving when rule is NULL.
+ * LOAMX_E_INVALID, with a message that names the argument, nothing written: NULL h, points (m, p), origin, n_points, n_segs or
+ * stats;  a configuration that fails loamx_densemap_segment_cloud_check (which > 2;  margin > 2;  map_min_points 0;
+ * connectivity not 6, 18 or 26;  min_points or min_voxels 0;  lo[a] > hi[a];  a bound outside +-(2^20 - 1));  a rule whose den
+ * is 0;  a rule on a handle without carving;  a source on another device;  a cloud of more than 2^30 points.
+ * LOAMX_E_CAPACITY: labels given and label_capacity < the cloud's count, or segs given and seg_capacity < the kept components.
+ * Only *n_points and *n_segs are written: they hold the needed counts.
+ *
+ * loamx_segments_match (host only, no device): following objects from call to call.  For each cur[j] the prev[i] whose inclusive
+ * box, grown by gap voxels on every side, shares the most cells with cur[j]'s box: per axis max(0, min(prev.hi + gap, cur.hi) -
+ * max(prev.lo - gap, cur.lo) + 1), the product of the three taken exactly (128 bits); ties go to the smaller min_key;
+ * prev_of_cur[j] = that i, LOAMX_SEGMENT_NONE when no box overlaps.  gap in 0..1024, n_prev < 2^32 - 1.  Nothing else of
+ * tracking is built: no motion model, no ids kept in the library. */
+#define LOAMX_CLOUD_ALL 0u     /* every admitted point */
+#define LOAMX_CLOUD_NEW 1u     /* admitted points with no mapped voxel within `margin` */
+#define LOAMX_CLOUD_KNOWN 2u   /* admitted points with one */
+typedef struct loamx_densemap_segment_cloud_config {
+  uint32_t which;            /* LOAMX_CLOUD_ALL / _NEW / _KNOWN (default NEW) */
+  uint32_t margin;           /* 0, 1 or 2: Chebyshev radius, in voxels, of the neighbourhood looked up in the map (default 1) */
+  uint32_t map_min_points;   /* a map voxel counts as mapped with n >= this, >= 1 (default 1) */
+  uint32_t connectivity;     /* 6, 18 or 26 (default 26) */
+  uint32_t min_points;       /* a voxel OF THE CLOUD is selected with >= this many entered points, >= 1 (default 1) */
+  uint32_t min_voxels;       /* components with fewer voxels are dropped, >= 1 (default 1) */
+  int32_t lo[3], hi[3];      /* inclusive window in voxel indices (ix, iy, iz); default -(2^20 - 1) .. 2^20 - 1: everything */
+} loamx_densemap_segment_cloud_config;
+void loamx_densemap_segment_cloud_default_config(loamx_densemap_segment_cloud_config* cfg);   /* host only */
+int loamx_densemap_segment_cloud_check(const loamx_densemap_segment_cloud_config* cfg);       /* host only; names the first bad field */
+int loamx_densemap_segment_cloud(loamx_densemap* h, const loamx_cloud* points, const float origin[3],
+                                 const loamx_densemap_segment_cloud_config* cfg /* NULL: the defaults */,
+                                 const loamx_densemap_static_rule* rule /* NULL: every voxel; else needs carving */,
+                                 uint32_t* labels /* NULL: not wanted */, uint64_t label_capacity, uint64_t* n_points,
+                                 loamx_segment* segs /* NULL: not wanted */, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[13]);
+int loamx_densemap_segment_cloud_from_map(loamx_densemap* h, loamx_map* m, const loamx_densemap_segment_cloud_config* cfg,
+                                          const loamx_densemap_static_rule* rule, uint32_t* labels, uint64_t label_capacity,
+                                          uint64_t* n_points, loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs,
+                                          uint64_t stats[13]);
+int loamx_densemap_segment_cloud_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot,
+                                               const loamx_densemap_segment_cloud_config* cfg, const loamx_densemap_static_rule* rule,
+                                               uint32_t* labels, uint64_t label_capacity, uint64_t* n_points, loamx_segment* segs,
+                                               uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[13]);
+int loamx_segments_match(const loamx_segment* prev, uint64_t n_prev, const loamx_segment* cur, uint64_t n_cur,
+                         uint32_t gap /* voxels, 0..1024 */, uint32_t* prev_of_cur /* n_cur words */);   /* host only */
+
 /* ------------------------------------------------------------------------------------------------------------
  * Place recognition (not in the reference): a database of rotation-invariant sweep descriptors in device memory (Scan Context: a
  * ring x sector polar grid of maximum heights around the sensor) and an exhaustive search for the earlier entries that look like a

@@ -13,6 +13,7 @@
 //   densemap_grid.hip     a window of the table projected to a 2-D navigation grid (DmGrid)
 //   densemap_route.hip    cost-to-go field and routes over that grid (DmRoute, densemap_route_schedule.hpp)
 //   densemap_segment.hip  connected components of the voxels (DmSegment)
+//   densemap_segment_cloud.hip  the objects of a cloud that is not in the map, tested against the table (DmSegCloud)
 //
 // One insert kernel per add: range filter, voxel key, a combine of equal keys inside the wave, the open-addressing insert and the
 // accumulation, in one pass over the cloud.  The host keeps an upper bound of the occupancy (last known count + points enqueued since)

@@ -288,8 +288,14 @@ class DmSegment {
   // the components of the table T (every add waited for, `occ` voxels, occ >= 1) under a checked configuration and rule, on st:
   // select, link, flatten, the two scans, ids and reduce, and the host's ordering by key.  Blocks.  segs: the kept components in
   // ascending min_key; labels (when want_labels): one word per voxel in ascending key order; stats as in include/loamx.h
+  // rank_of_id (optional): per compact id the component's place in segs, NONE when min_voxels dropped it
   void run(const DmTable& T, const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint64_t occ, bool want_labels,
-           std::vector<uint32_t>& labels, std::vector<loamx_segment>& segs, uint64_t stats[6], hipStream_t st);
+           std::vector<uint32_t>& labels, std::vector<loamx_segment>& segs, uint64_t stats[6], hipStream_t st,
+           std::vector<uint32_t>* rank_of_id = nullptr);
+  // what the last run left on the device, per slot of its table: the root of a selected slot (NONE: not selected), and a root's
+  // compact id (DmSegCloud labels points through them)
+  const uint32_t* parent() const { return parent_.p; }
+  const uint32_t* rootid() const { return rootid_.p; }
 
  private:
   DevBuf<uint32_t> parent_, rootid_;       // per slot: the union-find word (NONE: not selected); the compact id of a root
@@ -303,6 +309,43 @@ class DmSegment {
   PinBuf<uint32_t> h_tot_, h_ids_;
   PinLanding<loamx_segment> h_acc_;
   PinLanding<unsigned long long> h_keys_;
+};
+
+struct DmFilter;   // densemap_dev.hpp
+
+// include/loamx.h, loamx_densemap_segment_cloud_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
+void dm_segment_cloud_check(const loamx_densemap_segment_cloud_config& c);
+
+// Objects of a cloud that is not in the map (include/loamx.h, loamx_densemap_segment_cloud; densemap_segment_cloud.hip): a scratch
+// table of the map's format without aux or mom (a power of two of at least twice the cloud's count, at least 1024 slots: kept, grown
+// to the largest call, cleared per call), one key word and one id word per point, six counters, and the staging and pinned blocks of
+// its own that the cloud, the counters and the ids cross through.  The live map is only read.
+class DmSegCloud {
+ public:
+  DmSegCloud() = default;
+  DmSegCloud(const DmSegCloud&) = delete;
+  DmSegCloud& operator=(const DmSegCloud&) = delete;
+  // the cloud (count >= 1) from the host into the feature's own device block, enqueued on st
+  const float4* stage(const loamx_cloud* c, hipStream_t st);
+  // n >= 1 points (readable on st) under the filter F of their origin against the live table M (every add waited for): the scratch
+  // table cleared, the admitted points that pass the map test of a checked configuration and rule (NULL: every voxel) inserted.
+  // Blocks.  counts: dropped by range, by the key rule, rejected by the map test, entered, voxels of the scratch table
+  void insert(const DmTable& M, const DmFilter& F, const loamx_densemap_segment_cloud_config& c, const loamx_densemap_static_rule* rule,
+              const float4* pts, uint32_t n, hipStream_t st, uint64_t counts[5]);
+  const DmTable& table() const { return tab_; }
+  // behind seg.run on table(): per point of the last insert the compact id (< n_roots) of its voxel's component, NONE when the point
+  // did not enter or its voxel was not selected; in pinned memory, valid until the next call.  Blocks
+  const uint32_t* ids(const DmSegment& seg, uint32_t n_roots, uint32_t n, hipStream_t st);
+
+ private:
+  DmTable tab_;               // (slots: the size this call uses, the front of an allocation of cap_slots_)
+  uint32_t cap_slots_ = 0;
+  DevBuf<float4> d_pts_;
+  PinBuf<float4> h_pts_;
+  DevBuf<unsigned long long> pkey_, ctr_;   // per point: its key, EMPTY when it did not enter; the counters
+  DevBuf<uint32_t> ids_;
+  PinLanding<unsigned long long> h_ctr_;
+  PinLanding<uint32_t> h_ids_;
 };
 
 }  // namespace loamx

@@ -120,6 +120,14 @@ class DenseMap {
   DmRoute& router() { return route_; }
   int segment(const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint32_t* labels, uint64_t label_capacity,
               uint64_t* n_voxels, loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[6]);
+  // ---- densemap_segment_cloud.hip: include/loamx.h, loamx_densemap_segment_cloud (the cloud staged from the host) and its from_*
+  // forms (the registered cloud where it lies); a checked configuration, a checked rule or none
+  int segment_cloud_host(const loamx_cloud* points, const float origin[3], const loamx_densemap_segment_cloud_config& c,
+                         const loamx_densemap_static_rule* rule, uint32_t* labels, uint64_t label_capacity, uint64_t* n_points,
+                         loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[13]);
+  int segment_cloud_device(const DenseSource& s, const loamx_densemap_segment_cloud_config& c, const loamx_densemap_static_rule* rule,
+                           uint32_t* labels, uint64_t label_capacity, uint64_t* n_points, loamx_segment* segs, uint64_t seg_capacity,
+                           uint64_t* n_segs, uint64_t stats[13]);
 
  private:
   // the table and its counters
@@ -154,6 +162,7 @@ class DenseMap {
   DmGrid grid_;       // densemap_grid.hip
   DmRoute route_;     // densemap_route.hip
   DmSegment seg_;     // densemap_segment.hip
+  DmSegCloud cseg_;   // densemap_segment_cloud.hip (labels its scratch table through seg_)
 
   // ---- densemap.hip
   DmFilter filter_for(const float origin[3]) const;   // the insert's filter about an origin
@@ -176,6 +185,10 @@ class DenseMap {
   // ---- densemap_raycast.hip
   void cast(const float4* pts, uint32_t n, const float origin[3], const loamx_densemap_raycast_config& c,
             const loamx_densemap_static_rule* rule, loamx_ray_hit* out, uint64_t counts[5]);
+  // ---- densemap_segment_cloud.hip: the tail of the three forms, behind a wait_adds(): n points readable on own_
+  int segment_cloud(const float4* pts, uint32_t n, const float origin[3], const loamx_densemap_segment_cloud_config& c,
+                    const loamx_densemap_static_rule* rule, uint32_t* labels, uint64_t label_capacity, uint64_t* n_points, loamx_segment* segs,
+                    uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[13]);
   // ---- densemap_pyramid.hip: the levels 1 .. top, each from the one below (level 1 from the map's table, which is only read, without
   // the voxels the rule calls dynamic); out[l - first] = the voxels of level l for l = first .. top.  Waits for the adds; blocks
   void cascade(uint32_t top, const loamx_densemap_static_rule* rule, uint32_t first, std::vector<Snapshot>& out);

@@ -258,7 +258,8 @@ __global__ __launch_bounds__(256) void k_dm_seg_reduce(const unsigned long long*
 }
 
 void DmSegment::run(const DmTable& T, const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint64_t occ,
-                    bool want_labels, std::vector<uint32_t>& labels, std::vector<loamx_segment>& segs, uint64_t stats[6], hipStream_t st) {
+                    bool want_labels, std::vector<uint32_t>& labels, std::vector<loamx_segment>& segs, uint64_t stats[6], hipStream_t st,
+                    std::vector<uint32_t>* rank_of_id) {
   const uint32_t slots = T.slots, nblk = (slots + 255u) / 256u;
   parent_.reserve(slots);
   rootid_.reserve(slots);
@@ -342,6 +343,7 @@ void DmSegment::run(const DmTable& T, const loamx_densemap_segment_config& c, co
     labels.resize(occ);
     for (size_t r = 0; r < kv.size(); r++) labels[r] = kv[r].second;
   }
+  if (rank_of_id) rank_of_id->swap(rank);
   stats[0] = selected; stats[1] = n_roots; stats[2] = segs.size(); stats[3] = kept_voxels; stats[4] = largest; stats[5] = lost;
 }
 

@@ -1418,6 +1418,39 @@ def segment_box(seg, leaf: float):
     return out[0], out[1], out[2]
 
 
+CLOUD_ALL, CLOUD_NEW, CLOUD_KNOWN = range(3)                                      # loamx_densemap_segment_cloud_config.which
+
+
+class SegmentCloudConfig(_DefaultedConfig, C.Structure):
+    """loamx_densemap_segment_cloud_config: which admitted points of a cloud enter (which: CLOUD_ALL, CLOUD_NEW = no mapped voxel
+    within margin cells, CLOUD_KNOWN = one; a map voxel is mapped with n >= map_min_points) and how the voxels they fill are grouped
+    (connectivity, min_points, min_voxels, the window lo .. hi, as in SegmentConfig).  SegmentCloudConfig() holds the defaults (NEW,
+    margin 1, 1, 26, 1, 1, the whole key range); keyword arguments replace them, lo and hi as triples."""
+    _fields_ = [("which", C.c_uint32), ("margin", C.c_uint32), ("map_min_points", C.c_uint32), ("connectivity", C.c_uint32),
+                ("min_points", C.c_uint32), ("min_voxels", C.c_uint32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
+
+    _default, _checker = "loamx_densemap_segment_cloud_default_config", "loamx_densemap_segment_cloud_check"
+
+    def update(self, **fields):
+        return super().update(**{k: (C.c_int32 * 3)(*v) if k in ("lo", "hi") else v for k, v in fields.items()})
+
+
+# stats[13] of loamx_densemap_segment_cloud
+SEGMENT_CLOUD_STATS = ("offered", "dropped_range", "dropped_key", "rejected", "entered", "voxels", "selected", "components", "kept",
+                       "kept_voxels", "largest", "labelled", "hooks_lost")
+
+
+def segments_match(prev, cur, gap=0) -> np.ndarray:
+    """loamx_segments_match (host only): for each SEGMENT record of cur the index of the record of prev whose box, grown by gap
+    voxels on every side, shares the most cells with it (ties to the smaller min_key), SEGMENT_NONE when none overlaps; uint32"""
+    a, b = np.ascontiguousarray(prev, SEGMENT).reshape(-1), np.ascontiguousarray(cur, SEGMENT).reshape(-1)
+    out = np.full(max(len(b), 1), SEGMENT_NONE, np.uint32)
+    _check(lib().loamx_segments_match(a.ctypes.data_as(C.c_void_p) if len(a) else None, C.c_uint64(len(a)),
+                                      b.ctypes.data_as(C.c_void_p) if len(b) else None, C.c_uint64(len(b)), C.c_uint32(gap),
+                                      out.ctypes.data_as(C.c_void_p)))
+    return out[:len(b)]
+
+
 def write_pcd(path: str, points, axes="loam"):
     """loamx_write_pcd: an (N, 4) / (N, 8) float32 cloud as a binary PCD v0.7 file (x y z intensity); axes="sensor" writes the sensor
     axes ingestion started from (x_s = z, y_s = x, z_s = y).  Host only."""
@@ -1931,6 +1964,51 @@ class DenseMap:
                 continue
             _check(rc)
             return (lab[:int(n_vox.value)] if labels else None), segs[:int(n_seg.value)], dict(zip(SEGMENT_STATS, (int(v) for v in st)))
+
+    def _segment_cloud(self, fn, head, n_pts, cfg, static, labels, fields):
+        # (as segment(): a refusal by capacity leaves the needed counts, and the call is made again with that room)
+        c = (SegmentCloudConfig() if cfg is None else cfg).copy(**fields).check()
+        n_pts, n_seg = C.c_uint64(n_pts if labels else 0), C.c_uint64(max(4096, getattr(self, "_cloud_segs", 0)))   # (room as the last call needed)
+        st = (C.c_uint64 * 13)()
+        while True:
+            lab = np.full(max(int(n_pts.value), 1), SEGMENT_NONE, np.uint32) if labels else None
+            segs = np.zeros(max(int(n_seg.value), 1), SEGMENT)
+            rc = fn(self.h, *head, C.byref(c), C.byref(static) if static is not None else None,
+                    lab.ctypes.data_as(C.c_void_p) if labels else None, C.c_uint64(int(n_pts.value)), C.byref(n_pts),
+                    segs.ctypes.data_as(C.c_void_p), C.c_uint64(int(n_seg.value)), C.byref(n_seg), st)
+            if rc == E_CAPACITY:
+                continue
+            _check(rc)
+            self._cloud_segs = int(n_seg.value) if rc == OK else 0
+            if rc == SKIPPED:
+                return rc, (np.zeros(0, np.uint32) if labels else None), segs[:0], dict.fromkeys(SEGMENT_CLOUD_STATS, 0)
+            return (rc, (lab[:int(n_pts.value)] if labels else None), segs[:int(n_seg.value)],
+                    dict(zip(SEGMENT_CLOUD_STATS, (int(v) for v in st))))
+
+    def segment_cloud(self, points, origin=(0.0, 0.0, 0.0), cfg=None, static=None, labels=True, **fields):
+        """loamx_densemap_segment_cloud: the objects of a cloud that is not in the map ((N, 4) / (N, 8), map frame, about origin as
+        add() takes them).  The points that add() would admit are tested against the live map (cfg.which: CLOUD_NEW keeps those with
+        no mapped voxel within cfg.margin cells, CLOUD_KNOWN those with one, CLOUD_ALL all of them; static, a StaticRule that needs
+        carving: the voxels it calls dynamic are not mapped), the kept ones are clustered as segment() clusters a map's voxels.  cfg:
+        a SegmentCloudConfig (None: the defaults); fields replace members of a copy of it.  Returns (labels, segments, stats): one
+        uint32 per point, the number of its object or SEGMENT_NONE (None with labels=False); SEGMENT records in ascending min_key;
+        a dict in the order of SEGMENT_CLOUD_STATS.  Blocks; the map is only read."""
+        a = as_points(points)
+        c = cloud_of(a)
+        o = np.ascontiguousarray(origin, np.float32)
+        assert o.shape == (3,)
+        return self._segment_cloud(lib().loamx_densemap_segment_cloud, (C.byref(c), o.ctypes.data_as(C.c_void_p)), len(a), cfg, static,
+                                   labels, fields)[1:]
+
+    def segment_cloud_from(self, mapping, cfg=None, static=None, labels=True, capacity=1 << 17, **fields):
+        """loamx_densemap_segment_cloud_from_map: the same for the registered cloud of mapping's last process, where it lies, about
+        its origin; capacity = the room for the labels to start with.  Returns (status code OK / SKIPPED, labels, segments, stats)"""
+        return self._segment_cloud(lib().loamx_densemap_segment_cloud_from_map, (mapping.h,), int(capacity), cfg, static, labels, fields)
+
+    def segment_cloud_from_pipeline(self, pipeline, slot: int, cfg=None, static=None, labels=True, capacity=1 << 17, **fields):
+        """loamx_densemap_segment_cloud_from_pipeline: the same for the slot-th stream registered in pipeline's last step"""
+        return self._segment_cloud(lib().loamx_densemap_segment_cloud_from_pipeline, (pipeline.h, C.c_uint32(slot)), int(capacity), cfg,
+                                   static, labels, fields)
 
     def save(self, path: str):
         """loamx_densemap_save: every word of the map as an 'LXDM' file (include/loamx.h), written beside path and renamed.  The
