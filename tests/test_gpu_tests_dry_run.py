@@ -42,6 +42,24 @@ def test_less_flat_voxel_grid_cases(orc, over_the_mock):
     V.check_handle_reuse(orc)
 
 
+def test_feature_ring_cases(orc, over_the_mock):
+    """tests/test_gpu_featring.py: every case, the reuse of one handle, the start-index family and the mixed batch — the double's scan
+    registration is the oracle's, so this checks the cases' configuration, the comparison, the message's plumbing and the
+    expectations.  The Pipeline test stays out: the double has no pipeline entry points."""
+    import test_gpu_featring as R
+    for case in R.CASES:
+        R.check_case(orc, case)
+    R.check_handle_reuse(orc)
+    R.check_start_index(orc)
+    R.check_mixed_batch(orc)
+    # the failure message names the path: a wrong cloud is explained, not only reported
+    case = R.fc.by_name("settlement, cascade", R.CASES)
+    want = R.fc.cached_oracle(orc, case)
+    wrong = {n: (want[n][1:] if n == "less_sharp" else want[n]) for n in R.fc.NAMES}
+    msg = R.explain(case, wrong, want)
+    assert "less_sharp" in msg and "side by side" in msg and "region 0" in msg and "remade" in msg
+
+
 def test_c_abi_node_graph(small_world, over_the_mock):
     import test_gpu_nodes as N
     N.test_c_abi_composition_vs_the_reference_nodes(small_world)
