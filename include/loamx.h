@@ -1549,6 +1549,92 @@ int loamx_densemap_segment_cloud_from_pipeline(loamx_densemap* h, loamx_pipeline
 int loamx_segments_match(const loamx_segment* prev, uint64_t n_prev, const loamx_segment* cur, uint64_t n_cur,
                          uint32_t gap /* voxels, 0..1024 */, uint32_t* prev_of_cur /* n_cur words */);   /* host only */
 
+/* Regions, eviction to tile files and paging (optional: a handle that never calls them runs the kernels it ran and exports the same
+ * bytes).  A map of a whole run cannot stay in device memory; these calls hand out a part of the map by place, take a part of it out
+ * into a file, and keep the map around a moving centre with the rest in a directory of tile files.  Every word of a voxel is an
+ * integer sum and loamx_densemap_merge_file adds a file into a live table word for word, so whatever is taken out into a file and
+ * merged back restores the map bit for bit.
+ *
+ * Region: an inclusive window of voxel indices (ix, iy, iz), as in loamx_densemap_segment_config, and a side.  INSIDE selects the
+ * voxels with lo[a] <= i_a <= hi[a] on every axis, OUTSIDE the others.  loamx_densemap_region_check: LOAMX_E_INVALID with a message
+ * that names the field for lo[a] > hi[a], a bound outside +-(2^20 - 1), side > 1, reserved != 0; every call below runs it first.
+ * Host-only helpers, no device:
+ *   region_default   everything, INSIDE.
+ *   region_about     the window of the box centre +- half (LOAM frame, metres): in double, lo_a = floor((c_a - h_a) / leaf) and
+ *                    hi_a = floor((c_a + h_a) / leaf), both clamped to +-(2^20 - 1).  LOAMX_E_INVALID: a non-finite input, a negative
+ *                    half extent, a leaf that create refuses.
+ *   tile_of          tile_a = floor(i_a / T), rounded towards minus infinity (index -1 lies in tile -1); T = tile_voxels in [1, 2^20].
+ *   tile_region      INSIDE, lo = tile * T, hi = tile * T + T - 1, clamped to +-(2^20 - 1); a tile that holds no index of that range:
+ *                    LOAMX_E_INVALID.
+ *   tile_name        "tile_<tx>_<ty>_<tz>.lxdm", signed decimal, with its NUL into buf (cap too small: LOAMX_E_INVALID).
+ *
+ * Reading a region.  count_region: counts[0] = the selected voxels, counts[1] = the sum of their n.  download_region: the records
+ * of loamx_densemap_download for the selected voxels only, in ascending key order; out->count is the capacity on the way in and the
+ * count on the way out (LOAMX_E_CAPACITY: out->count = the needed count, nothing else written).  save_region: an 'LXDM' version 1 file
+ * of the selected voxels by the writer of loamx_densemap_save (temporary name, rename); flags, leaf and the carving configuration are
+ * the handle's, `offered` is the sum of n of the file's voxels, and dropped by range, dropped by key and the six carve statistics are
+ * 0.  load, merge_file and file_info(deep) accept it as it is.  All three wait for the adds as download does, run on the map's own
+ * stream and only read the map: one pass over the keys selects, and only the selected records cross to the host.
+ *
+ * loamx_densemap_evict(h, region, path, removed): the selected voxels leave the map, into the file of save_region when path is not
+ * NULL, discarded when it is.  removed[0] = voxels, removed[1] = points (the sum of their n).  Order: the adds are waited for and the
+ * selected voxels counted; the new table is allocated, the smallest power of two of slots that is >= initial_slots and >= 2 x the
+ * voxels that stay (the table SHRINKS: bounded memory is the point; prune keeps its size); with a path the file is written; the
+ * voxels that are not selected are rehashed into the new table with every word they hold (n, S*, miss, stamp, moments); the table is
+ * replaced.  A failed allocation or a failed write leaves the map, its statistics and the directory as they were, with no file and
+ * no .part file: the allocation comes before the file, so no file can exist for voxels the map still holds.
+ * Statistics: `offered` decreases by removed[1]; the two drop counts and the carve statistics stay.  So evict(region, path) followed
+ * by merge_file(path) restores get_stats (but for slots), get_carve_stats and every export, loamx_densemap_save included, bit for bit.
+ * With a cap, an add refused before an evict is admitted after it.  The frozen snapshot and the coarse levels are not touched, as
+ * with prune.  A handle with history may evict; as with prune, a rebuild brings the voxels back from the log.
+ *
+ * loamx_densemap_file_merge(path_a, path_b, path_out) (host only, no device): the records of two files added per key as
+ * loamx_densemap_merge defines it (n, S* and the moments modulo 2^64, miss modulo 2^32, header statistics summed; the carving
+ * configuration is a's).  Both files get the deep check; the bits of the leaf and the flags must be equal (LOAMX_E_INVALID names
+ * the field).  The output is written under a temporary name and renamed; path_out may equal path_a.
+ *
+ * loamx_densemap_page(h, cfg, centre, stats): the map stays resident around `centre` (LOAM frame, metres), the rest lives in
+ * cfg->dir as one file per tile of tile_voxels^3 voxels, named by tile_name.  The centre tile is tile_of(floor(centre / leaf))
+ * (in double, clamped); the keep box is the tiles within radius[a] of it on axis a.
+ *   Page in: every tile of the keep box that has a file in dir is merged with merge_file, in ascending (tz, ty, tx), and the file is
+ *   unlinked once its merge succeeded.  LOAMX_E_CAPACITY from merge_file ends the call with that status: the tiles not yet merged
+ *   stay on disk, and nothing is paged out.
+ *   Page out: one evict of OUTSIDE the keep box brings the records down once; the host buckets them by tile; a tile that has a file
+ *   already is merged into it on the host (far returns land in tiles that were paged out earlier).  Every tile file of the call is
+ *   first written as .part, then all are renamed, and only then is the table rehashed.  A failed write removes the .part files and
+ *   leaves the map and the directory unchanged.  Nothing to page out: the table stays as it is.
+ *   stats: [0] tiles paged in, [1] voxels merged in, [2] tile files written, [3] voxels paged out, [4] tile files that were merged
+ *   with an existing one, [5] resident voxels afterwards.
+ * Invariant: at every return, the map of the whole run is the resident map plus every tile file, summed as merge sums.
+ * Known limits: with carving, rays do not count misses on voxels that are not resident.  page is not safe against the process dying
+ * between the renames and the rehash (the voxels are then in the files AND in the map).  A handle with history cannot page in,
+ * because merge_file refuses it. */
+#define LOAMX_REGION_INSIDE 0u
+#define LOAMX_REGION_OUTSIDE 1u
+typedef struct loamx_densemap_region {
+  int32_t lo[3], hi[3];   /* inclusive window in voxel indices (ix, iy, iz), as in loamx_densemap_segment_config */
+  uint32_t side;          /* INSIDE: lo[a] <= i_a <= hi[a] on every axis; OUTSIDE: the negation */
+  uint32_t reserved;      /* 0 */
+} loamx_densemap_region;
+typedef struct loamx_densemap_page_config {
+  const char* dir;        /* the tile directory; it must exist */
+  uint32_t tile_voxels;   /* T: voxels per tile edge, in [1, 2^20] */
+  uint32_t radius[3];     /* tiles kept on either side of the centre tile, per axis */
+} loamx_densemap_page_config;
+void loamx_densemap_region_default(loamx_densemap_region* region);                                                /* host only */
+int loamx_densemap_region_check(const loamx_densemap_region* region);                                             /* host only */
+int loamx_densemap_region_about(float leaf, const float centre[3], const float half[3], loamx_densemap_region* region);   /* host only */
+int loamx_densemap_tile_of(const int32_t idx[3], uint32_t tile_voxels, int32_t tile[3]);                          /* host only */
+int loamx_densemap_tile_region(const int32_t tile[3], uint32_t tile_voxels, loamx_densemap_region* region);       /* host only */
+int loamx_densemap_tile_name(const int32_t tile[3], char* buf, uint64_t cap);                                     /* host only */
+int loamx_densemap_file_merge(const char* path_a, const char* path_b, const char* path_out);                      /* host only */
+int loamx_densemap_count_region(loamx_densemap* h, const loamx_densemap_region* region, uint64_t counts[2]);
+int loamx_densemap_download_region(loamx_densemap* h, const loamx_densemap_region* region, loamx_cloud* out, int axes);
+int loamx_densemap_save_region(loamx_densemap* h, const loamx_densemap_region* region, const char* path);
+int loamx_densemap_evict(loamx_densemap* h, const loamx_densemap_region* region, const char* path /* NULL: discard */,
+                         uint64_t removed[2]);
+int loamx_densemap_page(loamx_densemap* h, const loamx_densemap_page_config* cfg, const float centre[3], uint64_t stats[6]);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Place recognition (not in the reference): a database of rotation-invariant sweep descriptors in device memory (Scan Context: a
  * ring x sector polar grid of maximum heights around the sensor) and an exhaustive search for the earlier entries that look like a

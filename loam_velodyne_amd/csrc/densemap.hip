@@ -3,7 +3,7 @@
 // densemap_map.hpp; every feature has a file of its own that holds its kernels, its members of the class and its C entry points:
 //
 //   densemap_dev.hpp      the device helpers that kernels of more than one file share (filter, claim, wave counters, the voxel walk)
-//   densemap.hip          insert, carve, rehash, compaction; create / add / stats / prune / reset / enable_carving / enable_moments
+//   densemap.hip          insert, carve, rehash; create / add / stats / prune / reset / enable_carving / enable_moments
 //   densemap_export.hip   the voxels on the host: records, misses, moment words, surfels, PCD files, and freeze
 //   densemap_merge.hip    save, load, merge of two maps and of a file (densemap_file.hpp)
 //   densemap_raycast.hip  first hits of rays through the table (DmCaster)
@@ -14,6 +14,7 @@
 //   densemap_route.hip    cost-to-go field and routes over that grid (DmRoute, densemap_route_schedule.hpp)
 //   densemap_segment.hip  connected components of the voxels (DmSegment)
 //   densemap_segment_cloud.hip  the objects of a cloud that is not in the map, tested against the table (DmSegCloud)
+//   densemap_region.hip   the compaction (of every voxel, or of a window's), region exports, evict, tile files and paging
 //
 // One insert kernel per add: range filter, voxel key, a combine of equal keys inside the wave, the open-addressing insert and the
 // accumulation, in one pass over the cloud.  The host keeps an upper bound of the occupancy (last known count + points enqueued since)
@@ -29,9 +30,7 @@
 // (covariance, normal, curvature) is computed on the host at export.
 #include "densemap_dev.hpp"
 #include "densemap_map.hpp"
-#include "scan.hpp"
 #include <algorithm>
-#include <numeric>
 
 namespace loamx {
 
@@ -71,18 +70,20 @@ __global__ __launch_bounds__(256) void k_dm_carve(const float4* __restrict__ pts
 }
 
 // every occupied slot of the old table into the new one (keys are unique: claim the first empty slot of the probe sequence).  AUX: the
-// slot's miss and stamp words travel with it.  PRUNE (with AUX): the voxels the rule calls dynamic stay behind, and the survivors are
-// counted into ctr[0] (zeroed before the launch).  MOM: the slot's nine moment words travel with it
-template <bool AUX, bool PRUNE, bool MOM>
+// slot's miss and stamp words travel with it.  DROP: what stays behind — DM_DROP_RULE (with AUX) the voxels the rule calls dynamic,
+// DM_DROP_WINDOW those the window selects (densemap_region.hip, evict); the survivors are then counted into ctr[0] (zeroed before the
+// launch).  MOM: the slot's nine moment words travel with it
+template <bool AUX, int DROP, bool MOM>
 __global__ __launch_bounds__(256) void k_dm_rehash(const unsigned long long* __restrict__ okeys, const unsigned long long* __restrict__ ovals,
                                                    uint32_t on, unsigned long long* __restrict__ keys, unsigned long long* __restrict__ vals,
                                                    uint32_t mask, uint32_t shift, unsigned long long* __restrict__ ctr,
                                                    const uint32_t* __restrict__ oaux, uint32_t* __restrict__ aux, loamx_densemap_static_rule rule,
-                                                   const unsigned long long* __restrict__ omom, unsigned long long* __restrict__ mom) {
+                                                   const unsigned long long* __restrict__ omom, unsigned long long* __restrict__ mom, DmWindow W) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const unsigned long long key = i < on ? okeys[i] : DM_EMPTY;
   bool live = key != DM_EMPTY;
-  if (PRUNE && live) live = !dm_dynamic(rule, ovals[4ull * i], oaux[2ull * i]);
+  if (DROP == DM_DROP_RULE && live) live = !dm_dynamic(rule, ovals[4ull * i], oaux[2ull * i]);
+  if (DROP == DM_DROP_WINDOW && live) live = !dm_in_window(key, W);
   uint32_t slot = 0;
   bool won = false;
   if (live) {
@@ -102,49 +103,7 @@ __global__ __launch_bounds__(256) void k_dm_rehash(const unsigned long long* __r
       ctr[3] = 1ull;
     }
   }
-  if (PRUNE) dm_wave_count(&ctr[0], won);
-}
-
-// compaction of the occupied slots in slot order: occupied slots per 256-slot block (ballot), then (behind an exclusive scan of those
-// counts) each block writes its keys and values at its offset
-__global__ __launch_bounds__(256) void k_dm_count(const unsigned long long* __restrict__ keys, uint32_t slots, uint32_t* __restrict__ blk) {
-  __shared__ uint32_t wc[4];
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned long long m = __ballot(i < slots && keys[i] != DM_EMPTY);
-  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) blk[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
-}
-
-// (AUX: the slot's miss word too; MOM: its nine moment words)
-template <bool AUX, bool MOM>
-__global__ __launch_bounds__(256) void k_dm_compact(const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ vals,
-                                                    uint32_t slots, const uint32_t* __restrict__ blk_off, unsigned long long* __restrict__ okeys,
-                                                    unsigned long long* __restrict__ ovals, const uint32_t* __restrict__ aux,
-                                                    uint32_t* __restrict__ omiss, const unsigned long long* __restrict__ mom,
-                                                    unsigned long long* __restrict__ omom) {
-  __shared__ uint32_t wc[4];
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
-  const bool occ = i < slots && keys[i] != DM_EMPTY;
-  const unsigned long long m = __ballot(occ);
-  if (lane == 0) wc[wid] = (uint32_t)__popcll(m);
-  __syncthreads();
-  if (!occ) return;
-  uint32_t pos = blk_off[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wid; w++) pos += wc[w];
-  okeys[pos] = keys[i];
-  const ulonglong2* s = (const ulonglong2*)(vals + 4ull * i);
-  ulonglong2* d = (ulonglong2*)(ovals + 4ull * pos);
-  d[0] = s[0];
-  d[1] = s[1];
-  if (AUX) omiss[pos] = aux[2ull * i];
-  if (MOM) {
-    const unsigned long long* ms = mom + (unsigned long long)DM_MOM_WORDS * i;
-    unsigned long long* md = omom + (unsigned long long)DM_MOM_WORDS * pos;
-#pragma unroll
-    for (int k = 0; k < DM_MOM_WORDS; k++) md[k] = ms[k];
-  }
+  if (DROP != DM_DROP_NONE) dm_wave_count(&ctr[0], won);
 }
 
 DenseMap::DenseMap(const loamx_densemap_config& c) : cfg(c) {
@@ -213,45 +172,7 @@ void DenseMap::snapshot(Snapshot& S, bool want_mom) {
   snapshot_of(tab_, occ_.occ, S, want_mom);
 }
 
-void DenseMap::snapshot_of(const DmTable& T, uint64_t occ, Snapshot& S, bool want_mom) {
-  const uint32_t nblk = (T.slots + 255) / 256;
-  DevBuf<uint32_t> blk, scratch, omiss;
-  DevBuf<unsigned long long> tiles, okeys, ovals, omom;
-  blk.reserve((size_t)nblk + 1);
-  scratch.reserve(2);
-  tiles.reserve(SCAN_SCRATCH_WORDS / 2);
-  okeys.reserve(occ + 1);
-  ovals.reserve(4 * (occ + 1));
-  if (T.aux) omiss.reserve(occ + 1);
-  if (want_mom) omom.reserve(DM_MOM_WORDS * (occ + 1));
-  LX_HIP(hipMemsetAsync(tiles.p, 0, sizeof(unsigned long long) * (SCAN_SCRATCH_WORDS / 2), own_));
-  hipLaunchKernelGGL(k_dm_count, dim3(nblk), dim3(256), 0, own_, T.keys, T.slots, blk.p);
-  exclusive_scan_u32_n(blk.p, blk.p, (uint32_t*)tiles.p, scratch.p, nblk, own_);
-  dm_dispatch2(T.aux != nullptr, want_mom, [&](auto A, auto M) {   // (an array that is off is not read: omiss.p, omom.p are NULL then)
-    hipLaunchKernelGGL((k_dm_compact<decltype(A)::value, decltype(M)::value>), dim3(nblk), dim3(256), 0, own_, T.keys, T.vals, T.slots, blk.p,
-                       okeys.p, ovals.p, T.aux, omiss.p, T.mom, omom.p);
-  });
-  LX_HIP(hipGetLastError());
-  S.k.resize(occ);
-  S.v.resize(4 * (size_t)occ);
-  S.miss.assign(T.aux ? occ : 0, 0u);
-  S.mom.resize(want_mom ? DM_MOM_WORDS * (size_t)occ : 0);
-  uint32_t total = 0;
-  LX_HIP(hipMemcpyAsync(&total, blk.p + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, own_));
-  if (occ) {
-    LX_HIP(hipMemcpyAsync(S.k.data(), okeys.p, sizeof(unsigned long long) * occ, hipMemcpyDeviceToHost, own_));
-    LX_HIP(hipMemcpyAsync(S.v.data(), ovals.p, sizeof(unsigned long long) * 4 * occ, hipMemcpyDeviceToHost, own_));
-    if (T.aux) LX_HIP(hipMemcpyAsync(S.miss.data(), omiss.p, sizeof(uint32_t) * occ, hipMemcpyDeviceToHost, own_));
-    if (want_mom)
-      LX_HIP(hipMemcpyAsync(S.mom.data(), omom.p, sizeof(unsigned long long) * DM_MOM_WORDS * occ, hipMemcpyDeviceToHost, own_));
-  }
-  LX_HIP(hipStreamSynchronize(own_));
-  scan_check_errors();
-  LX_REQUIRE(total == occ, "dense map: the compaction disagrees with the occupancy count");
-  S.idx.resize(occ);
-  std::iota(S.idx.begin(), S.idx.end(), 0u);
-  std::sort(S.idx.begin(), S.idx.end(), [&](uint32_t a, uint32_t b) { return S.k[a] < S.k[b]; });
-}
+void DenseMap::snapshot_of(const DmTable& T, uint64_t occ, Snapshot& S, bool want_mom) { compact_of(T, nullptr, occ, &S, want_mom, nullptr); }
 
 void DenseMap::enable_moments() {
   read_counters();
@@ -286,7 +207,7 @@ uint64_t DenseMap::prune(const loamx_densemap_static_rule& rule) {
   nt.alloc(tab_.slots, true, tab_.mom != nullptr);   // (aux whatever the map has: the callers require carving)
   nt.clear(own_);
   LX_HIP(hipMemsetAsync(ctr_.p, 0, sizeof(unsigned long long), own_));   // (the occupancy: recounted by the kernel)
-  launch_rehash<true>(own_, nt, rule);
+  launch_rehash<DM_DROP_RULE>(own_, nt, rule, DmWindow());
   LX_HIP(hipGetLastError());
   replace_table(nt);
   read_counters();
@@ -328,16 +249,18 @@ void DenseMap::replace_table(DmTable& nt) {
   tab_.swap(nt);
   nt.retire(graveyard_);
 }
-// the current table into nt on st, under the map's features; PRUNE (carving is on): the rule's dynamic voxels stay behind
-template <bool PRUNE> void DenseMap::launch_rehash(hipStream_t st, const DmTable& nt, const loamx_densemap_static_rule& rule) {
+// the current table into nt on st, under the map's features; DROP: DM_DROP_RULE (carving is on) the rule's dynamic voxels stay
+// behind, DM_DROP_WINDOW those the window selects
+template <int DROP> void DenseMap::launch_rehash(hipStream_t st, const DmTable& nt, const loamx_densemap_static_rule& rule, const DmWindow& W) {
   const DmTable& T = tab_;
   dm_dispatch2(T.aux != nullptr, T.mom != nullptr, [&](auto A, auto M) {
     constexpr bool AUX = decltype(A)::value, MOM = decltype(M)::value;
-    if constexpr (AUX || !PRUNE)
-      hipLaunchKernelGGL((k_dm_rehash<AUX, PRUNE, MOM>), dim3((T.slots + 255) / 256), dim3(256), 0, st, T.keys, T.vals, T.slots, nt.keys, nt.vals,
-                         nt.mask(), nt.shift(), ctr_.p, T.aux, nt.aux, rule, T.mom, nt.mom);
+    if constexpr (AUX || DROP != DM_DROP_RULE)
+      hipLaunchKernelGGL((k_dm_rehash<AUX, DROP, MOM>), dim3((T.slots + 255) / 256), dim3(256), 0, st, T.keys, T.vals, T.slots, nt.keys, nt.vals,
+                         nt.mask(), nt.shift(), ctr_.p, T.aux, nt.aux, rule, T.mom, nt.mom, W);
   });
 }
+template void DenseMap::launch_rehash<DM_DROP_WINDOW>(hipStream_t, const DmTable&, const loamx_densemap_static_rule&, const DmWindow&);   // (densemap_region.hip)
 // the insert of one add; the combine by the bench hook, the moment words when the map has them
 template <bool STAMP> void DenseMap::launch_insert(hipStream_t st, const float4* pts, uint32_t n, const DmFilter& F, uint32_t seq) {
   const DmTable& T = tab_;
@@ -396,7 +319,7 @@ void DenseMap::grow_for(uint64_t n, hipStream_t st) {
     DmTable nt;
     nt.alloc(want, tab_.aux != nullptr, tab_.mom != nullptr);
     nt.clear(st);
-    launch_rehash<false>(st, nt, loamx_densemap_static_rule{0u, 0u, 0u});
+    launch_rehash<DM_DROP_NONE>(st, nt, loamx_densemap_static_rule{0u, 0u, 0u}, DmWindow());
     replace_table(nt);
     rehashes++;
   }

@@ -57,6 +57,29 @@ __device__ inline void dm_wave_sum(unsigned long long* ctr, uint32_t v) {
   if (v && (threadIdx.x & 63) == 0) atomicAdd(ctr, (unsigned long long)v);
 }
 
+// the same for a 64-bit value per lane (modulo 2^64): one atomic per wave
+__device__ inline void dm_wave_sum64(unsigned long long* ctr, unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
+  if (v && (threadIdx.x & 63) == 0) atomicAdd(ctr, v);
+}
+
+// A window of voxel indices as the kernels test it (include/loamx.h, loamx_densemap_region): lo <= i <= hi on every axis, or with
+// `outside` the negation.  Integer compares on the three 21-bit fields of the key; the caller has an occupied slot's key
+struct DmWindow {
+  int lo[3], hi[3];
+  uint32_t outside;
+};
+__device__ inline bool dm_in_window(unsigned long long key, const DmWindow& W) {
+  const int ix = (int)(key & 0x1FFFFFull) - (1 << DM_QBITS), iy = (int)((key >> DM_KBITS) & 0x1FFFFFull) - (1 << DM_QBITS),
+            iz = (int)((key >> (2 * DM_KBITS)) & 0x1FFFFFull) - (1 << DM_QBITS);
+  const bool in = ix >= W.lo[0] && ix <= W.hi[0] && iy >= W.lo[1] && iy <= W.hi[1] && iz >= W.lo[2] && iz <= W.hi[2];
+  return in != (W.outside != 0u);
+}
+
+// what a rehash leaves behind (k_dm_rehash, densemap.hip)
+constexpr int DM_DROP_NONE = 0, DM_DROP_RULE = 1, DM_DROP_WINDOW = 2;
+
 // the key rule of a point: its cell's indices stay inside the key (a NaN or an infinite component fails it too)
 __device__ inline bool dm_in_key_range(const float4 p, float inv) {
   return fabsf(floorf(p.x * inv)) < DM_IMAX && fabsf(floorf(p.y * inv)) < DM_IMAX && fabsf(floorf(p.z * inv)) < DM_IMAX;

@@ -48,9 +48,9 @@ void dm_surfel(double leaf, const long long ia[3], const unsigned long long* v4,
   out.curvature = (float)curv;
 }
 
-void DenseMap::records(std::vector<float4>& out, int axes, const loamx_densemap_static_rule* rule) {
+void DenseMap::records(std::vector<float4>& out, int axes, const loamx_densemap_static_rule* rule, const DmWindow* W) {
   Snapshot S;
-  snapshot(S);
+  if (W) select(*W, &S, false, nullptr); else snapshot(S);
   out.clear();
   out.reserve(S.idx.size());
   const double leaf = (double)cfg.leaf;

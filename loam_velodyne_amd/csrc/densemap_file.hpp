@@ -166,11 +166,10 @@ inline std::string dmf_read(const char* path, bool deep, DmFile& out) {
   return dmf_check_records(out.keys.data(), out.vals.data(), n);
 }
 
-// header and records (ascending keys; miss / mom NULL without the feature) to a temporary name beside `path`, renamed when complete:
-// a write that fails leaves nothing under `path`.  "" or the reason
-inline std::string dmf_write(const char* path, const DmFileHeader& h, const uint64_t* keys, const uint64_t* vals, const uint32_t* miss,
-                             const uint64_t* mom) {
-  const std::string tmp = std::string(path) + ".part";
+// header and records (ascending keys; miss / mom NULL without the feature) under the name `tmp` itself; a write that fails leaves
+// nothing there.  "" or the reason (`path`: the name the messages speak of)
+inline std::string dmf_write_part(const std::string& tmp, const char* path, const DmFileHeader& h, const uint64_t* keys, const uint64_t* vals,
+                                  const uint32_t* miss, const uint64_t* mom) {
   FILE* f = fopen(tmp.c_str(), "wb");
   if (!f) return "cannot open " + tmp + " for writing";
   unsigned char hdr[DMF_HEADER_BYTES];
@@ -184,7 +183,18 @@ inline std::string dmf_write(const char* path, const DmFileHeader& h, const uint
   }
   if (ok && (h.flags & DMF_MOMENTS) && n) ok = fwrite(mom, 8 * DMF_MOM_WORDS, n, f) == n;
   const bool closed = fclose(f) == 0;
-  if (ok && closed && rename(tmp.c_str(), path) == 0) return "";
+  if (ok && closed) return "";
+  (void)remove(tmp.c_str());
+  return std::string("write to ") + path + " failed";
+}
+
+// the same to a temporary name beside `path`, renamed when complete: a write that fails leaves nothing under `path`.  "" or the reason
+inline std::string dmf_write(const char* path, const DmFileHeader& h, const uint64_t* keys, const uint64_t* vals, const uint32_t* miss,
+                             const uint64_t* mom) {
+  const std::string tmp = std::string(path) + ".part";
+  const std::string e = dmf_write_part(tmp, path, h, keys, vals, miss, mom);
+  if (!e.empty()) return e;
+  if (rename(tmp.c_str(), path) == 0) return "";
   (void)remove(tmp.c_str());
   return std::string("write to ") + path + " failed";
 }

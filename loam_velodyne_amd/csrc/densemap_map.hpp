@@ -10,6 +10,8 @@ namespace loamx {
 struct DmFilter;   // densemap_dev.hpp
 struct DmCarve;
 struct DmCtrAdd;   // densemap_merge.hip
+struct DmWindow;
+struct DmFileHeader;   // densemap_file.hpp
 
 // two runtime booleans as the two std::bool_constant arguments of f: the kernels' feature switches are template parameters
 template <class F> static void dm_dispatch2(bool a, bool b, F&& f) {
@@ -64,7 +66,8 @@ class DenseMap {
 
   // ---- densemap_export.hip: the voxels on the host.  records: axes 0: LOAM frame, 1: sensor axes, ascending key order; with a rule,
   // without the voxels it calls dynamic.  misses, moment_words, surfels: in the order of records()
-  void records(std::vector<float4>& out, int axes, const loamx_densemap_static_rule* rule = nullptr);
+  // (W: only the voxels the window selects)
+  void records(std::vector<float4>& out, int axes, const loamx_densemap_static_rule* rule = nullptr, const DmWindow* W = nullptr);
   void misses(std::vector<uint32_t>& out);
   void moment_words(std::vector<unsigned long long>& out);
   void surfels(std::vector<loamx_surfel>& out, int axes, const loamx_densemap_surfel_config& sc, const loamx_densemap_static_rule* rule);
@@ -93,6 +96,19 @@ class DenseMap {
   void save(const char* path);
   int merge(DenseMap& src);
   int merge_file(const char* path, bool loading);
+
+  // ---- densemap_region.hip: include/loamx.h, loamx_densemap_count_region ... page.  A checked window each
+  // the compaction behind snapshot_of and select: the occupied slots of T (W: of those, the ones the window selects) in slot order
+  // on own_, brought to the host and ordered by key.  Without W, occ is T's count and one wait serves; with W the block counts are
+  // scanned and the total and the sum of n waited for first (counts, when given: voxels, points), and only the selected records
+  // cross.  S NULL (with W): the counts alone
+  void compact_of(const DmTable& T, const DmWindow* W, uint64_t occ, Snapshot* S, bool want_mom, uint64_t counts[2]);
+  // waits for the adds; the voxels the window selects as a snapshot (S NULL: only counted)
+  void select(const DmWindow& W, Snapshot* S, bool want_mom, uint64_t counts[2]);
+  void save_region(const DmWindow& W, const char* path);
+  // the selected voxels leave the table (path: into a file first; NULL: discarded); removed: voxels, points
+  void evict(const DmWindow& W, const char* path, uint64_t removed[2]);
+  int page(const char* dir, uint32_t tile_voxels, const uint32_t radius[3], const float centre[3], uint64_t stats[6]);
 
   // ---- densemap_raycast.hip: include/loamx.h, loamx_densemap_raycast (the ends staged from the host) and its from_* forms (the
   // registered cloud where it lies)
@@ -168,7 +184,7 @@ class DenseMap {
   DmFilter filter_for(const float origin[3]) const;   // the insert's filter about an origin
   DmCarve carve_args(uint32_t seq) const;             // the ray kernel's arguments for the call with that stamp
   void replace_table(DmTable& nt);   // nt becomes the map's table; the one it replaces goes to the graveyard
-  template <bool PRUNE> void launch_rehash(hipStream_t st, const DmTable& nt, const loamx_densemap_static_rule& rule);
+  template <int DROP> void launch_rehash(hipStream_t st, const DmTable& nt, const loamx_densemap_static_rule& rule, const DmWindow& W);
   template <bool STAMP> void launch_insert(hipStream_t st, const float4* pts, uint32_t n, const DmFilter& F, uint32_t seq);
   void clear(hipStream_t st);        // the table and the counters (the one place that zeroes both)
   void free_graveyard();
@@ -182,6 +198,8 @@ class DenseMap {
   // ---- densemap_merge.hip
   void merge_records(const unsigned long long* skeys, const unsigned long long* svals, uint32_t sn, uint64_t s_occ, const uint32_t* smiss,
                      uint32_t miss_stride, const unsigned long long* smom, const DmCtrAdd& add, uint64_t s_offered);
+  // ---- densemap_region.hip
+  void region_header(DmFileHeader& H) const;   // flags, leaf and the carving configuration of the handle; every statistic 0
   // ---- densemap_raycast.hip
   void cast(const float4* pts, uint32_t n, const float origin[3], const loamx_densemap_raycast_config& c,
             const loamx_densemap_static_rule* rule, loamx_ray_hit* out, uint64_t counts[5]);

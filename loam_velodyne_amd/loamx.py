@@ -1036,6 +1036,91 @@ def densemap_file_info(path: str, deep: bool = False) -> dict:
                            max_steps=int(i.carve.max_steps)) if carving else None)
 
 
+REGION_INSIDE, REGION_OUTSIDE = 0, 1
+
+
+class DenseMapRegion(C.Structure):
+    """loamx_densemap_region: an inclusive window of voxel indices and a side (REGION_INSIDE: the voxels inside it, REGION_OUTSIDE:
+    the others).  DenseMapRegion() selects everything; lo / hi: three indices each"""
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("side", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, lo=None, hi=None, side=None):
+        super().__init__()
+        lib().loamx_densemap_region_default(C.byref(self))
+        if lo is not None:
+            self.lo[:] = [int(v) for v in lo]
+        if hi is not None:
+            self.hi[:] = [int(v) for v in hi]
+        if side is not None:
+            self.side = side
+
+    def check(self):
+        """loamx_densemap_region_check (host only): LoamxError E_INVALID names the offending field"""
+        _check(lib().loamx_densemap_region_check(C.byref(self)))
+        return self
+
+    def outside(self) -> "DenseMapRegion":
+        """the same window with the other side"""
+        return DenseMapRegion(list(self.lo), list(self.hi), REGION_OUTSIDE if self.side == REGION_INSIDE else REGION_INSIDE)
+
+    def as_dict(self) -> dict:
+        return dict(lo=list(self.lo), hi=list(self.hi), side=int(self.side))
+
+
+class DenseMapPageConfig(C.Structure):
+    """loamx_densemap_page_config: the tile directory, the voxels per tile edge and the tiles kept around the centre tile per axis"""
+    _fields_ = [("dir", C.c_char_p), ("tile_voxels", C.c_uint32), ("radius", C.c_uint32 * 3)]
+
+    def __init__(self, dir=None, tile_voxels=64, radius=(1, 1, 1)):
+        super().__init__()
+        self.dir = os.fsencode(dir) if dir is not None else None
+        self.tile_voxels = tile_voxels
+        self.radius[:] = [int(v) for v in radius]
+
+
+def _f3(v):
+    a = np.ascontiguousarray(v, np.float32)
+    assert a.shape == (3,)
+    return a
+
+
+def _i3(v):
+    return (C.c_int32 * 3)(*[int(x) for x in v])
+
+
+def densemap_region_about(leaf: float, centre, half) -> DenseMapRegion:
+    """loamx_densemap_region_about (host only): the window of the box centre +- half (metres) in a map of this leaf"""
+    r, c, h = DenseMapRegion(), _f3(centre), _f3(half)
+    _check(lib().loamx_densemap_region_about(C.c_float(leaf), c.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p), C.byref(r)))
+    return r
+
+
+def densemap_tile_of(idx, tile_voxels: int):
+    """loamx_densemap_tile_of (host only): the tile of a voxel, floor(i / tile_voxels) per axis"""
+    t = (C.c_int32 * 3)()
+    _check(lib().loamx_densemap_tile_of(_i3(idx), C.c_uint32(tile_voxels), t))
+    return tuple(int(v) for v in t)
+
+
+def densemap_tile_region(tile, tile_voxels: int) -> DenseMapRegion:
+    """loamx_densemap_tile_region (host only): the voxels of a tile as a window"""
+    r = DenseMapRegion()
+    _check(lib().loamx_densemap_tile_region(_i3(tile), C.c_uint32(tile_voxels), C.byref(r)))
+    return r
+
+
+def densemap_tile_name(tile) -> str:
+    """loamx_densemap_tile_name (host only): tile_<tx>_<ty>_<tz>.lxdm"""
+    buf = C.create_string_buffer(64)
+    _check(lib().loamx_densemap_tile_name(_i3(tile), buf, C.c_uint64(64)))
+    return buf.value.decode()
+
+
+def densemap_file_merge(path_a: str, path_b: str, path_out: str):
+    """loamx_densemap_file_merge (host only): the records of two dense map files added per key, as DenseMap.merge adds"""
+    _check(lib().loamx_densemap_file_merge(os.fsencode(path_a), os.fsencode(path_b), os.fsencode(path_out)))
+
+
 class StaticRule(C.Structure):
     """loamx_densemap_static_rule: a voxel is dynamic iff miss >= min_misses and miss * den > n * num.  StaticRule() is the default
     rule (3, 1, 1)."""
@@ -2028,6 +2113,45 @@ class DenseMap:
     def merge_file(self, path: str):
         """loamx_densemap_merge_file: the same with a saved map as the source"""
         _check(lib().loamx_densemap_merge_file(self.h, os.fsencode(path)))
+
+    def count_region(self, region: DenseMapRegion):
+        """loamx_densemap_count_region: (voxels, points) the region selects, counted on the device"""
+        c = (C.c_uint64 * 2)()
+        _check(lib().loamx_densemap_count_region(self.h, C.byref(region), c))
+        return int(c[0]), int(c[1])
+
+    def region_points(self, region: DenseMapRegion, axes="loam"):
+        """loamx_densemap_download_region: the records of points() for the voxels the region selects only, in ascending key order;
+        only those cross to the host"""
+        n = 0
+        while True:
+            out = np.zeros((max(n, 1), 4), np.float32)
+            c = cloud_of(out)
+            c.count = n
+            rc = lib().loamx_densemap_download_region(self.h, C.byref(region), C.byref(c), _axes(axes))
+            if rc == E_CAPACITY:
+                n = int(c.count)
+                continue
+            _check(rc)
+            return out[:c.count]
+
+    def save_region(self, region: DenseMapRegion, path: str):
+        """loamx_densemap_save_region: the voxels the region selects as an 'LXDM' file that load and merge_file accept"""
+        _check(lib().loamx_densemap_save_region(self.h, C.byref(region), os.fsencode(path)))
+
+    def evict(self, region: DenseMapRegion, path=None):
+        """loamx_densemap_evict: the voxels the region selects leave the map — into the file `path` (merge_file brings them back bit
+        for bit), or discarded with path None — and the table shrinks to what stays.  Returns (voxels, points) removed"""
+        r = (C.c_uint64 * 2)()
+        _check(lib().loamx_densemap_evict(self.h, C.byref(region), os.fsencode(path) if path is not None else None, r))
+        return int(r[0]), int(r[1])
+
+    def page(self, cfg: DenseMapPageConfig, centre) -> dict:
+        """loamx_densemap_page: the tiles of cfg.dir around `centre` merged in, everything outside the keep box moved out to tile files"""
+        s, c = (C.c_uint64 * 6)(), _f3(centre)
+        _check(lib().loamx_densemap_page(self.h, C.byref(cfg), c.ctypes.data_as(C.c_void_p), s))
+        keys = ("tiles_in", "voxels_in", "files_written", "voxels_out", "files_merged", "resident")
+        return dict(zip(keys, (int(v) for v in s)))
 
     def enable_history(self, max_bytes=0, initial_points=1 << 20):
         """the sweep log (include/loamx.h): from now on every add also appends its whole cloud, as offered, to a block in device
