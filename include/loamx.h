@@ -1403,6 +1403,86 @@ int loamx_grid_route_points(const loamx_densemap_grid_config* grid_cfg, float le
 int loamx_densemap_grid_cell_of(const loamx_densemap_grid_config* grid_cfg, float leaf, float x, float z, uint32_t* rx, uint32_t* rz,
                                 int* inside);   /* host only */
 
+/* Frontiers of the navigation grid (optional: a handle that never asks for them runs the kernels it ran and allocates what it
+ * allocated; loamx_densemap_grid and the route calls return the bytes they returned).  "Where do I go when nobody names a cell?":
+ * where known free ground meets ground the map has not seen (Yamauchi's frontier-based exploration).  The frontier cells of a window,
+ * grouped into connected frontiers, each with its size, box, centroid sums, the width of its opening and the cheapest of its cells to
+ * reach, computed on the device from the grid and the field where they lie; a few records of 64 bytes come back.  Every word is an
+ * exact function of the grid's integers (cls, clear2) and of the field.
+ *
+ * Cells, the window and record indices are those of the routing section: a cell is (rx, rz), window-relative, record c = rz * nx + rx.
+ * Frontier cell: a cell with cls == LOAMX_GRID_FREE and clear2 >= min_clear2 of whose eight neighbours (rx + dx, rz + dz),
+ * |dx|, |dz| <= 1, not both 0, that lie inside the window at least min_unknown have cls == LOAMX_GRID_UNKNOWN.  Cells outside the
+ * window are not unknown: a FREE cell on the outermost ring is a frontier cell only on account of neighbours inside the window, the
+ * rule STEP follows at the edge.  unknown8(c) is the count of those unknown neighbours, 0..8.
+ * Adjacency: two frontier cells are adjacent iff they differ by (dx, dz) with |dx|, |dz| <= 1, not both 0, and |dx| + |dz| <= 1
+ * under connectivity == 4, <= 2 under 8.  A cell that is no frontier cell connects nothing.
+ * Frontiers: the classes of the transitive closure of adjacency.  A frontier is kept iff it has at least min_cells cells; the kept
+ * ones are numbered 0 .. F-1 in ascending min_cell, the smallest record index in them, and out[f] is frontier f.
+ * Labels (optional): one uint32_t per cell in record order: the number of the cell's frontier, LOAMX_FRONTIER_NONE for a cell that
+ * is no frontier cell or whose frontier was dropped.
+ * stats[6]: frontier cells;  frontiers before min_cells;  frontiers kept;  cells in kept frontiers;  kept frontiers with
+ * reachable > 0;  hook attempts that lost to another thread.  The first five are part of the definition and exact, the last
+ * describes the schedule.
+ * The field: move costs are symmetric (the routing section), so the cost from the vehicle to a cell is the cost-to-go of a field whose
+ * only goal is the vehicle's cell.  With start_xz given the call routes towards that one goal under route_cfg exactly as
+ * loamx_densemap_route_cells would; the field stays in the handle as that call's would and replaces the last one, so
+ * loamx_densemap_route_trace from a frontier's best_cell yields the route from the frontier to the vehicle: reversed, the way there.
+ * A start outside the window or on a blocked cell is ignored, as a goal is: every frontier then has reachable == 0 and the call is
+ * still LOAMX_OK.  With start_xz == NULL nothing is routed, the handle's field is left alone, and reachable, best_cost and
+ * best_cell hold 0, LOAMX_ROUTE_UNREACHABLE and LOAMX_FRONTIER_NONE.
+ *
+ * loamx_densemap_frontiers: runs the grid of grid_cfg / rule exactly as loamx_densemap_grid does, routes when a start is given, and
+ * finds the frontiers on the records where they lie on the device; only the kept records cross, and the labels when wanted.
+ * loamx_densemap_frontiers_cells: the same on a grid of the caller's, uploaded as loamx_densemap_route_cells uploads; nothing that
+ * loamx_densemap_grid keeps is replaced or disturbed.
+ * loamx_frontiers_best (host only, no device): *best = the index of the frontier with the smallest best_cost among those with
+ * min_cost <= best_cost < LOAMX_ROUTE_UNREACHABLE, ties to the smaller index; LOAMX_FRONTIER_NONE when there is none.  min_cost
+ * lets the caller skip the frontier it is standing on.  LOAMX_E_INVALID for a NULL best, or a NULL f with n > 0.
+ * Ordering: as loamx_densemap_segment the calls wait for every add, run on the map's own stream and block until the outputs are back
+ * through pinned memory.  The map is only read: every export is byte for byte what it was before the call.  Integer atomics only.
+ * The work arrays live in the handle, are allocated by the first call, grow to the largest window asked for and are freed on
+ * destroy.  labels and out may each be NULL: that output is skipped.  The outputs are written last, all or none.  An all-UNKNOWN
+ * grid or an empty map is LOAMX_OK with every count zero.
+ * LOAMX_E_INVALID, with a message that names the argument, nothing written to any output: NULL h, n_frontiers or stats;  a
+ * configuration that fails loamx_grid_frontier_check (connectivity not 4 or 8;  min_unknown outside 1..8;  min_clear2 or min_cells 0)
+ * or loamx_grid_route_check;  everything the grid or the route call under it refuses (cells NULL, a cls above 3);  nx * nz > 2^22
+ * when a start is given;  nx * nz > 2^26 always.
+ * LOAMX_E_CAPACITY: out given and capacity < F.  Only *n_frontiers is written, and it holds the needed count.
+ * LOAMX_E_INTERNAL: a bound of the union-find was reached, which its invariant excludes. */
+#define LOAMX_FRONTIER_NONE 0xFFFFFFFFu
+typedef struct loamx_grid_frontier_config {
+  uint32_t connectivity;   /* grouping of frontier cells, 4 or 8 (default 8) */
+  uint32_t min_unknown;    /* UNKNOWN cells among the eight neighbours, 1..8 (default 1) */
+  uint32_t min_clear2;     /* a frontier cell has clear2 >= this, >= 1 (default 1) */
+  uint32_t min_cells;      /* frontiers with fewer cells are dropped, >= 1 (default 1) */
+} loamx_grid_frontier_config;
+typedef struct loamx_frontier {   /* 64 bytes */
+  uint32_t min_cell;       /* smallest record index of its cells: its identity */
+  uint32_t cells;          /* frontier cells in it */
+  uint32_t lo[2], hi[2];   /* inclusive box, (rx, rz) */
+  uint64_t sum_rx, sum_rz; /* sums of rx and of rz over its cells (the centroid's numerators) */
+  uint64_t unknown_links;  /* sum of unknown8 over its cells: how wide the opening is */
+  uint32_t reachable;      /* its cells with a finite cost in the field; 0 without a field */
+  uint32_t best_cost;      /* smallest cost over its cells; LOAMX_ROUTE_UNREACHABLE: none, or no field */
+  uint32_t best_cell;      /* smallest record index among its cells with cost == best_cost; LOAMX_FRONTIER_NONE: none */
+  uint32_t reserved;       /* 0 */
+} loamx_frontier;
+void loamx_grid_frontier_default_config(loamx_grid_frontier_config* cfg);   /* host only */
+int loamx_grid_frontier_check(const loamx_grid_frontier_config* cfg);        /* host only; names the first bad field */
+int loamx_densemap_frontiers(loamx_densemap* h, const loamx_densemap_grid_config* grid_cfg /* NULL: the defaults */,
+                             const loamx_densemap_static_rule* rule /* NULL: every voxel; else needs carving */,
+                             const loamx_grid_route_config* route_cfg /* NULL: the defaults */,
+                             const loamx_grid_frontier_config* cfg /* NULL: the defaults */, const uint32_t start_xz[2] /* NULL: no routing */,
+                             uint32_t* labels /* nx * nz; NULL: not wanted */, loamx_frontier* out /* NULL: not wanted */,
+                             uint64_t capacity, uint64_t* n_frontiers, uint64_t stats[6]);
+int loamx_densemap_frontiers_cells(loamx_densemap* h, const loamx_grid_cell* cells, uint32_t nx, uint32_t nz,
+                                   const loamx_grid_route_config* route_cfg /* NULL: the defaults */,
+                                   const loamx_grid_frontier_config* cfg /* NULL: the defaults */, const uint32_t start_xz[2] /* NULL: no routing */,
+                                   uint32_t* labels /* nx * nz; NULL: not wanted */, loamx_frontier* out /* NULL: not wanted */,
+                                   uint64_t capacity, uint64_t* n_frontiers, uint64_t stats[6]);
+int loamx_frontiers_best(const loamx_frontier* f, uint64_t n, uint32_t min_cost, uint32_t* best);   /* host only, no device */
+
 /* Objects: connected components of the voxel map (optional: a handle that never segments runs the kernels it ran and allocates what
  * it allocated).  "Which voxels belong together?": on the voxel lattice, Euclidean clustering with a tolerance of one leaf is
  * connected-component labelling of the selected voxels, done on the device where the table lies; a component list and one word

@@ -252,6 +252,8 @@ class DmRoute {
   bool has_field() const { return valid_; }
   // the routes of n_starts in 1..4096 starts over the field of the last run (include/loamx.h, loamx_densemap_route_trace); blocks
   void trace(const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity, uint32_t* lengths, hipStream_t st);
+  // the field of the last run where it lies on the device (DmFrontier reads the costs there), valid until the next run
+  const loamx_route_cell* field_on_device() const { return field_.p; }
 
   uint32_t batch = 16;          // rounds per look (bench / test hook; the choice and its measurement: densemap_route.hip)
   uint64_t active_rounds = 0;   // of the last run: rounds in which a tile ran (test hook)
@@ -271,6 +273,47 @@ class DmRoute {
   PinBuf<unsigned long long> h_off_;
   uint32_t nx_ = 0, nz_ = 0;
   bool valid_ = false;
+};
+
+// include/loamx.h, loamx_grid_frontier_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
+void dm_frontier_check(const loamx_grid_frontier_config& c);
+
+// the accumulator of one frontier on the device: loamx_frontier with best_cost and best_cell as one aligned 64-bit word,
+// (cost << 32) | cell, so that one atomicMin keeps "the smallest cost, then the smallest index"
+struct DmFrAcc {
+  uint32_t min_cell, cells, lo[2], hi[2];
+  unsigned long long sum_rx, sum_rz, links, best;
+  uint32_t reachable, reserved;
+};
+static_assert(sizeof(DmFrAcc) == 64 && sizeof(loamx_frontier) == 64, "64-byte records");
+
+// Frontiers of the navigation grid (include/loamx.h, loamx_densemap_frontiers ...; densemap_frontier.hip): one parent word, one id word
+// and one byte per cell of a window, the per-block root counts, the frontiers' accumulators, the labels, and the pinned blocks the
+// counters, the accumulators, the ranks and the labels cross through.  Allocated by the first call, grow to the largest window asked
+// for; the map, the grid's records and the route's field are only read.
+class DmFrontier {
+ public:
+  DmFrontier() = default;
+  DmFrontier(const DmFrontier&) = delete;
+  DmFrontier& operator=(const DmFrontier&) = delete;
+  // the frontiers of nx * nz <= 2^26 records d_cells on the device (written by work enqueued on st) under a checked configuration:
+  // mark, link, flatten, the scan, ids and reduce, and the host's min_cells and ranks.  d_field (NULL: none): the nx * nz records of a
+  // route's field on the device, whose costs give reachable and best.  Blocks.  out: the kept frontiers in ascending min_cell; stats
+  // as in include/loamx.h.  Returns, when want_labels, the nx * nz labels in pinned memory, valid until the next run
+  const uint32_t* run(const loamx_grid_cell* d_cells, uint32_t nx, uint32_t nz, const loamx_grid_frontier_config& c,
+                      const loamx_route_cell* d_field, bool want_labels, std::vector<loamx_frontier>& out, uint64_t stats[6], hipStream_t st);
+
+ private:
+  DevBuf<uint32_t> parent_, rootid_;   // per cell: the union-find word (NONE: no frontier cell); the compact id of a root
+  DevBuf<unsigned char> u8_;           // per cell: unknown8 of a frontier cell
+  DevBuf<uint32_t> blk_;               // roots per 256-cell block, + 1 word for the total
+  DevBuf<uint32_t> scratch_;           // the scan's two words
+  DevBuf<unsigned long long> tiles_;   // the scan's chain state, zeroed when allocated
+  DevBuf<uint32_t> ctr_;               // frontier cells, hook attempts lost, a loop bound reached, roots
+  DevBuf<DmFrAcc> acc_;                // one accumulator per frontier, by compact id
+  DevBuf<uint32_t> rank_, lab_;        // with labels: per compact id its rank (NONE: dropped); per cell its label
+  PinBuf<uint32_t> h_ctr_, h_rank_, h_lab_;
+  PinLanding<DmFrAcc> h_acc_;
 };
 
 // include/loamx.h, loamx_densemap_segment_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds

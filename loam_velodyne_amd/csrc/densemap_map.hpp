@@ -134,6 +134,14 @@ class DenseMap {
                    uint32_t n_goals, loamx_route_cell* out_field, uint64_t stats[6]);
   void route_trace(const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity, uint32_t* lengths);
   DmRoute& router() { return route_; }
+  // ---- densemap_frontier.hip: include/loamx.h, loamx_densemap_frontiers and loamx_densemap_frontiers_cells; checked configurations.
+  // LOAMX_E_CAPACITY: only *n_frontiers is written
+  int frontiers(const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, const loamx_grid_route_config& rc,
+                const loamx_grid_frontier_config& fc, const uint32_t* start_xz, uint32_t* labels, loamx_frontier* out, uint64_t capacity,
+                uint64_t* n_frontiers, uint64_t stats[6]);
+  int frontiers_cells(const loamx_grid_cell* cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config& rc,
+                      const loamx_grid_frontier_config& fc, const uint32_t* start_xz, uint32_t* labels, loamx_frontier* out,
+                      uint64_t capacity, uint64_t* n_frontiers, uint64_t stats[6]);
   int segment(const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint32_t* labels, uint64_t label_capacity,
               uint64_t* n_voxels, loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[6]);
   // ---- densemap_segment_cloud.hip: include/loamx.h, loamx_densemap_segment_cloud (the cloud staged from the host) and its from_*
@@ -177,6 +185,7 @@ class DenseMap {
   DmCaster caster_;   // densemap_raycast.hip
   DmGrid grid_;       // densemap_grid.hip
   DmRoute route_;     // densemap_route.hip
+  DmFrontier fr_;     // densemap_frontier.hip (routes towards the start through route_)
   DmSegment seg_;     // densemap_segment.hip
   DmSegCloud cseg_;   // densemap_segment_cloud.hip (labels its scratch table through seg_)
 
@@ -203,6 +212,10 @@ class DenseMap {
   // ---- densemap_raycast.hip
   void cast(const float4* pts, uint32_t n, const float origin[3], const loamx_densemap_raycast_config& c,
             const loamx_densemap_static_rule* rule, loamx_ray_hit* out, uint64_t counts[5]);
+  // ---- densemap_frontier.hip: the tail of the two forms, behind a wait_adds(): the nx * nz records d_cells written by work on own_
+  int frontiers_on(const loamx_grid_cell* d_cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config& rc,
+                   const loamx_grid_frontier_config& fc, const uint32_t* start_xz, uint32_t* labels, loamx_frontier* out, uint64_t capacity,
+                   uint64_t* n_frontiers, uint64_t stats[6]);
   // ---- densemap_segment_cloud.hip: the tail of the three forms, behind a wait_adds(): n points readable on own_
   int segment_cloud(const float4* pts, uint32_t n, const float origin[3], const loamx_densemap_segment_cloud_config& c,
                     const loamx_densemap_static_rule* rule, uint32_t* labels, uint64_t label_capacity, uint64_t* n_points, loamx_segment* segs,

@@ -1300,7 +1300,7 @@ def range_image_ends(pose, elevations_deg, n_azimuth: int, max_range: float) -> 
 
 
 class _DefaultedConfig:
-    """what GridConfig, RouteConfig and SegmentConfig share, beside C.Structure: construction from the library's defaults (the
+    """what GridConfig, RouteConfig, FrontierConfig and SegmentConfig share, beside C.Structure: construction from the library's defaults (the
     function named by _default) with keyword arguments on top, update, copy, and check by the function named by _checker"""
     _default = _checker = None
 
@@ -1465,6 +1465,33 @@ def grid_cell_of(cfg: GridConfig, leaf: float, x: float, z: float):
     return (rx.value, rz.value) if inside.value else None
 
 
+class FrontierConfig(_DefaultedConfig, C.Structure):
+    """loamx_grid_frontier_config: which FREE cells of a navigation grid are frontier cells (min_unknown of the eight neighbours
+    UNKNOWN, clear2 >= min_clear2), how they join (connectivity 4 or 8) and which frontiers are kept (min_cells).  FrontierConfig()
+    holds the defaults (8, 1, 1, 1); keyword arguments replace them."""
+    _fields_ = [("connectivity", C.c_uint32), ("min_unknown", C.c_uint32), ("min_clear2", C.c_uint32), ("min_cells", C.c_uint32)]
+
+    _default, _checker = "loamx_grid_frontier_default_config", "loamx_grid_frontier_check"
+
+
+FRONTIER_NONE = 0xffffffff                                                        # label of a cell in no kept frontier; no best_cell
+# loamx_frontier, 64 bytes: min_cell (the smallest record index of its cells, its identity), cells, the inclusive box lo .. hi in
+# (rx, rz), the sums of rx and rz, unknown_links (the sum of unknown8), and from the field reachable, best_cost and best_cell
+FRONTIER = np.dtype([("min_cell", "<u4"), ("cells", "<u4"), ("lo", "<u4", 2), ("hi", "<u4", 2), ("sum_rx", "<u8"), ("sum_rz", "<u8"),
+                     ("unknown_links", "<u8"), ("reachable", "<u4"), ("best_cost", "<u4"), ("best_cell", "<u4"), ("reserved", "<u4")])
+FRONTIER_STATS = ("cells", "frontiers", "kept", "kept_cells", "kept_reachable", "hooks_lost")   # stats[6] of loamx_densemap_frontiers
+
+
+def frontiers_best(frontiers, min_cost=0) -> int:
+    """loamx_frontiers_best (host only): the index of the FRONTIER record with the smallest best_cost among those with
+    min_cost <= best_cost < ROUTE_UNREACHABLE, ties to the smaller index; FRONTIER_NONE when there is none"""
+    a = np.ascontiguousarray(frontiers, FRONTIER).reshape(-1)
+    best = C.c_uint32(0)
+    _check(lib().loamx_frontiers_best(a.ctypes.data_as(C.c_void_p) if len(a) else None, C.c_uint64(len(a)), C.c_uint32(min_cost),
+                                      C.byref(best)))
+    return int(best.value)
+
+
 SEGMENT_NONE = 0xffffffff                                                         # label of a voxel in no kept component
 SEGMENT_ALL, SEGMENT_STATIC, SEGMENT_DYNAMIC = range(3)                           # loamx_densemap_segment_config.which
 
@@ -1574,6 +1601,7 @@ class DenseMap:
         L.loamx_densemap_rehashes.restype = C.c_uint64
         L.loamx_densemap_route_active_rounds.restype = C.c_uint64
         self.route_stats = None
+        self.frontier_stats = None
         self._level = 0   # the level select_level chose (loamx_densemap_align_select_level)
         self._c = _cfg(DenseMapConfig, "loamx_densemap_default_config", leaf=leaf, min_range=min_range, max_range=max_range,
                        max_voxels=max_voxels, initial_slots=initial_slots, device=device)
@@ -2028,6 +2056,46 @@ class DenseMap:
     def route_set_batch(self, batch: int):
         """bench hook: the relaxation rounds launched per look at the counters (1..64)"""
         _check(lib().loamx_densemap_route_set_batch(self.h, C.c_uint32(batch)))
+
+    def _frontiers(self, fn, head, shape, cfg, route, start, labels, fields):
+        # (as segment(): a refusal by capacity leaves the needed count, and the call is made again with that room)
+        c = (FrontierConfig() if cfg is None else cfg).copy(**fields).check()
+        rc = (RouteConfig() if route is None else route).copy().check()
+        xz = None if start is None else _xz_pairs([start])
+        n_fr = C.c_uint64(256)
+        st = (C.c_uint64 * 6)()
+        while True:
+            lab = np.full(shape, FRONTIER_NONE, np.uint32) if labels else None
+            out = np.zeros(max(int(n_fr.value), 1), FRONTIER)
+            code = fn(self.h, *head, C.byref(rc), C.byref(c), xz.ctypes.data_as(C.c_void_p) if xz is not None else None,
+                      lab.ctypes.data_as(C.c_void_p) if labels else None, out.ctypes.data_as(C.c_void_p), C.c_uint64(int(n_fr.value)),
+                      C.byref(n_fr), st)
+            if code == E_CAPACITY:
+                continue
+            _check(code)
+            self.frontier_stats = dict(zip(FRONTIER_STATS, (int(v) for v in st)))
+            return lab, out[:int(n_fr.value)]
+
+    def frontiers(self, cfg=None, grid=None, static=None, route=None, start=None, labels=True, **fields):
+        """loamx_densemap_frontiers: the navigation grid of a window (grid: a GridConfig, None: the defaults; static: a StaticRule)
+        and, on it where it lies on the device, its frontiers: the FREE cells that touch UNKNOWN ones, grouped under cfg (a
+        FrontierConfig, None: the defaults; fields replace members of a copy of it).  start = (rx, rz), the vehicle's cell: the call
+        routes towards it under route (a RouteConfig, None: the defaults), every frontier gets reachable, best_cost and best_cell,
+        and the field stays on the device, so that route_trace([best_cell's (rx, rz)], ...) walks from the frontier to the vehicle.
+        start None: nothing is routed and the handle's field is left alone.  Returns (labels, frontiers): an (nz, nx) uint32 array,
+        the number of each cell's frontier or FRONTIER_NONE (None with labels=False), and the kept frontiers as FRONTIER records in
+        ascending min_cell.  The six stats of the call are left in frontier_stats.  Blocks; the map is only read."""
+        g = (GridConfig() if grid is None else grid).copy().check()
+        head = (C.byref(g), C.byref(static) if static is not None else None)
+        return self._frontiers(lib().loamx_densemap_frontiers, head, (g.nz, g.nx), cfg, route, start, labels, fields)
+
+    def frontiers_cells(self, cells, cfg=None, route=None, start=None, labels=True, **fields):
+        """loamx_densemap_frontiers_cells: the same on an (nz, nx) array of GRID_CELL records of the caller's, uploaded as
+        route_cells() uploads"""
+        a = _grid_cells(cells)
+        assert a.ndim == 2, "cells must be an (nz, nx) array"
+        head = (a.ctypes.data_as(C.c_void_p), C.c_uint32(a.shape[1]), C.c_uint32(a.shape[0]))
+        return self._frontiers(lib().loamx_densemap_frontiers_cells, head, a.shape, cfg, route, start, labels, fields)
 
     def segment(self, cfg=None, static=None, labels=True, **fields):
         """loamx_densemap_segment: the connected components of the selected voxels, labelled on the device.  cfg: a SegmentConfig
