@@ -1173,7 +1173,7 @@ int loamx_densemap_raycast_from_pipeline(loamx_densemap* h, loamx_pipeline* p, u
 /* Sweep log and rebuild (optional: a handle that never calls loamx_densemap_enable_history runs the kernels it ran, allocates what
  * it allocated and exports the same bytes).  The map keeps sums per voxel, not sweeps; with history on it also keeps every added
  * cloud in device memory, and loamx_densemap_rebuild replays that log under one rigid correction per logged call into a fresh
- * table: after a loop closure (loamx_place -> loamx_densemap_align_many -> the host's pose graph) the map is made consistent with
+ * table: after a loop closure (loamx_place -> loamx_densemap_align_many -> loamx_posegraph_optimize) the map is made consistent with
  * the corrected poses without a point crossing PCIe.
  *
  * The log.  loamx_densemap_enable_history is allowed only on an empty map (a fresh handle, or right after reset; otherwise
@@ -1195,7 +1195,7 @@ int loamx_densemap_raycast_from_pipeline(loamx_densemap* h, loamx_pipeline* p, u
  * call beyond the log or a handle without history.
  *
  * The correction.  A correction is a row-major 3x4 matrix R | t from the map frame to the map frame, x -> R x + t; for logged call k
- * the host computes it in double as P_k(now) * P_k(when added)^-1.  Its 12 doubles must be finite; nothing else is checked (the host
+ * the host computes it in double as P_k(now) * P_k(when added)^-1 (loamx_posegraph_corrections).  Its 12 doubles must be finite; nothing else is checked (the host
  * answers for R being a rotation).  It is rounded to f32 once, entry by entry, and applied per point in f32, no fused multiply-add,
  * in this order:  p'_a = ((R_a0*x + R_a1*y) + R_a2*z) + t_a;  w is untouched.  The call's origin goes through the same expression.
  * A correction whose 12 rounded entries compare equal (==) to the identity's is the identity: that call is replayed from its logged
@@ -1718,7 +1718,8 @@ int loamx_densemap_page(loamx_densemap* h, const loamx_densemap_page_config* cfg
 /* ------------------------------------------------------------------------------------------------------------
  * Place recognition (not in the reference): a database of rotation-invariant sweep descriptors in device memory (Scan Context: a
  * ring x sector polar grid of maximum heights around the sensor) and an exhaustive search for the earlier entries that look like a
- * query, with the yaw between the two.  Detection only: what is done with a match (a pose graph, a correction) is the host's.
+ * query, with the yaw between the two.  Detection only: a match becomes a constraint in loamx_densemap_align_many and an edge of
+ * loamx_posegraph (below).
  *
  * Descriptor of a cloud about an origin o (LOAM frame: x left, y up, z forward), everything per point in f32, no fused multiply-add:
  *   d = p - o per component;  a = d.z, b = d.x;  r2 = a*a + b*b;  h = d.y + height_offset.
@@ -1796,6 +1797,100 @@ int loamx_place_get_descriptor(loamx_place* h, uint32_t id, float* desc, float* 
  * file's (LOAMX_E_INVALID otherwise, handle unchanged); the loaded handle answers every query with the same bytes */
 int loamx_place_save(loamx_place* h, const char* path);
 int loamx_place_load(loamx_place* h, const char* path);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Pose graph (not in the reference, which never closes a loop): the run's poses optimised on the device, the link between
+ * loamx_densemap_align_many / align_pyramid (a 6-DOF constraint between two sweeps) and loamx_densemap_rebuild (one rigid correction
+ * per sweep).  All arithmetic is FP64, no fused multiply-add; every sum has one fixed order, so a run is reproducible to the bit.
+ *
+ * Poses are double[12], a row-major 3x4 matrix (R | t) mapping node frame to map frame: the layout of
+ * loamx_densemap_align_result.pose and of rebuild's corrections.
+ * Edge (i, j, Z, Omega): Z = (R_z, t_z) is the measured T_i^-1 T_j; Omega is a symmetric 6x6 information matrix given as its 21
+ * upper-triangle entries, row-major.
+ * Residual: with A = T_i^-1 T_j = (R_A, t_A) and E = Z^-1 A = (R_E, t_E):
+ *   R_A = R_i^T R_j,  t_A = R_i^T (t_j - t_i);   R_E = R_z^T R_A,  t_E = R_z^T (t_A - t_z);
+ *   r = [t_E ; Log(R_E)]: translation first, then the rotation vector of angle in [0, pi].
+ *   Log(R): v = the vector of (R - R^T) / 2, c = (trace R - 1) / 2, angle = atan2(|v|, c), Log = v * angle / |v|, and v itself below
+ *   1e-8 rad.  Exp(w) = I + a [w]x + b [w]x^2 with a = sin|w| / |w|, b = (1 - cos|w|) / |w|^2, and a = 1, b = 1/2 below 1e-8 rad.
+ *   The series branches are part of the definition.  The caller keeps |Log(R_E)| <= pi - 1e-6.
+ * Cost: chi2_e = r^T Omega r;  F = sum_e rho_e(chi2_e);  rho(s) = s for plain edges; for edges flagged LOAMX_PG_EDGE_ROBUST with
+ *   huber_delta > 0: rho(s) = s if s <= delta^2, else 2 delta sqrt(s) - delta^2.  The solver treats this as IRLS, with the weight
+ *   w_e = min(1, delta / sqrt(chi2)) evaluated at the linearisation point.
+ * Retraction: delta_k = (v, w):  t_k <- t_k + R_k v,  R_k <- R_k Exp(w).  A free node's rotation is then made orthonormal again by
+ *   Gram-Schmidt on its columns (c0 normalised; c1 minus its part along c0, normalised; c2 = c0 x c1).  Fixed nodes are never written:
+ *   get_poses returns them byte for byte as they were given.
+ * Jacobians of r at delta = 0, with phi = Log(R_E) and Q = Jr^-1(phi) = I + 1/2 [phi]x + (1/|phi|^2 - (1 + cos|phi|) / (2 |phi|
+ *   sin|phi|)) [phi]x^2 (coefficient 1/12 below 1e-8 rad); rows t, phi; columns v, w:
+ *   J_j = [[R_E, 0], [0, Q]],   J_i = [[-R_z^T, R_z^T [t_A]x], [0, -Q R_A^T]].
+ * Gauge: nodes carry a `fixed` flag, and every connected component of the graph must contain a fixed node; an isolated node must
+ *   itself be fixed.
+ * One step solves (H + lambda D) delta = -g over the free nodes, H = sum_e w_e J^T Omega J, g = sum_e w_e J^T Omega r, D the 6x6
+ *   block diagonal of H, by conjugate gradients preconditioned with the inverse of (1 + lambda) D per node (6x6 Cholesky; a node with a
+ *   pivot that is not positive gets a zero step).  CG ends at the first k with r_k.z_k <= cg_tolerance^2 r_0.z_0 or at
+ *   max_cg_iterations; the stop is found on the device, so the result does not depend on cg_batch.
+ * Levenberg-Marquardt: a step is accepted iff it lowers F (then lambda <- lambda / 10); a rejected step restores the poses and raises
+ *   lambda tenfold (to 1e-6 from 0), up to a cap of 1e12 (status 2).  Converged (status 0): an accepted step with max |delta| <= eps_step
+ *   or one that lowered F by <= eps_cost * F; also a rejected step with max |delta| <= eps_step (at the minimum rounding alone decides
+ *   whether F falls).  max_iterations counts every step tried.
+ *
+ * Refused with LOAMX_E_INVALID, a message that names the argument, and nothing changed: a NULL where it is not allowed; an id beyond
+ * the nodes; i == j; a non-finite entry; a rotation with max |R^T R - I| > 1e-6 or a determinant that is not positive; an info with a
+ * negative diagonal entry; optimize / linearise on a graph that fails the gauge check.  LOAMX_E_CAPACITY, handle unchanged: an
+ * allocation for growth failed (rooms double).
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct loamx_posegraph loamx_posegraph;
+typedef struct loamx_posegraph_config {
+  uint32_t max_iterations;      /* LM steps tried, 0..10000 (default 50); 0: optimize changes nothing */
+  uint32_t max_cg_iterations;   /* per step, 1..100000 (default 500) */
+  uint32_t cg_batch;            /* CG iterations enqueued per host look, 1..64 (default 16) */
+  uint32_t initial_nodes, initial_edges;   /* room at creation, 1..2^26 (defaults 1024, 2048); both grow by doubling */
+  double cg_tolerance;          /* (0, 1): CG ends at the first k with r_k.z_k <= tol^2 * r_0.z_0 (default 1e-8) */
+  double eps_step;              /* > 0: converged when an accepted step has max |delta| <= eps_step (default 1e-9) */
+  double eps_cost;              /* >= 0: ... or lowered F by <= eps_cost * F (default 1e-12) */
+  double lambda_init;           /* >= 0 (default 1e-6) */
+  double huber_delta;           /* >= 0; 0: ROBUST flags are ignored (default 0) */
+  int device;
+} loamx_posegraph_config;
+#define LOAMX_PG_EDGE_ROBUST 1u
+typedef struct loamx_posegraph_edge {   /* 280 bytes */
+  uint32_t i, j, flags, reserved;
+  double z[12];
+  double info[21];
+} loamx_posegraph_edge;
+typedef struct loamx_posegraph_result {
+  uint32_t iterations, accepted, cg_iterations, looks;
+  int status;                   /* 0 converged, 1 max_iterations, 2 lambda reached its cap without an accepted step */
+  double cost_initial, cost_final, last_step, lambda_final;
+} loamx_posegraph_result;
+
+/* host only, no device needed */
+void loamx_posegraph_default_config(loamx_posegraph_config* cfg);
+int loamx_posegraph_check(const loamx_posegraph_config* cfg);   /* names the first field out of its bounds */
+int loamx_posegraph_between(const double Ti[12], const double Tj[12], double z[12]);   /* z = Ti^-1 Tj: the odometry edge of two sweeps */
+int loamx_posegraph_residual(const double Ti[12], const double Tj[12], const double z[12], double r[6]);
+/* Omega = diag(1 / sigma_t^2 three times, 1 / sigma_r^2 three times); both sigmas > 0 */
+int loamx_posegraph_info_diagonal(double sigma_t, double sigma_r, double info[21]);
+/* LOAMX_E_INVALID and *bad_node = the smallest node id of a component without a fixed node (only i and j of the edges are read) */
+int loamx_posegraph_check_gauge(uint32_t n_nodes, const uint8_t* fixed, const loamx_posegraph_edge* edges, uint64_t n_edges, uint32_t* bad_node);
+/* out_k = after_k * before_k^-1 for n poses: the corrections[12 * n] that loamx_densemap_rebuild takes */
+int loamx_posegraph_corrections(const double* before, const double* after, uint32_t n, double* out);
+
+loamx_posegraph* loamx_posegraph_create(const loamx_posegraph_config* cfg);   /* NULL: the defaults */
+void loamx_posegraph_destroy(loamx_posegraph* h);
+int loamx_posegraph_reset(loamx_posegraph* h);                                /* no nodes, no edges; the rooms and the statistics stay */
+/* n new free nodes with ids *first_id (may be NULL) .. *first_id + n - 1 */
+int loamx_posegraph_add_nodes(loamx_posegraph* h, const double* poses, uint32_t n, uint32_t* first_id);
+int loamx_posegraph_set_fixed(loamx_posegraph* h, uint32_t id, int fixed);
+int loamx_posegraph_set_poses(loamx_posegraph* h, uint32_t first, uint32_t n, const double* poses);
+int loamx_posegraph_get_poses(loamx_posegraph* h, uint32_t first, uint32_t n, double* poses);
+int loamx_posegraph_add_edges(loamx_posegraph* h, const loamx_posegraph_edge* edges, uint64_t n);
+int loamx_posegraph_size(loamx_posegraph* h, uint32_t* nodes, uint64_t* edges);
+/* the probe: the linearisation at the current poses with the weights of lambda = 0.  chi2[n_edges], grad[6 * n_nodes] (g per node),
+ * diag[36 * n_nodes] (the node's block of H, row-major), *cost = F; each may be NULL.  Fixed nodes get zeros in grad and diag */
+int loamx_posegraph_linearise(loamx_posegraph* h, double* chi2, double* grad, double* diag, double* cost);
+int loamx_posegraph_optimize(loamx_posegraph* h, loamx_posegraph_result* result);   /* result may be NULL */
+/* launches, looks (host round trips), CG iterations, linearisations since the handle's creation; never cleared */
+int loamx_posegraph_get_stats(loamx_posegraph* h, uint64_t stats[4]);
 
 #ifdef __cplusplus
 }

@@ -2403,6 +2403,183 @@ class PlaceDB:
         return int(lib().loamx_place_growths(self.h))
 
 
+class PoseGraphConfig(_DefaultedConfig, C.Structure):
+    """loamx_posegraph_config.  PoseGraphConfig() holds the defaults (50 LM steps, 500 CG iterations per step in batches of 16, room for
+    1024 nodes and 2048 edges, cg_tolerance 1e-8, eps_step 1e-9, eps_cost 1e-12, lambda_init 1e-6, huber_delta 0); keyword arguments
+    replace them."""
+    _fields_ = [("max_iterations", C.c_uint32), ("max_cg_iterations", C.c_uint32), ("cg_batch", C.c_uint32), ("initial_nodes", C.c_uint32),
+                ("initial_edges", C.c_uint32), ("cg_tolerance", C.c_double), ("eps_step", C.c_double), ("eps_cost", C.c_double),
+                ("lambda_init", C.c_double), ("huber_delta", C.c_double), ("device", C.c_int)]
+
+    _default, _checker = "loamx_posegraph_default_config", "loamx_posegraph_check"
+
+
+class PoseGraphEdge(C.Structure):
+    _fields_ = [("i", C.c_uint32), ("j", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32), ("z", C.c_double * 12),
+                ("info", C.c_double * 21)]
+
+
+class PoseGraphResult(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("accepted", C.c_uint32), ("cg_iterations", C.c_uint32), ("looks", C.c_uint32),
+                ("status", C.c_int), ("cost_initial", C.c_double), ("cost_final", C.c_double), ("last_step", C.c_double),
+                ("lambda_final", C.c_double)]
+
+
+PG_EDGE_ROBUST = 1                                                               # LOAMX_PG_EDGE_ROBUST
+POSEGRAPH_EDGE = np.dtype([("i", "<u4"), ("j", "<u4"), ("flags", "<u4"), ("reserved", "<u4"), ("z", "<f8", 12), ("info", "<f8", 21)])
+POSEGRAPH_STATS = ("launches", "looks", "cg_iterations", "linearisations")      # stats[4] of loamx_posegraph_get_stats
+POSEGRAPH_STATUS = ("converged", "max_iterations", "lambda_cap")                 # loamx_posegraph_result.status
+
+
+def _poses12(poses) -> np.ndarray:
+    """(N, 12) float64 from (N, 12), (N, 3, 4) or (N, 4, 4); a single pose becomes N = 1"""
+    a = np.asarray(poses, np.float64)
+    if a.ndim == 1 or (a.ndim == 2 and a.shape[-1] == 4):
+        a = a[None]
+    if a.ndim == 3:
+        a = a[:, :3, :4].reshape(len(a), 12)
+    assert a.ndim == 2 and a.shape[1] == 12, "poses must be (N, 12), (N, 3, 4) or (N, 4, 4)"
+    return np.ascontiguousarray(a)
+
+
+def posegraph_edges(i, j, z, info, flags=0) -> np.ndarray:
+    """POSEGRAPH_EDGE records from arrays: i, j (M,), z (M, 12) / (M, 3, 4) / (M, 4, 4), info (M, 21) or one (21,) for all"""
+    i = np.atleast_1d(np.asarray(i, np.uint32))
+    e = np.zeros(len(i), POSEGRAPH_EDGE)
+    e["i"], e["j"], e["flags"] = i, np.asarray(j, np.uint32), flags
+    e["z"] = _poses12(z)
+    e["info"] = np.asarray(info, np.float64)
+    return e
+
+
+def posegraph_between(Ti, Tj) -> np.ndarray:
+    """loamx_posegraph_between (host only): z = Ti^-1 Tj as (12,) float64, the odometry edge between two registered sweeps"""
+    a, b, z = _poses12(Ti), _poses12(Tj), np.zeros(12)
+    _check(lib().loamx_posegraph_between(a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), z.ctypes.data_as(C.c_void_p)))
+    return z
+
+
+def posegraph_residual(Ti, Tj, z) -> np.ndarray:
+    """loamx_posegraph_residual (host only): r = [t_E ; Log(R_E)] of the edge z between the poses Ti and Tj, (6,) float64"""
+    a, b, m, r = _poses12(Ti), _poses12(Tj), _poses12(z), np.zeros(6)
+    _check(lib().loamx_posegraph_residual(a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p),
+                                          r.ctypes.data_as(C.c_void_p)))
+    return r
+
+
+def posegraph_info_diagonal(sigma_t: float, sigma_r: float) -> np.ndarray:
+    """loamx_posegraph_info_diagonal (host only): the 21 upper-triangle entries of diag(1 / sigma_t^2 x 3, 1 / sigma_r^2 x 3)"""
+    info = np.zeros(21)
+    _check(lib().loamx_posegraph_info_diagonal(C.c_double(sigma_t), C.c_double(sigma_r), info.ctypes.data_as(C.c_void_p)))
+    return info
+
+
+def posegraph_check_gauge(fixed, edges):
+    """loamx_posegraph_check_gauge (host only): None when every connected component has a fixed node, else the smallest node id of a
+    component without one.  fixed: (N,) flags; edges: POSEGRAPH_EDGE records (only i and j are read)"""
+    f = np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8)
+    e = np.ascontiguousarray(edges, POSEGRAPH_EDGE)
+    bad = C.c_uint32(0)
+    L = lib()
+    rc = L.loamx_posegraph_check_gauge(C.c_uint32(len(f)), f.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), C.c_uint64(len(e)),
+                                       C.byref(bad))
+    if rc == OK:
+        return None
+    if "gauge" not in L.loamx_last_error().decode():
+        _check(rc)
+    return int(bad.value)
+
+
+def posegraph_corrections(before, after) -> np.ndarray:
+    """loamx_posegraph_corrections (host only): C_k = after_k * before_k^-1 as (N, 12) float64, what DenseMap.rebuild takes"""
+    b, a = _poses12(before), _poses12(after)
+    assert a.shape == b.shape
+    out = np.zeros_like(a)
+    _check(lib().loamx_posegraph_corrections(b.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), C.c_uint32(len(a)),
+                                             out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+class PoseGraph:
+    """loamx_posegraph_*: SE(3) poses (double[12], row-major 3x4) and relative-pose edges in device memory, optimised there by
+    Levenberg-Marquardt with a block-Jacobi PCG (include/loamx.h has every definition).  config: a PoseGraphConfig, or keyword
+    arguments on top of the defaults."""
+
+    def __init__(self, config: PoseGraphConfig = None, **fields):
+        L = lib()
+        L.loamx_posegraph_create.restype = C.c_void_p
+        L.loamx_posegraph_bad_pivots.restype = C.c_uint32
+        self.config = (config.copy(**fields) if config is not None else PoseGraphConfig(**fields))
+        self.h = C.c_void_p(L.loamx_posegraph_create(C.byref(self.config)))
+        if not self.h:
+            raise LoamxError(E_INVALID, L.loamx_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().loamx_posegraph_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def reset(self):
+        _check(lib().loamx_posegraph_reset(self.h))
+
+    @property
+    def size(self):
+        """(nodes, edges)"""
+        n, e = C.c_uint32(0), C.c_uint64(0)
+        _check(lib().loamx_posegraph_size(self.h, C.byref(n), C.byref(e)))
+        return int(n.value), int(e.value)
+
+    def add_nodes(self, poses) -> int:
+        """new free nodes with these poses; returns the id of the first"""
+        a = _poses12(poses)
+        first = C.c_uint32(0)
+        _check(lib().loamx_posegraph_add_nodes(self.h, a.ctypes.data_as(C.c_void_p), C.c_uint32(len(a)), C.byref(first)))
+        return int(first.value)
+
+    def set_fixed(self, node: int, fixed=True):
+        _check(lib().loamx_posegraph_set_fixed(self.h, C.c_uint32(node), C.c_int(1 if fixed else 0)))
+
+    def set_poses(self, first: int, poses):
+        a = _poses12(poses)
+        _check(lib().loamx_posegraph_set_poses(self.h, C.c_uint32(first), C.c_uint32(len(a)), a.ctypes.data_as(C.c_void_p)))
+
+    def poses(self, first=0, n=None) -> np.ndarray:
+        """(n, 12) float64: the poses of the nodes first .. first + n - 1 (n None: to the last node)"""
+        if n is None:
+            n = self.size[0] - first
+        out = np.zeros((max(int(n), 0), 12))
+        _check(lib().loamx_posegraph_get_poses(self.h, C.c_uint32(first), C.c_uint32(n), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def add_edges(self, edges):
+        """POSEGRAPH_EDGE records (posegraph_edges builds them from arrays)"""
+        e = np.ascontiguousarray(edges, POSEGRAPH_EDGE)
+        _check(lib().loamx_posegraph_add_edges(self.h, e.ctypes.data_as(C.c_void_p), C.c_uint64(len(e))))
+
+    def linearise(self) -> dict:
+        """the probe: chi2 (E,), grad (N, 6), diag (N, 6, 6) and cost at the current poses, weights at lambda = 0"""
+        n, m = self.size
+        chi2, grad, diag, cost = np.zeros(m), np.zeros((n, 6)), np.zeros((n, 6, 6)), C.c_double(0.0)
+        _check(lib().loamx_posegraph_linearise(self.h, chi2.ctypes.data_as(C.c_void_p), grad.ctypes.data_as(C.c_void_p),
+                                               diag.ctypes.data_as(C.c_void_p), C.byref(cost)))
+        return dict(chi2=chi2, grad=grad, diag=diag, cost=float(cost.value))
+
+    def optimize(self) -> dict:
+        """loamx_posegraph_optimize: the result record as a dict (status 0 converged, 1 max_iterations, 2 lambda at its cap)"""
+        r = PoseGraphResult()
+        _check(lib().loamx_posegraph_optimize(self.h, C.byref(r)))
+        out = {f: getattr(r, f) for f, _ in PoseGraphResult._fields_}
+        out["bad_pivots"] = int(lib().loamx_posegraph_bad_pivots(self.h))
+        return out
+
+    def stats(self) -> dict:
+        s = (C.c_uint64 * 4)()
+        _check(lib().loamx_posegraph_get_stats(self.h, s))
+        return dict(zip(POSEGRAPH_STATS, (int(v) for v in s)))
+
+
 def dist_shard_of(rank: int, world: int, batch: int):
     b, e = C.c_uint32(0), C.c_uint32(0)
     _check(lib().loamx_dist_shard_of(rank, world, batch, C.byref(b), C.byref(e)))
