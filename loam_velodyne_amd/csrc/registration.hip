@@ -931,11 +931,13 @@ void Registrar::enqueue_full(int mode) {
                      stats_.p, full_done_.p, mode, full_tag_, skip, vb_.epoch());
 }
 
-// k_pose_init + stack round trip + voxel grid of the stack clouds
+// sweep set-up (k_pose_init; on the bucketed path k_vb_plan does it) + stack round trip + voxel grid of the stack clouds
 void Registrar::enqueue_front(bool legacy) {
   const uint32_t ns = n_sweeps_, nseg = 2 * ns, n = n_in_;
-  hipLaunchKernelGGL(k_pose_init, dim3((ns + 63) / 64), dim3(64), 0, st_, d_guess_, ns, poses_.p, stats_.p, vox_.seg_minmax(), arrive_.p,
-                     full_done_.p);
+  // the bucketed stage's plan sets the sweeps up itself (VbPoseInit): one launch less in front of every registration
+  if (legacy || n == 0)
+    hipLaunchKernelGGL(k_pose_init, dim3((ns + 63) / 64), dim3(64), 0, st_, d_guess_, ns, poses_.p, stats_.p, vox_.seg_minmax(), arrive_.p,
+                       full_done_.p);
   if (n == 0) {
     LX_HIP(hipMemsetAsync(ds_off_.p, 0, sizeof(uint32_t) * (nseg + 1), st_));
     return;
@@ -946,8 +948,12 @@ void Registrar::enqueue_front(bool legacy) {
                        1.0f / params.surf_leaf, stack_.p, vox_.ijk(), vox_.seg_minmax());
     vox_.sort_reduce(stack_.p, nullptr, n, d_seg_off_, nseg, ds_pts_.p, ds_off_.p);
   } else {
+    static_assert(sizeof(SweepStats) == 8 * sizeof(int), "VbPoseInit::stats clears eight words per sweep");
+    VbPoseInit init;
+    init.guess = d_guess_; init.poses = poses_.p; init.stats = reinterpret_cast<int*>(stats_.p); init.seg_minmax = vox_.seg_minmax();
+    init.ticket = arrive_.p; init.full_done = full_done_.p; init.ns = ns;
     vb_.run(in_.p, d_src_, n, d_seg_off_, h_seg_off_.data(), nseg, poses_.p, 1.0f / params.corner_leaf, 1.0f / params.surf_leaf, stack_.p,
-            ds_pts_.p, ds_off_.p);
+            ds_pts_.p, ds_off_.p, &init);
   }
 }
 

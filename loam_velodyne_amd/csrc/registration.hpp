@@ -132,7 +132,7 @@ class Registrar {
   VoxBucket vb_;
   bool vb_disabled_ = false;   // LOAMX_VOX_LEGACY
   bool jacobi_eig_ = false;    // LOAMX_EIG_JACOBI: the edge fit's eigen-decomposition by the oracle's Jacobi iteration instead of the closed form
-  void enqueue_front(bool legacy);   // k_pose_init + stack round trip + voxel grid
+  void enqueue_front(bool legacy);   // sweep set-up (k_pose_init, or inside k_vb_plan) + stack round trip + voxel grid
   void enqueue_full(int mode);       // transformFullResToMap
   void redo_if_bucket_path_failed(); // after a stream sync
   uint32_t n_in_ = 0, n_full_ = 0, max_q_per_sweep_ = 0;
