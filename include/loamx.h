@@ -1483,6 +1483,83 @@ int loamx_densemap_frontiers_cells(loamx_densemap* h, const loamx_grid_cell* cel
                                    uint64_t capacity, uint64_t* n_frontiers, uint64_t stats[6]);
 int loamx_frontiers_best(const loamx_frontier* f, uint64_t n, uint32_t min_cost, uint32_t* best);   /* host only, no device */
 
+/* Distance field (optional: a handle that never calls loamx_densemap_dist runs the kernels it ran, allocates what it allocated and
+ * exports the same bytes).  "How far is the nearest surface from here, and where is it?": for every cell of a 3-D window of the
+ * map the exact squared Euclidean distance, in cells, to the nearest occupied cell of the window, and which cell that is, computed
+ * on the device from the table where it lies; then points are looked up in the field where it lies.  Every word is an integer with
+ * one value: the field depends on neither the thread schedule, the order of the points, the split into add calls (without a rule)
+ * nor the table's size or the number of rehashes.
+ *
+ * A cell is a cube of k = cell_leaves voxels on a side: voxel (ix, iy, iz) lies in cell (cx, cy, cz) = (floor(ix / k),
+ * floor(iy / k), floor(iz / k)) — floor, not truncation: ix = -1, k = 3 gives cx = -1.  The window is the nx * ny * nz cells
+ * cx in [x0, x0 + nx), cy in [y0, y0 + ny), cz in [z0, z0 + nz); with (rx, ry, rz) = (cx - x0, cy - y0, cz - z0), cell
+ * (cx, cy, cz) is record (rz * ny + ry) * nx + rx.  A voxel qualifies when it lies in the window, holds n >= min_points points
+ * and, with a rule, is not dynamic under it (the rule of the carving section, on the voxel's n and miss:
+ * loamx_densemap_rule_is_dynamic).  A cell is occupied when it holds at least one qualifying voxel.
+ * Per cell, with R = d_max and D = the smallest dx*dx + dy*dy + dz*dz (in cells) to an occupied cell of the window:
+ *   d2   = (uint16_t) D when D <= R*R, else (R+1)*(R+1) ("capped"; also when the window has no occupied cell).  An occupied cell
+ *          has 0.  Cells outside the window are not obstacles.  With R = 0 this is 0 on occupied cells and 1 elsewhere, with no
+ *          special case.
+ *   near = (uint32_t) rx' | ry' << 10 | rz' << 20 of an occupied cell at that distance: among the occupied cells of the window with
+ *          dx*dx + dy*dy + dz*dz == D, the one with the smallest (rz', ry', rx') in lexicographic order.  An occupied cell names
+ *          itself.  LOAMX_DIST_NONE when d2 is capped.
+ * The distance is between cells, that is between cell centres: two points in cells D apart (d_a per axis) are at least
+ * e * sqrt(sum over the axes of max(|d_a| - 1, 0)^2) apart, e = leaf * k; a body of radius r is clear of every occupied cell when
+ * d2 >= (r / e + sqrt(3))^2.
+ * loamx_densemap_dist: waits for the adds as download does, runs one memset and three kernels on the map's own stream (mark: one bit
+ * per occupied cell; the x and y passes in one; the z pass, which writes d2, near and the counts) and blocks.  The planes wanted
+ * come back through pinned memory; with out_d2 and out_near NULL only the four stats words cross.  Either way the field stays on
+ * the device for loamx_densemap_dist_query until the next loamx_densemap_dist, loamx_densemap_reset or destroy: it shows the map as
+ * it was at the call.  It changes nothing in the map.  The device buffers, 10 1/8 bytes per cell (0.68 GB at 2^26 cells), live in
+ * the handle, grow to the largest window asked for and are freed on destroy.  An empty map is valid: every cell is capped.
+ * stats: [0] qualifying voxels inside the window, [1] occupied cells, [2] cells with d2 <= R*R, [3] the largest d2 <= R*R, 0 when
+ * there is none.
+ * LOAMX_E_INVALID, with a message that names the argument, nothing written, the field of an earlier call kept: NULL h or stats;  a
+ * configuration that fails loamx_densemap_dist_check;  a rule with den == 0;  a rule on a handle without carving.
+ * loamx_densemap_dist_query: per point the two words of its cell.  A point's voxel is the one loamx_densemap_add puts it in,
+ * i_a = (int)floorf(p_a * inv) per axis with inv = 1.0f / leaf in f32, under the key rule |floorf(p_a * inv)| < 2^20 on every axis,
+ * without the range filter; its cell is the floor division above.  A point that fails the key rule (a NaN or an infinite
+ * component fails it) or whose cell lies outside the window gets d2 = LOAMX_DIST_OUTSIDE and near = LOAMX_DIST_NONE.
+ * stats: [0] points inside, [1] points outside, [2] inside and capped, [3] inside with d2 < min_d2, [4] (the smallest d2 of a point
+ * inside) << 32 | the smallest index of a point with it, UINT64_MAX when no point is inside.  out NULL: the stats alone.  Runs on
+ * the map's own stream and blocks; the map and the field are only read.  An empty cloud is LOAMX_OK with zero counts.
+ * LOAMX_E_INVALID, nothing written: NULL h, points or stats;  a cloud descriptor that the adds refuse;  no field (no
+ * loamx_densemap_dist yet, or a reset since).  LOAMX_E_CAPACITY, nothing written: out given and capacity < points->count.
+ *
+ * loamx_densemap_dist_check (host only): LOAMX_OK, or LOAMX_E_INVALID with a message that names the first field out of its bounds,
+ * in the order cell_leaves, x0, y0, z0, nx, ny, nz, nx * ny * nz, min_points, d_max.
+ * loamx_densemap_dist_window (host only): x0, nx, y0, ny, z0, nz of the window about centre[3] with half_extent[3], both in metres,
+ * for cfg->cell_leaves; per axis, in double, e = (double)leaf * k, lo = floor(((double)c - (double)h) / e),
+ * hi = floor(((double)c + (double)h) / e), first = lo, count = hi - lo + 1.  LOAMX_E_INVALID, cfg unchanged, when an argument is
+ * NULL or not finite, leaf <= 0, a half extent < 0 or the result breaks a bound of loamx_densemap_dist_check.
+ * loamx_dist_near_unpack (host only): rx = near & 1023, ry = near >> 10 & 1023, rz = near >> 20.  LOAMX_E_INVALID, nothing written,
+ * for LOAMX_DIST_NONE, a word with a bit above the three fields, or a NULL pointer.
+ * loamx_dist_metres (host only): sqrt((double)d2) * (double)leaf * (double)cell_leaves, the distance between the cell centres. */
+#define LOAMX_DIST_NONE 0xFFFFFFFFu
+#define LOAMX_DIST_OUTSIDE 0xFFFFFFFFu
+typedef struct loamx_densemap_dist_config {
+  uint32_t cell_leaves;    /* k, 1..64 (default 2) */
+  int32_t  x0, y0, z0;     /* first cell of the window, |x0|, |y0|, |z0| <= 2^21 (default 0, 0, 0) */
+  uint32_t nx, ny, nz;     /* 1..1024 each (near packs 10 bits per axis), nx * ny * nz <= 2^26 (default 128, 32, 128) */
+  uint32_t min_points;     /* a voxel qualifies when n >= min_points, >= 1 (default 2) */
+  uint32_t d_max;          /* R, cells, 0..254: (R+1)^2 = 65025 fits the 16 bits of d2 (default 16) */
+} loamx_densemap_dist_config;
+typedef struct loamx_dist_sample {   /* 8 bytes */
+  uint32_t d2;     /* the cell's d2; LOAMX_DIST_OUTSIDE: the point has no cell in the window */
+  uint32_t near;   /* the cell's near; LOAMX_DIST_NONE: capped, or outside */
+} loamx_dist_sample;
+void loamx_densemap_dist_default_config(loamx_densemap_dist_config* cfg);   /* host only */
+int loamx_densemap_dist_check(const loamx_densemap_dist_config* cfg);        /* host only */
+int loamx_densemap_dist_window(float leaf, const float centre[3], const float half_extent[3], loamx_densemap_dist_config* cfg);   /* host only */
+int loamx_densemap_dist(loamx_densemap* h, const loamx_densemap_dist_config* cfg /* NULL: the defaults */,
+                        const loamx_densemap_static_rule* rule /* NULL: every voxel; else needs carving */,
+                        uint16_t* out_d2 /* nx * ny * nz; NULL: not wanted */, uint32_t* out_near /* nx * ny * nz; NULL: not wanted */,
+                        uint64_t stats[4]);
+int loamx_densemap_dist_query(loamx_densemap* h, const loamx_cloud* points, uint32_t min_d2, loamx_dist_sample* out /* NULL: stats only */,
+                              uint64_t capacity, uint64_t stats[5]);
+int loamx_dist_near_unpack(uint32_t near, uint32_t* rx, uint32_t* ry, uint32_t* rz);   /* host only */
+double loamx_dist_metres(uint32_t d2, float leaf, uint32_t cell_leaves);               /* host only */
+
 /* Objects: connected components of the voxel map (optional: a handle that never segments runs the kernels it ran and allocates what
  * it allocated).  "Which voxels belong together?": on the voxel lattice, Euclidean clustering with a tolerance of one leaf is
  * connected-component labelling of the selected voxels, done on the device where the table lies; a component list and one word

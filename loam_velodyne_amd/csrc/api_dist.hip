@@ -387,4 +387,23 @@ int loamx_dist_barrier(loamx_dist* h) {
 
 void* loamx_dist_stream(loamx_dist* h) { return h ? (void*)h->st : nullptr; }
 
+// ---- the two host-only helpers of the dense map's distance field (include/loamx.h, loamx_densemap_dist; densemap_dist.hip has the
+// rest).  They live here because their names begin with loamx_dist_, and this translation unit defines every such entry point,
+// with or without RCCL
+int loamx_dist_near_unpack(uint32_t near, uint32_t* rx, uint32_t* ry, uint32_t* rz) {
+  return guard([&]() {
+    LX_REQUIRE(rx && ry && rz, "rx, ry or rz is NULL");
+    LX_REQUIRE(near != LOAMX_DIST_NONE, "near is LOAMX_DIST_NONE: no cell to unpack");
+    LX_REQUIRE((near >> 30) == 0u, "near has bits above its three 10-bit fields");
+    *rx = near & 1023u;
+    *ry = (near >> 10) & 1023u;
+    *rz = near >> 20;
+    return LOAMX_OK;
+  });
+}
+
+double loamx_dist_metres(uint32_t d2, float leaf, uint32_t cell_leaves) {
+  return std::sqrt((double)d2) * (double)leaf * (double)cell_leaves;
+}
+
 }  // extern "C"

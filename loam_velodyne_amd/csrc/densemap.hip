@@ -221,6 +221,7 @@ void DenseMap::reset() {
   LX_HIP(hipStreamSynchronize(own_));
   frozen.drop();
   drop_coarse();
+  dist_.drop();
   occ_.reset();
   offered_ = drop_range_ = drop_key_ = 0;
   for (uint64_t& c : carve_ctr_) c = 0;

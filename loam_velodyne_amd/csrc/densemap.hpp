@@ -316,6 +316,50 @@ class DmFrontier {
   PinLanding<DmFrAcc> h_acc_;
 };
 
+// include/loamx.h, loamx_densemap_dist_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
+void dm_dist_check(const loamx_densemap_dist_config& c);
+
+// Distance field (include/loamx.h, loamx_densemap_dist and loamx_densemap_dist_query; densemap_dist.hip): per cell of a 3-D window
+// 1/8 byte of the bit volume, the 4-byte word of the y pass, 2 bytes of d2 and 4 of near, 10 1/8 bytes per cell in all (0.68 GB at
+// 2^26 cells), and the pinned blocks that the stats, the planes wanted, the query's points and its samples cross through.  Allocated
+// by the first call, grow to the largest window asked for; the live map is only read.
+class DmDist {
+ public:
+  DmDist() = default;
+  DmDist(const DmDist&) = delete;
+  DmDist& operator=(const DmDist&) = delete;
+  // the field of a checked configuration over the table T (every add waited for) under a checked rule or none, on st: one memset
+  // and three kernels.  Blocks until the four stats and the planes wanted are in pinned memory (valid until the next run); the
+  // field stays on the device for query()
+  void run(const DmTable& T, const loamx_densemap_dist_config& c, const loamx_densemap_static_rule* rule, bool want_d2, bool want_near,
+           uint64_t stats[4], hipStream_t st);
+  const uint16_t* d2_on_host() const { return (const uint16_t*)h_d2_.data(); }
+  const uint32_t* near_on_host() const { return h_near_.data(); }
+  bool has_field() const { return valid_; }
+  void drop() { valid_ = false; }   // (the buffers stay for the next field)
+  // a checked cloud from the host into the feature's own device block, enqueued on st
+  const float4* stage(const loamx_cloud* c, hipStream_t st);
+  // n >= 1 points (readable on st) against the field of the last run: the five stats and, when want_samples, the n samples in
+  // pinned memory, valid until the next query.  Blocks
+  const loamx_dist_sample* query(const float4* pts, uint32_t n, float inv, uint32_t min_d2, bool want_samples, uint64_t stats[5],
+                                 hipStream_t st);
+
+ private:
+  DevBuf<unsigned long long> vol_;   // the four stats words, then the bit volume: ceil(nx / 64) words per row (rz, ry)
+  DevBuf<uint32_t> yx_;              // per cell: rx | ry << 10 of the nearest occupied cell of its plane, NONE
+  DevBuf<uint32_t> d2_;              // per cell 16 bits, two cells per word
+  DevBuf<uint32_t> near_;
+  DevBuf<unsigned long long> qc_;    // the query's five words
+  DevBuf<float4> d_pts_;
+  DevBuf<loamx_dist_sample> d_out_;
+  PinBuf<float4> h_pts_;
+  PinLanding<unsigned long long> h_ctr_, h_qc_;
+  PinLanding<uint32_t> h_d2_, h_near_;
+  PinLanding<loamx_dist_sample> h_out_;
+  loamx_densemap_dist_config cfg_ = {};   // of the field that stands
+  bool valid_ = false;
+};
+
 // include/loamx.h, loamx_densemap_segment_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
 void dm_segment_check(const loamx_densemap_segment_config& c);
 

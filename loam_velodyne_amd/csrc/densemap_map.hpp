@@ -142,6 +142,11 @@ class DenseMap {
   int frontiers_cells(const loamx_grid_cell* cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config& rc,
                       const loamx_grid_frontier_config& fc, const uint32_t* start_xz, uint32_t* labels, loamx_frontier* out,
                       uint64_t capacity, uint64_t* n_frontiers, uint64_t stats[6]);
+  // ---- densemap_dist.hip: include/loamx.h, loamx_densemap_dist and loamx_densemap_dist_query; a checked configuration, a checked
+  // rule or none.  The field stays in dist_ until the next dist, reset or destroy
+  void dist(const loamx_densemap_dist_config& c, const loamx_densemap_static_rule* rule, uint16_t* out_d2, uint32_t* out_near,
+            uint64_t stats[4]);
+  int dist_query(const loamx_cloud* points, uint32_t min_d2, loamx_dist_sample* out, uint64_t capacity, uint64_t stats[5]);
   int segment(const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint32_t* labels, uint64_t label_capacity,
               uint64_t* n_voxels, loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[6]);
   // ---- densemap_segment_cloud.hip: include/loamx.h, loamx_densemap_segment_cloud (the cloud staged from the host) and its from_*
@@ -184,6 +189,7 @@ class DenseMap {
   // the features that only read the table, each with its own buffers, allocated by its first call
   DmCaster caster_;   // densemap_raycast.hip
   DmGrid grid_;       // densemap_grid.hip
+  DmDist dist_;       // densemap_dist.hip
   DmRoute route_;     // densemap_route.hip
   DmFrontier fr_;     // densemap_frontier.hip (routes towards the start through route_)
   DmSegment seg_;     // densemap_segment.hip

@@ -1492,6 +1492,48 @@ def frontiers_best(frontiers, min_cost=0) -> int:
     return int(best.value)
 
 
+class DistConfig(_DefaultedConfig, C.Structure):
+    """loamx_densemap_dist_config: the 3-D window (cell_leaves, x0, y0, z0, nx, ny, nz), which voxels count (min_points) and the cap
+    d_max of the distance field.  DistConfig() holds the defaults (2; 0, 0, 0; 128 x 32 x 128; min_points 2; d_max 16); keyword
+    arguments replace them."""
+    _fields_ = [("cell_leaves", C.c_uint32), ("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_uint32),
+                ("ny", C.c_uint32), ("nz", C.c_uint32), ("min_points", C.c_uint32), ("d_max", C.c_uint32)]
+
+    _default, _checker = "loamx_densemap_dist_default_config", "loamx_densemap_dist_check"
+
+
+DIST_NONE = 0xffffffff                                                            # near of a capped cell, and of a point outside
+DIST_OUTSIDE = 0xffffffff                                                         # d2 of a point that has no cell in the window
+DIST_SAMPLE = np.dtype([("d2", "<u4"), ("near", "<u4")])                          # loamx_dist_sample, 8 bytes
+DIST_STATS = ("voxels", "occupied", "within", "max_d2")                           # stats[4] of loamx_densemap_dist
+DIST_QUERY_STATS = ("inside", "outside", "capped", "below", "best")               # stats[5] of loamx_densemap_dist_query
+
+
+def dist_window(leaf, x, y, z, half_extent_xyz, cell_leaves=2) -> DistConfig:
+    """loamx_densemap_dist_window (host only): a DistConfig (defaults otherwise) whose window covers (x, y, z) +- half_extent_xyz
+    metres (LOAM frame; one number serves the three axes) with cells of cell_leaves voxels.  LoamxError E_INVALID when the window
+    breaks a bound of the check."""
+    c = DistConfig(cell_leaves=cell_leaves)
+    centre = (C.c_float * 3)(x, y, z)
+    half = (C.c_float * 3)(*np.broadcast_to(np.asarray(half_extent_xyz, np.float32), (3,)).tolist())
+    _check(lib().loamx_densemap_dist_window(C.c_float(leaf), centre, half, C.byref(c)))
+    return c
+
+
+def dist_near_unpack(near):
+    """loamx_dist_near_unpack (host only): the window-relative cell (rx, ry, rz) of a near word; LoamxError E_INVALID for DIST_NONE"""
+    rx, ry, rz = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    _check(lib().loamx_dist_near_unpack(C.c_uint32(int(near)), C.byref(rx), C.byref(ry), C.byref(rz)))
+    return rx.value, ry.value, rz.value
+
+
+def dist_metres(d2, leaf: float, cell_leaves: int) -> float:
+    """loamx_dist_metres (host only): sqrt(d2) * leaf * cell_leaves in double, the distance between the cell centres"""
+    fn = lib().loamx_dist_metres
+    fn.restype = C.c_double
+    return float(fn(C.c_uint32(int(d2)), C.c_float(leaf), C.c_uint32(cell_leaves)))
+
+
 SEGMENT_NONE = 0xffffffff                                                         # label of a voxel in no kept component
 SEGMENT_ALL, SEGMENT_STATIC, SEGMENT_DYNAMIC = range(3)                           # loamx_densemap_segment_config.which
 
@@ -1997,6 +2039,37 @@ class DenseMap:
         _check(lib().loamx_densemap_grid(self.h, C.byref(c), C.byref(static) if static is not None else None,
                                          out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def dist(self, cfg=None, static=None, want_d2=True, want_near=False, **fields):
+        """loamx_densemap_dist: the exact squared distance, in cells, from every cell of a 3-D window to the nearest occupied cell
+        of the window, capped at d_max, computed on the device.  cfg: a DistConfig (None: the defaults; dist_window() makes one
+        around a position); fields replace members of a copy of it.  static (a StaticRule; needs carving): without the voxels the
+        rule calls dynamic.  Returns (d2, near): (nz, ny, nx) arrays, [cz - z0, cy - y0, cx - x0], uint16 and uint32 (DIST_NONE:
+        capped), None for a plane not wanted.  With neither only the stats cross; the field stays on the device for dist_query()
+        either way.  The four stats of the call are left in dist_stats."""
+        c = (DistConfig() if cfg is None else cfg).copy(**fields).check()
+        d2 = np.zeros((c.nz, c.ny, c.nx), np.uint16) if want_d2 else None
+        near = np.zeros((c.nz, c.ny, c.nx), np.uint32) if want_near else None
+        st = (C.c_uint64 * 4)()
+        _check(lib().loamx_densemap_dist(self.h, C.byref(c), C.byref(static) if static is not None else None,
+                                         d2.ctypes.data_as(C.c_void_p) if want_d2 else None,
+                                         near.ctypes.data_as(C.c_void_p) if want_near else None, st))
+        self.dist_stats = dict(zip(DIST_STATS, (int(v) for v in st)))
+        return d2, near
+
+    def dist_query(self, points, min_d2=0, records=True):
+        """loamx_densemap_dist_query: the d2 and near of the cell of every point ((N, 4) / (N, 8), map frame) in the field of the
+        last dist() call, looked up on the device.  Returns (samples, stats): DIST_SAMPLE records, d2 = DIST_OUTSIDE for a point
+        without a cell in the window (None with records=False), and a dict in the order of DIST_QUERY_STATS: points inside,
+        outside, inside and capped, inside with d2 < min_d2, and best = (the smallest d2) << 32 | the smallest index with it,
+        2^64 - 1 when no point is inside.  Blocks."""
+        a = as_points(points)
+        c = cloud_of(a)
+        out = np.zeros(max(len(a), 1), DIST_SAMPLE) if records else None
+        st = (C.c_uint64 * 5)()
+        _check(lib().loamx_densemap_dist_query(self.h, C.byref(c), C.c_uint32(min_d2), out.ctypes.data_as(C.c_void_p) if records else None,
+                                               C.c_uint64(len(a)), st))
+        return (out[:len(a)] if records else None), dict(zip(DIST_QUERY_STATS, (int(v) for v in st)))
 
     ROUTE_STATS = ("traversable", "reachable", "goals_used", "max_cost", "rounds", "tile_runs")
 
