@@ -5,6 +5,7 @@
 #include "common.h"
 #include "densemap_growth.hpp"
 #include "pinned_copy.hpp"
+#include "scan.hpp"
 #include <vector>
 
 namespace loamx {
@@ -91,6 +92,45 @@ struct DmTable {
   }
 };
 
+// The chained scan (scan.hpp) of the per-block counts behind a ballot compaction: its chain state, zero-filled once, on first use, and
+// its two scratch words.  scan.hpp lets one state serve all scans of ONE stream and no others: a DenseMap owns one DmScan and hands
+// it to compact_of, DmSegment::run and DmFrontier::run, all three of which scan on the map's own stream, own_
+struct DmScan {
+  // the nblk counts at blk become their exclusive prefix sums in place and blk[nblk] their total, enqueued on st
+  void run(uint32_t* blk, uint32_t nblk, hipStream_t st) {
+    scratch_.reserve(2);
+    if (!state_.p) {
+      state_.reserve(chained_scan_state_words());
+      LX_HIP(hipMemsetAsync(state_.p, 0, sizeof(unsigned long long) * state_.cap, st));
+    }
+    exclusive_scan_u32_n(blk, blk, (uint32_t*)state_.p, scratch_.p, nblk, st);
+  }
+
+ private:
+  DevBuf<unsigned long long> state_;
+  DevBuf<uint32_t> scratch_;
+};
+
+// A cloud from the host on its way to the device: a pinned block and a device block, grown to the largest cloud.  Each feature that
+// stages keeps one of its own: their clouds stay resident independently of each other
+struct DmCloudStage {
+  // the points of a checked cloud, packed, in the device block, enqueued on st (count + 1 entries: an empty cloud has a pointer too)
+  const float4* stage(const loamx_cloud* c, hipStream_t st) {
+    const uint32_t n = c->count;
+    h_.reserve((size_t)n + 1);
+    d_.reserve((size_t)n + 1);
+    if (n) {
+      pack_cloud(c, h_.p);
+      fetch_from_pinned(d_.p, h_.p, n, st);
+    }
+    return d_.p;
+  }
+
+ private:
+  PinBuf<float4> h_;
+  DevBuf<float4> d_;
+};
+
 // Where a device-side add reads: a registered cloud that some other handle keeps in HBM, the stream that wrote it, and the pose of the
 // sweep.  Filled by the internal accessors of mapping.hip / pipeline.hip (the handle structs stay where they are).
 struct DenseSource {
@@ -145,8 +185,8 @@ class DmFrozen {
   void drop();
   // replaces the snapshot by the n voxels (keys[i], rec[6 * i ..]); blocks until the table stands
   void build(const unsigned long long* keys, const float* rec, size_t n, hipStream_t st);
-  // the cloud of the steps that follow, from the host (staged) or where it lies on the device
-  const float4* stage(const loamx_cloud* c, hipStream_t st);
+  // the cloud of the steps that follow, checked and staged from the host, enqueued on st
+  const float4* stage(const loamx_cloud* c, hipStream_t st) { check_cloud(c, false); return pts_.stage(c, st); }
   // one linearisation (include/loamx.h, loamx_densemap_align_step); blocks until the 33 words are back
   void step(const float4* pts, uint32_t n, const float rtc[15], float inv, uint32_t neighbourhood, float max_residual, hipStream_t st,
             int64_t sums[28], uint64_t counts[5]);
@@ -165,8 +205,7 @@ class DmFrozen {
   uint64_t count_ = 0;
   DevBuf<unsigned long long> acc_;
   PinLanding<unsigned long long> h_acc_;
-  PinBuf<float4> h_pts_;
-  DevBuf<float4> d_pts_;
+  DmCloudStage pts_;
   PinBuf<float4> h_poses_;
   DevBuf<float4> d_poses_;
   uint64_t stats_[3] = {0, 0, 0};
@@ -297,18 +336,18 @@ class DmFrontier {
   DmFrontier(const DmFrontier&) = delete;
   DmFrontier& operator=(const DmFrontier&) = delete;
   // the frontiers of nx * nz <= 2^26 records d_cells on the device (written by work enqueued on st) under a checked configuration:
-  // mark, link, flatten, the scan, ids and reduce, and the host's min_cells and ranks.  d_field (NULL: none): the nx * nz records of a
-  // route's field on the device, whose costs give reachable and best.  Blocks.  out: the kept frontiers in ascending min_cell; stats
-  // as in include/loamx.h.  Returns, when want_labels, the nx * nz labels in pinned memory, valid until the next run
+  // mark, link, flatten, the scan (through the map's DmScan: st is the stream of its scans), ids and reduce, and the host's min_cells
+  // and ranks.  d_field (NULL: none): the nx * nz records of a route's field on the device, whose costs give reachable and best.
+  // Blocks.  out: the kept frontiers in ascending min_cell; stats as in include/loamx.h.  Returns, when want_labels, the nx * nz
+  // labels in pinned memory, valid until the next run
   const uint32_t* run(const loamx_grid_cell* d_cells, uint32_t nx, uint32_t nz, const loamx_grid_frontier_config& c,
-                      const loamx_route_cell* d_field, bool want_labels, std::vector<loamx_frontier>& out, uint64_t stats[6], hipStream_t st);
+                      const loamx_route_cell* d_field, bool want_labels, std::vector<loamx_frontier>& out, uint64_t stats[6], DmScan& scan,
+                      hipStream_t st);
 
  private:
   DevBuf<uint32_t> parent_, rootid_;   // per cell: the union-find word (NONE: no frontier cell); the compact id of a root
   DevBuf<unsigned char> u8_;           // per cell: unknown8 of a frontier cell
   DevBuf<uint32_t> blk_;               // roots per 256-cell block, + 1 word for the total
-  DevBuf<uint32_t> scratch_;           // the scan's two words
-  DevBuf<unsigned long long> tiles_;   // the scan's chain state, zeroed when allocated
   DevBuf<uint32_t> ctr_;               // frontier cells, hook attempts lost, a loop bound reached, roots
   DevBuf<DmFrAcc> acc_;                // one accumulator per frontier, by compact id
   DevBuf<uint32_t> rank_, lab_;        // with labels: per compact id its rank (NONE: dropped); per cell its label
@@ -337,8 +376,7 @@ class DmDist {
   const uint32_t* near_on_host() const { return h_near_.data(); }
   bool has_field() const { return valid_; }
   void drop() { valid_ = false; }   // (the buffers stay for the next field)
-  // a checked cloud from the host into the feature's own device block, enqueued on st
-  const float4* stage(const loamx_cloud* c, hipStream_t st);
+  DmCloudStage cloud;   // the query's points from the host, in the feature's own device block
   // n >= 1 points (readable on st) against the field of the last run: the five stats and, when want_samples, the n samples in
   // pinned memory, valid until the next query.  Blocks
   const loamx_dist_sample* query(const float4* pts, uint32_t n, float inv, uint32_t min_d2, bool want_samples, uint64_t stats[5],
@@ -350,9 +388,7 @@ class DmDist {
   DevBuf<uint32_t> d2_;              // per cell 16 bits, two cells per word
   DevBuf<uint32_t> near_;
   DevBuf<unsigned long long> qc_;    // the query's five words
-  DevBuf<float4> d_pts_;
   DevBuf<loamx_dist_sample> d_out_;
-  PinBuf<float4> h_pts_;
   PinLanding<unsigned long long> h_ctr_, h_qc_;
   PinLanding<uint32_t> h_d2_, h_near_;
   PinLanding<loamx_dist_sample> h_out_;
@@ -373,11 +409,12 @@ class DmSegment {
   DmSegment(const DmSegment&) = delete;
   DmSegment& operator=(const DmSegment&) = delete;
   // the components of the table T (every add waited for, `occ` voxels, occ >= 1) under a checked configuration and rule, on st:
-  // select, link, flatten, the two scans, ids and reduce, and the host's ordering by key.  Blocks.  segs: the kept components in
-  // ascending min_key; labels (when want_labels): one word per voxel in ascending key order; stats as in include/loamx.h
+  // select, link, flatten, the two scans (through the map's DmScan: st is the stream of its scans), ids and reduce, and the host's
+  // ordering by key.  Blocks.  segs: the kept components in ascending min_key; labels (when want_labels): one word per voxel in
+  // ascending key order; stats as in include/loamx.h
   // rank_of_id (optional): per compact id the component's place in segs, NONE when min_voxels dropped it
   void run(const DmTable& T, const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint64_t occ, bool want_labels,
-           std::vector<uint32_t>& labels, std::vector<loamx_segment>& segs, uint64_t stats[6], hipStream_t st,
+           std::vector<uint32_t>& labels, std::vector<loamx_segment>& segs, uint64_t stats[6], DmScan& scan, hipStream_t st,
            std::vector<uint32_t>* rank_of_id = nullptr);
   // what the last run left on the device, per slot of its table: the root of a selected slot (NONE: not selected), and a root's
   // compact id (DmSegCloud labels points through them)
@@ -387,9 +424,7 @@ class DmSegment {
  private:
   DevBuf<uint32_t> parent_, rootid_;       // per slot: the union-find word (NONE: not selected); the compact id of a root
   DevBuf<uint32_t> blk_;                   // two runs of blocks + 1 words: roots, then occupied slots, per 256-slot block
-  DevBuf<uint32_t> scratch_;               // the scans' two words
-  DevBuf<unsigned long long> tiles_;       // the scans' chain state, zeroed when allocated
-  DevBuf<unsigned long long> ctr_;         // voxels selected, hook attempts lost
+  DevBuf<unsigned long long> ctr_;         // voxels selected, hook attempts lost, the two totals, a loop bound reached
   DevBuf<loamx_segment> acc_;              // one accumulator per component, by compact id
   DevBuf<unsigned long long> okeys_;       // with labels: the occupied slots' keys in slot order ...
   DevBuf<uint32_t> oids_;                  // ... and their compact ids (NONE: not selected)
@@ -412,8 +447,7 @@ class DmSegCloud {
   DmSegCloud() = default;
   DmSegCloud(const DmSegCloud&) = delete;
   DmSegCloud& operator=(const DmSegCloud&) = delete;
-  // the cloud (count >= 1) from the host into the feature's own device block, enqueued on st
-  const float4* stage(const loamx_cloud* c, hipStream_t st);
+  DmCloudStage cloud;   // the cloud from the host, in the feature's own device block
   // n >= 1 points (readable on st) under the filter F of their origin against the live table M (every add waited for): the scratch
   // table cleared, the admitted points that pass the map test of a checked configuration and rule (NULL: every voxel) inserted.
   // Blocks.  counts: dropped by range, by the key rule, rejected by the map test, entered, voxels of the scratch table
@@ -427,8 +461,6 @@ class DmSegCloud {
  private:
   DmTable tab_;               // (slots: the size this call uses, the front of an allocation of cap_slots_)
   uint32_t cap_slots_ = 0;
-  DevBuf<float4> d_pts_;
-  PinBuf<float4> h_pts_;
   DevBuf<unsigned long long> pkey_, ctr_;   // per point: its key, EMPTY when it did not enter; the counters
   DevBuf<uint32_t> ids_;
   PinLanding<unsigned long long> h_ctr_;

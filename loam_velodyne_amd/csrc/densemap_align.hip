@@ -145,18 +145,6 @@ void DmFrozen::build(const unsigned long long* keys, const float* rec, size_t n,
   count_ = n;
 }
 
-const float4* DmFrozen::stage(const loamx_cloud* c, hipStream_t st) {
-  check_cloud(c, false);
-  const uint32_t n = c->count;
-  h_pts_.reserve((size_t)n + 1);
-  d_pts_.reserve((size_t)n + 1);
-  if (n) {
-    pack_cloud(c, h_pts_.p);
-    fetch_from_pinned(d_pts_.p, h_pts_.p, n, st);
-  }
-  return d_pts_.p;
-}
-
 void DmFrozen::step(const float4* pts, uint32_t n, const float rtc[15], float inv, uint32_t neighbourhood, float max_residual, hipStream_t st,
                     int64_t sums[28], uint64_t counts[5]) {
   LX_REQUIRE(valid(), "nothing is frozen (loamx_densemap_freeze)");

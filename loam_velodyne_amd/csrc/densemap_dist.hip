@@ -332,17 +332,6 @@ void DmDist::run(const DmTable& T, const loamx_densemap_dist_config& c, const lo
   valid_ = true;
 }
 
-const float4* DmDist::stage(const loamx_cloud* c, hipStream_t st) {
-  const uint32_t n = c->count;
-  h_pts_.reserve((size_t)n + 1);
-  d_pts_.reserve((size_t)n + 1);
-  if (n) {
-    pack_cloud(c, h_pts_.p);
-    fetch_from_pinned(d_pts_.p, h_pts_.p, n, st);
-  }
-  return d_pts_.p;
-}
-
 const loamx_dist_sample* DmDist::query(const float4* pts, uint32_t n, float inv, uint32_t min_d2, bool want_samples, uint64_t stats[5],
                                        hipStream_t st) {
   qc_.reserve(5);
@@ -410,7 +399,7 @@ int DenseMap::dist_query(const loamx_cloud* points, uint32_t min_d2, loamx_dist_
   uint64_t s[5] = {0, 0, 0, 0, ~0ull};
   if (n) {
     LX_HIP(hipSetDevice(cfg.device));
-    const float4* pts = dist_.stage(points, own_);
+    const float4* pts = dist_.cloud.stage(points, own_);
     const loamx_dist_sample* got = dist_.query(pts, n, inv_, min_d2, out != nullptr, s, own_);
     if (out) memcpy(out, got, sizeof(loamx_dist_sample) * n);
   }

@@ -7,7 +7,7 @@
 //   k_dm_fr_mark      one block per tile of 32 x 32 cells.  The class of every cell of the tile and of a halo of one (0 other, 1 UNKNOWN,
 //                     2 FREE with clear2 >= min_clear2; outside the window: 0) goes to LDS as a byte, each thread counts the unknown
 //                     neighbours of its four cells there, and the tile's frontier cells are labelled INSIDE the tile at once, by a
-//                     union-find over a 1024-word LDS array (the union of k_dm_seg_link on local indices, LDS atomics).  It writes
+//                     union-find over a 1024-word LDS array (densemap_label.hpp, workgroup scope, on local indices).  It writes
 //                     parent[c] = the record index of the cell's root inside the tile (NONE: no frontier cell) and unknown8 as a
 //                     byte, and counts the frontier cells with one atomic per block.  Only the owning tile writes a word, so these
 //                     are plain stores.  Marking and the in-tile labelling share a launch because they share the staged tile; the
@@ -16,19 +16,17 @@
 //                     before: 128 threads per tile, 96 at work, one per border cell: the last row joins its three neighbours below, the
 //                     last column its neighbours to the right, the first column the one below to the left (the forward half of
 //                     the neighbourhood: 2 offsets under connectivity 4, 4 under 8; the pairs inside a tile were joined in LDS).  The
-//                     union is the lock-free one of k_dm_seg_link over parent[]: find both roots, hook the root with the LARGER cell index
-//                     under the smaller by atomicCAS, from the finds again when the CAS loses.  The index falls strictly along every
-//                     chain: no cycles, and the root of a finished frontier is its min_cell whatever the schedule.  No spin-wait, no
-//                     grid barrier; parent[] is read and written with agent-scope atomics only.  Every loop is bounded in the code: a
-//                     find by the number of cells (a chain visits a cell once), a union by the number of cells + 1 (a lost CAS means
-//                     a root stopped being one, which happens once per cell).  A bound that is reached raises ctr[2], and the host
-//                     reports LOAMX_E_INTERNAL.
-//   k_dm_fr_flatten   parent[c] = root, the roots of each 256-cell block counted; the chained scan of scan.hpp over the counts gives
-//                     every root a compact id.  Roots are cell indices, so the ids ascend with min_cell: the final order.
+//                     union-find of densemap_label.hpp over parent[] in HBM (agent scope; the argument for it is there), a cell's
+//                     rank being its index, so that the root of a finished frontier is its min_cell whatever the schedule.  The bound
+//                     of every loop is the number of cells (of a tile in k_dm_fr_mark); one that is reached raises ctr[2], and the
+//                     host reports LOAMX_E_INTERNAL.
+//   k_dm_fr_flatten   parent[c] = root, the roots of each 256-cell block counted (dm_block_count); the chained scan of scan.hpp over
+//                     the counts gives every root a compact id.  Roots are cell indices, so the ids ascend with min_cell: the final
+//                     order.
 //   k_dm_fr_ids       a root writes its id and the empty accumulator of its frontier.
 //   k_dm_fr_reduce    per frontier cell: cells, the sums of rx, rz and unknown8 and the reachable count by integer adds, the box by
 //                     min / max, best by one 64-bit atomicMin of (cost << 32) | cell: "smallest cost, then smallest index".  Combined
-//                     inside the block in a 256-entry LDS table keyed by the id, as k_dm_seg_reduce does, then one global atomic per
+//                     inside the block in a 256-entry LDS table keyed by the id (dm_lds_claim), then one global atomic per
 //                     (block, frontier, word).
 //   k_dm_fr_labels    only when labels are wanted: the host has applied min_cells and ranked the kept frontiers; the ranks go up, one
 //                     word per cell comes down.
@@ -47,47 +45,20 @@
 // plain read of the accumulator in front of each minimum and maximum, to send only those that change something, with cells and
 // reachable in one 64-bit add.  Same bytes, but reduce took 489 us instead of 250 (86 instead of 40 at 512 x 512): an atomic whose
 // result nobody reads is sent and forgotten, a read of the same contended line is waited for.
+#include "densemap_label.hpp"
 #include "densemap_map.hpp"
 #include "pinned_copy.hpp"
-#include "scan.hpp"
 
 namespace loamx {
 
 constexpr int DM_FR_TILE = 32;
 constexpr int DM_FR_SIDE = DM_FR_TILE + 2;   // with the halo
 constexpr uint32_t DM_FR_NONE = LOAMX_FRONTIER_NONE;
+static_assert(DM_FR_NONE == DM_UF_NONE, "the union-find's NONE is the label of a cell in no frontier");
+constexpr int DM_FR_LDS_SCOPE = __HIP_MEMORY_SCOPE_WORKGROUP, DM_FR_AGENT = __HIP_MEMORY_SCOPE_AGENT;   // a tile's array; parent[] in HBM
 constexpr uint32_t DM_FR_MAX_CELLS = 1u << 26;
 constexpr uint32_t DM_FR_MAX_ROUTED = 1u << 22;
-constexpr int DM_FR_LDS = 256;   // entries of k_dm_fr_reduce's table: the block's threads, the most ids it can meet
 constexpr unsigned long long DM_FR_NO_BEST = ~0ull;   // (LOAMX_ROUTE_UNREACHABLE << 32) | LOAMX_FRONTIER_NONE
-
-__device__ inline uint32_t dm_fr_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline uint32_t dm_fr_lds_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-// the root above x in the tile's LDS array, halving the path; at most 1024 steps (the index falls along the chain).  NONE: the bound
-__device__ inline uint32_t dm_fr_lds_find(uint32_t* par, uint32_t x) {
-  for (int k = 0; k < DM_FR_TILE * DM_FR_TILE; k++) {
-    const uint32_t p = dm_fr_lds_load(&par[x]);
-    if (p == x) return x;
-    const uint32_t g = dm_fr_lds_load(&par[p]);
-    if (g == p) return p;
-    __hip_atomic_store(&par[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // (x is no root and stays none: g is an ancestor)
-    x = g;
-  }
-  return DM_FR_NONE;
-}
-// the same over parent[] in HBM; at most `cells` steps
-__device__ inline uint32_t dm_fr_find(uint32_t* parent, uint32_t x, uint32_t cells) {
-  for (uint32_t k = 0; k < cells; k++) {
-    const uint32_t p = dm_fr_load(&parent[x]);
-    if (p == x) return x;
-    const uint32_t g = dm_fr_load(&parent[p]);
-    if (g == p) return p;
-    __hip_atomic_store(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = g;
-  }
-  return DM_FR_NONE;
-}
 
 // grid: tiles_x x tiles_z.  ctr: [0] frontier cells, [1] hooks lost, [2] a loop bound was reached
 __global__ __launch_bounds__(256) void k_dm_fr_mark(const loamx_grid_cell* __restrict__ cells, uint32_t nx, uint32_t nz, int diag,
@@ -142,19 +113,8 @@ __global__ __launch_bounds__(256) void k_dm_fr_mark(const loamx_grid_cell* __res
       const int ax = lx + dx, az = lz + dz;
       if (ax < 0 || ax >= DM_FR_TILE || az >= DM_FR_TILE) continue;   // (across the border: k_dm_fr_link)
       const uint32_t nb = (uint32_t)(az * DM_FR_TILE + ax);
-      if (dm_fr_lds_load(&s_par[nb]) == DM_FR_NONE) continue;
-      uint32_t a = l, b = nb;
-      int tries = 0;
-      for (; tries <= DM_FR_TILE * DM_FR_TILE; tries++) {   // a lost CAS: a root stopped being one, once per cell
-        a = dm_fr_lds_find(s_par, a);
-        b = dm_fr_lds_find(s_par, b);
-        if (a == DM_FR_NONE || b == DM_FR_NONE) { bad = 1u; break; }
-        if (a == b) break;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }   // a: the root with the larger index
-        if (atomicCAS(&s_par[a], a, b) == a) break;
-        lost++;
-      }
-      if (tries > DM_FR_TILE * DM_FR_TILE) bad = 1u;
+      if (dm_uf_load<DM_FR_LDS_SCOPE>(&s_par[nb]) == DM_FR_NONE) continue;
+      if (!dm_uf_union<DM_FR_LDS_SCOPE>(s_par, l, nb, DM_FR_TILE * DM_FR_TILE, [](uint32_t e) { return e; }, lost)) bad = 1u;
     }
   }
   if (mine) atomicAdd(&s_n, mine);
@@ -169,7 +129,7 @@ __global__ __launch_bounds__(256) void k_dm_fr_mark(const loamx_grid_cell* __res
     const uint32_t l = (uint32_t)(lz * DM_FR_TILE + lx);
     uint32_t root = DM_FR_NONE;
     if (s_par[l] != DM_FR_NONE) {
-      const uint32_t r = dm_fr_lds_find(s_par, l);
+      const uint32_t r = dm_uf_find<DM_FR_LDS_SCOPE>(s_par, l, DM_FR_TILE * DM_FR_TILE);
       if (r == DM_FR_NONE) atomicOr(&s_bad, 1u);
       // (a cell whose find gave up stays a root of its own: still a frontier cell, and the host reports the bound)
       const uint32_t rl = r == DM_FR_NONE ? l : r;
@@ -196,7 +156,7 @@ __global__ __launch_bounds__(128) void k_dm_fr_link(uint32_t nx, uint32_t nz, in
   const uint32_t x = blockIdx.x * DM_FR_TILE + lx, z = blockIdx.y * DM_FR_TILE + lz;
   if (x >= nx || z >= nz) return;
   const uint32_t cells = nx * nz, c = z * nx + x;
-  if (dm_fr_load(&parent[c]) == DM_FR_NONE) return;
+  if (dm_uf_load<DM_FR_AGENT>(&parent[c]) == DM_FR_NONE) return;
   uint32_t lost = 0u, bad = 0u;
   for (int o = 0; o < 4; o++) {   // (dx, dz) = (1, 0), (-1, 1), (0, 1), (1, 1)
     const int dx = o == 0 ? 1 : o - 2, dz = o == 0 ? 0 : 1;
@@ -206,18 +166,8 @@ __global__ __launch_bounds__(128) void k_dm_fr_link(uint32_t nx, uint32_t nz, in
     const uint32_t qx = x + (uint32_t)dx, qz = z + (uint32_t)dz;    // (a cell before the window wraps)
     if (qx >= nx || qz >= nz) continue;
     const uint32_t nb = qz * nx + qx;
-    if (dm_fr_load(&parent[nb]) == DM_FR_NONE) continue;
-    uint32_t a = c, b = nb, tries = 0u;
-    for (; tries <= cells; tries++) {   // a lost CAS: a root stopped being one, once per cell
-      a = dm_fr_find(parent, a, cells);
-      b = dm_fr_find(parent, b, cells);
-      if (a == DM_FR_NONE || b == DM_FR_NONE) { bad = 1u; break; }
-      if (a == b) break;
-      if (a < b) { const uint32_t s = a; a = b; b = s; }   // a: the root with the larger index
-      if (atomicCAS(&parent[a], a, b) == a) break;
-      lost++;
-    }
-    if (tries > cells) bad = 1u;
+    if (dm_uf_load<DM_FR_AGENT>(&parent[nb]) == DM_FR_NONE) continue;
+    if (!dm_uf_union<DM_FR_AGENT>(parent, c, nb, cells, [](uint32_t e) { return e; }, lost)) bad = 1u;
   }
   if (lost) atomicAdd(&ctr[1], lost);
   if (bad) atomicOr(&ctr[2], 1u);
@@ -225,27 +175,19 @@ __global__ __launch_bounds__(128) void k_dm_fr_link(uint32_t nx, uint32_t nz, in
 
 __global__ __launch_bounds__(256) void k_dm_fr_flatten(uint32_t cells, uint32_t* parent, uint32_t* __restrict__ blk_roots,
                                                        uint32_t* __restrict__ ctr) {
-  __shared__ uint32_t wr[4];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   bool root = false;
   if (i < cells) {
-    uint32_t x = dm_fr_load(&parent[i]);
+    const uint32_t x = dm_uf_load<DM_FR_AGENT>(&parent[i]);
     if (x != DM_FR_NONE) {
       root = x == i;
-      uint32_t k = 0u;
-      for (; k < cells; k++) {   // (the index falls along the chain: it ends within `cells` steps)
-        const uint32_t p = dm_fr_load(&parent[x]);
-        if (p == x) break;
-        x = p;
-      }
-      if (k == cells) atomicOr(&ctr[2], 1u);
-      if (!root) __hip_atomic_store(&parent[i], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint32_t r = dm_uf_root<DM_FR_AGENT>(parent, x, cells);
+      if (r == DM_FR_NONE) atomicOr(&ctr[2], 1u);
+      else if (!root) __hip_atomic_store(&parent[i], r, __ATOMIC_RELAXED, DM_FR_AGENT);
     }
   }
-  const unsigned long long mr = __ballot(root);
-  if ((threadIdx.x & 63) == 0) wr[threadIdx.x >> 6] = (uint32_t)__popcll(mr);
-  __syncthreads();
-  if (threadIdx.x == 0) blk_roots[blockIdx.x] = wr[0] + wr[1] + wr[2] + wr[3];
+  const uint32_t n_roots = dm_block_count(root);
+  if (threadIdx.x == 0) blk_roots[blockIdx.x] = n_roots;
 }
 
 // the total of the scan beside the three counters: the four words that go back before the second half is sized
@@ -256,16 +198,11 @@ __global__ void k_dm_fr_totals(const uint32_t* __restrict__ total_roots, uint32_
 // behind the scan of the root counts: a root's compact id and the empty accumulator of its frontier
 __global__ __launch_bounds__(256) void k_dm_fr_ids(uint32_t cells, const uint32_t* __restrict__ parent, const uint32_t* __restrict__ off_roots,
                                                    uint32_t n_roots, uint32_t* __restrict__ rootid, DmFrAcc* __restrict__ acc) {
-  __shared__ uint32_t wc[4];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
   const bool root = i < cells && parent[i] == i;
-  const unsigned long long m = __ballot(root);
-  if (lane == 0) wc[wid] = (uint32_t)__popcll(m);
-  __syncthreads();
+  const unsigned long long m = dm_block_vote(root);
   if (!root) return;
-  uint32_t id = off_roots[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wid; w++) id += wc[w];
+  const uint32_t id = dm_block_rank(m, off_roots[blockIdx.x]);
   if (id >= n_roots) return;   // (cannot happen: the scan counted these roots)
   rootid[i] = id;
   DmFrAcc a;
@@ -284,9 +221,9 @@ __global__ __launch_bounds__(256) void k_dm_fr_reduce(uint32_t nx, uint32_t cell
                                                       const uint32_t* __restrict__ rootid, uint32_t n_roots,
                                                       const unsigned char* __restrict__ u8, const loamx_route_cell* __restrict__ field,
                                                       DmFrAcc* __restrict__ acc) {
-  __shared__ uint32_t s_id[DM_FR_LDS];
-  __shared__ uint32_t s_w[DM_FR_LDS][6];               // cells, reachable, lo, hi
-  __shared__ unsigned long long s_sum[DM_FR_LDS][4];   // sum_rx, sum_rz, links, best
+  __shared__ uint32_t s_id[DM_LDS_IDS];
+  __shared__ uint32_t s_w[DM_LDS_IDS][6];               // cells, reachable, lo, hi
+  __shared__ unsigned long long s_sum[DM_LDS_IDS][4];   // sum_rx, sum_rz, links, best
   const uint32_t t = threadIdx.x, i = blockIdx.x * blockDim.x + t;
   s_id[t] = DM_FR_NONE;
   s_w[t][0] = s_w[t][1] = 0u;
@@ -304,12 +241,7 @@ __global__ __launch_bounds__(256) void k_dm_fr_reduce(uint32_t nx, uint32_t cell
   if (id != DM_FR_NONE) {
     const uint32_t rx = i % nx, rz = i / nx;
     const uint32_t cost = field ? field[i].cost : LOAMX_ROUTE_UNREACHABLE;
-    uint32_t h = id & (DM_FR_LDS - 1);
-    for (int probe = 0; probe < DM_FR_LDS; probe++) {   // (a block meets at most 256 ids: a probe always ends)
-      const uint32_t prev = atomicCAS(&s_id[h], DM_FR_NONE, id);
-      if (prev == DM_FR_NONE || prev == id) break;
-      h = (h + 1u) & (DM_FR_LDS - 1);
-    }
+    const uint32_t h = dm_lds_claim(s_id, id);
     atomicAdd(&s_w[h][0], 1u);
     atomicMin(&s_w[h][2], rx);
     atomicMin(&s_w[h][3], rz);
@@ -365,27 +297,22 @@ void dm_frontier_check(const loamx_grid_frontier_config& c) {
 
 const uint32_t* DmFrontier::run(const loamx_grid_cell* d_cells, uint32_t nx, uint32_t nz, const loamx_grid_frontier_config& c,
                                 const loamx_route_cell* d_field, bool want_labels, std::vector<loamx_frontier>& out, uint64_t stats[6],
-                                hipStream_t st) {
+                                DmScan& scan, hipStream_t st) {
   const uint32_t n = nx * nz, nblk = (n + 255u) / 256u;
   const uint32_t tiles_x = (nx + DM_FR_TILE - 1) / DM_FR_TILE, tiles_z = (nz + DM_FR_TILE - 1) / DM_FR_TILE;
   parent_.reserve(n);
   rootid_.reserve(n);
   u8_.reserve(n);
   blk_.reserve((size_t)nblk + 1);
-  scratch_.reserve(2);
   ctr_.reserve(4);
   h_ctr_.reserve(4);
-  if (!tiles_.p) {
-    tiles_.reserve(chained_scan_state_words());
-    LX_HIP(hipMemsetAsync(tiles_.p, 0, sizeof(unsigned long long) * tiles_.cap, st));
-  }
   const int diag = c.connectivity == 8u ? 1 : 0;
   const dim3 per_tile(tiles_x, tiles_z), per_cell(nblk), block(256);
   LX_HIP(hipMemsetAsync(ctr_.p, 0, sizeof(uint32_t) * 4, st));
   hipLaunchKernelGGL(k_dm_fr_mark, per_tile, block, 0, st, d_cells, nx, nz, diag, c.min_unknown, c.min_clear2, parent_.p, u8_.p, ctr_.p);
   hipLaunchKernelGGL(k_dm_fr_link, per_tile, dim3(128), 0, st, nx, nz, diag, parent_.p, ctr_.p);
   hipLaunchKernelGGL(k_dm_fr_flatten, per_cell, block, 0, st, n, parent_.p, blk_.p, ctr_.p);
-  exclusive_scan_u32_n(blk_.p, blk_.p, (uint32_t*)tiles_.p, scratch_.p, nblk, st);   // ([nblk]: the total)
+  scan.run(blk_.p, nblk, st);   // ([nblk]: the total)
   hipLaunchKernelGGL(k_dm_fr_totals, dim3(1), dim3(64), 0, st, blk_.p + nblk, ctr_.p);
   LX_HIP(hipGetLastError());
   store_to_pinned_u32(h_ctr_.p, ctr_.p, 4, st);
@@ -464,7 +391,7 @@ int DenseMap::frontiers_on(const loamx_grid_cell* d_cells, uint32_t nx, uint32_t
   }
   std::vector<loamx_frontier> fr;
   uint64_t s[6] = {0, 0, 0, 0, 0, 0};
-  const uint32_t* lab = fr_.run(d_cells, nx, nz, fc, d_field, labels != nullptr, fr, s, own_);
+  const uint32_t* lab = fr_.run(d_cells, nx, nz, fc, d_field, labels != nullptr, fr, s, scan_, own_);
   *n_frontiers = fr.size();
   if (out && capacity < fr.size()) return LOAMX_E_CAPACITY;
   if (labels) memcpy(labels, lab, sizeof(uint32_t) * (size_t)nx * nz);

@@ -99,7 +99,7 @@ class DenseMap {
 
   // ---- densemap_region.hip: include/loamx.h, loamx_densemap_count_region ... page.  A checked window each
   // the compaction behind snapshot_of and select: the occupied slots of T (W: of those, the ones the window selects) in slot order
-  // on own_, brought to the host and ordered by key.  Without W, occ is T's count and one wait serves; with W the block counts are
+  // on own_ (the block counts scanned through scan_), brought to the host and ordered by key.  Without W, occ is T's count and one wait serves; with W the block counts are
   // scanned and the total and the sum of n waited for first (counts, when given: voxels, points), and only the selected records
   // cross.  S NULL (with W): the counts alone
   void compact_of(const DmTable& T, const DmWindow* W, uint64_t occ, Snapshot* S, bool want_mom, uint64_t counts[2]);
@@ -164,6 +164,7 @@ class DenseMap {
   float inv_ = 10.f;
   DevBuf<unsigned long long> ctr_;
   PinLanding<unsigned long long> h_ctr_, h_snap_;
+  DmScan scan_;       // the one scan state of the handle: compact_of, seg_ and fr_ scan through it, each on own_
   DmOccupancy occ_;   // the bound of the occupancy that growth and admission are decided on (densemap_growth.hpp)
   uint64_t offered_ = 0, drop_range_ = 0, drop_key_ = 0;
   std::vector<void*> graveyard_;   // tables replaced by a rehash: freed at the next point where the host waits anyway

@@ -12,9 +12,9 @@
 // evict: the count, the smaller table allocated, (with a path) the compaction and the file, then k_dm_rehash with the window as what
 // stays behind (densemap.hip), then the swap.  Everything that can fail comes before the first change of the handle.
 #include "densemap_dev.hpp"
+#include "densemap_label.hpp"
 #include "densemap_map.hpp"
 #include "densemap_tiles.hpp"
-#include "scan.hpp"
 #include <algorithm>
 #include <cstddef>
 #include <dirent.h>
@@ -37,16 +37,13 @@ template <bool REGION>
 __global__ __launch_bounds__(256) void k_dm_count(const unsigned long long* __restrict__ keys, uint32_t slots, uint32_t* __restrict__ blk,
                                                   DmWindow W, const unsigned long long* __restrict__ vals,
                                                   unsigned long long* __restrict__ points) {
-  __shared__ uint32_t wc[4];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const unsigned long long key = i < slots ? keys[i] : DM_EMPTY;
   bool sel = key != DM_EMPTY;
   if (REGION && sel) sel = dm_in_window(key, W);
-  const unsigned long long m = __ballot(sel);
-  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = (uint32_t)__popcll(m);
   if (REGION) dm_wave_sum64(points + (size_t)((i >> 6) & (DM_SEL_SUMS - 1u)) * DM_SEL_STRIDE, sel ? vals[4ull * i] : 0ull);
-  __syncthreads();
-  if (threadIdx.x == 0) blk[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+  const uint32_t n_sel = dm_block_count(sel);
+  if (threadIdx.x == 0) blk[blockIdx.x] = n_sel;
 }
 
 // behind the exclusive scan of those counts each block writes its selected slots at its offset, in slot order (AUX: the slot's miss
@@ -57,18 +54,13 @@ __global__ __launch_bounds__(256) void k_dm_compact(const unsigned long long* __
                                                     unsigned long long* __restrict__ ovals, const uint32_t* __restrict__ aux,
                                                     uint32_t* __restrict__ omiss, const unsigned long long* __restrict__ mom,
                                                     unsigned long long* __restrict__ omom, DmWindow W) {
-  __shared__ uint32_t wc[4];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
   const unsigned long long key = i < slots ? keys[i] : DM_EMPTY;
   bool occ = key != DM_EMPTY;
   if (REGION && occ) occ = dm_in_window(key, W);
-  const unsigned long long m = __ballot(occ);
-  if (lane == 0) wc[wid] = (uint32_t)__popcll(m);
-  __syncthreads();
+  const unsigned long long m = dm_block_vote(occ);
   if (!occ) return;
-  uint32_t pos = blk_off[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wid; w++) pos += wc[w];
+  const uint32_t pos = dm_block_rank(m, blk_off[blockIdx.x]);
   okeys[pos] = key;
   const ulonglong2* s = (const ulonglong2*)(vals + 4ull * i);
   ulonglong2* d = (ulonglong2*)(ovals + 4ull * pos);
@@ -85,19 +77,16 @@ __global__ __launch_bounds__(256) void k_dm_compact(const unsigned long long* __
 
 void DenseMap::compact_of(const DmTable& T, const DmWindow* W, uint64_t occ, Snapshot* S, bool want_mom, uint64_t counts[2]) {
   const uint32_t nblk = (T.slots + 255) / 256;
-  DevBuf<uint32_t> blk, scratch, omiss;
-  DevBuf<unsigned long long> tiles, okeys, ovals, omom, points;
+  DevBuf<uint32_t> blk, omiss;
+  DevBuf<unsigned long long> okeys, ovals, omom, points;
   blk.reserve((size_t)nblk + 1);
-  scratch.reserve(2);
-  tiles.reserve(SCAN_SCRATCH_WORDS / 2);
-  LX_HIP(hipMemsetAsync(tiles.p, 0, sizeof(unsigned long long) * (SCAN_SCRATCH_WORDS / 2), own_));
   uint32_t total = 0;
   if (W) {
     constexpr size_t sum_words = (size_t)DM_SEL_SUMS * DM_SEL_STRIDE;
     points.reserve(sum_words);
     LX_HIP(hipMemsetAsync(points.p, 0, sizeof(unsigned long long) * sum_words, own_));
     hipLaunchKernelGGL(k_dm_count<true>, dim3(nblk), dim3(256), 0, own_, T.keys, T.slots, blk.p, *W, T.vals, points.p);
-    exclusive_scan_u32_n(blk.p, blk.p, (uint32_t*)tiles.p, scratch.p, nblk, own_);
+    scan_.run(blk.p, nblk, own_);
     LX_HIP(hipGetLastError());
     std::vector<unsigned long long> sums(sum_words);
     LX_HIP(hipMemcpyAsync(&total, blk.p + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, own_));
@@ -111,7 +100,7 @@ void DenseMap::compact_of(const DmTable& T, const DmWindow* W, uint64_t occ, Sna
     if (!S) return;
   } else {
     hipLaunchKernelGGL(k_dm_count<false>, dim3(nblk), dim3(256), 0, own_, T.keys, T.slots, blk.p, DmWindow(), nullptr, nullptr);
-    exclusive_scan_u32_n(blk.p, blk.p, (uint32_t*)tiles.p, scratch.p, nblk, own_);
+    scan_.run(blk.p, nblk, own_);
   }
   okeys.reserve(occ + 1);
   ovals.reserve(4 * (occ + 1));

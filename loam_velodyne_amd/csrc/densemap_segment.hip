@@ -6,16 +6,12 @@
 //   k_dm_seg_select   parent[slot] = slot for a selected voxel, NONE otherwise; counts the selected.
 //   k_dm_seg_link     per selected slot, the forward half of its neighbourhood (the offsets that are lexicographically positive in
 //                     (dz, dy, dx): 3, 9 or 13 of them); the index-range test comes before the neighbour's key is formed; dm_find, and
-//                     a union when the neighbour is selected.  The union-find is lock-free over parent[]: find both roots, hook the
-//                     root with the LARGER key under the one with the smaller by atomicCAS(&parent[hi], hi, lo), and start again from
-//                     the finds when the CAS loses.  Along every parent chain the key decreases strictly, so there are no cycles, every
-//                     loop ends without waiting for another thread (a lost CAS means that slot stopped being a root, which happens once
-//                     per slot), and the root of a finished component is its smallest key whatever the slot layout.  find halves the
-//                     paths it walks: a slot that is not a root never becomes one again and any ancestor is a valid parent.  No
-//                     spin-wait, no grid barrier; every word of parent[] that another workgroup may write in the launch is read and
-//                     written with agent-scope atomics.
-//   k_dm_seg_flatten  parent[slot] = root, and the roots and the occupied slots of each 256-slot block counted (ballot), as k_dm_count
-//                     does; the scans of the two count runs give every root a compact id and every voxel its place in slot order.
+//                     a union when the neighbour is selected: the lock-free union-find of densemap_label.hpp over parent[] in HBM
+//                     (agent scope; the argument for it is there), a slot's rank being its KEY, so that the root of a finished
+//                     component is its smallest key whatever the slot layout.  The bound of every loop is the number of slots; one
+//                     that is reached raises ctr[3], and the host reports LOAMX_E_INTERNAL.
+//   k_dm_seg_flatten  parent[slot] = root, and the roots and the occupied slots of each 256-slot block counted (dm_block_count2);
+//                     the scans of the two count runs give every root a compact id and every voxel its place in slot order.
 //   k_dm_seg_ids      a root writes its id and the empty accumulator of its component (min_key = its own key).
 //   k_dm_seg_reduce   per selected voxel: voxels, points and the three index sums by 64-bit integer adds, the box by 32-bit signed min
 //                     and max: integer, commutative, exact.  With labels it also writes (key, id) of every occupied slot, compacted.
@@ -29,17 +25,17 @@
 //
 // The host orders the results, as loamx_densemap_download does: components by min_key, voxels by key; it applies min_voxels, maps compact
 // ids to ranks and fills the labels.  Compact ids follow the slot layout and never leave this file.
+#include "densemap_label.hpp"
 #include "densemap_map.hpp"
 #include "pinned_copy.hpp"
-#include "scan.hpp"
 #include <algorithm>
 #include <climits>
 #include <numeric>
 
 namespace loamx {
 
-constexpr uint32_t DM_SEG_NONE = 0xffffffffu;
-constexpr int DM_SEG_LDS = 256;   // entries of k_dm_seg_reduce's table: the block's threads, the most ids it can meet
+constexpr uint32_t DM_SEG_NONE = DM_UF_NONE;
+constexpr int DM_SEG_AGENT = __HIP_MEMORY_SCOPE_AGENT;   // parent[] is in HBM: other workgroups of the launch hook into it
 
 struct DmSegArgs {
   uint32_t which, maxsum, min_points;   // maxsum: 1, 2 or 3, the largest |dx| + |dy| + |dz| of a neighbour
@@ -52,7 +48,6 @@ __device__ inline void dm_seg_indices(unsigned long long key, int ia[3]) {
 #pragma unroll
   for (int a = 0; a < 3; a++) ia[a] = (int)((uint32_t)(key >> (DM_KBITS * a)) & km) - (1 << DM_QBITS);
 }
-__device__ inline uint32_t dm_seg_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ __launch_bounds__(256) void k_dm_seg_select(DmSegArgs G, const unsigned long long* __restrict__ keys,
                                                        const unsigned long long* __restrict__ vals, const uint32_t* __restrict__ aux,
@@ -74,25 +69,14 @@ __global__ __launch_bounds__(256) void k_dm_seg_select(DmSegArgs G, const unsign
   if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(&ctr[0], (unsigned long long)__popcll(m));
 }
 
-// the root above x, halving the path on the way (x is selected: every word on the chain is a slot)
-__device__ inline uint32_t dm_seg_find(uint32_t* parent, uint32_t x) {
-  for (;;) {
-    const uint32_t p = dm_seg_load(&parent[x]);
-    if (p == x) return x;
-    const uint32_t g = dm_seg_load(&parent[p]);
-    if (g == p) return p;
-    __hip_atomic_store(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (x is no root and stays none: g is an ancestor)
-    x = g;
-  }
-}
-
+// ctr: [0] voxels selected, [1] hooks lost, [2] the two totals (k_dm_seg_totals), [3] a loop bound was reached
 __global__ __launch_bounds__(256) void k_dm_seg_link(uint32_t maxsum, const unsigned long long* __restrict__ keys, uint32_t slots, uint32_t mask,
                                                      uint32_t shift, uint32_t* parent, unsigned long long* __restrict__ ctr) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= slots || dm_seg_load(&parent[i]) == DM_SEG_NONE) return;
+  if (i >= slots || dm_uf_load<DM_SEG_AGENT>(&parent[i]) == DM_SEG_NONE) return;
   int ia[3];
   dm_seg_indices(keys[i], ia);
-  uint32_t lost = 0;
+  uint32_t lost = 0u, bad = 0u;
   for (int o = 14; o < 27; o++) {   // (dz, dy, dx) lexicographically positive
     const int dx = o % 3 - 1, dy = (o / 3) % 3 - 1, dz = o / 9 - 1;
     if ((uint32_t)((dx != 0) + (dy != 0) + (dz != 0)) > maxsum) continue;
@@ -101,44 +85,37 @@ __global__ __launch_bounds__(256) void k_dm_seg_link(uint32_t maxsum, const unsi
     if (nx < -lim || nx > lim || ny < -lim || ny > lim || nz < -lim || nz > lim) continue;   // no such voxel: not looked up
     uint32_t nb = 0;
     if (dm_find(keys, mask, shift, dm_key(nx, ny, nz), nb) != 1) continue;
-    if (dm_seg_load(&parent[nb]) == DM_SEG_NONE) continue;
-    uint32_t a = i, b = nb;
-    for (;;) {
-      a = dm_seg_find(parent, a);
-      b = dm_seg_find(parent, b);
-      if (a == b) break;
-      if (keys[a] < keys[b]) { const uint32_t t = a; a = b; b = t; }   // a: the root with the larger key
-      if (atomicCAS(&parent[a], a, b) == a) break;
-      lost++;   // (a was hooked by another thread meanwhile: from the finds again)
-    }
+    if (dm_uf_load<DM_SEG_AGENT>(&parent[nb]) == DM_SEG_NONE) continue;
+    if (!dm_uf_union<DM_SEG_AGENT>(parent, i, nb, slots, [keys](uint32_t s) { return keys[s]; }, lost)) bad = 1u;
   }
   if (lost) atomicAdd(&ctr[1], (unsigned long long)lost);
+  if (bad) atomicOr(&ctr[3], 1ull);
 }
 
 __global__ __launch_bounds__(256) void k_dm_seg_flatten(const unsigned long long* __restrict__ keys, uint32_t slots, uint32_t* parent,
-                                                        uint32_t* __restrict__ blk_roots, uint32_t* __restrict__ blk_occ) {
-  __shared__ uint32_t wr[4], wo[4];
+                                                        uint32_t* __restrict__ blk_roots, uint32_t* __restrict__ blk_occ,
+                                                        unsigned long long* __restrict__ ctr) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   bool occ = false, root = false;
   if (i < slots) {
     occ = keys[i] != DM_EMPTY;
-    uint32_t x = dm_seg_load(&parent[i]);
+    const uint32_t x = dm_uf_load<DM_SEG_AGENT>(&parent[i]);
     if (x != DM_SEG_NONE) {
       root = x == i;
-      for (uint32_t p = dm_seg_load(&parent[x]); p != x; p = dm_seg_load(&parent[x])) x = p;   // (keys decrease along the chain: it ends)
-      if (!root) __hip_atomic_store(&parent[i], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint32_t r = dm_uf_root<DM_SEG_AGENT>(parent, x, slots);
+      if (r == DM_SEG_NONE) atomicOr(&ctr[3], 1ull);
+      else if (!root) __hip_atomic_store(&parent[i], r, __ATOMIC_RELAXED, DM_SEG_AGENT);
     }
   }
-  const unsigned long long mr = __ballot(root), mo = __ballot(occ);
-  if ((threadIdx.x & 63) == 0) { wr[threadIdx.x >> 6] = (uint32_t)__popcll(mr); wo[threadIdx.x >> 6] = (uint32_t)__popcll(mo); }
-  __syncthreads();
+  uint32_t n_roots, n_occ;
+  dm_block_count2(root, occ, n_roots, n_occ);
   if (threadIdx.x == 0) {
-    blk_roots[blockIdx.x] = wr[0] + wr[1] + wr[2] + wr[3];
-    blk_occ[blockIdx.x] = wo[0] + wo[1] + wo[2] + wo[3];
+    blk_roots[blockIdx.x] = n_roots;
+    blk_occ[blockIdx.x] = n_occ;
   }
 }
 
-// the two totals of the scans beside the two counters: the six words that go back before the second half is sized
+// the two totals of the scans beside the counters: the eight words that go back before the second half is sized
 __global__ void k_dm_seg_totals(const uint32_t* __restrict__ total_roots, const uint32_t* __restrict__ total_occ, unsigned long long* __restrict__ ctr) {
   if (threadIdx.x == 0 && blockIdx.x == 0) ctr[2] = (unsigned long long)*total_roots | ((unsigned long long)*total_occ << 32);
 }
@@ -147,16 +124,11 @@ __global__ void k_dm_seg_totals(const uint32_t* __restrict__ total_roots, const 
 __global__ __launch_bounds__(256) void k_dm_seg_ids(const unsigned long long* __restrict__ keys, uint32_t slots, const uint32_t* __restrict__ parent,
                                                     const uint32_t* __restrict__ off_roots, uint32_t n_roots, uint32_t* __restrict__ rootid,
                                                     loamx_segment* __restrict__ acc) {
-  __shared__ uint32_t wc[4];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = (int)(threadIdx.x & 63), wid = (int)(threadIdx.x >> 6);
   const bool root = i < slots && parent[i] == i;
-  const unsigned long long m = __ballot(root);
-  if (lane == 0) wc[wid] = (uint32_t)__popcll(m);
-  __syncthreads();
+  const unsigned long long m = dm_block_vote(root);
   if (!root) return;
-  uint32_t id = off_roots[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wid; w++) id += wc[w];
+  const uint32_t id = dm_block_rank(m, off_roots[blockIdx.x]);
   if (id >= n_roots) return;   // (cannot happen: the scan counted these roots)
   rootid[i] = id;
   loamx_segment s;
@@ -171,12 +143,11 @@ __global__ __launch_bounds__(256) void k_dm_seg_reduce(const unsigned long long*
                                                        uint32_t slots, const uint32_t* __restrict__ parent, const uint32_t* __restrict__ rootid,
                                                        uint32_t n_roots, loamx_segment* __restrict__ acc, const uint32_t* __restrict__ off_occ,
                                                        uint32_t n_occ, unsigned long long* __restrict__ okeys, uint32_t* __restrict__ oids) {
-  __shared__ uint32_t s_id[DM_SEG_LDS];
-  __shared__ unsigned long long s_sum[DM_SEG_LDS][5];   // voxels, points, sum_idx
-  __shared__ int s_box[DM_SEG_LDS][6];                  // lo, hi
-  __shared__ uint32_t wc[4];
+  __shared__ uint32_t s_id[DM_LDS_IDS];
+  __shared__ unsigned long long s_sum[DM_LDS_IDS][5];   // voxels, points, sum_idx
+  __shared__ int s_box[DM_LDS_IDS][6];                  // lo, hi
   const uint32_t t = threadIdx.x, i = blockIdx.x * blockDim.x + t;
-  const int lane = (int)(t & 63), wid = (int)(t >> 6);
+  const int lane = (int)(t & 63);
   s_id[t] = DM_SEG_NONE;
 #pragma unroll
   for (int k = 0; k < 5; k++) s_sum[t][k] = 0ull;
@@ -193,12 +164,10 @@ __global__ __launch_bounds__(256) void k_dm_seg_reduce(const unsigned long long*
   }
   if (id != DM_SEG_NONE && id >= n_roots) id = DM_SEG_NONE;   // (cannot happen: every root got an id below n_roots)
   const bool occ = key != DM_EMPTY, sel = id != DM_SEG_NONE;
-  const unsigned long long mo = __ballot(occ);
-  if (LABELS && lane == 0) wc[wid] = (uint32_t)__popcll(mo);
-  __syncthreads();
+  unsigned long long mo = 0ull;   // (the one barrier behind the table's initial values, with labels in the vote, without on its own)
+  if (LABELS) mo = dm_block_vote(occ); else __syncthreads();
   if (LABELS && occ) {
-    uint32_t pos = off_occ[blockIdx.x] + (uint32_t)__popcll(mo & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wid; w++) pos += wc[w];
+    const uint32_t pos = dm_block_rank(mo, off_occ[blockIdx.x]);
     if (pos < n_occ) { okeys[pos] = key; oids[pos] = id; }
   }
   // this lane's contribution (the identities when it is not selected)
@@ -232,12 +201,7 @@ __global__ __launch_bounds__(256) void k_dm_seg_reduce(const unsigned long long*
     }
   }
   if (put) {
-    uint32_t h = id & (DM_SEG_LDS - 1);
-    for (int probe = 0; probe < DM_SEG_LDS; probe++) {
-      const uint32_t prev = atomicCAS(&s_id[h], DM_SEG_NONE, id);
-      if (prev == DM_SEG_NONE || prev == id) break;
-      h = (h + 1u) & (DM_SEG_LDS - 1);
-    }
+    const uint32_t h = dm_lds_claim(s_id, id);
 #pragma unroll
     for (int k = 0; k < 5; k++) atomicAdd(&s_sum[h][k], sum[k]);
 #pragma unroll
@@ -258,19 +222,14 @@ __global__ __launch_bounds__(256) void k_dm_seg_reduce(const unsigned long long*
 }
 
 void DmSegment::run(const DmTable& T, const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint64_t occ,
-                    bool want_labels, std::vector<uint32_t>& labels, std::vector<loamx_segment>& segs, uint64_t stats[6], hipStream_t st,
-                    std::vector<uint32_t>* rank_of_id) {
+                    bool want_labels, std::vector<uint32_t>& labels, std::vector<loamx_segment>& segs, uint64_t stats[6], DmScan& scan_state,
+                    hipStream_t st, std::vector<uint32_t>* rank_of_id) {
   const uint32_t slots = T.slots, nblk = (slots + 255u) / 256u;
   parent_.reserve(slots);
   rootid_.reserve(slots);
   blk_.reserve(2 * ((size_t)nblk + 1));
-  scratch_.reserve(2);
-  ctr_.reserve(3);
-  h_tot_.reserve(6);
-  if (!tiles_.p) {
-    tiles_.reserve(chained_scan_state_words());
-    LX_HIP(hipMemsetAsync(tiles_.p, 0, sizeof(unsigned long long) * tiles_.cap, st));
-  }
+  ctr_.reserve(4);
+  h_tot_.reserve(8);
   uint32_t *blk_roots = blk_.p, *blk_occ = blk_.p + nblk + 1;
   DmSegArgs G;
   G.which = c.which;
@@ -279,19 +238,20 @@ void DmSegment::run(const DmTable& T, const loamx_densemap_segment_config& c, co
   for (int a = 0; a < 3; a++) { G.lo[a] = c.lo[a]; G.hi[a] = c.hi[a]; }
   G.rule = rule;
   const dim3 scan(nblk), block(256);
-  LX_HIP(hipMemsetAsync(ctr_.p, 0, sizeof(unsigned long long) * 2, st));
+  LX_HIP(hipMemsetAsync(ctr_.p, 0, sizeof(unsigned long long) * 4, st));
   hipLaunchKernelGGL(k_dm_seg_select, scan, block, 0, st, G, T.keys, T.vals, T.aux, slots, parent_.p, ctr_.p);
   hipLaunchKernelGGL(k_dm_seg_link, scan, block, 0, st, G.maxsum, T.keys, slots, T.mask(), T.shift(), parent_.p, ctr_.p);
-  hipLaunchKernelGGL(k_dm_seg_flatten, scan, block, 0, st, T.keys, slots, parent_.p, blk_roots, blk_occ);
-  exclusive_scan_u32_n(blk_roots, blk_roots, (uint32_t*)tiles_.p, scratch_.p, nblk, st);   // ([nblk]: the total)
-  exclusive_scan_u32_n(blk_occ, blk_occ, (uint32_t*)tiles_.p, scratch_.p, nblk, st);
+  hipLaunchKernelGGL(k_dm_seg_flatten, scan, block, 0, st, T.keys, slots, parent_.p, blk_roots, blk_occ, ctr_.p);
+  scan_state.run(blk_roots, nblk, st);   // ([nblk]: the total)
+  scan_state.run(blk_occ, nblk, st);
   hipLaunchKernelGGL(k_dm_seg_totals, dim3(1), dim3(64), 0, st, blk_roots + nblk, blk_occ + nblk, ctr_.p);
   LX_HIP(hipGetLastError());
-  store_to_pinned_u32(h_tot_.p, (const uint32_t*)ctr_.p, 6, st);
+  store_to_pinned_u32(h_tot_.p, (const uint32_t*)ctr_.p, 8, st);
   LX_HIP(hipStreamSynchronize(st));
   scan_check_errors();
   const uint64_t selected = h_tot_.p[0] | ((uint64_t)h_tot_.p[1] << 32), lost = h_tot_.p[2] | ((uint64_t)h_tot_.p[3] << 32);
   const uint32_t n_roots = h_tot_.p[4];
+  if (h_tot_.p[6]) throw Error(LOAMX_E_INTERNAL, "segment: a union-find loop reached its bound");
   if (h_tot_.p[5] != occ) throw Error(LOAMX_E_INTERNAL, "segment: the compaction disagrees with the occupancy count");
   if (n_roots > selected) throw Error(LOAMX_E_INTERNAL, "segment: more components than selected voxels");
 
@@ -369,7 +329,7 @@ int DenseMap::segment(const loamx_densemap_segment_config& c, const loamx_densem
   std::vector<uint32_t> lab;
   std::vector<loamx_segment> sg;
   uint64_t s[6] = {0, 0, 0, 0, 0, 0};
-  if (occ) seg_.run(tab_, c, rule, occ, labels != nullptr, lab, sg, s, own_);
+  if (occ) seg_.run(tab_, c, rule, occ, labels != nullptr, lab, sg, s, scan_, own_);
   *n_voxels = occ;
   *n_segs = sg.size();
   if ((labels && label_capacity < occ) || (segs && seg_capacity < sg.size())) return LOAMX_E_CAPACITY;

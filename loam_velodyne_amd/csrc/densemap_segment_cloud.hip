@@ -116,15 +116,6 @@ __global__ __launch_bounds__(256) void k_dm_cseg_labels(const unsigned long long
   ids[i] = id;
 }
 
-const float4* DmSegCloud::stage(const loamx_cloud* c, hipStream_t st) {
-  const uint32_t n = c->count;
-  h_pts_.reserve(n);
-  pack_cloud(c, h_pts_.p);
-  d_pts_.reserve(n);
-  fetch_from_pinned(d_pts_.p, h_pts_.p, n, st);
-  return d_pts_.p;
-}
-
 void DmSegCloud::insert(const DmTable& M, const DmFilter& F, const loamx_densemap_segment_cloud_config& c, const loamx_densemap_static_rule* rule,
                         const float4* pts, uint32_t n, hipStream_t st, uint64_t counts[5]) {
   LX_REQUIRE(n <= (1u << 30), "points: more than 2^30 points in one cloud");   // (the scratch table indexes 2^31 slots)
@@ -197,7 +188,7 @@ int DenseMap::segment_cloud(const float4* pts, uint32_t n, const float origin[3]
       sc.connectivity = c.connectivity; sc.min_points = c.min_points; sc.min_voxels = c.min_voxels;
       for (int a = 0; a < 3; a++) { sc.lo[a] = c.lo[a]; sc.hi[a] = c.hi[a]; }
       uint64_t ss[6];
-      seg_.run(cseg_.table(), sc, loamx_densemap_static_rule{0u, 0u, 0u}, s[5], false, none, sg, ss, own_, &rank);
+      seg_.run(cseg_.table(), sc, loamx_densemap_static_rule{0u, 0u, 0u}, s[5], false, none, sg, ss, scan_, own_, &rank);
       s[6] = ss[0]; s[7] = ss[1]; s[8] = ss[2]; s[9] = ss[3]; s[10] = ss[4]; s[12] = ss[5];
       for (const loamx_segment& g : sg) s[11] += g.points;   // (a voxel's n counts the entered points in it)
       if (labels && label_capacity >= n && !(segs && seg_capacity < sg.size())) ids = cseg_.ids(seg_, (uint32_t)rank.size(), n, own_);
@@ -227,7 +218,7 @@ int DenseMap::segment_cloud_host(const loamx_cloud* points, const float origin[3
   check_cloud(points, false);
   LX_HIP(hipSetDevice(cfg.device));
   wait_adds();
-  const float4* pts = points->count ? cseg_.stage(points, own_) : nullptr;
+  const float4* pts = points->count ? cseg_.cloud.stage(points, own_) : nullptr;
   return segment_cloud(pts, points->count, origin, c, rule, labels, label_capacity, n_points, segs, seg_capacity, n_segs, stats);
 }
 

@@ -9,8 +9,13 @@ import numpy as np
 import pytest
 
 import densemap_carve_model as cm
+import densemap_file_model as flm
+import densemap_frontier_model as frm
 import densemap_model as dm
 import densemap_raycast_model as rm
+import densemap_region_model as rgm
+import densemap_route_model as rtm
+import densemap_segment_cloud_model as scm
 import densemap_segment_model as sm
 from loam_velodyne_amd import loamx
 
@@ -328,7 +333,57 @@ def test_call_grow_call():
     check(d, m, connectivity=26)
 
 
-# ---- 9: the outputs and the refusals ---------------------------------------------------------------------------------------------------------------
+# ---- 9: one scan state behind the region export, both labellers and the download of one handle ----------------------------------------------------
+def test_one_scan_state_serves_every_user_of_a_handle():
+    """download_region, segment, frontiers_cells, segment_cloud and download in turn on one handle, twice over and once more after the
+    table has grown: the three users of the handle's chained-scan state (the region's compaction, the segments' two scans, the
+    frontiers' scan) follow each other at four blocks of slots and five of cells, and every result equals its model"""
+    cells = serpentine(rows=12)   # 299 voxels in 1,024 slots: four blocks of 256
+    d, m = pair_of(cells)
+    assert d.rehashes == 0 and d.stats()["slots"] == 1024
+    rng = np.random.default_rng(33)
+    cls = rng.choice(4, size=(33, 33), p=[0.25, 0.6, 0.1, 0.05])   # 2 x 2 tiles; 1,089 cells: five blocks of 256, the last of 65
+    clear2 = rng.integers(1, 30, size=(33, 33))
+    clear2[cls >= frm.gm.OBSTACLE] = 0
+    grid = rtm.cells_of(cls, clear2)
+    want_fr = frm.frontiers(grid, dict(connectivity=8))[:3]
+    assert want_fr[2][1] >= 2    # (several frontiers)
+    # two sheets three cells above the map (new: they enter, before and after the growth) and a row that touches it (known: rejected)
+    cloud = sm.points_of_cells([(x, y, 3) for x in range(24) for y in range(12) if y != 5] + [(x, 0, 1) for x in range(24)], LEAF)
+    reg = rgm.region([-rgm.IMAX] * 3, [11, rgm.IMAX, rgm.IMAX])   # x index <= 11: half of every row
+    hr = loamx.DenseMapRegion(reg["lo"], reg["hi"], reg["side"])
+
+    def round_():
+        """one round against the models; every word it produced but the two schedule-dependent 'hooks lost' statistics"""
+        sel = rgm.select(flm.records_of(m), reg)
+        assert 0 < len(sel["keys"]) < len(m)
+        got = [d.region_points(hr).tobytes()]
+        assert got[-1] == dm.export(sel["keys"], sel["vals"], LEAF).tobytes()
+        labels, segs, st = check(d, m, connectivity=6)
+        got += [labels.tobytes(), segs.tobytes(), [st[k] for k in sm.STAT_KEYS]]
+        lab, out = d.frontiers_cells(grid, connectivity=8)
+        fst = d.frontier_stats
+        assert out.tobytes() == want_fr[0].tobytes() and lab.tobytes() == want_fr[1].tobytes()
+        assert tuple(fst[k] for k in loamx.FRONTIER_STATS[:5]) == want_fr[2]
+        got += [lab.tobytes(), out.tobytes(), [fst[k] for k in loamx.FRONTIER_STATS[:5]]]
+        cl, cs, cst = d.segment_cloud(cloud, ORIGIN)
+        wl, ws, wst, _ = scm.segment_cloud(m, cloud, ORIGIN, None)
+        assert cl.tobytes() == wl.tobytes() and cs.tobytes() == ws.tobytes() and {k: cst[k] for k in scm.STAT_KEYS} == wst
+        assert (wst["entered"], wst["rejected"], wst["components"]) == (24 * 11, 24, 2)
+        got += [cl.tobytes(), cs.tobytes(), [cst[k] for k in scm.STAT_KEYS]]
+        got.append(d.points().tobytes())
+        assert got[-1] == m.points().tobytes()
+        return got
+
+    first = round_()
+    assert round_() == first
+    more = sweeps_of([(x, y, 1) for x in range(24) for y in range(0, 40, 2)])   # one larger add: the table grows
+    feed(d, more), feed(m, more)
+    assert d.rehashes >= 1 and d.stats()["slots"] > 1024 and len(d) == len(m) == 299 + 480
+    assert round_() != first
+
+
+# ---- 10: the outputs and the refusals ---------------------------------------------------------------------------------------------------------------
 def raw(d, cfg=None, rule=None, n_lab=None, n_seg=None, lab_cap=None, seg_cap=None, null=()):
     """loamx_densemap_segment itself, every output pre-filled with a pattern: (rc, n_voxels, n_segs, stats, labels, segs);
     n_lab / n_seg None: that output is NULL; null: the names of pointer arguments to pass as NULL"""
