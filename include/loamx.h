@@ -1239,6 +1239,66 @@ int loamx_densemap_rebuild(loamx_densemap* h, const double* corrections /* 12 * 
                            uint64_t n_calls);
 int loamx_densemap_get_rebuild_stats(loamx_densemap* h, uint64_t stats[4]);
 
+/* Snapshots built on the device, and snapshots of a window of the sweep log (optional: a handle that never calls these runs the
+ * kernels it ran, allocates what it allocated and exports the same bytes).  loamx_densemap_freeze brings every voxel's thirteen words
+ * to the host, computes the surfels there and sends them back, and what it freezes is always the whole map.  Here the surfels are
+ * computed where the words lie, and a snapshot can be made of the sweeps j - w .. j + w of the log alone: a loamx_place match (i, j)
+ * becomes freeze_history of the window around j, align_many_from_history of sweep i, and one edge j -> i of the pose graph, without a
+ * point crossing to the host.
+ *
+ * The surfel on the device.  Kernel k_dm_surfels, one thread per slot of a table of the map's format: an occupied slot that the rule
+ * does not call dynamic computes its surfel by the definition of "Second moments and surfels" with the host's own operations in the
+ * host's order — f64 + - * / sqrt, comparisons, integer -> double conversions (the 128-bit one written out: nearest, ties to even)
+ * and one f64 -> f32 rounding per output, no fused multiply-add — each of which is correctly rounded on either side, so the six f32 of
+ * an entry are the bytes loamx_densemap_download_surfels gives.  The voxels that have a surfel take consecutive places of two device
+ * arrays (key; six f32) through one counter, one atomic per wave; the host reads the count (8 bytes), sizes the snapshot's table by
+ * the rule of loamx_densemap_freeze and fills it from the arrays.  The order of the arrays, and with it the slot an entry lands in
+ * among the slots of its probe sequence, depends on the schedule; the SET of entries does not, and no alignment word depends on
+ * the placement.
+ *
+ * loamx_densemap_freeze_device: loamx_densemap_freeze with the surfels computed on the device — the same preconditions, waits,
+ * refusals and side effects (level 0 is replaced, the coarse levels go, the selection returns to level 0) and the same set of
+ * (key, six f32) entries, byte for byte.  loamx_densemap_freeze_pyramid_device: the same for loamx_densemap_freeze_pyramid; the
+ * cascade's level tables are read where they stand instead of being downloaded.
+ *
+ * loamx_densemap_freeze_history(h, first_call, n_calls, corrections, cfg, n_surfels): needs history and moments.  The logged calls
+ * [first_call, first_call + n_calls) are replayed by the kernel of loamx_densemap_rebuild, call k OF THE WINDOW under
+ * corrections[12 k ..] (NULL: every correction the identity; the checks and the f32 rounding are rebuild's), into a scratch table of
+ * the map's format with moment words, no carve words and counters of its own, sized as a rebuild sizes its attempts (doubled on the
+ * "too small" word); k_dm_surfels runs on it without a rule, level 0 is built from the result and the scratch table is freed.
+ * Afterwards level 0 is the snapshot that a fresh handle of the same loamx_densemap_config with moments on would hold after
+ * add(correct(C_k, points_k), correct(C_k, origin_k)) for the window's calls followed by loamx_densemap_freeze(cfg, NULL); the coarse
+ * levels go and the selection returns to level 0 as after any freeze.  The live map, its statistics (rebuild's included), its log and
+ * its carve words are not touched.  LOAMX_E_INVALID with a message that names the argument: no history, no moments, n_calls == 0, a
+ * window that reaches beyond the log, a non-finite correction entry.  LOAMX_E_CAPACITY: with max_voxels, the window holds more voxels
+ * than the cap.  After any refusal or failure, a failed allocation included, the old snapshot stands.
+ *
+ * loamx_densemap_download_frozen: the entries of snapshot level `level` in ascending key order, keys[i] and rec[6 i ..] = mean x, y,
+ * z, normal x, y, z.  *n = entries; LOAMX_E_CAPACITY, nothing written, when capacity < *n (keys, rec may be NULL with capacity 0);
+ * LOAMX_E_INVALID for a level that does not stand.
+ *
+ * loamx_densemap_align_from_history, _many_from_history, _pyramid_from_history: the from_* forms of loamx_densemap_align,
+ * loamx_densemap_align_many and loamx_densemap_align_pyramid on the points of logged call `call` where they lie in the log, behind
+ * the adds, with the call's logged origin as the centre.  Every result is byte for byte what the host-fed form returns for the cloud
+ * and origin of loamx_densemap_history_download(call) with centre = that origin (pose_in NULL: the identity, as for the other from_*
+ * forms).  LOAMX_E_INVALID: no history, a call beyond the log, no snapshot, and whatever the host-fed form refuses. */
+int loamx_densemap_freeze_device(loamx_densemap* h, const loamx_densemap_surfel_config* cfg, const loamx_densemap_static_rule* rule,
+                                 uint64_t* n_surfels);
+int loamx_densemap_freeze_pyramid_device(loamx_densemap* h, const loamx_densemap_surfel_config* cfg, const loamx_densemap_static_rule* rule,
+                                         const loamx_densemap_pyramid_config* pyramid /* NULL: the defaults */, uint64_t* n_surfels /* levels */);
+int loamx_densemap_freeze_history(loamx_densemap* h, uint64_t first_call, uint64_t n_calls,
+                                  const double* corrections /* 12 * n_calls; NULL: every call the identity */,
+                                  const loamx_densemap_surfel_config* cfg, uint64_t* n_surfels);
+int loamx_densemap_download_frozen(loamx_densemap* h, uint32_t level, uint64_t* keys, float* rec /* 6 per entry */, uint64_t capacity,
+                                   uint64_t* n);
+int loamx_densemap_align_from_history(loamx_densemap* h, uint64_t call, const double pose_in[12] /* NULL: identity */,
+                                      const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out);
+int loamx_densemap_align_many_from_history(loamx_densemap* h, uint64_t call, const double* poses_in, uint32_t n_poses,
+                                           const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out, uint32_t* best);
+int loamx_densemap_align_pyramid_from_history(loamx_densemap* h, uint64_t call, const double pose_in[12],
+                                              const loamx_densemap_align_config* cfg, uint32_t first_level,
+                                              loamx_densemap_align_result* out /* first_level + 1 */);
+
 /* Navigation grid (optional: a handle that never calls loamx_densemap_grid runs the kernels it ran, allocates what it allocated and
  * exports the same bytes).  "Where can I drive?": a window of the map projected along the up axis to a 2-D grid of ground height,
  * obstacle count, overhead clearance, class and squared distance to the nearest obstacle, computed on the device from the table

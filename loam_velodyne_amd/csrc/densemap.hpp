@@ -185,6 +185,10 @@ class DmFrozen {
   void drop();
   // replaces the snapshot by the n voxels (keys[i], rec[6 * i ..]); blocks until the table stands
   void build(const unsigned long long* keys, const float* rec, size_t n, hipStream_t st);
+  // the same from arrays that lie on the device, written by work enqueued on st (k_dm_surfels, densemap_freeze.hip): no upload
+  void build_device(const unsigned long long* d_keys, const float* d_rec, size_t n, hipStream_t st);
+  // the entries on the host in ascending key order: keys[i], rec[6 * i ..]; blocks
+  void download(std::vector<unsigned long long>& keys, std::vector<float>& rec, hipStream_t st) const;
   // the cloud of the steps that follow, checked and staged from the host, enqueued on st
   const float4* stage(const loamx_cloud* c, hipStream_t st) { check_cloud(c, false); return pts_.stage(c, st); }
   // one linearisation (include/loamx.h, loamx_densemap_align_step); blocks until the 33 words are back

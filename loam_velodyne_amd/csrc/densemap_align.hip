@@ -17,6 +17,7 @@
 // to the kernels a level is another table and another inv.  loamx_densemap_align_pyramid is the single loop per level, coarse to
 // fine, over a cloud staged once through level 0's buffers.
 #include "densemap_map.hpp"
+#include <algorithm>
 
 namespace loamx {
 
@@ -112,23 +113,30 @@ void DmFrozen::drop() {
 }
 
 void DmFrozen::build(const unsigned long long* keys, const float* rec, size_t n, hipStream_t st) {
+  DevBuf<unsigned long long> d_keys;
+  DevBuf<float> d_rec;
+  if (n) {
+    d_keys.reserve(n);
+    d_rec.reserve(6 * n);
+    LX_HIP(hipMemcpyAsync(d_keys.p, keys, sizeof(unsigned long long) * n, hipMemcpyHostToDevice, st));
+    LX_HIP(hipMemcpyAsync(d_rec.p, rec, sizeof(float) * 6 * n, hipMemcpyHostToDevice, st));
+  }
+  build_device(d_keys.p, d_rec.p, n, st);   // (blocks: the two blocks are read before they go)
+}
+
+void DmFrozen::build_device(const unsigned long long* d_keys, const float* d_rec, size_t n, hipStream_t st) {
   const uint64_t slots = dm_slots_for(1024, n);
   LX_REQUIRE(slots <= (1ull << 31), "dense map: more surfels than the snapshot can index");
   DmFrozenEntry* tab = nullptr;
   LX_HIP(hipMalloc((void**)&tab, sizeof(DmFrozenEntry) * slots));
   try {
-    DevBuf<unsigned long long> d_keys, d_flag;
-    DevBuf<float> d_rec;
+    DevBuf<unsigned long long> d_flag;
     d_flag.reserve(1);
     unsigned long long flag = 0ull;
     LX_HIP(hipMemsetAsync(tab, 0xff, sizeof(DmFrozenEntry) * slots, st));   // (every key EMPTY; a free slot's payload is never read)
     LX_HIP(hipMemsetAsync(d_flag.p, 0, sizeof(unsigned long long), st));
     if (n) {
-      d_keys.reserve(n);
-      d_rec.reserve(6 * n);
-      LX_HIP(hipMemcpyAsync(d_keys.p, keys, sizeof(unsigned long long) * n, hipMemcpyHostToDevice, st));
-      LX_HIP(hipMemcpyAsync(d_rec.p, rec, sizeof(float) * 6 * n, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_dm_freeze_insert, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, d_keys.p, d_rec.p, (uint32_t)n, tab,
+      hipLaunchKernelGGL(k_dm_freeze_insert, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, d_keys, d_rec, (uint32_t)n, tab,
                          (uint32_t)(slots - 1), 64u - log2u(slots), d_flag.p);
       LX_HIP(hipGetLastError());
     }
@@ -143,6 +151,26 @@ void DmFrozen::build(const unsigned long long* keys, const float* rec, size_t n,
   tab_ = tab;
   slots_ = (uint32_t)slots;
   count_ = n;
+}
+
+// the entries of the snapshot on the host in ascending key order (include/loamx.h, loamx_densemap_download_frozen); blocks
+void DmFrozen::download(std::vector<unsigned long long>& keys, std::vector<float>& rec, hipStream_t st) const {
+  LX_REQUIRE(valid(), "nothing is frozen (loamx_densemap_freeze)");
+  std::vector<DmFrozenEntry> tab(slots_);
+  LX_HIP(hipMemcpyAsync(tab.data(), tab_, sizeof(DmFrozenEntry) * slots_, hipMemcpyDeviceToHost, st));
+  LX_HIP(hipStreamSynchronize(st));
+  std::vector<uint32_t> idx;
+  idx.reserve(count_);
+  for (uint32_t i = 0; i < slots_; i++)
+    if (tab[i].key != DM_EMPTY) idx.push_back(i);
+  std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return tab[a].key < tab[b].key; });
+  keys.resize(idx.size());
+  rec.resize(6 * idx.size());
+  for (size_t i = 0; i < idx.size(); i++) {
+    const DmFrozenEntry& e = tab[idx[i]];
+    keys[i] = e.key;
+    for (int k = 0; k < 3; k++) { rec[6 * i + k] = e.mean[k]; rec[6 * i + 3 + k] = e.normal[k]; }
+  }
 }
 
 void DmFrozen::step(const float4* pts, uint32_t n, const float rtc[15], float inv, uint32_t neighbourhood, float max_residual, hipStream_t st,
@@ -645,6 +673,41 @@ int loamx_densemap_align_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uin
     DenseSource s;
     loamx_pipeline_dense_source(p, slot, s);
     return align_from_source(h, s, pose_in, cfg, out);
+  });
+}
+
+// The from_history forms: the cloud is logged call `call` where it lies in the sweep log (DenseMap::history_source waits for the adds),
+// its logged origin the centre; everything else is the from_* forms'
+int loamx_densemap_align_from_history(loamx_densemap* h, uint64_t call, const double pose_in[12], const loamx_densemap_align_config* cfg,
+                                      loamx_densemap_align_result* out) {
+  return guard([&]() {
+    not_null(h, "h");
+    not_null(out, "out");
+    DenseSource s;
+    h->d.history_source(call, s);
+    return align_from_source(h, s, pose_in, cfg, out);
+  });
+}
+
+int loamx_densemap_align_many_from_history(loamx_densemap* h, uint64_t call, const double* poses_in, uint32_t n_poses,
+                                           const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out, uint32_t* best) {
+  return guard([&]() {
+    not_null(h, "h");
+    not_null(out, "out");
+    DenseSource s;
+    h->d.history_source(call, s);
+    return align_many_from_source(h, s, poses_in, n_poses, cfg, out, best);
+  });
+}
+
+int loamx_densemap_align_pyramid_from_history(loamx_densemap* h, uint64_t call, const double pose_in[12], const loamx_densemap_align_config* cfg,
+                                              uint32_t first_level, loamx_densemap_align_result* out) {
+  return guard([&]() {
+    not_null(h, "h");
+    not_null(out, "out");
+    DenseSource s;
+    h->d.history_source(call, s);
+    return align_pyramid_from_source(h, s, pose_in, cfg, first_level, out);
   });
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include "densemap.hpp"
 #include "densemap_history.hpp"
+#include <functional>
 #include <type_traits>
 
 namespace loamx {
@@ -12,6 +13,7 @@ struct DmCarve;
 struct DmCtrAdd;   // densemap_merge.hip
 struct DmWindow;
 struct DmFileHeader;   // densemap_file.hpp
+struct DmSurfelList;   // densemap_freeze.hip
 
 // two runtime booleans as the two std::bool_constant arguments of f: the kernels' feature switches are template parameters
 template <class F> static void dm_dispatch2(bool a, bool b, F&& f) {
@@ -90,6 +92,17 @@ class DenseMap {
   uint32_t frozen_levels() const;
   DmFrozen& level(uint32_t l) { return l ? coarse[l - 1] : frozen; }
   float level_leaf(uint32_t l) const { return cfg.leaf * (float)(1u << l); }   // (one f32 multiply by a power of two)
+
+  // ---- densemap_freeze.hip: snapshots whose surfels are computed on the device (include/loamx.h, loamx_densemap_freeze_device ...).
+  // freeze_device / freeze_pyramid_device: the entries of freeze / freeze_pyramid, from the tables where they lie.  freeze_history:
+  // level 0 from the window [first_call, first_call + n_calls) of the log, call k of the window under corrections[12 * k ..] (NULL:
+  // identities); the map is only read.  history_source: the points of a logged call where they lie, every add waited for
+  uint64_t freeze_device(const loamx_densemap_surfel_config& sc, const loamx_densemap_static_rule* rule);
+  void freeze_pyramid_device(const loamx_densemap_surfel_config& sc, const loamx_densemap_static_rule* rule,
+                             const loamx_densemap_pyramid_config& pc, uint64_t* n_surfels);
+  int freeze_history(uint64_t first_call, uint64_t n_calls, const double* corrections, const loamx_densemap_surfel_config& sc,
+                     uint64_t* n_surfels);
+  void history_source(uint64_t call, DenseSource& s);
 
   // ---- densemap_merge.hip: include/loamx.h, loamx_densemap_save / merge / merge_file and, with `loading`, load
   uint32_t flags() const;   // the features of the handle as the file's flags
@@ -230,9 +243,17 @@ class DenseMap {
   // ---- densemap_pyramid.hip: the levels 1 .. top, each from the one below (level 1 from the map's table, which is only read, without
   // the voxels the rule calls dynamic); out[l - first] = the voxels of level l for l = first .. top.  Waits for the adds; blocks
   void cascade(uint32_t top, const loamx_densemap_static_rule* rule, uint32_t first, std::vector<Snapshot>& out);
+  // the same cascade with each level handed to f where it stands on the device: f(l, the level's table, its voxels) for l = 1 .. top,
+  // everything that wrote the table waited for; the table goes when the level above it has been built
+  void cascade_each(uint32_t top, const loamx_densemap_static_rule* rule, const std::function<void(uint32_t, const DmTable&, uint64_t)>& f);
+  // ---- densemap_freeze.hip
+  void surfel_list(const DmTable& T, uint64_t occ, double leaf, const loamx_densemap_surfel_config& sc, const loamx_densemap_static_rule* rule,
+                   float max_curvature, DmSurfelList& L);
   // ---- densemap_rebuild.hip
   void log_reserve(uint64_t n, hipStream_t st);
   void launch_replay(const DmTable& nt, unsigned long long* nctr);
+  void launch_replay_range(const DmTable& nt, unsigned long long* nctr, const DmReplayCall* d_calls, uint32_t n_calls, uint64_t first,
+                           uint64_t points);
 };
 
 }  // namespace loamx

@@ -69,8 +69,17 @@ __global__ __launch_bounds__(256) void k_dm_coarsen(const unsigned long long* __
 }
 
 void DenseMap::cascade(uint32_t top, const loamx_densemap_static_rule* rule, uint32_t first, std::vector<Snapshot>& out) {
-  read_counters();
   out.clear();
+  cascade_each(top, rule, [&](uint32_t l, const DmTable& T, uint64_t occ) {
+    if (l < first) return;
+    out.emplace_back();
+    snapshot_of(T, occ, out.back(), true);
+  });
+}
+
+void DenseMap::cascade_each(uint32_t top, const loamx_densemap_static_rule* rule,
+                            const std::function<void(uint32_t, const DmTable&, uint64_t)>& f) {
+  read_counters();
   DevBuf<unsigned long long> ctr;
   ctr.reserve(2);
   DmTable below;   // level l - 1 once l >= 2
@@ -93,10 +102,7 @@ void DenseMap::cascade(uint32_t top, const loamx_densemap_static_rule* rule, uin
     LX_HIP(hipMemcpyAsync(c, ctr.p, sizeof(c), hipMemcpyDeviceToHost, own_));
     LX_HIP(hipStreamSynchronize(own_));
     if (c[1] != 0ull) throw Error(LOAMX_E_INTERNAL, "dense map: a coarse level's table overflowed");
-    if (l >= first) {
-      out.emplace_back();
-      snapshot_of(dst, c[0], out.back(), true);
-    }
+    f(l, dst, c[0]);
     below.swap(dst);   // (the level below it, now in dst, is freed here: everything that read it has been waited for)
     src = &below;
     src_occ = c[0];

@@ -155,6 +155,20 @@ void DenseMap::launch_replay(const DmTable& nt, unsigned long long* nctr) {
   rebuild_stats_[3] += hist_.points;
 }
 
+// the replay of a window of the log (densemap_freeze.hip, freeze_history): the `points` points from `first` on, which belong to the
+// n_calls records at d_calls, into the table nt (moment words, no carve words: one launch, no word depends on the order of the calls)
+// with the counter words nctr ([DM_CTR_WORDS]: too small), enqueued on own_ without a host wait.  The rebuild's statistics stay
+void DenseMap::launch_replay_range(const DmTable& nt, unsigned long long* nctr, const DmReplayCall* d_calls, uint32_t n_calls, uint64_t first,
+                                   uint64_t points) {
+  const float no_origin[3] = {0.f, 0.f, 0.f};   // (each point is filtered about its own call's origin)
+  const DmFilter F = filter_for(no_origin);
+  dm_dispatch2(combine, nt.mom != nullptr, [&](auto C, auto M) {
+    hipLaunchKernelGGL((k_dm_rebuild<decltype(C)::value, false, decltype(M)::value>), dim3((uint32_t)((points + 255) / 256)), dim3(256), 0, own_,
+                       log_, (unsigned long long)first, (unsigned long long)points, d_calls, 0u, n_calls, F, nt.keys, nt.vals, nt.mask(),
+                       nt.shift(), nctr, (uint32_t*)nullptr, nt.mom, nctr + DM_CTR_WORDS);
+  });
+}
+
 // Everything is built beside the handle (table, counter words) and swapped in at the end: a refusal or a failure on the way leaves
 // the handle as it was
 int DenseMap::rebuild(const double* corrections, uint64_t n_calls) {

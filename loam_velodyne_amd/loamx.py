@@ -2334,6 +2334,84 @@ class DenseMap:
         assert a.ndim == 3 and a.shape[1:] == (3, 4), "corrections must be (n_calls, 3, 4) or (n_calls, 4, 4)"
         return _check(lib().loamx_densemap_rebuild(self.h, a.ctypes.data_as(C.c_void_p), C.c_uint64(a.shape[0])))
 
+    def freeze_device(self, min_points=None, min_planar_ratio=None, static=None) -> int:
+        """loamx_densemap_freeze_device: freeze() with the surfels computed on the device, from the table where it lies — the same
+        set of entries byte for byte, no voxel crosses to the host.  Returns their number.  Needs moments."""
+        c = SurfelConfig(min_points, min_planar_ratio)
+        n = C.c_uint64(0)
+        _check(lib().loamx_densemap_freeze_device(self.h, C.byref(c), C.byref(static) if static is not None else None, C.byref(n)))
+        self._level = 0
+        return int(n.value)
+
+    def freeze_pyramid_device(self, levels=None, max_curvature=None, min_points=None, min_planar_ratio=None, static=None):
+        """loamx_densemap_freeze_pyramid_device: freeze_pyramid() with every level's surfels computed on the device; the same
+        entries per level.  Returns the entry counts per level.  The selected level returns to 0"""
+        c = SurfelConfig(min_points, min_planar_ratio)
+        pc = _cfg(PyramidConfig, "loamx_densemap_pyramid_default_config",
+                  **{k: v for k, v in (("levels", levels), ("max_curvature", max_curvature)) if v is not None})
+        n = (C.c_uint64 * PYRAMID_MAX_LEVELS)()
+        _check(lib().loamx_densemap_freeze_pyramid_device(self.h, C.byref(c), C.byref(static) if static is not None else None, C.byref(pc), n))
+        self._level = 0
+        return [int(v) for v in n[:pc.levels]]
+
+    def freeze_history(self, first: int, n: int, corrections=None, min_points=None, min_planar_ratio=None) -> int:
+        """loamx_densemap_freeze_history: level 0 becomes the snapshot of the logged calls first .. first + n - 1 alone, call k of the
+        window moved by corrections[k] (row-major 3x4 or 4x4, map <- map, float64; None: every sweep where it was): what a fresh map
+        fed with those sweeps would freeze.  On the device, from the log; the live map is only read.  Returns the entries"""
+        c = SurfelConfig(min_points, min_planar_ratio)
+        out = C.c_uint64(0)
+        p = None
+        if corrections is not None:
+            a = np.asarray(corrections, np.float64)
+            a = np.ascontiguousarray(a.reshape(-1, *a.shape[-2:])[:, :3, :4] if a.size else a.reshape(0, 3, 4))
+            assert a.ndim == 3 and a.shape[1:] == (3, 4) and a.shape[0] == n, "corrections must be (n, 3, 4) or (n, 4, 4)"
+            p = a.ctypes.data_as(C.c_void_p)
+        _check(lib().loamx_densemap_freeze_history(self.h, C.c_uint64(first), C.c_uint64(n), p, C.byref(c), C.byref(out)))
+        self._level = 0
+        return int(out.value)
+
+    def download_frozen(self, level=0):
+        """loamx_densemap_download_frozen: the entries of snapshot level `level` in ascending key order as (keys (n,) uint64,
+        rec (n, 6) float32: mean x, y, z, normal x, y, z)"""
+        n, cap = C.c_uint64(0), 0
+        while True:
+            keys, rec = np.zeros(max(cap, 1), np.uint64), np.zeros((max(cap, 1), 6), np.float32)
+            rc = lib().loamx_densemap_download_frozen(self.h, C.c_uint32(level), keys.ctypes.data_as(C.c_void_p),
+                                                      rec.ctypes.data_as(C.c_void_p), C.c_uint64(cap), C.byref(n))
+            if rc == E_CAPACITY:
+                cap = int(n.value)
+                continue
+            _check(rc)
+            return keys[:int(n.value)], rec[:int(n.value)]
+
+    def align_from_history(self, call: int, pose=None, **cfg) -> dict:
+        """loamx_densemap_align_from_history: align() of logged call `call` where it lies in the log, about its logged origin; pose
+        None: identity.  Byte for byte align(*history(call)'s cloud, pose, centre=its origin)"""
+        p = None if pose is None else _pose12(pose)
+        k, out = AlignConfig(**cfg), AlignResult()
+        _check(lib().loamx_densemap_align_from_history(self.h, C.c_uint64(call), None if p is None else p.ctypes.data_as(C.c_void_p),
+                                                       C.byref(k), C.byref(out)))
+        return out.as_dict()
+
+    def align_many_from_history(self, call: int, poses=None, raw=False, **cfg):
+        """loamx_densemap_align_many_from_history: align_many() of logged call `call` where it lies, about its logged origin; poses
+        None: the identity alone.  Returns (results, best)"""
+        p = None if poses is None else self._poses(poses)
+        n = 1 if p is None else len(p)
+        k, out, best = AlignConfig(**cfg), (AlignResult * max(n, 1))(), C.c_uint32(0xFFFFFFFF)
+        rc = _check(lib().loamx_densemap_align_many_from_history(self.h, C.c_uint64(call), None if p is None else p.ctypes.data_as(C.c_void_p),
+                                                                 C.c_uint32(n), C.byref(k), out, C.byref(best)))
+        return self._many_out(rc, out, n, best, raw)[1:]
+
+    def align_pyramid_from_history(self, call: int, pose=None, first_level=None, **cfg):
+        """loamx_densemap_align_pyramid_from_history: align_pyramid() of logged call `call` where it lies, about its logged origin"""
+        p = None if pose is None else _pose12(pose)
+        first = max(self.frozen_levels - 1, 0) if first_level is None else int(first_level)
+        k, out = AlignConfig(**cfg), (AlignResult * PYRAMID_MAX_LEVELS)()
+        _check(lib().loamx_densemap_align_pyramid_from_history(self.h, C.c_uint64(call), None if p is None else p.ctypes.data_as(C.c_void_p),
+                                                               C.byref(k), C.c_uint32(first), out))
+        return self._pyramid_out(out, first)
+
     def rebuild_stats(self) -> dict:
         s = (C.c_uint64 * 4)()
         _check(lib().loamx_densemap_get_rebuild_stats(self.h, s))
