@@ -111,7 +111,6 @@ DenseMap::DenseMap(const loamx_densemap_config& c) : cfg(c) {
   LX_HIP(hipStreamCreateWithFlags(&own_, hipStreamNonBlocking));
   LX_HIP(hipEventCreateWithFlags(&ev_last_, hipEventDisableTiming));
   LX_HIP(hipEventCreateWithFlags(&ev_snap_, hipEventDisableTiming));
-  LX_HIP(hipEventCreateWithFlags(&ev_staged_, hipEventDisableTiming));
   ctr_.reserve(DM_CTR_WORDS);
   h_ctr_.reserve(DM_CTR_WORDS);
   h_snap_.reserve(1);   // (must not move while a snapshot is in flight)
@@ -129,35 +128,26 @@ DenseMap::~DenseMap() {
   DmTable().swap(tab_);
   (void)hipEventDestroy(ev_last_);
   (void)hipEventDestroy(ev_snap_);
-  (void)hipEventDestroy(ev_staged_);
   (void)hipStreamDestroy(own_);
 }
 
-int DenseMap::add_host(const loamx_cloud* c, const float origin[3]) {
+DenseSource DenseMap::host_source(DmCloudStage& via, const loamx_cloud* c, const float origin[3]) {
   check_cloud(c, false);
   LX_HIP(hipSetDevice(cfg.device));
-  const uint32_t n = c->count;
-  if (!admit(n) || !hist_.admits(n)) return LOAMX_E_CAPACITY;
-  if (!n) return LOAMX_OK;
-  if (staged_pending_) { LX_HIP(hipEventSynchronize(ev_staged_)); staged_pending_ = false; }   // (the staging block is still being read)
-  h_stage_.reserve(n);
-  pack_cloud(c, h_stage_.p);
-  d_stage_.reserve(n);
-  order_behind(own_);
-  fetch_from_pinned(d_stage_.p, h_stage_.p, n, own_);
-  LX_HIP(hipEventRecord(ev_staged_, own_));
-  staged_pending_ = true;
-  enqueue_add(d_stage_.p, n, origin, own_);
-  return LOAMX_OK;
+  return via.source(c, origin, own_, cfg.device);
 }
 
-int DenseMap::add_device(const DenseSource& s) {
+// enqueued on the source's stream, behind every add so far: own_ for a cloud from the host, the stream that wrote a registered cloud
+int DenseMap::add(const DenseSource& s) {
   LX_REQUIRE(s.device == cfg.device, "the dense map and its source live on different devices");
   if (!s.has_cloud) return LOAMX_SKIPPED;
   LX_HIP(hipSetDevice(cfg.device));
   if (!admit(s.n) || !hist_.admits(s.n)) return LOAMX_E_CAPACITY;
+  // (kept from the host form, which no test pins: an empty cloud from the host returns before it is staged and enqueues nothing, not
+  // even the event of the last add; an empty registered cloud goes on and moves that event to its stream)
+  if (!s.n && s.stream == own_) return LOAMX_OK;
   order_behind(s.stream);
-  enqueue_add(s.pts, s.n, s.origin, s.stream);
+  enqueue_add(s.points(), s.n, s.origin, s.stream);
   return LOAMX_OK;
 }
 
@@ -283,7 +273,7 @@ void DenseMap::order_behind(hipStream_t st) {
 }
 void DenseMap::wait_adds() {
   if (last_st_) LX_HIP(hipEventSynchronize(ev_last_));
-  if (staged_pending_) { LX_HIP(hipEventSynchronize(ev_staged_)); staged_pending_ = false; }
+  stage.settle();
   occ_.snapshot_abandoned();
   free_graveyard();
 }
@@ -395,7 +385,7 @@ int loamx_densemap_reset(loamx_densemap* h) {
 int loamx_densemap_add(loamx_densemap* h, const loamx_cloud* points, const float origin[3]) {
   return guard([&]() {
     LX_REQUIRE(h && points && origin, "NULL argument");
-    return h->d.add_host(points, origin);
+    return h->d.add(h->d.host_source(h->d.stage, points, origin));
   });
 }
 int loamx_densemap_add_from_map(loamx_densemap* h, loamx_map* m) {
@@ -403,7 +393,7 @@ int loamx_densemap_add_from_map(loamx_densemap* h, loamx_map* m) {
     LX_REQUIRE(h && m, "NULL argument");
     DenseSource s;
     loamx_map_dense_source(m, s);
-    return h->d.add_device(s);
+    return h->d.add(s);
   });
 }
 int loamx_densemap_add_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot) {
@@ -411,7 +401,7 @@ int loamx_densemap_add_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint3
     LX_REQUIRE(h && p, "NULL argument");
     DenseSource s;
     loamx_pipeline_dense_source(p, slot, s);
-    return h->d.add_device(s);
+    return h->d.add(s);
   });
 }
 int loamx_densemap_get_stats(loamx_densemap* h, uint64_t stats[6]) {

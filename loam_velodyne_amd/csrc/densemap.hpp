@@ -3,6 +3,7 @@
 // 20-bit fixed-point offsets inside the voxel, so the table does not depend on the order of the additions).
 #pragma once
 #include "common.h"
+#include "cloud_stage.hpp"
 #include "densemap_growth.hpp"
 #include "pinned_copy.hpp"
 #include "scan.hpp"
@@ -28,16 +29,6 @@ inline void dm_key_indices(unsigned long long k, long long ia[3]) {
 }
 
 inline uint32_t log2u(uint64_t v) { uint32_t r = 0; while ((1ull << r) < v) r++; return r; }
-
-// `behind` runs behind whatever `ahead` holds now
-inline void dm_stream_behind(hipStream_t behind, hipStream_t ahead) {
-  hipEvent_t ev = nullptr;
-  LX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  hipError_t e = hipEventRecord(ev, ahead);
-  if (e == hipSuccess) e = hipStreamWaitEvent(behind, ev, 0);
-  (void)hipEventDestroy(ev);   // (the wait keeps what it needs)
-  LX_HIP(e);
-}
 
 // The map's table in HBM: `slots` (a power of two) keys, four value words per slot and, where the feature is on, aux (carving: 2 x 32
 // bits per slot, [2 * slot] miss, [2 * slot + 1] stamp) and mom (moments: nine words per slot).  Owns its arrays; the kernels take them
@@ -111,37 +102,6 @@ struct DmScan {
   DevBuf<uint32_t> scratch_;
 };
 
-// A cloud from the host on its way to the device: a pinned block and a device block, grown to the largest cloud.  Each feature that
-// stages keeps one of its own: their clouds stay resident independently of each other
-struct DmCloudStage {
-  // the points of a checked cloud, packed, in the device block, enqueued on st (count + 1 entries: an empty cloud has a pointer too)
-  const float4* stage(const loamx_cloud* c, hipStream_t st) {
-    const uint32_t n = c->count;
-    h_.reserve((size_t)n + 1);
-    d_.reserve((size_t)n + 1);
-    if (n) {
-      pack_cloud(c, h_.p);
-      fetch_from_pinned(d_.p, h_.p, n, st);
-    }
-    return d_.p;
-  }
-
- private:
-  PinBuf<float4> h_;
-  DevBuf<float4> d_;
-};
-
-// Where a device-side add reads: a registered cloud that some other handle keeps in HBM, the stream that wrote it, and the pose of the
-// sweep.  Filled by the internal accessors of mapping.hip / pipeline.hip (the handle structs stay where they are).
-struct DenseSource {
-  const float4* pts = nullptr;
-  uint32_t n = 0;
-  hipStream_t stream = nullptr;
-  int device = 0;
-  float origin[3] = {0.f, 0.f, 0.f};
-  bool has_cloud = false;    // false: the last call produced no registered cloud (the add is LOAMX_SKIPPED)
-};
-
 // the home slot of a key in a table of 2^(64 - shift) slots (the map's table and the frozen snapshot's)
 __device__ inline unsigned long long dm_hash(unsigned long long key, uint32_t shift) {
   return (key * 0x9E3779B97F4A7C15ull) >> shift;
@@ -189,8 +149,7 @@ class DmFrozen {
   void build_device(const unsigned long long* d_keys, const float* d_rec, size_t n, hipStream_t st);
   // the entries on the host in ascending key order: keys[i], rec[6 * i ..]; blocks
   void download(std::vector<unsigned long long>& keys, std::vector<float>& rec, hipStream_t st) const;
-  // the cloud of the steps that follow, checked and staged from the host, enqueued on st
-  const float4* stage(const loamx_cloud* c, hipStream_t st) { check_cloud(c, false); return pts_.stage(c, st); }
+  DmCloudStage cloud{false};   // the cloud of the steps that follow from the host, in the feature's own device block (level 0's serves every level; every step blocks: no guard)
   // one linearisation (include/loamx.h, loamx_densemap_align_step); blocks until the 33 words are back
   void step(const float4* pts, uint32_t n, const float rtc[15], float inv, uint32_t neighbourhood, float max_residual, hipStream_t st,
             int64_t sums[28], uint64_t counts[5]);
@@ -209,7 +168,6 @@ class DmFrozen {
   uint64_t count_ = 0;
   DevBuf<unsigned long long> acc_;
   PinLanding<unsigned long long> h_acc_;
-  DmCloudStage pts_;
   PinBuf<float4> h_poses_;
   DevBuf<float4> d_poses_;
   uint64_t stats_[3] = {0, 0, 0};
@@ -380,7 +338,7 @@ class DmDist {
   const uint32_t* near_on_host() const { return h_near_.data(); }
   bool has_field() const { return valid_; }
   void drop() { valid_ = false; }   // (the buffers stay for the next field)
-  DmCloudStage cloud;   // the query's points from the host, in the feature's own device block
+  DmCloudStage cloud{false};   // the query's points from the host, in the feature's own device block (query() blocks: no guard)
   // n >= 1 points (readable on st) against the field of the last run: the five stats and, when want_samples, the n samples in
   // pinned memory, valid until the next query.  Blocks
   const loamx_dist_sample* query(const float4* pts, uint32_t n, float inv, uint32_t min_d2, bool want_samples, uint64_t stats[5],
@@ -451,7 +409,7 @@ class DmSegCloud {
   DmSegCloud() = default;
   DmSegCloud(const DmSegCloud&) = delete;
   DmSegCloud& operator=(const DmSegCloud&) = delete;
-  DmCloudStage cloud;   // the cloud from the host, in the feature's own device block
+  DmCloudStage cloud{false};   // the cloud from the host, in the feature's own device block (insert() blocks: no guard)
   // n >= 1 points (readable on st) under the filter F of their origin against the live table M (every add waited for): the scratch
   // table cleared, the admitted points that pass the map test of a checked configuration and rule (NULL: every voxel) inserted.
   // Blocks.  counts: dropped by range, by the key rule, rejected by the map test, entered, voxels of the scratch table
@@ -472,8 +430,3 @@ class DmSegCloud {
 };
 
 }  // namespace loamx
-
-// internal accessors (not exported in include/loamx.h): the registered cloud of the mapper's last process() / process_linked(), and of
-// the slot-th stream registered in the pipeline's last step (LOAMX_E_INVALID for a slot beyond them)
-void loamx_map_dense_source(loamx_map* h, loamx::DenseSource& out);
-void loamx_pipeline_dense_source(loamx_pipeline* h, uint32_t slot, loamx::DenseSource& out);

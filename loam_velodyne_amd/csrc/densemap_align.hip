@@ -427,7 +427,14 @@ static int align_many_loop(loamx_densemap* h, const float4* pts, uint32_t n, con
   return LOAMX_OK;
 }
 
-// the cloud of a mapper / a pipeline where it lies: the handle's own stream runs behind the stream that wrote it.  false: no cloud
+// The one body of each alignment form takes the cloud as a DenseSource where it lies: a mapper's, a pipeline slot's, a logged call's, or
+// a cloud from the host that comes up through the snapshot's stager on the handle's own stream, its centre (NULL: zeros) the origin.
+// What differs between the forms and is kept: the single form looks at the pose last, in align_loop, so that a non-finite pose on a
+// source without a cloud is SKIPPED; the pyramid looks at it before the cloud, and the many form at its poses first of all.  pose_in
+// NULL is the identity here; the host entry points refuse it before they come here.
+//
+// what the single and the many form check alike; the handle's own stream then runs behind the stream that wrote the cloud,
+// unconditionally (an empty cloud too).  false: no cloud
 static bool align_source_ready(loamx_densemap* h, const DenseSource& s, const loamx_densemap_align_config* cfg, loamx_densemap_align_config& c,
                                hipStream_t& st) {
   const loamx_densemap_config& mc = h->d.cfg;
@@ -446,17 +453,17 @@ static int align_from_source(loamx_densemap* h, const DenseSource& s, const doub
   loamx_densemap_align_config c;
   hipStream_t st = nullptr;
   if (!align_source_ready(h, s, cfg, c, st)) return LOAMX_SKIPPED;
-  return align_loop(h, s.pts, s.n, pose_in, s.origin, c, st, h->d.align_level, out);
+  return align_loop(h, s.points(), s.n, pose_in, s.origin, c, st, h->d.align_level, out);
 }
 
 static void not_null(const void* p, const char* name) {
   if (!p) throw Error(LOAMX_E_INVALID, std::string("NULL argument: ") + name);
 }
 
-static void check_start_poses(const double* poses_in, uint32_t n_poses, bool null_is_identity) {
+static void check_start_poses(const double* poses_in, uint32_t n_poses) {
   LX_REQUIRE(n_poses >= 1u && n_poses <= LOAMX_ALIGN_MAX_POSES, "n_poses must be in [1, LOAMX_ALIGN_MAX_POSES]");
   if (!poses_in) {
-    LX_REQUIRE(null_is_identity && n_poses == 1u, "poses_in may be NULL (the identity) only with n_poses == 1");
+    LX_REQUIRE(n_poses == 1u, "poses_in may be NULL (the identity) only with n_poses == 1");
     return;
   }
   pose_must_be_finite(poses_in, 12 * (size_t)n_poses);
@@ -464,11 +471,11 @@ static void check_start_poses(const double* poses_in, uint32_t n_poses, bool nul
 
 static int align_many_from_source(loamx_densemap* h, const DenseSource& s, const double* poses_in, uint32_t n_poses,
                                   const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out, uint32_t* best) {
-  check_start_poses(poses_in, n_poses, true);
+  check_start_poses(poses_in, n_poses);
   loamx_densemap_align_config c;
   hipStream_t st = nullptr;
   if (!align_source_ready(h, s, cfg, c, st)) return LOAMX_SKIPPED;
-  return align_many_loop(h, s.pts, s.n, poses_in, n_poses, s.origin, c, st, out, best);
+  return align_many_loop(h, s.points(), s.n, poses_in, n_poses, s.origin, c, st, out, best);
 }
 
 // Coarse to fine (include/loamx.h, loamx_densemap_align_pyramid): the settings of every level first_level .. 0, each checked with its
@@ -500,7 +507,7 @@ static int align_pyramid_from_source(loamx_densemap* h, const DenseSource& s, co
   LX_HIP(hipSetDevice(h->d.cfg.device));
   hipStream_t st = h->d.own_stream();
   dm_stream_behind(st, s.stream);
-  return align_pyramid_loop(h, s.pts, s.n, pose_in, s.origin, c, st, first_level, out);
+  return align_pyramid_loop(h, s.points(), s.n, pose_in, s.origin, c, st, first_level, out);
 }
 
 }  // namespace loamx
@@ -538,11 +545,8 @@ int loamx_densemap_align_step(loamx_densemap* h, const loamx_cloud* points, cons
     LX_REQUIRE(max_residual > 0.f && max_residual <= 16.f, "max_residual must be in (0, 16]");   // (NaN too)
     DmFrozen& F = h->d.level(h->d.align_level);
     LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
-    const loamx_densemap_config& mc = h->d.cfg;
-    LX_HIP(hipSetDevice(mc.device));
-    hipStream_t st = h->d.own_stream();
-    const float4* pts = h->d.frozen.stage(points, st);
-    F.step(pts, points->count, rtc, 1.0f / h->d.level_leaf(h->d.align_level), neighbourhood, max_residual, st, sums, counts);
+    const DenseSource s = h->d.host_source(h->d.frozen.cloud, points, nullptr);
+    F.step(s.points(), s.n, rtc, 1.0f / h->d.level_leaf(h->d.align_level), neighbourhood, max_residual, s.stream, sums, counts);
     return LOAMX_OK;
   });
 }
@@ -551,14 +555,7 @@ int loamx_densemap_align(loamx_densemap* h, const loamx_cloud* points, const dou
                          const loamx_densemap_align_config* cfg, loamx_densemap_align_result* out) {
   return guard([&]() {
     LX_REQUIRE(h && points && pose_in && out, "NULL argument");
-    const loamx_densemap_config& mc = h->d.cfg;
-    const loamx_densemap_align_config c = checked_align_config(cfg, h->d.level_leaf(h->d.align_level));
-    DmFrozen& F = h->d.frozen;
-    LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
-    LX_HIP(hipSetDevice(mc.device));
-    hipStream_t st = h->d.own_stream();
-    const float4* pts = F.stage(points, st);
-    return align_loop(h, pts, points->count, pose_in, centre, c, st, h->d.align_level, out);
+    return align_from_source(h, h->d.host_source(h->d.frozen.cloud, points, centre), pose_in, cfg, out);
   });
 }
 
@@ -575,16 +572,13 @@ int loamx_densemap_align_step_many(loamx_densemap* h, const loamx_cloud* points,
     LX_REQUIRE(max_residual > 0.f && max_residual <= 16.f, "max_residual must be in (0, 16]");   // (NaN too)
     DmFrozen& F = h->d.level(h->d.align_level);
     LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
-    const loamx_densemap_config& mc = h->d.cfg;
-    LX_HIP(hipSetDevice(mc.device));
-    hipStream_t st = h->d.own_stream();
-    const float4* pts = h->d.frozen.stage(points, st);
+    const DenseSource s = h->d.host_source(h->d.frozen.cloud, points, nullptr);
     float* table = F.pose_table(n_poses);
     for (uint32_t k = 0; k < n_poses; k++) {
       for (int j = 0; j < 15; j++) table[16 * (size_t)k + j] = rtc[15 * (size_t)k + j];
       table[16 * (size_t)k + 15] = 0.f;
     }
-    const unsigned long long* w = F.step_many(pts, points->count, n_poses, 1.0f / h->d.level_leaf(h->d.align_level), neighbourhood, max_residual, st);
+    const unsigned long long* w = F.step_many(s.points(), s.n, n_poses, 1.0f / h->d.level_leaf(h->d.align_level), neighbourhood, max_residual, s.stream);
     for (uint32_t k = 0; k < n_poses; k++) {
       for (int j = 0; j < DM_ALIGN_SUMS; j++) sums[DM_ALIGN_SUMS * (size_t)k + j] = (int64_t)w[DM_ALIGN_WORDS * (size_t)k + j];
       for (int j = 0; j < DM_ALIGN_COUNTS; j++) counts[DM_ALIGN_COUNTS * (size_t)k + j] = w[DM_ALIGN_WORDS * (size_t)k + DM_ALIGN_SUMS + j];
@@ -600,15 +594,7 @@ int loamx_densemap_align_many(loamx_densemap* h, const loamx_cloud* points, cons
     not_null(points, "points");
     not_null(poses_in, "poses_in");
     not_null(out, "out");
-    check_start_poses(poses_in, n_poses, false);
-    const loamx_densemap_config& mc = h->d.cfg;
-    const loamx_densemap_align_config c = checked_align_config(cfg, h->d.level_leaf(h->d.align_level));
-    DmFrozen& F = h->d.frozen;
-    LX_REQUIRE(F.valid(), "nothing is frozen (loamx_densemap_freeze)");
-    LX_HIP(hipSetDevice(mc.device));
-    hipStream_t st = h->d.own_stream();
-    const float4* pts = F.stage(points, st);
-    return align_many_loop(h, pts, points->count, poses_in, n_poses, centre, c, st, out, best);
+    return align_many_from_source(h, h->d.host_source(h->d.frozen.cloud, points, centre), poses_in, n_poses, cfg, out, best);
   });
 }
 
@@ -727,13 +713,8 @@ int loamx_densemap_align_pyramid(loamx_densemap* h, const loamx_cloud* points, c
     not_null(points, "points");
     not_null(pose_in, "pose_in");
     not_null(out, "out");
-    loamx_densemap_align_config c[LOAMX_PYRAMID_MAX_LEVELS];
-    checked_pyramid_configs(h, cfg, first_level, c);
-    pose_must_be_finite(pose_in, 12);
-    LX_HIP(hipSetDevice(h->d.cfg.device));
-    hipStream_t st = h->d.own_stream();
-    const float4* pts = h->d.frozen.stage(points, st);   // (staged once: every level's step reads it where level 0 put it)
-    return align_pyramid_loop(h, pts, points->count, pose_in, centre, c, st, first_level, out);
+    // (staged once: every level's step reads it where level 0 put it)
+    return align_pyramid_from_source(h, h->d.host_source(h->d.frozen.cloud, points, centre), pose_in, cfg, first_level, out);
   });
 }
 

@@ -27,8 +27,10 @@ class DenseMap {
   explicit DenseMap(const loamx_densemap_config& c);
   ~DenseMap();
   loamx_densemap_config cfg;
-  int add_host(const loamx_cloud* c, const float origin[3]);
-  int add_device(const DenseSource& s);
+  // a checked cloud from the host about origin (NULL: zeros) as a source on own_, up through `via`, a stager of this handle
+  DenseSource host_source(DmCloudStage& via, const loamx_cloud* c, const float origin[3]);
+  DmCloudStage stage;   // the staging block of the adds; the ray casts' ends go up through it too
+  int add(const DenseSource& s);
   // [voxels, slots, offered, added, dropped by range, dropped by key]
   void stats(uint64_t out[6]);
   // the occupied slots on the host: keys, values, (carving) miss words and (on request, moments) the nine moment words, and idx =
@@ -123,12 +125,9 @@ class DenseMap {
   void evict(const DmWindow& W, const char* path, uint64_t removed[2]);
   int page(const char* dir, uint32_t tile_voxels, const uint32_t radius[3], const float centre[3], uint64_t stats[6]);
 
-  // ---- densemap_raycast.hip: include/loamx.h, loamx_densemap_raycast (the ends staged from the host) and its from_* forms (the
-  // registered cloud where it lies)
-  int raycast_host(const loamx_cloud* ends, const float origin[3], const loamx_densemap_raycast_config& c,
-                   const loamx_densemap_static_rule* rule, loamx_ray_hit* out, uint64_t capacity, uint64_t counts[5]);
-  int raycast_device(const DenseSource& s, const loamx_densemap_raycast_config& c, const loamx_densemap_static_rule* rule,
-                     loamx_ray_hit* out, uint64_t capacity, uint64_t counts[5]);
+  // ---- densemap_raycast.hip: include/loamx.h, loamx_densemap_raycast and its from_* forms: the rays from s.origin to the points of s
+  int raycast(const DenseSource& s, const loamx_densemap_raycast_config& c, const loamx_densemap_static_rule* rule, loamx_ray_hit* out,
+              uint64_t capacity, uint64_t counts[5]);
 
   // ---- densemap_rebuild.hip: the sweep log and its replay (include/loamx.h, loamx_densemap_enable_history ... rebuild)
   void enable_history(const loamx_densemap_history_config& c);
@@ -162,14 +161,12 @@ class DenseMap {
   int dist_query(const loamx_cloud* points, uint32_t min_d2, loamx_dist_sample* out, uint64_t capacity, uint64_t stats[5]);
   int segment(const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint32_t* labels, uint64_t label_capacity,
               uint64_t* n_voxels, loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[6]);
-  // ---- densemap_segment_cloud.hip: include/loamx.h, loamx_densemap_segment_cloud (the cloud staged from the host) and its from_*
-  // forms (the registered cloud where it lies); a checked configuration, a checked rule or none
-  int segment_cloud_host(const loamx_cloud* points, const float origin[3], const loamx_densemap_segment_cloud_config& c,
-                         const loamx_densemap_static_rule* rule, uint32_t* labels, uint64_t label_capacity, uint64_t* n_points,
-                         loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[13]);
-  int segment_cloud_device(const DenseSource& s, const loamx_densemap_segment_cloud_config& c, const loamx_densemap_static_rule* rule,
-                           uint32_t* labels, uint64_t label_capacity, uint64_t* n_points, loamx_segment* segs, uint64_t seg_capacity,
-                           uint64_t* n_segs, uint64_t stats[13]);
+  // ---- densemap_segment_cloud.hip: include/loamx.h, loamx_densemap_segment_cloud and its from_* forms: the objects of the cloud of
+  // s (a host cloud comes up through cloud_stage()); a checked configuration, a checked rule or none
+  int segment_cloud(const DenseSource& s, const loamx_densemap_segment_cloud_config& c, const loamx_densemap_static_rule* rule,
+                    uint32_t* labels, uint64_t label_capacity, uint64_t* n_points, loamx_segment* segs, uint64_t seg_capacity,
+                    uint64_t* n_segs, uint64_t stats[13]);
+  DmCloudStage& cloud_stage() { return cseg_.cloud; }
 
  private:
   // the table and its counters
@@ -184,10 +181,7 @@ class DenseMap {
   // adds
   hipStream_t own_ = nullptr;      // host-fed adds, rehash of those, exports
   hipStream_t last_st_ = nullptr;  // the stream of the last enqueued add (ev_last_ recorded behind it)
-  hipEvent_t ev_last_ = nullptr, ev_snap_ = nullptr, ev_staged_ = nullptr;
-  bool staged_pending_ = false;
-  PinBuf<float4> h_stage_;
-  DevBuf<float4> d_stage_;
+  hipEvent_t ev_last_ = nullptr, ev_snap_ = nullptr;
   // carving
   loamx_densemap_carve_config carve_ = {0.f, 1u, 1u, 4096u};
   uint32_t seq_ = 0;          // sequence number of the last add call (stamp values; 0 = never stamped)
@@ -199,6 +193,7 @@ class DenseMap {
   PinBuf<DmReplayCall> h_calls_;
   DevBuf<DmReplayCall> d_calls_;
   PinLanding<unsigned long long> h_rb_;
+  PinLanding<float4> h_sweep_;   // history_download's landing
   uint64_t rebuild_stats_[4] = {0, 0, 0, 0};
   // the features that only read the table, each with its own buffers, allocated by its first call
   DmCaster caster_;   // densemap_raycast.hip
@@ -229,17 +224,10 @@ class DenseMap {
                      uint32_t miss_stride, const unsigned long long* smom, const DmCtrAdd& add, uint64_t s_offered);
   // ---- densemap_region.hip
   void region_header(DmFileHeader& H) const;   // flags, leaf and the carving configuration of the handle; every statistic 0
-  // ---- densemap_raycast.hip
-  void cast(const float4* pts, uint32_t n, const float origin[3], const loamx_densemap_raycast_config& c,
-            const loamx_densemap_static_rule* rule, loamx_ray_hit* out, uint64_t counts[5]);
   // ---- densemap_frontier.hip: the tail of the two forms, behind a wait_adds(): the nx * nz records d_cells written by work on own_
   int frontiers_on(const loamx_grid_cell* d_cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config& rc,
                    const loamx_grid_frontier_config& fc, const uint32_t* start_xz, uint32_t* labels, loamx_frontier* out, uint64_t capacity,
                    uint64_t* n_frontiers, uint64_t stats[6]);
-  // ---- densemap_segment_cloud.hip: the tail of the three forms, behind a wait_adds(): n points readable on own_
-  int segment_cloud(const float4* pts, uint32_t n, const float origin[3], const loamx_densemap_segment_cloud_config& c,
-                    const loamx_densemap_static_rule* rule, uint32_t* labels, uint64_t label_capacity, uint64_t* n_points, loamx_segment* segs,
-                    uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[13]);
   // ---- densemap_pyramid.hip: the levels 1 .. top, each from the one below (level 1 from the map's table, which is only read, without
   // the voxels the rule calls dynamic); out[l - first] = the voxels of level l for l = first .. top.  Waits for the adds; blocks
   void cascade(uint32_t top, const loamx_densemap_static_rule* rule, uint32_t first, std::vector<Snapshot>& out);

@@ -119,45 +119,23 @@ void DmCaster::results(uint32_t n, loamx_ray_hit* out, uint64_t counts[5]) const
   if (out) memcpy(out, h_hits_.data(), sizeof(loamx_ray_hit) * n);
 }
 
-// the tail of the ray casts, behind a wait_adds(): n rays from origin to pts (readable on own_) against the live table; returns
-// when the counts and, with out, the n records are back.  read_counters() is the wait: it also reports a probe overflow
-void DenseMap::cast(const float4* pts, uint32_t n, const float origin[3], const loamx_densemap_raycast_config& c,
-                    const loamx_densemap_static_rule* rule, loamx_ray_hit* out, uint64_t counts[5]) {
-  for (int k = 0; k < 5; k++) counts[k] = 0;
-  if (!n) return;
-  caster_.enqueue(tab_, ctr_.p, inv_, (double)cfg.leaf, pts, n, origin, c, rule, out != nullptr, own_);
-  read_counters();
-  caster_.results(n, out, counts);
-}
-
-// the ends go up through the staging block of the adds (free once they are waited for)
-int DenseMap::raycast_host(const loamx_cloud* ends, const float origin[3], const loamx_densemap_raycast_config& c,
-                           const loamx_densemap_static_rule* rule, loamx_ray_hit* out, uint64_t capacity, uint64_t counts[5]) {
-  check_cloud(ends, false);
-  const uint32_t n = ends->count;
-  if (out && capacity < n) throw Error(LOAMX_E_CAPACITY, "capacity is smaller than the cloud's count");
-  LX_HIP(hipSetDevice(cfg.device));
-  wait_adds();
-  if (n) {
-    h_stage_.reserve(n);
-    pack_cloud(ends, h_stage_.p);
-    d_stage_.reserve(n);
-    fetch_from_pinned(d_stage_.p, h_stage_.p, n, own_);
-  }
-  cast(d_stage_.p, n, origin, c, rule, out, counts);
-  return LOAMX_OK;
-}
-
-// the registered cloud where it lies, own_ behind the stream that wrote it
-int DenseMap::raycast_device(const DenseSource& s, const loamx_densemap_raycast_config& c, const loamx_densemap_static_rule* rule,
-                             loamx_ray_hit* out, uint64_t capacity, uint64_t counts[5]) {
+// include/loamx.h, loamx_densemap_raycast: the rays from s.origin to the points of s where they lie, against the live table, own_
+// behind the stream that wrote them (ends from the host go up through the staging block of the adds, on own_, behind the wait for the adds).  capacity is looked
+// at after has_cloud: a source without a cloud is SKIPPED whatever the room.  Returns when the counts and, with out, the records are
+// back; read_counters() is the wait: it also reports a probe overflow
+int DenseMap::raycast(const DenseSource& s, const loamx_densemap_raycast_config& c, const loamx_densemap_static_rule* rule, loamx_ray_hit* out,
+                      uint64_t capacity, uint64_t counts[5]) {
   LX_REQUIRE(s.device == cfg.device, "the dense map and its source live on different devices");
   if (!s.has_cloud) return LOAMX_SKIPPED;
   if (out && capacity < s.n) throw Error(LOAMX_E_CAPACITY, "capacity is smaller than the cloud's count");
   LX_HIP(hipSetDevice(cfg.device));
   wait_adds();
-  if (s.n) dm_stream_behind(own_, s.stream);
-  cast(s.pts, s.n, s.origin, c, rule, out, counts);
+  for (int k = 0; k < 5; k++) counts[k] = 0;
+  if (!s.n) return LOAMX_OK;
+  dm_stream_behind(own_, s.stream);
+  caster_.enqueue(tab_, ctr_.p, inv_, (double)cfg.leaf, s.points(), s.n, s.origin, c, rule, out != nullptr, own_);
+  read_counters();
+  caster_.results(s.n, out, counts);
   return LOAMX_OK;
 }
 
@@ -193,7 +171,7 @@ int loamx_densemap_raycast(loamx_densemap* h, const loamx_cloud* ends, const flo
     LX_REQUIRE(ends, "ends is NULL");
     LX_REQUIRE(origin, "origin is NULL");
     const loamx_densemap_raycast_config c = checked_raycast(h, cfg, rule, counts);
-    return h->d.raycast_host(ends, origin, c, rule, out, capacity, counts);
+    return h->d.raycast(h->d.host_source(h->d.stage, ends, origin), c, rule, out, capacity, counts);
   });
 }
 int loamx_densemap_raycast_from_map(loamx_densemap* h, loamx_map* m, const loamx_densemap_raycast_config* cfg,
@@ -204,7 +182,7 @@ int loamx_densemap_raycast_from_map(loamx_densemap* h, loamx_map* m, const loamx
     const loamx_densemap_raycast_config c = checked_raycast(h, cfg, rule, counts);
     DenseSource s;
     loamx_map_dense_source(m, s);
-    return h->d.raycast_device(s, c, rule, out, capacity, counts);
+    return h->d.raycast(s, c, rule, out, capacity, counts);
   });
 }
 int loamx_densemap_raycast_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot, const loamx_densemap_raycast_config* cfg,
@@ -216,7 +194,7 @@ int loamx_densemap_raycast_from_pipeline(loamx_densemap* h, loamx_pipeline* p, u
     const loamx_densemap_raycast_config c = checked_raycast(h, cfg, rule, counts);
     DenseSource s;
     loamx_pipeline_dense_source(p, slot, s);
-    return h->d.raycast_device(s, c, rule, out, capacity, counts);
+    return h->d.raycast(s, c, rule, out, capacity, counts);
   });
 }
 

@@ -102,11 +102,10 @@ int DenseMap::history_download(uint64_t call, loamx_cloud* out, float origin[3])
   if (c.count > out->count) { out->count = c.count; return LOAMX_E_CAPACITY; }
   LX_HIP(hipSetDevice(cfg.device));
   wait_adds();
-  h_stage_.reserve(c.count);   // (free: the adds were waited for)
-  store_to_pinned_u32((uint32_t*)h_stage_.p, (const uint32_t*)(log_ + c.first), 4 * (size_t)c.count, own_);
+  const float4* pts = h_sweep_.fetch(log_ + c.first, c.count, own_);
   LX_HIP(hipStreamSynchronize(own_));
   for (int a = 0; a < 3; a++) origin[a] = c.origin[a];
-  return unpack_cloud(h_stage_.p, c.count, out);
+  return unpack_cloud(pts, c.count, out);
 }
 
 // room for n more points in the log: a block of the doubled capacity, the logged points copied over on st, the old block to the

@@ -167,18 +167,26 @@ void dm_segment_cloud_check(const loamx_densemap_segment_cloud_config& c) {
   dm_segment_check(s);
 }
 
-// include/loamx.h, loamx_densemap_segment_cloud: n points readable on own_ (every add waited for), a checked configuration and rule.
-// The outputs are written last, all or none; LOAMX_E_CAPACITY: only the two counts
-int DenseMap::segment_cloud(const float4* pts, uint32_t n, const float origin[3], const loamx_densemap_segment_cloud_config& c,
-                            const loamx_densemap_static_rule* rule, uint32_t* labels, uint64_t label_capacity, uint64_t* n_points,
-                            loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[13]) {
+// include/loamx.h, loamx_densemap_segment_cloud: the cloud of src where it lies, own_ behind the stream that wrote it (a cloud from the
+// host comes up through the feature's own staging block, on own_; an empty one is not staged), every add waited for; a checked configuration and rule.  The outputs are written last, all or none;
+// LOAMX_E_CAPACITY: only the two counts
+int DenseMap::segment_cloud(const DenseSource& src, const loamx_densemap_segment_cloud_config& c, const loamx_densemap_static_rule* rule,
+                            uint32_t* labels, uint64_t label_capacity, uint64_t* n_points, loamx_segment* segs, uint64_t seg_capacity,
+                            uint64_t* n_segs, uint64_t stats[13]) {
+  LX_REQUIRE(src.device == cfg.device, "the dense map and its source live on different devices");
+  if (!src.has_cloud) return LOAMX_SKIPPED;
+  LX_HIP(hipSetDevice(cfg.device));
+  wait_adds();
+  if (src.n) dm_stream_behind(own_, src.stream);
+  const float4* pts = src.n ? src.points() : nullptr;
+  const uint32_t n = src.n;
   uint64_t s[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   std::vector<loamx_segment> sg;
   std::vector<uint32_t> none, rank;
   const uint32_t* ids = nullptr;
   if (n) {
     uint64_t cnt[5];
-    cseg_.insert(tab_, filter_for(origin), c, rule, pts, n, own_, cnt);
+    cseg_.insert(tab_, filter_for(src.origin), c, rule, pts, n, own_, cnt);
     s[0] = n;
     for (int k = 0; k < 5; k++) s[1 + k] = cnt[k];
     if (s[1] + s[2] + s[3] + s[4] != s[0]) throw Error(LOAMX_E_INTERNAL, "segment_cloud: the counters do not add up to the cloud's count");
@@ -209,29 +217,6 @@ int DenseMap::segment_cloud(const float4* pts, uint32_t n, const float origin[3]
   if (segs && !sg.empty()) memcpy(segs, sg.data(), sizeof(loamx_segment) * sg.size());
   memcpy(stats, s, sizeof(s));
   return LOAMX_OK;
-}
-
-// the cloud goes up through a staging block of the feature's own
-int DenseMap::segment_cloud_host(const loamx_cloud* points, const float origin[3], const loamx_densemap_segment_cloud_config& c,
-                                 const loamx_densemap_static_rule* rule, uint32_t* labels, uint64_t label_capacity, uint64_t* n_points,
-                                 loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[13]) {
-  check_cloud(points, false);
-  LX_HIP(hipSetDevice(cfg.device));
-  wait_adds();
-  const float4* pts = points->count ? cseg_.cloud.stage(points, own_) : nullptr;
-  return segment_cloud(pts, points->count, origin, c, rule, labels, label_capacity, n_points, segs, seg_capacity, n_segs, stats);
-}
-
-// the registered cloud where it lies, own_ behind the stream that wrote it
-int DenseMap::segment_cloud_device(const DenseSource& src, const loamx_densemap_segment_cloud_config& c, const loamx_densemap_static_rule* rule,
-                                   uint32_t* labels, uint64_t label_capacity, uint64_t* n_points, loamx_segment* segs, uint64_t seg_capacity,
-                                   uint64_t* n_segs, uint64_t stats[13]) {
-  LX_REQUIRE(src.device == cfg.device, "the dense map and its source live on different devices");
-  if (!src.has_cloud) return LOAMX_SKIPPED;
-  LX_HIP(hipSetDevice(cfg.device));
-  wait_adds();
-  if (src.n) dm_stream_behind(own_, src.stream);
-  return segment_cloud(src.pts, src.n, src.origin, c, rule, labels, label_capacity, n_points, segs, seg_capacity, n_segs, stats);
 }
 
 // what the three forms check alike: the outputs that must be there, the configuration (cfg NULL: the defaults) and the rule (NULL
@@ -288,7 +273,7 @@ int loamx_densemap_segment_cloud(loamx_densemap* h, const loamx_cloud* points, c
     LX_REQUIRE(points, "points is NULL");
     LX_REQUIRE(origin, "origin is NULL");
     const loamx_densemap_segment_cloud_config c = checked_segment_cloud(h, cfg, rule, n_points, n_segs, stats);
-    return h->d.segment_cloud_host(points, origin, c, rule, labels, label_capacity, n_points, segs, seg_capacity, n_segs, stats);
+    return h->d.segment_cloud(h->d.host_source(h->d.cloud_stage(), points, origin), c, rule, labels, label_capacity, n_points, segs, seg_capacity, n_segs, stats);
   });
 }
 
@@ -301,7 +286,7 @@ int loamx_densemap_segment_cloud_from_map(loamx_densemap* h, loamx_map* m, const
     const loamx_densemap_segment_cloud_config c = checked_segment_cloud(h, cfg, rule, n_points, n_segs, stats);
     DenseSource s;
     loamx_map_dense_source(m, s);
-    return h->d.segment_cloud_device(s, c, rule, labels, label_capacity, n_points, segs, seg_capacity, n_segs, stats);
+    return h->d.segment_cloud(s, c, rule, labels, label_capacity, n_points, segs, seg_capacity, n_segs, stats);
   });
 }
 
@@ -315,7 +300,7 @@ int loamx_densemap_segment_cloud_from_pipeline(loamx_densemap* h, loamx_pipeline
     const loamx_densemap_segment_cloud_config c = checked_segment_cloud(h, cfg, rule, n_points, n_segs, stats);
     DenseSource s;
     loamx_pipeline_dense_source(p, slot, s);
-    return h->d.segment_cloud_device(s, c, rule, labels, label_capacity, n_points, segs, seg_capacity, n_segs, stats);
+    return h->d.segment_cloud(s, c, rule, labels, label_capacity, n_points, segs, seg_capacity, n_segs, stats);
   });
 }
 

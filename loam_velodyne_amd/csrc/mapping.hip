@@ -1320,7 +1320,7 @@ int loamx_map_get_stats(loamx_map* h, int s[8]) {
 
 }  // extern "C"
 
-// the registered cloud of the last process() / process_linked(), for the dense map (densemap.hpp): the registrar's full-resolution buffer,
+// the registered cloud of the last process() / process_linked(), for the dense map (cloud_stage.hpp): the registrar's full-resolution buffer,
 // written on the registrar's stream and rewritten only by the next sweep's upload on that same stream
 void loamx_map_dense_source(loamx_map* h, loamx::DenseSource& out) {
   LX_REQUIRE(h, "NULL mapper");

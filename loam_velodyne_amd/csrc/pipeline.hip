@@ -1110,7 +1110,7 @@ void* loamx_pipeline_stream(loamx_pipeline* h) { return h ? (void*)h->p.reg.stre
 
 }  // extern "C"
 
-// the registered cloud of the slot-th stream registered in the last step, for the dense map (densemap.hpp): it lies in the registrar's
+// the registered cloud of the slot-th stream registered in the last step, for the dense map (cloud_stage.hpp): it lies in the registrar's
 // full-resolution buffer until the registrar's stream passes the next step's gather, so an add enqueued on that stream reads it in time
 void loamx_pipeline_dense_source(loamx_pipeline* h, uint32_t slot, loamx::DenseSource& out) {
   LX_REQUIRE(h, "NULL pipeline");

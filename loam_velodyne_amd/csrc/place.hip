@@ -7,8 +7,7 @@
 // k_pl_merge).  Every order used is total ((value, id) with distinct ids), and every sum has a fixed order: results are reproducible
 // to the bit and equal tests/place_model.py.
 #include "place.hpp"
-#include "densemap.hpp"
-#include "pinned_copy.hpp"
+#include "cloud_stage.hpp"
 #include <algorithm>
 
 namespace loamx {
@@ -237,7 +236,6 @@ class PlaceDB {
     }
     LX_HIP(hipStreamCreateWithFlags(&own_, hipStreamNonBlocking));
     LX_HIP(hipEventCreateWithFlags(&ev_last_, hipEventDisableTiming));
-    LX_HIP(hipEventCreateWithFlags(&ev_staged_, hipEventDisableTiming));
     LX_HIP(hipEventCreateWithFlags(&ev_done_, hipEventDisableTiming));
     std::vector<float> tab(2 * (size_t)S);
     place_sector_table(S, tab.data());
@@ -262,7 +260,6 @@ class PlaceDB {
     (void)hipFree(desc_);
     (void)hipFree(keys_);
     (void)hipEventDestroy(ev_last_);
-    (void)hipEventDestroy(ev_staged_);
     (void)hipEventDestroy(ev_done_);
     (void)hipStreamDestroy(own_);
     (void)hipGetLastError();   // (whatever the calls above were answered with is not the next caller's error)
@@ -273,23 +270,51 @@ class PlaceDB {
 
   uint32_t size() const { return n_; }
 
-  int add_host(const loamx_cloud* c, const float origin[3], uint32_t* id) {
+  // a cloud from the host about a finite origin as a source on own_, up through the database's stager
+  DenseSource host_source(const loamx_cloud* c, const float origin[3]) {
     check_cloud(c, false);
     check_origin(origin);
     LX_HIP(hipSetDevice(cfg.device));
-    if (full()) return LOAMX_E_CAPACITY;
-    order_behind(own_);
-    const float4* pts = stage(c);
-    return add(pts, c->count, origin, own_, id);
+    return stage_.source(c, origin, own_, cfg.device);
   }
 
-  int add_device(const DenseSource& s, uint32_t* id) {
+  // enqueued on the source's stream, behind every add so far: own_ for a cloud from the host, the stream that wrote a registered cloud
+  // (kept: a non-finite origin from the host is refused in host_source, before the database is found full; a source's only here, after)
+  int add(const DenseSource& s, uint32_t* id) {
     LX_REQUIRE(s.device == cfg.device, "the place database and its source live on different devices");
     if (!s.has_cloud) return LOAMX_SKIPPED;
     LX_HIP(hipSetDevice(cfg.device));
     if (full()) return LOAMX_E_CAPACITY;
-    order_behind(s.stream);
-    return add(s.pts, s.n, s.origin, s.stream, id);
+    hipStream_t st = s.stream;
+    order_behind(st);
+    check_origin(s.origin);
+    if (n_ + 1u > cap_) {   // growth by doubling: a device-to-device copy on the stream of this add, the old arrays freed later
+      LX_REQUIRE(cap_ <= (1u << 29), "place database: more entries than it can index");
+      const uint32_t want = cap_ * 2u;
+      float *nd = nullptr, *nk = nullptr;
+      alloc_entries(want, nd, nk);
+      LX_HIP(hipMemcpyAsync(nd, desc_, sizeof(float) * RS * n_, hipMemcpyDeviceToDevice, st));
+      LX_HIP(hipMemcpyAsync(nk, keys_, sizeof(float) * R * n_, hipMemcpyDeviceToDevice, st));
+      graveyard_.push_back(desc_);
+      graveyard_.push_back(keys_);
+      desc_ = nd;
+      keys_ = nk;
+      cap_ = want;
+      growths++;
+    }
+    describe(s.points(), s.n, s.origin, desc_ + (size_t)n_ * RS, keys_ + (size_t)n_ * R, st);
+    // The order is handed on to own_ at once: a source's stream may be destroyed before the database next waits, and an event that was
+    // last recorded on a destroyed stream must not be waited for, queried or synchronised (the runtime looks at that stream and has
+    // answered "event last recorded in a capturing stream").  Outside this function ev_last_ is an event of own_.
+    LX_HIP(hipEventRecord(ev_last_, st));
+    if (st != own_) {
+      LX_HIP(hipStreamWaitEvent(own_, ev_last_, 0));
+      LX_HIP(hipEventRecord(ev_last_, own_));
+    }
+    added_ = true;
+    if (id) *id = n_;
+    n_++;
+    return LOAMX_OK;
   }
 
   int query_entry(uint32_t id, loamx_place_match* out, uint32_t n_results, uint32_t* n_found) {
@@ -301,12 +326,9 @@ class PlaceDB {
 
   int query_cloud(const loamx_cloud* c, const float origin[3], uint32_t exclude_recent, loamx_place_match* out, uint32_t n_results,
                   uint32_t* n_found) {
-    check_cloud(c, false);
-    check_origin(origin);
-    LX_HIP(hipSetDevice(cfg.device));
+    const DenseSource s = host_source(c, origin);
     order_behind(own_);
-    const float4* pts = stage(c);
-    describe(pts, c->count, origin, q_desc_.p, q_key_.p, own_);
+    describe(s.points(), s.n, s.origin, q_desc_.p, q_key_.p, own_);
     return search(q_desc_.p, q_key_.p, n_, exclude_recent, out, n_results, n_found);
   }
 
@@ -391,8 +413,7 @@ class PlaceDB {
  private:
   hipStream_t own_ = nullptr;      // host-fed adds, queries, exports
   bool added_ = false;             // ev_last_ has been recorded: on own_, behind every add enqueued so far (add())
-  hipEvent_t ev_last_ = nullptr, ev_staged_ = nullptr, ev_done_ = nullptr;
-  bool staged_pending_ = false;
+  hipEvent_t ev_last_ = nullptr, ev_done_ = nullptr;
   float* desc_ = nullptr;          // cap_ x R*S
   float* keys_ = nullptr;          // cap_ x R
   uint32_t cap_ = 0, n_ = 0;
@@ -403,8 +424,7 @@ class PlaceDB {
   DevBuf<uint32_t> shift_, cand_;
   DevBuf<unsigned long long> dkey_, part_;
   PinBuf<loamx_place_match> h_res_;
-  PinBuf<float4> h_stage_;
-  DevBuf<float4> d_stage_;
+  DmCloudStage stage_;             // add()'s and query_cloud()'s clouds from the host
   std::vector<void*> graveyard_;   // arrays replaced by a growth: freed at the next point where the host waits anyway
 
   static void check_origin(const float o[3]) {
@@ -425,22 +445,8 @@ class PlaceDB {
   }
   void wait_adds() {
     if (added_) LX_HIP(hipEventSynchronize(ev_last_));
-    if (staged_pending_) { LX_HIP(hipEventSynchronize(ev_staged_)); staged_pending_ = false; }
+    stage_.settle();
     free_graveyard();
-  }
-  // the caller's cloud as packed points in device memory, on own_
-  const float4* stage(const loamx_cloud* c) {
-    const uint32_t n = c->count;
-    if (!n) return nullptr;
-    if (staged_pending_) { LX_HIP(hipEventSynchronize(ev_staged_)); staged_pending_ = false; }   // (the staging block is still being read)
-    h_stage_.reserve(n);
-    pack_cloud(c, h_stage_.p);
-    if (n > d_stage_.cap) LX_HIP(hipStreamSynchronize(own_));   // (a describe of the previous cloud may still read the block about to be replaced)
-    d_stage_.reserve(n);
-    fetch_from_pinned(d_stage_.p, h_stage_.p, n, own_);
-    LX_HIP(hipEventRecord(ev_staged_, own_));
-    staged_pending_ = true;
-    return d_stage_.p;
   }
   void describe(const float4* pts, uint32_t n, const float origin[3], float* cells, float* key, hipStream_t st) {
     hipLaunchKernelGGL(k_pl_clear, dim3((uint32_t)((RS + 255) / 256)), dim3(256), 0, st, (uint32_t*)cells, (uint32_t)RS);
@@ -452,36 +458,6 @@ class PlaceDB {
     }
     hipLaunchKernelGGL(k_pl_keys, dim3(1), dim3(64), 0, st, cells, key, R, S);
     LX_HIP(hipGetLastError());
-  }
-  int add(const float4* pts, uint32_t n, const float origin[3], hipStream_t st, uint32_t* id) {
-    check_origin(origin);
-    if (n_ + 1u > cap_) {   // growth by doubling: a device-to-device copy on the stream of this add, the old arrays freed later
-      LX_REQUIRE(cap_ <= (1u << 29), "place database: more entries than it can index");
-      const uint32_t want = cap_ * 2u;
-      float *nd = nullptr, *nk = nullptr;
-      alloc_entries(want, nd, nk);
-      LX_HIP(hipMemcpyAsync(nd, desc_, sizeof(float) * RS * n_, hipMemcpyDeviceToDevice, st));
-      LX_HIP(hipMemcpyAsync(nk, keys_, sizeof(float) * R * n_, hipMemcpyDeviceToDevice, st));
-      graveyard_.push_back(desc_);
-      graveyard_.push_back(keys_);
-      desc_ = nd;
-      keys_ = nk;
-      cap_ = want;
-      growths++;
-    }
-    describe(pts, n, origin, desc_ + (size_t)n_ * RS, keys_ + (size_t)n_ * R, st);
-    // The order is handed on to own_ at once: a source's stream may be destroyed before the database next waits, and an event that was
-    // last recorded on a destroyed stream must not be waited for, queried or synchronised (the runtime looks at that stream and has
-    // answered "event last recorded in a capturing stream").  Outside this function ev_last_ is an event of own_.
-    LX_HIP(hipEventRecord(ev_last_, st));
-    if (st != own_) {
-      LX_HIP(hipStreamWaitEvent(own_, ev_last_, 0));
-      LX_HIP(hipEventRecord(ev_last_, own_));
-    }
-    added_ = true;
-    if (id) *id = n_;
-    n_++;
-    return LOAMX_OK;
   }
   // on own_, which the caller has ordered behind every add
   int search(const float* Q, const float* rq, uint32_t q, uint32_t exclude_recent, loamx_place_match* out, uint32_t n_results, uint32_t* n_found) {
@@ -590,7 +566,7 @@ int loamx_place_sector_table(int n_sectors, float* table) {
 int loamx_place_add(loamx_place* h, const loamx_cloud* points, const float origin[3], uint32_t* id) {
   return guard([&]() {
     LX_REQUIRE(h && points && origin, "NULL argument");
-    return h->d.add_host(points, origin, id);
+    return h->d.add(h->d.host_source(points, origin), id);
   });
 }
 int loamx_place_add_from_map(loamx_place* h, loamx_map* m, uint32_t* id) {
@@ -598,7 +574,7 @@ int loamx_place_add_from_map(loamx_place* h, loamx_map* m, uint32_t* id) {
     LX_REQUIRE(h && m, "NULL argument");
     DenseSource s;
     loamx_map_dense_source(m, s);
-    return h->d.add_device(s, id);
+    return h->d.add(s, id);
   });
 }
 int loamx_place_add_from_pipeline(loamx_place* h, loamx_pipeline* p, uint32_t slot, uint32_t* id) {
@@ -606,7 +582,7 @@ int loamx_place_add_from_pipeline(loamx_place* h, loamx_pipeline* p, uint32_t sl
     LX_REQUIRE(h && p, "NULL argument");
     DenseSource s;
     loamx_pipeline_dense_source(p, slot, s);
-    return h->d.add_device(s, id);
+    return h->d.add(s, id);
   });
 }
 int loamx_place_query_entry(loamx_place* h, uint32_t id, loamx_place_match* matches, uint32_t n_results, uint32_t* n_found) {

@@ -1802,35 +1802,40 @@ class DenseMap:
                                                sums.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
         return sums, counts
 
+    @staticmethod
+    def _ptr(a):
+        return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+    @staticmethod
+    def _host_cloud(points, centre):
+        """what the host forms of align* pass before and behind the pose: (the cloud,) and (the centre or NULL,), and in front of
+        both the arrays they point into, for the caller to hold during the call"""
+        a = as_points(points)
+        ctr = None if centre is None else np.ascontiguousarray(centre, np.float32)
+        assert ctr is None or ctr.shape == (3,)
+        return (a, ctr), (C.byref(cloud_of(a)),), (DenseMap._ptr(ctr),)
+
+    def _align(self, fn, head, pose, mid, cfg):
+        # the marshalling every form of align shares: head and mid are the arguments before and behind the pose
+        p = None if pose is None else _pose12(pose)
+        k, out = AlignConfig(**cfg), AlignResult()
+        rc = _check(fn(self.h, *head, self._ptr(p), *mid, C.byref(k), C.byref(out)))
+        return rc, out.as_dict()
+
     def align(self, points, pose=np.eye(3, 4), centre=None, **cfg) -> dict:
         """loamx_densemap_align: Gauss-Newton point-to-plane alignment of (N, 4) / (N, 8) points to the frozen snapshot from pose
         (3x4, map <- cloud), rotating about centre (default 0).  cfg: the fields of AlignConfig.  Blocks; returns AlignResult.as_dict()"""
-        a = as_points(points)
-        c = cloud_of(a)
-        p = _pose12(pose)
-        ctr = None if centre is None else np.ascontiguousarray(centre, np.float32)
-        assert ctr is None or ctr.shape == (3,)
-        k, out = AlignConfig(**cfg), AlignResult()
-        _check(lib().loamx_densemap_align(self.h, C.byref(c), p.ctypes.data_as(C.c_void_p),
-                                          None if ctr is None else ctr.ctypes.data_as(C.c_void_p), C.byref(k), C.byref(out)))
-        return out.as_dict()
+        keep, head, mid = self._host_cloud(points, centre)
+        return self._align(lib().loamx_densemap_align, head, pose, mid, cfg)[1]
 
     def align_from(self, mapping, pose=None, **cfg):
         """loamx_densemap_align_from_map: the registered cloud of mapping's last process, where it lies, about its origin; pose None:
         identity.  Returns (status code OK / SKIPPED, AlignResult.as_dict())"""
-        p = None if pose is None else _pose12(pose)
-        k, out = AlignConfig(**cfg), AlignResult()
-        rc = _check(lib().loamx_densemap_align_from_map(self.h, mapping.h, None if p is None else p.ctypes.data_as(C.c_void_p),
-                                                        C.byref(k), C.byref(out)))
-        return rc, out.as_dict()
+        return self._align(lib().loamx_densemap_align_from_map, (mapping.h,), pose, (), cfg)
 
     def align_from_pipeline(self, pipeline, slot: int, pose=None, **cfg):
         """loamx_densemap_align_from_pipeline: the same for the slot-th stream registered in pipeline's last step"""
-        p = None if pose is None else _pose12(pose)
-        k, out = AlignConfig(**cfg), AlignResult()
-        rc = _check(lib().loamx_densemap_align_from_pipeline(self.h, pipeline.h, C.c_uint32(slot),
-                                                             None if p is None else p.ctypes.data_as(C.c_void_p), C.byref(k), C.byref(out)))
-        return rc, out.as_dict()
+        return self._align(lib().loamx_densemap_align_from_pipeline, (pipeline.h, C.c_uint32(slot)), pose, (), cfg)
 
     def align_step_many(self, points, rtc, neighbourhood=1, max_residual=None):
         """loamx_densemap_align_step_many: the linearisation of align_step about the K poses rtc (K, 15) float32 in one launch.
@@ -1852,44 +1857,29 @@ class DenseMap:
         assert p.ndim >= 2 and p.size == len(p) * 12, "start poses are (K, 3, 4) or (K, 12)"
         return p.reshape(len(p), 12)
 
-    @staticmethod
-    def _many_out(rc, out, k, best, raw):
-        b = None if best.value == 0xFFFFFFFF else int(best.value)
-        return rc, (out if raw else [out[i].as_dict() for i in range(k)]), b
+    def _align_many(self, fn, head, poses, mid, raw, cfg):
+        # the marshalling every form of align_many shares: head and mid are the arguments before the poses and behind their count
+        p = None if poses is None else self._poses(poses)
+        n = 1 if p is None else len(p)
+        k, out, best = AlignConfig(**cfg), (AlignResult * max(n, 1))(), C.c_uint32(0xFFFFFFFF)
+        rc = _check(fn(self.h, *head, self._ptr(p), C.c_uint32(n), *mid, C.byref(k), out, C.byref(best)))
+        return rc, (out if raw else [out[i].as_dict() for i in range(n)]), (None if best.value == 0xFFFFFFFF else int(best.value))
 
     def align_many(self, points, poses, centre=None, raw=False, **cfg):
         """loamx_densemap_align_many: align() from each of the K start poses (K, 3, 4), their Gauss-Newton loops in lockstep: one
         launch and one readback per iteration for all of them.  Returns (results, best): results[k] is what align(points, poses[k],
         centre, **cfg) returns (raw=True: the ctypes array of AlignResult instead of dicts), best the index align_best picks or None"""
-        a = as_points(points)
-        c = cloud_of(a)
-        p = self._poses(poses)
-        ctr = None if centre is None else np.ascontiguousarray(centre, np.float32)
-        assert ctr is None or ctr.shape == (3,)
-        k, out, best = AlignConfig(**cfg), (AlignResult * max(len(p), 1))(), C.c_uint32(0xFFFFFFFF)
-        rc = _check(lib().loamx_densemap_align_many(self.h, C.byref(c), p.ctypes.data_as(C.c_void_p), C.c_uint32(len(p)),
-                                                    None if ctr is None else ctr.ctypes.data_as(C.c_void_p), C.byref(k), out, C.byref(best)))
-        return self._many_out(rc, out, len(p), best, raw)[1:]
+        keep, head, mid = self._host_cloud(points, centre)
+        return self._align_many(lib().loamx_densemap_align_many, head, poses, mid, raw, cfg)[1:]
 
     def align_many_from(self, mapping, poses=None, raw=False, **cfg):
         """loamx_densemap_align_many_from_map: the same for the registered cloud of mapping's last process, where it lies, about its
         origin; poses None: the identity alone.  Returns (status code OK / SKIPPED, results, best)"""
-        p = None if poses is None else self._poses(poses)
-        n = 1 if p is None else len(p)
-        k, out, best = AlignConfig(**cfg), (AlignResult * max(n, 1))(), C.c_uint32(0xFFFFFFFF)
-        rc = _check(lib().loamx_densemap_align_many_from_map(self.h, mapping.h, None if p is None else p.ctypes.data_as(C.c_void_p),
-                                                             C.c_uint32(n), C.byref(k), out, C.byref(best)))
-        return self._many_out(rc, out, n, best, raw)
+        return self._align_many(lib().loamx_densemap_align_many_from_map, (mapping.h,), poses, (), raw, cfg)
 
     def align_many_from_pipeline(self, pipeline, slot: int, poses=None, raw=False, **cfg):
         """loamx_densemap_align_many_from_pipeline: the same for the slot-th stream registered in pipeline's last step"""
-        p = None if poses is None else self._poses(poses)
-        n = 1 if p is None else len(p)
-        k, out, best = AlignConfig(**cfg), (AlignResult * max(n, 1))(), C.c_uint32(0xFFFFFFFF)
-        rc = _check(lib().loamx_densemap_align_many_from_pipeline(self.h, pipeline.h, C.c_uint32(slot),
-                                                                  None if p is None else p.ctypes.data_as(C.c_void_p), C.c_uint32(n),
-                                                                  C.byref(k), out, C.byref(best)))
-        return self._many_out(rc, out, n, best, raw)
+        return self._align_many(lib().loamx_densemap_align_many_from_pipeline, (pipeline.h, C.c_uint32(slot)), poses, (), raw, cfg)
 
     def align_stats(self) -> dict:
         """loamx_densemap_get_align_stats: launches of either step kernel, readbacks of accumulator words and pose-steps (the sum of
@@ -1944,44 +1934,30 @@ class DenseMap:
         """the leaf of a level (default: the selected one) as the library computes it: one f32 multiply by a power of two"""
         return float(np.float32(self._c.leaf) * np.float32(1 << (self._level if level is None else level)))
 
-    @staticmethod
-    def _pyramid_out(out, first_level):
-        return [out[k].as_dict() for k in range(first_level + 1)]
+    def _align_pyramid(self, fn, head, pose, mid, first_level, cfg):
+        # the marshalling every form of align_pyramid shares: head and mid are the arguments before and behind the pose
+        p = None if pose is None else _pose12(pose)
+        first = max(self.frozen_levels - 1, 0) if first_level is None else int(first_level)
+        k, out = AlignConfig(**cfg), (AlignResult * PYRAMID_MAX_LEVELS)()
+        rc = _check(fn(self.h, *head, self._ptr(p), *mid, C.byref(k), C.c_uint32(first), out))
+        return rc, [out[i].as_dict() for i in range(first + 1)]
 
     def align_pyramid(self, points, pose=np.eye(3, 4), centre=None, first_level=None, **cfg):
         """loamx_densemap_align_pyramid: align() against level first_level (default: the coarsest that stands), then against each
         finer level from the pose the level before reported.  Returns first_level + 1 result dicts, coarsest first; the last one is
         level 0's.  Each is what select_level(level) + align() returns from the same start; the selected level is left alone"""
-        a = as_points(points)
-        c = cloud_of(a)
-        p = _pose12(pose)
-        ctr = None if centre is None else np.ascontiguousarray(centre, np.float32)
-        assert ctr is None or ctr.shape == (3,)
-        first = max(self.frozen_levels - 1, 0) if first_level is None else int(first_level)
-        k, out = AlignConfig(**cfg), (AlignResult * PYRAMID_MAX_LEVELS)()
-        _check(lib().loamx_densemap_align_pyramid(self.h, C.byref(c), p.ctypes.data_as(C.c_void_p),
-                                                  None if ctr is None else ctr.ctypes.data_as(C.c_void_p), C.byref(k), C.c_uint32(first), out))
-        return self._pyramid_out(out, first)
+        keep, head, mid = self._host_cloud(points, centre)
+        return self._align_pyramid(lib().loamx_densemap_align_pyramid, head, pose, mid, first_level, cfg)[1]
 
     def align_pyramid_from(self, mapping, pose=None, first_level=None, **cfg):
         """loamx_densemap_align_pyramid_from_map: the same for the registered cloud of mapping's last process, where it lies, about its
         origin; pose None: identity.  Returns (status code OK / SKIPPED, results)"""
-        p = None if pose is None else _pose12(pose)
-        first = max(self.frozen_levels - 1, 0) if first_level is None else int(first_level)
-        k, out = AlignConfig(**cfg), (AlignResult * PYRAMID_MAX_LEVELS)()
-        rc = _check(lib().loamx_densemap_align_pyramid_from_map(self.h, mapping.h, None if p is None else p.ctypes.data_as(C.c_void_p),
-                                                                C.byref(k), C.c_uint32(first), out))
-        return rc, self._pyramid_out(out, first)
+        return self._align_pyramid(lib().loamx_densemap_align_pyramid_from_map, (mapping.h,), pose, (), first_level, cfg)
 
     def align_pyramid_from_pipeline(self, pipeline, slot: int, pose=None, first_level=None, **cfg):
         """loamx_densemap_align_pyramid_from_pipeline: the same for the slot-th stream registered in pipeline's last step"""
-        p = None if pose is None else _pose12(pose)
-        first = max(self.frozen_levels - 1, 0) if first_level is None else int(first_level)
-        k, out = AlignConfig(**cfg), (AlignResult * PYRAMID_MAX_LEVELS)()
-        rc = _check(lib().loamx_densemap_align_pyramid_from_pipeline(self.h, pipeline.h, C.c_uint32(slot),
-                                                                     None if p is None else p.ctypes.data_as(C.c_void_p), C.byref(k),
-                                                                     C.c_uint32(first), out))
-        return rc, self._pyramid_out(out, first)
+        return self._align_pyramid(lib().loamx_densemap_align_pyramid_from_pipeline, (pipeline.h, C.c_uint32(slot)), pose, (), first_level,
+                                   cfg)
 
     def _raycast(self, fn, head, n, max_steps, skip_steps, min_points, static, records):
         k = _cfg(RaycastConfig, "loamx_densemap_raycast_default_config", max_steps=max_steps, skip_steps=skip_steps, min_points=min_points)
@@ -2387,30 +2363,16 @@ class DenseMap:
     def align_from_history(self, call: int, pose=None, **cfg) -> dict:
         """loamx_densemap_align_from_history: align() of logged call `call` where it lies in the log, about its logged origin; pose
         None: identity.  Byte for byte align(*history(call)'s cloud, pose, centre=its origin)"""
-        p = None if pose is None else _pose12(pose)
-        k, out = AlignConfig(**cfg), AlignResult()
-        _check(lib().loamx_densemap_align_from_history(self.h, C.c_uint64(call), None if p is None else p.ctypes.data_as(C.c_void_p),
-                                                       C.byref(k), C.byref(out)))
-        return out.as_dict()
+        return self._align(lib().loamx_densemap_align_from_history, (C.c_uint64(call),), pose, (), cfg)[1]
 
     def align_many_from_history(self, call: int, poses=None, raw=False, **cfg):
         """loamx_densemap_align_many_from_history: align_many() of logged call `call` where it lies, about its logged origin; poses
         None: the identity alone.  Returns (results, best)"""
-        p = None if poses is None else self._poses(poses)
-        n = 1 if p is None else len(p)
-        k, out, best = AlignConfig(**cfg), (AlignResult * max(n, 1))(), C.c_uint32(0xFFFFFFFF)
-        rc = _check(lib().loamx_densemap_align_many_from_history(self.h, C.c_uint64(call), None if p is None else p.ctypes.data_as(C.c_void_p),
-                                                                 C.c_uint32(n), C.byref(k), out, C.byref(best)))
-        return self._many_out(rc, out, n, best, raw)[1:]
+        return self._align_many(lib().loamx_densemap_align_many_from_history, (C.c_uint64(call),), poses, (), raw, cfg)[1:]
 
     def align_pyramid_from_history(self, call: int, pose=None, first_level=None, **cfg):
         """loamx_densemap_align_pyramid_from_history: align_pyramid() of logged call `call` where it lies, about its logged origin"""
-        p = None if pose is None else _pose12(pose)
-        first = max(self.frozen_levels - 1, 0) if first_level is None else int(first_level)
-        k, out = AlignConfig(**cfg), (AlignResult * PYRAMID_MAX_LEVELS)()
-        _check(lib().loamx_densemap_align_pyramid_from_history(self.h, C.c_uint64(call), None if p is None else p.ctypes.data_as(C.c_void_p),
-                                                               C.byref(k), C.c_uint32(first), out))
-        return self._pyramid_out(out, first)
+        return self._align_pyramid(lib().loamx_densemap_align_pyramid_from_history, (C.c_uint64(call),), pose, (), first_level, cfg)[1]
 
     def rebuild_stats(self) -> dict:
         s = (C.c_uint64 * 4)()
@@ -2485,27 +2447,26 @@ class PlaceDB:
         assert o.shape == (3,)
         return o
 
+    def _add(self, fn, *head):
+        # the new entry's id, or None when the source had no cloud
+        i = C.c_uint32(0)
+        rc = _check(fn(self.h, *head, C.byref(i)))
+        return int(i.value) if rc == OK else None
+
     def add(self, points, origin=(0.0, 0.0, 0.0)) -> int:
         """describe an (N, 4) / (N, 8) cloud about origin and store it; returns the new entry's id.  LoamxError E_CAPACITY when
         max_entries would be passed (the database is then unchanged)"""
         a = as_points(points)
-        c = cloud_of(a)
         o = self._origin(origin)
-        i = C.c_uint32(0)
-        _check(lib().loamx_place_add(self.h, C.byref(c), o.ctypes.data_as(C.c_void_p), C.byref(i)))
-        return int(i.value)
+        return self._add(lib().loamx_place_add, C.byref(cloud_of(a)), o.ctypes.data_as(C.c_void_p))
 
     def add_from(self, mapping):
         """the registered full-resolution cloud of mapping's last process / process_linked: the new id, or None when it produced none"""
-        i = C.c_uint32(0)
-        rc = _check(lib().loamx_place_add_from_map(self.h, mapping.h, C.byref(i)))
-        return int(i.value) if rc == OK else None
+        return self._add(lib().loamx_place_add_from_map, mapping.h)
 
     def add_from_pipeline(self, pipeline, slot: int):
         """the registered cloud of the slot-th stream registered in pipeline's last step: the new id, or None when it registered none"""
-        i = C.c_uint32(0)
-        rc = _check(lib().loamx_place_add_from_pipeline(self.h, pipeline.h, slot, C.byref(i)))
-        return int(i.value) if rc == OK else None
+        return self._add(lib().loamx_place_add_from_pipeline, pipeline.h, slot)
 
     @staticmethod
     def _matches(m, n):

@@ -32,7 +32,7 @@ static int run_log(uint64_t max_bytes, uint64_t initial_points) {
       unsigned long long n;
       float o[3];
       if (scanf("%llu %f %f %f", &n, &o[0], &o[1], &o[2]) != 4) return 2;
-      // DenseMap::add_host / add_device: the cap first, then (a call that reaches the insert) the block, the copy, the record
+      // DenseMap::add: the cap first, then (a call that reaches the insert) the block, the copy, the record
       admitted = h.admits(n) ? 1 : 0;
       if (admitted && n) {
         const uint64_t want = h.capacity_for(n);

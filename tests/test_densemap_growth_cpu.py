@@ -90,7 +90,7 @@ class Old:
             self.slots_ = want
         return True
 
-    def add(self, n, v):                   # add_host / add_device, then enqueue_add
+    def add(self, n, v):                   # DenseMap::add, then enqueue_add
         self.admitted = int(self.admit(n, v))
         if not self.admitted:
             return
