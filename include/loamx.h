@@ -1620,6 +1620,114 @@ int loamx_densemap_dist_query(loamx_densemap* h, const loamx_cloud* points, uint
 int loamx_dist_near_unpack(uint32_t near, uint32_t* rx, uint32_t* ry, uint32_t* rz);   /* host only */
 double loamx_dist_metres(uint32_t d2, float leaf, uint32_t cell_leaves);               /* host only */
 
+/* Signed distance along the sweep rays, and a triangle mesh of it (optional: a handle that never calls loamx_densemap_tsdf_* or
+ * loamx_densemap_mesh runs the kernels it ran, allocates what it allocated and exports the same bytes).  "Where is the surface?":
+ * every ray of a sweep adds its signed distance to the cells it crosses near its end, as integers; the zero crossing of the
+ * averaged field is extracted on the device as an indexed triangle mesh.  Every stored word is an integer sum: the field depends on
+ * neither the thread schedule, the order of the points nor the split into calls (ray_stride counts i per call), and the mesh is one
+ * fixed byte string.  All f32 arithmetic below is without fused multiply-add; / and sqrtf are correctly rounded.
+ *
+ * The field.  A window of nx * ny * nz cells of one voxel each: voxel (ix, iy, iz) with (rx, ry, rz) = (ix - x0, iy - y0, iz - z0)
+ * inside [0, nx) x [0, ny) x [0, nz) is record (rz * ny + ry) * nx + rx.  Each cell holds W (uint32_t) and D (int64_t, two's
+ * complement).  tau = trunc_leaves * leaf in f32; inv = 1.0f / leaf as the adds have it.
+ * loamx_densemap_tsdf_begin: allocates the volume in the handle (12 bytes per cell; it grows to the largest window asked for and is
+ * freed on destroy) or clears the one that stands, and clears the statistics.  loamx_densemap_reset drops the field.
+ * Integration of point i of a call, p, with the call's origin o:
+ *   - i % ray_stride != 0: not traced (stride).
+ *   - d = p - o per axis, d2 = (dx*dx + dy*dy) + dz*dz; the insert's range filter with this configuration's min_range and max_range
+ *     (d2 >= min_range*min_range, and d2 <= max_range*max_range when max_range > 0) and the key rule |floorf(p_a * inv)| < 2^20 on
+ *     every axis; a point that fails either is not traced (filter).
+ *   - len = sqrtf(d2); len == 0: dropped (zero length).
+ *   - u_a = d_a / len;  back = free_space ? len : fminf(tau, len);  s_a = p_a - u_a * back;  e_a = p_a + u_a * tau.
+ *   - the walk is carving's walk (above) from s to e instead of from the origin to the point: per axis so = s_a * inv, sp = e_a * inv,
+ *     c = (int)floorf(so), the step sign, rem = |(int)floorf(sp) - c|, tmax and tdelta as there; n_steps = the sum of the three rem.
+ *     A ray with n_steps > max_steps, or whose start cell fails the key rule (a NaN fails it), is not traced (steps or key).
+ *   - all n_steps + 1 cells k = 0 .. n_steps are visited, both ends included; a visited cell outside the window is skipped.
+ *   - a visited cell inside, with indices c and centre m_a = ((float)c_a + 0.5f) * leaf:
+ *       sd = ((p_x - m_x) * u_x + (p_y - m_y) * u_y) + (p_z - m_z) * u_z
+ *       r  = fminf(fmaxf(sd / tau, -1.f), 1.f)
+ *       q  = (int)rintf(r * 1024.0f)                      (ties to even)
+ *       W += 1 and D += q, both device atomics.
+ * Positive is in front of the surface, toward the sensor.  With free_space = 1 the whole ray is walked and every cell between the
+ * sensor and the band receives +1024: what moved away is averaged out by the rays that later pass through it.  Every later step
+ * is exact while each cell's W < 2^25: then |D| <= 2^35 and the cross products of the mesh fit a signed 64-bit integer.
+ * Sources, the four standard forms: loamx_densemap_tsdf_add (a cloud from the host and its origin), _add_from_map and
+ * _add_from_pipeline (the registered cloud where it lies, as loamx_densemap_add_from_*; LOAMX_SKIPPED when there is none) and
+ * _add_from_history: the logged calls [first_call, first_call + n_calls) where they lie, in one launch, call k of the window under
+ * corrections[12 * k ..] (rebuild's per-call table: rounded to f32 once, the identity rule, the origin corrected by the same
+ * expression; NULL: identities).  It needs history (loamx_densemap_enable_history), neither carving nor moments.  None of the
+ * four touches the live map, the log or their statistics; the kernels run on the map's own stream behind the source and return
+ * without a host wait (the history form waits).  They answer LOAMX_E_INVALID without a field.
+ * loamx_densemap_tsdf_download: waits and returns the planes (either pointer may be NULL) and stats since _begin: [0] rays
+ * traced, not traced by [1] stride, [2] filter, [3] step count or key, [4] zero length, [5] cells visited inside the window,
+ * [6] cells with W > 0, [7] the largest W.  [0] + ... + [4] is the number of points offered.
+ * loamx_densemap_tsdf_check (host only): LOAMX_OK, or LOAMX_E_INVALID naming the first field out of its bounds, in the order x0, y0,
+ * z0, nx, ny, nz, nx * ny * nz, trunc_leaves, free_space, ray_stride, max_steps, min_range, max_range.
+ * loamx_densemap_tsdf_window (host only): x0, nx, ... of the window about centre[3] with half_extent[3] in metres, per axis in
+ * double lo = floor(((double)c - (double)h) / (double)leaf), hi = floor(((double)c + (double)h) / (double)leaf), first = lo,
+ * count = max(hi - lo + 1, 2).  LOAMX_E_INVALID, cfg unchanged, as loamx_densemap_dist_window.
+ *
+ * The mesh: marching tetrahedra over the lattice of cell centres.  A cell is valid when W >= min_weight; a valid cell is inside
+ * when D < 0 (an integer test: D == 0 is outside).
+ * A cube is the 8 cells (x + bx, y + by, z + bz), corner number bx | by << 1 | bz << 2, for every lower cell with rx < nx - 1,
+ * ry < ny - 1, rz < nz - 1.  Its six tetrahedra 0..5 follow the axis orders (1,2,4), (1,4,2), (2,1,4), (2,4,1), (4,1,2), (4,2,1):
+ * order (a,b,c) has corners t0 = 0, t1 = a, t2 = a|b, t3 = 7 and parity f = 0,1,1,0,0,1 respectively.  A tetrahedron is processed
+ * iff its four cells are valid (a cube need not be complete).  Every edge (t_i, t_j), i < j, runs from a cell to one that is larger
+ * in each coordinate where they differ: seven directions x, y, xy, z, xz, yz, xyz numbered e = (t_j ^ t_i) - 1; the lower cell owns
+ * the edge.
+ * Triangles, with k the number of inside corners and E(i,j) the vertex on the edge between t_i and t_j:
+ *   k = 0, 4: none.
+ *   k = 1, 3: a = the position of the one inside (k = 3: the one outside) corner, o0 < o1 < o2 the other three positions; the
+ *             triangle E(a,o0), E(a,o1), E(a,o2), its last two swapped when f + a + [k = 3] is odd.
+ *   k = 2:    inside positions a < b, outside c < d; the quad q = E(a,c), E(a,d), E(b,d), E(b,c), reversed (q3, q2, q1, q0) when
+ *             f + the number of inversions of the sequence (a,b,c,d) is odd; triangles (q0,q1,q2) and (q0,q2,q3).
+ * (v1 - v0) x (v2 - v0) points to the positive side, free space.
+ * Vertices: an edge (A, B), A its owner, used by at least one emitted triangle has one vertex.  N = D_A * W_B and
+ * M = N - D_B * W_A as exact int64; t = (double)N / (double)M; per axis m_A = ((double)c_A + 0.5) * (double)leaf, m_B likewise,
+ * v = (float)(m_A + t * (m_B - m_A)), no fused multiply-add.  axes: 0 LOAM frame (x, y, z), 1 sensor axes (z, x, y).
+ * Order: vertices ascend by (owner's record, e); triangles by (cube's lower-cell record, tetrahedron, triangle).  verts: 3 f32
+ * per vertex; tris: 3 uint32_t per triangle.
+ * loamx_densemap_mesh: behind every tsdf add, four kernels and two scans on the map's own stream; the host reads the two totals to
+ * size the buffers and nothing else crosses until the result does.  *n_verts and *n_tris are written even on LOAMX_E_CAPACITY
+ * (cap_v < vertices or cap_t < triangles), and nothing else is then.  verts and tris both NULL with zero capacities: the counts
+ * and the stats only.  stats: [0] valid cells, [1] inside cells, [2] tetrahedra processed, [3] tetrahedra with an invalid corner
+ * and a sign change among their valid corners (holes), [4] vertices, [5] triangles.  An empty field is LOAMX_OK with zero counts.
+ * LOAMX_E_INVALID, nothing written: NULL h, n_verts, n_tris or stats; one of verts, tris NULL and not the other; min_weight 0;
+ * axes not 0 or 1; no field.
+ * loamx_write_ply (host only): binary little-endian PLY, float x y z per vertex and list uchar int vertex_indices per face.
+ * loamx_densemap_save_ply: loamx_densemap_mesh, then loamx_write_ply. */
+typedef struct loamx_densemap_tsdf_config {
+  int32_t  x0, y0, z0;      /* first voxel index of the window, each in [-2^21, 2^21] (default -64) */
+  uint32_t nx, ny, nz;      /* 2..1024 each, nx * ny * nz <= 2^26 (default 128) */
+  float    trunc_leaves;    /* 1..16: tau = trunc_leaves * leaf (default 3) */
+  uint32_t free_space;      /* 0: the band only (default); 1: the whole ray */
+  uint32_t ray_stride;      /* >= 1 (default 1) */
+  uint32_t max_steps;       /* 1..65536 (default 4096) */
+  float    min_range;       /* >= 0 (default 0) */
+  float    max_range;       /* 0: none (default), else >= min_range */
+} loamx_densemap_tsdf_config;
+typedef struct loamx_densemap_mesh_config {
+  uint32_t min_weight;      /* >= 1 (default 2) */
+  int32_t  axes;            /* 0 or 1 (default 0) */
+} loamx_densemap_mesh_config;
+void loamx_densemap_tsdf_default_config(loamx_densemap_tsdf_config* cfg);   /* host only */
+int loamx_densemap_tsdf_check(const loamx_densemap_tsdf_config* cfg);        /* host only */
+int loamx_densemap_tsdf_window(float leaf, const float centre[3], const float half_extent[3], loamx_densemap_tsdf_config* cfg);   /* host only */
+int loamx_densemap_tsdf_begin(loamx_densemap* h, const loamx_densemap_tsdf_config* cfg /* NULL: the defaults */);
+int loamx_densemap_tsdf_add(loamx_densemap* h, const loamx_cloud* cloud, const float origin[3]);
+int loamx_densemap_tsdf_add_from_map(loamx_densemap* h, loamx_map* m);
+int loamx_densemap_tsdf_add_from_pipeline(loamx_densemap* h, loamx_pipeline* p, uint32_t slot);
+int loamx_densemap_tsdf_add_from_history(loamx_densemap* h, uint64_t first_call, uint64_t n_calls,
+                                         const double* corrections /* 12 * n_calls; NULL: identities */);
+int loamx_densemap_tsdf_download(loamx_densemap* h, uint32_t* out_w /* nx * ny * nz; NULL: not wanted */,
+                                 int64_t* out_d /* nx * ny * nz; NULL: not wanted */, uint64_t stats[8]);
+void loamx_densemap_mesh_default_config(loamx_densemap_mesh_config* cfg);   /* host only */
+int loamx_densemap_mesh(loamx_densemap* h, const loamx_densemap_mesh_config* cfg /* NULL: the defaults */, float* verts, uint64_t cap_v,
+                        uint32_t* tris, uint64_t cap_t, uint64_t* n_verts, uint64_t* n_tris, uint64_t stats[6]);
+int loamx_write_ply(const char* path, const float* verts, uint64_t n_verts, const uint32_t* tris, uint64_t n_tris);   /* host only */
+int loamx_densemap_save_ply(loamx_densemap* h, const loamx_densemap_mesh_config* cfg /* NULL: the defaults */, const char* path,
+                            uint64_t stats[6]);
+
 /* Objects: connected components of the voxel map (optional: a handle that never segments runs the kernels it ran and allocates what
  * it allocated).  "Which voxels belong together?": on the voxel lattice, Euclidean clustering with a tolerance of one leaf is
  * connected-component labelling of the selected voxels, done on the device where the table lies; a component list and one word

@@ -212,6 +212,7 @@ void DenseMap::reset() {
   frozen.drop();
   drop_coarse();
   dist_.drop();
+  tsdf_.drop();
   occ_.reset();
   offered_ = drop_range_ = drop_key_ = 0;
   for (uint64_t& c : carve_ctr_) c = 0;

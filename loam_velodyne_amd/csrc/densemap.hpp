@@ -358,6 +358,38 @@ class DmDist {
   bool valid_ = false;
 };
 
+// include/loamx.h, loamx_densemap_tsdf_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
+void dm_tsdf_check(const loamx_densemap_tsdf_config& c);
+
+constexpr int DM_TSDF_CTR = 8;   // counter words of the field: [0] traced, [2] filter, [3] steps or key, [4] zero length, [5] visited
+                                 // inside, and at a download [6] cells with W > 0, [7] the largest W ([1], stride, is the host's)
+
+// Signed distance field and its mesh (include/loamx.h, loamx_densemap_tsdf_* and loamx_densemap_mesh; densemap_mesh.hip): per cell
+// of the window 4 bytes of W and 8 of D and, from the first mesh on, one byte of edge bits and 4 bytes of vertex base; the counters,
+// the per-block counts of the two scans and the mesh's buffers.  Allocated by loamx_densemap_tsdf_begin and by the first mesh, grow
+// to the largest window asked for; the live map and its log are only read.
+struct DmTsdf {
+  DmTsdf() = default;
+  DmTsdf(const DmTsdf&) = delete;
+  DmTsdf& operator=(const DmTsdf&) = delete;
+  bool has_field() const { return valid_; }
+  void drop() { valid_ = false; }   // (the buffers stay for the next field)
+  size_t cells() const { return (size_t)cfg_.nx * cfg_.ny * cfg_.nz; }
+
+  DmCloudStage cloud;                 // a cloud from the host, in the feature's own device block (the adds do not block: guarded)
+  DevBuf<uint32_t> w_;                // per cell: W
+  DevBuf<unsigned long long> d_;      // per cell: D, two's complement
+  DevBuf<unsigned long long> ctr_;    // DM_TSDF_CTR words, then the mesh's four (valid, inside, tetrahedra, holes)
+  DevBuf<uint32_t> mask_;             // per cell one byte, four cells per word: bit e = the edge e of this owner has a vertex
+  DevBuf<uint32_t> vbase_;            // per cell: the index of its first vertex
+  DevBuf<uint32_t> blk_;              // two runs of blocks + 1 words: triangles, then vertices, per 256-cell block
+  DevBuf<float> verts_;
+  DevBuf<uint32_t> tris_;
+  loamx_densemap_tsdf_config cfg_ = {};   // of the field that stands
+  uint64_t stride_skipped_ = 0;           // stats[1]: decided on the host, per call
+  bool valid_ = false;
+};
+
 // include/loamx.h, loamx_densemap_segment_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
 void dm_segment_check(const loamx_densemap_segment_config& c);
 

@@ -159,6 +159,15 @@ class DenseMap {
   void dist(const loamx_densemap_dist_config& c, const loamx_densemap_static_rule* rule, uint16_t* out_d2, uint32_t* out_near,
             uint64_t stats[4]);
   int dist_query(const loamx_cloud* points, uint32_t min_d2, loamx_dist_sample* out, uint64_t capacity, uint64_t stats[5]);
+  // ---- densemap_mesh.hip: include/loamx.h, loamx_densemap_tsdf_* and loamx_densemap_mesh; checked configurations.  The field
+  // stays in tsdf_ until the next tsdf_begin, reset or destroy; everything runs on own_
+  void tsdf_begin(const loamx_densemap_tsdf_config& c);
+  int tsdf_add(const DenseSource& s);
+  int tsdf_add_history(uint64_t first_call, uint64_t n_calls, const double* corrections);
+  void tsdf_download(uint32_t* out_w, int64_t* out_d, uint64_t stats[8]);
+  int mesh(const loamx_densemap_mesh_config& c, float* verts, uint64_t cap_v, uint32_t* tris, uint64_t cap_t, uint64_t* n_verts,
+           uint64_t* n_tris, uint64_t stats[6]);
+  DmCloudStage& tsdf_stage() { return tsdf_.cloud; }
   int segment(const loamx_densemap_segment_config& c, const loamx_densemap_static_rule& rule, uint32_t* labels, uint64_t label_capacity,
               uint64_t* n_voxels, loamx_segment* segs, uint64_t seg_capacity, uint64_t* n_segs, uint64_t stats[6]);
   // ---- densemap_segment_cloud.hip: include/loamx.h, loamx_densemap_segment_cloud and its from_* forms: the objects of the cloud of
@@ -199,6 +208,7 @@ class DenseMap {
   DmCaster caster_;   // densemap_raycast.hip
   DmGrid grid_;       // densemap_grid.hip
   DmDist dist_;       // densemap_dist.hip
+  DmTsdf tsdf_;       // densemap_mesh.hip
   DmRoute route_;     // densemap_route.hip
   DmFrontier fr_;     // densemap_frontier.hip (routes towards the start through route_)
   DmSegment seg_;     // densemap_segment.hip

@@ -1534,6 +1534,45 @@ def dist_metres(d2, leaf: float, cell_leaves: int) -> float:
     return float(fn(C.c_uint32(int(d2)), C.c_float(leaf), C.c_uint32(cell_leaves)))
 
 
+class TsdfConfig(_DefaultedConfig, C.Structure):
+    """loamx_densemap_tsdf_config: the window of one-voxel cells (x0, y0, z0, nx, ny, nz), the truncation in leaves, whether the
+    whole ray is integrated (free_space), the ray stride, the step limit and the range filter of the signed distance field.
+    TsdfConfig() holds the defaults (-64, -64, -64; 128^3; 3 leaves; band only; stride 1; 4096 steps; no range limits); keyword
+    arguments replace them."""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32), ("nx", C.c_uint32), ("ny", C.c_uint32), ("nz", C.c_uint32),
+                ("trunc_leaves", C.c_float), ("free_space", C.c_uint32), ("ray_stride", C.c_uint32), ("max_steps", C.c_uint32),
+                ("min_range", C.c_float), ("max_range", C.c_float)]
+
+    _default, _checker = "loamx_densemap_tsdf_default_config", "loamx_densemap_tsdf_check"
+
+
+class MeshConfig(C.Structure):
+    """loamx_densemap_mesh_config: min_weight (a cell is valid when W >= min_weight) and axes (0: LOAM frame, 1: sensor axes)"""
+    _fields_ = [("min_weight", C.c_uint32), ("axes", C.c_int32)]
+
+
+TSDF_STATS = ("traced", "skipped_stride", "skipped_filter", "skipped_steps", "zero_length", "cells_visited", "cells_set", "max_weight")
+MESH_STATS = ("valid", "inside", "tetrahedra", "holes", "vertices", "triangles")     # stats[6] of loamx_densemap_mesh
+
+
+def tsdf_window(leaf, x, y, z, half_extent_xyz, **fields) -> TsdfConfig:
+    """loamx_densemap_tsdf_window (host only): a TsdfConfig (defaults and fields otherwise) whose window covers (x, y, z) +-
+    half_extent_xyz metres (LOAM frame; one number serves the three axes).  LoamxError E_INVALID when it breaks a bound of the check."""
+    c = TsdfConfig(**fields)
+    centre = (C.c_float * 3)(x, y, z)
+    half = (C.c_float * 3)(*np.broadcast_to(np.asarray(half_extent_xyz, np.float32), (3,)).tolist())
+    _check(lib().loamx_densemap_tsdf_window(C.c_float(leaf), centre, half, C.byref(c)))
+    return c
+
+
+def write_ply(path: str, verts, tris):
+    """loamx_write_ply (host only): (V, 3) float32 vertices and (T, 3) uint32 indices as a binary little-endian PLY file"""
+    v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+    _check(lib().loamx_write_ply(os.fsencode(path), v.ctypes.data_as(C.c_void_p) if len(v) else None, C.c_uint64(len(v)),
+                                 t.ctypes.data_as(C.c_void_p) if len(t) else None, C.c_uint64(len(t))))
+
+
 SEGMENT_NONE = 0xffffffff                                                         # label of a voxel in no kept component
 SEGMENT_ALL, SEGMENT_STATIC, SEGMENT_DYNAMIC = range(3)                           # loamx_densemap_segment_config.which
 
@@ -2046,6 +2085,71 @@ class DenseMap:
         _check(lib().loamx_densemap_dist_query(self.h, C.byref(c), C.c_uint32(min_d2), out.ctypes.data_as(C.c_void_p) if records else None,
                                                C.c_uint64(len(a)), st))
         return (out[:len(a)] if records else None), dict(zip(DIST_QUERY_STATS, (int(v) for v in st)))
+
+    def tsdf_begin(self, cfg=None, **fields):
+        """loamx_densemap_tsdf_begin: a zeroed signed distance field over the window of cfg (a TsdfConfig, None: the defaults;
+        tsdf_window() makes one around a position; fields replace members of a copy of it), kept in the handle.  Returns the
+        configuration used"""
+        c = (TsdfConfig() if cfg is None else cfg).copy(**fields).check()
+        _check(lib().loamx_densemap_tsdf_begin(self.h, C.byref(c)))
+        return c
+
+    def tsdf_add(self, points, origin=(0.0, 0.0, 0.0)):
+        """loamx_densemap_tsdf_add: the rays from origin to map-frame points (N, 4) / (N, 8) into the field; does not wait"""
+        a = as_points(points)
+        c = cloud_of(a)
+        o = np.ascontiguousarray(origin, np.float32)
+        assert o.shape == (3,)
+        return _check(lib().loamx_densemap_tsdf_add(self.h, C.byref(c), o.ctypes.data_as(C.c_void_p)))
+
+    def tsdf_add_from(self, mapping):
+        """loamx_densemap_tsdf_add_from_map: the registered cloud of mapping's last process (SKIPPED when it produced none)"""
+        return _check(lib().loamx_densemap_tsdf_add_from_map(self.h, mapping.h))
+
+    def tsdf_add_from_pipeline(self, pipeline, slot: int):
+        """loamx_densemap_tsdf_add_from_pipeline: the registered cloud of the slot-th stream of pipeline's last step"""
+        return _check(lib().loamx_densemap_tsdf_add_from_pipeline(self.h, pipeline.h, slot))
+
+    def tsdf_add_history(self, first: int, n: int, corrections=None):
+        """loamx_densemap_tsdf_add_from_history: the logged calls first .. first + n - 1 where they lie in the log, in one launch,
+        call k of the window moved by corrections[k] (row-major 3x4 or 4x4, map <- map, float64; None: where they were)"""
+        p = None
+        if corrections is not None:
+            a = np.asarray(corrections, np.float64)
+            a = np.ascontiguousarray(a.reshape(-1, *a.shape[-2:])[:, :3, :4] if a.size else a.reshape(0, 3, 4))
+            assert a.ndim == 3 and a.shape[1:] == (3, 4) and a.shape[0] == n, "corrections must be (n, 3, 4) or (n, 4, 4)"
+            p = a.ctypes.data_as(C.c_void_p)
+        return _check(lib().loamx_densemap_tsdf_add_from_history(self.h, C.c_uint64(first), C.c_uint64(n), p))
+
+    def tsdf(self, cfg: TsdfConfig, want_w=True, want_d=True):
+        """loamx_densemap_tsdf_download: waits; (W, D, stats) with W uint32 and D int64 as (nz, ny, nx) arrays of the window of cfg
+        (what tsdf_begin returned; None for a plane not wanted) and a dict in the order of TSDF_STATS"""
+        w = np.zeros((cfg.nz, cfg.ny, cfg.nx), np.uint32) if want_w else None
+        d = np.zeros((cfg.nz, cfg.ny, cfg.nx), np.int64) if want_d else None
+        st = (C.c_uint64 * 8)()
+        _check(lib().loamx_densemap_tsdf_download(self.h, w.ctypes.data_as(C.c_void_p) if want_w else None,
+                                                  d.ctypes.data_as(C.c_void_p) if want_d else None, st))
+        return w, d, dict(zip(TSDF_STATS, (int(v) for v in st)))
+
+    def mesh(self, min_weight=None, axes="loam", count_only=False):
+        """loamx_densemap_mesh: the zero crossing of the field as an indexed triangle mesh, extracted on the device: (verts (V, 3)
+        float32, tris (T, 3) uint32, stats in the order of MESH_STATS); count_only: (V, T, stats), nothing else crosses"""
+        c = _cfg(MeshConfig, "loamx_densemap_mesh_default_config", axes=_axes(axes), **({} if min_weight is None else dict(min_weight=min_weight)))
+        nv, nt, st = C.c_uint64(0), C.c_uint64(0), (C.c_uint64 * 6)()
+        _check(lib().loamx_densemap_mesh(self.h, C.byref(c), None, C.c_uint64(0), None, C.c_uint64(0), C.byref(nv), C.byref(nt), st))
+        if count_only:
+            return int(nv.value), int(nt.value), dict(zip(MESH_STATS, (int(v) for v in st)))
+        v, t = np.zeros((max(nv.value, 1), 3), np.float32), np.zeros((max(nt.value, 1), 3), np.uint32)
+        _check(lib().loamx_densemap_mesh(self.h, C.byref(c), v.ctypes.data_as(C.c_void_p), C.c_uint64(nv.value), t.ctypes.data_as(C.c_void_p),
+                                         C.c_uint64(nt.value), C.byref(nv), C.byref(nt), st))
+        return v[:nv.value], t[:nt.value], dict(zip(MESH_STATS, (int(v) for v in st)))
+
+    def save_ply(self, path: str, min_weight=None, axes="loam") -> dict:
+        """loamx_densemap_save_ply: mesh(), written as a binary little-endian PLY file; returns the stats"""
+        c = _cfg(MeshConfig, "loamx_densemap_mesh_default_config", axes=_axes(axes), **({} if min_weight is None else dict(min_weight=min_weight)))
+        st = (C.c_uint64 * 6)()
+        _check(lib().loamx_densemap_save_ply(self.h, C.byref(c), os.fsencode(path), st))
+        return dict(zip(MESH_STATS, (int(v) for v in st)))
 
     ROUTE_STATS = ("traversable", "reachable", "goals_used", "max_cost", "rounds", "tile_runs")
 
