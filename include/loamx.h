@@ -1620,6 +1620,101 @@ int loamx_densemap_dist_query(loamx_densemap* h, const loamx_cloud* points, uint
 int loamx_dist_near_unpack(uint32_t near, uint32_t* rx, uint32_t* ry, uint32_t* rz);   /* host only */
 double loamx_dist_metres(uint32_t d2, float leaf, uint32_t cell_leaves);               /* host only */
 
+/* Routing in 3-D over the distance field (optional: a handle that never calls loamx_densemap_route3* runs the kernels it ran and
+ * allocates what it allocated; loamx_densemap_dist, loamx_densemap_dist_query, the route calls and the frontier calls return the
+ * bytes they returned).  "How does a flying or tall body get there?": the cost-to-go of every cell of a 3-D window towards a set of
+ * goal cells, the next step per cell, and routes traced from many starts, computed on the device over the d2 plane of the distance
+ * field where it lies; only what is asked for comes back.  The input is integer (d2) and so is the answer: shortest-path costs over
+ * integer move costs are a unique fixed point that depends on neither the thread schedule, the number of relaxation rounds nor the
+ * rounds per look.
+ *
+ * Cells, window, record index: those of the distance-field section.  A cell is (rx, ry, rz), window-relative, its record
+ * (rz * ny + ry) * nx + rx.  Routing needs nx * ny * nz <= 2^22; the per-axis limits of loamx_densemap_dist_check stay.
+ * Weight of a cell, w(c), from its d2 alone (the capped value (d_max + 1)^2 is a number like any other): w = 0 (blocked) when
+ * d2 < min_d2; otherwise w = 1 + p, p = floor(soft_weight * (soft_d2 - d2) / soft_d2) when d2 < soft_d2, else 0.  So w is 0, or
+ * 1..16.  loamx_route3_weight (host only) is this expression: 0..16, or a negative error for NULL or a configuration that fails its
+ * check.  An occupied cell (d2 == 0) is always blocked, because min_d2 >= 1; a min_d2 above every d2 of the window blocks every
+ * cell and is still LOAMX_OK.
+ * Moves: direction d = 0..25 is (dx, dy, dz), in this order:
+ *   axial, d = 0..5: (1,0,0) (-1,0,0) (0,1,0) (0,-1,0) (0,0,1) (0,0,-1);
+ *   face diagonals, d = 6..17: (1,1,0) (-1,1,0) (1,-1,0) (-1,-1,0) (1,0,1) (-1,0,1) (1,0,-1) (-1,0,-1) (0,1,1) (0,-1,1) (0,1,-1)
+ *   (0,-1,-1);
+ *   space diagonals, d = 18 + i, i = 0..7: dx = i & 1 ? -1 : 1, dy = i & 2 ? -1 : 1, dz = i & 4 ? -1 : 1.
+ * connectivity 6, 18 or 26 uses the directions d < connectivity: each connectivity is a prefix, and next prefers the straighter
+ * move.  loamx_route3_move (host only) is this table.
+ * A move a -> b is legal when b lies in the window, w(a) > 0 and w(b) > 0 and no corner is cut: every cell a + (sx, sy, sz) with
+ * sx in {0, dx}, sy in {0, dy}, sz in {0, dz} has w > 0, which is two more cells for a face diagonal and six more for a space
+ * diagonal.  Its cost is s * (w(a) + w(b)), s = 5, 7, 9 for one, two or three non-zero components: 10 / 14 / 18 on unit weights,
+ * symmetric, and in the units of the 2-D field, so that a route that stays in a plane costs what the 2-D route costs.
+ * Overflow: a move costs at most 9 * 32 = 288 and a path visits a cell at most once, so cost < 2^22 * 288 < 2^31.
+ * Goals: n_goals triples (rx, ry, rz), 1 <= n_goals <= 4096.  A triple outside the window or on a blocked cell is ignored and not
+ * counted in stats[2]; a cell named twice counts twice.  With no goal left every cell is unreachable and the call is still LOAMX_OK.
+ * Field: one loamx_route_cell per cell (the 8-byte record of the routing section).  cost = the smallest sum of move costs to any
+ * used goal, LOAMX_ROUTE_UNREACHABLE for a blocked cell or one with no path.  next = LOAMX_ROUTE3_GOAL when cost == 0,
+ * LOAMX_ROUTE3_NONE when unreachable, otherwise the smallest d whose move c -> nb is legal and has cost[nb] + move == cost[c]; it
+ * is derived from the final costs in a pass of its own.
+ * stats[6]: traversable cells (w > 0);  reachable cells;  goals used;  the largest finite cost (0: none);  relaxation rounds
+ * launched;  brick runs that did work (a brick: 8 x 8 x 8 cells).  The first four are part of the definition and exact, the last
+ * two describe the schedule.
+ *
+ * loamx_densemap_route3: runs the distance field of dist_cfg / rule exactly as loamx_densemap_dist does with both planes NULL; that
+ * field replaces the standing one and stays for loamx_densemap_dist_query; then routes on its d2 where it lies, with nothing stale.
+ * loamx_densemap_route3_last: routes on the distance field that stands; LOAMX_E_INVALID when there is none.
+ * loamx_densemap_route3_cells: the same on a d2 plane of the caller's, nx * ny * nz values in record order (an earlier field
+ * painted with no-fly zones, or a hand-made one), uploaded to a buffer of the route's own; the standing distance field is neither
+ * replaced nor disturbed.
+ * loamx_densemap_route3_trace: routes over the field of this handle's last successful route3 call, traced on the device; only the
+ * routes come back.  A route is the list of cells from the start, following next, up to and including the goal cell.  lengths[i]
+ * is the full number of cells of route i, 0 when the start is outside the window or unreachable.  Of a route longer than capacity
+ * only the first capacity triples are written; lengths[i] still holds the full length.  Start i's slice of out_xyz begins at
+ * 3 * capacity * i; the words beyond its route are left untouched.
+ * loamx_route3_trace (host only): the same walk over a field the caller holds, the same bytes.  It stops with LOAMX_E_INVALID,
+ * nothing written, on a field that is not one of ours: a next above 27, a step that leaves the window, a step to a cell whose cost
+ * is not strictly smaller (which also bounds the walk by nx * ny * nz steps), a route that ends on a cell that is no goal.
+ * loamx_route3_points (host only): the cell centres of a route in metres, LOAM frame: per axis
+ * x = (float)(((double)x0 + rx + 0.5) * (double)leaf * k).
+ * loamx_densemap_dist_cell_of (host only): the cell of a position: in double, rx = floor((double)x / ((double)leaf * k)) - x0, y
+ * and z alike; *inside = 0, r untouched, when the cell is outside the window.
+ * Ordering: the route3 calls wait for the adds as loamx_densemap_dist does, run on the map's own stream, change nothing in the map
+ * and block until what was asked for is back through pinned memory.  Integer atomics only.  The planes (13 bytes per cell beside
+ * the distance field's) live in the handle, are allocated by the first route3 call, grow to the largest window asked for and are
+ * freed on destroy.  loamx_densemap_reset drops the route3 field, as it drops the distance field.
+ * LOAMX_E_INVALID, with a message that names the argument, nothing written to any output: NULL h, goals_xyz, starts_xyz, lengths,
+ * d2, or out_xyz with capacity > 0;  n_goals or n_starts outside 1..4096;  a configuration that fails loamx_route3_check;
+ * everything loamx_densemap_dist refuses (but for its stats);  nx * ny * nz > 2^22;  an axis outside 1..1024 in route3_cells;
+ * route3_last on a handle that has no distance field;  route3_trace on a handle that has no route3 field (none yet, or a reset
+ * since).  LOAMX_E_INTERNAL: the relaxation did not settle within nx * ny * nz + 2 rounds, which the kernel's invariant excludes.
+ * loamx_route3_check (host only): names the first field out of its bounds, in the order of the struct. */
+#define LOAMX_ROUTE3_GOAL 26u
+#define LOAMX_ROUTE3_NONE 27u
+typedef struct loamx_route3_config {
+  uint32_t connectivity;   /* 6, 18 or 26 (default 26) */
+  uint32_t min_d2;         /* smallest d2 of a traversable cell, >= 1 (default 1) */
+  uint32_t soft_d2;        /* d2 below which a cell pays a penalty, 0..65025 (default 0) */
+  uint32_t soft_weight;    /* largest penalty, 0..15 (default 0) */
+} loamx_route3_config;
+void loamx_route3_default_config(loamx_route3_config* cfg);   /* host only */
+int loamx_route3_check(const loamx_route3_config* cfg);        /* host only */
+int loamx_route3_weight(uint32_t d2, const loamx_route3_config* cfg);   /* host only */
+int loamx_route3_move(uint32_t d, int32_t dxyz[3]);                     /* host only */
+int loamx_densemap_route3(loamx_densemap* h, const loamx_densemap_dist_config* dist_cfg /* NULL: the defaults */,
+                          const loamx_densemap_static_rule* rule /* NULL: every voxel; else needs carving */,
+                          const loamx_route3_config* cfg /* NULL: the defaults */, const uint32_t* goals_xyz, uint32_t n_goals,
+                          loamx_route_cell* out_field /* nx * ny * nz; NULL: not wanted */, uint64_t stats[6] /* NULL: not wanted */);
+int loamx_densemap_route3_last(loamx_densemap* h, const loamx_route3_config* cfg /* NULL: the defaults */, const uint32_t* goals_xyz,
+                               uint32_t n_goals, loamx_route_cell* out_field /* NULL: not wanted */, uint64_t stats[6] /* NULL: not wanted */);
+int loamx_densemap_route3_cells(loamx_densemap* h, const uint16_t* d2 /* nx * ny * nz */, uint32_t nx, uint32_t ny, uint32_t nz,
+                                const loamx_route3_config* cfg /* NULL: the defaults */, const uint32_t* goals_xyz, uint32_t n_goals,
+                                loamx_route_cell* out_field /* NULL: not wanted */, uint64_t stats[6] /* NULL: not wanted */);
+int loamx_densemap_route3_trace(loamx_densemap* h, const uint32_t* starts_xyz, uint32_t n_starts /* 1..4096 */,
+                                uint32_t* out_xyz /* n_starts * capacity triples */, uint32_t capacity, uint32_t* lengths /* n_starts */);
+int loamx_route3_trace(const loamx_route_cell* field, uint32_t nx, uint32_t ny, uint32_t nz, const uint32_t start[3],
+                       uint32_t* out_xyz /* capacity triples */, uint32_t capacity, uint32_t* length);   /* host only */
+int loamx_route3_points(const loamx_densemap_dist_config* dist_cfg, float leaf, const uint32_t* route_xyz, uint32_t n,
+                        float* out_xyz /* 3 * n */);   /* host only */
+int loamx_densemap_dist_cell_of(const loamx_densemap_dist_config* dist_cfg, float leaf, float x, float y, float z, uint32_t r[3],
+                                int* inside);   /* host only */
+
 /* Signed distance along the sweep rays, and a triangle mesh of it (optional: a handle that never calls loamx_densemap_tsdf_* or
  * loamx_densemap_mesh runs the kernels it ran, allocates what it allocated and exports the same bytes).  "Where is the surface?":
  * every ray of a sweep adds its signed distance to the cells it crosses near its end, as integers; the zero crossing of the

@@ -337,6 +337,9 @@ class DmDist {
   const uint16_t* d2_on_host() const { return (const uint16_t*)h_d2_.data(); }
   const uint32_t* near_on_host() const { return h_near_.data(); }
   bool has_field() const { return valid_; }
+  // the d2 plane of the field that stands where it lies on the device, 16 bits per cell, and its configuration (DmRoute3 routes there)
+  const unsigned short* d2_on_device() const { return (const unsigned short*)d2_.p; }
+  const loamx_densemap_dist_config& config() const { return cfg_; }
   void drop() { valid_ = false; }   // (the buffers stay for the next field)
   DmCloudStage cloud{false};   // the query's points from the host, in the feature's own device block (query() blocks: no guard)
   // n >= 1 points (readable on st) against the field of the last run: the five stats and, when want_samples, the n samples in
@@ -355,6 +358,73 @@ class DmDist {
   PinLanding<uint32_t> h_d2_, h_near_;
   PinLanding<loamx_dist_sample> h_out_;
   loamx_densemap_dist_config cfg_ = {};   // of the field that stands
+  bool valid_ = false;
+};
+
+// include/loamx.h, weight of a cell of the distance field under a checked configuration: 0 = blocked, otherwise 1..16
+// (loamx_route3_weight, the device's k_dm_route3_weights and a caller's own planner share this one expression)
+__host__ __device__ inline uint32_t dm_route3_weight(uint32_t d2, const loamx_route3_config& c) {
+  if (d2 < c.min_d2) return 0u;
+  return 1u + (d2 < c.soft_d2 ? c.soft_weight * (c.soft_d2 - d2) / c.soft_d2 : 0u);   // (<= 15 * 65025)
+}
+// include/loamx.h, the moves: (dx, dy, dz) of direction d < 26
+__host__ __device__ inline void dm_route3_move(uint32_t d, int& dx, int& dy, int& dz) {
+  dx = dy = dz = 0;
+  if (d < 6u) {
+    const int s = (d & 1u) ? -1 : 1;
+    if (d < 2u) dx = s; else if (d < 4u) dy = s; else dz = s;
+  } else if (d < 18u) {
+    const uint32_t i = d - 6u;
+    const int a = (i & 1u) ? -1 : 1, b = (i & 2u) ? -1 : 1;
+    if (i < 4u) { dx = a; dy = b; } else if (i < 8u) { dx = a; dz = b; } else { dy = a; dz = b; }
+  } else {
+    const uint32_t i = d - 18u;
+    dx = (i & 1u) ? -1 : 1;
+    dy = (i & 2u) ? -1 : 1;
+    dz = (i & 4u) ? -1 : 1;
+  }
+}
+// include/loamx.h, loamx_route3_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
+void dm_route3_check(const loamx_route3_config& c);
+
+// Routing over the distance field (include/loamx.h, loamx_densemap_route3 ...; densemap_route3.hip): the weight, cost and dirty planes
+// of a 3-D window, its field records and the pinned blocks that goals, starts, counters, field and routes cross through.  Allocated
+// by the first route3 call, grow to the largest window asked for; the map and the distance field's own buffers are only read.
+class DmRoute3 {
+ public:
+  DmRoute3() = default;
+  DmRoute3(const DmRoute3&) = delete;
+  DmRoute3& operator=(const DmRoute3&) = delete;
+  // the caller's n d2 values in a device buffer of the route's own, enqueued on st
+  const unsigned short* upload(const uint16_t* d2, size_t n, hipStream_t st);
+  // the field of nx * ny * nz <= 2^22 cells whose d2 lie at d_d2 on the device (written by work enqueued on st) under a checked
+  // configuration towards n_goals in 1..4096 triples: weights, seeding, the relaxation rounds of densemap_route_schedule.hpp, next
+  // and the four exact stats.  Blocks; the field stays on the device for trace() and, when want_field, lies in pinned memory at the
+  // return (valid until the next run).  LOAMX_E_INTERNAL when the rounds reach their cap unsettled
+  const loamx_route_cell* run(const unsigned short* d_d2, uint32_t nx, uint32_t ny, uint32_t nz, const loamx_route3_config& c,
+                              const uint32_t* goals_xyz, uint32_t n_goals, bool want_field, uint64_t stats[6], hipStream_t st);
+  bool has_field() const { return valid_; }
+  void drop() { valid_ = false; }   // (the buffers stay for the next field)
+  // the routes of n_starts in 1..4096 starts over the field of the last run (include/loamx.h, loamx_densemap_route3_trace); blocks
+  void trace(const uint32_t* starts_xyz, uint32_t n_starts, uint32_t* out_xyz, uint32_t capacity, uint32_t* lengths, hipStream_t st);
+
+  uint32_t batch = 16;          // rounds per look (bench / test hook; the choice and its measurement: densemap_route3.hip)
+  uint64_t active_rounds = 0;   // of the last run: rounds in which a brick ran (test hook)
+
+ private:
+  DevBuf<uint32_t> own_d2_;             // route3_cells' upload, two cells per word
+  DevBuf<unsigned char> w_;             // weight per cell
+  DevBuf<uint32_t> cost_;               // cost per cell
+  DevBuf<uint32_t> dirty_;              // two planes of one word per brick
+  DevBuf<loamx_route_cell> field_;
+  DevBuf<uint32_t> ctr_;                // ROUTE_MAX_BATCH slots of two words (densemap_route_schedule.hpp)
+  DevBuf<unsigned long long> st_;       // the four exact stats
+  DevBuf<uint32_t> d_xyz_, d_len_, d_routes_;   // goals or starts; the routes' lengths; the routes back to back
+  DevBuf<unsigned long long> d_off_;            // the first triple of each route in d_routes_
+  PinBuf<uint32_t> h_xyz_, h_ctr_, h_len_, h_routes_;
+  PinLanding<loamx_route_cell> h_field_;
+  PinBuf<unsigned long long> h_off_;
+  uint32_t nx_ = 0, ny_ = 0, nz_ = 0;
   bool valid_ = false;
 };
 

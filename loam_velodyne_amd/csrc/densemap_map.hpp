@@ -159,6 +159,20 @@ class DenseMap {
   void dist(const loamx_densemap_dist_config& c, const loamx_densemap_static_rule* rule, uint16_t* out_d2, uint32_t* out_near,
             uint64_t stats[4]);
   int dist_query(const loamx_cloud* points, uint32_t min_d2, loamx_dist_sample* out, uint64_t capacity, uint64_t stats[5]);
+  bool has_dist() const { return dist_.has_field(); }
+  const loamx_densemap_dist_config& dist_config() const { return dist_.config(); }   // of the field that stands
+  // ---- densemap_route3.hip: include/loamx.h, loamx_densemap_route3 ...; checked configurations, a checked rule or none.  route3
+  // replaces the distance field in dist_ as dist() does and routes on it; route3_last routes on the one that stands (the caller has
+  // seen to it that there is one of at most 2^22 cells); route3_cells leaves dist_ alone.  The field stays in route3_ until the
+  // next of the three, reset or destroy; the outputs are written last, all or none
+  void route3(const loamx_densemap_dist_config& c, const loamx_densemap_static_rule* rule, const loamx_route3_config& rc,
+              const uint32_t* goals_xyz, uint32_t n_goals, loamx_route_cell* out_field, uint64_t stats[6]);
+  void route3_last(const loamx_route3_config& rc, const uint32_t* goals_xyz, uint32_t n_goals, loamx_route_cell* out_field,
+                   uint64_t stats[6]);
+  void route3_cells(const uint16_t* d2, uint32_t nx, uint32_t ny, uint32_t nz, const loamx_route3_config& rc, const uint32_t* goals_xyz,
+                    uint32_t n_goals, loamx_route_cell* out_field, uint64_t stats[6]);
+  void route3_trace(const uint32_t* starts_xyz, uint32_t n_starts, uint32_t* out_xyz, uint32_t capacity, uint32_t* lengths);
+  DmRoute3& router3() { return route3_; }
   // ---- densemap_mesh.hip: include/loamx.h, loamx_densemap_tsdf_* and loamx_densemap_mesh; checked configurations.  The field
   // stays in tsdf_ until the next tsdf_begin, reset or destroy; everything runs on own_
   void tsdf_begin(const loamx_densemap_tsdf_config& c);
@@ -210,6 +224,7 @@ class DenseMap {
   DmDist dist_;       // densemap_dist.hip
   DmTsdf tsdf_;       // densemap_mesh.hip
   DmRoute route_;     // densemap_route.hip
+  DmRoute3 route3_;   // densemap_route3.hip (routes on dist_'s d2 plane, or on an upload of its own)
   DmFrontier fr_;     // densemap_frontier.hip (routes towards the start through route_)
   DmSegment seg_;     // densemap_segment.hip
   DmSegCloud cseg_;   // densemap_segment_cloud.hip (labels its scratch table through seg_)

@@ -1534,6 +1534,84 @@ def dist_metres(d2, leaf: float, cell_leaves: int) -> float:
     return float(fn(C.c_uint32(int(d2)), C.c_float(leaf), C.c_uint32(cell_leaves)))
 
 
+class Route3Config(_DefaultedConfig, C.Structure):
+    """loamx_route3_config: how the cells of a distance field are weighted and joined for routing in 3-D.  Route3Config() holds the
+    defaults (connectivity 26, min_d2 1, soft_d2 0, soft_weight 0); keyword arguments replace them."""
+    _fields_ = [("connectivity", C.c_uint32), ("min_d2", C.c_uint32), ("soft_d2", C.c_uint32), ("soft_weight", C.c_uint32)]
+
+    _default, _checker = "loamx_route3_default_config", "loamx_route3_check"
+
+
+ROUTE3_GOAL, ROUTE3_NONE = 26, 27
+# (dx, dy, dz) of direction d: six axial, twelve face diagonals, eight space diagonals (include/loamx.h; loamx_route3_move)
+ROUTE3_MOVES = (((1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1))
+                + tuple((a, b, 0) for b in (1, -1) for a in (1, -1)) + tuple((a, 0, b) for b in (1, -1) for a in (1, -1))
+                + tuple((0, a, b) for b in (1, -1) for a in (1, -1)) + tuple((a, b, c) for c in (1, -1) for b in (1, -1) for a in (1, -1)))
+ROUTE3_STATS = ("traversable", "reachable", "goals_used", "max_cost", "rounds", "brick_runs")   # stats[6] of loamx_densemap_route3
+
+
+def _xyz_triples(triples) -> np.ndarray:
+    """(n, 3) uint32, C order, of a list of (rx, ry, rz) triples"""
+    return np.ascontiguousarray(np.asarray(triples, np.uint32).reshape(-1, 3))
+
+
+def _route3_field(field) -> np.ndarray:
+    a = np.ascontiguousarray(field)
+    assert a.dtype == ROUTE_CELL and a.ndim == 3, "field must be an (nz, ny, nx) array of ROUTE_CELL records"
+    return a
+
+
+def route3_weight(d2, cfg: Route3Config = None) -> np.ndarray:
+    """loamx_route3_weight (host only): the weight of every cell of a d2 array under cfg, uint8 of its shape: 0 blocked, otherwise
+    1..16"""
+    a = np.asarray(d2)
+    c = Route3Config() if cfg is None else cfg
+    L = lib()
+    return np.array([_check(L.loamx_route3_weight(C.c_uint32(int(v)), C.byref(c))) for v in a.reshape(-1)], np.uint8).reshape(a.shape)
+
+
+def route3_move(d: int):
+    """loamx_route3_move (host only): (dx, dy, dz) of direction d = 0..25"""
+    out = (C.c_int32 * 3)()
+    _check(lib().loamx_route3_move(C.c_uint32(d), out))
+    return tuple(out)
+
+
+def route3_trace(field, start, capacity=None):
+    """loamx_route3_trace (host only): the route from start = (rx, ry, rz) over an (nz, ny, nx) field -> ((min(n, capacity), 3)
+    uint32 of (rx, ry, rz) triples up to and including the goal cell, n = the full length; 0 for a start outside the window or
+    unreachable).  capacity None: the whole route.  LoamxError E_INVALID on a field that is not a route3 field"""
+    f = _route3_field(field)
+    nz, ny, nx = f.shape
+    s = (C.c_uint32 * 3)(*[int(v) for v in start])
+    n = C.c_uint32(0)
+    if capacity is None:
+        _check(lib().loamx_route3_trace(f.ctypes.data_as(C.c_void_p), nx, ny, nz, s, None, 0, C.byref(n)))
+        capacity = n.value
+    out = np.zeros((capacity, 3), np.uint32)
+    _check(lib().loamx_route3_trace(f.ctypes.data_as(C.c_void_p), nx, ny, nz, s, out.ctypes.data_as(C.c_void_p), C.c_uint32(capacity),
+                                    C.byref(n)))
+    return out[:min(n.value, capacity)], n.value
+
+
+def route3_points(cfg: DistConfig, leaf: float, route) -> np.ndarray:
+    """loamx_route3_points (host only): (n, 3) float32 metres in the LOAM frame, the cell centres of the (rx, ry, rz) triples of a
+    route"""
+    r = _xyz_triples(route)
+    out = np.zeros((len(r), 3), np.float32)
+    _check(lib().loamx_route3_points(C.byref(cfg), C.c_float(leaf), r.ctypes.data_as(C.c_void_p), C.c_uint32(len(r)),
+                                     out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def dist_cell_of(cfg: DistConfig, leaf: float, x: float, y: float, z: float):
+    """loamx_densemap_dist_cell_of (host only): the window-relative cell (rx, ry, rz) of a position in metres (LOAM frame), or None
+    when it lies outside the window"""
+    r, inside = (C.c_uint32 * 3)(), C.c_int(0)
+    _check(lib().loamx_densemap_dist_cell_of(C.byref(cfg), C.c_float(leaf), C.c_float(x), C.c_float(y), C.c_float(z), r, C.byref(inside)))
+    return tuple(r) if inside.value else None
+
+
 class TsdfConfig(_DefaultedConfig, C.Structure):
     """loamx_densemap_tsdf_config: the window of one-voxel cells (x0, y0, z0, nx, ny, nz), the truncation in leaves, whether the
     whole ray is integrated (free_space), the ray stride, the step limit and the range filter of the signed distance field.
@@ -1681,7 +1759,10 @@ class DenseMap:
         L.loamx_densemap_create.restype = C.c_void_p
         L.loamx_densemap_rehashes.restype = C.c_uint64
         L.loamx_densemap_route_active_rounds.restype = C.c_uint64
+        L.loamx_densemap_route3_active_rounds.restype = C.c_uint64
         self.route_stats = None
+        self.route3_stats = None
+        self._dist_shape = None   # (nz, ny, nx) of the distance field that stands, for route3_last
         self.frontier_stats = None
         self._level = 0   # the level select_level chose (loamx_densemap_align_select_level)
         self._c = _cfg(DenseMapConfig, "loamx_densemap_default_config", leaf=leaf, min_range=min_range, max_range=max_range,
@@ -2070,6 +2151,7 @@ class DenseMap:
                                          d2.ctypes.data_as(C.c_void_p) if want_d2 else None,
                                          near.ctypes.data_as(C.c_void_p) if want_near else None, st))
         self.dist_stats = dict(zip(DIST_STATS, (int(v) for v in st)))
+        self._dist_shape = (c.nz, c.ny, c.nx)
         return d2, near
 
     def dist_query(self, points, min_d2=0, records=True):
@@ -2209,6 +2291,63 @@ class DenseMap:
     def route_set_batch(self, batch: int):
         """bench hook: the relaxation rounds launched per look at the counters (1..64)"""
         _check(lib().loamx_densemap_route_set_batch(self.h, C.c_uint32(batch)))
+
+    def _route3(self, fn, head, shape, goals, cfg, want_field, fields):
+        c = (Route3Config() if cfg is None else cfg).copy(**fields).check()
+        xyz = _xyz_triples(goals)
+        field = np.zeros(shape, ROUTE_CELL) if want_field else None
+        st = (C.c_uint64 * 6)()
+        _check(fn(self.h, *head, C.byref(c), xyz.ctypes.data_as(C.c_void_p), C.c_uint32(len(xyz)),
+                  field.ctypes.data_as(C.c_void_p) if want_field else None, st))
+        self.route3_stats = dict(zip(ROUTE3_STATS, (int(v) for v in st)))
+        return field
+
+    def route3(self, goals, cfg=None, dist=None, static=None, want_field=True, **fields):
+        """loamx_densemap_route3: the distance field of a 3-D window (dist: a DistConfig, None: the defaults; static: a StaticRule),
+        which replaces the standing one and stays for dist_query(), and on its d2 where it lies on the device the cost-to-go field
+        towards goals, a list of window-relative (rx, ry, rz) triples, under cfg (a Route3Config, None: the defaults; fields
+        replace members of a copy of it).  Returns the (nz, ny, nx) array of ROUTE_CELL records; want_field=False leaves the field
+        on the device for route3_trace() and returns None.  The six stats of the call are left in route3_stats."""
+        g = (DistConfig() if dist is None else dist).copy().check()
+        head = (C.byref(g), C.byref(static) if static is not None else None)
+        out = self._route3(lib().loamx_densemap_route3, head, (g.nz, g.ny, g.nx), goals, cfg, want_field, fields)
+        self._dist_shape = (g.nz, g.ny, g.nx)
+        return out
+
+    def route3_last(self, goals, cfg=None, want_field=True, **fields):
+        """loamx_densemap_route3_last: the same on the distance field that stands (dist() or route3()); LoamxError E_INVALID when
+        there is none"""
+        return self._route3(lib().loamx_densemap_route3_last, (), self._dist_shape or (1, 1, 1), goals, cfg, want_field, fields)
+
+    def route3_cells(self, d2, goals, cfg=None, want_field=True, **fields):
+        """loamx_densemap_route3_cells: the same on an (nz, ny, nx) uint16 array of d2 values of the caller's (an earlier field
+        painted with no-fly zones, or a hand-made one), uploaded to a buffer of the route's own; the standing distance field is
+        left alone"""
+        a = np.ascontiguousarray(d2, np.uint16)
+        assert a.ndim == 3, "d2 must be an (nz, ny, nx) array"
+        head = (a.ctypes.data_as(C.c_void_p), C.c_uint32(a.shape[2]), C.c_uint32(a.shape[1]), C.c_uint32(a.shape[0]))
+        return self._route3(lib().loamx_densemap_route3_cells, head, a.shape, goals, cfg, want_field, fields)
+
+    def route3_trace(self, starts, capacity):
+        """loamx_densemap_route3_trace: the routes from starts, a list of 1..4096 (rx, ry, rz) triples, over the field of the last
+        route3 / route3_last / route3_cells call, traced on the device -> (a list of (min(n_i, capacity), 3) uint32 arrays of
+        triples up to and including the goal cell, the full lengths n_i as uint32; 0: the start is outside the window or
+        unreachable)"""
+        xyz = _xyz_triples(starts)
+        out = np.zeros((len(xyz), capacity, 3), np.uint32)
+        lengths = np.zeros(len(xyz), np.uint32)
+        _check(lib().loamx_densemap_route3_trace(self.h, xyz.ctypes.data_as(C.c_void_p), C.c_uint32(len(xyz)), out.ctypes.data_as(C.c_void_p),
+                                                 C.c_uint32(capacity), lengths.ctypes.data_as(C.c_void_p)))
+        return [out[i, :min(int(n), capacity)] for i, n in enumerate(lengths)], lengths
+
+    @property
+    def route3_active_rounds(self) -> int:
+        """test hook: the relaxation rounds of the last route3 call in which a brick ran"""
+        return int(lib().loamx_densemap_route3_active_rounds(self.h))
+
+    def route3_set_batch(self, batch: int):
+        """bench hook: the relaxation rounds launched per look at the counters (1..64)"""
+        _check(lib().loamx_densemap_route3_set_batch(self.h, C.c_uint32(batch)))
 
     def _frontiers(self, fn, head, shape, cfg, route, start, labels, fields):
         # (as segment(): a refusal by capacity leaves the needed count, and the call is made again with that room)
