@@ -11,8 +11,8 @@
 //   densemap_align.hip    alignment of sweeps against the frozen surfel snapshot (DmFrozen)
 //   densemap_pyramid.hip  coarser levels of the table and of the snapshot, and the coarse-to-fine alignment over them
 //   densemap_grid.hip     a window of the table projected to a 2-D navigation grid (DmGrid)
-//   densemap_route.hip    cost-to-go field and routes over that grid (DmRoute, densemap_route_schedule.hpp)
-//   densemap_route3.hip   cost-to-go field and routes in 3-D over the distance field (DmRoute3, the same schedule)
+//   densemap_route.hip    cost-to-go field and routes over that grid (DmRoute: the engine of densemap_route_core.hpp, densemap_route_schedule.hpp)
+//   densemap_route3.hip   cost-to-go field and routes in 3-D over the distance field (DmRoute3: the same engine, the same schedule)
 //   densemap_segment.hip  connected components of the voxels (DmSegment)
 //   densemap_segment_cloud.hip  the objects of a cloud that is not in the map, tested against the table (DmSegCloud)
 //   densemap_region.hip   the compaction (of every voxel, or of a window's), region exports, evict, tile files and paging

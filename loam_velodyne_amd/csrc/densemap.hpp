@@ -208,7 +208,7 @@ class DmGrid {
                              hipStream_t st) {
     return fetch(enqueue(T, c, rule, leaf, st), (size_t)c.nx * c.nz, st);
   }
-  // the two halves of run (DmRoute routes on the records where enqueue leaves them): the memset and the four kernels, enqueued;
+  // the two halves of run (DmRoute, densemap_route_core.hpp, routes on the records where enqueue leaves them): the memset and the four kernels, enqueued;
   // returns the records on the device, valid until the next enqueue.  fetch: the readback of n of them, blocking
   const loamx_grid_cell* enqueue(const DmTable& T, const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, double leaf,
                                  hipStream_t st);
@@ -224,7 +224,7 @@ class DmGrid {
 void dm_grid_check(const loamx_densemap_grid_config& c);
 
 // include/loamx.h, weight of a cell under a checked configuration: 0 = blocked, otherwise 1..32 (loamx_grid_route_weight, the
-// device's k_dm_route_weights and a caller's own planner share this one expression)
+// device's k_dm_route_weights<DmRouteGrid> and a caller's own planner share this one expression)
 __host__ __device__ inline uint32_t dm_route_weight(uint32_t cls, uint32_t clear2, const loamx_grid_route_config& c) {
   if (clear2 < c.min_clear2) return 0u;
   if (cls != LOAMX_GRID_FREE && !(cls == LOAMX_GRID_UNKNOWN && c.unknown_weight > 0u)) return 0u;
@@ -233,48 +233,7 @@ __host__ __device__ inline uint32_t dm_route_weight(uint32_t cls, uint32_t clear
 }
 // include/loamx.h, loamx_grid_route_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
 void dm_route_check(const loamx_grid_route_config& c);
-
-// Routing on the navigation grid (include/loamx.h, loamx_densemap_route ...; densemap_route.hip): the weight, cost and dirty planes of
-// a window, its field records and the pinned blocks that goals, starts, counters, field and routes cross through.  Allocated by the
-// first route call, grow to the largest window asked for; the map and the grid's own buffers are only read.
-class DmRoute {
- public:
-  DmRoute() = default;
-  DmRoute(const DmRoute&) = delete;
-  DmRoute& operator=(const DmRoute&) = delete;
-  // the caller's nx * nz records (every cls checked) in a device buffer of the route's own, enqueued on st
-  const loamx_grid_cell* upload(const loamx_grid_cell* cells, size_t n, hipStream_t st);
-  // the field of nx * nz <= 2^22 records d_cells on the device (written by work enqueued on st) under a checked configuration towards
-  // n_goals in 1..4096 pairs: weights, seeding, the relaxation rounds of densemap_route_schedule.hpp, next and the four exact stats.
-  // Blocks; the field stays on the device for trace() and, when want_field, lies in pinned memory at the return (valid until the
-  // next run).  LOAMX_E_INTERNAL when the rounds reach their cap unsettled
-  const loamx_route_cell* run(const loamx_grid_cell* d_cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config& c,
-                              const uint32_t* goals_xz, uint32_t n_goals, bool want_field, uint64_t stats[6], hipStream_t st);
-  bool has_field() const { return valid_; }
-  // the routes of n_starts in 1..4096 starts over the field of the last run (include/loamx.h, loamx_densemap_route_trace); blocks
-  void trace(const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity, uint32_t* lengths, hipStream_t st);
-  // the field of the last run where it lies on the device (DmFrontier reads the costs there), valid until the next run
-  const loamx_route_cell* field_on_device() const { return field_.p; }
-
-  uint32_t batch = 16;          // rounds per look (bench / test hook; the choice and its measurement: densemap_route.hip)
-  uint64_t active_rounds = 0;   // of the last run: rounds in which a tile ran (test hook)
-
- private:
-  DevBuf<loamx_grid_cell> own_cells_;   // route_cells' upload
-  DevBuf<unsigned char> w_;             // weight per cell
-  DevBuf<uint32_t> cost_;               // cost per cell
-  DevBuf<uint32_t> dirty_;              // two planes of one word per tile
-  DevBuf<loamx_route_cell> field_;
-  DevBuf<uint32_t> ctr_;                // ROUTE_MAX_BATCH slots of two words (densemap_route_schedule.hpp)
-  DevBuf<unsigned long long> st_;       // the four exact stats
-  DevBuf<uint32_t> d_xz_, d_len_, d_routes_;   // goals or starts; the routes' lengths; the routes back to back
-  DevBuf<unsigned long long> d_off_;           // the first pair of each route in d_routes_
-  PinBuf<uint32_t> h_xz_, h_ctr_, h_len_, h_routes_;
-  PinLanding<loamx_route_cell> h_field_;
-  PinBuf<unsigned long long> h_off_;
-  uint32_t nx_ = 0, nz_ = 0;
-  bool valid_ = false;
-};
+// (the route over these weights: DmRoute, an instance of the route engine of densemap_route_core.hpp)
 
 // include/loamx.h, loamx_grid_frontier_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
 void dm_frontier_check(const loamx_grid_frontier_config& c);
@@ -362,7 +321,7 @@ class DmDist {
 };
 
 // include/loamx.h, weight of a cell of the distance field under a checked configuration: 0 = blocked, otherwise 1..16
-// (loamx_route3_weight, the device's k_dm_route3_weights and a caller's own planner share this one expression)
+// (loamx_route3_weight, the device's k_dm_route_weights<DmRouteVol> and a caller's own planner share this one expression)
 __host__ __device__ inline uint32_t dm_route3_weight(uint32_t d2, const loamx_route3_config& c) {
   if (d2 < c.min_d2) return 0u;
   return 1u + (d2 < c.soft_d2 ? c.soft_weight * (c.soft_d2 - d2) / c.soft_d2 : 0u);   // (<= 15 * 65025)
@@ -386,47 +345,7 @@ __host__ __device__ inline void dm_route3_move(uint32_t d, int& dx, int& dy, int
 }
 // include/loamx.h, loamx_route3_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
 void dm_route3_check(const loamx_route3_config& c);
-
-// Routing over the distance field (include/loamx.h, loamx_densemap_route3 ...; densemap_route3.hip): the weight, cost and dirty planes
-// of a 3-D window, its field records and the pinned blocks that goals, starts, counters, field and routes cross through.  Allocated
-// by the first route3 call, grow to the largest window asked for; the map and the distance field's own buffers are only read.
-class DmRoute3 {
- public:
-  DmRoute3() = default;
-  DmRoute3(const DmRoute3&) = delete;
-  DmRoute3& operator=(const DmRoute3&) = delete;
-  // the caller's n d2 values in a device buffer of the route's own, enqueued on st
-  const unsigned short* upload(const uint16_t* d2, size_t n, hipStream_t st);
-  // the field of nx * ny * nz <= 2^22 cells whose d2 lie at d_d2 on the device (written by work enqueued on st) under a checked
-  // configuration towards n_goals in 1..4096 triples: weights, seeding, the relaxation rounds of densemap_route_schedule.hpp, next
-  // and the four exact stats.  Blocks; the field stays on the device for trace() and, when want_field, lies in pinned memory at the
-  // return (valid until the next run).  LOAMX_E_INTERNAL when the rounds reach their cap unsettled
-  const loamx_route_cell* run(const unsigned short* d_d2, uint32_t nx, uint32_t ny, uint32_t nz, const loamx_route3_config& c,
-                              const uint32_t* goals_xyz, uint32_t n_goals, bool want_field, uint64_t stats[6], hipStream_t st);
-  bool has_field() const { return valid_; }
-  void drop() { valid_ = false; }   // (the buffers stay for the next field)
-  // the routes of n_starts in 1..4096 starts over the field of the last run (include/loamx.h, loamx_densemap_route3_trace); blocks
-  void trace(const uint32_t* starts_xyz, uint32_t n_starts, uint32_t* out_xyz, uint32_t capacity, uint32_t* lengths, hipStream_t st);
-
-  uint32_t batch = 16;          // rounds per look (bench / test hook; the choice and its measurement: densemap_route3.hip)
-  uint64_t active_rounds = 0;   // of the last run: rounds in which a brick ran (test hook)
-
- private:
-  DevBuf<uint32_t> own_d2_;             // route3_cells' upload, two cells per word
-  DevBuf<unsigned char> w_;             // weight per cell
-  DevBuf<uint32_t> cost_;               // cost per cell
-  DevBuf<uint32_t> dirty_;              // two planes of one word per brick
-  DevBuf<loamx_route_cell> field_;
-  DevBuf<uint32_t> ctr_;                // ROUTE_MAX_BATCH slots of two words (densemap_route_schedule.hpp)
-  DevBuf<unsigned long long> st_;       // the four exact stats
-  DevBuf<uint32_t> d_xyz_, d_len_, d_routes_;   // goals or starts; the routes' lengths; the routes back to back
-  DevBuf<unsigned long long> d_off_;            // the first triple of each route in d_routes_
-  PinBuf<uint32_t> h_xyz_, h_ctr_, h_len_, h_routes_;
-  PinLanding<loamx_route_cell> h_field_;
-  PinBuf<unsigned long long> h_off_;
-  uint32_t nx_ = 0, ny_ = 0, nz_ = 0;
-  bool valid_ = false;
-};
+// (the route over these weights and moves: DmRoute3, the other instance of the route engine of densemap_route_core.hpp)
 
 // include/loamx.h, loamx_densemap_tsdf_check: throws LOAMX_E_INVALID with a message that names the first field out of its bounds
 void dm_tsdf_check(const loamx_densemap_tsdf_config& c);

@@ -3,6 +3,7 @@
 #pragma once
 #include "densemap.hpp"
 #include "densemap_history.hpp"
+#include "densemap_route_core.hpp"
 #include <functional>
 #include <type_traits>
 
@@ -144,8 +145,25 @@ class DenseMap {
              const uint32_t* goals_xz, uint32_t n_goals, loamx_grid_cell* out_cells, loamx_route_cell* out_field, uint64_t stats[6]);
   void route_cells(const loamx_grid_cell* cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config& rc, const uint32_t* goals_xz,
                    uint32_t n_goals, loamx_route_cell* out_field, uint64_t stats[6]);
-  void route_trace(const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity, uint32_t* lengths);
   DmRoute& router() { return route_; }
+  // what the 2-D and the 3-D route calls share, r being route_ or route3_.  route_on: r.run on own_, then `between` (what else
+  // has to succeed before anything is written), then the field and the stats out, each where wanted
+  template <class K, class Between = void (*)()>
+  void route_on(DmRouteT<K>& r, const typename K::Cell* d_in, uint32_t nx, uint32_t ny, uint32_t nz, const typename K::Config& rc,
+                const uint32_t* goals, uint32_t n_goals, loamx_route_cell* out_field, uint64_t stats[6], Between between = [] {}) {
+    uint64_t s[6];
+    const loamx_route_cell* field = r.run(d_in, nx, ny, nz, rc, goals, n_goals, out_field != nullptr, s, own_);
+    between();
+    if (out_field) memcpy(out_field, field, sizeof(loamx_route_cell) * nx * ny * nz);
+    if (stats) memcpy(stats, s, sizeof(s));
+  }
+  // include/loamx.h, loamx_densemap_route_trace and loamx_densemap_route3_trace: checked starts over the field that stands in r
+  template <class K> void route_trace_on(DmRouteT<K>& r, const uint32_t* starts, uint32_t n_starts, uint32_t* out, uint32_t capacity,
+                                         uint32_t* lengths) {
+    LX_REQUIRE(r.has_field(), std::string("the handle has no field yet (") + K::FIELD_FROM + ")");
+    LX_HIP(hipSetDevice(cfg.device));
+    r.trace(starts, n_starts, out, capacity, lengths, own_);
+  }
   // ---- densemap_frontier.hip: include/loamx.h, loamx_densemap_frontiers and loamx_densemap_frontiers_cells; checked configurations.
   // LOAMX_E_CAPACITY: only *n_frontiers is written
   int frontiers(const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, const loamx_grid_route_config& rc,
@@ -171,7 +189,6 @@ class DenseMap {
                    uint64_t stats[6]);
   void route3_cells(const uint16_t* d2, uint32_t nx, uint32_t ny, uint32_t nz, const loamx_route3_config& rc, const uint32_t* goals_xyz,
                     uint32_t n_goals, loamx_route_cell* out_field, uint64_t stats[6]);
-  void route3_trace(const uint32_t* starts_xyz, uint32_t n_starts, uint32_t* out_xyz, uint32_t capacity, uint32_t* lengths);
   DmRoute3& router3() { return route3_; }
   // ---- densemap_mesh.hip: include/loamx.h, loamx_densemap_tsdf_* and loamx_densemap_mesh; checked configurations.  The field
   // stays in tsdf_ until the next tsdf_begin, reset or destroy; everything runs on own_
@@ -299,6 +316,29 @@ inline void checked_optional_rule(loamx_densemap* h, const loamx_densemap_static
   if (!rule) return;
   LX_REQUIRE(rule->den != 0u, "the rule's den must not be 0");
   LX_REQUIRE(h->d.carving(), "a rule needs carving, which is not enabled");
+}
+// densemap_route.hip and densemap_route3.hip: the bodies of loamx_densemap_route_trace / loamx_densemap_route3_trace and of the
+// bench / test hooks loamx_densemap_route_set_batch / loamx_densemap_route3_set_batch (rounds per look, 1..64); `router` is
+// &DenseMap::router or &DenseMap::router3
+template <class K, class R>
+int dm_route_trace_entry(loamx_densemap* h, R& (DenseMap::*router)(), const uint32_t* starts, uint32_t n_starts, uint32_t* out,
+                         uint32_t capacity, uint32_t* lengths) {
+  return guard([&]() {
+    LX_REQUIRE(h, "h is NULL");
+    dm_route_check_tuples<K>(starts, n_starts, "starts");
+    LX_REQUIRE(out || !capacity, std::string("out_") + K::AXES + " is NULL");
+    LX_REQUIRE(lengths, "lengths is NULL");
+    h->d.route_trace_on<K>((h->d.*router)(), starts, n_starts, out, capacity, lengths);
+    return LOAMX_OK;
+  });
+}
+template <class R> int dm_route_set_batch_entry(loamx_densemap* h, R& (DenseMap::*router)(), uint32_t batch) {
+  return guard([&]() {
+    LX_REQUIRE(h, "NULL handle");
+    LX_REQUIRE(batch >= 1u && batch <= 64u, "batch must be in [1, 64]");
+    (h->d.*router)().batch = batch;
+    return LOAMX_OK;
+  });
 }
 // densemap_export.hip, shared with densemap_pyramid.hip: the surfel of a voxel from its words (include/loamx.h), the surfel settings
 // of a call, checked (NULL: the defaults), and the optional rule of a surfel call (NULL stays NULL: every voxel; a rule is checked

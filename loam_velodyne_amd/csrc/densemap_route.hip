@@ -1,10 +1,5 @@
-// Routing on the navigation grid (densemap.hpp DmRoute, include/loamx.h loamx_densemap_route and what goes with it): the cost-to-go of
-// every cell of a window towards a set of goal cells, the next step per cell and routes traced from many starts.
-//
-// k_dm_route_weights gives every cell its weight (a byte) and the cost UINT32_MAX, k_dm_route_seed puts 0 on the used goals and marks
-// their tiles, k_dm_route_relax is launched round after round (densemap_route_schedule.hpp) until no tile is marked, k_dm_route_next
-// derives next from the final costs and counts, k_dm_route_trace walks next from many starts.  Integer atomics only; the costs are the
-// unique fixed point of cost[c] = min over legal moves of cost[nb] + move, so no word depends on the schedule.
+// Routing on the navigation grid (DmRoute, include/loamx.h loamx_densemap_route and what goes with it): the route engine of
+// densemap_route_core.hpp for the kind DmRouteGrid, compiled here, the relax kernel of that kind, and the entry points.
 //
 // k_dm_route_relax, one block per tile of 32 x 32 cells: the tile's weights and costs with a halo of one cell go to LDS, the block
 // relaxes there until no cell of the tile changes, and writes back the cells that fell.  Only the owning tile writes a cell.  A halo
@@ -21,54 +16,11 @@
 // Inside LDS a sweep lowers at least the next cell of every unfinished cheapest path, so 32 * 32 sweeps and one that finds nothing
 // bound the loop; the bound is in the code, and a tile that ever left it unsettled would mark itself.
 #include "densemap_map.hpp"
-#include "densemap_route_schedule.hpp"
-#include "pinned_copy.hpp"
 
 namespace loamx {
 
-constexpr int DM_ROUTE_TILE = 32;
+constexpr int DM_ROUTE_TILE = DmRouteGrid::TILE;
 constexpr int DM_ROUTE_SIDE = DM_ROUTE_TILE + 2;   // with the halo
-constexpr uint32_t DM_ROUTE_MAX_CELLS = 1u << 22;
-constexpr uint32_t DM_ROUTE_MAX_XZ = 4096;         // goals, starts
-constexpr uint32_t DM_ROUTE_INF = LOAMX_ROUTE_UNREACHABLE;
-
-// (dx, dz) of direction d
-__host__ __device__ inline int dm_route_dx(uint32_t d) { return d == 0u || d == 1u || d == 7u ? 1 : (d >= 3u && d <= 5u ? -1 : 0); }
-__host__ __device__ inline int dm_route_dz(uint32_t d) { return d >= 1u && d <= 3u ? 1 : (d >= 5u ? -1 : 0); }
-
-__global__ __launch_bounds__(256) void k_dm_route_weights(const loamx_grid_cell* __restrict__ cells, uint32_t n, loamx_grid_route_config C,
-                                                          unsigned char* __restrict__ w, uint32_t* __restrict__ cost,
-                                                          unsigned long long* __restrict__ st) {
-  __shared__ uint32_t s_n;
-  if (threadIdx.x == 0) s_n = 0u;
-  __syncthreads();
-  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t wt = 0u;
-  if (c < n) {
-    wt = dm_route_weight(cells[c].cls, cells[c].clear2, C);
-    w[c] = (unsigned char)wt;
-    cost[c] = DM_ROUTE_INF;
-  }
-  const unsigned long long b = __ballot(wt > 0u);
-  if ((threadIdx.x & 63u) == 0u && b) atomicAdd(&s_n, (uint32_t)__popcll(b));
-  __syncthreads();
-  if (threadIdx.x == 0 && s_n) atomicAdd(&st[0], (unsigned long long)s_n);
-}
-
-// one thread per goal pair: 0 on a used goal (every writer stores the same word), its tile marked for round 0
-__global__ __launch_bounds__(256) void k_dm_route_seed(const uint32_t* __restrict__ goals, uint32_t n_goals, uint32_t nx, uint32_t nz,
-                                                       uint32_t tiles_x, const unsigned char* __restrict__ w, uint32_t* __restrict__ cost,
-                                                       uint32_t* __restrict__ dirty, unsigned long long* __restrict__ st) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_goals) return;
-  const uint32_t x = goals[2u * i], z = goals[2u * i + 1u];
-  if (x >= nx || z >= nz) return;
-  const uint32_t c = z * nx + x;
-  if (!w[c]) return;
-  cost[c] = 0u;
-  dirty[(z / DM_ROUTE_TILE) * tiles_x + x / DM_ROUTE_TILE] = 1u;
-  atomicAdd(&st[2], 1ull);
-}
 
 // one round (the file's head comment).  grid: tiles_x x tiles_z; slot: {tiles that ran, tiles that marked} of this round
 __global__ __launch_bounds__(256) void k_dm_route_relax(uint32_t nx, uint32_t nz, int diag, const unsigned char* __restrict__ w, uint32_t* cost,
@@ -168,73 +120,19 @@ __global__ __launch_bounds__(256) void k_dm_route_relax(uint32_t nx, uint32_t nz
   }
 }
 
-// one thread per cell: the record from the final costs, the smallest d first; the reachable cells and the largest finite cost
-__global__ __launch_bounds__(256) void k_dm_route_next(uint32_t nx, uint32_t nz, int diag, const unsigned char* __restrict__ w,
-                                                       const uint32_t* __restrict__ cost, loamx_route_cell* __restrict__ field,
-                                                       unsigned long long* __restrict__ st) {
-  __shared__ uint32_t s_n, s_max;
-  if (threadIdx.x == 0) s_n = s_max = 0u;
-  __syncthreads();
-  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-  bool reach = false;
-  if (c < nx * nz) {
-    const uint32_t x = c % nx, z = c / nx, cc = cost[c], wa = w[c];
-    uint32_t next = LOAMX_ROUTE_NONE;
-    reach = cc != DM_ROUTE_INF;
-    if (cc == 0u) next = LOAMX_ROUTE_GOAL;
-    else if (reach) {
-      for (uint32_t d = 0; d < 8u && next == LOAMX_ROUTE_NONE; d += diag ? 1u : 2u) {
-        const int dx = dm_route_dx(d), dz = dm_route_dz(d);
-        const uint32_t bxx = x + (uint32_t)dx, bzz = z + (uint32_t)dz;   // (a cell before the window wraps)
-        if (bxx >= nx || bzz >= nz) continue;
-        const uint32_t nb = bzz * nx + bxx, wb = w[nb], cn = cost[nb];
-        if (!wb || cn == DM_ROUTE_INF) continue;
-        if ((d & 1u) && (!w[z * nx + bxx] || !w[bzz * nx + x])) continue;
-        if (cn + ((d & 1u) ? 7u : 5u) * (wa + wb) == cc) next = d;
-      }
-      atomicMax(&s_max, cc);
-    }
-    loamx_route_cell r;
-    r.cost = cc;
-    r.next = next;
-    field[c] = r;
-  }
-  const unsigned long long b = __ballot(reach);
-  if ((threadIdx.x & 63u) == 0u && b) atomicAdd(&s_n, (uint32_t)__popcll(b));
-  __syncthreads();
-  if (threadIdx.x == 0 && s_n) {
-    atomicAdd(&st[1], (unsigned long long)s_n);
-    atomicMax(&st[3], (unsigned long long)s_max);
-  }
+// Rounds per look: DmRoute::batch = 16.  Measured on one MI355X, one run (scripts/bench_densemap_route.py --batches 1,2,4,8,16,32,64;
+// the blocking call with nothing back, median of 30 / of 10; a look is about 14 us, an idle round of 1024 blocks 2 to 5):
+//   batch                                   1       2       4       8      16      32      64
+//   terrain, 1024 x 1024, 33 rounds      2.27    2.01    1.89    1.87    1.82    1.88    1.81  ms
+//   serpentine, 1024 x 1024, 7969 rounds 454.9   391.5   359.8   349.5   338.6   333.2   330.3 ms
+// From 8 to 16 both still gain; beyond 16 the terrain gains nothing and the serpentine 2.4 % at most, while a window of a few tiles,
+// which settles in two or three rounds, would pay for up to 63 idle launches instead of 15.
+void DmRouteGrid::relax(uint32_t nx, uint32_t, uint32_t nz, uint32_t connectivity, const unsigned char* w, uint32_t* cost,
+                        uint32_t* dirty_read, uint32_t* dirty_mark, uint32_t* slot, hipStream_t st) {
+  hipLaunchKernelGGL(k_dm_route_relax, dim3(dm_route_tiles<DmRouteGrid>(nx), dm_route_tiles<DmRouteGrid>(nz)), dim3(256), 0, st, nx, nz,
+                     connectivity == 8u ? 1 : 0, w, cost, dirty_read, dirty_mark, slot);
 }
-
-// one thread per start, walking next; bounded by nx * nz steps.  offsets NULL: the lengths only.  Otherwise start i's pairs go to
-// out + 2 * offsets[i], the first min(length, capacity) of them (the same walk as the counting pass over the same field)
-__global__ __launch_bounds__(256) void k_dm_route_trace(const loamx_route_cell* __restrict__ field, uint32_t nx, uint32_t nz,
-                                                        const uint32_t* __restrict__ starts, uint32_t n_starts, uint32_t capacity,
-                                                        const unsigned long long* __restrict__ offsets, uint32_t* __restrict__ lengths,
-                                                        uint32_t* __restrict__ out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_starts) return;
-  uint32_t x = starts[2u * i], z = starts[2u * i + 1u], len = 0u;
-  if (x < nx && z < nz) {
-    const uint32_t cells = nx * nz;
-    for (uint32_t step = 0; step < cells; step++) {
-      const uint32_t next = field[(size_t)z * nx + x].next;
-      if (next >= LOAMX_ROUTE_NONE) break;
-      if (offsets && len < capacity) {
-        out[2ull * (offsets[i] + len)] = x;
-        out[2ull * (offsets[i] + len) + 1ull] = z;
-      }
-      len++;
-      if (next == LOAMX_ROUTE_GOAL) break;
-      x += (uint32_t)dm_route_dx(next);
-      z += (uint32_t)dm_route_dz(next);
-      if (x >= nx || z >= nz) break;   // (never on a field of k_dm_route_next)
-    }
-  }
-  if (!offsets) lengths[i] = len;
-}
+template class DmRouteT<DmRouteGrid>;   // upload, run and trace of the engine, and its four kernels, for the grid
 
 void dm_route_check(const loamx_grid_route_config& c) {
   LX_REQUIRE(c.connectivity == 4u || c.connectivity == 8u, "connectivity must be 4 or 8");
@@ -244,120 +142,6 @@ void dm_route_check(const loamx_grid_route_config& c) {
   LX_REQUIRE(c.unknown_weight <= 16u, "unknown_weight must be in [0, 16]");
 }
 
-const loamx_grid_cell* DmRoute::upload(const loamx_grid_cell* cells, size_t n, hipStream_t st) {
-  own_cells_.reserve(n);
-  LX_HIP(hipMemcpyAsync(own_cells_.p, cells, sizeof(loamx_grid_cell) * n, hipMemcpyHostToDevice, st));
-  return own_cells_.p;
-}
-
-// Rounds per look: DmRoute::batch = 16.  Measured on one MI355X, one run (scripts/bench_densemap_route.py --batches 1,2,4,8,16,32,64;
-// the blocking call with nothing back, median of 30 / of 10; a look is about 14 us, an idle round of 1024 blocks 2 to 5):
-//   batch                                   1       2       4       8      16      32      64
-//   terrain, 1024 x 1024, 33 rounds      2.27    2.01    1.89    1.87    1.82    1.88    1.81  ms
-//   serpentine, 1024 x 1024, 7969 rounds 454.9   391.5   359.8   349.5   338.6   333.2   330.3 ms
-// From 8 to 16 both still gain; beyond 16 the terrain gains nothing and the serpentine 2.4 % at most, while a window of a few tiles,
-// which settles in two or three rounds, would pay for up to 63 idle launches instead of 15.
-const loamx_route_cell* DmRoute::run(const loamx_grid_cell* d_cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config& c,
-                                     const uint32_t* goals_xz, uint32_t n_goals, bool want_field, uint64_t stats[6], hipStream_t st) {
-  const uint32_t n = nx * nz, tiles_x = (nx + DM_ROUTE_TILE - 1) / DM_ROUTE_TILE, tiles_z = (nz + DM_ROUTE_TILE - 1) / DM_ROUTE_TILE;
-  const uint32_t tiles = tiles_x * tiles_z;
-  constexpr uint32_t CTR_WORDS = 2u * ROUTE_MAX_BATCH, ST_WORDS = 8u;   // the slots; the four 64-bit stats as 32-bit words
-  valid_ = false;
-  w_.reserve(n);
-  cost_.reserve(n);
-  field_.reserve(n);
-  dirty_.reserve(2 * (size_t)tiles);
-  ctr_.reserve(CTR_WORDS);
-  st_.reserve(ST_WORDS / 2);
-  d_xz_.reserve(2 * DM_ROUTE_MAX_XZ);
-  h_xz_.reserve(2 * DM_ROUTE_MAX_XZ);
-  h_ctr_.reserve(CTR_WORDS + ST_WORDS);
-  if (want_field) h_field_.reserve(n);
-  memcpy(h_xz_.p, goals_xz, sizeof(uint32_t) * 2 * n_goals);
-  LX_HIP(hipMemcpyAsync(d_xz_.p, h_xz_.p, sizeof(uint32_t) * 2 * n_goals, hipMemcpyHostToDevice, st));
-  LX_HIP(hipMemsetAsync(dirty_.p, 0, sizeof(uint32_t) * 2 * (size_t)tiles, st));
-  LX_HIP(hipMemsetAsync(st_.p, 0, sizeof(uint32_t) * ST_WORDS, st));
-  const dim3 per_cell((n + 255u) / 256u), per_tile(tiles_x, tiles_z);
-  const int diag = c.connectivity == 8u ? 1 : 0;
-  hipLaunchKernelGGL(k_dm_route_weights, per_cell, dim3(256), 0, st, d_cells, n, c, w_.p, cost_.p, st_.p);
-  hipLaunchKernelGGL(k_dm_route_seed, dim3((n_goals + 255u) / 256u), dim3(256), 0, st, d_xz_.p, n_goals, nx, nz, tiles_x, w_.p, cost_.p,
-                     dirty_.p, st_.p);
-  LX_HIP(hipGetLastError());
-  struct Ops {
-    DmRoute& r;
-    uint32_t nx, nz, tiles;
-    int diag;
-    dim3 per_tile;
-    hipStream_t st;
-    void begin(uint32_t) { LX_HIP(hipMemsetAsync(r.ctr_.p, 0, sizeof(uint32_t) * CTR_WORDS, st)); }
-    void round(uint64_t, uint32_t read_plane, uint32_t mark_plane, uint32_t slot) {
-      hipLaunchKernelGGL(k_dm_route_relax, per_tile, dim3(256), 0, st, nx, nz, diag, r.w_.p, r.cost_.p, r.dirty_.p + (size_t)read_plane * tiles,
-                         r.dirty_.p + (size_t)mark_plane * tiles, r.ctr_.p + 2u * slot);
-    }
-    const RouteSlot* look(uint32_t k) {
-      LX_HIP(hipGetLastError());
-      store_to_pinned_u32(r.h_ctr_.p, r.ctr_.p, 2u * k, st);
-      LX_HIP(hipStreamSynchronize(st));
-      return (const RouteSlot*)r.h_ctr_.p;
-    }
-  } ops{*this, nx, nz, tiles, diag, per_tile, st};
-  const RouteOutcome o = route_schedule(ops, RoutePlan{batch, (uint64_t)n + 2u});
-  if (!o.settled) throw Error(LOAMX_E_INTERNAL, "route: the relaxation did not settle within nx * nz + 2 rounds");
-  hipLaunchKernelGGL(k_dm_route_next, per_cell, dim3(256), 0, st, nx, nz, diag, w_.p, cost_.p, field_.p, st_.p);
-  LX_HIP(hipGetLastError());
-  store_to_pinned_u32(h_ctr_.p + CTR_WORDS, (const uint32_t*)st_.p, ST_WORDS, st);
-  if (want_field) h_field_.fetch(field_.p, n, st);
-  LX_HIP(hipStreamSynchronize(st));
-  uint64_t s4[4];
-  memcpy(s4, h_ctr_.p + CTR_WORDS, sizeof(s4));
-  for (int k = 0; k < 4; k++) stats[k] = s4[k];
-  stats[4] = o.rounds;
-  stats[5] = o.tile_runs;
-  active_rounds = o.active_rounds;
-  nx_ = nx;
-  nz_ = nz;
-  valid_ = true;
-  return want_field ? h_field_.data() : nullptr;
-}
-
-void DmRoute::trace(const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity, uint32_t* lengths, hipStream_t st) {
-  d_xz_.reserve(2 * DM_ROUTE_MAX_XZ);
-  h_xz_.reserve(2 * DM_ROUTE_MAX_XZ);
-  d_len_.reserve(DM_ROUTE_MAX_XZ);
-  d_off_.reserve(DM_ROUTE_MAX_XZ);
-  h_len_.reserve(DM_ROUTE_MAX_XZ);
-  h_off_.reserve(DM_ROUTE_MAX_XZ);
-  memcpy(h_xz_.p, starts_xz, sizeof(uint32_t) * 2 * n_starts);
-  LX_HIP(hipMemcpyAsync(d_xz_.p, h_xz_.p, sizeof(uint32_t) * 2 * n_starts, hipMemcpyHostToDevice, st));
-  const dim3 per_start((n_starts + 255u) / 256u);
-  hipLaunchKernelGGL(k_dm_route_trace, per_start, dim3(256), 0, st, field_.p, nx_, nz_, d_xz_.p, n_starts, capacity,
-                     (const unsigned long long*)nullptr, d_len_.p, (uint32_t*)nullptr);
-  LX_HIP(hipGetLastError());
-  store_to_pinned_u32(h_len_.p, d_len_.p, n_starts, st);
-  LX_HIP(hipStreamSynchronize(st));
-  // the routes back to back on the device: start i's min(length, capacity) pairs begin at pair offsets[i]
-  size_t total = 0;
-  for (uint32_t i = 0; i < n_starts; i++) {
-    h_off_.p[i] = total;
-    total += std::min(h_len_.p[i], capacity);
-  }
-  if (total) {
-    d_routes_.reserve(2 * total);
-    h_routes_.reserve(2 * total);
-    LX_HIP(hipMemcpyAsync(d_off_.p, h_off_.p, sizeof(unsigned long long) * n_starts, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_dm_route_trace, per_start, dim3(256), 0, st, field_.p, nx_, nz_, d_xz_.p, n_starts, capacity, d_off_.p, d_len_.p,
-                       d_routes_.p);
-    LX_HIP(hipGetLastError());
-    store_to_pinned_u32(h_routes_.p, d_routes_.p, 2 * total, st);
-    LX_HIP(hipStreamSynchronize(st));
-  }
-  for (uint32_t i = 0; i < n_starts; i++) {
-    const size_t m = std::min(h_len_.p[i], capacity);
-    if (m) memcpy(out_xz + 2 * (size_t)capacity * i, h_routes_.p + 2 * (size_t)h_off_.p[i], sizeof(uint32_t) * 2 * m);
-    lengths[i] = h_len_.p[i];
-  }
-}
-
 // include/loamx.h, loamx_densemap_route: the grid's kernels as grid() runs them, the route on their records where they lie
 void DenseMap::route(const loamx_densemap_grid_config& c, const loamx_densemap_static_rule* rule, const loamx_grid_route_config& rc,
                      const uint32_t* goals_xz, uint32_t n_goals, loamx_grid_cell* out_cells, loamx_route_cell* out_field, uint64_t stats[6]) {
@@ -365,28 +149,16 @@ void DenseMap::route(const loamx_densemap_grid_config& c, const loamx_densemap_s
   wait_adds();
   const size_t n = (size_t)c.nx * c.nz;
   const loamx_grid_cell* d_cells = grid_.enqueue(tab_, c, rule, (double)cfg.leaf, own_);
-  uint64_t s[6];
-  const loamx_route_cell* field = route_.run(d_cells, c.nx, c.nz, rc, goals_xz, n_goals, out_field != nullptr, s, own_);
-  const loamx_grid_cell* cells = out_cells ? grid_.fetch(d_cells, n, own_) : nullptr;
-  if (out_cells) memcpy(out_cells, cells, sizeof(loamx_grid_cell) * n);
-  if (out_field) memcpy(out_field, field, sizeof(loamx_route_cell) * n);
-  if (stats) memcpy(stats, s, sizeof(s));
+  route_on(route_, d_cells, c.nx, 1u, c.nz, rc, goals_xz, n_goals, out_field, stats, [&] {
+    if (out_cells) memcpy(out_cells, grid_.fetch(d_cells, n, own_), sizeof(loamx_grid_cell) * n);
+  });
 }
 // loamx_densemap_route_cells: the same on the caller's records (every cls checked), in a buffer of the route's own
 void DenseMap::route_cells(const loamx_grid_cell* cells, uint32_t nx, uint32_t nz, const loamx_grid_route_config& rc, const uint32_t* goals_xz,
                            uint32_t n_goals, loamx_route_cell* out_field, uint64_t stats[6]) {
   LX_HIP(hipSetDevice(cfg.device));
   wait_adds();
-  const size_t n = (size_t)nx * nz;
-  uint64_t s[6];
-  const loamx_route_cell* field = route_.run(route_.upload(cells, n, own_), nx, nz, rc, goals_xz, n_goals, out_field != nullptr, s, own_);
-  if (out_field) memcpy(out_field, field, sizeof(loamx_route_cell) * n);
-  if (stats) memcpy(stats, s, sizeof(s));
-}
-void DenseMap::route_trace(const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity, uint32_t* lengths) {
-  LX_REQUIRE(route_.has_field(), "the handle has no field yet (loamx_densemap_route, loamx_densemap_route_cells)");
-  LX_HIP(hipSetDevice(cfg.device));
-  route_.trace(starts_xz, n_starts, out_xz, capacity, lengths, own_);
+  route_on(route_, route_.upload(cells, (size_t)nx * nz, own_), nx, 1u, nz, rc, goals_xz, n_goals, out_field, stats);
 }
 
 // the checks the route's entry points share: the configuration (NULL: the defaults), the goals and the window's size
@@ -394,9 +166,8 @@ static loamx_grid_route_config checked_route(const loamx_grid_route_config* cfg,
                                              uint32_t nz) {
   const loamx_grid_route_config rc = or_default(cfg, loamx_grid_route_default_config);
   dm_route_check(rc);
-  LX_REQUIRE(goals_xz, "goals_xz is NULL");
-  LX_REQUIRE(n_goals >= 1u && n_goals <= 4096u, "n_goals must be in [1, 4096]");
-  LX_REQUIRE(nx >= 1u && nz >= 1u && (uint64_t)nx * nz <= (1ull << 22), "nx * nz must be in [1, 2^22] for a route");
+  dm_route_check_tuples<DmRouteGrid>(goals_xz, n_goals, "goals");
+  LX_REQUIRE(nx >= 1u && nz >= 1u && (uint64_t)nx * nz <= DM_ROUTE_MAX_CELLS, "nx * nz must be in [1, 2^22] for a route");
   return rc;
 }
 
@@ -461,26 +232,11 @@ int loamx_densemap_route_cells(loamx_densemap* h, const loamx_grid_cell* cells, 
 
 int loamx_densemap_route_trace(loamx_densemap* h, const uint32_t* starts_xz, uint32_t n_starts, uint32_t* out_xz, uint32_t capacity,
                                uint32_t* lengths) {
-  return guard([&]() {
-    LX_REQUIRE(h, "h is NULL");
-    LX_REQUIRE(starts_xz, "starts_xz is NULL");
-    LX_REQUIRE(n_starts >= 1u && n_starts <= 4096u, "n_starts must be in [1, 4096]");
-    LX_REQUIRE(out_xz || !capacity, "out_xz is NULL");
-    LX_REQUIRE(lengths, "lengths is NULL");
-    h->d.route_trace(starts_xz, n_starts, out_xz, capacity, lengths);
-    return LOAMX_OK;
-  });
+  return dm_route_trace_entry<DmRouteGrid>(h, &DenseMap::router, starts_xz, n_starts, out_xz, capacity, lengths);
 }
 
 // bench / test hooks (not in include/loamx.h): the route's rounds per look (1..64), and the rounds of the last route in which a tile ran
-int loamx_densemap_route_set_batch(loamx_densemap* h, uint32_t batch) {
-  return guard([&]() {
-    LX_REQUIRE(h, "NULL handle");
-    LX_REQUIRE(batch >= 1u && batch <= 64u, "batch must be in [1, 64]");
-    h->d.router().batch = batch;
-    return LOAMX_OK;
-  });
-}
+int loamx_densemap_route_set_batch(loamx_densemap* h, uint32_t batch) { return dm_route_set_batch_entry(h, &DenseMap::router, batch); }
 uint64_t loamx_densemap_route_active_rounds(loamx_densemap* h) { return h ? h->d.router().active_rounds : 0; }
 
 int loamx_grid_route_trace(const loamx_route_cell* field, uint32_t nx, uint32_t nz, uint32_t start_x, uint32_t start_z, uint32_t* out_xz,
@@ -490,33 +246,8 @@ int loamx_grid_route_trace(const loamx_route_cell* field, uint32_t nx, uint32_t 
     LX_REQUIRE(nx >= 1u && nz >= 1u && (uint64_t)nx * nz <= DM_ROUTE_MAX_CELLS, "nx * nz must be in [1, 2^22]");
     LX_REQUIRE(out_xz || !capacity, "out_xz is NULL");
     LX_REQUIRE(length, "length is NULL");
-    uint32_t len = 0;
-    // the walk twice: checked to its end first, so that a field that is not one of ours leaves nothing written
-    for (int pass = 0; pass < 2; pass++) {
-      uint32_t x = start_x, z = start_z;
-      len = 0;
-      if (x >= nx || z >= nz) break;
-      for (;;) {
-        const loamx_route_cell& r = field[(size_t)z * nx + x];
-        LX_REQUIRE(r.next <= LOAMX_ROUTE_NONE, "field: a next above 9");
-        if (r.next == LOAMX_ROUTE_NONE) {
-          LX_REQUIRE(len == 0u, "field: the route ends on a cell that is no goal");
-          break;
-        }
-        if (pass && len < capacity) {
-          out_xz[2 * (size_t)len] = x;
-          out_xz[2 * (size_t)len + 1] = z;
-        }
-        len++;
-        if (r.next == LOAMX_ROUTE_GOAL) break;
-        const uint32_t bx = x + (uint32_t)dm_route_dx(r.next), bz = z + (uint32_t)dm_route_dz(r.next);
-        LX_REQUIRE(bx < nx && bz < nz, "field: a step leaves the window");
-        LX_REQUIRE(field[(size_t)bz * nx + bx].cost < r.cost, "field: a step to a cell whose cost is not strictly smaller");
-        x = bx;
-        z = bz;
-      }
-    }
-    *length = len;
+    const uint32_t start[2] = {start_x, start_z};
+    *length = dm_route_walk<DmRouteGrid>(field, nx, 1u, nz, start, out_xz, capacity);
     return LOAMX_OK;
   });
 }

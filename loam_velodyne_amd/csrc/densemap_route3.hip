@@ -1,83 +1,27 @@
-// Routing in 3-D over the distance field (densemap.hpp DmRoute3, include/loamx.h loamx_densemap_route3 and what goes with it): the
-// cost-to-go of every cell of a 3-D window towards a set of goal cells, the next step per cell and routes traced from many starts.
-//
-// k_dm_route3_weights gives every cell its weight (a byte, from its 16-bit d2) and the cost UINT32_MAX, k_dm_route3_seed puts 0 on the
-// used goals and marks their bricks, k_dm_route3_relax is launched round after round (densemap_route_schedule.hpp, as it is) until no
-// brick is marked, k_dm_route3_next derives next from the final costs and counts, k_dm_route3_trace walks next from many starts.
-// Integer atomics only; the costs are the unique fixed point of cost[c] = min over legal moves of cost[nb] + move, so no word
-// depends on the schedule, the number of rounds or the rounds per look.
+// Routing in 3-D over the distance field (DmRoute3, include/loamx.h loamx_densemap_route3 and what goes with it): the route engine of
+// densemap_route_core.hpp for the kind DmRouteVol, compiled here, the relax kernel of that kind, and the entry points.
 //
 // k_dm_route3_relax, one block of 256 threads per brick of 8 x 8 x 8 cells: the brick's weights and costs with a halo of one cell
 // (10^3 cells, 1,000 + 4,000 bytes) go to LDS, every thread works out once, for its two cells, which of the 26 moves are legal and
 // what they cost (every intermediate cell of the corner rule lies in the halo, the steps being +-1), the block relaxes in LDS until
-// no cell of the brick changes, and writes back the cells that fell.  Only the owning brick writes a cell.  The argument of
-// densemap_route.hip, restated for three dimensions:
-//   * a halo read of a neighbour brick that is writing in the same launch is benign: costs only fall, an aligned 32-bit read is
-//     whole, and every value ever stored is the cost of a real path, an upper bound of the final cost;
-//   * a brick whose border cell fell marks, AFTER its stores, every one of the up to 26 neighbour bricks whose halo holds that cell
-//     (a face cell one, an edge cell three, a corner cell seven), in the plane of the next round.  A neighbour that read the old
-//     value in this launch therefore re-runs behind the kernel boundary, where the new value is visible; a brick that is not marked
-//     has a halo that did not change since it last ran, and is at its fixed point already;
-//   * so after round r (r = 0: the goals' bricks) every cell whose cheapest path crosses at most r brick borders is final: by
-//     induction, the path's last cell h before it enters the brick is final after round r - 1, the round that made it final marked
-//     this brick (a move is one step on every axis, so h lies in this brick's halo), the brick runs behind that round, reads h final
-//     and relaxes the path's stretch inside the brick to the end in LDS.  The corner rule does not disturb this: it only decides
-//     which moves exist, from weights, which never change.
-// With M the largest such count over the reachable cells the costs are final after round M, round M + 1 runs what those last falls
-// marked and changes nothing, and no later round runs a brick: at most M + 2 rounds run a brick, M < nx * ny * nz.
-// Inside LDS a sweep lowers at least the next cell of every unfinished cheapest path, so 512 sweeps and one that finds nothing
-// bound the loop; the bound (512 + 2) is in the code, and a brick that ever left it unsettled would mark itself.
+// no cell of the brick changes, and writes back the cells that fell.  Only the owning brick writes a cell.  Why the rounds reach the
+// fixed point is argued in the head comment of densemap_route.hip, with "brick" for "tile"; three dimensions add to it only that
+//   * a brick whose border cell fell marks up to 26 neighbour bricks, every one whose halo holds that cell: a face cell one, an edge
+//     cell three, a corner cell seven;
+//   * a move is one step on every axis, so the last cell of a cheapest path before it enters a brick lies in that brick's halo, as
+//     the induction needs;
+//   * the corner rule does not disturb the argument: it only decides which moves exist, from weights, which never change;
+//   * the bounds are M < nx * ny * nz for the rounds and 8 * 8 * 8 sweeps and one that finds nothing (512 + 2 in the code) in LDS.
 #include "densemap_map.hpp"
-#include "densemap_route_schedule.hpp"
-#include "pinned_copy.hpp"
 
 namespace loamx {
 
-constexpr int DM_ROUTE3_BRICK = 8;
+constexpr int DM_ROUTE3_BRICK = DmRouteVol::TILE;
 constexpr int DM_ROUTE3_SIDE = DM_ROUTE3_BRICK + 2;   // with the halo
 constexpr int DM_ROUTE3_LDS = DM_ROUTE3_SIDE * DM_ROUTE3_SIDE * DM_ROUTE3_SIDE;
 constexpr int DM_ROUTE3_SWEEPS = DM_ROUTE3_BRICK * DM_ROUTE3_BRICK * DM_ROUTE3_BRICK + 2;
-constexpr uint32_t DM_ROUTE3_MAX_CELLS = 1u << 22;
 constexpr uint32_t DM_ROUTE3_MAX_SIDE = 1024;
-constexpr uint32_t DM_ROUTE3_MAX_XYZ = 4096;   // goals, starts
-constexpr uint32_t DM_ROUTE3_INF = LOAMX_ROUTE_UNREACHABLE;
-
-__host__ __device__ inline uint32_t dm_route3_scale(int dx, int dy, int dz) { return 3u + 2u * (uint32_t)((dx != 0) + (dy != 0) + (dz != 0)); }
-
-__global__ __launch_bounds__(256) void k_dm_route3_weights(const unsigned short* __restrict__ d2, uint32_t n, loamx_route3_config C,
-                                                           unsigned char* __restrict__ w, uint32_t* __restrict__ cost,
-                                                           unsigned long long* __restrict__ st) {
-  __shared__ uint32_t s_n;
-  if (threadIdx.x == 0) s_n = 0u;
-  __syncthreads();
-  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t wt = 0u;
-  if (c < n) {
-    wt = dm_route3_weight(d2[c], C);   // (16 bits per cell, two cells per word of the distance field's plane)
-    w[c] = (unsigned char)wt;
-    cost[c] = DM_ROUTE3_INF;
-  }
-  const unsigned long long b = __ballot(wt > 0u);
-  if ((threadIdx.x & 63u) == 0u && b) atomicAdd(&s_n, (uint32_t)__popcll(b));
-  __syncthreads();
-  if (threadIdx.x == 0 && s_n) atomicAdd(&st[0], (unsigned long long)s_n);
-}
-
-// one thread per goal triple: 0 on a used goal (every writer stores the same word), its brick marked for round 0
-__global__ __launch_bounds__(256) void k_dm_route3_seed(const uint32_t* __restrict__ goals, uint32_t n_goals, uint32_t nx, uint32_t ny,
-                                                        uint32_t nz, uint32_t bricks_x, uint32_t bricks_y,
-                                                        const unsigned char* __restrict__ w, uint32_t* __restrict__ cost,
-                                                        uint32_t* __restrict__ dirty, unsigned long long* __restrict__ st) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_goals) return;
-  const uint32_t x = goals[3u * i], y = goals[3u * i + 1u], z = goals[3u * i + 2u];
-  if (x >= nx || y >= ny || z >= nz) return;
-  const uint32_t c = (z * ny + y) * nx + x;
-  if (!w[c]) return;
-  cost[c] = 0u;
-  dirty[((z / DM_ROUTE3_BRICK) * bricks_y + y / DM_ROUTE3_BRICK) * bricks_x + x / DM_ROUTE3_BRICK] = 1u;
-  atomicAdd(&st[2], 1ull);
-}
+constexpr uint32_t DM_ROUTE3_INF = DM_ROUTE_INF;
 
 // one round (the file's head comment).  grid: bricks_x x bricks_y x bricks_z; slot: {bricks that ran, bricks that marked} of this round
 __global__ __launch_bounds__(256) void k_dm_route3_relax(uint32_t nx, uint32_t ny, uint32_t nz, uint32_t conn,
@@ -194,97 +138,6 @@ __global__ __launch_bounds__(256) void k_dm_route3_relax(uint32_t nx, uint32_t n
   }
 }
 
-// one thread per cell: the record from the final costs, the smallest d first; the reachable cells and the largest finite cost
-__global__ __launch_bounds__(256) void k_dm_route3_next(uint32_t nx, uint32_t ny, uint32_t nz, uint32_t conn,
-                                                        const unsigned char* __restrict__ w, const uint32_t* __restrict__ cost,
-                                                        loamx_route_cell* __restrict__ field, unsigned long long* __restrict__ st) {
-  __shared__ uint32_t s_n, s_max;
-  if (threadIdx.x == 0) s_n = s_max = 0u;
-  __syncthreads();
-  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-  bool reach = false;
-  if (c < nx * ny * nz) {
-    const uint32_t x = c % nx, y = (c / nx) % ny, z = c / (nx * ny), cc = cost[c], wa = w[c];
-    uint32_t next = LOAMX_ROUTE3_NONE;
-    reach = cc != DM_ROUTE3_INF;
-    if (cc == 0u) next = LOAMX_ROUTE3_GOAL;
-    else if (reach) {
-      for (uint32_t d = 0; d < conn && next == LOAMX_ROUTE3_NONE; d++) {
-        int dx, dy, dz;
-        dm_route3_move(d, dx, dy, dz);
-        const uint32_t bxx = x + (uint32_t)dx, byy = y + (uint32_t)dy, bzz = z + (uint32_t)dz;   // (a cell before the window wraps)
-        if (bxx >= nx || byy >= ny || bzz >= nz) continue;
-        const uint32_t nb = (bzz * ny + byy) * nx + bxx, wb = w[nb], cn = cost[nb];
-        if (!wb || cn == DM_ROUTE3_INF) continue;
-        bool ok = true;   // no corner cutting (the cells between lie in the box of a and b, inside the window)
-        for (int m = 1; m < 7 && ok; m++) {
-          const uint32_t sx = (m & 1) ? bxx : x, sy = (m & 2) ? byy : y, sz = (m & 4) ? bzz : z;
-          ok = w[(sz * ny + sy) * nx + sx] > 0u;   // (a or b again where an axis does not move: both > 0)
-        }
-        if (ok && cn + dm_route3_scale(dx, dy, dz) * (wa + wb) == cc) next = d;
-      }
-      atomicMax(&s_max, cc);
-    }
-    loamx_route_cell r;
-    r.cost = cc;
-    r.next = next;
-    field[c] = r;
-  }
-  const unsigned long long b = __ballot(reach);
-  if ((threadIdx.x & 63u) == 0u && b) atomicAdd(&s_n, (uint32_t)__popcll(b));
-  __syncthreads();
-  if (threadIdx.x == 0 && s_n) {
-    atomicAdd(&st[1], (unsigned long long)s_n);
-    atomicMax(&st[3], (unsigned long long)s_max);
-  }
-}
-
-// one thread per start, walking next; bounded by nx * ny * nz steps.  offsets NULL: the lengths only.  Otherwise start i's triples go
-// to out + 3 * offsets[i], the first min(length, capacity) of them (the same walk as the counting pass over the same field)
-__global__ __launch_bounds__(256) void k_dm_route3_trace(const loamx_route_cell* __restrict__ field, uint32_t nx, uint32_t ny, uint32_t nz,
-                                                         const uint32_t* __restrict__ starts, uint32_t n_starts, uint32_t capacity,
-                                                         const unsigned long long* __restrict__ offsets, uint32_t* __restrict__ lengths,
-                                                         uint32_t* __restrict__ out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_starts) return;
-  uint32_t x = starts[3u * i], y = starts[3u * i + 1u], z = starts[3u * i + 2u], len = 0u;
-  if (x < nx && y < ny && z < nz) {
-    const uint32_t cells = nx * ny * nz;
-    for (uint32_t step = 0; step < cells; step++) {
-      const uint32_t next = field[((size_t)z * ny + y) * nx + x].next;
-      if (next >= LOAMX_ROUTE3_NONE) break;
-      if (offsets && len < capacity) {
-        uint32_t* o = out + 3ull * (offsets[i] + len);
-        o[0] = x;
-        o[1] = y;
-        o[2] = z;
-      }
-      len++;
-      if (next == LOAMX_ROUTE3_GOAL) break;
-      int dx, dy, dz;
-      dm_route3_move(next, dx, dy, dz);
-      x += (uint32_t)dx;
-      y += (uint32_t)dy;
-      z += (uint32_t)dz;
-      if (x >= nx || y >= ny || z >= nz) break;   // (never on a field of k_dm_route3_next)
-    }
-  }
-  if (!offsets) lengths[i] = len;
-}
-
-void dm_route3_check(const loamx_route3_config& c) {
-  LX_REQUIRE(c.connectivity == 6u || c.connectivity == 18u || c.connectivity == 26u, "connectivity must be 6, 18 or 26");
-  LX_REQUIRE(c.min_d2 >= 1u, "min_d2 must be >= 1");
-  LX_REQUIRE(c.soft_d2 <= 65025u, "soft_d2 must be in [0, 65025]");
-  LX_REQUIRE(c.soft_weight <= 15u, "soft_weight must be in [0, 15]");
-}
-
-const unsigned short* DmRoute3::upload(const uint16_t* d2, size_t n, hipStream_t st) {
-  own_d2_.reserve((n + 1) / 2);
-  LX_HIP(hipMemcpyAsync(own_d2_.p, d2, sizeof(uint16_t) * n, hipMemcpyHostToDevice, st));
-  return (const unsigned short*)own_d2_.p;
-}
-
 // Rounds per look: DmRoute3::batch = 16.  Measured on one MI355X, one run (scripts/bench_densemap_route3.py --batches 1,2,4,8,16,32,64;
 // the blocking route3_cells with nothing back, the 2 MB upload of the d2 plane included, median of 30 / of 10 after 3 warm-up calls):
 //   batch                                            1       2       4       8      16      32      64
@@ -295,107 +148,18 @@ const unsigned short* DmRoute3::upload(const uint16_t* d2, size_t n, hipStream_t
 // for up to 63 idle launches instead of 15.  So the 2-D route's 16 holds here as well.  A round of the serpentine, 2,048 blocks of which
 // about 32 run their brick, takes 26 us on average (656 rounds, 20,852 brick runs in 17.4 ms); nothing in the table speaks for a brick
 // other than 8 x 8 x 8, and none was tried.
-const loamx_route_cell* DmRoute3::run(const unsigned short* d_d2, uint32_t nx, uint32_t ny, uint32_t nz, const loamx_route3_config& c,
-                                      const uint32_t* goals_xyz, uint32_t n_goals, bool want_field, uint64_t stats[6], hipStream_t st) {
-  const uint32_t n = nx * ny * nz;
-  const uint32_t bricks_x = (nx + DM_ROUTE3_BRICK - 1) / DM_ROUTE3_BRICK, bricks_y = (ny + DM_ROUTE3_BRICK - 1) / DM_ROUTE3_BRICK,
-                 bricks_z = (nz + DM_ROUTE3_BRICK - 1) / DM_ROUTE3_BRICK;
-  const uint32_t bricks = bricks_x * bricks_y * bricks_z;
-  constexpr uint32_t CTR_WORDS = 2u * ROUTE_MAX_BATCH, ST_WORDS = 8u;   // the slots; the four 64-bit stats as 32-bit words
-  valid_ = false;
-  w_.reserve(n);
-  cost_.reserve(n);
-  field_.reserve(n);
-  dirty_.reserve(2 * (size_t)bricks);
-  ctr_.reserve(CTR_WORDS);
-  st_.reserve(ST_WORDS / 2);
-  d_xyz_.reserve(3 * DM_ROUTE3_MAX_XYZ);
-  h_xyz_.reserve(3 * DM_ROUTE3_MAX_XYZ);
-  h_ctr_.reserve(CTR_WORDS + ST_WORDS);
-  if (want_field) h_field_.reserve(n);
-  memcpy(h_xyz_.p, goals_xyz, sizeof(uint32_t) * 3 * n_goals);
-  LX_HIP(hipMemcpyAsync(d_xyz_.p, h_xyz_.p, sizeof(uint32_t) * 3 * n_goals, hipMemcpyHostToDevice, st));
-  LX_HIP(hipMemsetAsync(dirty_.p, 0, sizeof(uint32_t) * 2 * (size_t)bricks, st));
-  LX_HIP(hipMemsetAsync(st_.p, 0, sizeof(uint32_t) * ST_WORDS, st));
-  const dim3 per_cell((n + 255u) / 256u), per_brick(bricks_x, bricks_y, bricks_z);
-  hipLaunchKernelGGL(k_dm_route3_weights, per_cell, dim3(256), 0, st, d_d2, n, c, w_.p, cost_.p, st_.p);
-  hipLaunchKernelGGL(k_dm_route3_seed, dim3((n_goals + 255u) / 256u), dim3(256), 0, st, d_xyz_.p, n_goals, nx, ny, nz, bricks_x, bricks_y,
-                     w_.p, cost_.p, dirty_.p, st_.p);
-  LX_HIP(hipGetLastError());
-  struct Ops {
-    DmRoute3& r;
-    uint32_t nx, ny, nz, bricks, conn;
-    dim3 per_brick;
-    hipStream_t st;
-    void begin(uint32_t) { LX_HIP(hipMemsetAsync(r.ctr_.p, 0, sizeof(uint32_t) * CTR_WORDS, st)); }
-    void round(uint64_t, uint32_t read_plane, uint32_t mark_plane, uint32_t slot) {
-      hipLaunchKernelGGL(k_dm_route3_relax, per_brick, dim3(256), 0, st, nx, ny, nz, conn, r.w_.p, r.cost_.p,
-                         r.dirty_.p + (size_t)read_plane * bricks, r.dirty_.p + (size_t)mark_plane * bricks, r.ctr_.p + 2u * slot);
-    }
-    const RouteSlot* look(uint32_t k) {
-      LX_HIP(hipGetLastError());
-      store_to_pinned_u32(r.h_ctr_.p, r.ctr_.p, 2u * k, st);
-      LX_HIP(hipStreamSynchronize(st));
-      return (const RouteSlot*)r.h_ctr_.p;
-    }
-  } ops{*this, nx, ny, nz, bricks, c.connectivity, per_brick, st};
-  const RouteOutcome o = route_schedule(ops, RoutePlan{batch, (uint64_t)n + 2u});
-  if (!o.settled) throw Error(LOAMX_E_INTERNAL, "route3: the relaxation did not settle within nx * ny * nz + 2 rounds");
-  hipLaunchKernelGGL(k_dm_route3_next, per_cell, dim3(256), 0, st, nx, ny, nz, c.connectivity, w_.p, cost_.p, field_.p, st_.p);
-  LX_HIP(hipGetLastError());
-  store_to_pinned_u32(h_ctr_.p + CTR_WORDS, (const uint32_t*)st_.p, ST_WORDS, st);
-  if (want_field) h_field_.fetch(field_.p, n, st);
-  LX_HIP(hipStreamSynchronize(st));
-  uint64_t s4[4];
-  memcpy(s4, h_ctr_.p + CTR_WORDS, sizeof(s4));
-  for (int k = 0; k < 4; k++) stats[k] = s4[k];
-  stats[4] = o.rounds;
-  stats[5] = o.tile_runs;
-  active_rounds = o.active_rounds;
-  nx_ = nx;
-  ny_ = ny;
-  nz_ = nz;
-  valid_ = true;
-  return want_field ? h_field_.data() : nullptr;
+void DmRouteVol::relax(uint32_t nx, uint32_t ny, uint32_t nz, uint32_t connectivity, const unsigned char* w, uint32_t* cost,
+                       uint32_t* dirty_read, uint32_t* dirty_mark, uint32_t* slot, hipStream_t st) {
+  hipLaunchKernelGGL(k_dm_route3_relax, dim3(dm_route_tiles<DmRouteVol>(nx), dm_route_tiles<DmRouteVol>(ny), dm_route_tiles<DmRouteVol>(nz)),
+                     dim3(256), 0, st, nx, ny, nz, connectivity, w, cost, dirty_read, dirty_mark, slot);
 }
+template class DmRouteT<DmRouteVol>;   // upload, run and trace of the engine, and its four kernels, for the distance field
 
-// the counting pass, the offsets and the writing pass of DmRoute::trace, with triples
-void DmRoute3::trace(const uint32_t* starts_xyz, uint32_t n_starts, uint32_t* out_xyz, uint32_t capacity, uint32_t* lengths, hipStream_t st) {
-  d_xyz_.reserve(3 * DM_ROUTE3_MAX_XYZ);
-  h_xyz_.reserve(3 * DM_ROUTE3_MAX_XYZ);
-  d_len_.reserve(DM_ROUTE3_MAX_XYZ);
-  d_off_.reserve(DM_ROUTE3_MAX_XYZ);
-  h_len_.reserve(DM_ROUTE3_MAX_XYZ);
-  h_off_.reserve(DM_ROUTE3_MAX_XYZ);
-  memcpy(h_xyz_.p, starts_xyz, sizeof(uint32_t) * 3 * n_starts);
-  LX_HIP(hipMemcpyAsync(d_xyz_.p, h_xyz_.p, sizeof(uint32_t) * 3 * n_starts, hipMemcpyHostToDevice, st));
-  const dim3 per_start((n_starts + 255u) / 256u);
-  hipLaunchKernelGGL(k_dm_route3_trace, per_start, dim3(256), 0, st, field_.p, nx_, ny_, nz_, d_xyz_.p, n_starts, capacity,
-                     (const unsigned long long*)nullptr, d_len_.p, (uint32_t*)nullptr);
-  LX_HIP(hipGetLastError());
-  store_to_pinned_u32(h_len_.p, d_len_.p, n_starts, st);
-  LX_HIP(hipStreamSynchronize(st));
-  // the routes back to back on the device: start i's min(length, capacity) triples begin at triple offsets[i]
-  size_t total = 0;
-  for (uint32_t i = 0; i < n_starts; i++) {
-    h_off_.p[i] = total;
-    total += std::min(h_len_.p[i], capacity);
-  }
-  if (total) {
-    d_routes_.reserve(3 * total);
-    h_routes_.reserve(3 * total);
-    LX_HIP(hipMemcpyAsync(d_off_.p, h_off_.p, sizeof(unsigned long long) * n_starts, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_dm_route3_trace, per_start, dim3(256), 0, st, field_.p, nx_, ny_, nz_, d_xyz_.p, n_starts, capacity, d_off_.p,
-                       d_len_.p, d_routes_.p);
-    LX_HIP(hipGetLastError());
-    store_to_pinned_u32(h_routes_.p, d_routes_.p, 3 * total, st);
-    LX_HIP(hipStreamSynchronize(st));
-  }
-  for (uint32_t i = 0; i < n_starts; i++) {
-    const size_t m = std::min(h_len_.p[i], capacity);
-    if (m) memcpy(out_xyz + 3 * (size_t)capacity * i, h_routes_.p + 3 * (size_t)h_off_.p[i], sizeof(uint32_t) * 3 * m);
-    lengths[i] = h_len_.p[i];
-  }
+void dm_route3_check(const loamx_route3_config& c) {
+  LX_REQUIRE(c.connectivity == 6u || c.connectivity == 18u || c.connectivity == 26u, "connectivity must be 6, 18 or 26");
+  LX_REQUIRE(c.min_d2 >= 1u, "min_d2 must be >= 1");
+  LX_REQUIRE(c.soft_d2 <= 65025u, "soft_d2 must be in [0, 65025]");
+  LX_REQUIRE(c.soft_weight <= 15u, "soft_weight must be in [0, 15]");
 }
 
 // include/loamx.h, loamx_densemap_route3: the distance field as dist() runs it with both planes NULL, the route on its d2 where it lies
@@ -413,27 +177,14 @@ void DenseMap::route3_last(const loamx_route3_config& rc, const uint32_t* goals_
   LX_HIP(hipSetDevice(cfg.device));
   wait_adds();
   const loamx_densemap_dist_config& c = dist_.config();
-  const size_t n = (size_t)c.nx * c.ny * c.nz;
-  uint64_t s[6];
-  const loamx_route_cell* field = route3_.run(dist_.d2_on_device(), c.nx, c.ny, c.nz, rc, goals_xyz, n_goals, out_field != nullptr, s, own_);
-  if (out_field) memcpy(out_field, field, sizeof(loamx_route_cell) * n);
-  if (stats) memcpy(stats, s, sizeof(s));
+  route_on(route3_, dist_.d2_on_device(), c.nx, c.ny, c.nz, rc, goals_xyz, n_goals, out_field, stats);
 }
 // loamx_densemap_route3_cells: the same on the caller's plane, in a buffer of the route's own
 void DenseMap::route3_cells(const uint16_t* d2, uint32_t nx, uint32_t ny, uint32_t nz, const loamx_route3_config& rc, const uint32_t* goals_xyz,
                             uint32_t n_goals, loamx_route_cell* out_field, uint64_t stats[6]) {
   LX_HIP(hipSetDevice(cfg.device));
   wait_adds();
-  const size_t n = (size_t)nx * ny * nz;
-  uint64_t s[6];
-  const loamx_route_cell* field = route3_.run(route3_.upload(d2, n, own_), nx, ny, nz, rc, goals_xyz, n_goals, out_field != nullptr, s, own_);
-  if (out_field) memcpy(out_field, field, sizeof(loamx_route_cell) * n);
-  if (stats) memcpy(stats, s, sizeof(s));
-}
-void DenseMap::route3_trace(const uint32_t* starts_xyz, uint32_t n_starts, uint32_t* out_xyz, uint32_t capacity, uint32_t* lengths) {
-  LX_REQUIRE(route3_.has_field(), "the handle has no field yet (loamx_densemap_route3, loamx_densemap_route3_last, loamx_densemap_route3_cells)");
-  LX_HIP(hipSetDevice(cfg.device));
-  route3_.trace(starts_xyz, n_starts, out_xyz, capacity, lengths, own_);
+  route_on(route3_, route3_.upload(d2, (size_t)nx * ny * nz, own_), nx, ny, nz, rc, goals_xyz, n_goals, out_field, stats);
 }
 
 // the checks the route3 entry points share: the configuration (NULL: the defaults), the goals and the window's size
@@ -441,9 +192,8 @@ static loamx_route3_config checked_route3(const loamx_route3_config* cfg, const 
                                           uint32_t nz) {
   const loamx_route3_config rc = or_default(cfg, loamx_route3_default_config);
   dm_route3_check(rc);
-  LX_REQUIRE(goals_xyz, "goals_xyz is NULL");
-  LX_REQUIRE(n_goals >= 1u && n_goals <= DM_ROUTE3_MAX_XYZ, "n_goals must be in [1, 4096]");
-  LX_REQUIRE((uint64_t)nx * ny * nz <= DM_ROUTE3_MAX_CELLS, "nx * ny * nz must be <= 2^22 for a route");
+  dm_route_check_tuples<DmRouteVol>(goals_xyz, n_goals, "goals");
+  LX_REQUIRE((uint64_t)nx * ny * nz <= DM_ROUTE_MAX_CELLS, "nx * ny * nz must be <= 2^22 for a route");
   return rc;
 }
 
@@ -532,68 +282,23 @@ int loamx_densemap_route3_cells(loamx_densemap* h, const uint16_t* d2, uint32_t 
 
 int loamx_densemap_route3_trace(loamx_densemap* h, const uint32_t* starts_xyz, uint32_t n_starts, uint32_t* out_xyz, uint32_t capacity,
                                 uint32_t* lengths) {
-  return guard([&]() {
-    LX_REQUIRE(h, "h is NULL");
-    LX_REQUIRE(starts_xyz, "starts_xyz is NULL");
-    LX_REQUIRE(n_starts >= 1u && n_starts <= DM_ROUTE3_MAX_XYZ, "n_starts must be in [1, 4096]");
-    LX_REQUIRE(out_xyz || !capacity, "out_xyz is NULL");
-    LX_REQUIRE(lengths, "lengths is NULL");
-    h->d.route3_trace(starts_xyz, n_starts, out_xyz, capacity, lengths);
-    return LOAMX_OK;
-  });
+  return dm_route_trace_entry<DmRouteVol>(h, &DenseMap::router3, starts_xyz, n_starts, out_xyz, capacity, lengths);
 }
 
 // bench / test hooks (not in include/loamx.h): the rounds per look (1..64), and the rounds of the last route3 in which a brick ran
-int loamx_densemap_route3_set_batch(loamx_densemap* h, uint32_t batch) {
-  return guard([&]() {
-    LX_REQUIRE(h, "NULL handle");
-    LX_REQUIRE(batch >= 1u && batch <= 64u, "batch must be in [1, 64]");
-    h->d.router3().batch = batch;
-    return LOAMX_OK;
-  });
-}
+int loamx_densemap_route3_set_batch(loamx_densemap* h, uint32_t batch) { return dm_route_set_batch_entry(h, &DenseMap::router3, batch); }
 uint64_t loamx_densemap_route3_active_rounds(loamx_densemap* h) { return h ? h->d.router3().active_rounds : 0; }
 
 int loamx_route3_trace(const loamx_route_cell* field, uint32_t nx, uint32_t ny, uint32_t nz, const uint32_t start[3], uint32_t* out_xyz,
                        uint32_t capacity, uint32_t* length) {
   return guard([&]() {
     LX_REQUIRE(field, "field is NULL");
-    LX_REQUIRE(nx >= 1u && ny >= 1u && nz >= 1u && (uint64_t)nx * ny * nz <= DM_ROUTE3_MAX_CELLS && (uint64_t)nx * ny <= DM_ROUTE3_MAX_CELLS,
+    LX_REQUIRE(nx >= 1u && ny >= 1u && nz >= 1u && (uint64_t)nx * ny * nz <= DM_ROUTE_MAX_CELLS && (uint64_t)nx * ny <= DM_ROUTE_MAX_CELLS,
                "nx * ny * nz must be in [1, 2^22]");
     LX_REQUIRE(start, "start is NULL");
     LX_REQUIRE(out_xyz || !capacity, "out_xyz is NULL");
     LX_REQUIRE(length, "length is NULL");
-    uint32_t len = 0;
-    // the walk twice: checked to its end first, so that a field that is not one of ours leaves nothing written
-    for (int pass = 0; pass < 2; pass++) {
-      uint32_t x = start[0], y = start[1], z = start[2];
-      len = 0;
-      if (x >= nx || y >= ny || z >= nz) break;
-      for (;;) {
-        const loamx_route_cell& r = field[((size_t)z * ny + y) * nx + x];
-        LX_REQUIRE(r.next <= LOAMX_ROUTE3_NONE, "field: a next above 27");
-        if (r.next == LOAMX_ROUTE3_NONE) {
-          LX_REQUIRE(len == 0u, "field: the route ends on a cell that is no goal");
-          break;
-        }
-        if (pass && len < capacity) {
-          out_xyz[3 * (size_t)len] = x;
-          out_xyz[3 * (size_t)len + 1] = y;
-          out_xyz[3 * (size_t)len + 2] = z;
-        }
-        len++;
-        if (r.next == LOAMX_ROUTE3_GOAL) break;
-        int dx, dy, dz;
-        dm_route3_move(r.next, dx, dy, dz);
-        const uint32_t bx = x + (uint32_t)dx, by = y + (uint32_t)dy, bz = z + (uint32_t)dz;
-        LX_REQUIRE(bx < nx && by < ny && bz < nz, "field: a step leaves the window");
-        LX_REQUIRE(field[((size_t)bz * ny + by) * nx + bx].cost < r.cost, "field: a step to a cell whose cost is not strictly smaller");
-        x = bx;
-        y = by;
-        z = bz;
-      }
-    }
-    *length = len;
+    *length = dm_route_walk<DmRouteVol>(field, nx, ny, nz, start, out_xyz, capacity);
     return LOAMX_OK;
   });
 }

@@ -1,7 +1,7 @@
-// Which relaxation rounds one route call launches, and when the host looks (DmRoute::run, densemap_route.hip; no HIP in here:
-// tests/test_densemap_route_cpu.py drives it on a CPU through tests/route_schedule_driver.cpp).
+// Which relaxation rounds one route call launches, and when the host looks (DmRouteT<K>::run, densemap_route_core.hpp, for the 2-D
+// and the 3-D route alike; no HIP in here: tests/test_densemap_route_cpu.py drives it on a CPU through tests/route_schedule_driver.cpp).
 //
-// Round r = 0, 1, ... is one launch of k_dm_route_relax over every tile.  A tile runs in round r only when it is marked in dirty plane
+// Round r = 0, 1, ... is one launch of the kind's relax kernel (k_dm_route_relax, k_dm_route3_relax) over every tile or brick.  A tile runs in round r only when it is marked in dirty plane
 // r & 1, which the goals' seeding (r = 0) or the tiles of round r - 1 wrote; it clears its own mark there and marks its neighbours in
 // plane (r + 1) & 1.  Nothing marks plane r & 1 during round r and only the owner clears, so the two planes never need a memset
 // between rounds.  Every round has a slot of two counters: the tiles that ran and the tiles that marked a neighbour.

@@ -1404,15 +1404,32 @@ ROUTE_MOVES = ((1, 0), (1, 1), (0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, 
 ROUTE_CELL = np.dtype([(n, np.dtype(t)) for n, t in RouteCell._fields_])              # the field as a structured numpy array
 
 
+def _tuples(cells, dim) -> np.ndarray:
+    """(n, dim) uint32, C order, of a list of cells, each a tuple of dim window-relative indices"""
+    return np.ascontiguousarray(np.asarray(cells, np.uint32).reshape(-1, dim))
+
+
 def _xz_pairs(pairs) -> np.ndarray:
     """(n, 2) uint32, C order, of a list of (rx, rz) pairs"""
-    return np.ascontiguousarray(np.asarray(pairs, np.uint32).reshape(-1, 2))
+    return _tuples(pairs, 2)
 
 
 def _route_field(field) -> np.ndarray:
     a = np.ascontiguousarray(field)
     assert a.dtype == ROUTE_CELL and a.ndim == 2, "field must be an (nz, nx) array of ROUTE_CELL records"
     return a
+
+
+def _host_trace(fn, f, dims, start, dim, capacity):
+    """route_trace and route3_trace: fn(field, *dims, *start, out, capacity, &n) walks on the host; capacity None: asked for the
+    length first"""
+    n = C.c_uint32(0)
+    if capacity is None:
+        _check(fn(f.ctypes.data_as(C.c_void_p), *dims, *start, None, 0, C.byref(n)))
+        capacity = n.value
+    out = np.zeros((capacity, dim), np.uint32)
+    _check(fn(f.ctypes.data_as(C.c_void_p), *dims, *start, out.ctypes.data_as(C.c_void_p), C.c_uint32(capacity), C.byref(n)))
+    return out[:min(n.value, capacity)], n.value
 
 
 def route_weight(cells, cfg: RouteConfig = None) -> np.ndarray:
@@ -1434,14 +1451,7 @@ def route_trace(field, start, capacity=None):
     capacity None: the whole route.  LoamxError E_INVALID on a field that is not a route field"""
     f = _route_field(field)
     nz, nx = f.shape
-    n = C.c_uint32(0)
-    if capacity is None:
-        _check(lib().loamx_grid_route_trace(f.ctypes.data_as(C.c_void_p), nx, nz, C.c_uint32(start[0]), C.c_uint32(start[1]), None, 0, C.byref(n)))
-        capacity = n.value
-    out = np.zeros((capacity, 2), np.uint32)
-    _check(lib().loamx_grid_route_trace(f.ctypes.data_as(C.c_void_p), nx, nz, C.c_uint32(start[0]), C.c_uint32(start[1]),
-                                        out.ctypes.data_as(C.c_void_p), C.c_uint32(capacity), C.byref(n)))
-    return out[:min(n.value, capacity)], n.value
+    return _host_trace(lib().loamx_grid_route_trace, f, (nx, nz), (C.c_uint32(start[0]), C.c_uint32(start[1])), 2, capacity)
 
 
 def route_points(cfg: GridConfig, leaf: float, route, cells=None) -> np.ndarray:
@@ -1552,7 +1562,7 @@ ROUTE3_STATS = ("traversable", "reachable", "goals_used", "max_cost", "rounds", 
 
 def _xyz_triples(triples) -> np.ndarray:
     """(n, 3) uint32, C order, of a list of (rx, ry, rz) triples"""
-    return np.ascontiguousarray(np.asarray(triples, np.uint32).reshape(-1, 3))
+    return _tuples(triples, 3)
 
 
 def _route3_field(field) -> np.ndarray:
@@ -1583,15 +1593,7 @@ def route3_trace(field, start, capacity=None):
     unreachable).  capacity None: the whole route.  LoamxError E_INVALID on a field that is not a route3 field"""
     f = _route3_field(field)
     nz, ny, nx = f.shape
-    s = (C.c_uint32 * 3)(*[int(v) for v in start])
-    n = C.c_uint32(0)
-    if capacity is None:
-        _check(lib().loamx_route3_trace(f.ctypes.data_as(C.c_void_p), nx, ny, nz, s, None, 0, C.byref(n)))
-        capacity = n.value
-    out = np.zeros((capacity, 3), np.uint32)
-    _check(lib().loamx_route3_trace(f.ctypes.data_as(C.c_void_p), nx, ny, nz, s, out.ctypes.data_as(C.c_void_p), C.c_uint32(capacity),
-                                    C.byref(n)))
-    return out[:min(n.value, capacity)], n.value
+    return _host_trace(lib().loamx_route3_trace, f, (nx, ny, nz), ((C.c_uint32 * 3)(*[int(v) for v in start]),), 3, capacity)
 
 
 def route3_points(cfg: DistConfig, leaf: float, route) -> np.ndarray:
@@ -2235,8 +2237,27 @@ class DenseMap:
 
     ROUTE_STATS = ("traversable", "reachable", "goals_used", "max_cost", "rounds", "tile_runs")
 
-    def _route_stats(self, st):
-        self.route_stats = dict(zip(self.ROUTE_STATS, (int(v) for v in st)))
+    def _route(self, dim, fn, head, mid, shape, goals, cfg, want_field, fields):
+        """the 2-D (dim 2) and 3-D (dim 3) route calls: fn(h, *head, cfg, goals, n_goals, *mid, field, stats); the stats are left in
+        route_stats or route3_stats"""
+        Config, names, attr = (RouteConfig, self.ROUTE_STATS, "route_stats") if dim == 2 else (Route3Config, ROUTE3_STATS, "route3_stats")
+        c = (Config() if cfg is None else cfg).copy(**fields).check()
+        t = _tuples(goals, dim)
+        field = np.zeros(shape, ROUTE_CELL) if want_field else None
+        st = (C.c_uint64 * 6)()
+        _check(fn(self.h, *head, C.byref(c), t.ctypes.data_as(C.c_void_p), C.c_uint32(len(t)), *mid,
+                  field.ctypes.data_as(C.c_void_p) if want_field else None, st))
+        setattr(self, attr, dict(zip(names, (int(v) for v in st))))
+        return field
+
+    def _route_trace(self, dim, fn, starts, capacity):
+        """route_trace (dim 2) and route3_trace (dim 3): fn(h, starts, n_starts, out, capacity, lengths) traces on the device"""
+        t = _tuples(starts, dim)
+        out = np.zeros((len(t), capacity, dim), np.uint32)
+        lengths = np.zeros(len(t), np.uint32)
+        _check(fn(self.h, t.ctypes.data_as(C.c_void_p), C.c_uint32(len(t)), out.ctypes.data_as(C.c_void_p), C.c_uint32(capacity),
+                  lengths.ctypes.data_as(C.c_void_p)))
+        return [out[i, :min(int(n), capacity)] for i, n in enumerate(lengths)], lengths
 
     def route(self, goals, cfg=None, grid=None, static=None, want_cells=False, want_field=True, **fields):
         """loamx_densemap_route: the navigation grid of a window (grid: a GridConfig, None: the defaults; static: a StaticRule)
@@ -2245,16 +2266,10 @@ class DenseMap:
         records, or (field, cells) with want_cells; want_field=False leaves the field on the device for route_trace() and returns
         None in its place.  The six stats of the call are left in route_stats."""
         g = (GridConfig() if grid is None else grid).copy().check()
-        c = (RouteConfig() if cfg is None else cfg).copy(**fields).check()
-        xz = _xz_pairs(goals)
-        field = np.zeros((g.nz, g.nx), ROUTE_CELL) if want_field else None
         cells = np.zeros((g.nz, g.nx), GRID_CELL) if want_cells else None
-        st = (C.c_uint64 * 6)()
-        _check(lib().loamx_densemap_route(self.h, C.byref(g), C.byref(static) if static is not None else None, C.byref(c),
-                                          xz.ctypes.data_as(C.c_void_p), C.c_uint32(len(xz)),
-                                          cells.ctypes.data_as(C.c_void_p) if want_cells else None,
-                                          field.ctypes.data_as(C.c_void_p) if want_field else None, st))
-        self._route_stats(st)
+        head = (C.byref(g), C.byref(static) if static is not None else None)
+        field = self._route(2, lib().loamx_densemap_route, head, (cells.ctypes.data_as(C.c_void_p) if want_cells else None,), (g.nz, g.nx),
+                            goals, cfg, want_field, fields)
         return (field, cells) if want_cells else field
 
     def route_cells(self, cells, goals, cfg=None, want_field=True, **fields):
@@ -2262,26 +2277,14 @@ class DenseMap:
         keep-out zones, or hand-made), uploaded to a buffer of the route's own"""
         a = _grid_cells(cells)
         assert a.ndim == 2, "cells must be an (nz, nx) array"
-        c = (RouteConfig() if cfg is None else cfg).copy(**fields).check()
-        xz = _xz_pairs(goals)
-        field = np.zeros(a.shape, ROUTE_CELL) if want_field else None
-        st = (C.c_uint64 * 6)()
-        _check(lib().loamx_densemap_route_cells(self.h, a.ctypes.data_as(C.c_void_p), C.c_uint32(a.shape[1]), C.c_uint32(a.shape[0]),
-                                                C.byref(c), xz.ctypes.data_as(C.c_void_p), C.c_uint32(len(xz)),
-                                                field.ctypes.data_as(C.c_void_p) if want_field else None, st))
-        self._route_stats(st)
-        return field
+        head = (a.ctypes.data_as(C.c_void_p), C.c_uint32(a.shape[1]), C.c_uint32(a.shape[0]))
+        return self._route(2, lib().loamx_densemap_route_cells, head, (), a.shape, goals, cfg, want_field, fields)
 
     def route_trace(self, starts, capacity):
         """loamx_densemap_route_trace: the routes from starts, a list of 1..4096 (rx, rz) pairs, over the field of the last route /
         route_cells call, traced on the device -> (a list of (min(n_i, capacity), 2) uint32 arrays of (rx, rz) pairs up to and
         including the goal cell, the full lengths n_i as uint32; 0: the start is outside the window or unreachable)"""
-        xz = _xz_pairs(starts)
-        out = np.zeros((len(xz), capacity, 2), np.uint32)
-        lengths = np.zeros(len(xz), np.uint32)
-        _check(lib().loamx_densemap_route_trace(self.h, xz.ctypes.data_as(C.c_void_p), C.c_uint32(len(xz)), out.ctypes.data_as(C.c_void_p),
-                                                C.c_uint32(capacity), lengths.ctypes.data_as(C.c_void_p)))
-        return [out[i, :min(int(n), capacity)] for i, n in enumerate(lengths)], lengths
+        return self._route_trace(2, lib().loamx_densemap_route_trace, starts, capacity)
 
     @property
     def route_active_rounds(self) -> int:
@@ -2292,16 +2295,6 @@ class DenseMap:
         """bench hook: the relaxation rounds launched per look at the counters (1..64)"""
         _check(lib().loamx_densemap_route_set_batch(self.h, C.c_uint32(batch)))
 
-    def _route3(self, fn, head, shape, goals, cfg, want_field, fields):
-        c = (Route3Config() if cfg is None else cfg).copy(**fields).check()
-        xyz = _xyz_triples(goals)
-        field = np.zeros(shape, ROUTE_CELL) if want_field else None
-        st = (C.c_uint64 * 6)()
-        _check(fn(self.h, *head, C.byref(c), xyz.ctypes.data_as(C.c_void_p), C.c_uint32(len(xyz)),
-                  field.ctypes.data_as(C.c_void_p) if want_field else None, st))
-        self.route3_stats = dict(zip(ROUTE3_STATS, (int(v) for v in st)))
-        return field
-
     def route3(self, goals, cfg=None, dist=None, static=None, want_field=True, **fields):
         """loamx_densemap_route3: the distance field of a 3-D window (dist: a DistConfig, None: the defaults; static: a StaticRule),
         which replaces the standing one and stays for dist_query(), and on its d2 where it lies on the device the cost-to-go field
@@ -2310,14 +2303,14 @@ class DenseMap:
         on the device for route3_trace() and returns None.  The six stats of the call are left in route3_stats."""
         g = (DistConfig() if dist is None else dist).copy().check()
         head = (C.byref(g), C.byref(static) if static is not None else None)
-        out = self._route3(lib().loamx_densemap_route3, head, (g.nz, g.ny, g.nx), goals, cfg, want_field, fields)
+        out = self._route(3, lib().loamx_densemap_route3, head, (), (g.nz, g.ny, g.nx), goals, cfg, want_field, fields)
         self._dist_shape = (g.nz, g.ny, g.nx)
         return out
 
     def route3_last(self, goals, cfg=None, want_field=True, **fields):
         """loamx_densemap_route3_last: the same on the distance field that stands (dist() or route3()); LoamxError E_INVALID when
         there is none"""
-        return self._route3(lib().loamx_densemap_route3_last, (), self._dist_shape or (1, 1, 1), goals, cfg, want_field, fields)
+        return self._route(3, lib().loamx_densemap_route3_last, (), (), self._dist_shape or (1, 1, 1), goals, cfg, want_field, fields)
 
     def route3_cells(self, d2, goals, cfg=None, want_field=True, **fields):
         """loamx_densemap_route3_cells: the same on an (nz, ny, nx) uint16 array of d2 values of the caller's (an earlier field
@@ -2326,19 +2319,14 @@ class DenseMap:
         a = np.ascontiguousarray(d2, np.uint16)
         assert a.ndim == 3, "d2 must be an (nz, ny, nx) array"
         head = (a.ctypes.data_as(C.c_void_p), C.c_uint32(a.shape[2]), C.c_uint32(a.shape[1]), C.c_uint32(a.shape[0]))
-        return self._route3(lib().loamx_densemap_route3_cells, head, a.shape, goals, cfg, want_field, fields)
+        return self._route(3, lib().loamx_densemap_route3_cells, head, (), a.shape, goals, cfg, want_field, fields)
 
     def route3_trace(self, starts, capacity):
         """loamx_densemap_route3_trace: the routes from starts, a list of 1..4096 (rx, ry, rz) triples, over the field of the last
         route3 / route3_last / route3_cells call, traced on the device -> (a list of (min(n_i, capacity), 3) uint32 arrays of
         triples up to and including the goal cell, the full lengths n_i as uint32; 0: the start is outside the window or
         unreachable)"""
-        xyz = _xyz_triples(starts)
-        out = np.zeros((len(xyz), capacity, 3), np.uint32)
-        lengths = np.zeros(len(xyz), np.uint32)
-        _check(lib().loamx_densemap_route3_trace(self.h, xyz.ctypes.data_as(C.c_void_p), C.c_uint32(len(xyz)), out.ctypes.data_as(C.c_void_p),
-                                                 C.c_uint32(capacity), lengths.ctypes.data_as(C.c_void_p)))
-        return [out[i, :min(int(n), capacity)] for i, n in enumerate(lengths)], lengths
+        return self._route_trace(3, lib().loamx_densemap_route3_trace, starts, capacity)
 
     @property
     def route3_active_rounds(self) -> int:
