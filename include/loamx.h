@@ -2138,6 +2138,77 @@ int loamx_place_get_descriptor(loamx_place* h, uint32_t id, float* desc, float* 
 int loamx_place_save(loamx_place* h, const char* path);
 int loamx_place_load(loamx_place* h, const char* path);
 
+/* Views described from a dense map (optional: a handle that never calls these runs the kernels it ran, allocates what it allocated and
+ * answers with the same bytes).  "Where am I in a loaded map?": a map that arrived by loamx_densemap_load or merge_file has no sweeps
+ * and therefore no place entries.  loamx_place_add_views describes the map from many virtual view points in one call, on the device:
+ * no ray, hit or voxel crosses to the host and no launch is spent per view point.  The chain is load -> loamx_densemap_grid ->
+ * loamx_grid_view_origins -> loamx_place_add_views -> loamx_place_query (the live sweep) -> loamx_place_view_pose ->
+ * loamx_densemap_align_many / align_pyramid.
+ *
+ * A view is a virtual sensor at an origin o in the map frame (LOAM axes).  Its entry is what loamx_place_add would store for a cloud
+ * V(o) described about o with the database's own R, S, ranges and height_offset: the same f32 arithmetic, the same sector table, the
+ * same ring key.  Two modes define V(o):
+ *   LOAMX_PLACE_VIEW_CAST (default): the caller gives n_rays offsets off[j] (f32 triples).  Ray j runs from o to end_j = o + off[j],
+ *     one f32 addition per component, and is cast exactly as loamx_densemap_raycast casts it: that section's walk, max_steps,
+ *     skip_steps, min_points, the optional rule, the end cell included.  V(o) is the positions x, y, z of the records with status HIT
+ *     or HIT_END (the bytes of loamx_ray_hit).  View o is loamx_densemap_raycast(ends, o) followed by loamx_place_add(hit positions,
+ *     o), byte for byte.  Several rays that hit the same voxel change nothing: a cell is a maximum.
+ *   LOAMX_PLACE_VIEW_VOXELS: V(o) is the exported positions (loamx_densemap_download, axes 0) of every voxel with n >= min_points that
+ *     the rule, if given, does not call dynamic: the map seen through walls.  A cheaper index for open terrain and a baseline for the
+ *     other mode.  offsets must be NULL and n_rays 0.
+ * An entry depends on the map's words, o, the offsets and the configuration alone: not on the order of origins or rays, on how the
+ * origins are split into calls, on the table's size or on the thread schedule.  Views are ordinary entries afterwards: query,
+ * query_entry, get_descriptor, save and load treat them as such.  Entry *first_id + i belongs to origins[3 i ..].
+ * stats: [0] entries added;  [1..5] the five counts of loamx_densemap_raycast (NOT_TRACED, MISS, HIT, HIT_END, cells looked up) summed
+ * over all views, integer sums;  in VOXELS mode [1] is the number of qualifying voxels and [2..5] are 0.
+ * Ordering: the call waits for the map's adds as download does, runs on the map's own stream behind every place add enqueued so far
+ * and blocks until the entries stand.  The table of entries grows in one step to the power of two that holds them.  An empty map is
+ * valid: n all-zero entries.  A probe overflow is reported by the map's next reading call, as for a ray cast.
+ * LOAMX_E_INVALID, with a message that names the argument, both handles unchanged: NULL pl, dm or origins;  a mode other than the
+ * two;  n outside 1..LOAMX_PLACE_VIEW_MAX_ORIGINS;  in CAST mode NULL offsets, n_rays outside 1..LOAMX_PLACE_VIEW_MAX_RAYS or
+ * max_steps outside 1..65536;  in VOXELS mode offsets given or n_rays != 0;  min_points == 0;  a rule with den == 0 or on a map
+ * without carving;  an origin or offset that is not finite;  handles on different devices.  LOAMX_E_CAPACITY, nothing added: max_entries
+ * would be passed.
+ *
+ * loamx_place_view_rays (host only): the offsets of a lidar of n_elevations rings with n_azimuth rays each, ray (e, a) at index
+ * e * n_azimuth + a: in double, az = 2 pi a / n_azimuth, el = (double)elevations[e] (radians), offset = ((float)(range * cos el *
+ * sin az), (float)(range * sin el), (float)(range * cos el * cos az)), the products from left to right: azimuth runs from +z towards
+ * +x, as the sectors do.  LOAMX_E_INVALID: NULL elevations or offsets;  n_azimuth or n_elevations 0;  their product above
+ * LOAMX_PLACE_VIEW_MAX_RAYS;  range not finite or not positive;  an elevation that is not finite.
+ * loamx_grid_view_origins (host only): where a vehicle can stand, as view origins.  The cells (rx, rz) of a grid with rx % stride == 0
+ * and rz % stride == 0 are looked at in ascending record order; a cell is kept when it is FREE with clear2 >= min_clear2, as
+ * x = (float)(((double)x0 + rx + 0.5) * (double)leaf * k), z alike (the expression of loamx_grid_route_points), y = elevation +
+ * sensor_height, one f32 addition.  *n is the full count; only the first `capacity` triples are written.  LOAMX_E_INVALID: NULL cells,
+ * cfg or n;  NULL origins with capacity > 0;  leaf not positive;  stride 0;  sensor_height not finite;  a configuration that fails
+ * loamx_densemap_grid_check.
+ * loamx_place_view_pose (host only): the start pose (row-major 3x4, map <- query frame) that a match (id, shift) of a query described
+ * about query_origin implies for the view at view_origin: in double, psi = shift * 2 pi / n_sectors, R = rot_y(psi) =
+ * [[cos psi, 0, sin psi], [0, 1, 0], [-sin psi, 0, cos psi]] — the yaw convention above: the query's frame has turned by +yaw_hint —
+ * and t = view_origin - R query_origin: t_x = v_x - (cos psi q_x + sin psi q_z), t_y = v_y - q_y, t_z = v_z - (cos psi q_z -
+ * sin psi q_x).  LOAMX_E_INVALID: NULL view_origin or pose;  n_sectors outside 4..128;  shift >= n_sectors;  an origin that is not finite. */
+#define LOAMX_PLACE_VIEW_CAST 0
+#define LOAMX_PLACE_VIEW_VOXELS 1
+#define LOAMX_PLACE_VIEW_MAX_ORIGINS 4096
+#define LOAMX_PLACE_VIEW_MAX_RAYS 65536
+typedef struct loamx_place_view_config {
+  uint32_t mode;                   /* LOAMX_PLACE_VIEW_CAST (default) or LOAMX_PLACE_VIEW_VOXELS */
+  uint32_t max_steps, skip_steps;  /* as loamx_densemap_raycast_config (defaults 4096, 0); CAST only */
+  uint32_t min_points;             /* a voxel with fewer points is not seen, >= 1 (default 1) */
+} loamx_place_view_config;
+void loamx_place_view_default_config(loamx_place_view_config* cfg);   /* host only */
+int loamx_place_view_rays(uint32_t n_azimuth, const float* elevations, uint32_t n_elevations, float range,
+                          float* offsets /* 3 * n_azimuth * n_elevations */);   /* host only */
+int loamx_place_add_views(loamx_place* pl, loamx_densemap* dm, const float* origins /* 3 * n */, uint32_t n,
+                          const float* offsets /* 3 * n_rays; NULL in VOXELS mode */, uint32_t n_rays,
+                          const loamx_place_view_config* cfg /* NULL: the defaults */,
+                          const loamx_densemap_static_rule* rule /* NULL: every voxel; else needs carving */,
+                          uint32_t* first_id /* may be NULL */, uint64_t stats[6] /* may be NULL */);
+int loamx_grid_view_origins(const loamx_grid_cell* cells, const loamx_densemap_grid_config* cfg, float leaf, uint32_t stride,
+                            uint32_t min_clear2, float sensor_height, float* origins /* 3 * capacity */, uint64_t capacity,
+                            uint64_t* n);   /* host only */
+int loamx_place_view_pose(const float view_origin[3], uint32_t shift, int n_sectors, const float query_origin[3] /* NULL: 0 */,
+                          double pose[12]);   /* host only */
+
 /* ------------------------------------------------------------------------------------------------------------
  * Pose graph (not in the reference, which never closes a loop): the run's poses optimised on the device, the link between
  * loamx_densemap_align_many / align_pyramid (a 6-DOF constraint between two sweeps) and loamx_densemap_rebuild (one rigid correction

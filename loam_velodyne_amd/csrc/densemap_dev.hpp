@@ -1,5 +1,5 @@
 // Dense map, device side: what the kernels of more than one file share (densemap.hip, densemap_rebuild.hip, densemap_raycast.hip,
-// densemap_merge.hip) — the arguments of the insert and of the carve, the claim of a slot, the wave-aggregated counters, the key rule
+// densemap_merge.hip, place_views.hip) — the arguments of the insert and of the carve, the claim of a slot, the wave-aggregated counters, the key rule
 // and the voxel walk of the rays.  dm_hash, dm_find and dm_dynamic are in densemap.hpp: the files that only read the table use them too.
 #pragma once
 #include "densemap.hpp"

@@ -130,6 +130,19 @@ class DenseMap {
   int raycast(const DenseSource& s, const loamx_densemap_raycast_config& c, const loamx_densemap_static_rule* rule, loamx_ray_hit* out,
               uint64_t capacity, uint64_t counts[5]);
 
+  // ---- place_views.hip: what a reader of the table outside the map is handed, as DmCaster::enqueue is: the table, the counters (a
+  // probe overflow goes to word 3), inv, the leaf, the voxel count and the map's own stream, every add waited for and the counters
+  // read (read_counters).  Read-only: valid until the next call that changes the map
+  struct TableView {
+    const DmTable* tab;
+    unsigned long long* ctr;
+    float inv;
+    double leaf;
+    uint64_t voxels;
+    hipStream_t stream;
+  };
+  TableView table_view();
+
   // ---- densemap_rebuild.hip: the sweep log and its replay (include/loamx.h, loamx_densemap_enable_history ... rebuild)
   void enable_history(const loamx_densemap_history_config& c);
   bool history() const { return history_; }

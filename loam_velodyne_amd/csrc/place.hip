@@ -7,16 +7,9 @@
 // k_pl_merge).  Every order used is total ((value, id) with distinct ids), and every sum has a fixed order: results are reproducible
 // to the bit and equal tests/place_model.py.
 #include "place.hpp"
-#include "cloud_stage.hpp"
 #include <algorithm>
 
 namespace loamx {
-
-struct PlParams {
-  float ox, oy, oz;
-  float min2, max2, hoff, ring_scale;
-  int R, S;
-};
 
 // f32 -> u32 with the same order (negative values too: a distance can round to a hair below zero)
 __device__ inline uint32_t pl_orderable(float f) {
@@ -38,24 +31,9 @@ __global__ __launch_bounds__(256) void k_pl_describe(const float4* __restrict__ 
   const uint32_t hi = n - lo < PL_DESCRIBE_SPAN ? n : lo + PL_DESCRIBE_SPAN;
   for (uint32_t i = lo + threadIdx.x; i < hi; i += 256) {
     const float4 p = pts[i];
-    if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) continue;
-    const float a = p.z - P.oz, b = p.x - P.ox;
-    const float r2 = a * a + b * b;
-    const float h = (p.y - P.oy) + P.hoff;
-    if (!(r2 >= P.min2 && r2 < P.max2 && h > 0.f)) continue;
-    int ring = (int)(sqrtf(r2) * P.ring_scale);
-    ring = ring < P.R - 1 ? ring : P.R - 1;
-    // the sector rule itself, at every boundary (S <= 128 broadcast reads of LDS per point): the smallest k with cross(k) >= 0 > cross(k + 1)
-    const float first = tab[0].x * b - tab[0].y * a;
-    float c0 = first;
-    int sec = -1;
-    for (int k = 0; k < P.S; k++) {
-      float c1 = first;
-      if (k + 1 < P.S) { const float2 t = tab[k + 1]; c1 = t.x * b - t.y * a; }
-      if (sec < 0 && c0 >= 0.f && c1 < 0.f) sec = k;
-      c0 = c1;
-    }
-    if (sec >= 0) atomicMax(&pl_grid[ring * P.S + sec], __float_as_uint(h));   // (h > 0: its bits order like the value)
+    float h = 0.f;
+    const int cell = pl_cell_of(P, tab, p.x, p.y, p.z, P.ox, P.oy, P.oz, h);   // (place.hpp: the use rule, the ring, the sector)
+    if (cell >= 0) atomicMax(&pl_grid[cell], __float_as_uint(h));   // (h > 0: its bits order like the value)
   }
   __syncthreads();
   for (int c = (int)threadIdx.x; c < RS; c += 256) {
@@ -221,297 +199,261 @@ __global__ __launch_bounds__(256) void k_pl_select(const unsigned long long* __r
   }
 }
 
-class PlaceDB {
- public:
-  explicit PlaceDB(const loamx_place_config& c) : cfg(c), R(c.n_rings), S(c.n_sectors), RS((size_t)c.n_rings * c.n_sectors) {
-    select_device(cfg.device);
-    lds_describe_ = sizeof(uint32_t) * ((RS + 1) & ~(size_t)1) + sizeof(float2) * S;
-    lds_distance_ = sizeof(float) * (2 * RS + 3 * (size_t)S + (size_t)S * S);
-    int lds_max = 0;
-    LX_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg.device));
-    LX_REQUIRE(lds_distance_ <= (size_t)lds_max, "n_rings x n_sectors needs more LDS per workgroup than this device has");
-    if (lds_distance_ > 48u * 1024u) {
-      (void)hipFuncSetAttribute((const void*)k_pl_distance, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_distance_);
-      (void)hipGetLastError();
-    }
-    LX_HIP(hipStreamCreateWithFlags(&own_, hipStreamNonBlocking));
-    LX_HIP(hipEventCreateWithFlags(&ev_last_, hipEventDisableTiming));
-    LX_HIP(hipEventCreateWithFlags(&ev_done_, hipEventDisableTiming));
-    std::vector<float> tab(2 * (size_t)S);
-    place_sector_table(S, tab.data());
-    d_table_.reserve(S);
-    LX_HIP(hipMemcpy(d_table_.p, tab.data(), sizeof(float2) * S, hipMemcpyHostToDevice));
-    q_desc_.reserve(RS);
-    q_key_.reserve(R);
-    h_res_.reserve(LOAMX_PLACE_MAX_RESULTS);
-    alloc_entries(cfg.initial_entries, desc_, keys_);
-    cap_ = cfg.initial_entries;
-    P_.min2 = cfg.min_range * cfg.min_range;
-    P_.max2 = cfg.max_range * cfg.max_range;
-    P_.hoff = cfg.height_offset;
-    P_.ring_scale = (float)R / cfg.max_range;
-    P_.R = R;
-    P_.S = S;
+PlaceDB::PlaceDB(const loamx_place_config& c) : cfg(c), R(c.n_rings), S(c.n_sectors), RS((size_t)c.n_rings * c.n_sectors) {
+  select_device(cfg.device);
+  lds_describe_ = sizeof(uint32_t) * ((RS + 1) & ~(size_t)1) + sizeof(float2) * S;
+  lds_distance_ = sizeof(float) * (2 * RS + 3 * (size_t)S + (size_t)S * S);
+  int lds_max = 0;
+  LX_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg.device));
+  LX_REQUIRE(lds_distance_ <= (size_t)lds_max, "n_rings x n_sectors needs more LDS per workgroup than this device has");
+  if (lds_distance_ > 48u * 1024u) {
+    (void)hipFuncSetAttribute((const void*)k_pl_distance, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_distance_);
+    (void)hipGetLastError();
   }
-  ~PlaceDB() {
-    (void)hipSetDevice(cfg.device);
-    (void)hipStreamSynchronize(own_);   // (behind every add: add())
-    free_graveyard();
+  LX_HIP(hipStreamCreateWithFlags(&own_, hipStreamNonBlocking));
+  LX_HIP(hipEventCreateWithFlags(&ev_last_, hipEventDisableTiming));
+  LX_HIP(hipEventCreateWithFlags(&ev_done_, hipEventDisableTiming));
+  std::vector<float> tab(2 * (size_t)S);
+  place_sector_table(S, tab.data());
+  d_table_.reserve(S);
+  LX_HIP(hipMemcpy(d_table_.p, tab.data(), sizeof(float2) * S, hipMemcpyHostToDevice));
+  q_desc_.reserve(RS);
+  q_key_.reserve(R);
+  h_res_.reserve(LOAMX_PLACE_MAX_RESULTS);
+  alloc_entries(cfg.initial_entries, desc_, keys_);
+  cap_ = cfg.initial_entries;
+  P_.min2 = cfg.min_range * cfg.min_range;
+  P_.max2 = cfg.max_range * cfg.max_range;
+  P_.hoff = cfg.height_offset;
+  P_.ring_scale = (float)R / cfg.max_range;
+  P_.R = R;
+  P_.S = S;
+}
+PlaceDB::~PlaceDB() {
+  (void)hipSetDevice(cfg.device);
+  (void)hipStreamSynchronize(own_);   // (behind every add: add())
+  free_graveyard();
+  (void)hipFree(desc_);
+  (void)hipFree(keys_);
+  (void)hipEventDestroy(ev_last_);
+  (void)hipEventDestroy(ev_done_);
+  (void)hipStreamDestroy(own_);
+  (void)hipGetLastError();   // (whatever the calls above were answered with is not the next caller's error)
+}
+
+DenseSource PlaceDB::host_source(const loamx_cloud* c, const float origin[3]) {
+  check_cloud(c, false);
+  check_origin(origin);
+  LX_HIP(hipSetDevice(cfg.device));
+  return stage_.source(c, origin, own_, cfg.device);
+}
+
+void PlaceDB::grow_to(uint32_t want, hipStream_t st) {
+  float *nd = nullptr, *nk = nullptr;
+  alloc_entries(want, nd, nk);
+  LX_HIP(hipMemcpyAsync(nd, desc_, sizeof(float) * RS * n_, hipMemcpyDeviceToDevice, st));
+  LX_HIP(hipMemcpyAsync(nk, keys_, sizeof(float) * R * n_, hipMemcpyDeviceToDevice, st));
+  graveyard_.push_back(desc_);
+  graveyard_.push_back(keys_);
+  desc_ = nd;
+  keys_ = nk;
+  cap_ = want;
+  growths++;
+}
+
+// The order is handed on to own_ at once: a source's stream may be destroyed before the database next waits, and an event that was
+// last recorded on a destroyed stream must not be waited for, queried or synchronised (the runtime looks at that stream and has
+// answered "event last recorded in a capturing stream").  Outside add() and add_views() ev_last_ is an event of own_.
+void PlaceDB::hand_on(hipStream_t st) {
+  LX_HIP(hipEventRecord(ev_last_, st));
+  if (st != own_) {
+    LX_HIP(hipStreamWaitEvent(own_, ev_last_, 0));
+    LX_HIP(hipEventRecord(ev_last_, own_));
+  }
+  added_ = true;
+}
+
+int PlaceDB::add(const DenseSource& s, uint32_t* id) {
+  LX_REQUIRE(s.device == cfg.device, "the place database and its source live on different devices");
+  if (!s.has_cloud) return LOAMX_SKIPPED;
+  LX_HIP(hipSetDevice(cfg.device));
+  if (full()) return LOAMX_E_CAPACITY;
+  hipStream_t st = s.stream;
+  order_behind(st);
+  check_origin(s.origin);
+  if (n_ + 1u > cap_) {   // growth by doubling: a device-to-device copy on the stream of this add, the old arrays freed later
+    LX_REQUIRE(cap_ <= (1u << 29), "place database: more entries than it can index");
+    grow_to(cap_ * 2u, st);
+  }
+  describe(s.points(), s.n, s.origin, desc_ + (size_t)n_ * RS, keys_ + (size_t)n_ * R, st);
+  hand_on(st);
+  if (id) *id = n_;
+  n_++;
+  return LOAMX_OK;
+}
+
+int PlaceDB::query_entry(uint32_t id, loamx_place_match* out, uint32_t n_results, uint32_t* n_found) {
+  LX_REQUIRE(id < n_, "no such entry");
+  LX_HIP(hipSetDevice(cfg.device));
+  order_behind(own_);
+  return search(desc_ + (size_t)id * RS, keys_ + (size_t)id * R, id, cfg.exclude_recent, out, n_results, n_found);
+}
+
+int PlaceDB::query_cloud(const loamx_cloud* c, const float origin[3], uint32_t exclude_recent, loamx_place_match* out, uint32_t n_results,
+                         uint32_t* n_found) {
+  const DenseSource s = host_source(c, origin);
+  order_behind(own_);
+  describe(s.points(), s.n, s.origin, q_desc_.p, q_key_.p, own_);
+  return search(q_desc_.p, q_key_.p, n_, exclude_recent, out, n_results, n_found);
+}
+
+void PlaceDB::get_descriptor(uint32_t id, float* desc, float* key) {
+  LX_REQUIRE(id < n_, "no such entry");
+  LX_HIP(hipSetDevice(cfg.device));
+  wait_adds();
+  if (desc) LX_HIP(hipMemcpyAsync(desc, desc_ + (size_t)id * RS, sizeof(float) * RS, hipMemcpyDeviceToHost, own_));
+  if (key) LX_HIP(hipMemcpyAsync(key, keys_ + (size_t)id * R, sizeof(float) * R, hipMemcpyDeviceToHost, own_));
+  LX_HIP(hipStreamSynchronize(own_));
+}
+
+void PlaceDB::reset() {
+  LX_HIP(hipSetDevice(cfg.device));
+  wait_adds();
+  LX_HIP(hipStreamSynchronize(own_));
+  n_ = 0;
+}
+
+void PlaceDB::save(const char* path) {
+  LX_HIP(hipSetDevice(cfg.device));
+  wait_adds();
+  std::vector<float> d(RS * n_), k((size_t)R * n_);
+  if (n_) {
+    LX_HIP(hipMemcpyAsync(d.data(), desc_, sizeof(float) * d.size(), hipMemcpyDeviceToHost, own_));
+    LX_HIP(hipMemcpyAsync(k.data(), keys_, sizeof(float) * k.size(), hipMemcpyDeviceToHost, own_));
+  }
+  LX_HIP(hipStreamSynchronize(own_));
+  FILE* f = fopen(path, "wb");
+  LX_REQUIRE(f, std::string("cannot open ") + path + " for writing");
+  const uint32_t hdr[5] = {PL_FILE_MAGIC, PL_FILE_VERSION, (uint32_t)R, (uint32_t)S, n_};
+  const float par[3] = {cfg.max_range, cfg.min_range, cfg.height_offset};
+  bool ok = fwrite(hdr, sizeof(hdr), 1, f) == 1 && fwrite(par, sizeof(par), 1, f) == 1;
+  ok = ok && (d.empty() || fwrite(d.data(), sizeof(float), d.size(), f) == d.size());
+  ok = ok && (k.empty() || fwrite(k.data(), sizeof(float), k.size(), f) == k.size());
+  const bool closed = fclose(f) == 0;
+  LX_REQUIRE(ok && closed, std::string("write to ") + path + " failed");
+}
+
+void PlaceDB::load(const char* path) {
+  FILE* f = fopen(path, "rb");
+  LX_REQUIRE(f, std::string("cannot open ") + path);
+  uint32_t hdr[5] = {0, 0, 0, 0, 0};
+  float par[3] = {0.f, 0.f, 0.f};
+  std::vector<float> d, k;
+  bool ok = fread(hdr, sizeof(hdr), 1, f) == 1 && fread(par, sizeof(par), 1, f) == 1;
+  const bool fits = ok && hdr[0] == PL_FILE_MAGIC && hdr[1] == PL_FILE_VERSION && hdr[2] == (uint32_t)R && hdr[3] == (uint32_t)S &&
+                    par[0] == cfg.max_range && par[1] == cfg.min_range && par[2] == cfg.height_offset && hdr[4] <= (1u << 30) &&
+                    (!cfg.max_entries || hdr[4] <= cfg.max_entries);
+  if (fits) {
+    d.resize(RS * hdr[4]);
+    k.resize((size_t)R * hdr[4]);
+    ok = (d.empty() || fread(d.data(), sizeof(float), d.size(), f) == d.size()) && (k.empty() || fread(k.data(), sizeof(float), k.size(), f) == k.size());
+  }
+  fclose(f);
+  LX_REQUIRE(ok, std::string(path) + " is not a complete place database file");
+  LX_REQUIRE(fits, std::string(path) + ": not a place database of this handle's n_rings, n_sectors, ranges and height_offset");
+  LX_HIP(hipSetDevice(cfg.device));
+  wait_adds();
+  LX_HIP(hipStreamSynchronize(own_));
+  const uint32_t n = hdr[4];
+  if (n > cap_) {
+    uint32_t want = cap_;
+    while (want < n) want *= 2;
+    float *nd = nullptr, *nk = nullptr;
+    alloc_entries(want, nd, nk);
     (void)hipFree(desc_);
     (void)hipFree(keys_);
-    (void)hipEventDestroy(ev_last_);
-    (void)hipEventDestroy(ev_done_);
-    (void)hipStreamDestroy(own_);
-    (void)hipGetLastError();   // (whatever the calls above were answered with is not the next caller's error)
+    desc_ = nd;
+    keys_ = nk;
+    cap_ = want;
   }
-  loamx_place_config cfg;
-  const int R, S;
-  const size_t RS;
-
-  uint32_t size() const { return n_; }
-
-  // a cloud from the host about a finite origin as a source on own_, up through the database's stager
-  DenseSource host_source(const loamx_cloud* c, const float origin[3]) {
-    check_cloud(c, false);
-    check_origin(origin);
-    LX_HIP(hipSetDevice(cfg.device));
-    return stage_.source(c, origin, own_, cfg.device);
+  if (n) {
+    LX_HIP(hipMemcpy(desc_, d.data(), sizeof(float) * d.size(), hipMemcpyHostToDevice));
+    LX_HIP(hipMemcpy(keys_, k.data(), sizeof(float) * k.size(), hipMemcpyHostToDevice));
   }
+  n_ = n;
+}
 
-  // enqueued on the source's stream, behind every add so far: own_ for a cloud from the host, the stream that wrote a registered cloud
-  // (kept: a non-finite origin from the host is refused in host_source, before the database is found full; a source's only here, after)
-  int add(const DenseSource& s, uint32_t* id) {
-    LX_REQUIRE(s.device == cfg.device, "the place database and its source live on different devices");
-    if (!s.has_cloud) return LOAMX_SKIPPED;
-    LX_HIP(hipSetDevice(cfg.device));
-    if (full()) return LOAMX_E_CAPACITY;
-    hipStream_t st = s.stream;
-    order_behind(st);
-    check_origin(s.origin);
-    if (n_ + 1u > cap_) {   // growth by doubling: a device-to-device copy on the stream of this add, the old arrays freed later
-      LX_REQUIRE(cap_ <= (1u << 29), "place database: more entries than it can index");
-      const uint32_t want = cap_ * 2u;
-      float *nd = nullptr, *nk = nullptr;
-      alloc_entries(want, nd, nk);
-      LX_HIP(hipMemcpyAsync(nd, desc_, sizeof(float) * RS * n_, hipMemcpyDeviceToDevice, st));
-      LX_HIP(hipMemcpyAsync(nk, keys_, sizeof(float) * R * n_, hipMemcpyDeviceToDevice, st));
-      graveyard_.push_back(desc_);
-      graveyard_.push_back(keys_);
-      desc_ = nd;
-      keys_ = nk;
-      cap_ = want;
-      growths++;
+void PlaceDB::alloc_entries(uint32_t cap, float*& d, float*& k) {
+  LX_HIP(hipMalloc((void**)&d, sizeof(float) * RS * cap));
+  LX_HIP(hipMalloc((void**)&k, sizeof(float) * R * cap));
+}
+void PlaceDB::free_graveyard() {
+  for (void* p : graveyard_) (void)hipFree(p);
+  graveyard_.clear();
+}
+void PlaceDB::wait_adds() {
+  if (added_) LX_HIP(hipEventSynchronize(ev_last_));
+  stage_.settle();
+  free_graveyard();
+}
+void PlaceDB::describe(const float4* pts, uint32_t n, const float origin[3], float* cells, float* key, hipStream_t st) {
+  hipLaunchKernelGGL(k_pl_clear, dim3((uint32_t)((RS + 255) / 256)), dim3(256), 0, st, (uint32_t*)cells, (uint32_t)RS);
+  if (n) {
+    PlParams P = P_;
+    P.ox = origin[0]; P.oy = origin[1]; P.oz = origin[2];
+    hipLaunchKernelGGL(k_pl_describe, dim3((n + PL_DESCRIBE_SPAN - 1) / PL_DESCRIBE_SPAN), dim3(256), lds_describe_, st, pts, n, P, d_table_.p,
+                       (uint32_t*)cells);
+  }
+  hipLaunchKernelGGL(k_pl_keys, dim3(1), dim3(64), 0, st, cells, key, R, S);
+  LX_HIP(hipGetLastError());
+}
+int PlaceDB::search(const float* Q, const float* rq, uint32_t q, uint32_t exclude_recent, loamx_place_match* out, uint32_t n_results,
+                    uint32_t* n_found) {
+  LX_REQUIRE(n_results >= 1 && n_results <= LOAMX_PLACE_MAX_RESULTS, "n_results must be in [1, LOAMX_PLACE_MAX_RESULTS]");
+  const uint32_t limit = q > exclude_recent ? std::min(q - exclude_recent, n_) : 0u;   // the candidates are the ids [0, limit)
+  uint32_t found = 0;
+  if (limit) {
+    const uint32_t K = (uint32_t)cfg.n_candidates;
+    const bool preselect = K > 0 && limit > K;
+    const uint32_t ncand = preselect ? K : limit;
+    const uint32_t nwg = (limit + PL_CHUNK - 1) / PL_CHUNK;
+    found = std::min(n_results, ncand);
+    dist_.reserve(n_);
+    rkd_.reserve(n_);
+    shift_.reserve(n_);
+    dkey_.reserve(ncand);
+    part_.reserve((size_t)nwg * std::max(K, (uint32_t)LOAMX_PLACE_MAX_RESULTS));
+    const uint32_t* cand = nullptr;
+    if (preselect) {
+      cand_.reserve(PL_MAX_CANDIDATES);
+      hipLaunchKernelGGL(k_pl_ringkey_topk, dim3(nwg), dim3(256), 0, own_, keys_, rq, limit, R, K, part_.p);
+      hipLaunchKernelGGL(k_pl_merge, dim3(1), dim3(256), 0, own_, part_.p, nwg * K, K, cand_.p);
+      cand = cand_.p;
     }
-    describe(s.points(), s.n, s.origin, desc_ + (size_t)n_ * RS, keys_ + (size_t)n_ * R, st);
-    // The order is handed on to own_ at once: a source's stream may be destroyed before the database next waits, and an event that was
-    // last recorded on a destroyed stream must not be waited for, queried or synchronised (the runtime looks at that stream and has
-    // answered "event last recorded in a capturing stream").  Outside this function ev_last_ is an event of own_.
-    LX_HIP(hipEventRecord(ev_last_, st));
-    if (st != own_) {
-      LX_HIP(hipStreamWaitEvent(own_, ev_last_, 0));
-      LX_HIP(hipEventRecord(ev_last_, own_));
+    hipLaunchKernelGGL(k_pl_distance, dim3(ncand), dim3(256), lds_distance_, own_, Q, rq, desc_, keys_, cand, R, S, dkey_.p, dist_.p, shift_.p,
+                       rkd_.p);
+    void* d_res = nullptr;
+    LX_HIP(hipHostGetDevicePointer(&d_res, h_res_.p, 0));
+    if (ncand > PL_CHUNK) {
+      const uint32_t nwg2 = (ncand + PL_CHUNK - 1) / PL_CHUNK;
+      hipLaunchKernelGGL(k_pl_part, dim3(nwg2), dim3(256), 0, own_, dkey_.p, ncand, found, part_.p);
+      hipLaunchKernelGGL(k_pl_select, dim3(1), dim3(256), 0, own_, part_.p, nwg2 * found, found, dist_.p, shift_.p, rkd_.p, (uint4*)d_res);
+    } else {
+      hipLaunchKernelGGL(k_pl_select, dim3(1), dim3(256), 0, own_, dkey_.p, ncand, found, dist_.p, shift_.p, rkd_.p, (uint4*)d_res);
     }
-    added_ = true;
-    if (id) *id = n_;
-    n_++;
-    return LOAMX_OK;
-  }
-
-  int query_entry(uint32_t id, loamx_place_match* out, uint32_t n_results, uint32_t* n_found) {
-    LX_REQUIRE(id < n_, "no such entry");
-    LX_HIP(hipSetDevice(cfg.device));
-    order_behind(own_);
-    return search(desc_ + (size_t)id * RS, keys_ + (size_t)id * R, id, cfg.exclude_recent, out, n_results, n_found);
-  }
-
-  int query_cloud(const loamx_cloud* c, const float origin[3], uint32_t exclude_recent, loamx_place_match* out, uint32_t n_results,
-                  uint32_t* n_found) {
-    const DenseSource s = host_source(c, origin);
-    order_behind(own_);
-    describe(s.points(), s.n, s.origin, q_desc_.p, q_key_.p, own_);
-    return search(q_desc_.p, q_key_.p, n_, exclude_recent, out, n_results, n_found);
-  }
-
-  void get_descriptor(uint32_t id, float* desc, float* key) {
-    LX_REQUIRE(id < n_, "no such entry");
-    LX_HIP(hipSetDevice(cfg.device));
-    wait_adds();
-    if (desc) LX_HIP(hipMemcpyAsync(desc, desc_ + (size_t)id * RS, sizeof(float) * RS, hipMemcpyDeviceToHost, own_));
-    if (key) LX_HIP(hipMemcpyAsync(key, keys_ + (size_t)id * R, sizeof(float) * R, hipMemcpyDeviceToHost, own_));
-    LX_HIP(hipStreamSynchronize(own_));
-  }
-
-  void reset() {
-    LX_HIP(hipSetDevice(cfg.device));
-    wait_adds();
-    LX_HIP(hipStreamSynchronize(own_));
-    n_ = 0;
-  }
-
-  void save(const char* path) {
-    LX_HIP(hipSetDevice(cfg.device));
-    wait_adds();
-    std::vector<float> d(RS * n_), k((size_t)R * n_);
-    if (n_) {
-      LX_HIP(hipMemcpyAsync(d.data(), desc_, sizeof(float) * d.size(), hipMemcpyDeviceToHost, own_));
-      LX_HIP(hipMemcpyAsync(k.data(), keys_, sizeof(float) * k.size(), hipMemcpyDeviceToHost, own_));
-    }
-    LX_HIP(hipStreamSynchronize(own_));
-    FILE* f = fopen(path, "wb");
-    LX_REQUIRE(f, std::string("cannot open ") + path + " for writing");
-    const uint32_t hdr[5] = {PL_FILE_MAGIC, PL_FILE_VERSION, (uint32_t)R, (uint32_t)S, n_};
-    const float par[3] = {cfg.max_range, cfg.min_range, cfg.height_offset};
-    bool ok = fwrite(hdr, sizeof(hdr), 1, f) == 1 && fwrite(par, sizeof(par), 1, f) == 1;
-    ok = ok && (d.empty() || fwrite(d.data(), sizeof(float), d.size(), f) == d.size());
-    ok = ok && (k.empty() || fwrite(k.data(), sizeof(float), k.size(), f) == k.size());
-    const bool closed = fclose(f) == 0;
-    LX_REQUIRE(ok && closed, std::string("write to ") + path + " failed");
-  }
-
-  void load(const char* path) {
-    FILE* f = fopen(path, "rb");
-    LX_REQUIRE(f, std::string("cannot open ") + path);
-    uint32_t hdr[5] = {0, 0, 0, 0, 0};
-    float par[3] = {0.f, 0.f, 0.f};
-    std::vector<float> d, k;
-    bool ok = fread(hdr, sizeof(hdr), 1, f) == 1 && fread(par, sizeof(par), 1, f) == 1;
-    const bool fits = ok && hdr[0] == PL_FILE_MAGIC && hdr[1] == PL_FILE_VERSION && hdr[2] == (uint32_t)R && hdr[3] == (uint32_t)S &&
-                      par[0] == cfg.max_range && par[1] == cfg.min_range && par[2] == cfg.height_offset && hdr[4] <= (1u << 30) &&
-                      (!cfg.max_entries || hdr[4] <= cfg.max_entries);
-    if (fits) {
-      d.resize(RS * hdr[4]);
-      k.resize((size_t)R * hdr[4]);
-      ok = (d.empty() || fread(d.data(), sizeof(float), d.size(), f) == d.size()) && (k.empty() || fread(k.data(), sizeof(float), k.size(), f) == k.size());
-    }
-    fclose(f);
-    LX_REQUIRE(ok, std::string(path) + " is not a complete place database file");
-    LX_REQUIRE(fits, std::string(path) + ": not a place database of this handle's n_rings, n_sectors, ranges and height_offset");
-    LX_HIP(hipSetDevice(cfg.device));
-    wait_adds();
-    LX_HIP(hipStreamSynchronize(own_));
-    const uint32_t n = hdr[4];
-    if (n > cap_) {
-      uint32_t want = cap_;
-      while (want < n) want *= 2;
-      float *nd = nullptr, *nk = nullptr;
-      alloc_entries(want, nd, nk);
-      (void)hipFree(desc_);
-      (void)hipFree(keys_);
-      desc_ = nd;
-      keys_ = nk;
-      cap_ = want;
-    }
-    if (n) {
-      LX_HIP(hipMemcpy(desc_, d.data(), sizeof(float) * d.size(), hipMemcpyHostToDevice));
-      LX_HIP(hipMemcpy(keys_, k.data(), sizeof(float) * k.size(), hipMemcpyHostToDevice));
-    }
-    n_ = n;
-  }
-
-  uint64_t growths = 0;
-
- private:
-  hipStream_t own_ = nullptr;      // host-fed adds, queries, exports
-  bool added_ = false;             // ev_last_ has been recorded: on own_, behind every add enqueued so far (add())
-  hipEvent_t ev_last_ = nullptr, ev_done_ = nullptr;
-  float* desc_ = nullptr;          // cap_ x R*S
-  float* keys_ = nullptr;          // cap_ x R
-  uint32_t cap_ = 0, n_ = 0;
-  PlParams P_{};
-  size_t lds_describe_ = 0, lds_distance_ = 0;
-  DevBuf<float2> d_table_;
-  DevBuf<float> q_desc_, q_key_, dist_, rkd_;
-  DevBuf<uint32_t> shift_, cand_;
-  DevBuf<unsigned long long> dkey_, part_;
-  PinBuf<loamx_place_match> h_res_;
-  DmCloudStage stage_;             // add()'s and query_cloud()'s clouds from the host
-  std::vector<void*> graveyard_;   // arrays replaced by a growth: freed at the next point where the host waits anyway
-
-  static void check_origin(const float o[3]) {
-    LX_REQUIRE(std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]), "origin must be finite");
-  }
-  void alloc_entries(uint32_t cap, float*& d, float*& k) {
-    LX_HIP(hipMalloc((void**)&d, sizeof(float) * RS * cap));
-    LX_HIP(hipMalloc((void**)&k, sizeof(float) * R * cap));
-  }
-  void free_graveyard() {
-    for (void* p : graveyard_) (void)hipFree(p);
-    graveyard_.clear();
-  }
-  bool full() const { return cfg.max_entries && n_ + 1u > cfg.max_entries; }
-  // st runs behind every add enqueued so far (on whichever stream)
-  void order_behind(hipStream_t st) {
-    if (added_ && st != own_) LX_HIP(hipStreamWaitEvent(st, ev_last_, 0));
-  }
-  void wait_adds() {
-    if (added_) LX_HIP(hipEventSynchronize(ev_last_));
-    stage_.settle();
-    free_graveyard();
-  }
-  void describe(const float4* pts, uint32_t n, const float origin[3], float* cells, float* key, hipStream_t st) {
-    hipLaunchKernelGGL(k_pl_clear, dim3((uint32_t)((RS + 255) / 256)), dim3(256), 0, st, (uint32_t*)cells, (uint32_t)RS);
-    if (n) {
-      PlParams P = P_;
-      P.ox = origin[0]; P.oy = origin[1]; P.oz = origin[2];
-      hipLaunchKernelGGL(k_pl_describe, dim3((n + PL_DESCRIBE_SPAN - 1) / PL_DESCRIBE_SPAN), dim3(256), lds_describe_, st, pts, n, P, d_table_.p,
-                         (uint32_t*)cells);
-    }
-    hipLaunchKernelGGL(k_pl_keys, dim3(1), dim3(64), 0, st, cells, key, R, S);
     LX_HIP(hipGetLastError());
   }
-  // on own_, which the caller has ordered behind every add
-  int search(const float* Q, const float* rq, uint32_t q, uint32_t exclude_recent, loamx_place_match* out, uint32_t n_results, uint32_t* n_found) {
-    LX_REQUIRE(n_results >= 1 && n_results <= LOAMX_PLACE_MAX_RESULTS, "n_results must be in [1, LOAMX_PLACE_MAX_RESULTS]");
-    const uint32_t limit = q > exclude_recent ? std::min(q - exclude_recent, n_) : 0u;   // the candidates are the ids [0, limit)
-    uint32_t found = 0;
-    if (limit) {
-      const uint32_t K = (uint32_t)cfg.n_candidates;
-      const bool preselect = K > 0 && limit > K;
-      const uint32_t ncand = preselect ? K : limit;
-      const uint32_t nwg = (limit + PL_CHUNK - 1) / PL_CHUNK;
-      found = std::min(n_results, ncand);
-      dist_.reserve(n_);
-      rkd_.reserve(n_);
-      shift_.reserve(n_);
-      dkey_.reserve(ncand);
-      part_.reserve((size_t)nwg * std::max(K, (uint32_t)LOAMX_PLACE_MAX_RESULTS));
-      const uint32_t* cand = nullptr;
-      if (preselect) {
-        cand_.reserve(PL_MAX_CANDIDATES);
-        hipLaunchKernelGGL(k_pl_ringkey_topk, dim3(nwg), dim3(256), 0, own_, keys_, rq, limit, R, K, part_.p);
-        hipLaunchKernelGGL(k_pl_merge, dim3(1), dim3(256), 0, own_, part_.p, nwg * K, K, cand_.p);
-        cand = cand_.p;
-      }
-      hipLaunchKernelGGL(k_pl_distance, dim3(ncand), dim3(256), lds_distance_, own_, Q, rq, desc_, keys_, cand, R, S, dkey_.p, dist_.p, shift_.p,
-                         rkd_.p);
-      void* d_res = nullptr;
-      LX_HIP(hipHostGetDevicePointer(&d_res, h_res_.p, 0));
-      if (ncand > PL_CHUNK) {
-        const uint32_t nwg2 = (ncand + PL_CHUNK - 1) / PL_CHUNK;
-        hipLaunchKernelGGL(k_pl_part, dim3(nwg2), dim3(256), 0, own_, dkey_.p, ncand, found, part_.p);
-        hipLaunchKernelGGL(k_pl_select, dim3(1), dim3(256), 0, own_, part_.p, nwg2 * found, found, dist_.p, shift_.p, rkd_.p, (uint4*)d_res);
-      } else {
-        hipLaunchKernelGGL(k_pl_select, dim3(1), dim3(256), 0, own_, dkey_.p, ncand, found, dist_.p, shift_.p, rkd_.p, (uint4*)d_res);
-      }
-      LX_HIP(hipGetLastError());
-    }
-    LX_HIP(hipEventRecord(ev_done_, own_));
-    wait_event(ev_done_);
-    free_graveyard();   // (own_ ran behind every add: nothing reads the replaced arrays any more)
-    for (uint32_t i = 0; i < found; i++) out[i] = h_res_.p[i];
-    if (n_found) *n_found = found;
-    return LOAMX_OK;
-  }
-};
+  LX_HIP(hipEventRecord(ev_done_, own_));
+  wait_event(ev_done_);
+  free_graveyard();   // (own_ ran behind every add: nothing reads the replaced arrays any more)
+  for (uint32_t i = 0; i < found; i++) out[i] = h_res_.p[i];
+  if (n_found) *n_found = found;
+  return LOAMX_OK;
+}
 
 }  // namespace loamx
 
 using namespace loamx;
-
-struct loamx_place {
-  PlaceDB d;
-  explicit loamx_place(const loamx_place_config& c) : d(c) {}
-};
 
 extern "C" {
 

@@ -2643,10 +2643,66 @@ def place_sector_table(n_sectors: int) -> np.ndarray:
     return out
 
 
+class PlaceViewConfig(C.Structure):
+    """loamx_place_view_config: how loamx_place_add_views sees the map from a view origin; the defaults are PLACE_VIEW_CAST, 4096, 0, 1"""
+    _fields_ = [("mode", C.c_uint32), ("max_steps", C.c_uint32), ("skip_steps", C.c_uint32), ("min_points", C.c_uint32)]
+
+
+PLACE_VIEW_CAST, PLACE_VIEW_VOXELS = 0, 1                                        # loamx_place_view_config.mode
+PLACE_VIEW_MAX_ORIGINS, PLACE_VIEW_MAX_RAYS = 4096, 65536
+PLACE_VIEW_STATS = ("entries", "not_traced", "miss", "hit", "hit_end", "cells")   # stats[6] of loamx_place_add_views (CAST mode)
+
+
+def _triples(a, what) -> np.ndarray:
+    t = np.ascontiguousarray(a, np.float32)
+    assert t.ndim == 2 and t.shape[1] == 3, what + " must be (n, 3)"
+    return t
+
+
+def view_rays(n_azimuth: int, elevations, range_m: float) -> np.ndarray:
+    """loamx_place_view_rays (host only): (len(elevations) * n_azimuth, 3) float32 offsets of a lidar's rays, ring-major, each range_m
+    long; elevations in radians, azimuth 2 pi a / n_azimuth from +z towards +x.  The offsets argument of PlaceDB.add_views."""
+    el = np.ascontiguousarray(elevations, np.float32).reshape(-1)
+    out = np.zeros((max(len(el) * int(n_azimuth), 1), 3), np.float32)
+    _check(lib().loamx_place_view_rays(C.c_uint32(n_azimuth), el.ctypes.data_as(C.c_void_p), C.c_uint32(len(el)), C.c_float(range_m),
+                                       out.ctypes.data_as(C.c_void_p)))
+    return out[:len(el) * int(n_azimuth)]
+
+
+def grid_view_origins(cells, cfg: GridConfig, leaf: float, stride=1, min_clear2=1, sensor_height=0.0, capacity=None) -> np.ndarray:
+    """loamx_grid_view_origins (host only): (n, 3) float32 view origins, one per FREE cell (rx, rz) of a navigation grid with
+    rx % stride == rz % stride == 0 and clear2 >= min_clear2, in ascending record order: the cell's centre in x and z, its elevation
+    + sensor_height in y.  capacity None: all of them; otherwise the first `capacity`."""
+    a = _grid_cells(cells)
+    assert a.size == cfg.nx * cfg.nz, "cells does not have the configuration's nx * nz records"
+    n = C.c_uint64(0)
+    args = (a.ctypes.data_as(C.c_void_p), C.byref(cfg), C.c_float(leaf), C.c_uint32(stride), C.c_uint32(min_clear2), C.c_float(sensor_height))
+    if capacity is None:
+        _check(lib().loamx_grid_view_origins(*args, None, C.c_uint64(0), C.byref(n)))
+        capacity = n.value
+    out = np.zeros((max(int(capacity), 1), 3), np.float32)
+    _check(lib().loamx_grid_view_origins(*args, out.ctypes.data_as(C.c_void_p), C.c_uint64(capacity), C.byref(n)))
+    return out[:min(int(capacity), n.value)]
+
+
+def view_pose(view_origin, shift: int, n_sectors: int, query_origin=None) -> np.ndarray:
+    """loamx_place_view_pose (host only): the (3, 4) float64 start pose, map <- query frame, that the match (id, shift) of a query
+    described about query_origin (None: 0) implies for the view at view_origin: R = rot_y(shift * 2 pi / n_sectors),
+    t = view_origin - R query_origin.  The pose argument of DenseMap.align_many / align_pyramid."""
+    v = np.ascontiguousarray(view_origin, np.float32)
+    q = None if query_origin is None else np.ascontiguousarray(query_origin, np.float32)
+    assert v.shape == (3,) and (q is None or q.shape == (3,))
+    out = np.zeros(12, np.float64)
+    _check(lib().loamx_place_view_pose(v.ctypes.data_as(C.c_void_p), C.c_uint32(shift), C.c_int(n_sectors),
+                                       q.ctypes.data_as(C.c_void_p) if q is not None else None, out.ctypes.data_as(C.c_void_p)))
+    return out.reshape(3, 4)
+
+
 class PlaceDB:
     """loamx_place_*: scan-context descriptors of sweeps in device memory and the search for earlier entries that look like a query.
-    add: a cloud from the host; add_from: a LaserMapping's last registered cloud; add_from_pipeline: a Pipeline's.  A match is
-    (id, shift, distance, ring_key_distance); yaw_hint(shift) = shift * 2 pi / n_sectors (include/loamx.h has the convention)."""
+    add: a cloud from the host; add_from: a LaserMapping's last registered cloud; add_from_pipeline: a Pipeline's; add_views: a
+    DenseMap seen from many view origins.  A match is (id, shift, distance, ring_key_distance); yaw_hint(shift) = shift * 2 pi /
+    n_sectors (include/loamx.h has the convention)."""
 
     def __init__(self, n_rings=20, n_sectors=60, max_range=80.0, min_range=0.0, height_offset=2.0, n_candidates=0, exclude_recent=50,
                  max_entries=0, initial_entries=1024, device=0):
@@ -2698,6 +2754,26 @@ class PlaceDB:
     def add_from_pipeline(self, pipeline, slot: int):
         """the registered cloud of the slot-th stream registered in pipeline's last step: the new id, or None when it registered none"""
         return self._add(lib().loamx_place_add_from_pipeline, pipeline.h, slot)
+
+    def add_views(self, densemap, origins, offsets=None, mode=None, max_steps=4096, skip_steps=0, min_points=1, static=None):
+        """loamx_place_add_views: one entry per view origin ((n, 3), map frame), described from densemap on the device.  With offsets
+        ((n_rays, 3), e.g. view_rays()) a view is what the rays origin -> origin + offset hit (PLACE_VIEW_CAST; max_steps, skip_steps
+        and min_points as DenseMap.raycast takes them); without, every voxel of the map (PLACE_VIEW_VOXELS).  mode None: by whether
+        offsets are given.  static (a StaticRule; needs carving): without the voxels the rule calls dynamic.  Returns (first_id,
+        stats): entry first_id + i belongs to origins[i]; stats is a dict in the order of PLACE_VIEW_STATS (in VOXELS mode
+        "not_traced" holds the number of qualifying voxels).  Blocks.  LoamxError E_CAPACITY when max_entries would be passed."""
+        o = _triples(origins, "origins")
+        f = None if offsets is None else _triples(offsets, "offsets")
+        if mode is None:
+            mode = PLACE_VIEW_VOXELS if f is None else PLACE_VIEW_CAST
+        k = _cfg(PlaceViewConfig, "loamx_place_view_default_config", mode=mode, max_steps=max_steps, skip_steps=skip_steps,
+                 min_points=min_points)
+        first, stats = C.c_uint32(0), np.zeros(6, np.uint64)
+        _check(lib().loamx_place_add_views(self.h, densemap.h, o.ctypes.data_as(C.c_void_p), C.c_uint32(len(o)),
+                                           f.ctypes.data_as(C.c_void_p) if f is not None else None, C.c_uint32(0 if f is None else len(f)),
+                                           C.byref(k), C.byref(static) if static is not None else None, C.byref(first),
+                                           stats.ctypes.data_as(C.c_void_p)))
+        return int(first.value), dict(zip(PLACE_VIEW_STATS, (int(v) for v in stats)))
 
     @staticmethod
     def _matches(m, n):
